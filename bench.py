@@ -5,10 +5,16 @@ One "step" = one pass of the hot path over one batch of synthetic input: a 1920x
 of 10 closed GOPs (1 I + 8 P frames each, VECTOR_LEVEL=3, Q_LEVEL=2, XL=YL=7) resident in HBM,
 encoded to the final MPEG-2 elementary stream in HBM through the C-ABI.  The timed loop keeps two such
 sequences in flight on two encoder handles (m2v_encode_resident_begin / _end): the stream assembly of one
-runs beside the first macroblock kernels of the next.  `one_synchronous_call_per_step` in the line is
+runs beside the first macroblock kernels of the next.  `one_synchronous_call_per_step` in the --full line is
 the same K steps as one blocking m2v_encode_resident call after the other (what rounds 1 and 2 timed).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode sequences|strips] [--config c3|c2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode sequences|strips] [--config c3|c2] [--full] [--dump-outputs DIR]
+
+A plain run (no --full) does what the headline needs and no more: set up, warm up, time the K steps, print the line (metric, value,
+unit, ms_per_step, ...).  --full adds everything else the benchmark measures or checks: the other submission form, the sustained loop, the
+profiled pass (per-kernel times, roofline), the whole-stream check against the oracle, the CPU baselines, the RTL probe, the HBM copy
+rate, end_to_end and, for N > 1, the per-rank oracle check and the strips legs.  --dump-outputs DIR writes the stream of the last
+timed step as .npy files (dump_outputs()); the clip is seeded, so the same arguments give the same inputs on every run.
 
 N > 1: one rank per GPU.  Either the caller starts the ranks (torch.distributed.run: RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_* in the environment), or - WORLD_SIZE unset - this process starts them itself: `python bench.py --gpus 8` alone is an
@@ -17,7 +23,7 @@ Every rank encodes its own clip (BASELINE config c4: independent sequences, no d
 --mode strips is config c5 (ONE sequence, macroblock-row strips, RCCL halo exchange or peer stores) -> "scaling": "strong".
 Rank 0 prints ONE JSON line; "n_gpus" is the world size the process group reports ("ranks_seen").
 
-What an unattended `bench.py --gpus N` (N > 1) runs, in order (bench_launch.py): the c4 measurement on N ranks; then, its line in hand
+What an unattended `bench.py --gpus N --full` (N > 1) runs, in order (bench_launch.py): the c4 measurement on N ranks; then, its line in hand
 and not yet printed, config c5 twice as N FRESH child processes each under a hard wall-clock bound - halo through RCCL, then the peer
 transport - whose results (or a stated error: timeout, exit code) become `strips: {rccl, peer}` of the c4 line; then the line, once.
 
@@ -92,6 +98,34 @@ def cpu_baseline_all_cores(clip_np, gpu_stream_bytes):
     return base, parity
 
 
+DUMP_BYTES = 64 << 20          # --dump-outputs: all files together stay below this
+SAMPLE_BYTES = 12 << 20        # stream bytes written in full (float32: 48 MiB); a longer stream is sampled at this many positions
+BLOCK = 4096                   # bytes per entry of stream_block_sums.npy
+
+
+def dump_outputs(path, stream):
+    """--dump-outputs DIR: what the last timed step handed its caller - the MPEG-2 elementary stream of the sequence, a uint8 tensor on
+    the device - as .npy files that two builds can be compared by, file for file:
+      stream.npy              float32, every byte of the stream, if it has at most SAMPLE_BYTES of them; otherwise
+      stream_sample.npy       float32, the bytes at SAMPLE_BYTES positions drawn once with numpy's default_rng(0) (without replacement,
+                              in stream order) - the same positions for the same stream length
+      stream_block_sums.npy   float64, per 4096-byte block of the whole stream (zero-padded) sum of (i + 1) * byte[i]: every byte counts
+      stream_length.npy       float64, [bytes in the stream]"""
+    import numpy as np
+    b = stream.cpu().numpy()
+    n = int(b.size)
+    os.makedirs(path, exist_ok=True)
+    if n <= SAMPLE_BYTES:
+        np.save(os.path.join(path, "stream.npy"), b.astype(np.float32))
+    else:
+        pos = np.sort(np.random.default_rng(0).choice(n, SAMPLE_BYTES, replace=False))
+        np.save(os.path.join(path, "stream_sample.npy"), b[pos].astype(np.float32))
+    blocks = np.concatenate([b, np.zeros(-n % BLOCK, np.uint8)]).reshape(-1, BLOCK).astype(np.float64)
+    np.save(os.path.join(path, "stream_block_sums.npy"), blocks @ np.arange(1, BLOCK + 1, dtype=np.float64))    # < 2^32: exact
+    np.save(os.path.join(path, "stream_length.npy"), np.array([n], np.float64))
+    assert 4 * min(n, SAMPLE_BYTES) + 8 * (n // BLOCK + 1) + 1024 < DUMP_BYTES
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -99,15 +133,21 @@ def main():
                     help="start / join the N ranks, all-reduce a 1 and print what the process group saw; no GPU work")
     ap.add_argument("--config", choices=["c3", "c2"], default="c3",
                     help="c3 (default, the metric's configuration): 1920x1152 I+P; c2: 640x480 I frames only (i_pframes_count = 0)")
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=100, help="timed steps (sequences); `ms_per_step` = their time / this")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--gops", type=int, default=GOPS)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: the other submission form, --sustain, the profiled pass (kernel times, "
+                         "roofline), the oracle's whole-stream parity check, CPU baselines, RTL probe, HBM copy rate, end_to_end, and for N > 1 "
+                         "the per-rank parity check and the strips legs.  Off: set up, warm up, time the K steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (the sequence's elementary stream) to DIR/*.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--prewarm", type=float, default=1.5,
                     help="seconds of untimed encoder steps BEFORE the W warmup steps: a step is ~2 ms, far shorter than the "
                          "GPU's clock ramp out of its idle state (sclk 312 MHz), so a cold start would time the ramp")
     ap.add_argument("--sustain", type=float, default=5.0,
-                    help="seconds of the SAME in-flight loop run once more after the K timed steps, in 0.5 s windows (the line's `sustained` "
+                    help="--full: seconds of the SAME in-flight loop run once more after the K timed steps, in 0.5 s windows (the line's `sustained` "
                          "object: clocks, power cap, thermal state over thousands of sequences instead of K); 0 = skip")
     ap.add_argument("--split", type=int, default=-1,
                     help="option split_streams of the encoder (GOP groups on that many HIP streams); -1 = the library's default (2)")
@@ -127,7 +167,7 @@ def main():
     ap.add_argument("--rotate-dst", action="store_true",
                     help="--mode strips: with sequences in flight, sequence i is assembled on rank i mod N (no single rank carries every gather)")
     ap.add_argument("--strips-legs", choices=["auto", "off"], default="auto",
-                    help="N > 1, default mode: after the c4 measurement run config c5 (--mode strips; RCCL halo, then --transport peer) as fresh child "
+                    help="N > 1, default mode, --full: after the c4 measurement run config c5 (--mode strips; RCCL halo, then --transport peer) as fresh child "
                          "processes under a time bound and attach the results to the c4 line as `strips` (bench_launch.py).  off: the c4 line alone")
     ap.add_argument("--strips-steps", type=int, default=40, help="steps of each strips leg")
     ap.add_argument("--long-gops", type=int, default=-1,
@@ -142,6 +182,10 @@ def main():
                     help="sequences (default): config c3 / c4, one 1920x1152 sequence per GPU, no collective; "
                          "strips: config c5, ONE 2048x2048 sequence cut into macroblock-row strips, RCCL halo exchange")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
+    if args.dump_outputs and args.mode != "sequences":
+        raise SystemExit("bench.py: --dump-outputs writes the outputs of the default mode (sequences)")
 
     # ---- N ranks: started by the caller (WORLD_SIZE set) or, failing that, by this process before it touches the GPU ----
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -308,15 +352,19 @@ def main():
                                                        per_step=1.0 / probe)
     # THE timed region: K steps of the encoder as shipped (no in-band timers)
     dt, nbytes = timed(args.steps, run_steps if submission == "in_flight" else sync_steps)
-    # the same K steps the other way (rounds 1 and 2 reported the blocking form as `value`)
-    dt_other, nbytes_other = timed(args.steps, sync_steps if submission == "in_flight" else run_steps) if nh > 1 else (dt, nbytes)
-    assert nbytes_other == nbytes
-    dt_sync, dt_fly = (dt_other, dt) if submission == "in_flight" else (dt, dt_other)
+    if args.dump_outputs and rank == 0:
+        # the last timed step went to handle (K - 1) mod nh in flight (its own output buffer), to `enc` / d_out otherwise
+        dump_outputs(args.dump_outputs, (d_outs[(args.steps - 1) % nh] if submission == "in_flight" else d_out)[:nbytes])
+    if args.full:
+        # the same K steps the other way (rounds 1 and 2 reported the blocking form as `value`)
+        dt_other, nbytes_other = timed(args.steps, sync_steps if submission == "in_flight" else run_steps) if nh > 1 else (dt, nbytes)
+        assert nbytes_other == nbytes
+        dt_sync, dt_fly = (dt_other, dt) if submission == "in_flight" else (dt, dt_other)
     # The K steps above are ~0.1 s of GPU time.  The same loop again for --sustain seconds of wall clock, in windows of ~0.5 s (a
     # window ends by collecting every handle, a bubble of one sequence in ~500): what the GPU holds once clocks, power and
     # temperature have settled.  Reported beside `value`, never as `value`.
     sustained = None
-    if args.sustain > 0:
+    if args.full and args.sustain > 0:
         fn = run_steps if submission == "in_flight" else sync_steps
         per = max(2 * nh, int(0.5 / max(dt / args.steps, 1e-6)))
         # the card this rank's HIP device IS, by PCI address (a lease that shows HIP one GPU of eight still lists all eight in sysfs)
@@ -368,16 +416,17 @@ def main():
                                        "not readable on this host (no /sys/class/drm card at PCI address %s)" % bus_id}
     # second pass, same K steps, for the per-kernel numbers: option "profile" brackets every launch with HIP events on the
     # launch stream and keeps the whole chunk on ONE stream, so that a launch's duration is the kernel alone on the GPU
-    enc.set_option("profile", 1)
-    step()
-    dt_prof, nbytes_prof = timed(args.steps, lambda k: [step() for _ in range(k)][-1])
-    assert nbytes_prof == nbytes
+    if args.full:
+        enc.set_option("profile", 1)
+        step()
+        dt_prof, nbytes_prof = timed(args.steps, lambda k: [step() for _ in range(k)][-1])
+        assert nbytes_prof == nbytes
 
     pixels_per_step = nframes * W * H
     value = world * args.steps * pixels_per_step / dt * 1e-6
 
     rank_parity = None
-    if world > 1:
+    if args.full and world > 1:
         # N > 1: every rank checks the first GOP of ITS sequence (its own seed) against the oracle - a few seconds of CPU per rank,
         # after the timed regions - and the ranks agree on the verdict.  (The whole-stream check of all GOPs is the N = 1 line's.)
         from oracle import m2v_oracle_ctypes as orc
@@ -395,23 +444,6 @@ def main():
                        "note": "every rank: sequence headers + first GOP of its own sequence against oracle/m2v_oracle.c"}
 
     if rank == 0:
-        # dominant kernel: k_mb<3,true> (P-frame macroblock kernel); for the I-only config c2 it is k_mb<1,false>.
-        # Statistics of the LAST step.
-        launches, ms, px = enc.kernel_stats(0)
-        li, msi, pxi = enc.kernel_stats(1)
-        l3, ms3, _ = enc.kernel_stats(3)
-        l4, ms4, _ = enc.kernel_stats(4)
-        if PFRAMES > 0:
-            # algorithmic HBM bytes per luma pixel of a P frame (SURVEY.md 8(d)): 3.0 input 4:4:4 + 1.5 reference
-            # load + 1.5 reconstruction store (frames that are referenced later); the bitstream leaves through k_assemble
-            dom, dom_name, dom_launches, dom_ms, tkey = "P", "k_mb<3,true> (P-frame macroblock kernel)", launches, ms, "k_mb_p_bytes_per_launch"
-            alg_bytes = (args.gops * (PFRAMES - 1) * 6.0 + args.gops * 4.5) * W * H
-        else:
-            # I frames that nothing references: 3.0 B/px of input, no reconstruction store
-            dom, dom_name, dom_launches, dom_ms, tkey = "I", "k_mb<1,false> (I-frame macroblock kernel, no search)", li, msi, "k_mb_i_c2_bytes_per_launch"
-            alg_bytes = nframes * 3.0 * W * H
-        achieved = alg_bytes / (dom_ms * 1e-3) * 1e-9 if dom_ms > 0 else 0.0
-        traffic = pmc_traffic(tkey) if PFRAMES > 0 and args.gops == GOPS or PFRAMES == 0 and nframes == 256 else {"traffic": None}   # measured for these launches
         workload = ("c3: 1920x1152 yuv444p, %d closed GOPs of 1 I + %d P frames (%d frames), VECTOR_LEVEL=3 Q_LEVEL=2 XL=YL=7, "
                     "one independent sequence per GPU (c4 for N > 1), no data-path collective" % (args.gops, PFRAMES, nframes)) if PFRAMES else \
                    ("c2: 640x480 yuv444p, %d I frames (i_pframes_count = 0), Q_LEVEL=2 XL=YL=7, one independent sequence per GPU, "
@@ -430,6 +462,28 @@ def main():
                        "sequences_in_flight": nh if submission == "in_flight" else 1,
                        "submission": submission + (" (checked by an untimed probe of both forms in the warm-up)" if nh > 1 else ""),
                        "queue_placement": placement},
+            "streams": {"per_sequence_in_the_timed_loop": args.split if args.split >= 0 else (1 if submission == "in_flight" else 2),
+                        "per_sequence_in_a_synchronous_call": args.split if args.split >= 0 else 2},
+        }
+    if rank == 0 and args.full:
+        # dominant kernel: k_mb<3,true> (P-frame macroblock kernel); for the I-only config c2 it is k_mb<1,false>.
+        # Statistics of the LAST step (of the profiled pass).
+        launches, ms, px = enc.kernel_stats(0)
+        li, msi, pxi = enc.kernel_stats(1)
+        l3, ms3, _ = enc.kernel_stats(3)
+        l4, ms4, _ = enc.kernel_stats(4)
+        if PFRAMES > 0:
+            # algorithmic HBM bytes per luma pixel of a P frame (SURVEY.md 8(d)): 3.0 input 4:4:4 + 1.5 reference
+            # load + 1.5 reconstruction store (frames that are referenced later); the bitstream leaves through k_assemble
+            dom, dom_name, dom_launches, dom_ms, tkey = "P", "k_mb<3,true> (P-frame macroblock kernel)", launches, ms, "k_mb_p_bytes_per_launch"
+            alg_bytes = (args.gops * (PFRAMES - 1) * 6.0 + args.gops * 4.5) * W * H
+        else:
+            # I frames that nothing references: 3.0 B/px of input, no reconstruction store
+            dom, dom_name, dom_launches, dom_ms, tkey = "I", "k_mb<1,false> (I-frame macroblock kernel, no search)", li, msi, "k_mb_i_c2_bytes_per_launch"
+            alg_bytes = nframes * 3.0 * W * H
+        achieved = alg_bytes / (dom_ms * 1e-3) * 1e-9 if dom_ms > 0 else 0.0
+        traffic = pmc_traffic(tkey) if PFRAMES > 0 and args.gops == GOPS or PFRAMES == 0 and nframes == 256 else {"traffic": None}   # measured for these launches
+        out.update({
             # `value`: K sequences, `sequences_in_flight` encoder handles taking turns (m2v_encode_resident_begin / _end): the stream
             # assembly of one sequence runs beside the first macroblock kernels of the next.  One handle, one blocking call per
             # sequence - what rounds 1 and 2 reported as `value` - is the entry below.
@@ -451,9 +505,7 @@ def main():
             "profiled_pass": {"value": round(world * args.steps * pixels_per_step / dt_prof * 1e-6, 2),
                               "ms_per_step": round(dt_prof / args.steps * 1e3, 3), "steps": args.steps,
                               "streams": 1, "in_band_event_timers": True},
-            "streams": {"per_sequence_in_the_timed_loop": args.split if args.split >= 0 else (1 if submission == "in_flight" else 2),
-                        "per_sequence_in_a_synchronous_call": args.split if args.split >= 0 else 2},
-        }
+        })
         if sustained is not None:
             sustained["vs_value"] = round(sustained["value"] * world / value, 4) if value > 0 else None
             out["sustained"] = sustained

@@ -5,7 +5,7 @@
   LOCAL_RANK / WORLD_SIZE / MASTER_* set, relays or keeps rank 0's stdout, and tears the job down when a rank dies or a deadline passes.
 * The strips legs: the driver's multi-GPU command is `bench.py --gpus N` in its default mode - config c4, independent sequences.  Config
   c5 (one frame sharded by macroblock rows, the north star's one collective config) is `--mode strips`, which the driver never passes.
-  So after the c4 measurement is in hand, and before its line is printed, every N > 1 job also runs `--mode strips` twice - halo through
+  So after the c4 measurement is in hand, and before its line is printed, every N > 1 job run with --full also runs `--mode strips` twice - halo through
   RCCL, then `--transport peer` - each as a batch of N FRESH child processes under a hard wall-clock bound, and attaches what they report
   as `strips: {rccl: {...}, peer: {...}}` to the c4 line, which is printed ONCE, LAST.  A strips leg that hangs, crashes or mismatches
   costs its own entry (`{"error": ...}`), never the c4 line and never the exit code.
@@ -255,8 +255,8 @@ def legs_from_rank(args, rank, world, ports):
 
 
 def legs_wanted(args, world):
-    """the strips legs ride on the DEFAULT job only: N > 1, sequences mode, the metric's configuration"""
-    if args.strips_legs == "off" or os.environ.get("M2V_BENCH_STRIPS_LEGS") == "0":
+    """the strips legs ride on the DEFAULT job only, with --full: N > 1, sequences mode, the metric's configuration"""
+    if not args.full or args.strips_legs == "off" or os.environ.get("M2V_BENCH_STRIPS_LEGS") == "0":
         return False
     return world > 1 and args.mode == "sequences" and args.config == "c3" and not args.ablate
 

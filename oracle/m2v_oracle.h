@@ -10,8 +10,8 @@
  * in the checkout, and no Verilog simulator exists in the build image, so this
  * restatement cannot be checked against an execution of the RTL here.  It is
  * pinned only by (i) a line-by-line reading of RTL/mpeg2encoder.v, cited at each
- * function, (ii) the RTL's own constant tables, compared entry by entry when
- * /root/reference is mounted (tests/test_tables_vs_rtl.py), (iii) hand-derived
+ * function, (ii) the RTL's own constant tables (the standard's), compared entry
+ * by entry in the RTL's layout (tests/test_tables_vs_rtl.py), (iii) hand-derived
  * known-answer bitstreams (tests/golden/), and (iv) an independent MPEG-2
  * decoder written from ISO/IEC 13818-2 that must reproduce the encoder's own
  * reconstruction (tests/m2v_decode.py).  tools/run_rtl_oracle.sh runs the real

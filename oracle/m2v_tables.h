@@ -4,8 +4,8 @@
  * TEST INFRASTRUCTURE ONLY (see oracle/README.md).  These are the ISO/IEC 13818-2
  * tables B-9, B-10, B-12, B-13, B-14, the default intra quantiser matrix, the
  * zig-zag scan and the HEVC-style integer DCT basis, written out in this repo's
- * own layout.  tests/test_tables_vs_rtl.py checks every entry against the live
- * `assign` lines of the reference RTL when /root/reference is mounted:
+ * own layout.  tests/test_tables_vs_rtl.py checks every entry against the tables
+ * of the reference RTL's `assign` lines, rebuilt in their layout from the standard:
  *
  *   DCT basis      RTL/mpeg2encoder.v:105-112
  *   intra matrix   RTL/mpeg2encoder.v:131-138

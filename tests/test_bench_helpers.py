@@ -67,3 +67,32 @@ def test_traffic_carries_the_tree_it_was_measured_on(tmp_path, monkeypatch):
     assert bench.pmc_valu_busy("k_mb_p_bytes_per_launch") == {}
     (tmp_path / "profiles" / "pmc_traffic.json").write_text(json.dumps({"kernel_sha": ksha, "valu_busy": {"k_mb_p_bytes_per_launch": 0.88, "source": "x", "kernel_sha": ksha}}))
     assert bench.pmc_valu_busy("k_mb_p_bytes_per_launch") == {"valu_busy": 0.88, "valu_busy_source": "x", "valu_busy_stale": False}
+
+
+def test_dump_outputs_writes_the_stream_as_float_arrays(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the stream in full while it fits, a fixed sample beyond; the block sums cover every byte either way"""
+    import torch
+    rng = np.random.default_rng(5)
+    data = rng.integers(0, 256, 10000, dtype=np.uint8)
+    w = np.arange(1, bench.BLOCK + 1, dtype=np.float64)
+    padded = np.concatenate([data, np.zeros(-data.size % bench.BLOCK, np.uint8)]).reshape(-1, bench.BLOCK)
+    want_sums = np.array([float(sum(int(b) * int(k) for b, k in zip(row, w))) for row in padded])
+    bench.dump_outputs(str(tmp_path / "whole"), torch.from_numpy(data))
+    s = np.load(tmp_path / "whole" / "stream.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, data.astype(np.float32))
+    assert not (tmp_path / "whole" / "stream_sample.npy").exists()
+    sums = np.load(tmp_path / "whole" / "stream_block_sums.npy")
+    assert sums.dtype == np.float64 and np.array_equal(sums, want_sums)
+    assert np.load(tmp_path / "whole" / "stream_length.npy").tolist() == [10000.0]
+    # longer than the budget: a sample at seeded positions, the same on every call; one flipped byte still changes a block sum
+    monkeypatch.setattr(bench, "SAMPLE_BYTES", 3000)
+    bench.dump_outputs(str(tmp_path / "a"), torch.from_numpy(data))
+    bench.dump_outputs(str(tmp_path / "b"), torch.from_numpy(data))
+    a, b = np.load(tmp_path / "a" / "stream_sample.npy"), np.load(tmp_path / "b" / "stream_sample.npy")
+    pos = np.sort(np.random.default_rng(0).choice(data.size, 3000, replace=False))
+    assert a.dtype == np.float32 and a.size == 3000 and np.array_equal(a, b) and np.array_equal(a, data[pos].astype(np.float32))
+    assert not (tmp_path / "a" / "stream.npy").exists()
+    flipped = data.copy()
+    flipped[7777] ^= 1
+    bench.dump_outputs(str(tmp_path / "c"), torch.from_numpy(flipped))
+    assert not np.array_equal(np.load(tmp_path / "a" / "stream_block_sums.npy"), np.load(tmp_path / "c" / "stream_block_sums.npy"))

@@ -22,7 +22,7 @@ def run(argv, env_extra=None, timeout=300):
 
 @pytest.mark.parametrize("n", [2, 3])
 def test_gpus_n_starts_n_ranks_by_itself(n):
-    r, lines = run(["--gpus", str(n), "--dry-launch"], {"M2V_DIST_BACKEND": "gloo"})
+    r, lines = run(["--gpus", str(n), "--dry-launch", "--full"], {"M2V_DIST_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(lines) == 1, "exactly one JSON line (rank 0's): %r" % r.stdout
     assert lines[0]["n_gpus"] == n and lines[0]["ranks_seen"] == n and lines[0]["ranks_counted"] == n
@@ -39,7 +39,7 @@ def test_a_strips_leg_that_hangs_or_fails_never_costs_the_c4_line():
     line, exit code 0; the RCCL leg beside it is fine.  Then a leg whose ranks exit with an error: a stated exit code, same line."""
     import time
     t0 = time.time()
-    r, lines = run(["--gpus", "2", "--dry-launch"], {"M2V_DIST_BACKEND": "gloo", "M2V_BENCH_TEST_HANG_LEG": "peer", "M2V_BENCH_LEG_TIMEOUT": "25"}, timeout=400)
+    r, lines = run(["--gpus", "2", "--dry-launch", "--full"], {"M2V_DIST_BACKEND": "gloo", "M2V_BENCH_TEST_HANG_LEG": "peer", "M2V_BENCH_LEG_TIMEOUT": "25"}, timeout=400)
     took = time.time() - t0
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(lines) == 1 and lines[0]["n_gpus"] == 2 and lines[0]["ranks_counted"] == 2
@@ -47,14 +47,16 @@ def test_a_strips_leg_that_hangs_or_fails_never_costs_the_c4_line():
     assert st["rccl"].get("dry_launch") is True and "error" not in st["rccl"]
     assert st["peer"]["error"] == "timeout" and 25 <= st["peer"]["seconds"] < 60          # (the bound is generous: a loaded box imports torch slowly)
     assert took < 240
-    r, lines = run(["--gpus", "2", "--dry-launch"], {"M2V_DIST_BACKEND": "gloo", "M2V_BENCH_TEST_FAIL_LEG": "rccl"}, timeout=240)
+    r, lines = run(["--gpus", "2", "--dry-launch", "--full"], {"M2V_DIST_BACKEND": "gloo", "M2V_BENCH_TEST_FAIL_LEG": "rccl"}, timeout=240)
     assert r.returncode == 0 and len(lines) == 1
     assert lines[0]["strips"]["rccl"]["error"] == "exit code 5" and lines[0]["strips"]["peer"].get("dry_launch") is True
 
 
 def test_strips_legs_can_be_switched_off():
-    r, lines = run(["--gpus", "2", "--dry-launch", "--strips-legs", "off"], {"M2V_DIST_BACKEND": "gloo"})
-    assert r.returncode == 0 and len(lines) == 1 and "strips" not in lines[0]
+    """the legs ride on --full only, and --strips-legs off drops them there too"""
+    for extra in ([], ["--full", "--strips-legs", "off"]):
+        r, lines = run(["--gpus", "2", "--dry-launch"] + extra, {"M2V_DIST_BACKEND": "gloo"})
+        assert r.returncode == 0 and len(lines) == 1 and "strips" not in lines[0], extra
 
 
 def test_one_gpu_needs_no_launcher():
@@ -68,7 +70,7 @@ def test_under_torch_distributed_run_the_ranks_are_not_started_twice():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     env["M2V_DIST_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", "29631", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-launch"],
+                        "--master-port", "29631", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-launch", "--full"],
                        capture_output=True, text=True, env=env, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
@@ -82,7 +84,7 @@ def test_under_torch_distributed_run_a_hanging_leg_is_ended_by_every_rank():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     env.update({"M2V_DIST_BACKEND": "gloo", "M2V_BENCH_TEST_HANG_LEG": "rccl", "M2V_BENCH_LEG_TIMEOUT": "25"})
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", "29633", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-launch"],
+                        "--master-port", "29633", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-launch", "--full"],
                        capture_output=True, text=True, env=env, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
@@ -97,7 +99,7 @@ def test_gpus_argument_must_match_the_launcher():
 
 def test_a_dying_rank_takes_the_job_down():
     """rank 1 fails before the rendezvous: the parent reports a non-zero code instead of waiting for ever"""
-    r, lines = run(["--gpus", "2", "--dry-launch"], {"M2V_DIST_BACKEND": "gloo", "M2V_BENCH_TEST_FAIL_RANK": "1"}, timeout=120)
+    r, lines = run(["--gpus", "2", "--dry-launch", "--full"], {"M2V_DIST_BACKEND": "gloo", "M2V_BENCH_TEST_FAIL_RANK": "1"}, timeout=120)
     assert r.returncode != 0
 
 
@@ -113,7 +115,7 @@ def test_a_rank_that_ignores_sigterm_is_killed(tmp_path):
     """rank 1 fails, rank 0 is stuck (as in a collective the failed rank never joins) and ignores SIGTERM: the launcher escalates
     to SIGKILL instead of looping for ever (round-3 advisor), and the stuck process is really gone afterwards"""
     pidfile = str(tmp_path / "deaf.pid")
-    r, _ = run(["--gpus", "2", "--dry-launch"], {"M2V_DIST_BACKEND": "gloo", "M2V_BENCH_TEST_FAIL_RANK": "1", "M2V_BENCH_TEST_DEAF_RANK": "0",
+    r, _ = run(["--gpus", "2", "--dry-launch", "--full"], {"M2V_DIST_BACKEND": "gloo", "M2V_BENCH_TEST_FAIL_RANK": "1", "M2V_BENCH_TEST_DEAF_RANK": "0",
                                                  "M2V_BENCH_TEST_PIDFILE": pidfile, "M2V_BENCH_GRACE": "2,2"}, timeout=120)
     assert r.returncode != 0
     assert not _alive(int(open(pidfile).read()))
@@ -126,7 +128,7 @@ def test_terminating_the_launcher_ends_its_ranks(tmp_path):
     pidfile = str(tmp_path / "deaf.pid")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update({"M2V_DIST_BACKEND": "gloo", "M2V_BENCH_TEST_DEAF_RANK": "1", "M2V_BENCH_TEST_PIDFILE": pidfile, "M2V_BENCH_GRACE": "2,2"})
-    p = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-launch"], env=env, cwd=ROOT,
+    p = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-launch", "--full"], env=env, cwd=ROOT,
                          stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     t0 = time.time()
     while not os.path.exists(pidfile) and time.time() - t0 < 90:

@@ -23,7 +23,8 @@ def run_bench(argv, timeout=900):
 
 
 def test_sequences_mode_two_ranks():
-    line = run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--prewarm", "0.2", "--no-cpu-baseline", "--gops", "2", "--strips-steps", "6", "--long-gops", "6"])
+    line = run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--prewarm", "0.2", "--no-cpu-baseline", "--gops", "2", "--strips-steps", "6", "--long-gops", "6",
+                      "--full"])
     assert line["n_gpus"] == 2 and line["ranks_seen"] == 2 and line["scaling"] == "weak"
     assert line["config"]["launched_by"] == "bench.py" and line["config"]["dist_backend"] == "gloo"
     assert line["value"] > 0 and line["roofline"]["frac"] > 0
@@ -50,7 +51,8 @@ def test_the_drivers_form_torch_distributed_run_also_measures_the_strips():
     env.update({"M2V_BENCH_SHARE_GPU": "1", "M2V_DIST_BACKEND": "gloo"})
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29641", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--prewarm", "0.2",
-                        "--gops", "2", "--strips-steps", "4", "--long-gops", "4", "--sustain", "0"], capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
+                        "--gops", "2", "--strips-steps", "4", "--long-gops", "4", "--sustain", "0", "--full"], capture_output=True, text=True, env=env, timeout=900,
+                       cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -85,7 +87,29 @@ def test_strips_mode_one_rank_runs_the_native_loop():
 
 
 def test_config_c2_line():
-    line = run_bench(["--config", "c2", "--steps", "3", "--warmup", "1", "--prewarm", "0.2", "--gops", "64", "--no-e2e"])
+    line = run_bench(["--config", "c2", "--steps", "3", "--warmup", "1", "--prewarm", "0.2", "--gops", "64", "--no-e2e", "--full"])
     assert line["config"]["frames"] == 64 and "I only" in line["metric"]
     assert line["parity_check"]["identical_to_oracle"] is True
     assert "k_mb<1,false>" in line["roofline"]["kernel"] and line["roofline"]["frac"] > 0
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline alone, K timed steps; --dump-outputs writes the stream of the
+    last timed step, which is the oracle's, GOP for GOP"""
+    import numpy as np
+    import m2v_load
+    from bench_util import compare_with_per_gop_oracle
+    from oracle import m2v_oracle_ctypes as orc
+    line = run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--prewarm", "0.2", "--gops", "2", "--dump-outputs", str(tmp_path)])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "MPixels/s" and line["higher_is_better"] is True and line["dtype"] == "u8" and "I+P" in line["metric"]
+    for key in ("roofline", "kernel_ms_per_step", "profiled_pass", "one_synchronous_call_per_step", "sustained", "cpu_baseline", "parity_check", "end_to_end"):
+        assert key not in line, key
+    n = line["config"]["stream_bytes"]
+    stream = np.load(tmp_path / "stream.npy")
+    assert stream.dtype == np.float32 and stream.size == n and np.load(tmp_path / "stream_length.npy").tolist() == [float(n)]
+    M = m2v_load.load()
+    clip = M.synth.clip_torch(1920, 1152, 18, clip_index=0, device="cuda:0").cpu().numpy()     # the benchmark's clip (rank 0)
+    orc.build()
+    refs = [orc.encode(clip[g * 9:(g + 1) * 9], 120, 72, 8, 7, 7, 3, 2) for g in range(2)]
+    assert compare_with_per_gop_oracle(stream.astype(np.uint8).tobytes(), refs, 9) == []

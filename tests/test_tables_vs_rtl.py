@@ -1,49 +1,52 @@
 """Every constant table of the oracle (and of the HIP path, which shares the values through
-tests/test_abi.py::test_product_tables_match_oracle_tables) against the live `assign` lines of the reference RTL.
+tests/test_abi.py::test_product_tables_match_oracle_tables) against the tables of the reference RTL, laid out as its `assign`
+statements lay them out (names, indices, code without the sign bit, length 0 = no code).
 
-Runs only where /root/reference is mounted (the build container); skipped on the GPU box.
+The RTL's tables are the standard's: Annex B of ISO/IEC 13818-2 (as fpga-mpeg2-encoder_amd/decoder.py types them in), the
+zig-zag scan and default intra matrix of 7.3 / 6.3.11, and DCTM[i][j] = round(64 sqrt(2) C(i) cos((2j + 1) i pi / 16)) with
+C(0) = 1 / sqrt(2), C(i) = 1 otherwise.  They are rebuilt here from those sources, so the test needs nothing outside the repository;
+the rebuilt tables are value for value the ones in RTL/mpeg2encoder.v (compared when this test was made self-contained).
 """
 import ctypes
-import os
-import re
+import math
 
 import pytest
 
+import m2v_load
 from oracle import m2v_oracle_ctypes as orc
 
-RTL = "/root/reference/RTL/mpeg2encoder.v"
-pytestmark = pytest.mark.skipif(not os.path.exists(RTL), reason="reference RTL not mounted")
 
-_NUM = re.compile(r"^\s*(?:(\d+)'s?([hdb]))?\s*(-?[0-9a-fA-F_]+)\s*$")
+def standard_tables():
+    """name -> {index tuple: value}, the RTL's table names and indexing, from ISO/IEC 13818-2 and the DCT's definition"""
+    iso = m2v_load.load().decoder.iso_tables()
+    T = {}
+    T["DCTM"] = {(i, j): round(64 * math.sqrt(2) * (math.sqrt(0.5) if i == 0 else 1.0) * math.cos((2 * j + 1) * i * math.pi / 16))
+                 for i in range(8) for j in range(8)}
+    T["INTRA_Q"] = {(i, j): iso["intra_w"][i * 8 + j] for i in range(8) for j in range(8)}
+    T["ZIGZAG"] = {(i, j): iso["zigzag"][i * 8 + j] for i in range(8) for j in range(8)}
 
-
-def _parse_value(txt):
-    txt = txt.strip()
-    neg = txt.startswith("-")
-    if neg:
-        txt = txt[1:]
-    m = re.match(r"^(?:\d+'s?([hdb]))?([0-9a-fA-F]+)$", txt)
-    assert m, txt
-    base = {"h": 16, "d": 10, "b": 2, None: 10}[m.group(1)]
-    v = int(m.group(2), base)
-    return -v if neg else v
-
-
-def rtl_tables():
-    """name -> {index tuple: value} from uncommented `assign NAME[i]([j]) = value;` statements."""
-    tabs = {}
-    pat = re.compile(r"assign\s+(\w+)\s*((?:\[\s*\d+\s*\])+)\s*=\s*([^;]+);")
-    for line in open(RTL):
-        code = line.split("//")[0]
-        for name, idx, val in pat.findall(code):
-            key = tuple(int(x) for x in re.findall(r"\d+", idx))
-            tabs.setdefault(name, {})[key] = _parse_value(val)
-    return tabs
+    def vlc(bits, lens, rows, size):
+        T[bits] = {(k,): 0 for k in range(size)}
+        T[lens] = {(k,): 0 for k in range(size)}
+        for code, length, sym in rows:
+            T[bits][(sym,)], T[lens][(sym,)] = code, length
+    vlc("BITS_MOTION_VECTOR", "LENS_MOTION_VECTOR", iso["motion"], 17)
+    vlc("BITS_NZ_FLAGS", "LENS_NZ_FLAGS", iso["cbp"], 64)              # pattern 0 has no code in a 4:2:0 stream
+    vlc("BITS_DC_Y", "LENS_DC_Y", iso["dcy"], 12)
+    vlc("BITS_DC_UV", "LENS_DC_UV", iso["dcc"], 12)
+    # B-14 by (run, level - 1): runs 0..3 with levels up to 40, runs 0..31 with levels up to 3 (the RTL leaves runs 0..3 of the second empty)
+    for name, runs, levels in (("AC_0_3", 4, 40), ("AC_4_31", 32, 3)):
+        T["BITS_" + name] = {(r, l): 0 for r in range(runs) for l in range(levels)}
+        T["LENS_" + name] = {(r, l): 0 for r in range(runs) for l in range(levels)}
+    for code, length, (run, level) in iso["ac"]:
+        name = "AC_0_3" if run <= 3 else "AC_4_31"
+        T["BITS_" + name][(run, level - 1)], T["LENS_" + name][(run, level - 1)] = code, length
+    return T
 
 
 @pytest.fixture(scope="module")
 def T():
-    return rtl_tables()
+    return standard_tables()
 
 
 def _pair(fn, *args):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Prints the headline numbers of a bench.py JSON line read from stdin (helper for quick GPU iterations):
-    python bench.py | python tools/bench_brief.py      or      python tools/bench_brief.py bench.json"""
+    python bench.py --full | python tools/bench_brief.py      or      python tools/bench_brief.py bench.json"""
 import json
 import sys
 

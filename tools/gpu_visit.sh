@@ -14,16 +14,16 @@ for what in "$@"; do
     newtests)
       timeout 1800 python3 -m pytest tests/test_gpu_strips.py tests/test_gpu_bench_launch.py -x -q -m gpu -s > $OUT/pytest_new.log 2>&1; echo "pytest rc=$?" >> $OUT/pytest_new.log; tail -12 $OUT/pytest_new.log ;;
     bench)
-      python3 bench.py --no-e2e > $OUT/bench.json 2> $OUT/bench.err; python3 tools/bench_brief.py < $OUT/bench.json ;;
+      python3 bench.py --full --no-e2e > $OUT/bench.json 2> $OUT/bench.err; python3 tools/bench_brief.py < $OUT/bench.json ;;
     benchfull)
-      python3 bench.py > $OUT/bench.json 2> $OUT/bench.err; python3 tools/bench_brief.py < $OUT/bench.json ;;
+      python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err; python3 tools/bench_brief.py < $OUT/bench.json ;;
     strips)
       python3 bench.py --mode strips > $OUT/strips_bench_1gpu.json 2> $OUT/strips.err
       python3 -c "
 import json; d=json.load(open('$OUT/strips_bench_1gpu.json'))
 print('strips: %.0f MPix/s  %.3f ms/step  loop %s  exchange %s  kernels %s  parity %s' % (d['value'], d['ms_per_step'], d['config']['strip_loop'], d['exchange_ms_per_step'], d['kernel_ms_per_step'], d.get('parity_check',{}).get('identical_to_oracle')))" ;;
     c2)
-      python3 bench.py --config c2 > $OUT/c2_bench.json 2> $OUT/c2.err
+      python3 bench.py --full --config c2 > $OUT/c2_bench.json 2> $OUT/c2.err
       python3 -c "
 import json; d=json.load(open('$OUT/c2_bench.json'))
 print('c2: %.0f MPix/s  %.3f ms/step  roofline %s  parity %s' % (d['value'], d['ms_per_step'], {k: d['roofline'][k] for k in ('achieved','frac','avg_launch_ms')}, d.get('parity_check',{}).get('identical_to_oracle')))" ;;

@@ -10,14 +10,14 @@ python3 -c "import __graft_entry__ as g; g.build()" > $OUT/build.log 2>&1
 M2V_DCT_MFMA=1 timeout 1800 python3 -m pytest tests -x -q -m gpu > $OUT/pytest_mfma.log 2>&1
 echo "pytest(mfma on) rc=$?"; tail -3 $OUT/pytest_mfma.log
 for V in 0 1; do
-  M2V_DCT_MFMA=$V rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/raw$V -o s -- python3 bench.py --split 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_rocprof_$V.log 2>&1
+  M2V_DCT_MFMA=$V rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/raw$V -o s -- python3 bench.py --full --split 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_rocprof_$V.log 2>&1
   python3 tools/summarize_rocprof.py $OUT/raw$V/s_kernel_stats.csv $OUT/kernel_stats_$V.csv; rm -rf $OUT/raw$V
-  M2V_DCT_MFMA=$V rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU_MFMA_I8 --output-format csv -d $OUT/p$V -o p -- python3 bench.py --inflight 1 --split 1 --steps 1 --warmup 1 --prewarm 0 --no-cpu-baseline > /dev/null 2>&1
+  M2V_DCT_MFMA=$V rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU_MFMA_I8 --output-format csv -d $OUT/p$V -o p -- python3 bench.py --full --inflight 1 --split 1 --steps 1 --warmup 1 --prewarm 0 --no-cpu-baseline > /dev/null 2>&1
   python3 tools/summarize_pmc.py $OUT/p$V > $OUT/pmc_$V.json; rm -rf $OUT/p$V
 done
 for i in 1 2 3; do
   for V in 0 1; do
-    M2V_DCT_MFMA=$V python3 bench.py --no-cpu-baseline --steps 200 2>/dev/null | python3 -c "
+    M2V_DCT_MFMA=$V python3 bench.py --full --no-cpu-baseline --steps 200 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('dct_mfma=$V  value %.0f MPixels/s  profiled-pass k_mb_P %.4f ms/step (%.2f us per launch)  k_mb_I %.4f' % (d['value'], d['kernel_ms_per_step']['k_mb_P'], d['roofline']['avg_launch_ms']*1e3, d['kernel_ms_per_step']['k_mb_I']))" | tee -a $OUT/ab.txt

@@ -2,7 +2,7 @@
 """How much of bench.py's timed loop (two sequences in flight) runs with 0 / 1 / 2+ encoder kernels on the GPU, from a rocprofv3
 --kernel-trace run.  Under the tracer kernels of different queues still overlap (it serialises nothing), but every dispatch is a little
 slower: read the shares, not the absolute time.
-    rocprofv3 --kernel-trace --output-format csv -d DIR -o t -- python3 bench.py --steps 12 --warmup 2 --no-cpu-baseline --no-e2e
+    rocprofv3 --kernel-trace --output-format csv -d DIR -o t -- python3 bench.py --full --steps 12 --warmup 2 --no-cpu-baseline --no-e2e
     python tools/overlap_timeline.py DIR"""
 import csv
 import glob

@@ -190,7 +190,7 @@ def compare_mb_dump(path, dump, W, H, limit=5):
 def main():
     import json
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rtl", default=os.environ.get("M2V_RTL", "/root/reference/RTL/mpeg2encoder.v"))
+    ap.add_argument("--rtl", default=os.environ.get("M2V_RTL", ""), help="the reference's RTL/mpeg2encoder.v (default: $M2V_RTL)")
     ap.add_argument("--keep", action="store_true")
     args = ap.parse_args()
     simname, build = find_simulator()

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Timeline of the encoder's kernels inside the last steps of a rocprofv3 --kernel-trace run of bench.py: when each launch
 starts and ends relative to the step, on which queue, and how much of the step no encoder kernel was running.
-    rocprofv3 --kernel-trace --output-format csv -d DIR -o t -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline
+    rocprofv3 --kernel-trace --output-format csv -d DIR -o t -- python3 bench.py --full --steps 4 --warmup 2 --no-cpu-baseline
     python tools/step_timeline.py DIR"""
 import csv
 import glob

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 for rep in 1 2 3; do
 for k in 0 ${1:-1 2 3 4 5 6} 0; do
   if [ $k = 0 ]; then A=1048576; else A=$((k * 65536)); fi     # kind 0: bit 20 = the debug library, no padding, no stop point
-  python3 bench.py --ablate $A --inflight 1 --split 1 --steps 30 --warmup 5 --no-cpu-baseline --no-e2e 2>/dev/null | python3 -c "
+  python3 bench.py --full --ablate $A --inflight 1 --split 1 --steps 30 --warmup 5 --no-cpu-baseline --no-e2e 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print('kind $k  P kernel ms/sequence', d['kernel_ms_per_step']['k_mb_P'], ' ms/step (profiled pass)', d['profiled_pass']['ms_per_step'])"
 done; done
