@@ -21,7 +21,7 @@ from . import decoder  # noqa: F401  (analysis tool: MPEG-2 ES decoder written f
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # M2V_LIB: development hook for same-box A/B timing of two builds (tools/ab.sh); never set otherwise
 LIB_PATH = os.environ.get("M2V_LIB") or os.path.join(_HERE, "libm2v_mi355x.so")
-# the -DM2V_DEBUG build (level dump, "keep_recon", "ablate"): stage-level parity tests and profiling scripts only
+# the -DM2V_DEBUG build (level dump, "keep_recon", "inject_strip_failure"): stage-level parity tests and profiling scripts only
 LIB_DBG_PATH = os.environ.get("M2V_LIB_DBG") or os.path.join(_HERE, "libm2v_mi355x_dbg.so")
 
 _libs = {}
@@ -185,8 +185,6 @@ class Mpeg2Encoder:
         if not self._h:
             raise M2VError("m2v_create failed with code %d (parameters %r, device %d): %s"
                            % (err.value, self.params, device, self._L.m2v_last_error(None).decode()))
-        if os.environ.get("M2V_DCT_MFMA") in ("0", "1"):      # development hook: A/B runs of the DCT-as-GEMM variant of the kernel
-            self.set_option("dct_mfma", int(os.environ["M2V_DCT_MFMA"]))
 
     def close(self):
         if getattr(self, "_h", None):

@@ -46,7 +46,6 @@ Geom make_geom(const m2v_enc *e, uint32_t xs, uint32_t ys)
     g.row0 = 0;
     g.row1 = g.mbh;
     g.strip = 0;
-    g.ablate = e->ablate;
     g.cu_pack = e->cu_pack;
     geom_finish(g);
     return g;
@@ -427,7 +426,7 @@ extern "C" {
 
 const char *m2v_version(void)
 {
-    return kDebug ? "m2v_mi355x 0.3-debug (gfx950, wave64, one wavefront per macroblock; M2V_DEBUG: level dump, keep_recon, ablate)"
+    return kDebug ? "m2v_mi355x 0.3-debug (gfx950, wave64, one wavefront per macroblock; M2V_DEBUG: level dump, keep_recon, inject_strip_failure)"
                   : "m2v_mi355x 0.3 (gfx950, wave64, one wavefront per macroblock)";
 }
 
@@ -637,7 +636,7 @@ int m2v_set_option(m2v_enc *e, const char *name, long long value)
     if (!strcmp(name, "copy_threads")) { if (value < 1 || value > 64) return M2V_E_PARAM; e->copy_threads = (int)value; return M2V_OK; }
     if (kDebug) {       // libm2v_mi355x_dbg.so only (-DM2V_DEBUG): the shipped library does not know these names
         if (!strcmp(name, "keep_recon")) { e->keep_recon = value != 0; return M2V_OK; }
-        if (!strcmp(name, "ablate")) { e->ablate = (int)value; return M2V_OK; }   // profiling aid: output is invalid when != 0
+        if (!strcmp(name, "inject_strip_failure")) { e->inject_strip_failure = value != 0; return M2V_OK; }   // tests of the failing-rank protocol
     }
     e->set_err("m2v_set_option: unknown option '%s'", name);
     return M2V_E_PARAM;

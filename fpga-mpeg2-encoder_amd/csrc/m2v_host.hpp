@@ -79,7 +79,7 @@ struct m2v_enc {
     // options
     size_t batch_frames = 96;
     bool profile = false;
-    int ablate = 0;               // profiling aid, see Geom::ablate
+    bool inject_strip_failure = false;  // debug: a strip encode fails on this rank after the collective set-up (option "inject_strip_failure")
     bool keep_recon = false;      // debug: every frame keeps its own reconstruction buffer, levels are dumped
 
     // sequence state (RTL:1017-1022)

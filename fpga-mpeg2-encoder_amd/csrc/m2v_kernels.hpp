@@ -581,9 +581,6 @@ __device__ __forceinline__ uint32_t vlc_tile_symbols_intra(const int16_t *zig, u
 // exactly the LDS write -> read ordering the phases need, and the static LDS base keeps every DS offset an immediate.
 // (Measured alternatives: 4 wavefronts per workgroup with per-wave LDS regions -16 %, a seq_cst wavefront fence -14 %.)
 #define M2V_WAVE_SYNC() __syncthreads()
-// -DM2V_DEBUG profiling aid: option "ablate" = n << 8 ends the kernel at stop point n (tools/phase_valu.sh: the counters of the
-// truncated kernels give the instruction count of every phase by difference; output invalid)
-#define M2V_STOP(n) do { if (kDebug && (g.ablate >> 8) == (n)) return; } while (0)
 
 typedef __attribute__((address_space(3))) uint32_t LdsU32;
 struct QsadRow { unsigned long long w01, w12, w23, w34; };    // the four overlapping 8-byte reference operands of one window row
@@ -591,13 +588,6 @@ struct QsadRow { unsigned long long w01, w12, w23, w34; };    // the four overla
 // full-pel search: the operands of a window row are issued one row ahead of their v_qsad (p / q alternate), by hand-issued ds_read_b64 - left to
 // itself the compiler fuses them into ds_read2_b64, which runs at half the LDS rate (MI355X_MICROARCH.md, LDS table).  ae / ao: LDS byte addresses
 // of the lane's even / odd dword pairs in its first window row.
-// Measurement aid of experiment 19 (profiles/r06_experiments.txt; tools/variant_build.sh ub=-DM2V_EXP19_QSAD_PER_STEP=3): with 3 every
-// step of the VECTOR_LEVEL 3 search drops its fourth v_qsad - a quarter of the search's vector cycles gone, results INVALID - which
-// bounds from above what any re-packing of the search's 39 dead candidate slots (of 208) could buy.  4 = the kernel as shipped.
-#ifndef M2V_EXP19_QSAD_PER_STEP
-#define M2V_EXP19_QSAD_PER_STEP 4
-#endif
-constexpr int kExp19QsadPerStep = M2V_EXP19_QSAD_PER_STEP;
 
 typedef const __attribute__((address_space(3))) u32x4_t *LdsU4;
 typedef const __attribute__((address_space(3))) u32x2_t *LdsU2;
@@ -647,7 +637,7 @@ __device__ __forceinline__ void search_rows13(uint32_t cur, uint32_t cur12, uint
         acc = __builtin_amdgcn_qsad_pk_u16_u8(p.w01, c.x, acc);
         acc = __builtin_amdgcn_qsad_pk_u16_u8(p.w12, c.y, acc);
         acc = __builtin_amdgcn_qsad_pk_u16_u8(p.w23, c.z, acc);
-        if constexpr (kExp19QsadPerStep >= 4) acc = __builtin_amdgcn_qsad_pk_u16_u8(p.w34, c.w, acc);
+        acc = __builtin_amdgcn_qsad_pk_u16_u8(p.w34, c.w, acc);
         if constexpr (RR == 2 || RR == 5 || RR == 8)
             asm volatile("s_mov_b64 exec, %2\n\tds_write_b64 %1, %0 offset:%3\n\ts_mov_b64 exec, -1"
                          : : "v"(acc), "v"(flush), "s"(hmask), "n"((RR / 3) * 8) : "memory");
@@ -984,15 +974,12 @@ __global__ __launch_bounds__(64, 8) void k_mb(const FrameJob *__restrict__ jobs,
             // (system-scope relaxed atomic loads = global_load .. sc0 sc1; the whole window of such a block, six loads per lane)
             bool far = false;
             if constexpr (PEER) {
-                // (-DM2V_DEBUG, option ablate bits 22-25: the hand-off's parts switched off one by one, to see what each costs - results invalid)
-                if (!(kDebug && (g.ablate & (1 << 24)))) {
-                    // every block of the neighbour's edge row, for every earlier frame of this GOP (they all are referenced: each has delivered)
-                    const unsigned int need = (unsigned int)job.i_frame * (unsigned int)g.mbw;
-                    const uint32_t slot = (uint32_t)job.rhidx * (uint32_t)kPeerCntStride;
-                    if (ext_u) peer_wait(ps.seen_up + slot, need, ps.gaveup, ps.budget, lane);
-                    if (ext_d) peer_wait(ps.seen_down + slot, need, ps.gaveup, ps.budget, lane);
-                }
-                far = (ext_u || ext_d) && !(kDebug && (g.ablate & (1 << 25)));
+                // every block of the neighbour's edge row, for every earlier frame of this GOP (they all are referenced: each has delivered)
+                const unsigned int need = (unsigned int)job.i_frame * (unsigned int)g.mbw;
+                const uint32_t slot = (uint32_t)job.rhidx * (uint32_t)kPeerCntStride;
+                if (ext_u) peer_wait(ps.seen_up + slot, need, ps.gaveup, ps.budget, lane);
+                if (ext_d) peer_wait(ps.seen_down + slot, need, ps.gaveup, ps.budget, lane);
+                far = ext_u || ext_d;
             }
             auto ld = [&](const uint8_t *base, uint32_t off) -> uint32_t {
                 typedef __attribute__((address_space(1))) unsigned int *gu32p;
@@ -1104,7 +1091,6 @@ __global__ __launch_bounds__(64, 8) void k_mb(const FrameJob *__restrict__ jobs,
         if (crow0 < CROWS)                      // s_cwin[plane][row * 4 + 2 * half]: (lane & 31) * 8 bytes into the plane's window
             *(LdsW64)(uintptr_t)(lds_off(&s_cwin[0][0]) + (uint32_t)cpl * (uint32_t)kCwinBytes + (uint32_t)(lane & 31) * 8u) = wc;
         M2V_WAVE_SYNC();
-        M2V_STOP(1);        // loads, chroma subsampling, window staging
 
         // ---- full-pel search: (2YR+1)^2 SADs (RTL:1634-1715) ---------------------------------
         // lane = (dy, group of 4 consecutive dx); v_qsad_pk_u16_u8 slides the 4 current pixels
@@ -1125,76 +1111,74 @@ __global__ __launch_bounds__(64, 8) void k_mb(const FrameJob *__restrict__ jobs,
             const int gq = VL == 3 ? s3_group(lane) : VL == 1 ? 1 + (pair & 1) : 1 + pair - 3 * dyi;
             const bool owner = VL == 3 || (part == 0 && pair0 < kPairs);
             const uint32_t sl_cb4 = sl.cb4, sl_dead_lo = sl.dead_lo, sl_dead_hi = sl.dead_hi;
-            if (!(kDebug && (g.ablate & 1))) {
-                unsigned long long acc = 0;
-                QsadRow ra, rb{};
-                if constexpr (VL == 3) {
-                    // all 64 lanes, 13 steps (see kS3Cur); every LDS address of the lane comes from the lane table
-                    const uint32_t lds0 = (uint32_t)(uintptr_t)(LdsU32 *)lds;      // 0: the block's only LDS object
-                    const uint32_t ae = lds0 + sl.even, ao = lds0 + sl.odd;
-                    const unsigned long long hmask = kS3Helpers;
-                    asm volatile("ds_read_b64 %0, %4\n\tds_read_b64 %1, %5\n\tds_read_b64 %2, %4 offset:8\n\tds_read_b64 %3, %5 offset:8"
-                                 : "=&v"(ra.w01), "=&v"(ra.w12), "=&v"(ra.w23), "=&v"(ra.w34) : "v"(ae), "v"(ao));
-                    search_rows13<0>(lds0 + sl.cur, lds0 + sl.cur12, ae, ao, lds0 + sl.plus, hmask, acc, ra, rb);
-                    asm volatile("s_mov_b64 exec, %2\n\tds_add_u64 %1, %0\n\ts_mov_b64 exec, -1"
-                                 : : "v"(acc), "v"(lds0 + sl.minus), "s"(hmask) : "memory");
-                    // owner lanes: + rows 13..15 = a difference of two running sums (no field borrows or carries: the sums grow
-                    // monotonically and a complete SAD is at most 65280); the helper lanes compute garbage and are dead below
-                    const u32x2_t sp = *(LdsU2)(uintptr_t)(lds0 + sl.plus), sm = *(LdsU2)(uintptr_t)(lds0 + sl.minus);
-                    const uint32_t lo = (uint32_t)acc + (sp.x - sm.x), hi = (uint32_t)(acc >> 32) + (sp.y - sm.y);
-                    acc = ((unsigned long long)hi << 32) | lo;
-                } else {
-                    // the pairs (w0,w1) (w2,w3) start at dword gq, the pairs (w1,w2) (w3,w4) at gq + 1: one of the two is even
-                    // in copy A, the other one in copy B (which holds dword j + 1 at index j)
-                    // hand-issued ds_read_b64, one row ahead (left to itself the compiler fuses them into ds_read2_b64,
-                    // which runs at half the LDS rate - MI355X_MICROARCH.md, LDS table)
-                    const int wrow = dyi + kNR * part;                 // the window row of the part's first macroblock row
-                    const uint32_t *const pe = (gq & 1) ? s_winb + wrow * kWS + gq - 1 : s_win + wrow * kWS + gq;
-                    const uint32_t *const po = (gq & 1) ? s_win + wrow * kWS + gq + 1 : s_winb + wrow * kWS + gq;
-                    const uint32_t ae = (uint32_t)(uintptr_t)(LdsU32 *)pe, ao = (uint32_t)(uintptr_t)(LdsU32 *)po;
-                    asm volatile("ds_read_b64 %0, %4\n\tds_read_b64 %1, %5\n\tds_read_b64 %2, %4 offset:8\n\tds_read_b64 %3, %5 offset:8"
-                                 : "=&v"(ra.w01), "=&v"(ra.w12), "=&v"(ra.w23), "=&v"(ra.w34) : "v"(ae), "v"(ao));
-                    search_rows_part<0, kNR, kWS>((uint32_t)(uintptr_t)(LdsU32 *)s_cur + (uint32_t)(part * kNR * 16), ae, ao, acc, ra, rb);
-                    // the parts' sums of a pair sit kLanesPerPart lanes apart: folded with the lane swaps (two rows of 32, then two rows of 16).
-                    // No field carries into its neighbour: a complete SAD is at most 65280.
-                    uint32_t lo = (uint32_t)acc, hi = (uint32_t)(acc >> 32);
-                    {
-                        const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-                        lo = a[0] + a[1]; hi = b[0] + b[1];
-                    }
-                    if constexpr (kParts == 4) {
-                        const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-                        lo = a[0] + a[1]; hi = b[0] + b[1];
-                    }
-                    acc = ((unsigned long long)hi << 32) | lo;
+            unsigned long long acc = 0;
+            QsadRow ra, rb{};
+            if constexpr (VL == 3) {
+                // all 64 lanes, 13 steps (see kS3Cur); every LDS address of the lane comes from the lane table
+                const uint32_t lds0 = (uint32_t)(uintptr_t)(LdsU32 *)lds;      // 0: the block's only LDS object
+                const uint32_t ae = lds0 + sl.even, ao = lds0 + sl.odd;
+                const unsigned long long hmask = kS3Helpers;
+                asm volatile("ds_read_b64 %0, %4\n\tds_read_b64 %1, %5\n\tds_read_b64 %2, %4 offset:8\n\tds_read_b64 %3, %5 offset:8"
+                             : "=&v"(ra.w01), "=&v"(ra.w12), "=&v"(ra.w23), "=&v"(ra.w34) : "v"(ae), "v"(ao));
+                search_rows13<0>(lds0 + sl.cur, lds0 + sl.cur12, ae, ao, lds0 + sl.plus, hmask, acc, ra, rb);
+                asm volatile("s_mov_b64 exec, %2\n\tds_add_u64 %1, %0\n\ts_mov_b64 exec, -1"
+                             : : "v"(acc), "v"(lds0 + sl.minus), "s"(hmask) : "memory");
+                // owner lanes: + rows 13..15 = a difference of two running sums (no field borrows or carries: the sums grow
+                // monotonically and a complete SAD is at most 65280); the helper lanes compute garbage and are dead below
+                const u32x2_t sp = *(LdsU2)(uintptr_t)(lds0 + sl.plus), sm = *(LdsU2)(uintptr_t)(lds0 + sl.minus);
+                const uint32_t lo = (uint32_t)acc + (sp.x - sm.x), hi = (uint32_t)(acc >> 32) + (sp.y - sm.y);
+                acc = ((unsigned long long)hi << 32) | lo;
+            } else {
+                // the pairs (w0,w1) (w2,w3) start at dword gq, the pairs (w1,w2) (w3,w4) at gq + 1: one of the two is even
+                // in copy A, the other one in copy B (which holds dword j + 1 at index j)
+                // hand-issued ds_read_b64, one row ahead (left to itself the compiler fuses them into ds_read2_b64,
+                // which runs at half the LDS rate - MI355X_MICROARCH.md, LDS table)
+                const int wrow = dyi + kNR * part;                 // the window row of the part's first macroblock row
+                const uint32_t *const pe = (gq & 1) ? s_winb + wrow * kWS + gq - 1 : s_win + wrow * kWS + gq;
+                const uint32_t *const po = (gq & 1) ? s_win + wrow * kWS + gq + 1 : s_winb + wrow * kWS + gq;
+                const uint32_t ae = (uint32_t)(uintptr_t)(LdsU32 *)pe, ao = (uint32_t)(uintptr_t)(LdsU32 *)po;
+                asm volatile("ds_read_b64 %0, %4\n\tds_read_b64 %1, %5\n\tds_read_b64 %2, %4 offset:8\n\tds_read_b64 %3, %5 offset:8"
+                             : "=&v"(ra.w01), "=&v"(ra.w12), "=&v"(ra.w23), "=&v"(ra.w34) : "v"(ae), "v"(ao));
+                search_rows_part<0, kNR, kWS>((uint32_t)(uintptr_t)(LdsU32 *)s_cur + (uint32_t)(part * kNR * 16), ae, ao, acc, ra, rb);
+                // the parts' sums of a pair sit kLanesPerPart lanes apart: folded with the lane swaps (two rows of 32, then two rows of 16).
+                // No field carries into its neighbour: a complete SAD is at most 65280.
+                uint32_t lo = (uint32_t)acc, hi = (uint32_t)(acc >> 32);
+                {
+                    const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+                    lo = a[0] + a[1]; hi = b[0] + b[1];
                 }
-                // minimum SAD; among equals the largest dy, then the largest dx (RTL:1694-1710): key = sad << 8 | (255 - index),
-                // index = dy' << 4 | dx + 8.  A SAD >= 4096 kills a candidate (RTL:1669-1670): such keys are >= 1 << 20 and lose
-                // against every live one, so the test is made once on the reduced key instead of per candidate.
-                // index has its two low bits clear, so 255 - index ends in 11 and candidate j's key is (sad_j << 8 | cbase) - j.
-                const uint32_t cbase = 255u - (uint32_t)((dyi << 4) | (4 * gq));
-                if (YR == 6 && sgpr(in_l & in_r & in_u & in_d)) {
-                    // VECTOR_LEVEL 3, a macroblock with all four neighbours (wave-uniform, 95 % of a frame): every dy is live and
-                    // the dead dx are the three slots beyond +-6 (dx = -8, -7 in group 0, dx = 7 in group 3): a dead slot gets SAD 0xFFFF
-                    // (the lane table holds those bits and the four position bytes cbase - j); one v_perm per key: [0, sad_hi, sad_lo, pos]
-                    const uint32_t l32 = (uint32_t)acc | sl_dead_lo, h32 = (uint32_t)(acc >> 32) | sl_dead_hi;
-                    const uint32_t k0 = __builtin_amdgcn_perm(l32, sl_cb4, 0x0C050400u), k1 = __builtin_amdgcn_perm(l32, sl_cb4, 0x0C070601u);
-                    const uint32_t k2 = __builtin_amdgcn_perm(h32, sl_cb4, 0x0C050402u), k3 = __builtin_amdgcn_perm(h32, sl_cb4, 0x0C070603u);
-                    key = umin32(umin32(k0, k1), umin32(k2, k3));
-                } else {
-                    // live dy / dx range at the frame border (RTL:1642-1645), wave-uniform and kept on the scalar unit: one
-                    // unsigned range compare per axis per candidate
-                    const int lo = -YR & -in_l, hi = YR & -in_r, ylo = -YR & -in_u, yhi = YR & -in_d;
-                    const uint32_t span = (uint32_t)(hi - lo), yspan = (uint32_t)(yhi - ylo);
-                    const bool rowok = (uint32_t)(dyi - YR - ylo) <= yspan;
-                    const int d0 = 4 * gq - 8 - lo;
+                if constexpr (kParts == 4) {
+                    const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+                    lo = a[0] + a[1]; hi = b[0] + b[1];
+                }
+                acc = ((unsigned long long)hi << 32) | lo;
+            }
+            // minimum SAD; among equals the largest dy, then the largest dx (RTL:1694-1710): key = sad << 8 | (255 - index),
+            // index = dy' << 4 | dx + 8.  A SAD >= 4096 kills a candidate (RTL:1669-1670): such keys are >= 1 << 20 and lose
+            // against every live one, so the test is made once on the reduced key instead of per candidate.
+            // index has its two low bits clear, so 255 - index ends in 11 and candidate j's key is (sad_j << 8 | cbase) - j.
+            const uint32_t cbase = 255u - (uint32_t)((dyi << 4) | (4 * gq));
+            if (YR == 6 && sgpr(in_l & in_r & in_u & in_d)) {
+                // VECTOR_LEVEL 3, a macroblock with all four neighbours (wave-uniform, 95 % of a frame): every dy is live and
+                // the dead dx are the three slots beyond +-6 (dx = -8, -7 in group 0, dx = 7 in group 3): a dead slot gets SAD 0xFFFF
+                // (the lane table holds those bits and the four position bytes cbase - j); one v_perm per key: [0, sad_hi, sad_lo, pos]
+                const uint32_t l32 = (uint32_t)acc | sl_dead_lo, h32 = (uint32_t)(acc >> 32) | sl_dead_hi;
+                const uint32_t k0 = __builtin_amdgcn_perm(l32, sl_cb4, 0x0C050400u), k1 = __builtin_amdgcn_perm(l32, sl_cb4, 0x0C070601u);
+                const uint32_t k2 = __builtin_amdgcn_perm(h32, sl_cb4, 0x0C050402u), k3 = __builtin_amdgcn_perm(h32, sl_cb4, 0x0C070603u);
+                key = umin32(umin32(k0, k1), umin32(k2, k3));
+            } else {
+                // live dy / dx range at the frame border (RTL:1642-1645), wave-uniform and kept on the scalar unit: one
+                // unsigned range compare per axis per candidate
+                const int lo = -YR & -in_l, hi = YR & -in_r, ylo = -YR & -in_u, yhi = YR & -in_d;
+                const uint32_t span = (uint32_t)(hi - lo), yspan = (uint32_t)(yhi - ylo);
+                const bool rowok = (uint32_t)(dyi - YR - ylo) <= yspan;
+                const int d0 = 4 * gq - 8 - lo;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const uint32_t sad = (uint32_t)(acc >> (16 * j)) & 0xFFFFu;
-                        const uint32_t k = (sad << 8) | (cbase - (uint32_t)j);
-                        const bool ok = owner && rowok && (uint32_t)(d0 + j) <= span;
-                        if (ok && k < key) key = k;
-                    }
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t sad = (uint32_t)(acc >> (16 * j)) & 0xFFFFu;
+                    const uint32_t k = (sad << 8) | (cbase - (uint32_t)j);
+                    const bool ok = owner && rowok && (uint32_t)(d0 + j) <= span;
+                    if (ok && k < key) key = k;
                 }
             }
             key = wave_min_u32(key);
@@ -1208,61 +1192,6 @@ __global__ __launch_bounds__(64, 8) void k_mb(const FrameJob *__restrict__ jobs,
             fx = sgpr(fx);
         }
 
-        M2V_STOP(2);        // ... up to the full-pel search
-        if (kDebug && ((g.ablate >> 16) & 15)) {
-            // -DM2V_DEBUG, option ablate bits 16-19: 64 extra INDEPENDENT vector instructions of one kind per macroblock - what does an
-            // instruction of that kind cost this kernel? (tools/valu_kind.sh; results unaffected: the values are discarded)
-            const int kind = sgpr((g.ablate >> 16) & 15);
-            uint32_t d0, d1, d2, d3;
-            const uint32_t a = (uint32_t)lane, b = cur4;
-#define M2V_PAD4(INS) INS(%0) INS(%1) INS(%2) INS(%3)
-#define M2V_PAD64(INS) asm volatile(M2V_PAD4(INS) M2V_PAD4(INS) M2V_PAD4(INS) M2V_PAD4(INS) M2V_PAD4(INS) M2V_PAD4(INS) M2V_PAD4(INS) M2V_PAD4(INS) \
-                                    M2V_PAD4(INS) M2V_PAD4(INS) M2V_PAD4(INS) M2V_PAD4(INS) M2V_PAD4(INS) M2V_PAD4(INS) M2V_PAD4(INS) M2V_PAD4(INS) \
-                                    : "=v"(d0), "=v"(d1), "=v"(d2), "=v"(d3) : "v"(a), "v"(b), "s"(kind))
-#define M2V_I_ADD(D)   "v_add_u32 " #D ", %4, %5\n\t"
-#define M2V_I_LSHL(D)  "v_lshlrev_b32 " #D ", 3, %4\n\t"
-#define M2V_I_MAD(D)   "v_mad_i32_i24 " #D ", %4, %5, %4\n\t"
-#define M2V_I_ADDS(D)  "v_add_u32 " #D ", %6, %4\n\t"
-#define M2V_I_ASHR(D)  "v_ashrrev_i32 " #D ", 3, %4\n\t"
-#define M2V_I_PERM(D)  "v_perm_b32 " #D ", %4, %5, %4\n\t"
-            if (kind == 7) {
-                // 16 LDS reads of 8 bytes per lane (64 LDS data cycles: + 5 % of the macroblock's), the lane's own window words
-                unsigned long long t0, t1, t2, t3;
-                asm volatile("ds_read_b64 %0, %4\n\tds_read_b64 %1, %4 offset:48\n\tds_read_b64 %2, %4 offset:96\n\tds_read_b64 %3, %4 offset:144\n\t"
-                             "ds_read_b64 %0, %4 offset:192\n\tds_read_b64 %1, %4 offset:240\n\tds_read_b64 %2, %4 offset:288\n\tds_read_b64 %3, %4 offset:336\n\t"
-                             "ds_read_b64 %0, %4 offset:8\n\tds_read_b64 %1, %4 offset:56\n\tds_read_b64 %2, %4 offset:104\n\tds_read_b64 %3, %4 offset:152\n\t"
-                             "ds_read_b64 %0, %4 offset:200\n\tds_read_b64 %1, %4 offset:248\n\tds_read_b64 %2, %4 offset:296\n\tds_read_b64 %3, %4 offset:344\n\t"
-                             "s_waitcnt lgkmcnt(0)" : "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3) : "v"(kq0.x) : "memory");
-            } else if (kind == 8) {
-                // 8 vector loads of one dword per lane from the lane table (L1 / L2 hits): + 24 % vector memory instructions
-                asm volatile("global_load_dword %0, %4, %5 offset:-4096\n\tglobal_load_dword %1, %4, %5 offset:-3072\n\t"
-                             "global_load_dword %2, %4, %5 offset:-2048\n\tglobal_load_dword %3, %4, %5 offset:-1024\n\t"
-                             "global_load_dword %0, %4, %5 offset:-4092\n\tglobal_load_dword %1, %4, %5 offset:-3068\n\t"
-                             "global_load_dword %2, %4, %5 offset:-2044\n\tglobal_load_dword %3, %4, %5 offset:-1020\n\t"
-                             "s_waitcnt vmcnt(0)" : "=&v"(d0), "=&v"(d1), "=&v"(d2), "=&v"(d3) : "v"(lane16), "s"(ltab) : "memory");
-            } else if (kind == 9) {
-                // ONE vector load and the wait for it: what an exposed memory round trip costs
-                asm volatile("global_load_dword %0, %1, %2 offset:-4096\n\ts_waitcnt vmcnt(0)" : "=&v"(d0) : "v"(lane16), "s"(ltab) : "memory");
-            } else if (kind == 11) {
-                // 64 scalar ALU instructions (four independent chains)
-                int a0 = sgpr(kind), a1 = a0, a2 = a0, a3 = a0;
-#define M2V_S4 "s_add_u32 %0, %0, 1\n\ts_add_u32 %1, %1, 1\n\ts_add_u32 %2, %2, 1\n\ts_add_u32 %3, %3, 1\n\t"
-                asm volatile(M2V_S4 M2V_S4 M2V_S4 M2V_S4 M2V_S4 M2V_S4 M2V_S4 M2V_S4 M2V_S4 M2V_S4 M2V_S4 M2V_S4 M2V_S4 M2V_S4 M2V_S4 M2V_S4
-                             : "+s"(a0), "+s"(a1), "+s"(a2), "+s"(a3) : : "scc");
-#undef M2V_S4
-            } else if (kind == 10) {
-                // ONE LDS read and the wait for it
-                asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(d0) : "v"(kq0.x) : "memory");
-            } else
-            if (kind == 1) M2V_PAD64(M2V_I_ADD);
-            else if (kind == 2) M2V_PAD64(M2V_I_LSHL);
-            else if (kind == 3) M2V_PAD64(M2V_I_MAD);
-            else if (kind == 4) M2V_PAD64(M2V_I_ADDS);
-            else if (kind == 5) M2V_PAD64(M2V_I_ASHR);
-            else M2V_PAD64(M2V_I_PERM);
-#undef M2V_PAD4
-#undef M2V_PAD64
-        }
         // ---- half-pel refinement + intra cost (RTL:1743-1816), four pixels per lane, packed bytes ----
         // T[y][x] = window[y+fy+YR][x+fx+8]; L/C/R = T[.][x-1 .. x+2], T[.][x .. x+3], T[.][x+1 .. x+4]
         uint32_t L0, C0, R0, L1, C1, R1, L2, C2, R2;
@@ -1297,43 +1226,40 @@ __global__ __launch_bounds__(64, 8) void k_mb(const FrameJob *__restrict__ jobs,
         // The decision (RTL:1784-1816): the ten costs as KEYS (cost << 16 | rank) whose minimum IS the RTL's tree with its tie-breaks (kHpRank
         // above).  A cost that the RTL caps at 4096 ("over", RTL:1784-1785) never wins - the intra cost is at most 4095 - so it is left
         // as it is, and a dead candidate just gets bit 12 set: five ORs on the packed pairs of totals, from a table word per pair.
-        uint32_t best = 2u;                                     // (search-less debug runs: the centre candidate at cost 0)
-        if (!(kDebug && (g.ablate & 2))) {
-            // "intra cost" accumulates the absolute deviation from the mean on top of the pixel sum, 16-bit wrap
-            // (RTL:1744, 1774-1777, 1791): the pixel sum S (formed in front of the search), then the deviation rides along with the nine SADs
-            const uint32_t m = (S >> 8) & 255u;
-            // half-pel candidates that would reach outside the frame or beyond the search range are dead (RTL:1757-1760)
-            // as 0 / 1 integers by sign-bit arithmetic: fx + YR - 1 is negative exactly for fx = -YR, and so on
-            const int no_l = (in_l ^ 1) | (int)((uint32_t)(fx + YR - 1) >> 31), no_r = (in_r ^ 1) | (int)((uint32_t)(YR - 1 - fx) >> 31);
-            const int no_u = (in_u ^ 1) | (int)((uint32_t)(fy + YR - 1) >> 31), no_d = (in_d ^ 1) | (int)((uint32_t)(YR - 1 - fy) >> 31);
-            typedef const __attribute__((address_space(4))) uint32_t *sld;
-            const sld dtab = (sld)(ltab2 - 1024 + kConstHpDead + (uint32_t)sgpr(no_l | (no_r << 1) | (no_u << 2) | (no_d << 3)) * (uint32_t)kHpDeadStride);
-            const uint32_t d0 = dtab[0], d1 = dtab[1], d2 = dtab[2], d3 = dtab[3], d4 = dtab[4];
-            // ten sums as five packed pairs (each total <= 65280; v_sad_hi_u8 packs for free), four of them reduced
-            // together by wave_sum4
-            uint32_t pk[5];
+        // "intra cost" accumulates the absolute deviation from the mean on top of the pixel sum, 16-bit wrap
+        // (RTL:1744, 1774-1777, 1791): the pixel sum S (formed in front of the search), then the deviation rides along with the nine SADs
+        const uint32_t m = (S >> 8) & 255u;
+        // half-pel candidates that would reach outside the frame or beyond the search range are dead (RTL:1757-1760)
+        // as 0 / 1 integers by sign-bit arithmetic: fx + YR - 1 is negative exactly for fx = -YR, and so on
+        const int no_l = (in_l ^ 1) | (int)((uint32_t)(fx + YR - 1) >> 31), no_r = (in_r ^ 1) | (int)((uint32_t)(YR - 1 - fx) >> 31);
+        const int no_u = (in_u ^ 1) | (int)((uint32_t)(fy + YR - 1) >> 31), no_d = (in_d ^ 1) | (int)((uint32_t)(YR - 1 - fy) >> 31);
+        typedef const __attribute__((address_space(4))) uint32_t *sld;
+        const sld dtab = (sld)(ltab2 - 1024 + kConstHpDead + (uint32_t)sgpr(no_l | (no_r << 1) | (no_u << 2) | (no_d << 3)) * (uint32_t)kHpDeadStride);
+        const uint32_t d0 = dtab[0], d1 = dtab[1], d2 = dtab[2], d3 = dtab[3], d4 = dtab[4];
+        // ten sums as five packed pairs (each total <= 65280; v_sad_hi_u8 packs for free), four of them reduced
+        // together by wave_sum4
+        uint32_t pk[5];
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
-                pk[k] = __builtin_amdgcn_sad_hi_u8(cur4, hp[2 * k + 1], __builtin_amdgcn_sad_u8(cur4, hp[2 * k], 0u));
-            pk[4] = __builtin_amdgcn_sad_hi_u8(cur4, m * 0x01010101u, __builtin_amdgcn_sad_u8(cur4, hp[8], 0u));
-            const int q4 = wave_sum4((int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]);
-            const uint32_t t01 = (uint32_t)__builtin_amdgcn_readlane(q4, 15) | d0, t23 = (uint32_t)__builtin_amdgcn_readlane(q4, 47) | d1;
-            const uint32_t t45 = (uint32_t)__builtin_amdgcn_readlane(q4, 31) | d2, t67 = (uint32_t)__builtin_amdgcn_readlane(q4, 63) | d3;
-            const uint32_t t8d = (uint32_t)wave_sum((int)pk[4]);
-            // key = cost << 16 | rank: ONE scalar instruction per candidate (s_pack_ll / s_pack_lh take the low / high half of the pair)
+        for (int k = 0; k < 4; ++k)
+            pk[k] = __builtin_amdgcn_sad_hi_u8(cur4, hp[2 * k + 1], __builtin_amdgcn_sad_u8(cur4, hp[2 * k], 0u));
+        pk[4] = __builtin_amdgcn_sad_hi_u8(cur4, m * 0x01010101u, __builtin_amdgcn_sad_u8(cur4, hp[8], 0u));
+        const int q4 = wave_sum4((int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]);
+        const uint32_t t01 = (uint32_t)__builtin_amdgcn_readlane(q4, 15) | d0, t23 = (uint32_t)__builtin_amdgcn_readlane(q4, 47) | d1;
+        const uint32_t t45 = (uint32_t)__builtin_amdgcn_readlane(q4, 31) | d2, t67 = (uint32_t)__builtin_amdgcn_readlane(q4, 63) | d3;
+        const uint32_t t8d = (uint32_t)wave_sum((int)pk[4]);
+        // key = cost << 16 | rank: ONE scalar instruction per candidate (s_pack_ll / s_pack_lh take the low / high half of the pair)
 #define M2V_KLO(p, k) ([](uint32_t pp) { uint32_t d; asm("s_pack_ll_b32_b16 %0, %1, %2" : "=s"(d) : "n"(kHpRank[k]), "s"(pp)); return d; }(p))
 #define M2V_KHI(p, k) ([](uint32_t pp) { uint32_t d; asm("s_pack_lh_b32_b16 %0, %1, %2" : "=s"(d) : "n"(kHpRank[k]), "s"(pp)); return d; }(p))
-            const uint32_t S2 = (S + (t8d >> 16)) & 0xFFFFu;       // the intra cost, capped at 0xFFF (RTL:1791)
-            const uint32_t k9 = M2V_KLO(umin32(S2, 0xFFFu), 9);
-            // (every two-way minimum pinned to the scalar unit: left alone the compiler folds them into v_min3_u32, which only the vector
-            // ALU has, with a v_mov per operand and a v_readfirstlane behind)
-            auto smin = [](uint32_t x, uint32_t y) { return (uint32_t)sgpr((int)umin32(x, y)); };
-            const uint32_t a = smin(smin(M2V_KLO(t01, 0), M2V_KHI(t01, 1)), smin(M2V_KLO(t23, 2), M2V_KHI(t23, 3)));
-            const uint32_t b = smin(smin(M2V_KLO(t45, 4), M2V_KHI(t45, 5)), smin(M2V_KLO(t67, 6), M2V_KHI(t67, 7)));
-            best = smin(smin(a, b), smin(M2V_KLO(t8d | d4, 8), k9));
+        const uint32_t S2 = (S + (t8d >> 16)) & 0xFFFFu;       // the intra cost, capped at 0xFFF (RTL:1791)
+        const uint32_t k9 = M2V_KLO(umin32(S2, 0xFFFu), 9);
+        // (every two-way minimum pinned to the scalar unit: left alone the compiler folds them into v_min3_u32, which only the vector
+        // ALU has, with a v_mov per operand and a v_readfirstlane behind)
+        auto smin = [](uint32_t x, uint32_t y) { return (uint32_t)sgpr((int)umin32(x, y)); };
+        const uint32_t a = smin(smin(M2V_KLO(t01, 0), M2V_KHI(t01, 1)), smin(M2V_KLO(t23, 2), M2V_KHI(t23, 3)));
+        const uint32_t b = smin(smin(M2V_KLO(t45, 4), M2V_KHI(t45, 5)), smin(M2V_KLO(t67, 6), M2V_KHI(t67, 7)));
+        const uint32_t best = smin(smin(a, b), smin(M2V_KLO(t8d | d4, 8), k9));
 #undef M2V_KLO
 #undef M2V_KHI
-        }
         const uint32_t rk = 2u * (best & 15u);                   // twice the winner's rank
         inter = (int)(rk != 2u);
         int hy = 0, hx = 0;
@@ -1403,7 +1329,6 @@ __global__ __launch_bounds__(64, 8) void k_mb(const FrameJob *__restrict__ jobs,
     }
     M2V_WAVE_SYNC();
 
-    M2V_STOP(3);            // ... up to the prediction
     // ---- stage G: 2-D forward DCT (RTL:2029-2062); lane = (i = lane>>3, j = lane&7) ------------
     keep_alive(kq2);
     // DCT-as-GEMM trial (north star): the four luma tiles through the matrix cores, the two chroma tiles as before
@@ -1482,7 +1407,6 @@ __global__ __launch_bounds__(64, 8) void k_mb(const FrameJob *__restrict__ jobs,
     }
     M2V_WAVE_SYNC();
 
-    M2V_STOP(4);            // ... up to the forward transform
     // ---- quantise (RTL:2065-2077), zig-zag + coded flags (RTL:2452-2468), dequantise (RTL:2129-2150)
     // the intra quantiser's lane constants: an I frame loads them up front, a P frame only inside its (rare) intra branch
     int wq = 0;
@@ -1493,14 +1417,11 @@ __global__ __launch_bounds__(64, 8) void k_mb(const FrameJob *__restrict__ jobs,
     // group 4 (column pass and chroma store of the reconstruction), requested two phases ahead
     const uint32_t k4r = kq4.y, k4p = kq4.z;
     const size_t mbidx = (size_t)fidx * g.mbs + mb;
-    const bool need_rec = job.rec != nullptr && !(kDebug && (g.ablate & 8));
+    const bool need_rec = job.rec != nullptr;
     int cbp = 0;
     v4i_t xl4 = {0, 0, 0, 0};           // matrix-core transform: the lane's four dequantised luma coefficients (row mc, columns 4 mg ..)
     const bool chroma_lane = ((((uint32_t)lane >> 5) ^ ((uint32_t)lane >> 3)) & 1u) == 0u;     // matrix-core layout: g >> 1 == c >> 3
-    if (kDebug && (g.ablate & 16)) {
-        for (int t = 0; t < 6; ++t) s_zig[t][lane] = 0;
-        cbp = inter ? 0 : 63;
-    } else if (inter) {
+    if (inter) {
         const int qneg = sgpr(-(((1 << (4 + Q)) - 5) << 12));      // MINUS the bias of a negative value (it multiplies the sign mask)
         if constexpr (kMfmaLuma) {
             // the four luma tiles in (transposed) accumulator layout: lane (g, c) owns columns 4g .. 4g+3 of row c of the 16x16 block,
@@ -1664,7 +1585,6 @@ __global__ __launch_bounds__(64, 8) void k_mb(const FrameJob *__restrict__ jobs,
     const uint32_t cbp_word = *(const __attribute__((address_space(4))) uint32_t *)(ltab2 - 1024 + kConstCbp + 4u * ((uint32_t)sgpr(cbp) >> 1));
     M2V_WAVE_SYNC();
 
-    M2V_STOP(5);            // ... up to the quantiser / inverse quantiser
     // ---- stage T, coefficient part: run/level VLC of the six tiles (RTL:2777-2847) -----------------
     // Pass 1 (per tile, lane = zig-zag index): ballot the non-zero levels, rank them, and append
     // {run, level} / raw-code symbols to one compact list.  Pass 2 (once per macroblock): table lookup,
@@ -1678,31 +1598,29 @@ __global__ __launch_bounds__(64, 8) void k_mb(const FrameJob *__restrict__ jobs,
     uint32_t nsym = 0, idxB = 0, idxC = 0;
     int dcs[6] = {0, 0, 0, 0, 0, 0};
     const uint32_t lane_pos = (uint32_t)lane << 20;
-    if (!(kDebug && (g.ablate & 4))) {
-        if (inter) {
-            const uint32_t e = (cbp_word >> (16 * (cbp & 1))) & 0xFFFFu;                    // d_cbp_code[cbp]
-            uint32_t nsym4 = ((uint32_t)-cbp >> 31) << 2;   // pattern 0 (motion vector only) has no code, and a raw symbol needs a length
-            const uint32_t eob = (uint32_t)vgpr_const((int)sym_raw(2u, 2u, true));
-            const uint32_t sym_base = lds_off(s_sym);
+    if (inter) {
+        const uint32_t e = (cbp_word >> (16 * (cbp & 1))) & 0xFFFFu;                    // d_cbp_code[cbp]
+        uint32_t nsym4 = ((uint32_t)-cbp >> 31) << 2;   // pattern 0 (motion vector only) has no code, and a raw symbol needs a length
+        const uint32_t eob = (uint32_t)vgpr_const((int)sym_raw(2u, 2u, true));
+        const uint32_t sym_base = lds_off(s_sym);
 #pragma unroll
-            for (int t = 0; t < 6; ++t)
-                if ((cbp >> (5 - t)) & 1) nsym4 = vlc_tile_symbols_inter(s_zig[slot_of_tile(t)], sym_base, lane, lane_pos, nsym4, eob);
-            if (lane == 0) s_sym[0] = sym_raw(e >> 8, e & 255u, true);
-            nsym = nsym4 >> 2;
-        } else {
-            if (lane == 0) s_sym[-1] = sym_raw(1u, 0u, false);  // the symbol "before" the first one: a block start
-            uint32_t nsym4 = 0;
-            const uint32_t eob = (uint32_t)vgpr_const((int)sym_raw(2u, 2u, false));
-            const uint32_t sym_base = lds_off(s_sym);
+        for (int t = 0; t < 6; ++t)
+            if ((cbp >> (5 - t)) & 1) nsym4 = vlc_tile_symbols_inter(s_zig[slot_of_tile(t)], sym_base, lane, lane_pos, nsym4, eob);
+        if (lane == 0) s_sym[0] = sym_raw(e >> 8, e & 255u, true);
+        nsym = nsym4 >> 2;
+    } else {
+        if (lane == 0) s_sym[-1] = sym_raw(1u, 0u, false);  // the symbol "before" the first one: a block start
+        uint32_t nsym4 = 0;
+        const uint32_t eob = (uint32_t)vgpr_const((int)sym_raw(2u, 2u, false));
+        const uint32_t sym_base = lds_off(s_sym);
 #pragma unroll
-            for (int t = 0; t < 6; ++t) {
-                if (t == 4) idxB = nsym4 >> 2;
-                if (t == 5) idxC = nsym4 >> 2;
-                nsym4 = vlc_tile_symbols_intra(s_zig[slot_of_tile(t)], sym_base, lane, lane_pos, nsym4, eob, dcs[t], t ? dcs[t - 1] : 0, t >= 1 && t <= 3,
-                                               ltab2 - 1024 + kConstDcLuma);
-            }
-            nsym = nsym4 >> 2;
+        for (int t = 0; t < 6; ++t) {
+            if (t == 4) idxB = nsym4 >> 2;
+            if (t == 5) idxC = nsym4 >> 2;
+            nsym4 = vlc_tile_symbols_intra(s_zig[slot_of_tile(t)], sym_base, lane, lane_pos, nsym4, eob, dcs[t], t ? dcs[t - 1] : 0, t >= 1 && t <= 3,
+                                           ltab2 - 1024 + kConstDcLuma);
         }
+        nsym = nsym4 >> 2;
     }
     M2V_WAVE_SYNC();
     // front half of pass 2 for symbol i: the symbol and, for a {run, level} one, its table entry (left in the load's register: anything
@@ -1788,7 +1706,6 @@ __global__ __launch_bounds__(64, 8) void k_mb(const FrameJob *__restrict__ jobs,
         M2V_WAVE_SYNC();
     }
 
-    M2V_STOP(6);            // everything but the second half of the entropy coder
     {
         // clear what pass 2 can reach: a symbol is at most 26 bits (typically 25 symbols: ONE store of 64 words instead of five
         // predicated ones over the whole 304-word buffer); the first 64 words always, they are what a compact slot copies out
@@ -1863,7 +1780,7 @@ __global__ __launch_bounds__(64, 8) void k_mb(const FrameJob *__restrict__ jobs,
                 // write-through costs 16 %; here it is 9 of a strip's 24 rows' worth of one macroblock row in sixteen.
                 auto st = [&](uint8_t *base, uint32_t off, uint32_t v) {
                     typedef __attribute__((address_space(1))) unsigned int *gu32p;
-                    if (PEER && !(kDebug && (g.ablate & (1 << 22)))) __hip_atomic_store((gu32p)(base + off), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    if (PEER) __hip_atomic_store((gu32p)(base + off), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                     else *(gst32)(base + off) = v;
                 };
                 const bool put_u = halo_up != nullptr && by == g.edge_top, put_d = halo_down != nullptr && by == g.edge_bot;     // wave-uniform
@@ -1879,7 +1796,7 @@ __global__ __launch_bounds__(64, 8) void k_mb(const FrameJob *__restrict__ jobs,
                     if (put_u || put_d) {
                         typedef __attribute__((address_space(1))) unsigned int *gu32p;
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // every store of this wavefront has left (one wavefront per block)
-                        if (lane == 0 && !(kDebug && (g.ablate & (1 << 23)))) {
+                        if (lane == 0) {
                             const uint32_t slot = (uint32_t)job.hidx * (uint32_t)kPeerCntStride;
                             if (put_u) __hip_atomic_fetch_add((gu32p)(ps.cnt_up + slot), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                             if (put_d) __hip_atomic_fetch_add((gu32p)(ps.cnt_down + slot), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

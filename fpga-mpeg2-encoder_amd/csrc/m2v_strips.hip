@@ -677,7 +677,7 @@ static int strip_launch(m2v_enc *e, StripFlight &F, const StripEncodeArgs &args,
 
     // ---- plan and buffers.  Everything up to here was the same on every rank; from here on a failure is this rank's alone and
     //      must not break the collective call order (see the head of this section) ----
-    if (kDebug && (e->ablate & (1 << 21))) { F.fail = M2V_E_HIP; F.fail_text = "injected failure (ablate bit 21)"; }    // -DM2V_DEBUG: the failure protocol under test
+    if (kDebug && e->inject_strip_failure) { F.fail = M2V_E_HIP; F.fail_text = "injected failure"; }    // -DM2V_DEBUG: the failure protocol under test
     // a bad output buffer is the output rank's alone to know: a local failure like any other (the other ranks are told through the
     // size table, nobody is left waiting in an exchange); with one rank it is simply the answer
     if (rank == a->dst && (!a->d_out || ((uintptr_t)a->d_out & 15u) != 0)) {

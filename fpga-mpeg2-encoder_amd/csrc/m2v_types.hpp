@@ -7,8 +7,8 @@
 namespace m2v {
 
 // -DM2V_DEBUG builds libm2v_mi355x_dbg.so, the library the stage-level parity tests and the profiling scripts load:
-// it can dump the quantised levels, keep every frame's reconstruction (option "keep_recon") and skip kernel phases
-// (option "ablate").  The shipped library has none of that code in its kernels.
+// it can dump the quantised levels and keep every frame's reconstruction (option "keep_recon").  The shipped library
+// has none of that code in its kernels.
 #ifdef M2V_DEBUG
 constexpr bool kDebug = true;
 #else
@@ -29,8 +29,6 @@ struct Geom {
     uint32_t rysz;   // bytes of the luma tiles of a reconstruction: (mbw + 1) * mbh * 256 (the chroma tiles follow; m2v_kernels.hpp, rec_luma_off)
     int row0, row1;  // macroblock rows this GPU encodes: [0, mbh) normally, a strip in multi-GPU strip mode
     int strip;       // 1 = strip mode: the stream buffer holds only this strip's slices, no headers
-    int ablate;      // M2V_DEBUG builds only: profiling aid (option "ablate", default 0 = everything on; results are INVALID otherwise):
-                     // bit0 skip full-pel search, bit1 skip half-pel SADs, bit2 skip VLC, bit3 skip IDCT/recon, bit4 skip DCT/quant
     uint32_t strip_mbs;      // (row1 - row0) * mbw
     uint32_t magic_strip;    // floor(2^32 / strip_mbs), floor(2^32 / mbw): wave-uniform divisions on the scalar unit
     uint32_t magic_mbw;      // (geom_finish() fills the three after any change of the rows)

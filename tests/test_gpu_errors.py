@@ -115,11 +115,20 @@ def test_create_failure_reports_text_without_a_handle():
     assert b"XL" in L.m2v_last_error(None)
     assert not L.m2v_create(6, 6, 3, 2, 99, ctypes.byref(err)) and err.value == -2
     assert b"device" in L.m2v_last_error(None)
-    # the shipped library has no profiling / dump switches
+    # the shipped library has no profiling / dump / fault-injection switches
     enc = M.Mpeg2Encoder(6, 6, 3, 2)
     try:
         assert L.m2v_set_option(enc._h, b"ablate", 1) == -1 and L.m2v_set_option(enc._h, b"keep_recon", 1) == -1
         assert b"unknown option" in L.m2v_last_error(enc._h)
+        assert L.m2v_set_option(enc._h, b"inject_strip_failure", 1) == -1
+        assert b"unknown option" in L.m2v_last_error(enc._h)
+    finally:
+        enc.close()
+    # ... and the debug library has no phase switches either
+    enc = M.Mpeg2Encoder(6, 6, 3, 2, debug=True)
+    try:
+        assert enc._L.m2v_set_option(enc._h, b"ablate", 1) == -1
+        assert b"unknown option" in enc._L.m2v_last_error(enc._h)
     finally:
         enc.close()
 

@@ -364,7 +364,7 @@ def test_a_rank_whose_own_work_fails_with_the_peer_transport():
                 if r == 0:
                     nbs[0] = nb.value
             if bad is not None:
-                encs[bad].set_option("ablate", 1 << 21)
+                encs[bad].set_option("inject_strip_failure", 1)
             th = [threading.Thread(target=work, args=(r,)) for r in range(3)]
             for t in th:
                 t.start()
@@ -372,7 +372,7 @@ def test_a_rank_whose_own_work_fails_with_the_peer_transport():
                 t.join(timeout=60)
             assert not any(t.is_alive() for t in th), "a rank is still waiting"
             if bad is not None:
-                encs[bad].set_option("ablate", 0)
+                encs[bad].set_option("inject_strip_failure", 0)
             return rc, msg, nbs[0]
         rc, msg, _ = run(1)
         assert rc[1] < 0 and b"injected failure" in msg[1]

@@ -299,7 +299,7 @@ def test_a_rank_whose_own_work_fails_keeps_the_call_order_and_everybody_returns_
             if r == 0:
                 rc.append(nb.value)
         if bad is not None:
-            encs[bad].set_option("ablate", 1 << 21)
+            encs[bad].set_option("inject_strip_failure", 1)
         th = [threading.Thread(target=work, args=(r,)) for r in range(3)]
         for t in th:
             t.start()
@@ -307,7 +307,7 @@ def test_a_rank_whose_own_work_fails_keeps_the_call_order_and_everybody_returns_
             t.join(timeout=60)
         assert not any(t.is_alive() for t in th), "a rank is still waiting"
         if bad is not None:
-            encs[bad].set_option("ablate", 0)
+            encs[bad].set_option("inject_strip_failure", 0)
         return rc, msg
     comm = M.StripComm.local(3, debug=True)
     try:
