@@ -40,6 +40,10 @@ EXPORTS = [
     "m2v_strip_encode_begin", "m2v_strip_encode_end",
 ]
 
+# the 4:2:0 entry points (kept apart: tests/test_abi.py matches EXPORTS against names of letters and underscores only)
+EXPORTS_420 = ["m2v_push_frames420", "m2v_push_frames420_pull", "m2v_encode_resident420", "m2v_encode_resident420_begin"]
+LAYOUTS_420 = {"i420": 0, "yv12": 1, "nv12": 2, "nv21": 3}          # M2V_420_*
+
 PEER_DESC_BYTES = 128          # M2V_PEER_DESC_BYTES
 
 
@@ -144,6 +148,11 @@ def lib(debug=False):
             L.m2v_device_pci_bus_id.argtypes = [ci, ctypes.c_char_p, sz]
             L.m2v_strip_encode_begin.argtypes = [vp, vp, ci, ci, ci, u32, u32, u32, vp, sz, vp, sz, vp]
             L.m2v_strip_encode_end.argtypes = [vp, ctypes.POINTER(sz)]
+            L.m2v_push_frames420.argtypes = [vp, u32, u32, u32, vp, sz, ci]
+            L.m2v_push_frames420_pull.restype = ctypes.c_longlong
+            L.m2v_push_frames420_pull.argtypes = [vp, u32, u32, u32, vp, sz, ci, vp, sz, ctypes.POINTER(ci)]
+            L.m2v_encode_resident420.argtypes = [vp, u32, u32, u32, vp, sz, ci, vp, sz, ctypes.POINTER(sz), vp]
+            L.m2v_encode_resident420_begin.argtypes = [vp, u32, u32, u32, vp, sz, ci, vp, sz, vp]
         except AttributeError:
             # an OLDER build handed in through M2V_LIB for a same-box A/B (tools/ab.sh) may lack the newer entry points; the library of
             # this tree must have every one of them (tests/test_abi.py)
@@ -162,6 +171,44 @@ def device_pci_bus_id(device=0):
     buf = ctypes.create_string_buffer(64)
     n = lib().m2v_device_pci_bus_id(int(device), buf, 64)
     return buf.value.decode() if n > 0 else None
+
+
+def _layout420(layout):
+    """a name of LAYOUTS_420 or an M2V_420_* code -> the code (unknown codes pass through: the library answers M2V_E_PARAM)"""
+    return LAYOUTS_420[layout] if isinstance(layout, str) else int(layout)
+
+
+def to444(frames420, W, H, layout="i420"):
+    """4:2:0 frames (uint8, W*H*3/2 bytes each) -> planar 4:4:4 [n, 3, H, W] with every chroma sample repeated 2 x 2: the frames
+    whose stream a 4:2:0 encode equals by definition (include/m2v_mi355x.h).  numpy, host side: a reference, not a fast path."""
+    code = _layout420(layout)
+    f = np.ascontiguousarray(frames420, np.uint8).reshape(-1, W * H * 3 // 2)
+    n, c = f.shape[0], W * H // 4
+    if code < 2:
+        a, b = f[:, W * H:W * H + c], f[:, W * H + c:]
+    else:
+        uv = f[:, W * H:].reshape(n, c, 2)
+        a, b = uv[:, :, 0], uv[:, :, 1]
+    u, v = (a, b) if code in (0, 2) else (b, a)
+    out = np.empty((n, 3, H, W), np.uint8)
+    out[:, 0] = f[:, :W * H].reshape(n, H, W)
+    for k, p in ((1, u), (2, v)):
+        out[:, k] = p.reshape(n, H // 2, W // 2).repeat(2, axis=1).repeat(2, axis=2)
+    return out
+
+
+def to420(frames444, layout="i420"):
+    """planar 4:4:4 [n, 3, H, W] -> 4:2:0 frames [n, W*H*3/2] by the module's own down-conversion: mean2 = (a + b + 1) >> 1 over
+    horizontal pairs, then over vertical pairs (RTL:1086-1089, 1167-1170).  to420(to444(x, l), l) == x."""
+    code = _layout420(layout)
+    f = np.asarray(frames444, np.uint8)
+    n, _, H, W = f.shape
+    c = f[:, 1:].astype(np.uint16)
+    h = (c[..., 0::2] + c[..., 1::2] + 1) >> 1
+    d = ((h[..., 0::2, :] + h[..., 1::2, :] + 1) >> 1).astype(np.uint8).reshape(n, 2, -1)
+    a, b = (d[:, 0], d[:, 1]) if code in (0, 2) else (d[:, 1], d[:, 0])
+    chroma = np.concatenate([a, b], axis=1) if code < 2 else np.stack([a, b], axis=2).reshape(n, -1)
+    return np.concatenate([f[:, 0].reshape(n, -1), chroma], axis=1)
 
 
 def clamp_geometry(xsize16, ysize16, XL=7, YL=7):
@@ -259,6 +306,26 @@ class Mpeg2Encoder:
                                                    dst.ctypes.data + offset, (dst.size - offset) & ~31, ctypes.byref(last)), "m2v_push_frames_pull")
         return n, bool(last.value)
 
+    def push_frames420(self, xsize16, ysize16, pframes_count, frames420, layout="i420"):
+        """m2v_push_frames420: whole 4:2:0 frames (W*H*3/2 bytes each) in one of LAYOUTS_420"""
+        W, H = self.geometry(xsize16, ysize16)
+        f = self._flat_u8(frames420)
+        assert f.size % (W * H * 3 // 2) == 0
+        self._chk(self._L.m2v_push_frames420(self._h, xsize16, ysize16, pframes_count, f.ctypes.data, f.size // (W * H * 3 // 2),
+                                             _layout420(layout)), "m2v_push_frames420")
+
+    def push_frames420_pull(self, xsize16, ysize16, pframes_count, frames420, dst, offset=0, layout="i420"):
+        """m2v_push_frames420_pull: push_frames420 + pull_into(dst, offset) in one call -> (bytes written, last)"""
+        W, H = self.geometry(xsize16, ysize16)
+        f = self._flat_u8(frames420)
+        assert f.size % (W * H * 3 // 2) == 0
+        assert dst.dtype == np.uint8 and dst.flags["C_CONTIGUOUS"]
+        last = ctypes.c_int(0)
+        n = self._chk(self._L.m2v_push_frames420_pull(self._h, xsize16, ysize16, pframes_count, f.ctypes.data, f.size // (W * H * 3 // 2),
+                                                      _layout420(layout), dst.ctypes.data + offset, (dst.size - offset) & ~31,
+                                                      ctypes.byref(last)), "m2v_push_frames420_pull")
+        return n, bool(last.value)
+
     def upload_wait(self):
         """option direct_upload = 2: returns when every frame handed to push_frames so far has been read"""
         self._chk(self._L.m2v_upload_wait(self._h), "m2v_upload_wait")
@@ -297,9 +364,15 @@ class Mpeg2Encoder:
                 break
         return b"".join(out)
 
-    def encode(self, frames444, xsize16, ysize16, pframes_count, nbeats=None):
-        """One whole sequence from host memory through the beat interface; returns the stream bytes."""
+    def encode(self, frames444, xsize16, ysize16, pframes_count, nbeats=None, layout=None):
+        """One whole sequence from host memory through the beat interface; returns the stream bytes.
+        layout (a name of LAYOUTS_420): `frames444` holds whole 4:2:0 frames instead."""
         W, H = self.geometry(xsize16, ysize16)
+        if layout is not None:
+            assert nbeats is None, "there are no 4:2:0 beats"
+            self.push_frames420(xsize16, ysize16, pframes_count, frames444, layout)
+            self.sequence_stop()
+            return self.pull_all()
         f = np.ascontiguousarray(frames444, np.uint8).reshape(-1, 3, H * W)
         bpf = W * H // 4
         total = f.shape[0] * bpf if nbeats is None else nbeats
@@ -324,6 +397,18 @@ class Mpeg2Encoder:
         """enqueue a whole sequence and return; encode_resident_end() waits for it and returns the byte count"""
         self._chk(self._L.m2v_encode_resident_begin(self._h, xsize16, ysize16, pframes_count, d_frames_ptr, nframes, d_out_ptr, cap,
                                                     stream), "m2v_encode_resident_begin")
+
+    def encode_resident420(self, d_frames_ptr, nframes, d_out_ptr, cap, xsize16, ysize16, pframes_count, layout="i420", stream=0):
+        """m2v_encode_resident420: `nframes` 4:2:0 frames at a 16-byte aligned device pointer"""
+        n = ctypes.c_size_t(0)
+        self._chk(self._L.m2v_encode_resident420(self._h, xsize16, ysize16, pframes_count, d_frames_ptr, nframes, _layout420(layout),
+                                                 d_out_ptr, cap, ctypes.byref(n), stream), "m2v_encode_resident420")
+        return n.value
+
+    def encode_resident420_begin(self, d_frames_ptr, nframes, d_out_ptr, cap, xsize16, ysize16, pframes_count, layout="i420", stream=0):
+        """enqueue a whole 4:2:0 sequence and return; encode_resident_end() waits for it and returns the byte count"""
+        self._chk(self._L.m2v_encode_resident420_begin(self._h, xsize16, ysize16, pframes_count, d_frames_ptr, nframes,
+                                                       _layout420(layout), d_out_ptr, cap, stream), "m2v_encode_resident420_begin")
 
     def encode_resident_end(self):
         n = ctypes.c_size_t(0)

@@ -486,7 +486,7 @@ void m2v_destroy(m2v_enc *e)
     (void)hipGetLastError();            // (a caller's stream that no longer exists: tolerated above, and not left behind as HIP's last error)
     e->d_coef.release(); e->d_mbaux.release(); e->d_slots.release(); e->d_slots_small.release(); e->d_mbinfo.release(); e->d_mblen.release();
     e->d_slice_bytes.release(); e->d_slice_off.release(); e->d_frame_off.release();
-    e->d_jobs.release(); e->d_lists.release(); e->d_joblist.release(); e->d_ctl.release(); e->d_segs.release();
+    e->d_jobs.release(); e->d_lists.release(); e->d_joblist.release(); e->d_ctl.release(); e->d_segs.release(); e->d_x444.release();
     for (auto p : e->rec_pool) (void)hipFree(p);
     for (auto &c : e->mbmaps) { if (c.ev) (void)hipEventDestroy(c.ev); c.d.release(); }
     for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
@@ -655,6 +655,14 @@ struct DebugArgs { int what; void *dst; size_t cap; long long ret; };
 static int debug_impl(m2v_enc *e, void *argp)
 {
     auto *a = (DebugArgs *)argp;
+    if (a->what == 4) {
+        // the expanded input of the last m2v_encode_resident420 call's last chunk, as its kernels read it
+        if (e->resident_inflight || !e->x444_bytes) { e->set_err("m2v_debug_read(4): no completed m2v_encode_resident420 call"); return M2V_E_STATE; }
+        if (e->x444_bytes > a->cap) return M2V_E_OVERFLOW;
+        HIPCHK(hipMemcpy(a->dst, e->d_x444.p, e->x444_bytes, hipMemcpyDeviceToHost));
+        a->ret = (long long)e->x444_bytes;
+        return M2V_OK;
+    }
     const Geom &g = e->g;
     const size_t nmb = e->dbg_frames * (size_t)g.mbs;
     const void *src = nullptr;

@@ -5,7 +5,8 @@
 //                     has to come from there)
 //   m2v_core.hip      handle life cycle, options, geometry (RTL:985-1006), the chunk plan (GOP segments, reconstruction slots, launch
 //                     lists) and its execution: plan_chunk -> run_step* -> finish_chunk
-//   m2v_port.hip      the port path: beats in (RTL:1027-1095), 32-byte words out (RTL:2961-2994), double-buffered staging
+//   m2v_port.hip      the port path: beats in (RTL:1027-1095), 32-byte words out (RTL:2961-2994), double-buffered staging; the input
+//                     conversions in front of a chunk (k_unpack444, k_expand420: no device globals, so they can live here)
 //   m2v_resident.hip  whole sequences resident in HBM (what bench.py times), one or several per call
 //   m2v_strips.hip    strip mode (BASELINE config c5) and the communicators of m2v_comm.hpp
 #pragma once
@@ -109,7 +110,8 @@ struct m2v_enc {
         // Frames that arrived as PACKED 4:4:4 samples (m2v_push_packed) keep the caller's byte order until they are on the device: one
         // linear run of bytes per chunk, frame after frame in arrival order, staged in pinned memory (or uploaded straight from
         // page-locked caller memory) and de-interleaved into d_in by k_unpack444 in front of the chunk's kernels
-        struct PkFrame { uint32_t frame; int layout; size_t off; };       // chunk frame index, M2V_PACKED_*, where its bytes start in h_pk / d_pk
+        // Whole 4:2:0 frames (m2v_push_frames420) are one more kind of run in the same bytes: kPk420 + M2V_420_*, expanded by k_expand420
+        struct PkFrame { uint32_t frame; int layout; size_t off; };       // chunk frame index, M2V_PACKED_* or kPk420 + M2V_420_*, where its bytes start in h_pk / d_pk
         std::vector<PkFrame> pk;
         uint8_t *h_pk = nullptr;              // pinned staging (only when packed beats come from ordinary memory)
         size_t h_pk_cap = 0;
@@ -235,6 +237,10 @@ struct m2v_enc {
     int strip_graph_opt = -1;
     struct StripStats { double halo_total_ms = 0, halo_exposed_ms = 0, gather_ms = 0, host_us_per_step = 0, comm_us_per_step = 0; int steps = 0; int graph = 0; int peer = 0; } strip_stats;
 
+    // m2v_encode_resident420: the chunk's frames expanded to planar 4:4:4 in front of its kernels (no recording references the buffer)
+    DevBuf<uint8_t> d_x444;
+    size_t x444_bytes = 0;                // ... what the last call's last chunk left there (m2v_debug_read, what = 4)
+
     // debug bookkeeping of the last resident encode
     size_t dbg_frames = 0;
     std::vector<int> dbg_rec_slot;
@@ -324,6 +330,14 @@ struct Timer {
         }
     }
 };
+
+// ---- m2v_port.hip ----
+// PkFrame::layout of a 4:2:0 frame is kPk420 + M2V_420_*
+constexpr int kPk420 = 16;
+inline bool layout420_ok(int layout) { return layout >= M2V_420_I420 && layout <= M2V_420_NV21; }
+// nframes 4:2:0 frames (ysz * 3 / 2 bytes each, back to back at src) -> planar 4:4:4 frames of 3 * ysz bytes at dst, every chroma
+// sample repeated 2 x 2 (k_expand420).  src and dst 16-byte aligned.
+void launch_expand420(hipStream_t s, int layout, const uint8_t *src, uint8_t *dst, const Geom &g, uint32_t nframes);
 
 // ---- m2v_strips.hip ----
 void strip_flight_release(m2v_enc *e);

@@ -145,6 +145,72 @@ void launch_unpack(hipStream_t s, int layout, const uint8_t *src, uint8_t *dst, 
     HIPCHK(hipGetLastError());
 }
 
+// source bytes of one frame of a run kind (PkFrame::layout): ysz * bytes per pixel, 1.5 for 4:2:0
+size_t pk_frame_bytes(int layout, uint32_t ysz)
+{
+    PackedFmt f{};
+    if (packed_fmt(layout, f)) return (size_t)ysz * (size_t)f.stride;
+    return (size_t)ysz + (ysz >> 1);
+}
+
+// 4:2:0 frames -> the three full-size planes of the chunk's frames, every chroma sample repeated 2 x 2 (the module's own two-stage mean2
+// of RTL:1086-1089, 1167-1170 then returns the caller's chroma: mean2(a, a) = a).  One lane per 16 output pixels of a row PAIR 2j, 2j + 1:
+// two 16-byte luma copies; the 8 U + 8 V source samples doubled in registers (v_perm_b32) and stored to both rows of either plane.
+// SEMI = false: I420 / YV12, 8-byte loads from the two chroma planes - a row of W / 2 bytes starts 8-byte aligned only (W is a multiple
+// of 16, not of 32); SEMI = true: NV12 / NV21, one 16-byte load of U V U V ...  VFIRST: the first plane / the even bytes are V.
+// src: frames of ysz * 3 / 2 bytes back to back; dst: frames of 3 * ysz bytes.  Every store 16-byte aligned (frame and plane sizes are
+// multiples of 128).  HBM traffic 1.5 + 3 bytes per pixel.
+template <bool SEMI, bool VFIRST>
+__global__ __launch_bounds__(256) void k_expand420(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, uint32_t W, uint32_t ysz, uint32_t nframes)
+{
+    const uint32_t cols = W >> 4, items = ysz >> 5;         // 16-pixel columns of a row; (H / 2) * cols row pairs x columns
+    auto dbl = [](uint32_t w, uint32_t sel) { return __builtin_amdgcn_perm(w, w, sel); };
+    for (uint32_t f = blockIdx.y; f < nframes; f += gridDim.y) {
+        const uint8_t *sf = src + (size_t)f * ((size_t)ysz + (ysz >> 1));
+        uint8_t *df = dst + (size_t)f * ysz * 3;
+        for (uint32_t t = blockIdx.x * 256u + threadIdx.x; t < items; t += gridDim.x * 256u) {
+            const uint32_t j = t / cols, c = t - j * cols;
+            const size_t o = (size_t)(2 * j) * W + (size_t)c * 16;          // row 2j, column 16c of a full-size plane
+            const uint4 y0 = *(const uint4 *)(sf + o), y1 = *(const uint4 *)(sf + o + W);
+            uint4 p0, p1;                                                   // first / second chroma component of the layout, doubled
+            if (SEMI) {
+                const uint4 q = *(const uint4 *)(sf + ysz + (size_t)j * W + (size_t)c * 16);
+                p0 = make_uint4(dbl(q.x, 0x02020000u), dbl(q.y, 0x02020000u), dbl(q.z, 0x02020000u), dbl(q.w, 0x02020000u));
+                p1 = make_uint4(dbl(q.x, 0x03030101u), dbl(q.y, 0x03030101u), dbl(q.z, 0x03030101u), dbl(q.w, 0x03030101u));
+            } else {
+                const uint8_t *cp = sf + ysz + (size_t)j * (W >> 1) + (size_t)c * 8;
+                const uint2 a = *(const uint2 *)cp, b = *(const uint2 *)(cp + (ysz >> 2));
+                p0 = make_uint4(dbl(a.x, 0x01010000u), dbl(a.x, 0x03030202u), dbl(a.y, 0x01010000u), dbl(a.y, 0x03030202u));
+                p1 = make_uint4(dbl(b.x, 0x01010000u), dbl(b.x, 0x03030202u), dbl(b.y, 0x01010000u), dbl(b.y, 0x03030202u));
+            }
+            uint8_t *du = df + ysz + o, *dv = df + 2 * (size_t)ysz + o;
+            *(uint4 *)(df + o) = y0;
+            *(uint4 *)(df + o + W) = y1;
+            *(uint4 *)du = VFIRST ? p1 : p0;
+            *(uint4 *)(du + W) = VFIRST ? p1 : p0;
+            *(uint4 *)dv = VFIRST ? p0 : p1;
+            *(uint4 *)(dv + W) = VFIRST ? p0 : p1;
+        }
+    }
+}
+
+}  // namespace
+
+void launch_expand420(hipStream_t s, int layout, const uint8_t *src, uint8_t *dst, const Geom &g, uint32_t nframes)
+{
+    const uint32_t W = (uint32_t)g.W, ysz = g.ysz;
+    const dim3 grid(std::min<uint32_t>(((ysz >> 5) + 255u) / 256u, 1024u), std::min<uint32_t>(nframes, 32768u)), block(256);
+    switch (layout) {
+    case M2V_420_I420: hipLaunchKernelGGL((k_expand420<false, false>), grid, block, 0, s, src, dst, W, ysz, nframes); break;
+    case M2V_420_YV12: hipLaunchKernelGGL((k_expand420<false, true>), grid, block, 0, s, src, dst, W, ysz, nframes); break;
+    case M2V_420_NV12: hipLaunchKernelGGL((k_expand420<true, false>), grid, block, 0, s, src, dst, W, ysz, nframes); break;
+    default: hipLaunchKernelGGL((k_expand420<true, true>), grid, block, 0, s, src, dst, W, ysz, nframes); break;
+    }
+    HIPCHK(hipGetLastError());
+}
+
+namespace {
+
 // The blocking call's wait for its direct uploads.  An event behind the last transfer (flush_buffered records one for the chunk's kernels)
 // is waited for ITSELF: the wait for the upload stream behind such an event takes ~30 us longer than the transfer, the wait for the event
 // ~15 (tools/ubench/h2d_kernel.hip; the event carries no system fence - an upload leaves nothing to release to the host).  Without an event
@@ -265,12 +331,14 @@ void flush_buffered(m2v_enc *e, bool last)
     if (!h.pk.empty()) {
         timer_break(e);
         for (size_t a = 0; a < h.pk.size();) {          // runs of consecutive frames of one layout: one launch each
-            PackedFmt f{};
-            packed_fmt(h.pk[a].layout, f);
+            const int layout = h.pk[a].layout;
+            const size_t src_bytes = pk_frame_bytes(layout, g.ysz);
             size_t b = a + 1;
-            while (b < h.pk.size() && h.pk[b].layout == h.pk[a].layout && h.pk[b].frame == h.pk[a].frame + (b - a) &&
-                   h.pk[b].off == h.pk[a].off + (b - a) * (size_t)g.ysz * (size_t)f.stride) ++b;
-            launch_unpack(s, h.pk[a].layout, h.d_pk.p + h.pk[a].off, h.d_in.p + (size_t)h.pk[a].frame * frame_bytes, g.ysz, (uint32_t)(b - a));
+            while (b < h.pk.size() && h.pk[b].layout == layout && h.pk[b].frame == h.pk[a].frame + (b - a) &&
+                   h.pk[b].off == h.pk[a].off + (b - a) * src_bytes) ++b;
+            uint8_t *to = h.d_in.p + (size_t)h.pk[a].frame * frame_bytes;
+            if (layout >= kPk420) launch_expand420(s, layout - kPk420, h.d_pk.p + h.pk[a].off, to, g, (uint32_t)(b - a));
+            else launch_unpack(s, layout, h.d_pk.p + h.pk[a].off, to, g.ysz, (uint32_t)(b - a));
             a = b;
         }
         h.pk.clear();
@@ -370,13 +438,13 @@ static bool page_locked_range(const void *p, size_t bytes)
 }
 
 // room for `bytes` more packed bytes in the stage being filled; false = the chunk has to leave first (a layout of more bytes per pixel
-// than the one the buffers were sized for arrived in the middle of a chunk)
-static bool pk_room(m2v_enc *e, m2v_enc::HostStage &h, size_t bytes, int stride)
+// than the one the buffers were sized for arrived in the middle of a chunk).  frame_bytes: one frame of the arriving kind
+static bool pk_room(m2v_enc *e, m2v_enc::HostStage &h, size_t bytes, size_t frame_bytes)
 {
     if (h.pk_used + bytes <= h.d_pk.n) return true;
     if (h.pk_used != 0) return false;
     h.d_pk.recorded = false;
-    h.d_pk.ensure(std::max(e->batch_frames * (size_t)e->g.ysz * (size_t)stride, bytes));
+    h.d_pk.ensure(std::max(e->batch_frames * frame_bytes, bytes));
     return true;
 }
 
@@ -441,7 +509,7 @@ static int push_beats_impl(m2v_enc *e, void *argp)
             const size_t fbytes = (size_t)g.ysz * (size_t)sf.stride;
             const size_t whole = std::min((a->n - i) / bpf, e->batch_frames - e->buffered);
             const size_t nfr = std::max<size_t>(whole, 1);
-            if (!pk_room(e, h, nfr * fbytes, sf.stride)) { flush_buffered(e, false); continue; }      // (pk_used != 0: complete frames are buffered)
+            if (!pk_room(e, h, nfr * fbytes, fbytes)) { flush_buffered(e, false); continue; }      // (pk_used != 0: complete frames are buffered)
             for (size_t k = 0; k < nfr; ++k) h.pk.push_back({(uint32_t)(e->buffered + k), src.kind - 1, h.pk_used + k * fbytes});
             e->cur_kind = src.kind;
             e->cur_pk_off = h.pk_used;
@@ -555,7 +623,8 @@ int m2v_push_packed(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pfr
     return guard(e, push_beats_impl, &a);
 }
 
-struct PushFramesArgs { uint32_t xs, ys, pf; const uint8_t *frames; size_t n; PullSink *sink; };
+// layout < 0: planar 4:4:4 frames (into h_in / d_in); M2V_420_*: 4:2:0 frames, which travel as one more kind of packed run (h_pk / d_pk)
+struct PushFramesArgs { uint32_t xs, ys, pf; const uint8_t *frames; size_t n; PullSink *sink; int layout = -1; };
 
 static int push_frames_impl(m2v_enc *e, void *argp)
 {
@@ -572,7 +641,8 @@ static int push_frames_impl(m2v_enc *e, void *argp)
     if (e->state == m2v_enc::ENDED || a->n == 0) { settle_deferred(); return M2V_OK; }
     if (e->state == m2v_enc::IDLE) start_sequence(e, a->xs, a->ys, a->pf);
     const Geom &g = e->g;
-    const size_t fb = (size_t)g.ysz * 3;
+    const bool is420 = a->layout >= 0;
+    const size_t fb = is420 ? pk_frame_bytes(kPk420 + a->layout, g.ysz) : (size_t)g.ysz * 3;      // the caller's bytes per frame
     if (e->beat_pos != 0) {
         settle_deferred();
         e->set_err("m2v_push_frames: a frame is partially filled by m2v_push_beats");
@@ -594,11 +664,28 @@ static int push_frames_impl(m2v_enc *e, void *argp)
     for (size_t k = 0; k < a->n;) {
         m2v_enc::HostStage &h = e->st();
         const size_t take = std::min(a->n - k, e->batch_frames - e->buffered);
+        size_t pk_off = 0;
+        if (is420) {
+            // (the packed bytes of the chunk are full - another kind of run sized them: the chunk leaves first; pk_used != 0 means
+            // complete frames are buffered)
+            if (!pk_room(e, h, take * fb, fb)) { flush_buffered(e, false); continue; }
+            pk_off = h.pk_used;
+            for (size_t j = 0; j < take; ++j) h.pk.push_back({(uint32_t)(e->buffered + j), kPk420 + a->layout, pk_off + j * fb});
+            h.pk_used += take * fb;
+            h.pk_valid = h.pk_used;
+        }
+        uint8_t *const d_to = is420 ? h.d_pk.p + pk_off : nullptr;
         if (pinned) {
-            h.d_in.ensure(e->batch_frames * fb);
-            if (h.uploaded < e->buffered)           // frames staged on the host earlier in this chunk go first
-                HIPCHK(hipMemcpyAsync(h.d_in.p + h.uploaded * fb, h.h_in + h.uploaded * fb, (e->buffered - h.uploaded) * fb,
-                                      hipMemcpyHostToDevice, e->up_stream));
+            if (is420) {
+                if (h.pk_up < pk_off)               // bytes staged on the host earlier in this chunk go first
+                    HIPCHK(hipMemcpyAsync(h.d_pk.p + h.pk_up, h.h_pk + h.pk_up, pk_off - h.pk_up, hipMemcpyHostToDevice, e->up_stream));
+                h.pk_up = pk_off + take * fb;
+            } else {
+                h.d_in.ensure(e->batch_frames * fb);
+                if (h.uploaded < e->buffered)           // frames staged on the host earlier in this chunk go first
+                    HIPCHK(hipMemcpyAsync(h.d_in.p + h.uploaded * fb, h.h_in + h.uploaded * fb, (e->buffered - h.uploaded) * fb,
+                                          hipMemcpyHostToDevice, e->up_stream));
+            }
             // (deferred completion: the calls' transfers alternate between two upload streams - the copy engine sets the next one up while
             // the running one drains, which one in-order stream does not allow; measured: one stream 47.6 GB/s, no better than blocking)
             hipStream_t ups = e->up_stream;
@@ -610,18 +697,21 @@ static int push_frames_impl(m2v_enc *e, void *argp)
                 if (!e->up_stream2) HIPCHK(hipStreamCreateWithFlags(&e->up_stream2, hipStreamNonBlocking));
                 ups = e->up_stream2;
             }
-            HIPCHK(hipMemcpyAsync(h.d_in.p + e->buffered * fb, a->frames + k * fb, take * fb, hipMemcpyHostToDevice, ups));
+            HIPCHK(hipMemcpyAsync(is420 ? d_to : h.d_in.p + e->buffered * fb, a->frames + k * fb, take * fb, hipMemcpyHostToDevice, ups));
             if (ups != e->up_stream) {
                 // the chunk's kernels (enqueued on the handle's stream by flush_buffered, possibly a few lines below) come behind these frames
                 if (!e->ev_up2) HIPCHK(hipEventCreateWithFlags(&e->ev_up2, hipEventDisableTiming));
                 HIPCHK(hipEventRecord(e->ev_up2, ups));
                 HIPCHK(hipStreamWaitEvent(e->stream, e->ev_up2, 0));
             }
-            h.uploaded = e->buffered + take;
+            if (!is420) h.uploaded = e->buffered + take;
             direct_pending = true;
             if (!e->direct_upload_deferred && ups == e->up_stream) { e->up_unsynced = true; e->up_wait_ev = nullptr; }     // (no event behind this transfer yet)
             // m2v_push_frames_pull: completed chunks leave for the caller's buffer HERE, while this call's frames cross the link
             if (a->sink) progress(e, false, -1, a->sink);
+        } else if (is420) {
+            pk_staging(h);
+            parallel_copy(h.h_pk + pk_off, a->frames + k * fb, take * fb, e->copy_threads);
         } else {
             parallel_copy(h.h_in + e->buffered * fb, a->frames + k * fb, take * fb, e->copy_threads);
         }
@@ -663,13 +753,11 @@ int m2v_push_frames(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pfr
 static long long pull_tail(m2v_enc *e, uint8_t *dst, size_t cap, const PullSink &sink, int *last);
 static int pull_progress_impl(m2v_enc *e, void *argp);
 
-long long m2v_push_frames_pull(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count, const uint8_t *frames444,
-                               size_t nframes, uint8_t *dst, size_t cap, int *last)
+static long long push_frames_pull(m2v_enc *e, PushFramesArgs a, uint8_t *dst, size_t cap, int *last)
 {
-    if (!e || (nframes && !frames444) || (!dst && cap)) return M2V_E_PARAM;
     if (last) *last = 0;
     PullSink sink{dst, cap, 0};
-    PushFramesArgs a{xsize16, ysize16, pframes_count, frames444, nframes, &sink};
+    a.sink = &sink;
     e->call_sink = &sink;
     int r = guard(e, push_frames_impl, &a);
     e->call_sink = nullptr;
@@ -691,6 +779,32 @@ long long m2v_push_frames_pull(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, u
         }
     }
     return pull_tail(e, dst, cap, sink, last);
+}
+
+long long m2v_push_frames_pull(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count, const uint8_t *frames444,
+                               size_t nframes, uint8_t *dst, size_t cap, int *last)
+{
+    if (!e || (nframes && !frames444) || (!dst && cap)) return M2V_E_PARAM;
+    return push_frames_pull(e, PushFramesArgs{xsize16, ysize16, pframes_count, frames444, nframes, nullptr}, dst, cap, last);
+}
+
+// Whole 4:2:0 frames: m2v_push_frames in everything but the bytes of a frame (W*H*3/2, half of what crosses the link otherwise) and
+// where they go - into the chunk's packed bytes, from which k_expand420 writes the planes the chunk's kernels read.
+int m2v_push_frames420(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count, const uint8_t *frames420,
+                       size_t nframes, int layout)
+{
+    if (!e || (nframes && !frames420)) return M2V_E_PARAM;
+    if (!layout420_ok(layout)) { e->set_err("m2v_push_frames420: unknown layout %d", layout); return M2V_E_PARAM; }
+    PushFramesArgs a{xsize16, ysize16, pframes_count, frames420, nframes, nullptr, layout};
+    return guard(e, push_frames_impl, &a);
+}
+
+long long m2v_push_frames420_pull(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count, const uint8_t *frames420,
+                                  size_t nframes, int layout, uint8_t *dst, size_t cap, int *last)
+{
+    if (!e || (nframes && !frames420) || (!dst && cap)) return M2V_E_PARAM;
+    if (!layout420_ok(layout)) { e->set_err("m2v_push_frames420_pull: unknown layout %d", layout); return M2V_E_PARAM; }
+    return push_frames_pull(e, PushFramesArgs{xsize16, ysize16, pframes_count, frames420, nframes, nullptr, layout}, dst, cap, last);
 }
 
 static int upload_wait_impl(m2v_enc *e, void *)

@@ -1,10 +1,11 @@
 // m2v_resident.hip — whole sequences with input and output resident in HBM (what bench.py times): m2v_encode_resident, its two
-// halves _begin / _end for callers that keep several sequences in flight.
+// halves _begin / _end for callers that keep several sequences in flight, and the same for 4:2:0 input (m2v_encode_resident420).
 #include "m2v_host.hpp"
 
 extern "C" {
 
-struct ResidentArgs { uint32_t xs, ys, pf; const uint8_t *d_in; size_t n; uint8_t *d_out; size_t cap; size_t *bytes; hipStream_t s; bool async = false; };
+struct ResidentArgs { uint32_t xs, ys, pf; const uint8_t *d_in; size_t n; uint8_t *d_out; size_t cap; size_t *bytes; hipStream_t s; bool async = false;
+                      int layout = -1; };      // layout >= 0: d_in holds 4:2:0 frames (M2V_420_*)
 
 // The resident entry in two halves: everything enqueued (m2v_encode_resident_begin), then the one wait and the byte count
 // (m2v_encode_resident_end).  m2v_encode_resident is both, back to back.
@@ -45,10 +46,25 @@ static int resident_impl(m2v_enc *e, void *argp)
     // align chunks to GOP boundaries so every chunk starts with an I frame where possible
     const size_t gop = e->pframes + 1u;
     size_t step = chunk >= gop ? chunk / gop * gop : chunk;
+    const bool is420 = a->layout >= 0;
+    const size_t fb420 = (size_t)g.ysz + (g.ysz >> 1);
+    if (is420) {
+        // each chunk's frames are expanded into planar 4:4:4 in front of its kernels, on the same stream; one buffer is enough because
+        // the chunks are synchronised below
+        e->d_x444.recorded = false;
+        e->d_x444.ensure(std::min(step, a->n) * fb);
+    }
     for (size_t k = 0; k < a->n; k += step) {
         const size_t nf = std::min(step, a->n - k);
         const bool first = k == 0, last = k + nf == a->n;
-        encode_chunk(e, s, a->d_in + k * fb, nf, first, last, g.ysz / 4, a->d_out, /*advance=*/k > 0);
+        const uint8_t *frames = is420 ? nullptr : a->d_in + k * fb;
+        if (is420) {
+            timer_break(e);
+            launch_expand420(s, a->layout, a->d_in + k * fb420, e->d_x444.p, g, (uint32_t)nf);
+            e->x444_bytes = nf * fb;
+            frames = e->d_x444.p;
+        }
+        encode_chunk(e, s, frames, nf, first, last, g.ysz / 4, a->d_out, /*advance=*/k > 0);
         if (!last) HIPCHK(hipStreamSynchronize(s));    // the per-chunk work buffers are reused
     }
     HIPCHK(hipMemcpyAsync(e->st().h_ctl, e->d_ctl.p, sizeof(StreamCtl), hipMemcpyDeviceToHost, s));
@@ -73,6 +89,29 @@ int m2v_encode_resident_begin(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, ui
     if (!e || (nframes && (!d_frames444 || !d_out))) return M2V_E_PARAM;
     ResidentArgs a{xsize16, ysize16, pframes_count, (const uint8_t *)d_frames444, nframes, (uint8_t *)d_out, cap, nullptr,
                    (hipStream_t)hip_stream, true};
+    return guard(e, resident_impl, &a);
+}
+
+// 4:2:0 frames resident in HBM: the same sequence with k_expand420 in front of every chunk
+int m2v_encode_resident420(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count, const void *d_frames420,
+                           size_t nframes, int layout, void *d_out, size_t cap, size_t *out_bytes, void *hip_stream)
+{
+    if (!e || (nframes && (!d_frames420 || !d_out))) return M2V_E_PARAM;
+    if (!layout420_ok(layout)) { e->set_err("m2v_encode_resident420: unknown layout %d", layout); return M2V_E_PARAM; }
+    if ((uintptr_t)d_frames420 & 15) { e->set_err("m2v_encode_resident420: d_frames420 must be 16-byte aligned"); return M2V_E_PARAM; }
+    ResidentArgs a{xsize16, ysize16, pframes_count, (const uint8_t *)d_frames420, nframes, (uint8_t *)d_out, cap, out_bytes,
+                   (hipStream_t)hip_stream, false, layout};
+    return guard(e, resident_impl, &a);
+}
+
+int m2v_encode_resident420_begin(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count, const void *d_frames420,
+                                 size_t nframes, int layout, void *d_out, size_t cap, void *hip_stream)
+{
+    if (!e || (nframes && (!d_frames420 || !d_out))) return M2V_E_PARAM;
+    if (!layout420_ok(layout)) { e->set_err("m2v_encode_resident420_begin: unknown layout %d", layout); return M2V_E_PARAM; }
+    if ((uintptr_t)d_frames420 & 15) { e->set_err("m2v_encode_resident420_begin: d_frames420 must be 16-byte aligned"); return M2V_E_PARAM; }
+    ResidentArgs a{xsize16, ysize16, pframes_count, (const uint8_t *)d_frames420, nframes, (uint8_t *)d_out, cap, nullptr,
+                   (hipStream_t)hip_stream, true, layout};
     return guard(e, resident_impl, &a);
 }
 

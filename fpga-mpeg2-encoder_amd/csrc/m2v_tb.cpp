@@ -1,8 +1,11 @@
 // m2v_tb — file-to-file driver over the C-ABI; the counterpart of SIM/tb_mpeg2encoder.v.
 //
 //   m2v_tb [-XL n] [-YL n] [-VL n] [-Q n] [-p pframes] [-d device] [-bubbles] [-conformant] [-ps] [-ts]
+//          [-i420 | -yv12 | -nv12 | -nv21]
 //          in.yuv W H out.m2v  [in2.yuv W2 H2 out2.m2v ...]
 //
+// -i420 / -yv12 / -nv12 / -nv21: the input files hold 4:2:0 frames of W*H*3/2 bytes in that layout (what ordinary tools write) instead
+// of the testbench's planar 4:4:4 frames; they go in through m2v_push_frames420.  At most one of the four.
 // -conformant switches the encoder's option "conformant" on (ISO reconstruction loop; NOT byte-identical to the RTL).
 // -ps / -ts additionally write out.m2v.mpg / out.m2v.ts: the same elementary stream in an MPEG-2 program / transport
 // stream (include/m2v_container.h), so the result plays in an ordinary player.
@@ -24,13 +27,17 @@
 
 int main(int argc, char **argv)
 {
-    int XL = 7, YL = 6, VL = 3, Q = 2, pf = 23, dev = 0, bubbles = 0, conformant = 0, want_ps = 0, want_ts = 0;
+    int XL = 7, YL = 6, VL = 3, Q = 2, pf = 23, dev = 0, bubbles = 0, conformant = 0, want_ps = 0, want_ts = 0, layout420 = -1, layouts = 0;
     int i = 1;
     for (; i < argc && argv[i][0] == '-'; ++i) {
         if (!strcmp(argv[i], "-bubbles")) { bubbles = 1; continue; }
         if (!strcmp(argv[i], "-conformant")) { conformant = 1; continue; }
         if (!strcmp(argv[i], "-ps")) { want_ps = 1; continue; }
         if (!strcmp(argv[i], "-ts")) { want_ts = 1; continue; }
+        if (!strcmp(argv[i], "-i420")) { layout420 = M2V_420_I420; ++layouts; continue; }
+        if (!strcmp(argv[i], "-yv12")) { layout420 = M2V_420_YV12; ++layouts; continue; }
+        if (!strcmp(argv[i], "-nv12")) { layout420 = M2V_420_NV12; ++layouts; continue; }
+        if (!strcmp(argv[i], "-nv21")) { layout420 = M2V_420_NV21; ++layouts; continue; }
         if (i + 1 >= argc) break;
         int v = atoi(argv[i + 1]);
         if (!strcmp(argv[i], "-XL")) XL = v; else if (!strcmp(argv[i], "-YL")) YL = v;
@@ -39,8 +46,8 @@ int main(int argc, char **argv)
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
         ++i;
     }
-    if ((argc - i) < 4 || (argc - i) % 4) {
-        fprintf(stderr, "usage: %s [-XL n] [-YL n] [-VL n] [-Q n] [-p pframes] [-d dev] in.yuv W H out.m2v ...\n", argv[0]);
+    if ((argc - i) < 4 || (argc - i) % 4 || layouts > 1 || (layout420 >= 0 && bubbles)) {          // (there are no 4:2:0 beats)
+        fprintf(stderr, "usage: %s [-XL n] [-YL n] [-VL n] [-Q n] [-p pframes] [-d dev] [-i420 | -yv12 | -nv12 | -nv21] in.yuv W H out.m2v ...\n", argv[0]);
         return 2;
     }
     int err = 0;
@@ -65,7 +72,7 @@ int main(int argc, char **argv)
             printf("*** ysize=%4d is invalid, which must in range [64,%4d], and must be a multiple of 16\n", ysize, 16 << YL);
             return 1;
         }
-        const size_t fb = (size_t)xsize * ysize * 3;
+        const size_t fb = layout420 >= 0 ? (size_t)xsize * ysize * 3 / 2 : (size_t)xsize * ysize * 3;
         std::vector<uint8_t> frame(fb), word(1 << 20), es;
         size_t frames = 0, bytes = 0;
         const auto t0 = std::chrono::steady_clock::now();
@@ -86,7 +93,9 @@ int main(int argc, char **argv)
         while (fread(frame.data(), 1, fb, fi) == fb) {                                         // complete frames only (TB:220)
             printf("  start to encode video %d frame %3zu\n", num_video, frames);
             int r;
-            if (!bubbles) {
+            if (layout420 >= 0) {
+                r = m2v_push_frames420(e, (uint32_t)xsize / 16, (uint32_t)ysize / 16, (uint32_t)pf, frame.data(), 1, layout420);
+            } else if (!bubbles) {
                 r = m2v_push_frames(e, (uint32_t)xsize / 16, (uint32_t)ysize / 16, (uint32_t)pf, frame.data(), 1);
             } else {                                                                           // beat-level, odd batch sizes
                 const size_t npix = (size_t)xsize * ysize;

@@ -88,6 +88,30 @@ int m2v_push_packed(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pfr
 int m2v_push_frames(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count,
                     const uint8_t *frames444, size_t nframes);
 
+/*
+ * Whole 4:2:0 frames, as decoders, cameras and ordinary .yuv files deliver them.  The module has no 4:2:0 port; the first thing it does
+ * with its 4:4:4 samples is the two-stage mean2 down-conversion (RTL:1086-1089, 1167-1170), and mean2(a, a) = a.  So by definition the
+ * stream of a 4:2:0 frame is, byte for byte, the stream of the 4:4:4 frame whose U and V planes are the 4:2:0 planes with every sample
+ * repeated 2 x 2: the encoder codes the caller's chroma, unfiltered.  W, H are the CLAMPED sizes (m2v_geometry), multiples of 16; a
+ * frame is W*H*3/2 bytes in one of these layouts:
+ */
+enum {
+    M2V_420_I420 = 0,        /* Y (W*H), U (W*H/4), V (W*H/4)                      */
+    M2V_420_YV12 = 1,        /* Y, V, U                                            */
+    M2V_420_NV12 = 2,        /* Y, then H/2 rows of W bytes U V U V ...            */
+    M2V_420_NV21 = 3         /* Y, then H/2 rows of W bytes V U V U ...            */
+};
+/*
+ * m2v_push_frames for `nframes` such frames, with every promise of it: the sizes and pframes_count are sampled on the first frame of a
+ * sequence only, frames are dropped while the previous sequence is ending, M2V_E_STATE while a frame is partly filled by m2v_push_beats,
+ * page-locked sources cross the link from where they are (option "direct_upload", 2 and m2v_upload_wait included), anything else goes
+ * through the pinned staging.  Half the bytes of the 4:4:4 form cross the link; the frames are expanded on the device in front of
+ * the chunk's kernels.  4:4:4 frames, packed beats and 4:2:0 frames may alternate inside one sequence.  M2V_E_PARAM for an unknown
+ * layout.  There are no 4:2:0 beats: half a chroma row has no meaning at the port.
+ */
+int m2v_push_frames420(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count,
+                       const uint8_t *frames420, size_t nframes, int layout);
+
 /* `i_sequence_stop` pulse with i_en = 0 (RTL:1090-1091; SIM/tb_mpeg2encoder.v:249-252). A frame
  * in progress is completed with black pixels (RTL:1048-1056). No effect while idle. */
 int m2v_sequence_stop(m2v_enc *e);
@@ -119,6 +143,10 @@ long long m2v_pull(m2v_enc *e, uint8_t *dst, size_t cap, int *last);
 long long m2v_push_frames_pull(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count,
                                const uint8_t *frames444, size_t nframes, uint8_t *dst, size_t cap, int *last);
 
+/* m2v_push_frames_pull for 4:2:0 frames (m2v_push_frames420 followed by m2v_pull into dst, in one call). */
+long long m2v_push_frames420_pull(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count,
+                                  const uint8_t *frames420, size_t nframes, int layout, uint8_t *dst, size_t cap, int *last);
+
 /* Clamped geometry the module would use for (xsize16, ysize16) (RTL:985-1006). */
 int m2v_geometry(const m2v_enc *e, uint32_t xsize16, uint32_t ysize16, int *width, int *height);
 
@@ -144,6 +172,16 @@ int m2v_encode_resident(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t
 int m2v_encode_resident_begin(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count,
                               const void *d_frames444, size_t nframes, void *d_out, size_t cap, void *hip_stream);
 int m2v_encode_resident_end(m2v_enc *e, size_t *out_bytes);
+/*
+ * The resident entries for 4:2:0 frames (M2V_420_*, W*H*3/2 bytes each, back to back at the 16-byte aligned device pointer
+ * `d_frames420`): each chunk is expanded into a planar 4:4:4 buffer the handle owns, on the call's stream in front of the chunk's
+ * kernels.  Everything else as m2v_encode_resident / m2v_encode_resident_begin; the latter is answered by m2v_encode_resident_end.
+ */
+int m2v_encode_resident420(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count,
+                           const void *d_frames420, size_t nframes, int layout, void *d_out, size_t cap,
+                           size_t *out_bytes, void *hip_stream);
+int m2v_encode_resident420_begin(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count,
+                                 const void *d_frames420, size_t nframes, int layout, void *d_out, size_t cap, void *hip_stream);
 
 /*
  * Strip mode (BASELINE config c5; no RTL counterpart — the RTL has one reference BRAM): several
@@ -377,6 +415,8 @@ int m2v_kernel_stats(const m2v_enc *e, int kernel, double *ms, double *units);
  *         1 = levels   int16  [frames][mbs][6][64] (zig-zag order)
  *         2 = mb bits  uint32 [frames][mbs]
  *         3 = recon    uint8  [frames][W*H*3/2]  (only frames that are referenced later; others 0)
+ *         4 = the expanded 4:4:4 input of the last m2v_encode_resident420 call's last chunk, uint8 [frames][3*W*H]: a plain copy of
+ *             the handle's own buffer (either library answers it; M2V_E_STATE before the first such call has completed)
  * Returns bytes copied or a negative error.
  */
 long long m2v_debug_read(m2v_enc *e, int what, void *dst, size_t cap);
