@@ -701,6 +701,7 @@ static int debug_impl(m2v_enc *e, void *argp)
             a->ret = (long long)bytes;
             return M2V_OK;
         }
+        case 5: src = e->d_mbaux.p; bytes = nmb * sizeof(MbAux); break;
         default: return M2V_E_PARAM;
     }
     if (bytes > a->cap) return M2V_E_OVERFLOW;

@@ -417,6 +417,9 @@ int m2v_kernel_stats(const m2v_enc *e, int kernel, double *ms, double *units);
  *         3 = recon    uint8  [frames][W*H*3/2]  (only frames that are referenced later; others 0)
  *         4 = the expanded 4:4:4 input of the last m2v_encode_resident420 call's last chunk, uint8 [frames][3*W*H]: a plain copy of
  *             the handle's own buffer (either library answers it; M2V_E_STATE before the first such call has completed)
+ *         5 = mb aux   uint32 [frames][mbs][4]: the record k_mb leaves next to the info word (either library).  Word 0 = bits of the
+ *             slot's first segment | second << 16, word 1 = bits of the third | DC level of V << 16, word 2 = DC levels of the first |
+ *             last luma tile << 16, word 3 = DC level of U.  The three segment lengths add up to the bits kept in the macroblock's slot.
  * Returns bytes copied or a negative error.
  */
 long long m2v_debug_read(m2v_enc *e, int what, void *dst, size_t cap);

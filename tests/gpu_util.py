@@ -57,11 +57,12 @@ def first_diff(a, b):
     return None if a.size == b.size else n
 
 
-def compare_stages(frames, xs16, ys16, pframes, XL=7, YL=7, VL=3, Q=2, batch_frames=None):
-    """Stage-by-stage comparison; returns a list of human-readable mismatch strings (empty = parity)."""
+def compare_stages(frames, xs16, ys16, pframes, XL=7, YL=7, VL=3, Q=2, batch_frames=None, ref=None):
+    """Stage-by-stage comparison; returns a list of human-readable mismatch strings (empty = parity).
+    ref: what orc.encode(..., dump=True) returned for the same arguments, when the caller has it already."""
     W, H = M.clamp_geometry(xs16, ys16, XL, YL)
     mbw = W // 16
-    ref_bytes, ref = orc.encode(frames, xs16, ys16, pframes, XL, YL, VL, Q, dump=True)
+    ref_bytes, ref = ref if ref is not None else orc.encode(frames, xs16, ys16, pframes, XL, YL, VL, Q, dump=True)
     got_bytes, got = resident_encode(frames, xs16, ys16, pframes, XL, YL, VL, Q, batch_frames, debug=True)
     problems = []
 

@@ -3,7 +3,8 @@ runs are checked through size-independent properties plus an oracle comparison o
   * closed GOPs: the stream of GOP k does not depend on what precedes it (same frames -> same bytes);
   * chunking invariance at full size;
   * every start code / slice count / length rule of the stream layer;
-  * first GOP byte-identical to the oracle (1920x1152, VL=3, Q=2)."""
+  * first GOP byte-identical to the oracle (1920x1152, VL=3, Q=2 here; VECTOR_LEVEL 1 and 2, the other Q_LEVELs and dense content at
+    full size: tests/test_gpu_dense_wide.py)."""
 import numpy as np
 import pytest
 
