@@ -38,11 +38,24 @@ EXPORTS = [
     "m2v_comm_init_callbacks", "m2v_comm_init_peer", "m2v_comm_peer_export", "m2v_comm_peer_connect", "m2v_comm_peer_connect_all",
     "m2v_comm_peer_stats", "m2v_comm_kind", "m2v_strip_last_form", "m2v_upload_wait", "m2v_device_pci_bus_id",
     "m2v_strip_encode_begin", "m2v_strip_encode_end",
+    "m2v_rgb_matrix", "m2v_push_rgb", "m2v_push_rgb_pull", "m2v_encode_resident_rgb", "m2v_encode_resident_rgb_begin",
 ]
 
 # the 4:2:0 entry points (kept apart: tests/test_abi.py matches EXPORTS against names of letters and underscores only)
 EXPORTS_420 = ["m2v_push_frames420", "m2v_push_frames420_pull", "m2v_encode_resident420", "m2v_encode_resident420_begin"]
 LAYOUTS_420 = {"i420": 0, "yv12": 1, "nv12": 2, "nv21": 3}          # M2V_420_*
+
+# RGB input (include/m2v_mi355x.h).  M2V_RGB_* layouts: name -> code; bytes per pixel and where R, G, B sit (rgbp: which plane)
+LAYOUTS_RGB = {"rgb24": 0, "bgr24": 1, "rgbx": 2, "bgrx": 3, "xrgb": 4, "xbgr": 5, "rgbp": 6}
+_RGB_FORM = {0: (3, (0, 1, 2)), 1: (3, (2, 1, 0)), 2: (4, (0, 1, 2)), 3: (4, (2, 1, 0)), 4: (4, (1, 2, 3)), 5: (4, (3, 2, 1)), 6: (3, (0, 1, 2))}
+# the matrices: name -> (code, T row by row (Y, U, V x R, G, B; scale 2^14), luma offset).  Typed out here, independent of the
+# library's table (m2v_rgb_matrix); tests/test_input_rgb.py holds the two against each other and against the derivation.
+MATRICES_RGB = {
+    "bt601": (0, (4207, 8260, 1604, -2428, -4768, 7196, 7196, -6026, -1170), 16),
+    "bt709": (1, (2991, 10064, 1016, -1649, -5547, 7196, 7196, -6536, -660), 16),
+    "bt601f": (2, (4899, 9617, 1868, -2765, -5427, 8192, 8192, -6860, -1332), 0),
+    "bt709f": (3, (3483, 11718, 1183, -1877, -6315, 8192, 8192, -7441, -751), 0),
+}
 
 PEER_DESC_BYTES = 128          # M2V_PEER_DESC_BYTES
 
@@ -153,6 +166,12 @@ def lib(debug=False):
             L.m2v_push_frames420_pull.argtypes = [vp, u32, u32, u32, vp, sz, ci, vp, sz, ctypes.POINTER(ci)]
             L.m2v_encode_resident420.argtypes = [vp, u32, u32, u32, vp, sz, ci, vp, sz, ctypes.POINTER(sz), vp]
             L.m2v_encode_resident420_begin.argtypes = [vp, u32, u32, u32, vp, sz, ci, vp, sz, vp]
+            L.m2v_rgb_matrix.argtypes = [ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+            L.m2v_push_rgb.argtypes = [vp, u32, u32, u32, vp, sz, ci, ci]
+            L.m2v_push_rgb_pull.restype = ctypes.c_longlong
+            L.m2v_push_rgb_pull.argtypes = [vp, u32, u32, u32, vp, sz, ci, ci, vp, sz, ctypes.POINTER(ci)]
+            L.m2v_encode_resident_rgb.argtypes = [vp, u32, u32, u32, vp, sz, ci, ci, vp, sz, ctypes.POINTER(sz), vp]
+            L.m2v_encode_resident_rgb_begin.argtypes = [vp, u32, u32, u32, vp, sz, ci, ci, vp, sz, vp]
         except AttributeError:
             # an OLDER build handed in through M2V_LIB for a same-box A/B (tools/ab.sh) may lack the newer entry points; the library of
             # this tree must have every one of them (tests/test_abi.py)
@@ -211,6 +230,42 @@ def to420(frames444, layout="i420"):
     return np.concatenate([f[:, 0].reshape(n, -1), chroma], axis=1)
 
 
+def _layout_rgb(layout):
+    """a name of LAYOUTS_RGB or an M2V_RGB_* layout code -> the code (unknown codes pass through: the library answers M2V_E_PARAM)"""
+    return LAYOUTS_RGB[layout] if isinstance(layout, str) else int(layout)
+
+
+def _matrix_rgb(matrix):
+    """a name of MATRICES_RGB or an M2V_RGB_* matrix code -> the code"""
+    return MATRICES_RGB[matrix][0] if isinstance(matrix, str) else int(matrix)
+
+
+def rgb_bytes_per_pixel(layout):
+    return _RGB_FORM[_layout_rgb(layout)][0]
+
+
+def rgb_to444(frames, W, H, layout="rgb24", matrix="bt601"):
+    """RGB frames (uint8, W*H*bpp bytes each, one of LAYOUTS_RGB) -> planar 4:4:4 [n, 3, H, W] by the integer transform of
+    include/m2v_mi355x.h: the frames whose stream an RGB encode equals by definition.  numpy integer arithmetic, host side: a
+    reference, not a fast path."""
+    code = _layout_rgb(layout)
+    bpp, (o_r, o_g, o_b) = _RGB_FORM[code]
+    _, T, yo = next(m for m in MATRICES_RGB.values() if m[0] == _matrix_rgb(matrix))
+    f = np.ascontiguousarray(frames, np.uint8).reshape(-1, W * H * bpp)
+    n = f.shape[0]
+    if code == 6:
+        px = f.reshape(n, 3, H * W)
+        r, g, b = (px[:, k].astype(np.int32) for k in (o_r, o_g, o_b))
+    else:
+        px = f.reshape(n, H * W, bpp)
+        r, g, b = (px[:, :, k].astype(np.int32) for k in (o_r, o_g, o_b))
+    out = np.empty((n, 3, H, W), np.uint8)
+    for k, off in enumerate((yo, 128, 128)):
+        v = ((T[3 * k] * r + T[3 * k + 1] * g + T[3 * k + 2] * b + 8192) >> 14) + off          # (>> of a numpy int32 is arithmetic)
+        out[:, k] = np.clip(v, 0, 255).astype(np.uint8).reshape(n, H, W)
+    return out
+
+
 def clamp_geometry(xsize16, ysize16, XL=7, YL=7):
     """Clamped (W, H) of RTL/mpeg2encoder.v:985-1006 (pure host arithmetic)."""
     def c(s, L):
@@ -225,6 +280,7 @@ class Mpeg2Encoder:
 
     def __init__(self, XL=6, YL=6, VECTOR_LEVEL=3, Q_LEVEL=2, device=0, debug=False):
         self.params = (XL, YL, VECTOR_LEVEL, Q_LEVEL)
+        self.device = device
         self._geom = {}
         err = ctypes.c_int(0)
         self._L = lib(debug)
@@ -326,6 +382,28 @@ class Mpeg2Encoder:
                                                       ctypes.byref(last)), "m2v_push_frames420_pull")
         return n, bool(last.value)
 
+    def push_rgb(self, xsize16, ysize16, pframes_count, frames, layout="rgb24", matrix="bt601"):
+        """m2v_push_rgb: whole RGB frames (W*H*3 or W*H*4 bytes each) in one of LAYOUTS_RGB, converted with one of MATRICES_RGB"""
+        W, H = self.geometry(xsize16, ysize16)
+        f = self._flat_u8(frames)
+        fb = W * H * rgb_bytes_per_pixel(layout)
+        assert f.size % fb == 0
+        self._chk(self._L.m2v_push_rgb(self._h, xsize16, ysize16, pframes_count, f.ctypes.data, f.size // fb, _layout_rgb(layout),
+                                       _matrix_rgb(matrix)), "m2v_push_rgb")
+
+    def push_rgb_pull(self, xsize16, ysize16, pframes_count, frames, dst, offset=0, layout="rgb24", matrix="bt601"):
+        """m2v_push_rgb_pull: push_rgb + pull_into(dst, offset) in one call -> (bytes written, last)"""
+        W, H = self.geometry(xsize16, ysize16)
+        f = self._flat_u8(frames)
+        fb = W * H * rgb_bytes_per_pixel(layout)
+        assert f.size % fb == 0
+        assert dst.dtype == np.uint8 and dst.flags["C_CONTIGUOUS"]
+        last = ctypes.c_int(0)
+        n = self._chk(self._L.m2v_push_rgb_pull(self._h, xsize16, ysize16, pframes_count, f.ctypes.data, f.size // fb, _layout_rgb(layout),
+                                                _matrix_rgb(matrix), dst.ctypes.data + offset, (dst.size - offset) & ~31,
+                                                ctypes.byref(last)), "m2v_push_rgb_pull")
+        return n, bool(last.value)
+
     def upload_wait(self):
         """option direct_upload = 2: returns when every frame handed to push_frames so far has been read"""
         self._chk(self._L.m2v_upload_wait(self._h), "m2v_upload_wait")
@@ -364,13 +442,17 @@ class Mpeg2Encoder:
                 break
         return b"".join(out)
 
-    def encode(self, frames444, xsize16, ysize16, pframes_count, nbeats=None, layout=None):
+    def encode(self, frames444, xsize16, ysize16, pframes_count, nbeats=None, layout=None, matrix="bt601"):
         """One whole sequence from host memory through the beat interface; returns the stream bytes.
-        layout (a name of LAYOUTS_420): `frames444` holds whole 4:2:0 frames instead."""
+        layout (a name of LAYOUTS_420 or LAYOUTS_RGB): `frames444` holds whole 4:2:0 or RGB frames instead; matrix (a name of
+        MATRICES_RGB) converts the latter."""
         W, H = self.geometry(xsize16, ysize16)
         if layout is not None:
-            assert nbeats is None, "there are no 4:2:0 beats"
-            self.push_frames420(xsize16, ysize16, pframes_count, frames444, layout)
+            assert nbeats is None, "there are no 4:2:0 or RGB beats"
+            if layout in LAYOUTS_RGB:
+                self.push_rgb(xsize16, ysize16, pframes_count, frames444, layout, matrix)
+            else:
+                self.push_frames420(xsize16, ysize16, pframes_count, frames444, layout)
             self.sequence_stop()
             return self.pull_all()
         f = np.ascontiguousarray(frames444, np.uint8).reshape(-1, 3, H * W)
@@ -409,6 +491,55 @@ class Mpeg2Encoder:
         """enqueue a whole 4:2:0 sequence and return; encode_resident_end() waits for it and returns the byte count"""
         self._chk(self._L.m2v_encode_resident420_begin(self._h, xsize16, ysize16, pframes_count, d_frames_ptr, nframes,
                                                        _layout420(layout), d_out_ptr, cap, stream), "m2v_encode_resident420_begin")
+
+    def encode_resident_rgb(self, d_frames_ptr, nframes, d_out_ptr, cap, xsize16, ysize16, pframes_count, layout="rgb24", matrix="bt601",
+                            stream=0):
+        """m2v_encode_resident_rgb: `nframes` RGB frames at a 16-byte aligned device pointer"""
+        n = ctypes.c_size_t(0)
+        self._chk(self._L.m2v_encode_resident_rgb(self._h, xsize16, ysize16, pframes_count, d_frames_ptr, nframes, _layout_rgb(layout),
+                                                  _matrix_rgb(matrix), d_out_ptr, cap, ctypes.byref(n), stream), "m2v_encode_resident_rgb")
+        return n.value
+
+    def encode_resident_rgb_begin(self, d_frames_ptr, nframes, d_out_ptr, cap, xsize16, ysize16, pframes_count, layout="rgb24",
+                                  matrix="bt601", stream=0):
+        """enqueue a whole RGB sequence and return; encode_resident_end() waits for it and returns the byte count"""
+        self._chk(self._L.m2v_encode_resident_rgb_begin(self._h, xsize16, ysize16, pframes_count, d_frames_ptr, nframes,
+                                                        _layout_rgb(layout), _matrix_rgb(matrix), d_out_ptr, cap, stream),
+                  "m2v_encode_resident_rgb_begin")
+
+    def encode_tensor(self, frames, pframes_count, order="rgb", matrix="bt601", out=None):
+        """One whole sequence from a torch image tensor on the handle's device, in one call: contiguous uint8 [N, H, W, 3] (order
+        "rgb" / "bgr"), [N, H, W, 4] ("rgbx" / "bgrx" / "xrgb" / "xbgr") or [N, 3, H, W] ("rgb": planar).  Runs
+        m2v_encode_resident_rgb on torch's current stream and returns the stream bytes as a uint8 device tensor (a view of `out` when
+        given; M2VError when it is too small).  ValueError for any other tensor."""
+        import torch
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4:
+            raise ValueError("encode_tensor: a uint8 tensor of 4 dimensions is required")
+        if not frames.is_cuda or frames.device.index != self.device:
+            raise ValueError("encode_tensor: the tensor is on %s, the handle on device %d" % (frames.device, self.device))
+        if not frames.is_contiguous():
+            raise ValueError("encode_tensor: the tensor must be contiguous")
+        if matrix not in MATRICES_RGB:
+            raise ValueError("encode_tensor: unknown matrix %r" % (matrix,))
+        N, d1, d2, d3 = frames.shape
+        if order in ("rgb", "bgr") and d3 == 3:
+            layout, H, W = order + "24", d1, d2
+        elif order in ("rgbx", "bgrx", "xrgb", "xbgr") and d3 == 4:
+            layout, H, W = order, d1, d2
+        elif order == "rgb" and d1 == 3:
+            layout, H, W = "rgbp", d2, d3
+        else:
+            raise ValueError("encode_tensor: shape %r does not go with order %r" % (tuple(frames.shape), order))
+        if H % 16 or W % 16 or self.geometry(W // 16, H // 16) != (W, H):
+            raise ValueError("encode_tensor: %d x %d is not a size of this handle (multiples of 16, 64 ... %d x 64 ... %d)"
+                             % (W, H, 16 << self.params[0], 16 << self.params[1]))
+        if out is None:
+            out = torch.empty(N * 3 * W * H + (1 << 16), dtype=torch.uint8, device=frames.device)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != frames.device or not out.is_contiguous() or out.dim() != 1:
+            raise ValueError("encode_tensor: out must be a contiguous one-dimensional uint8 tensor on the frames' device")
+        nb = self.encode_resident_rgb(frames.data_ptr(), N, out.data_ptr(), out.numel(), W // 16, H // 16, pframes_count, layout, matrix,
+                                      stream=torch.cuda.current_stream(frames.device).cuda_stream)
+        return out[:nb]
 
     def encode_resident_end(self):
         n = ctypes.c_size_t(0)

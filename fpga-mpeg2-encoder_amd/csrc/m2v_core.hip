@@ -656,8 +656,8 @@ static int debug_impl(m2v_enc *e, void *argp)
 {
     auto *a = (DebugArgs *)argp;
     if (a->what == 4) {
-        // the expanded input of the last m2v_encode_resident420 call's last chunk, as its kernels read it
-        if (e->resident_inflight || !e->x444_bytes) { e->set_err("m2v_debug_read(4): no completed m2v_encode_resident420 call"); return M2V_E_STATE; }
+        // the expanded / converted input of the last m2v_encode_resident420 / m2v_encode_resident_rgb call's last chunk, as its kernels read it
+        if (e->resident_inflight || !e->x444_bytes) { e->set_err("m2v_debug_read(4): no completed m2v_encode_resident420 / m2v_encode_resident_rgb call"); return M2V_E_STATE; }
         if (e->x444_bytes > a->cap) return M2V_E_OVERFLOW;
         HIPCHK(hipMemcpy(a->dst, e->d_x444.p, e->x444_bytes, hipMemcpyDeviceToHost));
         a->ret = (long long)e->x444_bytes;

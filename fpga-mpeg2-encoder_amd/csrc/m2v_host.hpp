@@ -6,7 +6,7 @@
 //   m2v_core.hip      handle life cycle, options, geometry (RTL:985-1006), the chunk plan (GOP segments, reconstruction slots, launch
 //                     lists) and its execution: plan_chunk -> run_step* -> finish_chunk
 //   m2v_port.hip      the port path: beats in (RTL:1027-1095), 32-byte words out (RTL:2961-2994), double-buffered staging; the input
-//                     conversions in front of a chunk (k_unpack444, k_expand420: no device globals, so they can live here)
+//                     conversions in front of a chunk (k_unpack444, k_expand420, k_rgb2yuv: no device globals, so they can live here)
 //   m2v_resident.hip  whole sequences resident in HBM (what bench.py times), one or several per call
 //   m2v_strips.hip    strip mode (BASELINE config c5) and the communicators of m2v_comm.hpp
 #pragma once
@@ -110,8 +110,9 @@ struct m2v_enc {
         // Frames that arrived as PACKED 4:4:4 samples (m2v_push_packed) keep the caller's byte order until they are on the device: one
         // linear run of bytes per chunk, frame after frame in arrival order, staged in pinned memory (or uploaded straight from
         // page-locked caller memory) and de-interleaved into d_in by k_unpack444 in front of the chunk's kernels
-        // Whole 4:2:0 frames (m2v_push_frames420) are one more kind of run in the same bytes: kPk420 + M2V_420_*, expanded by k_expand420
-        struct PkFrame { uint32_t frame; int layout; size_t off; };       // chunk frame index, M2V_PACKED_* or kPk420 + M2V_420_*, where its bytes start in h_pk / d_pk
+        // Whole 4:2:0 frames (m2v_push_frames420) are one more kind of run in the same bytes: kPk420 + M2V_420_*, expanded by k_expand420;
+        // whole RGB frames (m2v_push_rgb) another: pk_rgb(M2V_RGB_* layout, matrix), converted by k_rgb2yuv
+        struct PkFrame { uint32_t frame; int layout; size_t off; };       // chunk frame index, M2V_PACKED_* / kPk420 + M2V_420_* / pk_rgb(), where its bytes start in h_pk / d_pk
         std::vector<PkFrame> pk;
         uint8_t *h_pk = nullptr;              // pinned staging (only when packed beats come from ordinary memory)
         size_t h_pk_cap = 0;
@@ -237,7 +238,7 @@ struct m2v_enc {
     int strip_graph_opt = -1;
     struct StripStats { double halo_total_ms = 0, halo_exposed_ms = 0, gather_ms = 0, host_us_per_step = 0, comm_us_per_step = 0; int steps = 0; int graph = 0; int peer = 0; } strip_stats;
 
-    // m2v_encode_resident420: the chunk's frames expanded to planar 4:4:4 in front of its kernels (no recording references the buffer)
+    // m2v_encode_resident420 / m2v_encode_resident_rgb: the chunk's frames as planar 4:4:4 in front of its kernels (no recording references the buffer)
     DevBuf<uint8_t> d_x444;
     size_t x444_bytes = 0;                // ... what the last call's last chunk left there (m2v_debug_read, what = 4)
 
@@ -338,6 +339,18 @@ inline bool layout420_ok(int layout) { return layout >= M2V_420_I420 && layout <
 // nframes 4:2:0 frames (ysz * 3 / 2 bytes each, back to back at src) -> planar 4:4:4 frames of 3 * ysz bytes at dst, every chroma
 // sample repeated 2 x 2 (k_expand420).  src and dst 16-byte aligned.
 void launch_expand420(hipStream_t s, int layout, const uint8_t *src, uint8_t *dst, const Geom &g, uint32_t nframes);
+// PkFrame::layout of an RGB frame: two neighbours that differ in layout or matrix are two runs
+constexpr int kPkRgb = 32;
+inline bool rgb_layout_ok(int layout) { return layout >= M2V_RGB_RGB24 && layout <= M2V_RGB_RGBP; }
+inline bool rgb_matrix_ok(int matrix) { return matrix >= M2V_RGB_BT601 && matrix <= M2V_RGB_BT709F; }
+inline int pk_rgb(int layout, int matrix) { return kPkRgb + 8 * matrix + layout; }
+inline int rgb_bpp(int layout) { return layout >= M2V_RGB_RGBX32 && layout <= M2V_RGB_XBGR32 ? 4 : 3; }
+// source bytes of one frame of a run kind (PkFrame::layout)
+size_t pk_frame_bytes(int kind, uint32_t ysz);
+// the frames of a 4:2:0 or RGB run kind (back to back at src) -> planar 4:4:4 frames of 3 * ysz bytes at dst.  src and dst 16-byte aligned.
+void launch_convert(hipStream_t s, int kind, const uint8_t *src, uint8_t *dst, const Geom &g, uint32_t nframes);
+// nframes RGB frames (ysz * rgb_bpp(layout) bytes each) -> planar 4:4:4 by the integer transform of include/m2v_mi355x.h (k_rgb2yuv)
+void launch_rgb2yuv(hipStream_t s, int layout, int matrix, const uint8_t *src, uint8_t *dst, uint32_t ysz, uint32_t nframes);
 
 // ---- m2v_strips.hip ----
 void strip_flight_release(m2v_enc *e);

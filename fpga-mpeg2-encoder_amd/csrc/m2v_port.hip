@@ -145,14 +145,6 @@ void launch_unpack(hipStream_t s, int layout, const uint8_t *src, uint8_t *dst, 
     HIPCHK(hipGetLastError());
 }
 
-// source bytes of one frame of a run kind (PkFrame::layout): ysz * bytes per pixel, 1.5 for 4:2:0
-size_t pk_frame_bytes(int layout, uint32_t ysz)
-{
-    PackedFmt f{};
-    if (packed_fmt(layout, f)) return (size_t)ysz * (size_t)f.stride;
-    return (size_t)ysz + (ysz >> 1);
-}
-
 // 4:2:0 frames -> the three full-size planes of the chunk's frames, every chroma sample repeated 2 x 2 (the module's own two-stage mean2
 // of RTL:1086-1089, 1167-1170 then returns the caller's chroma: mean2(a, a) = a).  One lane per 16 output pixels of a row PAIR 2j, 2j + 1:
 // two 16-byte luma copies; the 8 U + 8 V source samples doubled in registers (v_perm_b32) and stored to both rows of either plane.
@@ -194,7 +186,90 @@ __global__ __launch_bounds__(256) void k_expand420(const uint8_t *__restrict__ s
     }
 }
 
+// RGB frames -> the three planes of the chunk's frames by the integer transform of include/m2v_mi355x.h.  Shaped like k_unpack444: 16
+// pixels per lane, STRIDE 16-byte loads, byte selection in registers, one 16-byte store per plane.  STRIDE = 1 is the planar form
+// (RGBP): three 16-byte loads from the planes OR, OG, OB of a frame of 3 * ysz bytes.  The rounding constant and the offset are one
+// addend: ((x + 8192) >> 14) + o = (x + 8192 + (o << 14)) >> 14, so a component is three v_mad_i32_i24 (every sum fits 24 bits), a
+// shift and a clamp.  The coefficients are kernel arguments (SGPRs): one kernel per layout, not per matrix.
+// src: frames of ysz * STRIDE (planar: 3 * ysz) bytes back to back; dst: frames of 3 * ysz bytes.  Every access 16-byte aligned
+// (ysz is a multiple of 256).  HBM traffic 3 + 3 or 4 + 3 bytes per pixel.
+struct RgbCoef { int c[9]; int ky, kc; };        // T row by row; 8192 + (o << 14); 8192 + (128 << 14)
+
+template <int STRIDE, int OR, int OG, int OB>
+__global__ __launch_bounds__(256) void k_rgb2yuv(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, uint32_t ysz, uint32_t nframes, RgbCoef m)
+{
+    constexpr bool PLANAR = STRIDE == 1;
+    constexpr int NW = PLANAR ? 12 : 4 * STRIDE;
+    const uint32_t per_frame = ysz >> 4;
+    for (uint32_t f = blockIdx.y; f < nframes; f += gridDim.y) {
+        const uint8_t *sf = src + (size_t)f * ysz * (PLANAR ? 3 : STRIDE);
+        uint8_t *df = dst + (size_t)f * ysz * 3;
+        for (uint32_t t = blockIdx.x * 256u + threadIdx.x; t < per_frame; t += gridDim.x * 256u) {
+            uint32_t w[NW];
+#pragma unroll
+            for (int k = 0; k < NW / 4; ++k) {
+                const uint4 q = PLANAR ? *(const uint4 *)(sf + (size_t)k * ysz + (size_t)t * 16) : ((const uint4 *)(sf + (size_t)t * 16 * STRIDE))[k];
+                w[4 * k] = q.x; w[4 * k + 1] = q.y; w[4 * k + 2] = q.z; w[4 * k + 3] = q.w;
+            }
+            auto byte = [&](int idx) -> int { return (int)((w[idx >> 2] >> (8 * (idx & 3))) & 0xFFu); };
+            auto comp = [&](int px, int o) -> int { return PLANAR ? byte(16 * o + px) : byte(px * STRIDE + o); };
+            auto row = [&](int r, int g, int b, int c0, int c1, int c2, int k) -> uint32_t {
+                // (never negative - tests/test_input_rgb.py walks all 2^24 inputs - so the clamp is an unsigned minimum.  Keep it
+                // unsigned: from min(max(v >> 14, 0), 255) hipcc selects v_ashr_pk_u8_i32 and ORs the neighbouring pixel into the
+                // upper half of its result register unmasked)
+                const uint32_t v = (uint32_t)(__mul24(c0, r) + __mul24(c1, g) + __mul24(c2, b) + k);
+                return min(v >> 14, 255u);
+            };
+            uint32_t y[4] = {0, 0, 0, 0}, u[4] = {0, 0, 0, 0}, v[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int px = 0; px < 16; ++px) {
+                const int r = comp(px, OR), g = comp(px, OG), b = comp(px, OB);
+                y[px >> 2] |= row(r, g, b, m.c[0], m.c[1], m.c[2], m.ky) << (8 * (px & 3));
+                u[px >> 2] |= row(r, g, b, m.c[3], m.c[4], m.c[5], m.kc) << (8 * (px & 3));
+                v[px >> 2] |= row(r, g, b, m.c[6], m.c[7], m.c[8], m.kc) << (8 * (px & 3));
+            }
+            ((uint4 *)df)[t] = make_uint4(y[0], y[1], y[2], y[3]);
+            ((uint4 *)(df + ysz))[t] = make_uint4(u[0], u[1], u[2], u[3]);
+            ((uint4 *)(df + 2 * (size_t)ysz))[t] = make_uint4(v[0], v[1], v[2], v[3]);
+        }
+    }
+}
+
 }  // namespace
+
+size_t pk_frame_bytes(int kind, uint32_t ysz)
+{
+    PackedFmt f{};
+    if (kind >= kPkRgb) return (size_t)ysz * (size_t)rgb_bpp((kind - kPkRgb) & 7);
+    if (packed_fmt(kind, f)) return (size_t)ysz * (size_t)f.stride;
+    return (size_t)ysz + (ysz >> 1);
+}
+
+void launch_rgb2yuv(hipStream_t s, int layout, int matrix, const uint8_t *src, uint8_t *dst, uint32_t ysz, uint32_t nframes)
+{
+    RgbCoef m{};
+    int yo = 0;
+    HIPCHK(m2v_rgb_matrix(matrix, m.c, &yo) == M2V_OK && rgb_layout_ok(layout) ? hipSuccess : hipErrorInvalidValue);      // (the entries have checked)
+    m.ky = 8192 + (yo << 14);
+    m.kc = 8192 + (128 << 14);
+    const dim3 grid(std::min<uint32_t>(((ysz >> 4) + 255u) / 256u, 1024u), std::min<uint32_t>(nframes, 32768u)), block(256);
+    switch (layout) {
+    case M2V_RGB_RGB24: hipLaunchKernelGGL((k_rgb2yuv<3, 0, 1, 2>), grid, block, 0, s, src, dst, ysz, nframes, m); break;
+    case M2V_RGB_BGR24: hipLaunchKernelGGL((k_rgb2yuv<3, 2, 1, 0>), grid, block, 0, s, src, dst, ysz, nframes, m); break;
+    case M2V_RGB_RGBX32: hipLaunchKernelGGL((k_rgb2yuv<4, 0, 1, 2>), grid, block, 0, s, src, dst, ysz, nframes, m); break;
+    case M2V_RGB_BGRX32: hipLaunchKernelGGL((k_rgb2yuv<4, 2, 1, 0>), grid, block, 0, s, src, dst, ysz, nframes, m); break;
+    case M2V_RGB_XRGB32: hipLaunchKernelGGL((k_rgb2yuv<4, 1, 2, 3>), grid, block, 0, s, src, dst, ysz, nframes, m); break;
+    case M2V_RGB_XBGR32: hipLaunchKernelGGL((k_rgb2yuv<4, 3, 2, 1>), grid, block, 0, s, src, dst, ysz, nframes, m); break;
+    default: hipLaunchKernelGGL((k_rgb2yuv<1, 0, 1, 2>), grid, block, 0, s, src, dst, ysz, nframes, m); break;
+    }
+    HIPCHK(hipGetLastError());
+}
+
+void launch_convert(hipStream_t s, int kind, const uint8_t *src, uint8_t *dst, const Geom &g, uint32_t nframes)
+{
+    if (kind >= kPkRgb) launch_rgb2yuv(s, (kind - kPkRgb) & 7, (kind - kPkRgb) >> 3, src, dst, g.ysz, nframes);
+    else launch_expand420(s, kind - kPk420, src, dst, g, nframes);
+}
 
 void launch_expand420(hipStream_t s, int layout, const uint8_t *src, uint8_t *dst, const Geom &g, uint32_t nframes)
 {
@@ -337,7 +412,7 @@ void flush_buffered(m2v_enc *e, bool last)
             while (b < h.pk.size() && h.pk[b].layout == layout && h.pk[b].frame == h.pk[a].frame + (b - a) &&
                    h.pk[b].off == h.pk[a].off + (b - a) * src_bytes) ++b;
             uint8_t *to = h.d_in.p + (size_t)h.pk[a].frame * frame_bytes;
-            if (layout >= kPk420) launch_expand420(s, layout - kPk420, h.d_pk.p + h.pk[a].off, to, g, (uint32_t)(b - a));
+            if (layout >= kPk420) launch_convert(s, layout, h.d_pk.p + h.pk[a].off, to, g, (uint32_t)(b - a));
             else launch_unpack(s, layout, h.d_pk.p + h.pk[a].off, to, g.ysz, (uint32_t)(b - a));
             a = b;
         }
@@ -623,8 +698,9 @@ int m2v_push_packed(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pfr
     return guard(e, push_beats_impl, &a);
 }
 
-// layout < 0: planar 4:4:4 frames (into h_in / d_in); M2V_420_*: 4:2:0 frames, which travel as one more kind of packed run (h_pk / d_pk)
-struct PushFramesArgs { uint32_t xs, ys, pf; const uint8_t *frames; size_t n; PullSink *sink; int layout = -1; };
+// kind < 0: planar 4:4:4 frames (into h_in / d_in); kPk420 + M2V_420_* or pk_rgb(): 4:2:0 or RGB frames, which travel as one more kind
+// of packed run (h_pk / d_pk)
+struct PushFramesArgs { uint32_t xs, ys, pf; const uint8_t *frames; size_t n; PullSink *sink; int kind = -1; };
 
 static int push_frames_impl(m2v_enc *e, void *argp)
 {
@@ -641,8 +717,8 @@ static int push_frames_impl(m2v_enc *e, void *argp)
     if (e->state == m2v_enc::ENDED || a->n == 0) { settle_deferred(); return M2V_OK; }
     if (e->state == m2v_enc::IDLE) start_sequence(e, a->xs, a->ys, a->pf);
     const Geom &g = e->g;
-    const bool is420 = a->layout >= 0;
-    const size_t fb = is420 ? pk_frame_bytes(kPk420 + a->layout, g.ysz) : (size_t)g.ysz * 3;      // the caller's bytes per frame
+    const bool is420 = a->kind >= 0;              // (or RGB: any kind that goes through the packed bytes)
+    const size_t fb = is420 ? pk_frame_bytes(a->kind, g.ysz) : (size_t)g.ysz * 3;      // the caller's bytes per frame
     if (e->beat_pos != 0) {
         settle_deferred();
         e->set_err("m2v_push_frames: a frame is partially filled by m2v_push_beats");
@@ -670,7 +746,7 @@ static int push_frames_impl(m2v_enc *e, void *argp)
             // complete frames are buffered)
             if (!pk_room(e, h, take * fb, fb)) { flush_buffered(e, false); continue; }
             pk_off = h.pk_used;
-            for (size_t j = 0; j < take; ++j) h.pk.push_back({(uint32_t)(e->buffered + j), kPk420 + a->layout, pk_off + j * fb});
+            for (size_t j = 0; j < take; ++j) h.pk.push_back({(uint32_t)(e->buffered + j), a->kind, pk_off + j * fb});
             h.pk_used += take * fb;
             h.pk_valid = h.pk_used;
         }
@@ -795,7 +871,7 @@ int m2v_push_frames420(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t 
 {
     if (!e || (nframes && !frames420)) return M2V_E_PARAM;
     if (!layout420_ok(layout)) { e->set_err("m2v_push_frames420: unknown layout %d", layout); return M2V_E_PARAM; }
-    PushFramesArgs a{xsize16, ysize16, pframes_count, frames420, nframes, nullptr, layout};
+    PushFramesArgs a{xsize16, ysize16, pframes_count, frames420, nframes, nullptr, kPk420 + layout};
     return guard(e, push_frames_impl, &a);
 }
 
@@ -804,7 +880,49 @@ long long m2v_push_frames420_pull(m2v_enc *e, uint32_t xsize16, uint32_t ysize16
 {
     if (!e || (nframes && !frames420) || (!dst && cap)) return M2V_E_PARAM;
     if (!layout420_ok(layout)) { e->set_err("m2v_push_frames420_pull: unknown layout %d", layout); return M2V_E_PARAM; }
-    return push_frames_pull(e, PushFramesArgs{xsize16, ysize16, pframes_count, frames420, nframes, nullptr, layout}, dst, cap, last);
+    return push_frames_pull(e, PushFramesArgs{xsize16, ysize16, pframes_count, frames420, nframes, nullptr, kPk420 + layout}, dst, cap, last);
+}
+
+// The table of include/m2v_mi355x.h: the single source of the coefficients (launch_rgb2yuv hands the kernel what this returns)
+int m2v_rgb_matrix(int matrix, int coeff[9], int *y_offset)
+{
+    static const int T[4][10] = {
+        {4207, 8260, 1604, -2428, -4768, 7196, 7196, -6026, -1170, 16},         // M2V_RGB_BT601
+        {2991, 10064, 1016, -1649, -5547, 7196, 7196, -6536, -660, 16},         // M2V_RGB_BT709
+        {4899, 9617, 1868, -2765, -5427, 8192, 8192, -6860, -1332, 0},          // M2V_RGB_BT601F
+        {3483, 11718, 1183, -1877, -6315, 8192, 8192, -7441, -751, 0},          // M2V_RGB_BT709F
+    };
+    if (!rgb_matrix_ok(matrix)) return M2V_E_PARAM;
+    if (coeff) for (int k = 0; k < 9; ++k) coeff[k] = T[matrix][k];
+    if (y_offset) *y_offset = T[matrix][9];
+    return M2V_OK;
+}
+
+static bool rgb_args_ok(m2v_enc *e, const char *fn, int layout, int matrix)
+{
+    if (!rgb_layout_ok(layout)) { e->set_err("%s: unknown layout %d", fn, layout); return false; }
+    if (!rgb_matrix_ok(matrix)) { e->set_err("%s: unknown matrix %d", fn, matrix); return false; }
+    return true;
+}
+
+// Whole RGB frames: m2v_push_frames420 with another run kind - the chunk's packed bytes, from which k_rgb2yuv writes the planes
+int m2v_push_rgb(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count, const uint8_t *frames, size_t nframes,
+                 int layout, int matrix)
+{
+    if (!e) return M2V_E_PARAM;
+    if (nframes && !frames) { e->set_err("m2v_push_rgb: frames is NULL"); return M2V_E_PARAM; }
+    if (!rgb_args_ok(e, "m2v_push_rgb", layout, matrix)) return M2V_E_PARAM;
+    PushFramesArgs a{xsize16, ysize16, pframes_count, frames, nframes, nullptr, pk_rgb(layout, matrix)};
+    return guard(e, push_frames_impl, &a);
+}
+
+long long m2v_push_rgb_pull(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count, const uint8_t *frames,
+                            size_t nframes, int layout, int matrix, uint8_t *dst, size_t cap, int *last)
+{
+    if (!e) return M2V_E_PARAM;
+    if ((nframes && !frames) || (!dst && cap)) { e->set_err("m2v_push_rgb_pull: frames or dst is NULL"); return M2V_E_PARAM; }
+    if (!rgb_args_ok(e, "m2v_push_rgb_pull", layout, matrix)) return M2V_E_PARAM;
+    return push_frames_pull(e, PushFramesArgs{xsize16, ysize16, pframes_count, frames, nframes, nullptr, pk_rgb(layout, matrix)}, dst, cap, last);
 }
 
 static int upload_wait_impl(m2v_enc *e, void *)

@@ -1,11 +1,12 @@
 // m2v_resident.hip — whole sequences with input and output resident in HBM (what bench.py times): m2v_encode_resident, its two
-// halves _begin / _end for callers that keep several sequences in flight, and the same for 4:2:0 input (m2v_encode_resident420).
+// halves _begin / _end for callers that keep several sequences in flight, and the same for 4:2:0 input (m2v_encode_resident420) and
+// RGB input (m2v_encode_resident_rgb).
 #include "m2v_host.hpp"
 
 extern "C" {
 
 struct ResidentArgs { uint32_t xs, ys, pf; const uint8_t *d_in; size_t n; uint8_t *d_out; size_t cap; size_t *bytes; hipStream_t s; bool async = false;
-                      int layout = -1; };      // layout >= 0: d_in holds 4:2:0 frames (M2V_420_*)
+                      int kind = -1; };        // kind >= 0: d_in holds 4:2:0 or RGB frames (a run kind: kPk420 + M2V_420_*, pk_rgb())
 
 // The resident entry in two halves: everything enqueued (m2v_encode_resident_begin), then the one wait and the byte count
 // (m2v_encode_resident_end).  m2v_encode_resident is both, back to back.
@@ -46,10 +47,10 @@ static int resident_impl(m2v_enc *e, void *argp)
     // align chunks to GOP boundaries so every chunk starts with an I frame where possible
     const size_t gop = e->pframes + 1u;
     size_t step = chunk >= gop ? chunk / gop * gop : chunk;
-    const bool is420 = a->layout >= 0;
-    const size_t fb420 = (size_t)g.ysz + (g.ysz >> 1);
+    const bool is420 = a->kind >= 0;              // (or RGB)
+    const size_t fb420 = is420 ? pk_frame_bytes(a->kind, g.ysz) : 0;
     if (is420) {
-        // each chunk's frames are expanded into planar 4:4:4 in front of its kernels, on the same stream; one buffer is enough because
+        // each chunk's frames are expanded or converted into planar 4:4:4 in front of its kernels, on the same stream; one buffer is enough because
         // the chunks are synchronised below
         e->d_x444.recorded = false;
         e->d_x444.ensure(std::min(step, a->n) * fb);
@@ -60,7 +61,7 @@ static int resident_impl(m2v_enc *e, void *argp)
         const uint8_t *frames = is420 ? nullptr : a->d_in + k * fb;
         if (is420) {
             timer_break(e);
-            launch_expand420(s, a->layout, a->d_in + k * fb420, e->d_x444.p, g, (uint32_t)nf);
+            launch_convert(s, a->kind, a->d_in + k * fb420, e->d_x444.p, g, (uint32_t)nf);
             e->x444_bytes = nf * fb;
             frames = e->d_x444.p;
         }
@@ -100,7 +101,7 @@ int m2v_encode_resident420(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint3
     if (!layout420_ok(layout)) { e->set_err("m2v_encode_resident420: unknown layout %d", layout); return M2V_E_PARAM; }
     if ((uintptr_t)d_frames420 & 15) { e->set_err("m2v_encode_resident420: d_frames420 must be 16-byte aligned"); return M2V_E_PARAM; }
     ResidentArgs a{xsize16, ysize16, pframes_count, (const uint8_t *)d_frames420, nframes, (uint8_t *)d_out, cap, out_bytes,
-                   (hipStream_t)hip_stream, false, layout};
+                   (hipStream_t)hip_stream, false, kPk420 + layout};
     return guard(e, resident_impl, &a);
 }
 
@@ -111,8 +112,34 @@ int m2v_encode_resident420_begin(m2v_enc *e, uint32_t xsize16, uint32_t ysize16,
     if (!layout420_ok(layout)) { e->set_err("m2v_encode_resident420_begin: unknown layout %d", layout); return M2V_E_PARAM; }
     if ((uintptr_t)d_frames420 & 15) { e->set_err("m2v_encode_resident420_begin: d_frames420 must be 16-byte aligned"); return M2V_E_PARAM; }
     ResidentArgs a{xsize16, ysize16, pframes_count, (const uint8_t *)d_frames420, nframes, (uint8_t *)d_out, cap, nullptr,
-                   (hipStream_t)hip_stream, true, layout};
+                   (hipStream_t)hip_stream, true, kPk420 + layout};
     return guard(e, resident_impl, &a);
+}
+
+// RGB frames resident in HBM: the same sequence with k_rgb2yuv in front of every chunk
+static int resident_rgb(m2v_enc *e, const char *fn, ResidentArgs a, int layout, int matrix)
+{
+    if (!e) return M2V_E_PARAM;
+    if (a.n && (!a.d_in || !a.d_out)) { e->set_err("%s: d_frames or d_out is NULL", fn); return M2V_E_PARAM; }
+    if (!rgb_layout_ok(layout)) { e->set_err("%s: unknown layout %d", fn, layout); return M2V_E_PARAM; }
+    if (!rgb_matrix_ok(matrix)) { e->set_err("%s: unknown matrix %d", fn, matrix); return M2V_E_PARAM; }
+    if ((uintptr_t)a.d_in & 15) { e->set_err("%s: d_frames must be 16-byte aligned", fn); return M2V_E_PARAM; }
+    a.kind = pk_rgb(layout, matrix);
+    return guard(e, resident_impl, &a);
+}
+
+int m2v_encode_resident_rgb(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count, const void *d_frames,
+                            size_t nframes, int layout, int matrix, void *d_out, size_t cap, size_t *out_bytes, void *hip_stream)
+{
+    return resident_rgb(e, "m2v_encode_resident_rgb", ResidentArgs{xsize16, ysize16, pframes_count, (const uint8_t *)d_frames, nframes,
+                        (uint8_t *)d_out, cap, out_bytes, (hipStream_t)hip_stream, false}, layout, matrix);
+}
+
+int m2v_encode_resident_rgb_begin(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count, const void *d_frames,
+                                  size_t nframes, int layout, int matrix, void *d_out, size_t cap, void *hip_stream)
+{
+    return resident_rgb(e, "m2v_encode_resident_rgb_begin", ResidentArgs{xsize16, ysize16, pframes_count, (const uint8_t *)d_frames, nframes,
+                        (uint8_t *)d_out, cap, nullptr, (hipStream_t)hip_stream, true}, layout, matrix);
 }
 
 int m2v_encode_resident_end(m2v_enc *e, size_t *out_bytes)

@@ -1,11 +1,14 @@
 // m2v_tb — file-to-file driver over the C-ABI; the counterpart of SIM/tb_mpeg2encoder.v.
 //
 //   m2v_tb [-XL n] [-YL n] [-VL n] [-Q n] [-p pframes] [-d device] [-bubbles] [-conformant] [-ps] [-ts]
-//          [-i420 | -yv12 | -nv12 | -nv21]
+//          [-i420 | -yv12 | -nv12 | -nv21 | -rgb24 | -bgr24 | -rgbx | -bgrx | -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f]
 //          in.yuv W H out.m2v  [in2.yuv W2 H2 out2.m2v ...]
 //
 // -i420 / -yv12 / -nv12 / -nv21: the input files hold 4:2:0 frames of W*H*3/2 bytes in that layout (what ordinary tools write) instead
 // of the testbench's planar 4:4:4 frames; they go in through m2v_push_frames420.  At most one of the four.
+// -rgb24 / -bgr24 / -rgbx / -bgrx / -xrgb / -xbgr / -rgbp: the input files (.rgb, .bgra, ...) hold RGB frames of W*H*3 or W*H*4 bytes in that
+// layout (M2V_RGB_*); they go in through m2v_push_rgb and are converted on the device with -matrix (default bt601).  At most one of
+// the eleven layout options.
 // -conformant switches the encoder's option "conformant" on (ISO reconstruction loop; NOT byte-identical to the RTL).
 // -ps / -ts additionally write out.m2v.mpg / out.m2v.ts: the same elementary stream in an MPEG-2 program / transport
 // stream (include/m2v_container.h), so the result plays in an ordinary player.
@@ -27,7 +30,8 @@
 
 int main(int argc, char **argv)
 {
-    int XL = 7, YL = 6, VL = 3, Q = 2, pf = 23, dev = 0, bubbles = 0, conformant = 0, want_ps = 0, want_ts = 0, layout420 = -1, layouts = 0;
+    int XL = 7, YL = 6, VL = 3, Q = 2, pf = 23, dev = 0, bubbles = 0, conformant = 0, want_ps = 0, want_ts = 0, layout420 = -1, layouts = 0, rgb = -1, matrix = M2V_RGB_BT601,
+        bad_matrix = 0;
     int i = 1;
     for (; i < argc && argv[i][0] == '-'; ++i) {
         if (!strcmp(argv[i], "-bubbles")) { bubbles = 1; continue; }
@@ -38,7 +42,18 @@ int main(int argc, char **argv)
         if (!strcmp(argv[i], "-yv12")) { layout420 = M2V_420_YV12; ++layouts; continue; }
         if (!strcmp(argv[i], "-nv12")) { layout420 = M2V_420_NV12; ++layouts; continue; }
         if (!strcmp(argv[i], "-nv21")) { layout420 = M2V_420_NV21; ++layouts; continue; }
+        static const char *const rgb_opts[] = {"-rgb24", "-bgr24", "-rgbx", "-bgrx", "-xrgb", "-xbgr", "-rgbp"};
+        int k = 0;
+        for (; k < 7 && strcmp(argv[i], rgb_opts[k]); ++k) {}
+        if (k < 7) { rgb = k; ++layouts; continue; }
         if (i + 1 >= argc) break;
+        if (!strcmp(argv[i], "-matrix")) {
+            static const char *const names[] = {"bt601", "bt709", "bt601f", "bt709f"};
+            for (k = 0; k < 4 && strcmp(argv[i + 1], names[k]); ++k) {}
+            if (k < 4) matrix = k; else bad_matrix = 1;
+            ++i;
+            continue;
+        }
         int v = atoi(argv[i + 1]);
         if (!strcmp(argv[i], "-XL")) XL = v; else if (!strcmp(argv[i], "-YL")) YL = v;
         else if (!strcmp(argv[i], "-VL")) VL = v; else if (!strcmp(argv[i], "-Q")) Q = v;
@@ -46,8 +61,9 @@ int main(int argc, char **argv)
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
         ++i;
     }
-    if ((argc - i) < 4 || (argc - i) % 4 || layouts > 1 || (layout420 >= 0 && bubbles)) {          // (there are no 4:2:0 beats)
-        fprintf(stderr, "usage: %s [-XL n] [-YL n] [-VL n] [-Q n] [-p pframes] [-d dev] [-i420 | -yv12 | -nv12 | -nv21] in.yuv W H out.m2v ...\n", argv[0]);
+    if ((argc - i) < 4 || (argc - i) % 4 || layouts > 1 || bad_matrix || (layouts && bubbles)) {          // (there are no 4:2:0 or RGB beats)
+        fprintf(stderr, "usage: %s [-XL n] [-YL n] [-VL n] [-Q n] [-p pframes] [-d dev] [-i420 | -yv12 | -nv12 | -nv21 | -rgb24 | -bgr24 | -rgbx | -bgrx |"
+                        " -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f] in.yuv W H out.m2v ...\n", argv[0]);
         return 2;
     }
     int err = 0;
@@ -72,7 +88,8 @@ int main(int argc, char **argv)
             printf("*** ysize=%4d is invalid, which must in range [64,%4d], and must be a multiple of 16\n", ysize, 16 << YL);
             return 1;
         }
-        const size_t fb = layout420 >= 0 ? (size_t)xsize * ysize * 3 / 2 : (size_t)xsize * ysize * 3;
+        const size_t fb = layout420 >= 0 ? (size_t)xsize * ysize * 3 / 2
+                                         : (size_t)xsize * ysize * (rgb >= M2V_RGB_RGBX32 && rgb <= M2V_RGB_XBGR32 ? 4 : 3);
         std::vector<uint8_t> frame(fb), word(1 << 20), es;
         size_t frames = 0, bytes = 0;
         const auto t0 = std::chrono::steady_clock::now();
@@ -93,7 +110,9 @@ int main(int argc, char **argv)
         while (fread(frame.data(), 1, fb, fi) == fb) {                                         // complete frames only (TB:220)
             printf("  start to encode video %d frame %3zu\n", num_video, frames);
             int r;
-            if (layout420 >= 0) {
+            if (rgb >= 0) {
+                r = m2v_push_rgb(e, (uint32_t)xsize / 16, (uint32_t)ysize / 16, (uint32_t)pf, frame.data(), 1, rgb, matrix);
+            } else if (layout420 >= 0) {
                 r = m2v_push_frames420(e, (uint32_t)xsize / 16, (uint32_t)ysize / 16, (uint32_t)pf, frame.data(), 1, layout420);
             } else if (!bubbles) {
                 r = m2v_push_frames(e, (uint32_t)xsize / 16, (uint32_t)ysize / 16, (uint32_t)pf, frame.data(), 1);

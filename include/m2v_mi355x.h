@@ -112,6 +112,60 @@ enum {
 int m2v_push_frames420(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count,
                        const uint8_t *frames420, size_t nframes, int layout);
 
+/*
+ * Whole RGB frames, as renderers, screen grabbers and image tensors hold them.  The module has no RGB port, so the behaviour is a
+ * definition: the stream of an RGB frame is, byte for byte, the stream of the planar 4:4:4 frame obtained by the integer transform
+ * below; the module's own two-stage mean2 then makes the 4:2:0 chroma from those planes as for any 4:4:4 caller.  Per pixel, with
+ * (R, G, B) in 0 ... 255, a matrix T of 3 x 3 integers (scale 2^14) and a luma offset o (>> is arithmetic, i.e. floor):
+ *
+ *     Y = clamp(((T00*R + T01*G + T02*B + 8192) >> 14) + o,   0, 255)
+ *     U = clamp(((T10*R + T11*G + T12*B + 8192) >> 14) + 128, 0, 255)        U = Cb
+ *     V = clamp(((T20*R + T21*G + T22*B + 8192) >> 14) + 128, 0, 255)        V = Cr
+ *
+ *     matrix           T (rows Y, U, V; columns R, G, B)                                   o
+ *     M2V_RGB_BT601    4207  8260 1604 / -2428 -4768 7196 / 7196 -6026 -1170              16    studio range, 16-235 / 16-240
+ *     M2V_RGB_BT709    2991 10064 1016 / -1649 -5547 7196 / 7196 -6536  -660              16    studio range
+ *     M2V_RGB_BT601F   4899  9617 1868 / -2765 -5427 8192 / 8192 -6860 -1332               0    full range (JFIF)
+ *     M2V_RGB_BT709F   3483 11718 1183 / -1877 -6315 8192 / 8192 -7441  -751               0    full range
+ *
+ * With Kr, Kb = 0.299, 0.114 (BT.601) or 0.2126, 0.0722 (BT.709), sy, sc = 219/255, 224/255 (studio) or 1, 1 (full) and
+ * r(x) = floor(x * 2^14 + 1/2):  T00 = r(Kr*sy), T02 = r(Kb*sy), T01 = r(sy) - T00 - T02;  T12 = r(sc/2), T10 = r(-Kr*sc / (2(1-Kb))),
+ * T11 = -T10 - T12;  T20 = r(sc/2), T22 = r(-Kb*sc / (2(1-Kr))), T21 = -T20 - T22.  The middle coefficient is the remainder on
+ * purpose: every grey gives exactly 128 / 128 and white exactly 235 (or 255).  The result is within 0.508 of the real-valued
+ * transform for every input; the clamp only ever acts in the two full-range matrices (Cb / Cr of pure blue / pure red reach 256).
+ *
+ * The stream carries NO colour description (the module writes no sequence_display_extension, RTL:2590-2716, and the stream stays what
+ * the module would emit for those samples): the caller picks the matrix its player will assume.
+ */
+enum {
+    M2V_RGB_BT601 = 0,
+    M2V_RGB_BT709 = 1,
+    M2V_RGB_BT601F = 2,
+    M2V_RGB_BT709F = 3
+};
+/* Layouts: a frame is W*H*bpp bytes in raster order, W, H the CLAMPED sizes (m2v_geometry). */
+enum {
+    M2V_RGB_RGB24 = 0,       /* R G B, 3 bytes per pixel                                            */
+    M2V_RGB_BGR24 = 1,       /* B G R                                                               */
+    M2V_RGB_RGBX32 = 2,      /* R G B x, 4 bytes per pixel, the 4th ignored (RGBA)                  */
+    M2V_RGB_BGRX32 = 3,      /* B G R x (BGRA)                                                      */
+    M2V_RGB_XRGB32 = 4,      /* x R G B (ARGB)                                                      */
+    M2V_RGB_XBGR32 = 5,      /* x B G R (ABGR)                                                      */
+    M2V_RGB_RGBP = 6         /* planar: R plane, G plane, B plane, W*H bytes each (a [3, H, W] image) */
+};
+/* The table above, readable without a GPU: coeff[9] row by row, *y_offset = o.  M2V_E_PARAM for an unknown matrix. */
+int m2v_rgb_matrix(int matrix, int coeff[9], int *y_offset);
+/*
+ * m2v_push_frames420 for `nframes` RGB frames, with every promise of it: parameters sampled on the first frame of a sequence only,
+ * frames dropped while the previous sequence is ending, M2V_E_STATE while a frame is partly filled by m2v_push_beats, page-locked
+ * sources cross the link from where they are (option "direct_upload", 2 and m2v_upload_wait included), anything else goes through the
+ * pinned staging.  The frames are converted on the device in front of the chunk's kernels.  RGB frames may alternate with 4:4:4
+ * frames, packed beats and 4:2:0 frames inside one sequence, and with RGB frames of another layout or matrix.  M2V_E_PARAM for an
+ * unknown layout or matrix.  Whole frames only: there are no RGB beats.
+ */
+int m2v_push_rgb(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count,
+                 const uint8_t *frames, size_t nframes, int layout, int matrix);
+
 /* `i_sequence_stop` pulse with i_en = 0 (RTL:1090-1091; SIM/tb_mpeg2encoder.v:249-252). A frame
  * in progress is completed with black pixels (RTL:1048-1056). No effect while idle. */
 int m2v_sequence_stop(m2v_enc *e);
@@ -146,6 +200,10 @@ long long m2v_push_frames_pull(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, u
 /* m2v_push_frames_pull for 4:2:0 frames (m2v_push_frames420 followed by m2v_pull into dst, in one call). */
 long long m2v_push_frames420_pull(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count,
                                   const uint8_t *frames420, size_t nframes, int layout, uint8_t *dst, size_t cap, int *last);
+
+/* m2v_push_frames_pull for RGB frames (m2v_push_rgb followed by m2v_pull into dst, in one call). */
+long long m2v_push_rgb_pull(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count,
+                            const uint8_t *frames, size_t nframes, int layout, int matrix, uint8_t *dst, size_t cap, int *last);
 
 /* Clamped geometry the module would use for (xsize16, ysize16) (RTL:985-1006). */
 int m2v_geometry(const m2v_enc *e, uint32_t xsize16, uint32_t ysize16, int *width, int *height);
@@ -182,6 +240,18 @@ int m2v_encode_resident420(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint3
                            size_t *out_bytes, void *hip_stream);
 int m2v_encode_resident420_begin(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count,
                                  const void *d_frames420, size_t nframes, int layout, void *d_out, size_t cap, void *hip_stream);
+/*
+ * The resident entries for RGB frames (M2V_RGB_* layout and matrix, W*H*bpp bytes each, back to back at the 16-byte aligned device
+ * pointer `d_frames`): each chunk is converted into the planar 4:4:4 buffer the handle owns, on the call's stream in front of the
+ * chunk's kernels.  Everything else as m2v_encode_resident / m2v_encode_resident_begin; the latter is answered by
+ * m2v_encode_resident_end.
+ */
+int m2v_encode_resident_rgb(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count,
+                            const void *d_frames, size_t nframes, int layout, int matrix, void *d_out, size_t cap,
+                            size_t *out_bytes, void *hip_stream);
+int m2v_encode_resident_rgb_begin(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count,
+                                  const void *d_frames, size_t nframes, int layout, int matrix, void *d_out, size_t cap,
+                                  void *hip_stream);
 
 /*
  * Strip mode (BASELINE config c5; no RTL counterpart — the RTL has one reference BRAM): several
@@ -415,7 +485,8 @@ int m2v_kernel_stats(const m2v_enc *e, int kernel, double *ms, double *units);
  *         1 = levels   int16  [frames][mbs][6][64] (zig-zag order)
  *         2 = mb bits  uint32 [frames][mbs]
  *         3 = recon    uint8  [frames][W*H*3/2]  (only frames that are referenced later; others 0)
- *         4 = the expanded 4:4:4 input of the last m2v_encode_resident420 call's last chunk, uint8 [frames][3*W*H]: a plain copy of
+ *         4 = the expanded 4:4:4 input of the last m2v_encode_resident420 / m2v_encode_resident_rgb call's last chunk (the converted
+ *             planes after an RGB call), uint8 [frames][3*W*H]: a plain copy of
  *             the handle's own buffer (either library answers it; M2V_E_STATE before the first such call has completed)
  *         5 = mb aux   uint32 [frames][mbs][4]: the record k_mb leaves next to the info word (either library).  Word 0 = bits of the
  *             slot's first segment | second << 16, word 1 = bits of the third | DC level of V << 16, word 2 = DC levels of the first |

@@ -3,6 +3,7 @@
 PSNR), optional PSNR against the source through the repo's decoder, optional PS / TS multiplexing.
 
     python tools/m2v_stats.py out.m2v [--yuv src.yuv [--i420 | --yv12 | --nv12 | --nv21]] [--ps out.mpg] [--ts out.ts]
+    python tools/m2v_stats.py out.m2v --yuv src.rgb [--rgb24 | --bgr24 | --rgbx | --bgrx | --xrgb | --xbgr | --rgbp] [--matrix bt601]
 """
 import argparse
 import os
@@ -20,6 +21,9 @@ def main():
     ap.add_argument("--yuv", help="planar yuv444p source (SIM/tb_mpeg2encoder.v:210-218 layout) for PSNR")
     for l in ("i420", "yv12", "nv12", "nv21"):
         ap.add_argument("--" + l, dest="layout", action="store_const", const=l, help="--yuv holds 4:2:0 frames in this layout (W*H*3/2 bytes each)")
+    for l in ("rgb24", "bgr24", "rgbx", "bgrx", "xrgb", "xbgr", "rgbp"):
+        ap.add_argument("--" + l, dest="layout", action="store_const", const=l, help="--yuv holds RGB frames in this layout (W*H*3 or W*H*4 bytes each)")
+    ap.add_argument("--matrix", default="bt601", choices=("bt601", "bt709", "bt601f", "bt709f"), help="the matrix the RGB frames were encoded with")
     ap.add_argument("--ps", help="write an MPEG-2 program stream")
     ap.add_argument("--ts", help="write an MPEG-2 transport stream")
     ap.add_argument("--pictures", action="store_true", help="one line per picture")
@@ -50,10 +54,14 @@ def main():
         dec = m2v_decode.decode(es, quirks=True)           # the encoder's own reconstruction (see fpga-mpeg2-encoder_amd/decoder.py)
         W, H = info.width, info.height
         src = np.fromfile(args.yuv, np.uint8)
-        fb = W * H * 3 // 2 if args.layout else 3 * W * H
+        rgb = args.layout in M.LAYOUTS_RGB
+        fb = W * H * M.rgb_bytes_per_pixel(args.layout) if rgb else W * H * 3 // 2 if args.layout else 3 * W * H
         n = min(src.size // fb, len(dec.frames))
         src = src[:n * fb].reshape(n, -1)
-        src = M.to444(src, W, H, args.layout) if args.layout else src.reshape(n, 3, H, W)
+        if rgb:
+            src = M.rgb_to444(src, W, H, args.layout, args.matrix)         # PSNR against the planes the encoder was given, by definition
+        else:
+            src = M.to444(src, W, H, args.layout) if args.layout else src.reshape(n, 3, H, W)
         ps = [m2v_decode.psnr(src[k, 0], dec.frames[k][0]) for k in range(n)]
         print("  luma PSNR over %d frames: mean %.2f dB  min %.2f dB" % (n, float(np.mean(ps)), float(np.min(ps))))
     if args.ps:
