@@ -1,7 +1,9 @@
 """Hand-built clips for corners of the RTL's arithmetic that seeded content does not reach (found by the mutation-kill matrix,
 tests/test_oracle_mutants.py: each of these was needed to catch one deliberate mis-reading).  Used three ways: by the second
 restatements of the RTL against the oracle (CPU), by the mutation test, and by the HIP path against the oracle (-m gpu,
-tests/test_gpu_corner_content.py).  Every function returns (clip [n, 3, H, W] uint8, pframes, VECTOR_LEVEL, Q_LEVEL)."""
+tests/test_gpu_corner_content.py).  Every function returns (clip [n, 3, H, W] uint8, pframes, VECTOR_LEVEL, Q_LEVEL).
+The corners of the motion search - every vector, the ties of the full-pel scan and of the ten-way decision, the masks at the frame's
+borders and at the end of the search range - live in tests/search_clips.py."""
 import numpy as np
 
 import m2v_load
