@@ -39,6 +39,7 @@ EXPORTS = [
     "m2v_comm_peer_stats", "m2v_comm_kind", "m2v_strip_last_form", "m2v_upload_wait", "m2v_device_pci_bus_id",
     "m2v_strip_encode_begin", "m2v_strip_encode_end",
     "m2v_rgb_matrix", "m2v_push_rgb", "m2v_push_rgb_pull", "m2v_encode_resident_rgb", "m2v_encode_resident_rgb_begin",
+    "m2v_set_frame_size", "m2v_fit_size",
 ]
 
 # the 4:2:0 entry points (kept apart: tests/test_abi.py matches EXPORTS against names of letters and underscores only)
@@ -172,6 +173,8 @@ def lib(debug=False):
             L.m2v_push_rgb_pull.argtypes = [vp, u32, u32, u32, vp, sz, ci, ci, vp, sz, ctypes.POINTER(ci)]
             L.m2v_encode_resident_rgb.argtypes = [vp, u32, u32, u32, vp, sz, ci, ci, vp, sz, ctypes.POINTER(sz), vp]
             L.m2v_encode_resident_rgb_begin.argtypes = [vp, u32, u32, u32, vp, sz, ci, ci, vp, sz, vp]
+            L.m2v_set_frame_size.argtypes = [vp, ci, ci, ci]
+            L.m2v_fit_size.argtypes = [ci, ci, ctypes.POINTER(u32), ctypes.POINTER(u32)]
         except AttributeError:
             # an OLDER build handed in through M2V_LIB for a same-box A/B (tools/ab.sh) may lack the newer entry points; the library of
             # this tree must have every one of them (tests/test_abi.py)
@@ -266,6 +269,66 @@ def rgb_to444(frames, W, H, layout="rgb24", matrix="bt601"):
     return out
 
 
+# ---- frames of any size (m2v_set_frame_size, include/m2v_mi355x.h) ----
+HEADER_MODES = {"module": 0, "true": 1}          # M2V_HEADER_*
+
+
+def fit_size(w, h):
+    """(xsize16, ysize16) of the whole macroblocks a w x h frame is padded to: ceil(/16) (m2v_fit_size)"""
+    if w < 1 or h < 1:
+        raise ValueError("fit_size: %d x %d" % (w, h))
+    return (w + 15) // 16, (h + 15) // 16
+
+
+def _planes(w, h, kind):
+    """the planes of a w x h frame of `kind` ("444", a name of LAYOUTS_420 or of LAYOUTS_RGB), in memory order:
+    [(element bytes, columns, rows, chroma?)]"""
+    cw, ch = (w + 1) // 2, (h + 1) // 2
+    if kind in ("444", "rgbp"):
+        return [(1, w, h, False)] * 3
+    if kind in ("i420", "yv12"):
+        return [(1, w, h, False), (1, cw, ch, True), (1, cw, ch, True)]
+    if kind in ("nv12", "nv21"):
+        return [(1, w, h, False), (2, cw, ch, True)]
+    if kind in LAYOUTS_RGB:
+        return [(_RGB_FORM[LAYOUTS_RGB[kind]][0], w, h, False)]
+    raise ValueError("unknown kind of frame %r" % (kind,))
+
+
+def frame_bytes(w, h, kind):
+    """bytes of one w x h source frame of `kind`: "444", a name of LAYOUTS_420 or a name of LAYOUTS_RGB"""
+    return sum(es * c * r for es, c, r, _ in _planes(w, h, kind))
+
+
+def pad_frames(frames, w, h, kind):
+    """w x h frames of `kind` -> [n, bytes] frames of the same kind at whole macroblocks, every plane extended to the right and then
+    downwards by its last column and its last row: the frames whose stream an encode with a frame size set equals by definition
+    (include/m2v_mi355x.h).  numpy, host side: a reference, not a fast path."""
+    xs, ys = fit_size(w, h)
+    W, H = 16 * xs, 16 * ys
+    f = np.ascontiguousarray(frames, np.uint8).reshape(-1, frame_bytes(w, h, kind))
+    n, out, at = f.shape[0], [], 0
+    for es, c, r, chroma in _planes(w, h, kind):
+        C, R = (W // 2, H // 2) if chroma else (W, H)
+        p = f[:, at:at + es * c * r].reshape(n, r, c, es)
+        at += es * c * r
+        out.append(np.pad(p, ((0, 0), (0, R - r), (0, C - c), (0, 0)), mode="edge").reshape(n, -1))
+    return np.ascontiguousarray(np.concatenate(out, axis=1))
+
+
+def set_header_size(stream, w, h):
+    """a copy of an encoder stream (bytes) with the four size fields rewritten: horizontal / vertical size of sequence_header (12 + 12
+    bits, bytes 4 - 6) and display size of sequence_display_extension (14 + 1 + 14 bits from byte 30).  What M2V_HEADER_TRUE writes."""
+    if not (0 < w < 4096 and 0 < h < 4096):
+        raise ValueError("set_header_size: %d x %d" % (w, h))
+    b = bytearray(stream)
+    assert bytes(b[0:4]) == b"\x00\x00\x01\xb3" and bytes(b[22:26]) == b"\x00\x00\x01\xb5" and b[26] >> 4 == 2, "not a stream of this encoder"
+    b[4:7] = ((w << 12) | h).to_bytes(3, "big")
+    keep = b[33] & 7
+    b[30:34] = ((((w << 15) | (1 << 14) | h) << 3) | keep).to_bytes(4, "big")
+    return bytes(b)
+
+
 def clamp_geometry(xsize16, ysize16, XL=7, YL=7):
     """Clamped (W, H) of RTL/mpeg2encoder.v:985-1006 (pure host arithmetic)."""
     def c(s, L):
@@ -308,6 +371,23 @@ class Mpeg2Encoder:
     def set_option(self, name, value):
         self._chk(self._L.m2v_set_option(self._h, name.encode(), int(value)), "m2v_set_option(%s)" % name)
 
+    def set_frame_size(self, w, h, header="module"):
+        """m2v_set_frame_size: from now on every whole-frame entry takes w x h frames in its own format and pads them on the device;
+        header "module" (the padded size in the stream's headers) or "true" (w x h).  (0, 0) switches it off.  Idle handles only."""
+        code = HEADER_MODES[header] if isinstance(header, str) else int(header)
+        self._chk(self._L.m2v_set_frame_size(self._h, int(w), int(h), code), "m2v_set_frame_size")
+        self._size = (int(w), int(h), code) if w or h else None
+
+    @property
+    def frame_size(self):
+        """(w, h, header code) set by set_frame_size, or None"""
+        return getattr(self, "_size", None)
+
+    def _fb(self, xsize16, ysize16, kind):
+        """bytes of one frame a whole-frame entry takes: of the size set, else of the clamped geometry"""
+        w, h = self._size[:2] if getattr(self, "_size", None) else self.geometry(xsize16, ysize16)
+        return frame_bytes(w, h, kind)
+
     def geometry(self, xsize16, ysize16):
         # (a handle's clamps are fixed at creation: asked once per size - the per-call bindings below are on a caller's critical path)
         got = self._geom.get((xsize16, ysize16))
@@ -344,58 +424,56 @@ class Mpeg2Encoder:
                                           code, int(bool(stop_with_last))), "m2v_push_packed")
 
     def push_frames(self, xsize16, ysize16, pframes_count, frames444):
-        W, H = self.geometry(xsize16, ysize16)
+        fb = self._fb(xsize16, ysize16, "444")
         f = self._flat_u8(frames444)
-        assert f.size % (3 * W * H) == 0
+        assert f.size % fb == 0
         self._chk(self._L.m2v_push_frames(self._h, xsize16, ysize16, pframes_count, f.ctypes.data,
-                                          f.size // (3 * W * H)), "m2v_push_frames")
+                                          f.size // fb), "m2v_push_frames")
 
     def push_frames_pull(self, xsize16, ysize16, pframes_count, frames444, dst, offset=0):
         """m2v_push_frames_pull: push_frames + pull_into(dst, offset) in one call, the stream bytes copied while the frames upload:
         -> (bytes written, last)"""
-        W, H = self.geometry(xsize16, ysize16)
+        fb = self._fb(xsize16, ysize16, "444")
         f = self._flat_u8(frames444)
-        assert f.size % (3 * W * H) == 0
+        assert f.size % fb == 0
         assert dst.dtype == np.uint8 and dst.flags["C_CONTIGUOUS"]
         last = ctypes.c_int(0)
-        n = self._chk(self._L.m2v_push_frames_pull(self._h, xsize16, ysize16, pframes_count, f.ctypes.data, f.size // (3 * W * H),
+        n = self._chk(self._L.m2v_push_frames_pull(self._h, xsize16, ysize16, pframes_count, f.ctypes.data, f.size // fb,
                                                    dst.ctypes.data + offset, (dst.size - offset) & ~31, ctypes.byref(last)), "m2v_push_frames_pull")
         return n, bool(last.value)
 
     def push_frames420(self, xsize16, ysize16, pframes_count, frames420, layout="i420"):
         """m2v_push_frames420: whole 4:2:0 frames (W*H*3/2 bytes each) in one of LAYOUTS_420"""
-        W, H = self.geometry(xsize16, ysize16)
+        fb = self._fb(xsize16, ysize16, "i420")
         f = self._flat_u8(frames420)
-        assert f.size % (W * H * 3 // 2) == 0
-        self._chk(self._L.m2v_push_frames420(self._h, xsize16, ysize16, pframes_count, f.ctypes.data, f.size // (W * H * 3 // 2),
+        assert f.size % fb == 0
+        self._chk(self._L.m2v_push_frames420(self._h, xsize16, ysize16, pframes_count, f.ctypes.data, f.size // fb,
                                              _layout420(layout)), "m2v_push_frames420")
 
     def push_frames420_pull(self, xsize16, ysize16, pframes_count, frames420, dst, offset=0, layout="i420"):
         """m2v_push_frames420_pull: push_frames420 + pull_into(dst, offset) in one call -> (bytes written, last)"""
-        W, H = self.geometry(xsize16, ysize16)
+        fb = self._fb(xsize16, ysize16, "i420")
         f = self._flat_u8(frames420)
-        assert f.size % (W * H * 3 // 2) == 0
+        assert f.size % fb == 0
         assert dst.dtype == np.uint8 and dst.flags["C_CONTIGUOUS"]
         last = ctypes.c_int(0)
-        n = self._chk(self._L.m2v_push_frames420_pull(self._h, xsize16, ysize16, pframes_count, f.ctypes.data, f.size // (W * H * 3 // 2),
+        n = self._chk(self._L.m2v_push_frames420_pull(self._h, xsize16, ysize16, pframes_count, f.ctypes.data, f.size // fb,
                                                       _layout420(layout), dst.ctypes.data + offset, (dst.size - offset) & ~31,
                                                       ctypes.byref(last)), "m2v_push_frames420_pull")
         return n, bool(last.value)
 
     def push_rgb(self, xsize16, ysize16, pframes_count, frames, layout="rgb24", matrix="bt601"):
         """m2v_push_rgb: whole RGB frames (W*H*3 or W*H*4 bytes each) in one of LAYOUTS_RGB, converted with one of MATRICES_RGB"""
-        W, H = self.geometry(xsize16, ysize16)
         f = self._flat_u8(frames)
-        fb = W * H * rgb_bytes_per_pixel(layout)
+        fb = self._fb(xsize16, ysize16, "rgb24" if rgb_bytes_per_pixel(layout) == 3 else "rgbx")
         assert f.size % fb == 0
         self._chk(self._L.m2v_push_rgb(self._h, xsize16, ysize16, pframes_count, f.ctypes.data, f.size // fb, _layout_rgb(layout),
                                        _matrix_rgb(matrix)), "m2v_push_rgb")
 
     def push_rgb_pull(self, xsize16, ysize16, pframes_count, frames, dst, offset=0, layout="rgb24", matrix="bt601"):
         """m2v_push_rgb_pull: push_rgb + pull_into(dst, offset) in one call -> (bytes written, last)"""
-        W, H = self.geometry(xsize16, ysize16)
         f = self._flat_u8(frames)
-        fb = W * H * rgb_bytes_per_pixel(layout)
+        fb = self._fb(xsize16, ysize16, "rgb24" if rgb_bytes_per_pixel(layout) == 3 else "rgbx")
         assert f.size % fb == 0
         assert dst.dtype == np.uint8 and dst.flags["C_CONTIGUOUS"]
         last = ctypes.c_int(0)
@@ -455,6 +533,11 @@ class Mpeg2Encoder:
                 self.push_frames420(xsize16, ysize16, pframes_count, frames444, layout)
             self.sequence_stop()
             return self.pull_all()
+        if getattr(self, "_size", None):
+            assert nbeats is None, "there are no partial frames while a frame size is set"
+            self.push_frames(xsize16, ysize16, pframes_count, frames444)
+            self.sequence_stop()
+            return self.pull_all()
         f = np.ascontiguousarray(frames444, np.uint8).reshape(-1, 3, H * W)
         bpf = W * H // 4
         total = f.shape[0] * bpf if nbeats is None else nbeats
@@ -507,11 +590,16 @@ class Mpeg2Encoder:
                                                         _layout_rgb(layout), _matrix_rgb(matrix), d_out_ptr, cap, stream),
                   "m2v_encode_resident_rgb_begin")
 
-    def encode_tensor(self, frames, pframes_count, order="rgb", matrix="bt601", out=None):
+    def encode_tensor(self, frames, pframes_count, order="rgb", matrix="bt601", out=None, header=None):
         """One whole sequence from a torch image tensor on the handle's device, in one call: contiguous uint8 [N, H, W, 3] (order
         "rgb" / "bgr"), [N, H, W, 4] ("rgbx" / "bgrx" / "xrgb" / "xbgr") or [N, 3, H, W] ("rgb": planar).  Runs
         m2v_encode_resident_rgb on torch's current stream and returns the stream bytes as a uint8 device tensor (a view of `out` when
-        given; M2VError when it is too small).  ValueError for any other tensor."""
+        given; M2VError when it is too small).  ValueError for any other tensor.
+        header = "true" or "module": H, W of any size the handle can pad to (set_frame_size for the duration of the call; the handle's
+        own setting is back afterwards), and what the stream's headers say of a size that is not whole macroblocks - "true": the
+        tensor's size, what a player is to show; "module": the padded size, the module's stream for the padded frames.  Without the
+        keyword H and W must be whole macroblocks, as ever: padding is asked for, never a surprise for a caller that relied on the
+        ValueError."""
         import torch
         if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4:
             raise ValueError("encode_tensor: a uint8 tensor of 4 dimensions is required")
@@ -530,15 +618,28 @@ class Mpeg2Encoder:
             layout, H, W = "rgbp", d2, d3
         else:
             raise ValueError("encode_tensor: shape %r does not go with order %r" % (tuple(frames.shape), order))
-        if H % 16 or W % 16 or self.geometry(W // 16, H // 16) != (W, H):
-            raise ValueError("encode_tensor: %d x %d is not a size of this handle (multiples of 16, 64 ... %d x 64 ... %d)"
+        if header is not None and header not in HEADER_MODES:
+            raise ValueError("encode_tensor: unknown header %r" % (header,))
+        xs, ys = (W + 15) // 16, (H + 15) // 16
+        if header is None and (H % 16 or W % 16):
+            raise ValueError("encode_tensor: %d x %d is not whole macroblocks; header=\"true\" or \"module\" pads it on the device" % (W, H))
+        if W < 1 or H < 1 or self.geometry(xs, ys) != (16 * xs, 16 * ys):
+            raise ValueError("encode_tensor: %d x %d does not pad to a size of this handle (64 ... %d x 64 ... %d)"
                              % (W, H, 16 << self.params[0], 16 << self.params[1]))
         if out is None:
-            out = torch.empty(N * 3 * W * H + (1 << 16), dtype=torch.uint8, device=frames.device)
+            out = torch.empty(N * 3 * 256 * xs * ys + (1 << 16), dtype=torch.uint8, device=frames.device)
         elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != frames.device or not out.is_contiguous() or out.dim() != 1:
             raise ValueError("encode_tensor: out must be a contiguous one-dimensional uint8 tensor on the frames' device")
-        nb = self.encode_resident_rgb(frames.data_ptr(), N, out.data_ptr(), out.numel(), W // 16, H // 16, pframes_count, layout, matrix,
-                                      stream=torch.cuda.current_stream(frames.device).cuda_stream)
+        before = self.frame_size
+        fit = bool(W % 16 or H % 16)
+        if fit or before:
+            self.set_frame_size(W if fit else 0, H if fit else 0, header if fit else "module")
+        try:
+            nb = self.encode_resident_rgb(frames.data_ptr(), N, out.data_ptr(), out.numel(), xs, ys, pframes_count, layout, matrix,
+                                          stream=torch.cuda.current_stream(frames.device).cuda_stream)
+        finally:
+            if fit or before:
+                self.set_frame_size(*(before or (0, 0, 0)))
         return out[:nb]
 
     def encode_resident_end(self):

@@ -486,7 +486,7 @@ void m2v_destroy(m2v_enc *e)
     (void)hipGetLastError();            // (a caller's stream that no longer exists: tolerated above, and not left behind as HIP's last error)
     e->d_coef.release(); e->d_mbaux.release(); e->d_slots.release(); e->d_slots_small.release(); e->d_mbinfo.release(); e->d_mblen.release();
     e->d_slice_bytes.release(); e->d_slice_off.release(); e->d_frame_off.release();
-    e->d_jobs.release(); e->d_lists.release(); e->d_joblist.release(); e->d_ctl.release(); e->d_segs.release(); e->d_x444.release();
+    e->d_jobs.release(); e->d_lists.release(); e->d_joblist.release(); e->d_ctl.release(); e->d_segs.release(); e->d_x444.release(); e->d_fit.release();
     for (auto p : e->rec_pool) (void)hipFree(p);
     for (auto &c : e->mbmaps) { if (c.ev) (void)hipEventDestroy(c.ev); c.d.release(); }
     for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
@@ -578,6 +578,36 @@ int m2v_geometry(const m2v_enc *e, uint32_t xsize16, uint32_t ysize16, int *widt
     return M2V_OK;
 }
 
+int m2v_fit_size(int width, int height, uint32_t *xsize16, uint32_t *ysize16)
+{
+    if (width < 1 || height < 1) return M2V_E_PARAM;
+    if (xsize16) *xsize16 = ((uint32_t)width + 15u) / 16u;
+    if (ysize16) *ysize16 = ((uint32_t)height + 15u) / 16u;
+    return M2V_OK;
+}
+
+int m2v_set_frame_size(m2v_enc *e, int width, int height, int header)
+{
+    if (!e) return M2V_E_PARAM;
+    if (e->state != m2v_enc::IDLE || e->resident_inflight || e->strip_active || e->strip_inflight) {
+        e->set_err("m2v_set_frame_size: a sequence is in progress (the size is sampled when a sequence starts)");
+        return M2V_E_STATE;
+    }
+    if (header != M2V_HEADER_MODULE && header != M2V_HEADER_TRUE) { e->set_err("m2v_set_frame_size: unknown header %d", header); return M2V_E_PARAM; }
+    // (what the last sequence sampled goes with the old setting: a sequence that beats start samples nothing, and only runs with no size set)
+    e->fit = SrcSize{};
+    e->hdr_true = false;
+    if (width == 0 && height == 0) { e->src_size = SrcSize{}; e->src_header = M2V_HEADER_MODULE; return M2V_OK; }
+    uint32_t xs = 0, ys = 0;
+    if (m2v_fit_size(width, height, &xs, &ys) != M2V_OK || xs < 4 || ys < 4 || xs > (1u << e->XL) || ys > (1u << e->YL)) {
+        e->set_err("m2v_set_frame_size: %d x %d does not pad to a size of this handle (64 ... %d by 64 ... %d)", width, height, 16 << e->XL, 16 << e->YL);
+        return M2V_E_PARAM;
+    }
+    e->src_size = SrcSize{width, height};
+    e->src_header = header;
+    return M2V_OK;
+}
+
 int m2v_set_option(m2v_enc *e, const char *name, long long value)
 {
     if (!e || !name) return M2V_E_PARAM;
@@ -657,7 +687,7 @@ static int debug_impl(m2v_enc *e, void *argp)
     auto *a = (DebugArgs *)argp;
     if (a->what == 4) {
         // the expanded / converted input of the last m2v_encode_resident420 / m2v_encode_resident_rgb call's last chunk, as its kernels read it
-        if (e->resident_inflight || !e->x444_bytes) { e->set_err("m2v_debug_read(4): no completed m2v_encode_resident420 / m2v_encode_resident_rgb call"); return M2V_E_STATE; }
+        if (e->resident_inflight || !e->x444_bytes) { e->set_err("m2v_debug_read(4): no completed m2v_encode_resident420 / m2v_encode_resident_rgb call (or m2v_encode_resident with a frame size set)"); return M2V_E_STATE; }
         if (e->x444_bytes > a->cap) return M2V_E_OVERFLOW;
         HIPCHK(hipMemcpy(a->dst, e->d_x444.p, e->x444_bytes, hipMemcpyDeviceToHost));
         a->ret = (long long)e->x444_bytes;

@@ -6,7 +6,7 @@
 //   m2v_core.hip      handle life cycle, options, geometry (RTL:985-1006), the chunk plan (GOP segments, reconstruction slots, launch
 //                     lists) and its execution: plan_chunk -> run_step* -> finish_chunk
 //   m2v_port.hip      the port path: beats in (RTL:1027-1095), 32-byte words out (RTL:2961-2994), double-buffered staging; the input
-//                     conversions in front of a chunk (k_unpack444, k_expand420, k_rgb2yuv: no device globals, so they can live here)
+//                     conversions in front of a chunk (k_unpack444, k_fit, k_expand420, k_rgb2yuv: no device globals, so they can live here)
 //   m2v_resident.hip  whole sequences resident in HBM (what bench.py times), one or several per call
 //   m2v_strips.hip    strip mode (BASELINE config c5) and the communicators of m2v_comm.hpp
 #pragma once
@@ -61,6 +61,8 @@ struct DevBuf {
 };
 
 struct KStat { int launches = 0; double ms = 0, units = 0; };
+struct SrcSize { int w = 0, h = 0; };       // pixels of a source frame; 0 x 0: the frames are W x H
+
 struct StripFlight;
 
 
@@ -111,7 +113,9 @@ struct m2v_enc {
         // linear run of bytes per chunk, frame after frame in arrival order, staged in pinned memory (or uploaded straight from
         // page-locked caller memory) and de-interleaved into d_in by k_unpack444 in front of the chunk's kernels
         // Whole 4:2:0 frames (m2v_push_frames420) are one more kind of run in the same bytes: kPk420 + M2V_420_*, expanded by k_expand420;
-        // whole RGB frames (m2v_push_rgb) another: pk_rgb(M2V_RGB_* layout, matrix), converted by k_rgb2yuv
+        // whole RGB frames (m2v_push_rgb) another: pk_rgb(M2V_RGB_* layout, matrix), converted by k_rgb2yuv.  While the sequence pads its
+        // frames (m2v_set_frame_size) every run holds frames of the SOURCE size, k_fit runs in front of the conversion, and whole planar
+        // 4:4:4 frames are a run kind too: kPk444
         struct PkFrame { uint32_t frame; int layout; size_t off; };       // chunk frame index, M2V_PACKED_* / kPk420 + M2V_420_* / pk_rgb(), where its bytes start in h_pk / d_pk
         std::vector<PkFrame> pk;
         uint8_t *h_pk = nullptr;              // pinned staging (only when packed beats come from ordinary memory)
@@ -242,6 +246,14 @@ struct m2v_enc {
     DevBuf<uint8_t> d_x444;
     size_t x444_bytes = 0;                // ... what the last call's last chunk left there (m2v_debug_read, what = 4)
 
+    // m2v_set_frame_size: the setting (0 x 0 = off), and what the sequence in progress sampled from it when it started: fit = the source
+    // size when the frames have to be padded (0 x 0 when not: no size set, or one of whole macroblocks), hdr_true = the headers say it
+    SrcSize src_size;
+    int src_header = M2V_HEADER_MODULE;
+    SrcSize fit;
+    bool hdr_true = false;
+    DevBuf<uint8_t> d_fit;                // padded frames in their own format, between k_fit and the conversion (no recording references it)
+
     // debug bookkeeping of the last resident encode
     size_t dbg_frames = 0;
     std::vector<int> dbg_rec_slot;
@@ -333,6 +345,20 @@ struct Timer {
 };
 
 // ---- m2v_port.hip ----
+// m2v_set_frame_size at the start of a sequence: false (M2V_E_PARAM, nothing started) when xs, ys are not m2v_fit_size's for the size set;
+// else samples e->fit / e->hdr_true
+bool sample_frame_size(m2v_enc *e, const char *fn, uint32_t xs, uint32_t ys);
+// the entries that take no frames of another size: true = refused (M2V_E_STATE) because a size is set
+inline bool size_refuses(m2v_enc *e, const char *fn, const char *why)
+{
+    if (!e->src_size.w) return false;
+    e->set_err("%s: a frame size is set (m2v_set_frame_size): %s", fn, why);
+    return true;
+}
+constexpr const char *kNoBeats = "the port has no partial macroblock, push whole frames";
+constexpr const char *kNoStrips = "strips take whole padded frames";
+// PkFrame::layout of a planar 4:4:4 frame of a sequence that pads its frames (no other planar frame travels as a run)
+constexpr int kPk444 = 8;
 // PkFrame::layout of a 4:2:0 frame is kPk420 + M2V_420_*
 constexpr int kPk420 = 16;
 inline bool layout420_ok(int layout) { return layout >= M2V_420_I420 && layout <= M2V_420_NV21; }
@@ -345,10 +371,12 @@ inline bool rgb_layout_ok(int layout) { return layout >= M2V_RGB_RGB24 && layout
 inline bool rgb_matrix_ok(int matrix) { return matrix >= M2V_RGB_BT601 && matrix <= M2V_RGB_BT709F; }
 inline int pk_rgb(int layout, int matrix) { return kPkRgb + 8 * matrix + layout; }
 inline int rgb_bpp(int layout) { return layout >= M2V_RGB_RGBX32 && layout <= M2V_RGB_XBGR32 ? 4 : 3; }
-// source bytes of one frame of a run kind (PkFrame::layout)
-size_t pk_frame_bytes(int kind, uint32_t ysz);
-// the frames of a 4:2:0 or RGB run kind (back to back at src) -> planar 4:4:4 frames of 3 * ysz bytes at dst.  src and dst 16-byte aligned.
-void launch_convert(hipStream_t s, int kind, const uint8_t *src, uint8_t *dst, const Geom &g, uint32_t nframes);
+// source bytes of one frame of a run kind (PkFrame::layout) whose frames are sz (0 x 0: W x H)
+size_t pk_frame_bytes(int kind, const Geom &g, SrcSize sz);
+// the frames of a 4:4:4 (kPk444), 4:2:0 or RGB run kind (back to back at src) -> planar 4:4:4 frames of 3 * ysz bytes at dst (16-byte
+// aligned).  e->fit set: the frames are of that size and are padded first (k_fit; src at any address), into e->d_fit or, 4:4:4, straight
+// into dst.  Else src is 16-byte aligned.
+void launch_convert(m2v_enc *e, hipStream_t s, int kind, const uint8_t *src, uint8_t *dst, uint32_t nframes);
 // nframes RGB frames (ysz * rgb_bpp(layout) bytes each) -> planar 4:4:4 by the integer transform of include/m2v_mi355x.h (k_rgb2yuv)
 void launch_rgb2yuv(hipStream_t s, int layout, int matrix, const uint8_t *src, uint8_t *dst, uint32_t ysz, uint32_t nframes);
 

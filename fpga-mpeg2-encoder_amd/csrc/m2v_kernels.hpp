@@ -1924,18 +1924,19 @@ __device__ inline void write_frame_headers(uint8_t *p, const FrameJob &job)
 }
 
 // sequence_header + sequence_extension + sequence_display_extension (RTL:2598-2617)
-__device__ inline void write_sequence_headers(uint8_t *p, const Geom &g)
+// width, height: the sizes to print - the coded W x H, or the source's where the caller asked for it (m2v_set_frame_size)
+__device__ inline void write_sequence_headers(uint8_t *p, int width, int height)
 {
     ByteWriter w{p, 0u, 0};
     w.put(0x000001B3u, 32);
-    w.put((uint32_t)g.W, 12); w.put((uint32_t)g.H, 12);
+    w.put((uint32_t)width, 12); w.put((uint32_t)height, 12);
     w.put(1u, 4); w.put(2u, 4); w.put(10000u, 18); w.put(1u, 1); w.put(0u, 10); w.put(0u, 3);
     w.put(0x000001B5u, 32);
     w.put(1u, 4); w.put(0x44u, 8); w.put(0u, 1); w.put(1u, 2); w.put(0u, 4); w.put(0u, 12); w.put(1u, 1);
     w.put(0u, 8); w.put(0u, 8);
     w.put(0x000001B5u, 32);
     w.put(2u, 4); w.put(1u, 3); w.put(1u, 1); w.put(5u, 8); w.put(5u, 8); w.put(5u, 8);
-    w.put((uint32_t)g.W, 14); w.put(1u, 1); w.put((uint32_t)g.H, 14);
+    w.put((uint32_t)width, 14); w.put(1u, 1); w.put((uint32_t)height, 14);
     w.align();
 }
 
@@ -1983,7 +1984,7 @@ __global__ __launch_bounds__(kAsmThreads, 8) void k_assemble(const FrameJob *__r
                                                  const unsigned long long *__restrict__ slice_off,
                                                  uint32_t *__restrict__ out32, const StreamCtl *__restrict__ ctl,
                                                  int first, int last, const unsigned long long *__restrict__ frame_off,
-                                                 const uint32_t *__restrict__ slice_bytes)
+                                                 const uint32_t *__restrict__ slice_bytes, int hdr_w, int hdr_h)
 {
     __shared__ uint32_t s_img[kAsmImageWords];
     __shared__ uint32_t s_slot[kAsmStageWords];
@@ -2121,7 +2122,7 @@ __global__ __launch_bounds__(kAsmThreads, 8) void k_assemble(const FrameJob *__r
     if (!g.strip && tid == 0) {
         uint8_t *const out8 = (uint8_t *)out32 + ctl->base_bytes;
         if (by == g.row0) {
-            if (first && f == 0) write_sequence_headers(out8, g);
+            if (first && f == 0) write_sequence_headers(out8, hdr_w, hdr_h);
             write_frame_headers(out8 + frame_off[f], jobs[f]);
         }
         if (last && f == nframes - 1 && by == g.row1 - 1) {
@@ -2427,7 +2428,7 @@ __global__ __launch_bounds__(kCopyThreads) void k_strip_assemble(const CopySeg *
             job.n = (uint32_t)f;
             write_frame_headers(out + frame_pos[f], job);
         }
-        if (f == 0) write_sequence_headers(out, g);
+        if (f == 0) write_sequence_headers(out, g.W, g.H);
         return;
     }
     // trailer: sequence_end_code + zero padding up to the stream length (RTL:2621-2628, 2932-2937)

@@ -235,14 +235,105 @@ __global__ __launch_bounds__(256) void k_rgb2yuv(const uint8_t *__restrict__ src
     }
 }
 
+// One plane of frames of any size -> the same plane at whole macroblocks, its last column repeated to the right and its last row
+// downwards (m2v_set_frame_size; numpy.pad(mode = "edge")).  A plane is cols x rows elements of ES bytes (1: a planar sample, 2: an
+// NV12 chroma pair, 3 / 4: an RGB pixel), padded to COLS x ROWS; the launch covers that plane of nframes frames, sstride / dstride
+// bytes apart.  One lane per 16 bytes of the padded plane, taken as one linear run: its rows are multiples of 16 bytes except the chroma
+// rows of I420 / YV12 (W / 2 bytes), where every other row starts in the middle of a lane's 16 bytes.
+//   - 16 bytes wholly inside the source's part of one row: one 16-byte load, from ANY address (a source row of 1918 RGB24 pixels is
+//     5754 bytes; global loads take unaligned addresses, at the price of a second cache line for some lanes), one aligned 16-byte store
+//   - anything else (the bytes around and beyond the last column, a lane that spans two rows): byte by byte with the element index
+//     clamped - for ES = 3 the phase of the 16 bytes against the pixels differs from lane to lane.  A few lanes per row.
+// Rows >= rows read source row rows - 1, never this kernel's output.  dst 16-byte aligned, COLS * ROWS * ES a multiple of 16.
+// HBM traffic: the source's bytes in, the padded frame's bytes out.  Offsets inside a plane fit 32 bits (2048 * 2048 * 4), the frame's
+// offset is 64 bits (96 such frames are 1.6 GB).
+struct FitLoad { uint32_t w[4]; } __attribute__((packed, aligned(1)));      // 16 bytes at any address
+
+template <int ES>
+__global__ __launch_bounds__(256) void k_fit(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, uint32_t cols, uint32_t rows, uint32_t COLS,
+                                             uint32_t ROWS, size_t sstride, size_t dstride, uint32_t nframes)
+{
+    const uint32_t srow = cols * ES, drow = COLS * ES, items = (drow * ROWS) >> 4;
+    for (uint32_t f = blockIdx.y; f < nframes; f += gridDim.y) {
+        const uint8_t *sf = src + (size_t)f * sstride;
+        uint8_t *df = dst + (size_t)f * dstride;
+        for (uint32_t t = blockIdx.x * 256u + threadIdx.x; t < items; t += gridDim.x * 256u) {
+            const uint32_t o = t * 16u, r = o / drow, x = o - r * drow;
+            uint4 v;
+            if (x + 16u <= srow) {
+                const FitLoad q = *(const FitLoad *)(sf + (size_t)min(r, rows - 1u) * srow + x);
+                v = make_uint4(q.w[0], q.w[1], q.w[2], q.w[3]);
+            } else {
+                uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+                for (uint32_t j = 0; j < 16u; ++j) {
+                    uint32_t rj = r, xj = x + j;
+                    if (xj >= drow) { xj -= drow; ++rj; }                  // (a row is at least 32 bytes: one wrap at most)
+                    const uint32_t el = xj / ES, b = xj - el * ES;
+                    w[j >> 2] |= (uint32_t)sf[(size_t)min(rj, rows - 1u) * srow + min(el, cols - 1u) * ES + b] << (8 * (j & 3));
+                }
+                v = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+            *(uint4 *)(df + o) = v;
+        }
+    }
+}
+
+template <int ES>
+void launch_fit(hipStream_t s, const uint8_t *src, uint8_t *dst, uint32_t cols, uint32_t rows, uint32_t COLS, uint32_t ROWS, size_t sstride,
+                size_t dstride, uint32_t nframes)
+{
+    const uint32_t items = (COLS * ES * ROWS) >> 4;
+    const dim3 grid(std::min<uint32_t>((items + 255u) / 256u, 1024u), std::min<uint32_t>(nframes, 32768u)), block(256);
+    hipLaunchKernelGGL((k_fit<ES>), grid, block, 0, s, src, dst, cols, rows, COLS, ROWS, sstride, dstride, nframes);
+    HIPCHK(hipGetLastError());
+}
+
+// bytes per pixel of a run kind whose frames are ONE plane of pixels (packed RGB); 0 for the planar kinds
+int pk_pixel_bytes(int kind)
+{
+    if (kind < kPkRgb) return 0;
+    const int layout = (kind - kPkRgb) & 7;
+    return layout == M2V_RGB_RGBP ? 0 : rgb_bpp(layout);
+}
+
 }  // namespace
 
-size_t pk_frame_bytes(int kind, uint32_t ysz)
+size_t pk_frame_bytes(int kind, const Geom &g, SrcSize sz)
 {
     PackedFmt f{};
-    if (kind >= kPkRgb) return (size_t)ysz * (size_t)rgb_bpp((kind - kPkRgb) & 7);
-    if (packed_fmt(kind, f)) return (size_t)ysz * (size_t)f.stride;
-    return (size_t)ysz + (ysz >> 1);
+    const size_t px = sz.w ? (size_t)sz.w * (size_t)sz.h : (size_t)g.ysz;
+    if (kind >= kPkRgb) return px * (size_t)rgb_bpp((kind - kPkRgb) & 7);
+    if (kind == kPk444) return px * 3;
+    if (packed_fmt(kind, f)) return px * (size_t)f.stride;
+    if (sz.w) return px + 2 * (size_t)((sz.w + 1) / 2) * (size_t)((sz.h + 1) / 2);
+    return (size_t)g.ysz + (g.ysz >> 1);
+}
+
+// nframes frames of w x h (sz) in the form of a run kind, back to back at src -> the same form at W x H, back to back at dst (16-byte
+// aligned): one k_fit launch per plane
+static void launch_fit_frames(hipStream_t s, int kind, const uint8_t *src, uint8_t *dst, const Geom &g, SrcSize sz, uint32_t nframes)
+{
+    const uint32_t w = (uint32_t)sz.w, h = (uint32_t)sz.h, W = (uint32_t)g.W, H = (uint32_t)g.H;
+    const size_t px = (size_t)w * h, sfb = pk_frame_bytes(kind, g, sz), dfb = pk_frame_bytes(kind, g, SrcSize{0, 0});
+    if (const int bpp = pk_pixel_bytes(kind)) {
+        if (bpp == 3) launch_fit<3>(s, src, dst, w, h, W, H, sfb, dfb, nframes);
+        else launch_fit<4>(s, src, dst, w, h, W, H, sfb, dfb, nframes);
+        return;
+    }
+    launch_fit<1>(s, src, dst, w, h, W, H, sfb, dfb, nframes);                                       // Y, or R
+    if (kind >= kPkRgb || kind == kPk444) {
+        for (int c = 1; c < 3; ++c) launch_fit<1>(s, src + c * px, dst + (size_t)c * g.ysz, w, h, W, H, sfb, dfb, nframes);
+        return;
+    }
+    const uint32_t cw = (w + 1) / 2, ch = (h + 1) / 2;
+    const int layout = kind - kPk420;
+    if (layout == M2V_420_NV12 || layout == M2V_420_NV21) {
+        launch_fit<2>(s, src + px, dst + g.ysz, cw, ch, W / 2, H / 2, sfb, dfb, nframes);
+    } else {
+        launch_fit<1>(s, src + px, dst + g.ysz, cw, ch, W / 2, H / 2, sfb, dfb, nframes);
+        launch_fit<1>(s, src + px + (size_t)cw * ch, dst + g.ysz + (g.ysz >> 2), cw, ch, W / 2, H / 2, sfb, dfb, nframes);
+    }
 }
 
 void launch_rgb2yuv(hipStream_t s, int layout, int matrix, const uint8_t *src, uint8_t *dst, uint32_t ysz, uint32_t nframes)
@@ -265,10 +356,44 @@ void launch_rgb2yuv(hipStream_t s, int layout, int matrix, const uint8_t *src, u
     HIPCHK(hipGetLastError());
 }
 
-void launch_convert(hipStream_t s, int kind, const uint8_t *src, uint8_t *dst, const Geom &g, uint32_t nframes)
+static void convert_run(hipStream_t s, int kind, const uint8_t *src, uint8_t *dst, const Geom &g, uint32_t nframes)
 {
     if (kind >= kPkRgb) launch_rgb2yuv(s, (kind - kPkRgb) & 7, (kind - kPkRgb) >> 3, src, dst, g.ysz, nframes);
     else launch_expand420(s, kind - kPk420, src, dst, g, nframes);
+}
+
+void launch_convert(m2v_enc *e, hipStream_t s, int kind, const uint8_t *src, uint8_t *dst, uint32_t nframes)
+{
+    const Geom &g = e->g;
+    if (!e->fit.w) { convert_run(s, kind, src, dst, g, nframes); return; }
+    if (kind == kPk444) { launch_fit_frames(s, kind, src, dst, g, e->fit, nframes); return; }
+    // the padded frames wait in a buffer of the handle's for the conversion behind them on the same stream; a long run takes turns in
+    // 128 MB of it (twenty 1920 x 1088 RGB24 frames)
+    const size_t sfb = pk_frame_bytes(kind, g, e->fit), dfb = pk_frame_bytes(kind, g, SrcSize{});
+    const uint32_t part = (uint32_t)std::min<size_t>(nframes, std::max<size_t>(1, ((size_t)128 << 20) / dfb));
+    e->d_fit.recorded = false;
+    e->d_fit.ensure((size_t)part * dfb);
+    for (uint32_t k = 0; k < nframes; k += part) {
+        const uint32_t n = std::min(part, nframes - k);
+        launch_fit_frames(s, kind, src + (size_t)k * sfb, e->d_fit.p, g, e->fit, n);
+        convert_run(s, kind, e->d_fit.p, dst + (size_t)k * g.ysz * 3, g, n);
+    }
+}
+
+bool sample_frame_size(m2v_enc *e, const char *fn, uint32_t xs, uint32_t ys)
+{
+    e->fit = SrcSize{};
+    e->hdr_true = false;
+    const SrcSize z = e->src_size;
+    if (!z.w) return true;
+    uint32_t fx = 0, fy = 0;
+    (void)m2v_fit_size(z.w, z.h, &fx, &fy);
+    if (xs != fx || ys != fy) {
+        e->set_err("%s: xsize16, ysize16 = %u, %u, but the frame size set is %d x %d (m2v_fit_size: %u, %u)", fn, xs, ys, z.w, z.h, fx, fy);
+        return false;
+    }
+    if ((z.w | z.h) & 15) { e->fit = z; e->hdr_true = e->src_header == M2V_HEADER_TRUE; }
+    return true;
 }
 
 void launch_expand420(hipStream_t s, int layout, const uint8_t *src, uint8_t *dst, const Geom &g, uint32_t nframes)
@@ -407,12 +532,12 @@ void flush_buffered(m2v_enc *e, bool last)
         timer_break(e);
         for (size_t a = 0; a < h.pk.size();) {          // runs of consecutive frames of one layout: one launch each
             const int layout = h.pk[a].layout;
-            const size_t src_bytes = pk_frame_bytes(layout, g.ysz);
+            const size_t src_bytes = pk_frame_bytes(layout, g, e->fit);
             size_t b = a + 1;
             while (b < h.pk.size() && h.pk[b].layout == layout && h.pk[b].frame == h.pk[a].frame + (b - a) &&
                    h.pk[b].off == h.pk[a].off + (b - a) * src_bytes) ++b;
             uint8_t *to = h.d_in.p + (size_t)h.pk[a].frame * frame_bytes;
-            if (layout >= kPk420) launch_convert(s, layout, h.d_pk.p + h.pk[a].off, to, g, (uint32_t)(b - a));
+            if (layout >= kPk444) launch_convert(e, s, layout, h.d_pk.p + h.pk[a].off, to, (uint32_t)(b - a));
             else launch_unpack(s, layout, h.d_pk.p + h.pk[a].off, to, g.ysz, (uint32_t)(b - a));
             a = b;
         }
@@ -555,6 +680,7 @@ static void pk_put(m2v_enc *e, m2v_enc::HostStage &h, size_t off, const uint8_t 
 static int push_beats_impl(m2v_enc *e, void *argp)
 {
     auto *a = (PushBeatsArgs *)argp;
+    if (size_refuses(e, a->src.kind ? "m2v_push_packed" : "m2v_push_beats", kNoBeats)) return M2V_E_STATE;
     if (e->strip_active) { e->set_err("m2v_push_*: a strip sequence is open (m2v_strip_finish or m2v_reset first)"); return M2V_E_STATE; }
     if (e->resident_inflight) { e->set_err("m2v_push_*: a resident sequence is in flight (m2v_encode_resident_end first)"); return M2V_E_STATE; }
     if (e->strip_inflight) { e->set_err("m2v_push_*: a strip sequence is in flight (m2v_strip_encode_end first)"); return M2V_E_STATE; }
@@ -715,10 +841,14 @@ static int push_frames_impl(m2v_enc *e, void *argp)
             if (e->upl_pending[k]) { HIPCHK(hipEventSynchronize(e->ev_upl[k])); e->upl_pending[k] = false; }
     };
     if (e->state == m2v_enc::ENDED || a->n == 0) { settle_deferred(); return M2V_OK; }
-    if (e->state == m2v_enc::IDLE) start_sequence(e, a->xs, a->ys, a->pf);
+    if (e->state == m2v_enc::IDLE) {
+        if (!sample_frame_size(e, "m2v_push_frames", a->xs, a->ys)) { settle_deferred(); return M2V_E_PARAM; }
+        start_sequence(e, a->xs, a->ys, a->pf);
+    }
     const Geom &g = e->g;
-    const bool is420 = a->kind >= 0;              // (or RGB: any kind that goes through the packed bytes)
-    const size_t fb = is420 ? pk_frame_bytes(a->kind, g.ysz) : (size_t)g.ysz * 3;      // the caller's bytes per frame
+    const int kind = a->kind < 0 && e->fit.w ? kPk444 : a->kind;       // (planar 4:4:4 frames that have to be padded are a run too)
+    const bool is420 = kind >= 0;                 // (or RGB: any kind that goes through the packed bytes)
+    const size_t fb = is420 ? pk_frame_bytes(kind, g, e->fit) : (size_t)g.ysz * 3;      // the caller's bytes per frame
     if (e->beat_pos != 0) {
         settle_deferred();
         e->set_err("m2v_push_frames: a frame is partially filled by m2v_push_beats");
@@ -746,7 +876,7 @@ static int push_frames_impl(m2v_enc *e, void *argp)
             // complete frames are buffered)
             if (!pk_room(e, h, take * fb, fb)) { flush_buffered(e, false); continue; }
             pk_off = h.pk_used;
-            for (size_t j = 0; j < take; ++j) h.pk.push_back({(uint32_t)(e->buffered + j), a->kind, pk_off + j * fb});
+            for (size_t j = 0; j < take; ++j) h.pk.push_back({(uint32_t)(e->buffered + j), kind, pk_off + j * fb});
             h.pk_used += take * fb;
             h.pk_valid = h.pk_used;
         }

@@ -32,6 +32,7 @@ static int resident_impl(m2v_enc *e, void *argp)
         e->resident_empty = a->async;                   // only _begin leaves an _end to answer
         return M2V_OK;
     }
+    if (!sample_frame_size(e, "m2v_encode_resident", a->xs, a->ys)) return M2V_E_PARAM;
     hipStream_t s = a->s ? a->s : e->stream;
     e->g = make_geom(e, a->xs, a->ys);
     e->pframes = a->pf & 0xFFu;
@@ -47,8 +48,9 @@ static int resident_impl(m2v_enc *e, void *argp)
     // align chunks to GOP boundaries so every chunk starts with an I frame where possible
     const size_t gop = e->pframes + 1u;
     size_t step = chunk >= gop ? chunk / gop * gop : chunk;
-    const bool is420 = a->kind >= 0;              // (or RGB)
-    const size_t fb420 = is420 ? pk_frame_bytes(a->kind, g.ysz) : 0;
+    const int kind = a->kind < 0 && e->fit.w ? kPk444 : a->kind;       // (planar 4:4:4 frames that have to be padded: through the handle's buffer too)
+    const bool is420 = kind >= 0;                 // (or RGB)
+    const size_t fb420 = is420 ? pk_frame_bytes(kind, g, e->fit) : 0;
     if (is420) {
         // each chunk's frames are expanded or converted into planar 4:4:4 in front of its kernels, on the same stream; one buffer is enough because
         // the chunks are synchronised below
@@ -61,7 +63,7 @@ static int resident_impl(m2v_enc *e, void *argp)
         const uint8_t *frames = is420 ? nullptr : a->d_in + k * fb;
         if (is420) {
             timer_break(e);
-            launch_convert(s, a->kind, a->d_in + k * fb420, e->d_x444.p, g, (uint32_t)nf);
+            launch_convert(e, s, kind, a->d_in + k * fb420, e->d_x444.p, (uint32_t)nf);
             e->x444_bytes = nf * fb;
             frames = e->d_x444.p;
         }

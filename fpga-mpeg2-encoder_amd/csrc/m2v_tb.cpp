@@ -2,8 +2,12 @@
 //
 //   m2v_tb [-XL n] [-YL n] [-VL n] [-Q n] [-p pframes] [-d device] [-bubbles] [-conformant] [-ps] [-ts]
 //          [-i420 | -yv12 | -nv12 | -nv21 | -rgb24 | -bgr24 | -rgbx | -bgrx | -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f]
+//          [-pad | -truesize]
 //          in.yuv W H out.m2v  [in2.yuv W2 H2 out2.m2v ...]
 //
+// -pad: W, H are any size from 49 up; the files hold frames of that size in the chosen format, which are padded to whole macroblocks on
+// the device (m2v_set_frame_size) - the stream is the module's for the padded frames.  -truesize: -pad, and the stream's headers say
+// W x H instead of the padded size (M2V_HEADER_TRUE; not the module's header).  Neither goes with -bubbles: there are no partial macroblocks.
 // -i420 / -yv12 / -nv12 / -nv21: the input files hold 4:2:0 frames of W*H*3/2 bytes in that layout (what ordinary tools write) instead
 // of the testbench's planar 4:4:4 frames; they go in through m2v_push_frames420.  At most one of the four.
 // -rgb24 / -bgr24 / -rgbx / -bgrx / -xrgb / -xbgr / -rgbp: the input files (.rgb, .bgra, ...) hold RGB frames of W*H*3 or W*H*4 bytes in that
@@ -31,13 +35,15 @@
 int main(int argc, char **argv)
 {
     int XL = 7, YL = 6, VL = 3, Q = 2, pf = 23, dev = 0, bubbles = 0, conformant = 0, want_ps = 0, want_ts = 0, layout420 = -1, layouts = 0, rgb = -1, matrix = M2V_RGB_BT601,
-        bad_matrix = 0;
+        bad_matrix = 0, pad = 0, truesize = 0;
     int i = 1;
     for (; i < argc && argv[i][0] == '-'; ++i) {
         if (!strcmp(argv[i], "-bubbles")) { bubbles = 1; continue; }
         if (!strcmp(argv[i], "-conformant")) { conformant = 1; continue; }
         if (!strcmp(argv[i], "-ps")) { want_ps = 1; continue; }
         if (!strcmp(argv[i], "-ts")) { want_ts = 1; continue; }
+        if (!strcmp(argv[i], "-pad")) { pad = 1; continue; }
+        if (!strcmp(argv[i], "-truesize")) { pad = truesize = 1; continue; }
         if (!strcmp(argv[i], "-i420")) { layout420 = M2V_420_I420; ++layouts; continue; }
         if (!strcmp(argv[i], "-yv12")) { layout420 = M2V_420_YV12; ++layouts; continue; }
         if (!strcmp(argv[i], "-nv12")) { layout420 = M2V_420_NV12; ++layouts; continue; }
@@ -61,9 +67,9 @@ int main(int argc, char **argv)
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
         ++i;
     }
-    if ((argc - i) < 4 || (argc - i) % 4 || layouts > 1 || bad_matrix || (layouts && bubbles)) {          // (there are no 4:2:0 or RGB beats)
+    if ((argc - i) < 4 || (argc - i) % 4 || layouts > 1 || bad_matrix || ((layouts || pad) && bubbles)) {          // (there are no 4:2:0 or RGB beats)
         fprintf(stderr, "usage: %s [-XL n] [-YL n] [-VL n] [-Q n] [-p pframes] [-d dev] [-i420 | -yv12 | -nv12 | -nv21 | -rgb24 | -bgr24 | -rgbx | -bgrx |"
-                        " -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f] in.yuv W H out.m2v ...\n", argv[0]);
+                        " -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f] [-pad | -truesize] in.yuv W H out.m2v ...\n", argv[0]);
         return 2;
     }
     int err = 0;
@@ -80,15 +86,24 @@ int main(int argc, char **argv)
         if (!fi) { printf("*** couldn't open input file\n"); return 1; }                       // TB:175-180
         FILE *fo = fopen(out, "wb");
         if (!fo) { printf("*** couldn't open output file\n"); return 1; }                      // TB:182-187
-        if (xsize < 64 || xsize > (16 << XL) || xsize % 16) {                                  // TB:189-194
+        uint32_t xs16 = (uint32_t)xsize / 16, ys16 = (uint32_t)ysize / 16;
+        if (pad) {
+            if (xsize < 49 || xsize > (16 << XL)) { printf("*** xsize=%4d is invalid, which must in range [49,%4d] with -pad\n", xsize, 16 << XL); return 1; }
+            if (ysize < 49 || ysize > (16 << YL)) { printf("*** ysize=%4d is invalid, which must in range [49,%4d] with -pad\n", ysize, 16 << YL); return 1; }
+            if (m2v_fit_size(xsize, ysize, &xs16, &ys16) < 0 || m2v_set_frame_size(e, xsize, ysize, truesize ? M2V_HEADER_TRUE : M2V_HEADER_MODULE) < 0) {
+                fprintf(stderr, "*** m2v_set_frame_size: %s\n", m2v_last_error(e));
+                return 1;
+            }
+        }
+        if (!pad && (xsize < 64 || xsize > (16 << XL) || xsize % 16)) {                        // TB:189-194
             printf("*** xsize=%4d is invalid, which must in range [64,%4d], and must be a multiple of 16\n", xsize, 16 << XL);
             return 1;
         }
-        if (ysize < 64 || ysize > (16 << YL) || ysize % 16) {                                  // TB:196-201
+        if (!pad && (ysize < 64 || ysize > (16 << YL) || ysize % 16)) {                        // TB:196-201
             printf("*** ysize=%4d is invalid, which must in range [64,%4d], and must be a multiple of 16\n", ysize, 16 << YL);
             return 1;
         }
-        const size_t fb = layout420 >= 0 ? (size_t)xsize * ysize * 3 / 2
+        const size_t fb = layout420 >= 0 ? (size_t)xsize * ysize + 2 * (size_t)((xsize + 1) / 2) * (size_t)((ysize + 1) / 2)
                                          : (size_t)xsize * ysize * (rgb >= M2V_RGB_RGBX32 && rgb <= M2V_RGB_XBGR32 ? 4 : 3);
         std::vector<uint8_t> frame(fb), word(1 << 20), es;
         size_t frames = 0, bytes = 0;
@@ -111,11 +126,11 @@ int main(int argc, char **argv)
             printf("  start to encode video %d frame %3zu\n", num_video, frames);
             int r;
             if (rgb >= 0) {
-                r = m2v_push_rgb(e, (uint32_t)xsize / 16, (uint32_t)ysize / 16, (uint32_t)pf, frame.data(), 1, rgb, matrix);
+                r = m2v_push_rgb(e, xs16, ys16, (uint32_t)pf, frame.data(), 1, rgb, matrix);
             } else if (layout420 >= 0) {
-                r = m2v_push_frames420(e, (uint32_t)xsize / 16, (uint32_t)ysize / 16, (uint32_t)pf, frame.data(), 1, layout420);
+                r = m2v_push_frames420(e, xs16, ys16, (uint32_t)pf, frame.data(), 1, layout420);
             } else if (!bubbles) {
-                r = m2v_push_frames(e, (uint32_t)xsize / 16, (uint32_t)ysize / 16, (uint32_t)pf, frame.data(), 1);
+                r = m2v_push_frames(e, xs16, ys16, (uint32_t)pf, frame.data(), 1);
             } else {                                                                           // beat-level, odd batch sizes
                 const size_t npix = (size_t)xsize * ysize;
                 size_t b = 0, nb = npix / 4;
@@ -123,7 +138,7 @@ int main(int argc, char **argv)
                 while (b < nb && r == 0) {
                     size_t take = 1 + (b * 7919) % 61;
                     if (take > nb - b) take = nb - b;
-                    r = m2v_push_beats(e, (uint32_t)xsize / 16, (uint32_t)ysize / 16, (uint32_t)pf, frame.data() + b * 4,
+                    r = m2v_push_beats(e, xs16, ys16, (uint32_t)pf, frame.data() + b * 4,
                                        frame.data() + npix + b * 4, frame.data() + 2 * npix + b * 4, take, 0);
                     b += take;
                 }

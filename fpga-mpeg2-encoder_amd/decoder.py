@@ -269,8 +269,11 @@ def decode(data, quirks=True):
     dh = br.bits(14)
     assert (dw, dh) == (out.width, out.height)
     out.sequence = hdr
-    W, H = out.width, out.height
-    mbw, mbh = W // 16, H // 16
+    # the header sizes are the displayable ones (6.3.3): the macroblock count rounds them up, the pictures are coded at whole
+    # macroblocks and handed out cropped to width x height (chroma to the halves, rounded up)
+    mbw, mbh = (out.width + 15) // 16, (out.height + 15) // 16
+    W, H = 16 * mbw, 16 * mbh
+    cw, ch = (out.width + 1) // 2, (out.height + 1) // 2
     ref = None
     ended = False
     while True:
@@ -422,7 +425,8 @@ def decode(data, quirks=True):
             pad = (-br.pos) & 7
             assert br.peek(pad) == 0 if pad else True
         ref = (Y, U, V)
-        out.frames.append(tuple(p.astype(np.uint8) for p in ref))
+        out.frames.append(tuple(np.ascontiguousarray(p[:r, :c]).astype(np.uint8)
+                                for p, r, c in zip(ref, (out.height, ch, ch), (out.width, cw, cw))))
         out.mbs.append(mbs)
     assert ended
     rest = data[(br.pos + 7) >> 3:]

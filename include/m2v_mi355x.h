@@ -166,6 +166,48 @@ int m2v_rgb_matrix(int matrix, int coeff[9], int *y_offset);
 int m2v_push_rgb(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pframes_count,
                  const uint8_t *frames, size_t nframes, int layout, int matrix);
 
+/*
+ * Frames of any size.  The module takes whole macroblocks only, and its README tells the user to pad ("a 1910x1080 video should be
+ * padded to 1920x1088").  With a size set, every whole-frame entry - m2v_push_frames, m2v_push_frames420, m2v_push_rgb and their _pull
+ * forms, m2v_encode_resident, m2v_encode_resident420, m2v_encode_resident_rgb and their _begin forms - takes frames of width x height
+ * pixels in its own format and pads them on the device (k_fit) in front of what it did before; only the source's bytes cross the link.
+ *
+ * DEFINITION.  W = 16 * ceil(width / 16), H = 16 * ceil(height / 16).  The padded frame has the format of the source; every plane is
+ * extended to the right and then downwards by repeating its last column and its last row (numpy.pad(..., mode = "edge")):
+ *
+ *     planar 4:4:4        Y, U, V: 1 byte, width x height                                     -> W x H
+ *     I420 / YV12         Y: 1 byte, width x height; two chroma planes: 1 byte, cw x ch       -> W x H; W/2 x H/2
+ *     NV12 / NV21         Y: 1 byte, width x height; one plane of 2-byte pairs, cw x ch       -> W x H; W/2 x H/2
+ *     RGB24 / BGR24       one plane of 3-byte pixels, width x height                          -> W x H
+ *     RGBX32 ... XBGR32   one plane of 4-byte pixels (the ignored byte travels with its pixel)   -> W x H
+ *     RGBP                R, G, B: 1 byte, width x height                                     -> W x H
+ *
+ * cw = (width + 1) / 2, ch = (height + 1) / 2 (integer division; odd sizes are legal), so a 4:2:0 source frame is
+ * width * height + 2 * cw * ch bytes.  4:2:0 chroma is padded in the 4:2:0 domain, before the 2 x 2 repeat.  Frames lie back to back
+ * with no alignment between them; only the base pointer of a resident 4:2:0 or RGB call keeps its 16-byte rule.  The stream is byte
+ * for byte the stream of those padded frames at xsize16 = W / 16, ysize16 = H / 16, and the call that starts a sequence must pass
+ * exactly these (m2v_fit_size): anything else is M2V_E_PARAM with nothing started.
+ *
+ * header: what sequence_header (12 + 12 bits, stream bytes 4 - 6) and sequence_display_extension (14 + 1 + 14 bits from byte 30) say.
+ *     M2V_HEADER_MODULE   W x H, as the module fed the padded frames writes it: a player shows the padding
+ *     M2V_HEADER_TRUE     width x height in those four fields and no other bit of the stream differs.  NOT the module's behaviour
+ *                         (like option "conformant"): ISO/IEC 13818-2 defines the fields as the displayable size and derives the
+ *                         macroblock count by rounding up, so this is the conformant stream of, say, a 1080-line picture.
+ *     Caveat, documented and not acted on: the module sets progressive_sequence = 0, and under that setting ISO derives the macroblock
+ *     rows as 2 * ceil(height / 32).  That equals the coded ceil(height / 16) rows only where the latter is even (1080 -> 68: yes).
+ *     The same already holds for the module's own streams with an odd number of macroblock rows.
+ *
+ * Only while the handle is idle (M2V_E_STATE otherwise); the setting stays until it is changed, m2v_reset keeps it, (0, 0, x) switches
+ * it off.  M2V_E_PARAM for a negative size, for one size zero and the other not, for a padded size outside 64 ... 16 << XL by
+ * 64 ... 16 << YL (so width, height >= 49), and for an unknown header.  A size of whole macroblocks launches no padding pass and
+ * behaves as no size set.  While a size is set m2v_push_beats, m2v_push_packed and every m2v_strip_* entry that starts something answer
+ * M2V_E_STATE: the port has no partial macroblock, and strips take whole padded frames.
+ */
+enum { M2V_HEADER_MODULE = 0, M2V_HEADER_TRUE = 1 };
+int m2v_set_frame_size(m2v_enc *e, int width, int height, int header);
+/* xsize16 = ceil(width / 16), ysize16 = ceil(height / 16): pure arithmetic, no GPU.  M2V_E_PARAM for a size below 1. */
+int m2v_fit_size(int width, int height, uint32_t *xsize16, uint32_t *ysize16);
+
 /* `i_sequence_stop` pulse with i_en = 0 (RTL:1090-1091; SIM/tb_mpeg2encoder.v:249-252). A frame
  * in progress is completed with black pixels (RTL:1048-1056). No effect while idle. */
 int m2v_sequence_stop(m2v_enc *e);
@@ -487,7 +529,8 @@ int m2v_kernel_stats(const m2v_enc *e, int kernel, double *ms, double *units);
  *         3 = recon    uint8  [frames][W*H*3/2]  (only frames that are referenced later; others 0)
  *         4 = the expanded 4:4:4 input of the last m2v_encode_resident420 / m2v_encode_resident_rgb call's last chunk (the converted
  *             planes after an RGB call), uint8 [frames][3*W*H]: a plain copy of
- *             the handle's own buffer (either library answers it; M2V_E_STATE before the first such call has completed)
+ *             the handle's own buffer (either library answers it; M2V_E_STATE before the first such call has completed).  With a frame
+ *             size set (m2v_set_frame_size) the planes are the padded ones, and m2v_encode_resident's frames pass through that buffer too
  *         5 = mb aux   uint32 [frames][mbs][4]: the record k_mb leaves next to the info word (either library).  Word 0 = bits of the
  *             slot's first segment | second << 16, word 1 = bits of the third | DC level of V << 16, word 2 = DC levels of the first |
  *             last luma tile << 16, word 3 = DC level of U.  The three segment lengths add up to the bits kept in the macroblock's slot.

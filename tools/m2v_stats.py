@@ -52,16 +52,20 @@ def main():
     if args.yuv:
         m2v_decode = M.decoder
         dec = m2v_decode.decode(es, quirks=True)           # the encoder's own reconstruction (see fpga-mpeg2-encoder_amd/decoder.py)
+        # (a true-size stream, M2V_HEADER_TRUE: the header's size is the source's own, the decoder hands out pictures of that size, and
+        # the planes the encoder was given are those of the source padded to whole macroblocks - compared where the source is)
         W, H = info.width, info.height
+        PW, PH = (16 * s16 for s16 in M.fit_size(W, H))
         src = np.fromfile(args.yuv, np.uint8)
         rgb = args.layout in M.LAYOUTS_RGB
-        fb = W * H * M.rgb_bytes_per_pixel(args.layout) if rgb else W * H * 3 // 2 if args.layout else 3 * W * H
+        fb = M.frame_bytes(W, H, args.layout or "444")
         n = min(src.size // fb, len(dec.frames))
-        src = src[:n * fb].reshape(n, -1)
+        src = M.pad_frames(src[:n * fb], W, H, args.layout or "444")
         if rgb:
-            src = M.rgb_to444(src, W, H, args.layout, args.matrix)         # PSNR against the planes the encoder was given, by definition
+            src = M.rgb_to444(src, PW, PH, args.layout, args.matrix)       # PSNR against the planes the encoder was given, by definition
         else:
-            src = M.to444(src, W, H, args.layout) if args.layout else src.reshape(n, 3, H, W)
+            src = M.to444(src, PW, PH, args.layout) if args.layout else src.reshape(n, 3, PH, PW)
+        src = src[:, :, :H, :W]
         ps = [m2v_decode.psnr(src[k, 0], dec.frames[k][0]) for k in range(n)]
         print("  luma PSNR over %d frames: mean %.2f dB  min %.2f dB" % (n, float(np.mean(ps)), float(np.min(ps))))
     if args.ps:
