@@ -39,7 +39,7 @@ EXPORTS = [
     "m2v_comm_peer_stats", "m2v_comm_kind", "m2v_strip_last_form", "m2v_upload_wait", "m2v_device_pci_bus_id",
     "m2v_strip_encode_begin", "m2v_strip_encode_end",
     "m2v_rgb_matrix", "m2v_push_rgb", "m2v_push_rgb_pull", "m2v_encode_resident_rgb", "m2v_encode_resident_rgb_begin",
-    "m2v_set_frame_size", "m2v_fit_size",
+    "m2v_set_frame_size", "m2v_fit_size", "m2v_picture_stats",
 ]
 
 # the 4:2:0 entry points (kept apart: tests/test_abi.py matches EXPORTS against names of letters and underscores only)
@@ -59,6 +59,27 @@ MATRICES_RGB = {
 }
 
 PEER_DESC_BYTES = 128          # M2V_PEER_DESC_BYTES
+
+
+class PictureStat(ctypes.Structure):
+    """m2v_picture_stat (include/m2v_mi355x.h): one picture's record of option "stats", 64 bytes"""
+    _fields_ = [("frame", ctypes.c_uint32), ("coding_type", ctypes.c_uint32), ("sse", ctypes.c_uint64 * 3), ("mb_bits", ctypes.c_uint64),
+                ("intra_mbs", ctypes.c_uint32), ("inter_mbs", ctypes.c_uint32), ("coded_blocks", ctypes.c_uint32),
+                ("mv_abs_x", ctypes.c_uint32), ("mv_abs_y", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+# the same record as a numpy structured dtype (Mpeg2Encoder.picture_stats)
+PICTURE_STAT_DTYPE = np.dtype([("frame", "<u4"), ("coding_type", "<u4"), ("sse", "<u8", (3,)), ("mb_bits", "<u8"), ("intra_mbs", "<u4"),
+                               ("inter_mbs", "<u4"), ("coded_blocks", "<u4"), ("mv_abs_x", "<u4"), ("mv_abs_y", "<u4"), ("reserved", "<u4")])
+
+
+def psnr_from_sse(sse, samples):
+    """10 log10(255^2 * samples / sse) in dB, inf where sse == 0: the PSNR of a plane (or of several: add their sse and their samples)
+    from a record's exact sum of squared errors.  Scalars or arrays."""
+    sse = np.asarray(sse, np.float64)
+    with np.errstate(divide="ignore"):
+        out = 10.0 * np.log10(255.0 * 255.0 * np.asarray(samples, np.float64) / sse)
+    return float(out) if out.ndim == 0 else out
 
 
 class CommCallbacks(ctypes.Structure):
@@ -175,6 +196,8 @@ def lib(debug=False):
             L.m2v_encode_resident_rgb_begin.argtypes = [vp, u32, u32, u32, vp, sz, ci, ci, vp, sz, vp]
             L.m2v_set_frame_size.argtypes = [vp, ci, ci, ci]
             L.m2v_fit_size.argtypes = [ci, ci, ctypes.POINTER(u32), ctypes.POINTER(u32)]
+            L.m2v_picture_stats.restype = ctypes.c_longlong
+            L.m2v_picture_stats.argtypes = [vp, vp, sz]
         except AttributeError:
             # an OLDER build handed in through M2V_LIB for a same-box A/B (tools/ab.sh) may lack the newer entry points; the library of
             # this tree must have every one of them (tests/test_abi.py)
@@ -370,6 +393,8 @@ class Mpeg2Encoder:
 
     def set_option(self, name, value):
         self._chk(self._L.m2v_set_option(self._h, name.encode(), int(value)), "m2v_set_option(%s)" % name)
+        if name == "stats":
+            self._stats = bool(value)
 
     def set_frame_size(self, w, h, header="module"):
         """m2v_set_frame_size: from now on every whole-frame entry takes w x h frames in its own format and pads them on the device;
@@ -590,7 +615,18 @@ class Mpeg2Encoder:
                                                         _layout_rgb(layout), _matrix_rgb(matrix), d_out_ptr, cap, stream),
                   "m2v_encode_resident_rgb_begin")
 
-    def encode_tensor(self, frames, pframes_count, order="rgb", matrix="bt601", out=None, header=None):
+    def picture_stats(self, max_records=None):
+        """Pops the waiting records of option "stats" (m2v_picture_stats), oldest first, at most max_records of them: a numpy structured
+        array of PICTURE_STAT_DTYPE, empty while the option is off."""
+        n = self._chk(self._L.m2v_picture_stats(self._h, None, 0), "m2v_picture_stats")
+        if max_records is not None:
+            n = min(n, int(max_records))
+        out = np.zeros(n, PICTURE_STAT_DTYPE)
+        if n:
+            n = self._chk(self._L.m2v_picture_stats(self._h, out.ctypes.data, n), "m2v_picture_stats")
+        return out[:n]
+
+    def encode_tensor(self, frames, pframes_count, order="rgb", matrix="bt601", out=None, header=None, stats=False):
         """One whole sequence from a torch image tensor on the handle's device, in one call: contiguous uint8 [N, H, W, 3] (order
         "rgb" / "bgr"), [N, H, W, 4] ("rgbx" / "bgrx" / "xrgb" / "xbgr") or [N, 3, H, W] ("rgb": planar).  Runs
         m2v_encode_resident_rgb on torch's current stream and returns the stream bytes as a uint8 device tensor (a view of `out` when
@@ -599,7 +635,9 @@ class Mpeg2Encoder:
         own setting is back afterwards), and what the stream's headers say of a size that is not whole macroblocks - "true": the
         tensor's size, what a player is to show; "module": the padded size, the module's stream for the padded frames.  Without the
         keyword H and W must be whole macroblocks, as ever: padding is asked for, never a surprise for a caller that relied on the
-        ValueError."""
+        ValueError.
+        stats=True: returns (stream, records) - the sequence's picture records (picture_stats; option "stats" for the duration of the
+        call, the handle's own setting is back afterwards)."""
         import torch
         if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4:
             raise ValueError("encode_tensor: a uint8 tensor of 4 dimensions is required")
@@ -634,13 +672,19 @@ class Mpeg2Encoder:
         fit = bool(W % 16 or H % 16)
         if fit or before:
             self.set_frame_size(W if fit else 0, H if fit else 0, header if fit else "module")
+        stats_before = getattr(self, "_stats", False)
+        if stats and not stats_before:
+            self.set_option("stats", 1)
         try:
             nb = self.encode_resident_rgb(frames.data_ptr(), N, out.data_ptr(), out.numel(), xs, ys, pframes_count, layout, matrix,
                                           stream=torch.cuda.current_stream(frames.device).cuda_stream)
+            records = self.picture_stats() if stats else None
         finally:
             if fit or before:
                 self.set_frame_size(*(before or (0, 0, 0)))
-        return out[:nb]
+            if stats and not stats_before:
+                self.set_option("stats", 0)
+        return (out[:nb], records) if stats else out[:nb]
 
     def encode_resident_end(self):
         n = ctypes.c_size_t(0)

@@ -116,7 +116,10 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
     }
     const size_t nseg = seg_start.size();
     e->rec_bytes = (size_t)g.rysz * 3 / 2;           // tiled, with one extra tile column (rec_luma_off)
-    const bool need_any_rec = e->pframes > 0;
+    // option "stats" measures every picture against its reconstruction: the unreferenced ones get a slot too (k_mb's need_rec is the
+    // runtime test job.rec != nullptr).  The two alternating slots of a segment still do: frame k writes slot k & 1 and reads (k - 1) & 1,
+    // and k_picstat reads frame k's slot on the segment's stream before frame k + 1 - let alone k + 2 - is launched.
+    const bool need_any_rec = e->pframes > 0 || e->stats_on;
     std::vector<int> rec_slot(nf, -1);
     if (need_any_rec) {
         if (e->rec_pool_bytes < e->rec_bytes) {       // geometry grew since the pool was allocated (new sequence)
@@ -126,7 +129,7 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
             e->rec_pool.clear();
             e->rec_pool_bytes = e->rec_bytes;
         }
-        const size_t want = e->keep_recon ? nf + 1 : 2 * nseg + 1;
+        const size_t want = e->keep_recon ? nf + 1 : e->pframes > 0 ? 2 * nseg + 1 : nseg + 1;       // (I pictures only, for "stats": one each)
         while (e->rec_pool.size() < want) {
             uint8_t *p = nullptr;
             HIPCHK(hipMalloc((void **)&p, e->rec_pool_bytes));
@@ -147,7 +150,7 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
                     if (prev < 0) throw HipError{hipErrorInvalidValue, "P frame without a reference"};
                     jobs[k].ref = e->rec_pool[prev];
                 }
-                if (followed) {
+                if (followed || e->stats_on) {
                     int sl;
                     if (e->keep_recon) sl = free_slots[fs++];
                     else {
@@ -258,6 +261,7 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
         e->dev_lists = lists;
         e->dev_jobs_p = e->d_jobs.p; e->dev_lists_p = e->d_lists.p; e->dev_joblist_p = e->d_joblist.p;
     }
+    if (e->stats_on) stats_begin_chunk(e, s, nf);
     e->plan_nf = nf;
     e->dbg_frames = nf;
     e->dbg_rec_slot = rec_slot;
@@ -366,6 +370,10 @@ void encode_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf,
                 hipStream_t sk = k == 0 ? s : e->side[k - 1];
                 launch_mb<false>(e, sk, e->d_lists.p + st.off_i + st.cut_i[k], st.cut_i[k + 1] - st.cut_i[k], e->g);
                 launch_mb<true>(e, sk, e->d_lists.p + st.off_p + st.cut_p[k], st.cut_p[k + 1] - st.cut_p[k], e->g);
+                if (e->stats_on) {      // behind the group's step on the group's stream: before step j + 1, whose successor reuses the slots
+                    launch_picstat(e, sk, e->d_lists.p + st.off_i + st.cut_i[k], st.cut_i[k + 1] - st.cut_i[k]);
+                    launch_picstat(e, sk, e->d_lists.p + st.off_p + st.cut_p[k], st.cut_p[k + 1] - st.cut_p[k]);
+                }
             }
         }
         // every group scans its own slices right behind its last macroblock kernel (nothing in k_slice_scan looks beyond a
@@ -379,11 +387,20 @@ void encode_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf,
         }
     } else {
         e->timer_merge = true;          // (option profile: the steps' launches of one kind as one timed interval)
-        for (size_t j = 0; j < e->plan_steps.size(); ++j) run_step(e, s, j);
+        for (size_t j = 0; j < e->plan_steps.size(); ++j) {
+            run_step(e, s, j);
+            if (e->stats_on) {
+                const m2v_enc::Step &st = e->plan_steps[j];
+                timer_break(e);         // (untimed work between two steps: the open interval ends here)
+                launch_picstat(e, s, e->d_lists.p + st.off_i, st.n_i);
+                launch_picstat(e, s, e->d_lists.p + st.off_p, st.n_p);
+            }
+        }
         e->timer_merge = false;
         timer_break(e);
     }
     finish_chunk(e, s, first, last, d_stream, advance);
+    if (e->stats_on) stats_finish_chunk(e, s);
 }
 
 // pinned host memory of at least `bytes`, kept with the handle
@@ -487,6 +504,7 @@ void m2v_destroy(m2v_enc *e)
     e->d_coef.release(); e->d_mbaux.release(); e->d_slots.release(); e->d_slots_small.release(); e->d_mbinfo.release(); e->d_mblen.release();
     e->d_slice_bytes.release(); e->d_slice_off.release(); e->d_frame_off.release();
     e->d_jobs.release(); e->d_lists.release(); e->d_joblist.release(); e->d_ctl.release(); e->d_segs.release(); e->d_x444.release(); e->d_fit.release();
+    e->d_pstat.release();
     for (auto p : e->rec_pool) (void)hipFree(p);
     for (auto &c : e->mbmaps) { if (c.ev) (void)hipEventDestroy(c.ev); c.d.release(); }
     for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
@@ -502,6 +520,7 @@ void m2v_destroy(m2v_enc *e)
         if (h.h_jobs) (void)hipHostFree(h.h_jobs);
         if (h.h_lists) (void)hipHostFree(h.h_lists);
         if (h.h_joblist) (void)hipHostFree(h.h_joblist);
+        if (h.h_pstat) (void)hipHostFree(h.h_pstat);
         if (h.ev_ctl) (void)hipEventDestroy(h.ev_ctl);
         if (h.ev_out) (void)hipEventDestroy(h.ev_out);
     }
@@ -550,6 +569,7 @@ int m2v_reset(m2v_enc *e)
     e->buffered = 0; e->beat_pos = 0; e->frames_total = 0; e->persist_slot = -1;
     e->first_chunk = true; e->stream_bytes = 0; e->cur = 0;
     e->fifo.clear(); e->fifo_rd = 0; e->end_pending = false;
+    stats_drop(e);
     // a strip sequence abandoned between m2v_strip_begin and m2v_strip_finish: back to the full frame
     e->strip_active = false;
     e->strip_inflight = false;
@@ -633,6 +653,12 @@ int m2v_set_option(m2v_enc *e, const char *name, long long value)
     if (!strcmp(name, "conformant")) {
         if (e->state != m2v_enc::IDLE) return M2V_E_PARAM;
         e->conformant = value != 0;
+        return M2V_OK;
+    }
+    if (!strcmp(name, "stats")) {
+        if (e->state != m2v_enc::IDLE) { e->set_err("m2v_set_option: \"stats\" can be set only while the handle is idle"); return M2V_E_STATE; }
+        e->stats_on = value != 0;
+        if (!e->stats_on) stats_drop(e);
         return M2V_OK;
     }
     if (!strcmp(name, "dct_mfma")) { e->dct_mfma = value != 0; return M2V_OK; }

@@ -9,6 +9,8 @@
 //                     conversions in front of a chunk (k_unpack444, k_fit, k_expand420, k_rgb2yuv: no device globals, so they can live here)
 //   m2v_resident.hip  whole sequences resident in HBM (what bench.py times), one or several per call
 //   m2v_strips.hip    strip mode (BASELINE config c5) and the communicators of m2v_comm.hpp
+//   m2v_stats.hip     option "stats": the per-picture records of m2v_picture_stats - their buffers, their way to the host and the queue
+//                     they wait in (the kernels that fill them, m2v_stats_kernels.hpp, need m2v_kernels.hpp and so belong to m2v_launch.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -127,6 +129,9 @@ struct m2v_enc {
         hipEvent_t ev_ctl = nullptr, ev_out = nullptr, ev_up = nullptr;
         size_t uploaded = 0;                  // leading frames of the chunk being filled that are already in d_in (page-locked
                                               // caller memory goes to the device directly, without the pinned staging copy)
+        m2v_picture_stat *h_pstat = nullptr;  // pinned: the chunk's picture records (option "stats"), read back in front of the control word
+        size_t h_pstat_cap = 0;
+        size_t nstat = 0;                     // records of the submitted chunk that stats_collect has not moved to the handle's queue yet
         int stage = 0;                        // 0 free, 1 encode submitted, 2 stream read-back submitted
         bool last = false;
         size_t bytes = 0;
@@ -254,6 +259,12 @@ struct m2v_enc {
     bool hdr_true = false;
     DevBuf<uint8_t> d_fit;                // padded frames in their own format, between k_fit and the conversion (no recording references it)
 
+    // option "stats" (m2v_stats.hip): the chunk's records on the device - k_picstat and k_picstat_mb fill them in place - and the
+    // completed pictures' records nobody has popped yet
+    bool stats_on = false;
+    DevBuf<m2v_picture_stat> d_pstat;
+    std::deque<m2v_picture_stat> pstat_q;
+
     // debug bookkeeping of the last resident encode
     size_t dbg_frames = 0;
     std::vector<int> dbg_rec_slot;
@@ -357,6 +368,14 @@ inline bool size_refuses(m2v_enc *e, const char *fn, const char *why)
 }
 constexpr const char *kNoBeats = "the port has no partial macroblock, push whole frames";
 constexpr const char *kNoStrips = "strips take whole padded frames";
+// the strip entries that start something: true = refused (M2V_E_STATE) because a size is set or option "stats" is on
+inline bool strip_refuses(m2v_enc *e, const char *fn)
+{
+    if (size_refuses(e, fn, kNoStrips)) return true;
+    if (!e->stats_on) return false;
+    e->set_err("%s: option \"stats\" is on: a strip holds part of a picture, and nothing sums the records across ranks", fn);
+    return true;
+}
 // PkFrame::layout of a planar 4:4:4 frame of a sequence that pads its frames (no other planar frame travels as a run)
 constexpr int kPk444 = 8;
 // PkFrame::layout of a 4:2:0 frame is kPk420 + M2V_420_*
@@ -382,6 +401,16 @@ void launch_rgb2yuv(hipStream_t s, int layout, int matrix, const uint8_t *src, u
 
 // ---- m2v_strips.hip ----
 void strip_flight_release(m2v_enc *e);
+
+// ---- m2v_stats.hip: option "stats"; plan_chunk and encode_chunk call the first two, and only while the option is on ----
+// the chunk's nf records on the device, zeroed on s (plan_chunk, in front of the chunk's first kernel)
+void stats_begin_chunk(m2v_enc *e, hipStream_t s, size_t nf);
+// behind the chunk's scans: macroblock counts and bits of its plan_nf frames, then the records into the current stage's pinned memory
+void stats_finish_chunk(m2v_enc *e, hipStream_t s);
+// a completed chunk's records (its stream has been waited for) from the stage to the handle's queue
+void stats_collect(m2v_enc *e, m2v_enc::HostStage &h);
+// a new sequence, or m2v_reset: nothing waits any more
+void stats_drop(m2v_enc *e);
 
 // ---- m2v_launch.hip: everything that touches device code ----
 // The constant tables live in each device's copy of the code object: uploaded once per device, whichever thread creates the first
@@ -412,6 +441,10 @@ void launch_halo_unpack(m2v_enc *e, hipStream_t s, const int *d_list, int count,
 // strip mode, output rank: where every (frame, rank) piece goes + the copy itself, headers and trailer (k_strip_layout, k_strip_assemble)
 void launch_strip_assemble(m2v_enc *e, hipStream_t s, const Geom &g, uint32_t gop, size_t nf, int nranks, const StripSrc &src,
                            const unsigned long long *d_all_off, uint8_t *d_out, unsigned long long cap);
+// option "stats": squared error of the `count` frames of a launch list (k_mb's own: d_list points into e->d_lists) into their records in
+// e->d_pstat, behind their k_mb launch on s (k_picstat); the rest of the records of the chunk's nf frames, behind its scans (k_picstat_mb)
+void launch_picstat(m2v_enc *e, hipStream_t s, const int *d_list, int count);
+void launch_picstat_mb(m2v_enc *e, hipStream_t s, size_t nf);
 int debug_table(int which, int i, int j);
 
 }  // namespace m2v

@@ -1,10 +1,12 @@
-// m2v_launch.hip — the one translation unit of libm2v_mi355x.so that contains device code: it includes m2v_kernels.hpp, uploads the
+// m2v_launch.hip — the one translation unit of libm2v_mi355x.so that contains device code: it includes m2v_kernels.hpp (and, for
+// option "stats", m2v_stats_kernels.hpp behind it), uploads the
 // constant tables into this code object's device globals and offers one plain C++ launch function per kernel to the host units
 // (m2v_host.hpp).  Kernel template arguments are chosen here from the handle's parameters (VECTOR_LEVEL, options).
 #include <mutex>
 
 #include "m2v_host.hpp"
 #include "m2v_kernels.hpp"
+#include "m2v_stats_kernels.hpp"
 
 namespace m2v {
 
@@ -397,6 +399,27 @@ void launch_strip_assemble(m2v_enc *e, hipStream_t s, const Geom &g, uint32_t go
     const unsigned blocks = (unsigned)(nsegs * (size_t)split + (nf + kCopyThreads - 1) / kCopyThreads + 1);
     hipLaunchKernelGGL(k_strip_assemble, dim3(blocks), dim3(kCopyThreads), 0, s, (const CopySeg *)e->d_segs.p, (int)nsegs, split, g, (int)nf, gop,
                        e->d_frame_pos.p, d_out, e->d_ctl.p);
+}
+
+// option "stats": squared error of the `count` pictures of a launch list (k_mb's own) against their reconstruction
+void launch_picstat(m2v_enc *e, hipStream_t s, const int *d_list, int count)
+{
+    if (count <= 0) return;
+    const Geom &g = e->g;
+    const uint32_t units = (uint32_t)((g.mbw + 1 + 7) / 8 * g.mbh);
+    const dim3 grid((units + kStatWaves * kUnitsPerWave - 1) / (kStatWaves * kUnitsPerWave), (unsigned)count);
+    // measured region: the source's size while the sequence pads its frames (m2v_set_frame_size), else the coded picture
+    StatRegion m{g.W, g.H, g.cw, g.ch};
+    if (e->fit.w) m = StatRegion{e->fit.w, e->fit.h, (e->fit.w + 1) / 2, (e->fit.h + 1) / 2};
+    hipLaunchKernelGGL(k_picstat, grid, dim3(kStatThreads), 0, s, e->d_joblist.p + (d_list - e->d_lists.p), g, m, e->d_pstat.p);
+    HIPCHK(hipGetLastError());
+}
+
+// ... and the macroblock counts and bits of the chunk's nf pictures (behind k_slice_scan, which makes the bit counts)
+void launch_picstat_mb(m2v_enc *e, hipStream_t s, size_t nf)
+{
+    hipLaunchKernelGGL(k_picstat_mb, dim3((unsigned)nf), dim3(kStatThreads), 0, s, e->d_jobs.p, e->g, e->d_mbinfo.p, e->d_mblen.p, e->d_pstat.p);
+    HIPCHK(hipGetLastError());
 }
 
 /* table accessors (no GPU needed): tests/test_abi.py checks the product's tables against the oracle's */

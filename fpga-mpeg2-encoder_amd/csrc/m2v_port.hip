@@ -474,6 +474,7 @@ void progress(m2v_enc *e, bool block, int until = -1, PullSink *sink = nullptr)
         e->fifo.insert(e->fifo.end(), h.h_out + direct, h.h_out + h.bytes);
         e->stream_bytes += h.bytes;
         if (h.last) e->end_pending = true;
+        stats_collect(e, h);            // (the chunk's picture records came back in front of its control word)
         h.stage = 0;
         e->pending.pop_front();
         if (idx == until) break;
@@ -589,6 +590,7 @@ void start_sequence(m2v_enc *e, uint32_t xs, uint32_t ys, uint32_t pf)
     e->fifo.clear();
     e->fifo_rd = 0;
     e->stream_bytes = 0;
+    stats_drop(e);
     for (auto &st : e->stats) st = KStat{};
     ensure_staging(e);
 }

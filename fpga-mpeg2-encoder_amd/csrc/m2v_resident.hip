@@ -17,6 +17,7 @@ static int resident_end_impl(m2v_enc *e, void *argp)
     e->resident_inflight = false;
     HIPCHK(hipStreamSynchronize(e->resident_stream));
     collect_timers(e);
+    stats_collect(e, e->st());
     if (e->st().h_ctl->overflow) { e->set_err("output buffer too small"); return M2V_E_OVERFLOW; }
     if (bytes) *bytes = (size_t)e->st().h_ctl->total_bytes;
     return M2V_OK;
@@ -27,6 +28,7 @@ static int resident_impl(m2v_enc *e, void *argp)
     auto *a = (ResidentArgs *)argp;
     if (e->state != m2v_enc::IDLE || e->strip_active || e->resident_inflight || e->strip_inflight) { e->set_err("m2v_encode_resident: encoder busy"); return M2V_E_STATE; }
     e->resident_empty = false;
+    stats_drop(e);                                      // (the previous sequence's unread picture records)
     if (a->n == 0) {                                    // no beat: the sequence never starts
         if (a->bytes) *a->bytes = 0;
         e->resident_empty = a->async;                   // only _begin leaves an _end to answer
@@ -68,7 +70,7 @@ static int resident_impl(m2v_enc *e, void *argp)
             frames = e->d_x444.p;
         }
         encode_chunk(e, s, frames, nf, first, last, g.ysz / 4, a->d_out, /*advance=*/k > 0);
-        if (!last) HIPCHK(hipStreamSynchronize(s));    // the per-chunk work buffers are reused
+        if (!last) { HIPCHK(hipStreamSynchronize(s)); stats_collect(e, e->st()); }    // the per-chunk work buffers are reused
     }
     HIPCHK(hipMemcpyAsync(e->st().h_ctl, e->d_ctl.p, sizeof(StreamCtl), hipMemcpyDeviceToHost, s));
     e->resident_inflight = true;

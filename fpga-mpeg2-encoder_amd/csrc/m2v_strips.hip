@@ -41,7 +41,7 @@ int m2v_strip_begin(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pfr
                     size_t nframes, int row0, int row1, void *hip_stream)
 {
     if (!e || !d_frames444) return M2V_E_PARAM;
-    if (size_refuses(e, "m2v_strip_begin", kNoStrips)) return M2V_E_STATE;
+    if (strip_refuses(e, "m2v_strip_begin")) return M2V_E_STATE;
     StripBeginArgs a{xsize16, ysize16, pframes_count, (const uint8_t *)d_frames444, nframes, row0, row1, (hipStream_t)hip_stream};
     return guard(e, strip_begin_impl, &a);
 }
@@ -259,7 +259,7 @@ int m2v_strip_assemble(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t 
                        size_t *out_bytes, void *hip_stream)
 {
     if (!e || !d_strips || !frame_off || !d_out || nranks < 1 || nframes == 0) return M2V_E_PARAM;
-    if (size_refuses(e, "m2v_strip_assemble", kNoStrips)) return M2V_E_STATE;
+    if (strip_refuses(e, "m2v_strip_assemble")) return M2V_E_STATE;
     StripAsmArgs a{xsize16, ysize16, pframes_count, nframes, nranks, d_strips, frame_off, (uint8_t *)d_out, cap, out_bytes,
                    (hipStream_t)hip_stream};
     return guard(e, strip_assemble_impl, &a);
@@ -880,7 +880,7 @@ int m2v_strip_encode(m2v_enc *e, m2v_comm *comm, int rank, int world, int dst_ra
                      void *hip_stream)
 {
     if (!e || !d_frames444 || nframes == 0) return M2V_E_PARAM;
-    if (size_refuses(e, "m2v_strip_encode", kNoStrips)) return M2V_E_STATE;       // (before anything starts: the communicator is not aborted)
+    if (strip_refuses(e, "m2v_strip_encode")) return M2V_E_STATE;       // (before anything starts: the communicator is not aborted)
     StripEncodeArgs a{comm, rank, world, dst_rank, xsize16, ysize16, pframes_count, (const uint8_t *)d_frames444, nframes, (uint8_t *)d_out, cap,
                       out_bytes, (hipStream_t)hip_stream};
     const bool was_inflight = e->strip_inflight;
@@ -895,7 +895,7 @@ int m2v_strip_encode_begin(m2v_enc *e, m2v_comm *comm, int rank, int world, int 
                            uint32_t pframes_count, const void *d_frames444, size_t nframes, void *d_out, size_t cap, void *hip_stream)
 {
     if (!e || !d_frames444 || nframes == 0) return M2V_E_PARAM;
-    if (size_refuses(e, "m2v_strip_encode_begin", kNoStrips)) return M2V_E_STATE;
+    if (strip_refuses(e, "m2v_strip_encode_begin")) return M2V_E_STATE;
     StripEncodeArgs a{comm, rank, world, dst_rank, xsize16, ysize16, pframes_count, (const uint8_t *)d_frames444, nframes, (uint8_t *)d_out, cap,
                       nullptr, (hipStream_t)hip_stream};
     const bool was_inflight = e->strip_inflight;

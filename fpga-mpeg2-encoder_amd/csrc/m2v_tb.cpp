@@ -2,7 +2,7 @@
 //
 //   m2v_tb [-XL n] [-YL n] [-VL n] [-Q n] [-p pframes] [-d device] [-bubbles] [-conformant] [-ps] [-ts]
 //          [-i420 | -yv12 | -nv12 | -nv21 | -rgb24 | -bgr24 | -rgbx | -bgrx | -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f]
-//          [-pad | -truesize]
+//          [-pad | -truesize] [-stats]
 //          in.yuv W H out.m2v  [in2.yuv W2 H2 out2.m2v ...]
 //
 // -pad: W, H are any size from 49 up; the files hold frames of that size in the chosen format, which are padded to whole macroblocks on
@@ -13,6 +13,10 @@
 // -rgb24 / -bgr24 / -rgbx / -bgrx / -xrgb / -xbgr / -rgbp: the input files (.rgb, .bgra, ...) hold RGB frames of W*H*3 or W*H*4 bytes in that
 // layout (M2V_RGB_*); they go in through m2v_push_rgb and are converted on the device with -matrix (default bt601).  At most one of
 // the eleven layout options.
+// -stats: the encoder's option "stats"; after each video one line per picture - frame, type, PSNR of Y, U, V against the source, intra /
+// inter macroblocks, bits of the macroblock layer, bytes of the picture in the stream (m2vc_scan) - and a mean / min summary line.
+// The PSNR is the module's reconstruction against the 4:2:0 source it codes, over the source's size under -pad (m2v_picture_stats in
+// include/m2v_mi355x.h says what that means without -conformant).
 // -conformant switches the encoder's option "conformant" on (ISO reconstruction loop; NOT byte-identical to the RTL).
 // -ps / -ts additionally write out.m2v.mpg / out.m2v.ts: the same elementary stream in an MPEG-2 program / transport
 // stream (include/m2v_container.h), so the result plays in an ordinary player.
@@ -23,6 +27,7 @@
 // (TB:249-252) and writes o_data byte 0 first (TB:260-262).  Defaults are the testbench's:
 // XL=7 YL=6 VECTOR_LEVEL=3 Q_LEVEL=2 i_pframes_count=23 (TB:23-24, 98-106).
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -35,7 +40,7 @@
 int main(int argc, char **argv)
 {
     int XL = 7, YL = 6, VL = 3, Q = 2, pf = 23, dev = 0, bubbles = 0, conformant = 0, want_ps = 0, want_ts = 0, layout420 = -1, layouts = 0, rgb = -1, matrix = M2V_RGB_BT601,
-        bad_matrix = 0, pad = 0, truesize = 0;
+        bad_matrix = 0, pad = 0, truesize = 0, stats = 0;
     int i = 1;
     for (; i < argc && argv[i][0] == '-'; ++i) {
         if (!strcmp(argv[i], "-bubbles")) { bubbles = 1; continue; }
@@ -43,6 +48,7 @@ int main(int argc, char **argv)
         if (!strcmp(argv[i], "-ps")) { want_ps = 1; continue; }
         if (!strcmp(argv[i], "-ts")) { want_ts = 1; continue; }
         if (!strcmp(argv[i], "-pad")) { pad = 1; continue; }
+        if (!strcmp(argv[i], "-stats")) { stats = 1; continue; }
         if (!strcmp(argv[i], "-truesize")) { pad = truesize = 1; continue; }
         if (!strcmp(argv[i], "-i420")) { layout420 = M2V_420_I420; ++layouts; continue; }
         if (!strcmp(argv[i], "-yv12")) { layout420 = M2V_420_YV12; ++layouts; continue; }
@@ -69,13 +75,14 @@ int main(int argc, char **argv)
     }
     if ((argc - i) < 4 || (argc - i) % 4 || layouts > 1 || bad_matrix || ((layouts || pad) && bubbles)) {          // (there are no 4:2:0 or RGB beats)
         fprintf(stderr, "usage: %s [-XL n] [-YL n] [-VL n] [-Q n] [-p pframes] [-d dev] [-i420 | -yv12 | -nv12 | -nv21 | -rgb24 | -bgr24 | -rgbx | -bgrx |"
-                        " -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f] [-pad | -truesize] in.yuv W H out.m2v ...\n", argv[0]);
+                        " -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f] [-pad | -truesize] [-stats] in.yuv W H out.m2v ...\n", argv[0]);
         return 2;
     }
     int err = 0;
     m2v_enc *e = m2v_create(XL, YL, VL, Q, dev, &err);
     if (!e) { fprintf(stderr, "*** m2v_create failed (%d): an MI355X is required, there is no CPU fallback\n", err); return 1; }
     if (conformant) m2v_set_option(e, "conformant", 1);
+    if (stats && m2v_set_option(e, "stats", 1) < 0) { fprintf(stderr, "*** m2v_set_option(stats): %s\n", m2v_last_error(e)); return 1; }
     int num_video = 0;
     for (; i + 3 < argc; i += 4) {
         ++num_video;
@@ -116,7 +123,7 @@ int main(int argc, char **argv)
                 if (n) {
                     fwrite(word.data(), 1, (size_t)n, fo);
                     bytes += (size_t)n;
-                    if (want_ps || want_ts) es.insert(es.end(), word.begin(), word.begin() + n);
+                    if (want_ps || want_ts || stats) es.insert(es.end(), word.begin(), word.begin() + n);
                 }
                 if (last || (!until_last && n == 0)) break;
                 if (until_last && n == 0 && !m2v_busy(e)) break;
@@ -166,6 +173,34 @@ int main(int argc, char **argv)
             fwrite(mux.data(), 1, need, fm);
             fclose(fm);
             printf("  %s: %zu bytes\n", name.c_str(), need);
+        }
+        if (stats) {
+            std::vector<m2v_picture_stat> rec(frames);
+            const long long got = m2v_picture_stats(e, rec.data(), rec.size());
+            std::vector<m2vc_picture> pics(frames);
+            size_t npics = 0;
+            m2vc_stream_info info;
+            if (got != (long long)frames || m2vc_scan(es.data(), es.size(), &info, pics.data(), pics.size(), &npics) < 0 || npics != frames) {
+                fprintf(stderr, "*** statistics: %lld records, %zu pictures in the stream for %zu frames\n", got, npics, frames);
+                return 1;
+            }
+            // samples of the measured region: the source's size (the coded size is the same without -pad)
+            const double ny = (double)xsize * ysize, nc = (double)((xsize + 1) / 2) * ((ysize + 1) / 2);
+            auto psnr = [](double sse, double n) { return sse > 0 ? 10.0 * std::log10(255.0 * 255.0 * n / sse) : INFINITY; };
+            double sum[3] = {0, 0, 0}, low[3] = {INFINITY, INFINITY, INFINITY};
+            unsigned long long bits = 0;
+            for (size_t k = 0; k < frames; ++k) {
+                const m2v_picture_stat &r = rec[k];
+                const double db[3] = {psnr((double)r.sse[0], ny), psnr((double)r.sse[1], nc), psnr((double)r.sse[2], nc)};
+                for (int c = 0; c < 3; ++c) { sum[c] += db[c]; if (db[c] < low[c]) low[c] = db[c]; }
+                bits += r.mb_bits;
+                printf("  stats video %d frame %3u %c  PSNR Y %6.2f U %6.2f V %6.2f  intra %5u inter %5u  mb bits %9llu  bytes %8llu\n", num_video, r.frame,
+                       r.coding_type == 1 ? 'I' : 'P', db[0], db[1], db[2], r.intra_mbs, r.inter_mbs, (unsigned long long)r.mb_bits,
+                       (unsigned long long)pics[k].bytes);
+            }
+            if (frames)
+                printf("  stats video %d: mean PSNR Y %6.2f U %6.2f V %6.2f  min Y %6.2f U %6.2f V %6.2f  mb bits %llu\n", num_video, sum[0] / frames,
+                       sum[1] / frames, sum[2] / frames, low[0], low[1], low[2], bits);
         }
         printf("end of video %d: %zu frames -> %zu bytes, %.3f s, %.1f MPixels/s incl. file I/O and PCIe\n", num_video, frames,
                bytes, s, (double)frames * xsize * ysize / s * 1e-6);

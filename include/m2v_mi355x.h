@@ -509,8 +509,49 @@ int m2v_strip_graph_stats(const m2v_enc *e, int *last_call_was_graph, int *recor
  * behaviour: the reconstruction loop follows ISO/IEC 13818-2 where the RTL deviates from it - four-sample average
  * rounded with +2, 4:2:0 chroma vector = mv / 2 toward zero, inverse quantiser truncating toward zero with
  * [-2048, 2047] saturation and mismatch control - so that a standard decoder reproduces the encoder's reference
- * frames exactly instead of drifting inside a GOP.  Only while idle). */
+ * frames exactly instead of drifting inside a GOP.  Only while idle),
+ * "stats" (default 0 = exactly the launches, buffers and bytes of a handle that never heard of it.  1 = every picture leaves a
+ * record for m2v_picture_stats, see there: the same stream, one reconstruction more per GOP and a pass over source and reconstruction
+ * per GOP step.  Only while idle, M2V_E_STATE otherwise). */
 int m2v_set_option(m2v_enc *e, const char *name, long long value);
+
+/*
+ * Per-picture statistics, computed on the device while a chunk is encoded (option "stats" = 1): the squared error of the
+ * reconstruction against the source, the bits of the macroblock layer and the macroblock decisions.
+ *
+ * Source: the 4:2:0 picture the module codes - Y as given, U and V after the module's own two-stage mean2 (RTL:1086-1089 the
+ * horizontal mean of a pixel pair, RTL:1167-1170 the vertical mean of two such means, each (a + b + 1) >> 1).  For 4:2:0 and RGB
+ * input that is taken after the expansion or conversion the handle does anyway.  A frame cut short by a stop counts with its black
+ * fill (Y = 0, U = V = 128, RTL:1048-1056), as it is coded.
+ * Reconstruction: what the module's reference memory would hold for the picture (every picture, the unreferenced last one of a GOP
+ * included).  With option "conformant" = 1 that is also the picture a standard decoder shows.  WITHOUT it a standard decoder drifts
+ * away from it inside a GOP (see "conformant"): the records then say how well the MODULE's loop tracked the source, not what a
+ * player displays; only the I pictures agree.
+ * Measured region: without a frame size set the whole coded W x H of luma and W/2 x H/2 of each chroma plane.  With
+ * m2v_set_frame_size(width, height, ...) the top-left width x height of luma and (width + 1) / 2 x (height + 1) / 2 of each
+ * chroma plane: the padding is coded, and not measured.
+ * Arithmetic: exact integers throughout, no float on the device, so a record does not depend on the launch shape, on "batch_frames",
+ * "split_streams" or "cu_pack".  PSNR is the caller's: 10 log10(255^2 * samples / sse), infinite for sse == 0.
+ *
+ * While "stats" is 1 every m2v_strip_* entry that starts something answers M2V_E_STATE (a strip holds part of a picture per GPU;
+ * nothing sums across ranks) - the rule a set frame size follows.
+ */
+typedef struct m2v_picture_stat {
+    uint32_t frame;          /* index of the picture in its sequence, 0-based (coding order = display order) */
+    uint32_t coding_type;    /* 1 = I, 2 = P, as m2vc_picture                                               */
+    uint64_t sse[3];         /* Y, U, V: sum over the measured region of (source - reconstruction)^2         */
+    uint64_t mb_bits;        /* bits of the macroblock layer of the picture (slice headers not counted)      */
+    uint32_t intra_mbs, inter_mbs;
+    uint32_t coded_blocks;   /* sum over macroblocks of popcount(coded block flags), 0 .. 6 each             */
+    uint32_t mv_abs_x, mv_abs_y;   /* sum over inter macroblocks of |vector| as transmitted, half-pel units  */
+    uint32_t reserved;       /* 0 */
+} m2v_picture_stat;          /* 64 bytes */
+/* Pops up to `cap` records of completed pictures, oldest first, into dst and returns how many it wrote; dst == NULL returns how
+ * many are waiting.  After m2v_encode_resident* or m2v_encode_resident_end has returned all nframes records of that sequence are
+ * waiting.  On the port path a chunk's records arrive when m2v_pull could hand out that chunk's words; after the stop has been
+ * pulled to `last`, all of them have.  Records still unread when the next sequence starts, or at m2v_reset, are dropped.  With
+ * "stats" = 0 the answer is 0.  Waits for nothing. */
+long long m2v_picture_stats(m2v_enc *e, m2v_picture_stat *dst, size_t cap);
 
 /* Per-kernel statistics of the last m2v_encode_resident call with "profile" = 1.
  * kernel: 0 = macroblock kernel on P frames, 1 = macroblock kernel on I frames,

@@ -3,7 +3,13 @@
 PSNR), optional PSNR against the source through the repo's decoder, optional PS / TS multiplexing.
 
     python tools/m2v_stats.py out.m2v [--yuv src.yuv [--i420 | --yv12 | --nv12 | --nv21]] [--ps out.mpg] [--ts out.ts]
+    python tools/m2v_stats.py out.m2v --yuv src.yuv --device [--VL 3] [--Q 2] [--pframes N] [--conformant]
     python tools/m2v_stats.py out.m2v --yuv src.rgb [--rgb24 | --bgr24 | --rgbx | --bgrx | --xrgb | --xbgr | --rgbp] [--matrix bt601]
+
+--device: the PSNR comes from the encoder itself (option "stats", m2v_picture_stats) instead of the Python decoder, which takes minutes
+per second of full-size video: the source is encoded again on the GPU with the given parameters, must give the file's stream byte for
+byte, and the records' exact squared errors make the PSNR of all three planes.  That PSNR is the module's reconstruction against the
+4:2:0 picture it codes (chroma: the module's two-stage mean of the 4:4:4 planes), over the source's size.
 """
 import argparse
 import os
@@ -27,6 +33,11 @@ def main():
     ap.add_argument("--ps", help="write an MPEG-2 program stream")
     ap.add_argument("--ts", help="write an MPEG-2 transport stream")
     ap.add_argument("--pictures", action="store_true", help="one line per picture")
+    ap.add_argument("--device", action="store_true", help="PSNR from the encoder's own statistics: --yuv is encoded again on the GPU and must give this stream")
+    ap.add_argument("--VL", type=int, default=3, help="--device: VECTOR_LEVEL the stream was made with")
+    ap.add_argument("--Q", type=int, default=2, help="--device: Q_LEVEL the stream was made with")
+    ap.add_argument("--pframes", type=int, default=None, help="--device: i_pframes_count (default: what the stream's first GOP shows)")
+    ap.add_argument("--conformant", action="store_true", help="--device: the stream was made with option conformant")
     args = ap.parse_args()
     M = m2v_load.load()
     C = M.container
@@ -49,7 +60,37 @@ def main():
         for k, p in enumerate(pics):
             print("  %5d  %s  tref %3d  %8d bytes  %d slices%s" % (k, "IP"[p.coding_type - 1], p.temporal_reference, p.bytes,
                                                                 p.slices, "  GOP" if p.gop_start else ""))
-    if args.yuv:
+    if args.yuv and args.device:
+        W, H = info.width, info.height
+        xs, ys = M.fit_size(W, H)
+        fb = M.frame_bytes(W, H, args.layout or "444")
+        src = np.fromfile(args.yuv, np.uint8)
+        n = min(src.size // fb, len(pics))
+        starts = [k for k, p in enumerate(pics) if p.gop_start]
+        pf = args.pframes if args.pframes is not None else (starts[1] - starts[0] if len(starts) > 1 else max(len(pics), 1)) - 1
+        level = lambda s16: max(4, (s16 - 1).bit_length())           # the smallest XL / YL that holds the size
+        enc = M.Mpeg2Encoder(level(xs), level(ys), args.VL, args.Q)
+        try:
+            enc.set_option("stats", 1)
+            enc.set_option("conformant", int(args.conformant))
+            if W % 16 or H % 16:
+                enc.set_frame_size(W, H, "true")
+            got = enc.encode(src[:n * fb], xs, ys, pf, layout=args.layout, matrix=args.matrix)
+            rec = enc.picture_stats()
+        finally:
+            enc.close()
+        if got != es:
+            sys.exit("  --device: encoding %s again with VL=%d Q=%d pframes=%d%s gives another stream (%d bytes): not this stream's source or parameters"
+                     % (args.yuv, args.VL, args.Q, pf, " conformant" if args.conformant else "", len(got)))
+        ny, nc = W * H, ((W + 1) // 2) * ((H + 1) // 2)
+        db = np.stack([M.psnr_from_sse(rec["sse"][:, 0], ny), M.psnr_from_sse(rec["sse"][:, 1], nc), M.psnr_from_sse(rec["sse"][:, 2], nc)], axis=1)
+        if args.pictures:
+            for r, d in zip(rec, db):
+                print("  %5d  %s  PSNR Y %6.2f U %6.2f V %6.2f  intra %5d inter %5d  mb bits %d" % (
+                    r["frame"], "IP"[r["coding_type"] - 1], d[0], d[1], d[2], r["intra_mbs"], r["inter_mbs"], r["mb_bits"]))
+        print("  luma PSNR over %d frames: mean %.2f dB  min %.2f dB   (from the encoder: U mean %.2f min %.2f, V mean %.2f min %.2f)" % (
+            n, db[:, 0].mean(), db[:, 0].min(), db[:, 1].mean(), db[:, 1].min(), db[:, 2].mean(), db[:, 2].min()))
+    elif args.yuv:
         m2v_decode = M.decoder
         dec = m2v_decode.decode(es, quirks=True)           # the encoder's own reconstruction (see fpga-mpeg2-encoder_amd/decoder.py)
         # (a true-size stream, M2V_HEADER_TRUE: the header's size is the source's own, the decoder hands out pictures of that size, and
