@@ -40,6 +40,7 @@ EXPORTS = [
     "m2v_strip_encode_begin", "m2v_strip_encode_end",
     "m2v_rgb_matrix", "m2v_push_rgb", "m2v_push_rgb_pull", "m2v_encode_resident_rgb", "m2v_encode_resident_rgb_begin",
     "m2v_set_frame_size", "m2v_fit_size", "m2v_picture_stats",
+    "m2v_set_gop_levels", "m2v_gop_report",
 ]
 
 # the 4:2:0 entry points (kept apart: tests/test_abi.py matches EXPORTS against names of letters and underscores only)
@@ -71,6 +72,17 @@ class PictureStat(ctypes.Structure):
 # the same record as a numpy structured dtype (Mpeg2Encoder.picture_stats)
 PICTURE_STAT_DTYPE = np.dtype([("frame", "<u4"), ("coding_type", "<u4"), ("sse", "<u8", (3,)), ("mb_bits", "<u8"), ("intra_mbs", "<u4"),
                                ("inter_mbs", "<u4"), ("coded_blocks", "<u4"), ("mv_abs_x", "<u4"), ("mv_abs_y", "<u4"), ("reserved", "<u4")])
+
+
+class GopStat(ctypes.Structure):
+    """m2v_gop_stat (include/m2v_mi355x.h): one GOP's record of option "gop_bytes_max", 32 bytes"""
+    _fields_ = [("gop", ctypes.c_uint32), ("first_frame", ctypes.c_uint32), ("frames", ctypes.c_uint32), ("level", ctypes.c_uint32),
+                ("bytes", ctypes.c_uint64), ("tries", ctypes.c_uint32), ("over", ctypes.c_uint32)]
+
+
+# the same record as a numpy structured dtype (Mpeg2Encoder.gop_report)
+GOP_STAT_DTYPE = np.dtype([("gop", "<u4"), ("first_frame", "<u4"), ("frames", "<u4"), ("level", "<u4"), ("bytes", "<u8"), ("tries", "<u4"),
+                           ("over", "<u4")])
 
 
 def psnr_from_sse(sse, samples):
@@ -198,6 +210,9 @@ def lib(debug=False):
             L.m2v_fit_size.argtypes = [ci, ci, ctypes.POINTER(u32), ctypes.POINTER(u32)]
             L.m2v_picture_stats.restype = ctypes.c_longlong
             L.m2v_picture_stats.argtypes = [vp, vp, sz]
+            L.m2v_set_gop_levels.argtypes = [vp, vp, sz]
+            L.m2v_gop_report.restype = ctypes.c_longlong
+            L.m2v_gop_report.argtypes = [vp, vp, sz]
         except AttributeError:
             # an OLDER build handed in through M2V_LIB for a same-box A/B (tools/ab.sh) may lack the newer entry points; the library of
             # this tree must have every one of them (tests/test_abi.py)
@@ -395,6 +410,29 @@ class Mpeg2Encoder:
         self._chk(self._L.m2v_set_option(self._h, name.encode(), int(value)), "m2v_set_option(%s)" % name)
         if name == "stats":
             self._stats = bool(value)
+        if name == "gop_bytes_max":
+            self._gop_cap = int(value)
+
+    def set_gop_levels(self, levels):
+        """m2v_set_gop_levels: GOP k of every sequence started from now on is coded at levels[min(k, len - 1)], each 1..4 (M2VError
+        otherwise, and the previous setting stays); None or an empty sequence clears the setting.  Not the module's behaviour."""
+        lv = [] if levels is None else [int(v) for v in levels]
+        if any(v < 0 or v > 255 for v in lv):
+            raise M2VError("m2v_set_gop_levels failed (-1): a level is 1..4")
+        buf = (ctypes.c_uint8 * max(1, len(lv)))(*lv)
+        self._chk(self._L.m2v_set_gop_levels(self._h, buf if lv else None, len(lv)), "m2v_set_gop_levels")
+        self._gop_levels = lv or None
+
+    def gop_report(self, max_records=None):
+        """Pops the waiting records of option "gop_bytes_max" (m2v_gop_report), oldest first, at most max_records of them: a numpy
+        structured array of GOP_STAT_DTYPE, empty while the cap is off."""
+        n = self._chk(self._L.m2v_gop_report(self._h, None, 0), "m2v_gop_report")
+        if max_records is not None:
+            n = min(n, int(max_records))
+        out = np.zeros(n, GOP_STAT_DTYPE)
+        if n:
+            n = self._chk(self._L.m2v_gop_report(self._h, out.ctypes.data, n), "m2v_gop_report")
+        return out[:n]
 
     def set_frame_size(self, w, h, header="module"):
         """m2v_set_frame_size: from now on every whole-frame entry takes w x h frames in its own format and pads them on the device;
@@ -626,7 +664,8 @@ class Mpeg2Encoder:
             n = self._chk(self._L.m2v_picture_stats(self._h, out.ctypes.data, n), "m2v_picture_stats")
         return out[:n]
 
-    def encode_tensor(self, frames, pframes_count, order="rgb", matrix="bt601", out=None, header=None, stats=False):
+    def encode_tensor(self, frames, pframes_count, order="rgb", matrix="bt601", out=None, header=None, stats=False, gop_levels=None,
+                      gop_bytes_max=0):
         """One whole sequence from a torch image tensor on the handle's device, in one call: contiguous uint8 [N, H, W, 3] (order
         "rgb" / "bgr"), [N, H, W, 4] ("rgbx" / "bgrx" / "xrgb" / "xbgr") or [N, 3, H, W] ("rgb": planar).  Runs
         m2v_encode_resident_rgb on torch's current stream and returns the stream bytes as a uint8 device tensor (a view of `out` when
@@ -637,7 +676,10 @@ class Mpeg2Encoder:
         keyword H and W must be whole macroblocks, as ever: padding is asked for, never a surprise for a caller that relied on the
         ValueError.
         stats=True: returns (stream, records) - the sequence's picture records (picture_stats; option "stats" for the duration of the
-        call, the handle's own setting is back afterwards)."""
+        call, the handle's own setting is back afterwards).
+        gop_levels = a sequence of levels 1..4, gop_bytes_max = B > 0: a level per GOP and a byte cap per GOP for this call
+        (set_gop_levels, option "gop_bytes_max"; the handle's own settings are back afterwards).  The cap's records wait for
+        gop_report()."""
         import torch
         if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4:
             raise ValueError("encode_tensor: a uint8 tensor of 4 dimensions is required")
@@ -675,7 +717,12 @@ class Mpeg2Encoder:
         stats_before = getattr(self, "_stats", False)
         if stats and not stats_before:
             self.set_option("stats", 1)
+        levels_before, cap_before = getattr(self, "_gop_levels", None), getattr(self, "_gop_cap", 0)
         try:
+            if gop_levels is not None:
+                self.set_gop_levels(gop_levels)
+            if gop_bytes_max:
+                self.set_option("gop_bytes_max", gop_bytes_max)
             nb = self.encode_resident_rgb(frames.data_ptr(), N, out.data_ptr(), out.numel(), xs, ys, pframes_count, layout, matrix,
                                           stream=torch.cuda.current_stream(frames.device).cuda_stream)
             records = self.picture_stats() if stats else None
@@ -684,6 +731,10 @@ class Mpeg2Encoder:
                 self.set_frame_size(*(before or (0, 0, 0)))
             if stats and not stats_before:
                 self.set_option("stats", 0)
+            if gop_levels is not None:
+                self.set_gop_levels(levels_before)
+            if gop_bytes_max:
+                self.set_option("gop_bytes_max", cap_before)
         return (out[:nb], records) if stats else out[:nb]
 
     def encode_resident_end(self):

@@ -112,6 +112,8 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
         jobs[k].fidx = 0;
         jobs[k].hidx = -1;
         jobs[k].rhidx = -1;
+        jobs[k].q = (uint32_t)level_of_frame(e, n);       // (a GOP that continues across a chunk boundary keeps its level: n counts from the sequence's start)
+        jobs[k].pad = 0;
         if (k == 0 || jobs[k].i_frame == 0) seg_start.push_back((int)k);
     }
     const size_t nseg = seg_start.size();
@@ -203,6 +205,11 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
             }
             const int cnt = (int)lists.size() - off;
             while (gnext <= m2v_enc::kMaxSplit) cut[gnext++] = cnt;
+            // a level per GOP: inside every group the list is stably partitioned by level, one launch per level present (launch_mb_levels).
+            // All at one level - every sequence without a schedule - leaves the list as it is.
+            if (pass < 2)
+                for (int k = 0; k < groups; ++k)
+                    std::stable_sort(lists.begin() + off + cut[k], lists.begin() + off + cut[k + 1], [&](int x, int y) { return jobs[(size_t)x].q < jobs[(size_t)y].q; });
             if (pass == 0) { st.off_i = off; st.n_i = cnt; memcpy(st.cut_i, cut, sizeof cut); }
             else if (pass == 1) { st.off_p = off; st.n_p = cnt; memcpy(st.cut_p, cut, sizeof cut); }
             else { st.off_h = off; st.n_h = cnt; }
@@ -210,11 +217,16 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
         e->plan_steps[j] = st;
     }
 
+    e->plan_nlists = lists.size();
+    const size_t redo_room = e->seq_cap ? nf : 0;        // the cap's redo lists follow the plan's (gop_cap_chunk): every frame at most once per try
+    e->plan_list_q.assign(lists.size() + redo_room, (uint8_t)e->Q);
+    for (size_t i = 0; i < lists.size(); ++i) e->plan_list_q[i] = (uint8_t)jobs[(size_t)lists[i]].q;
+
     // ---- device buffers ----
     const size_t nmb = nf * (size_t)g.mbs;
     e->d_jobs.ensure(nf);
-    e->d_lists.ensure(lists.size());
-    e->d_joblist.ensure(lists.size());
+    e->d_lists.ensure(lists.size() + redo_room);
+    e->d_joblist.ensure(lists.size() + redo_room);
     if (e->keep_recon) e->d_coef.ensure(nmb * 384);
     e->d_mbaux.ensure(nmb);
     e->d_slots.ensure(nmb * (size_t)kSlotWords + 8);
@@ -270,8 +282,8 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
 void run_step(m2v_enc *e, hipStream_t s, size_t j)
 {
     const m2v_enc::Step &st = e->plan_steps[j];
-    launch_mb<false>(e, s, e->d_lists.p + st.off_i, st.n_i, e->g);
-    launch_mb<true>(e, s, e->d_lists.p + st.off_p, st.n_p, e->g);
+    launch_mb_levels<false>(e, s, st.off_i, st.n_i);
+    launch_mb_levels<true>(e, s, st.off_p, st.n_p);
 }
 
 // macroblock rows [r0, r1) of GOP step j only (strip mode: edge rows first, so that their halo is on its way to the
@@ -368,8 +380,8 @@ void encode_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf,
             const m2v_enc::Step &st = e->plan_steps[j];
             for (int k = 0; k < G; ++k) {
                 hipStream_t sk = k == 0 ? s : e->side[k - 1];
-                launch_mb<false>(e, sk, e->d_lists.p + st.off_i + st.cut_i[k], st.cut_i[k + 1] - st.cut_i[k], e->g);
-                launch_mb<true>(e, sk, e->d_lists.p + st.off_p + st.cut_p[k], st.cut_p[k + 1] - st.cut_p[k], e->g);
+                launch_mb_levels<false>(e, sk, st.off_i + st.cut_i[k], st.cut_i[k + 1] - st.cut_i[k]);
+                launch_mb_levels<true>(e, sk, st.off_p + st.cut_p[k], st.cut_p[k + 1] - st.cut_p[k]);
                 if (e->stats_on) {      // behind the group's step on the group's stream: before step j + 1, whose successor reuses the slots
                     launch_picstat(e, sk, e->d_lists.p + st.off_i + st.cut_i[k], st.cut_i[k + 1] - st.cut_i[k]);
                     launch_picstat(e, sk, e->d_lists.p + st.off_p + st.cut_p[k], st.cut_p[k + 1] - st.cut_p[k]);
@@ -399,6 +411,7 @@ void encode_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf,
         e->timer_merge = false;
         timer_break(e);
     }
+    if (e->seq_cap) gop_cap_chunk(e, s);          // option "gop_bytes_max": the GOPs over the cap again, coarser (waits for the device)
     finish_chunk(e, s, first, last, d_stream, advance);
     if (e->stats_on) stats_finish_chunk(e, s);
 }
@@ -505,6 +518,9 @@ void m2v_destroy(m2v_enc *e)
     e->d_slice_bytes.release(); e->d_slice_off.release(); e->d_frame_off.release();
     e->d_jobs.release(); e->d_lists.release(); e->d_joblist.release(); e->d_ctl.release(); e->d_segs.release(); e->d_x444.release(); e->d_fit.release();
     e->d_pstat.release();
+    e->d_gop.release();
+    if (e->ev_gop) (void)hipEventDestroy(e->ev_gop);
+    if (e->h_redo) (void)hipHostFree(e->h_redo);
     for (auto p : e->rec_pool) (void)hipFree(p);
     for (auto &c : e->mbmaps) { if (c.ev) (void)hipEventDestroy(c.ev); c.d.release(); }
     for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
@@ -521,6 +537,7 @@ void m2v_destroy(m2v_enc *e)
         if (h.h_lists) (void)hipHostFree(h.h_lists);
         if (h.h_joblist) (void)hipHostFree(h.h_joblist);
         if (h.h_pstat) (void)hipHostFree(h.h_pstat);
+        if (h.h_gop) (void)hipHostFree(h.h_gop);
         if (h.ev_ctl) (void)hipEventDestroy(h.ev_ctl);
         if (h.ev_out) (void)hipEventDestroy(h.ev_out);
     }
@@ -570,6 +587,7 @@ int m2v_reset(m2v_enc *e)
     e->first_chunk = true; e->stream_bytes = 0; e->cur = 0;
     e->fifo.clear(); e->fifo_rd = 0; e->end_pending = false;
     stats_drop(e);
+    gop_drop(e);
     // a strip sequence abandoned between m2v_strip_begin and m2v_strip_finish: back to the full frame
     e->strip_active = false;
     e->strip_inflight = false;
@@ -659,6 +677,12 @@ int m2v_set_option(m2v_enc *e, const char *name, long long value)
         if (e->state != m2v_enc::IDLE) { e->set_err("m2v_set_option: \"stats\" can be set only while the handle is idle"); return M2V_E_STATE; }
         e->stats_on = value != 0;
         if (!e->stats_on) stats_drop(e);
+        return M2V_OK;
+    }
+    if (!strcmp(name, "gop_bytes_max")) {
+        if (e->state != m2v_enc::IDLE) { e->set_err("m2v_set_option: \"gop_bytes_max\" can be set only while the handle is idle"); return M2V_E_STATE; }
+        if (value < 0) { e->set_err("m2v_set_option: gop_bytes_max is a byte count, 0 = off"); return M2V_E_PARAM; }
+        e->gop_bytes_max = (unsigned long long)value;
         return M2V_OK;
     }
     if (!strcmp(name, "dct_mfma")) { e->dct_mfma = value != 0; return M2V_OK; }

@@ -9,6 +9,8 @@
 //                     conversions in front of a chunk (k_unpack444, k_fit, k_expand420, k_rgb2yuv: no device globals, so they can live here)
 //   m2v_resident.hip  whole sequences resident in HBM (what bench.py times), one or several per call
 //   m2v_strips.hip    strip mode (BASELINE config c5) and the communicators of m2v_comm.hpp
+//   m2v_gop.hip       a level per GOP: the caller's schedule (m2v_set_gop_levels) and option "gop_bytes_max", the byte cap the device judges
+//                     (k_gop_judge, m2v_gop_kernels.hpp, launched from m2v_launch.hip) and the host's redo loop; m2v_gop_report
 //   m2v_stats.hip     option "stats": the per-picture records of m2v_picture_stats - their buffers, their way to the host and the queue
 //                     they wait in (the kernels that fill them, m2v_stats_kernels.hpp, need m2v_kernels.hpp and so belong to m2v_launch.hip)
 #pragma once
@@ -132,6 +134,9 @@ struct m2v_enc {
         m2v_picture_stat *h_pstat = nullptr;  // pinned: the chunk's picture records (option "stats"), read back in front of the control word
         size_t h_pstat_cap = 0;
         size_t nstat = 0;                     // records of the submitted chunk that stats_collect has not moved to the handle's queue yet
+        m2v_gop_stat *h_gop = nullptr;        // pinned: the chunk's GOP records (option "gop_bytes_max"), written by k_gop_judge itself
+        size_t h_gop_cap = 0;
+        size_t ngop = 0;                      // records of the submitted chunk that gop_collect has not moved to the handle's queue yet
         int stage = 0;                        // 0 free, 1 encode submitted, 2 stream read-back submitted
         bool last = false;
         size_t bytes = 0;
@@ -265,6 +270,18 @@ struct m2v_enc {
     DevBuf<m2v_picture_stat> d_pstat;
     std::deque<m2v_picture_stat> pstat_q;
 
+    // a level per GOP (m2v_gop.hip): the caller's schedule and the byte cap - the settings, and what the sequence in progress sampled
+    // from them when it started (seq_levels empty: every GOP at Q; seq_cap 0: no cap)
+    std::vector<uint8_t> gop_levels, seq_levels;
+    unsigned long long gop_bytes_max = 0, seq_cap = 0;
+    std::vector<uint8_t> plan_list_q;     // the level of every entry of the plan's launch lists (the redo lists of the cap follow the plan's)
+    size_t plan_nlists = 0;               // entries of the plan's own lists in d_lists / d_joblist
+    DevBuf<m2v_gop_stat> d_gop;           // the chunk's GOP records on the device (k_gop_judge reads its own verdict of the previous try there)
+    std::deque<m2v_gop_stat> gop_q;       // completed GOPs' records nobody has popped yet
+    hipEvent_t ev_gop = nullptr;          // behind a k_gop_judge whose verdict the host needs
+    uint8_t *h_redo = nullptr;            // pinned staging of the redo lists
+    size_t h_redo_cap = 0;
+
     // debug bookkeeping of the last resident encode
     size_t dbg_frames = 0;
     std::vector<int> dbg_rec_slot;
@@ -372,10 +389,40 @@ constexpr const char *kNoStrips = "strips take whole padded frames";
 inline bool strip_refuses(m2v_enc *e, const char *fn)
 {
     if (size_refuses(e, fn, kNoStrips)) return true;
-    if (!e->stats_on) return false;
-    e->set_err("%s: option \"stats\" is on: a strip holds part of a picture, and nothing sums the records across ranks", fn);
+    if (e->stats_on) {
+        e->set_err("%s: option \"stats\" is on: a strip holds part of a picture, and nothing sums the records across ranks", fn);
+        return true;
+    }
+    if (!e->gop_levels.empty() || e->gop_bytes_max) {
+        e->set_err("%s: a level per GOP is set (m2v_set_gop_levels or option \"gop_bytes_max\"): a strip is coded at the handle's Q_LEVEL", fn);
+        return true;
+    }
+    e->seq_levels.clear();      // (what an earlier whole-frame sequence sampled)
+    e->seq_cap = 0;
+    return false;
+}
+// ---- m2v_gop.hip ----
+// the level frame n of the sequence in progress is coded at, before the cap has had its say
+inline int level_of_frame(const m2v_enc *e, size_t n)
+{
+    if (e->seq_levels.empty()) return e->Q;
+    return e->seq_levels[std::min(n / (e->pframes + 1u), e->seq_levels.size() - 1)];
+}
+// the start of a sequence samples the schedule and the cap (where sample_frame_size is called; with_cap: the resident entries)
+void sample_gop_levels(m2v_enc *e, bool with_cap);
+// the chunk's steps have been enqueued and every group has joined s: slice scan, k_gop_judge, and the GOPs over the cap again at the next
+// level until every GOP fits or is at level 4.  Waits for the device, at most three times (encode_chunk, only with the cap on)
+void gop_cap_chunk(m2v_enc *e, hipStream_t s);
+void gop_collect(m2v_enc *e, m2v_enc::HostStage &h);
+void gop_drop(m2v_enc *e);
+// the port entries that start a sequence: true = refused (M2V_E_STATE) because option "gop_bytes_max" is set
+inline bool cap_refuses(m2v_enc *e, const char *fn)
+{
+    if (!e->gop_bytes_max) return false;
+    e->set_err("%s: option \"gop_bytes_max\" is set: the cap needs whole GOPs in a chunk, which only the resident entries give", fn);
     return true;
 }
+
 // PkFrame::layout of a planar 4:4:4 frame of a sequence that pads its frames (no other planar frame travels as a run)
 constexpr int kPk444 = 8;
 // PkFrame::layout of a 4:2:0 frame is kPk420 + M2V_420_*
@@ -425,6 +472,19 @@ extern template void launch_mb_peer<false>(m2v_enc *, hipStream_t, const int *, 
 extern template void launch_mb_peer<true>(m2v_enc *, hipStream_t, const int *, int, const Geom &, uint8_t *, uint8_t *, const uint8_t *, const uint8_t *, const PeerStep &);
 extern template void launch_mb<false>(m2v_enc *, hipStream_t, const int *, int, const Geom &);
 extern template void launch_mb<true>(m2v_enc *, hipStream_t, const int *, int, const Geom &);
+// entries [off, off + count) of the launch lists, one launch_mb per run of one level (plan_chunk partitions by level: one per level
+// present, and exactly launch_mb(.., e->g) where every entry is at the handle's Q_LEVEL)
+template <bool P> inline void launch_mb_levels(m2v_enc *e, hipStream_t s, int off, int count)
+{
+    for (int a = off, end = off + count; a < end;) {
+        int b = a + 1;
+        while (b < end && e->plan_list_q[(size_t)b] == e->plan_list_q[(size_t)a]) ++b;
+        Geom gg = e->g;
+        gg.Q = e->plan_list_q[(size_t)a];
+        launch_mb<P>(e, s, e->d_lists.p + a, b - a, gg);
+        a = b;
+    }
+}
 extern template void launch_mb_edges<false>(m2v_enc *, hipStream_t, const int *, int, const Geom &, uint8_t *, uint8_t *, const uint8_t *, const uint8_t *);
 extern template void launch_mb_edges<true>(m2v_enc *, hipStream_t, const int *, int, const Geom &, uint8_t *, uint8_t *, const uint8_t *, const uint8_t *);
 // start of a chunk's stream: the bytes of the sequence that precede it are the previous chunk's prior + total (still in *ctl: one
@@ -445,6 +505,9 @@ void launch_strip_assemble(m2v_enc *e, hipStream_t s, const Geom &g, uint32_t go
 // e->d_pstat, behind their k_mb launch on s (k_picstat); the rest of the records of the chunk's nf frames, behind its scans (k_picstat_mb)
 void launch_picstat(m2v_enc *e, hipStream_t s, const int *d_list, int count);
 void launch_picstat_mb(m2v_enc *e, hipStream_t s, size_t nf);
+// option "gop_bytes_max": one block per GOP of the chunk's nf frames (whole GOPs of gop frames, the last one may be cut short) sums the
+// GOP's bytes, writes its record to e->d_gop and to h_recs (pinned) and raises FrameJob::q of a GOP over the cap (k_gop_judge)
+void launch_gop_judge(m2v_enc *e, hipStream_t s, size_t nf, uint32_t gop, unsigned long long cap, m2v_gop_stat *h_recs);
 int debug_table(int which, int i, int j);
 
 }  // namespace m2v

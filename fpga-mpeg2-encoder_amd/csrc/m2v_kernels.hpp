@@ -2075,7 +2075,7 @@ __global__ __launch_bounds__(kAsmThreads, 8) void k_assemble(const FrameJob *__r
             if (tid == 0) {
                 // slice header: start code, slice_vertical_position, quantiser_scale_code, extra_bit_slice (RTL:2708-2710)
                 asm_put(s_img, nw, pos, 0x000001u, 24);
-                asm_put(s_img, nw, pos + 24, ((uint32_t)(by + 1) << 6) | (2u << g.Q), 14);
+                asm_put(s_img, nw, pos + 24, ((uint32_t)(by + 1) << 6) | (2u << jobs[f].q), 14);
                 pos += 38;
             }
             const uint32_t codes[3] = {c1, c2, c3};

@@ -1,5 +1,5 @@
 // m2v_launch.hip — the one translation unit of libm2v_mi355x.so that contains device code: it includes m2v_kernels.hpp (and, for
-// option "stats", m2v_stats_kernels.hpp behind it), uploads the
+// option "stats", m2v_stats_kernels.hpp, for option "gop_bytes_max", m2v_gop_kernels.hpp behind it), uploads the
 // constant tables into this code object's device globals and offers one plain C++ launch function per kernel to the host units
 // (m2v_host.hpp).  Kernel template arguments are chosen here from the handle's parameters (VECTOR_LEVEL, options).
 #include <mutex>
@@ -7,6 +7,7 @@
 #include "m2v_host.hpp"
 #include "m2v_kernels.hpp"
 #include "m2v_stats_kernels.hpp"
+#include "m2v_gop_kernels.hpp"
 
 namespace m2v {
 
@@ -419,6 +420,15 @@ void launch_picstat(m2v_enc *e, hipStream_t s, const int *d_list, int count)
 void launch_picstat_mb(m2v_enc *e, hipStream_t s, size_t nf)
 {
     hipLaunchKernelGGL(k_picstat_mb, dim3((unsigned)nf), dim3(kStatThreads), 0, s, e->d_jobs.p, e->g, e->d_mbinfo.p, e->d_mblen.p, e->d_pstat.p);
+    HIPCHK(hipGetLastError());
+}
+
+// option "gop_bytes_max": every GOP of the chunk against the cap (behind k_slice_scan of all its frames)
+void launch_gop_judge(m2v_enc *e, hipStream_t s, size_t nf, uint32_t gop, unsigned long long cap, m2v_gop_stat *h_recs)
+{
+    const size_t nseg = (nf + gop - 1) / gop;
+    hipLaunchKernelGGL(k_gop_judge, dim3((unsigned)nseg), dim3(kJudgeThreads), 0, s, e->d_jobs.p, e->g, (int)nf, (int)gop, e->d_slice_bytes.p, cap,
+                       e->d_gop.p, h_recs);
     HIPCHK(hipGetLastError());
 }
 

@@ -577,6 +577,7 @@ void start_sequence(m2v_enc *e, uint32_t xs, uint32_t ys, uint32_t pf)
     e->up_wait_ev = nullptr;
     e->g = make_geom(e, xs, ys);            // latched on the first beat (RTL:1060-1065)
     e->pframes = pf & 0xFFu;
+    sample_gop_levels(e, false);            // (the schedule; the cap is the resident entries': the callers refuse with it set)
     e->state = m2v_enc::DURING;
     e->frames_total = 0;
     e->first_chunk = true;
@@ -591,6 +592,7 @@ void start_sequence(m2v_enc *e, uint32_t xs, uint32_t ys, uint32_t pf)
     e->fifo_rd = 0;
     e->stream_bytes = 0;
     stats_drop(e);
+    gop_drop(e);
     for (auto &st : e->stats) st = KStat{};
     ensure_staging(e);
 }
@@ -692,7 +694,10 @@ static int push_beats_impl(m2v_enc *e, void *argp)
         if (a->stop && e->state == m2v_enc::DURING) do_stop(e);
         return M2V_OK;
     }
-    if (e->state == m2v_enc::IDLE) start_sequence(e, a->xs, a->ys, a->pf);
+    if (e->state == m2v_enc::IDLE) {
+        if (cap_refuses(e, "m2v_push_beats")) return M2V_E_STATE;
+        start_sequence(e, a->xs, a->ys, a->pf);
+    }
     const Geom &g = e->g;
     const size_t bpf = g.ysz / 4;
     const BeatSrc &src = a->src;
@@ -844,6 +849,7 @@ static int push_frames_impl(m2v_enc *e, void *argp)
     };
     if (e->state == m2v_enc::ENDED || a->n == 0) { settle_deferred(); return M2V_OK; }
     if (e->state == m2v_enc::IDLE) {
+        if (cap_refuses(e, "m2v_push_frames")) { settle_deferred(); return M2V_E_STATE; }
         if (!sample_frame_size(e, "m2v_push_frames", a->xs, a->ys)) { settle_deferred(); return M2V_E_PARAM; }
         start_sequence(e, a->xs, a->ys, a->pf);
     }

@@ -18,6 +18,7 @@ static int resident_end_impl(m2v_enc *e, void *argp)
     HIPCHK(hipStreamSynchronize(e->resident_stream));
     collect_timers(e);
     stats_collect(e, e->st());
+    gop_collect(e, e->st());
     if (e->st().h_ctl->overflow) { e->set_err("output buffer too small"); return M2V_E_OVERFLOW; }
     if (bytes) *bytes = (size_t)e->st().h_ctl->total_bytes;
     return M2V_OK;
@@ -29,15 +30,22 @@ static int resident_impl(m2v_enc *e, void *argp)
     if (e->state != m2v_enc::IDLE || e->strip_active || e->resident_inflight || e->strip_inflight) { e->set_err("m2v_encode_resident: encoder busy"); return M2V_E_STATE; }
     e->resident_empty = false;
     stats_drop(e);                                      // (the previous sequence's unread picture records)
+    gop_drop(e);
     if (a->n == 0) {                                    // no beat: the sequence never starts
         if (a->bytes) *a->bytes = 0;
         e->resident_empty = a->async;                   // only _begin leaves an _end to answer
         return M2V_OK;
     }
     if (!sample_frame_size(e, "m2v_encode_resident", a->xs, a->ys)) return M2V_E_PARAM;
+    if (e->gop_bytes_max && (size_t)(a->pf & 0xFFu) + 1 > e->batch_frames) {
+        e->set_err("m2v_encode_resident: option \"gop_bytes_max\" needs whole GOPs in a chunk: pframes_count + 1 = %u is more than batch_frames = %zu",
+                   (a->pf & 0xFFu) + 1u, e->batch_frames);
+        return M2V_E_PARAM;
+    }
     hipStream_t s = a->s ? a->s : e->stream;
     e->g = make_geom(e, a->xs, a->ys);
     e->pframes = a->pf & 0xFFu;
+    sample_gop_levels(e, true);
     e->frames_total = 0;
     e->persist_slot = -1;
     for (auto &st : e->stats) st = KStat{};
@@ -70,7 +78,7 @@ static int resident_impl(m2v_enc *e, void *argp)
             frames = e->d_x444.p;
         }
         encode_chunk(e, s, frames, nf, first, last, g.ysz / 4, a->d_out, /*advance=*/k > 0);
-        if (!last) { HIPCHK(hipStreamSynchronize(s)); stats_collect(e, e->st()); }    // the per-chunk work buffers are reused
+        if (!last) { HIPCHK(hipStreamSynchronize(s)); stats_collect(e, e->st()); gop_collect(e, e->st()); }    // the per-chunk work buffers are reused
     }
     HIPCHK(hipMemcpyAsync(e->st().h_ctl, e->d_ctl.p, sizeof(StreamCtl), hipMemcpyDeviceToHost, s));
     e->resident_inflight = true;

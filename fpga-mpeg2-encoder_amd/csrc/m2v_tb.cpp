@@ -2,7 +2,7 @@
 //
 //   m2v_tb [-XL n] [-YL n] [-VL n] [-Q n] [-p pframes] [-d device] [-bubbles] [-conformant] [-ps] [-ts]
 //          [-i420 | -yv12 | -nv12 | -nv21 | -rgb24 | -bgr24 | -rgbx | -bgrx | -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f]
-//          [-pad | -truesize] [-stats]
+//          [-pad | -truesize] [-stats] [-qgop q0,q1,...]
 //          in.yuv W H out.m2v  [in2.yuv W2 H2 out2.m2v ...]
 //
 // -pad: W, H are any size from 49 up; the files hold frames of that size in the chosen format, which are padded to whole macroblocks on
@@ -17,6 +17,8 @@
 // inter macroblocks, bits of the macroblock layer, bytes of the picture in the stream (m2vc_scan) - and a mean / min summary line.
 // The PSNR is the module's reconstruction against the 4:2:0 source it codes, over the source's size under -pad (m2v_picture_stats in
 // include/m2v_mi355x.h says what that means without -conformant).
+// -qgop 1,4,3: a level per GOP (m2v_set_gop_levels): GOP k of every video at the k-th value, the last value for the GOPs beyond; NOT
+// the module's behaviour, -Q stays the handle's level.
 // -conformant switches the encoder's option "conformant" on (ISO reconstruction loop; NOT byte-identical to the RTL).
 // -ps / -ts additionally write out.m2v.mpg / out.m2v.ts: the same elementary stream in an MPEG-2 program / transport
 // stream (include/m2v_container.h), so the result plays in an ordinary player.
@@ -41,6 +43,7 @@ int main(int argc, char **argv)
 {
     int XL = 7, YL = 6, VL = 3, Q = 2, pf = 23, dev = 0, bubbles = 0, conformant = 0, want_ps = 0, want_ts = 0, layout420 = -1, layouts = 0, rgb = -1, matrix = M2V_RGB_BT601,
         bad_matrix = 0, pad = 0, truesize = 0, stats = 0;
+    std::vector<uint8_t> qgop;
     int i = 1;
     for (; i < argc && argv[i][0] == '-'; ++i) {
         if (!strcmp(argv[i], "-bubbles")) { bubbles = 1; continue; }
@@ -59,6 +62,13 @@ int main(int argc, char **argv)
         for (; k < 7 && strcmp(argv[i], rgb_opts[k]); ++k) {}
         if (k < 7) { rgb = k; ++layouts; continue; }
         if (i + 1 >= argc) break;
+        if (!strcmp(argv[i], "-qgop")) {
+            for (const char *c = argv[i + 1]; *c; ++c)
+                if (*c >= '0' && *c <= '9') qgop.push_back((uint8_t)(*c - '0'));
+                else if (*c != ',') qgop.push_back(0);              // (not a level: m2v_set_gop_levels says so)
+            ++i;
+            continue;
+        }
         if (!strcmp(argv[i], "-matrix")) {
             static const char *const names[] = {"bt601", "bt709", "bt601f", "bt709f"};
             for (k = 0; k < 4 && strcmp(argv[i + 1], names[k]); ++k) {}
@@ -75,7 +85,7 @@ int main(int argc, char **argv)
     }
     if ((argc - i) < 4 || (argc - i) % 4 || layouts > 1 || bad_matrix || ((layouts || pad) && bubbles)) {          // (there are no 4:2:0 or RGB beats)
         fprintf(stderr, "usage: %s [-XL n] [-YL n] [-VL n] [-Q n] [-p pframes] [-d dev] [-i420 | -yv12 | -nv12 | -nv21 | -rgb24 | -bgr24 | -rgbx | -bgrx |"
-                        " -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f] [-pad | -truesize] [-stats] in.yuv W H out.m2v ...\n", argv[0]);
+                        " -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f] [-pad | -truesize] [-stats] [-qgop q0,q1,...] in.yuv W H out.m2v ...\n", argv[0]);
         return 2;
     }
     int err = 0;
@@ -83,6 +93,7 @@ int main(int argc, char **argv)
     if (!e) { fprintf(stderr, "*** m2v_create failed (%d): an MI355X is required, there is no CPU fallback\n", err); return 1; }
     if (conformant) m2v_set_option(e, "conformant", 1);
     if (stats && m2v_set_option(e, "stats", 1) < 0) { fprintf(stderr, "*** m2v_set_option(stats): %s\n", m2v_last_error(e)); return 1; }
+    if (!qgop.empty() && m2v_set_gop_levels(e, qgop.data(), qgop.size()) < 0) { fprintf(stderr, "*** m2v_set_gop_levels: %s\n", m2v_last_error(e)); return 1; }
     int num_video = 0;
     for (; i + 3 < argc; i += 4) {
         ++num_video;

@@ -69,6 +69,9 @@ struct FrameJob {           // one per frame of the chunk (device memory)
     uint32_t       fidx;    // k_mb's copies in launch-list order: the frame's index in the chunk (0 in the per-frame array)
     int32_t        hidx;    // strip mode: the frame's position in its GOP step's halo list (frames whose reconstruction is referenced later), -1 = none
     int32_t        rhidx;   // ... and that of its reference frame in the previous step's list (where the neighbours' rows of it were received)
+    uint32_t       q;       // the level (1..4) the frame's GOP is coded at: the handle's Q_LEVEL, or m2v_set_gop_levels' entry; k_assemble prints it
+                            // in the slice headers, k_gop_judge raises it (k_mb takes the level from its launch's Geom::Q, not from here)
+    uint32_t       pad;     // (the structure is compared and copied as whole dwords: no unnamed padding)
 };
 
 struct StreamCtl {          // device-resident stream bookkeeping, carried across chunks

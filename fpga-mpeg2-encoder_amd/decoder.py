@@ -233,6 +233,7 @@ class Decoded:
         self.mbs = []               # per picture: list of dict(type, mv, cbp)
         self.width = self.height = 0
         self.gops = []
+        self.slice_qcodes = []      # per picture: the quantiser_scale_code of every slice, top to bottom (1 << level: a level per GOP)
 
 
 def decode(data, quirks=True):
@@ -318,10 +319,12 @@ def decode(data, quirks=True):
         U = np.zeros((H // 2, W // 2), np.int64)
         V = np.zeros((H // 2, W // 2), np.int64)
         mbs = []
+        qcodes = []
         for row in range(mbh):
             assert br.next_start_code() == row + 1, "slices must come one per macroblock row, in order"
             br.bits(32)
-            qscale = 2 * br.bits(5)                             # q_scale_type 0
+            qcodes.append(br.bits(5))
+            qscale = 2 * qcodes[-1]                             # q_scale_type 0
             assert br.bits(1) == 0                              # extra_bit_slice
             dc_pred = [0, 0, 0]                                 # relative to the reset value 1 << (7 + precision)
             pmv = [0, 0]
@@ -428,6 +431,7 @@ def decode(data, quirks=True):
         out.frames.append(tuple(np.ascontiguousarray(p[:r, :c]).astype(np.uint8)
                                 for p, r, c in zip(ref, (out.height, ch, ch), (out.width, cw, cw))))
         out.mbs.append(mbs)
+        out.slice_qcodes.append(qcodes)
     assert ended
     rest = data[(br.pos + 7) >> 3:]
     assert not any(rest) and len(data) % 32 == 0, "only zero padding may follow sequence_end_code"

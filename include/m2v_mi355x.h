@@ -512,8 +512,59 @@ int m2v_strip_graph_stats(const m2v_enc *e, int *last_call_was_graph, int *recor
  * frames exactly instead of drifting inside a GOP.  Only while idle),
  * "stats" (default 0 = exactly the launches, buffers and bytes of a handle that never heard of it.  1 = every picture leaves a
  * record for m2v_picture_stats, see there: the same stream, one reconstruction more per GOP and a pass over source and reconstruction
- * per GOP step.  Only while idle, M2V_E_STATE otherwise). */
+ * per GOP step.  Only while idle, M2V_E_STATE otherwise),
+ * "gop_bytes_max" (default 0 = off.  B > 0 = NOT the module's behaviour: a byte cap per GOP, held on the device - see m2v_gop_report.
+ * Only while idle, M2V_E_STATE otherwise; a negative value is M2V_E_PARAM). */
 int m2v_set_option(m2v_enc *e, const char *name, long long value);
+
+/*
+ * A level per GOP.  NOT the module's behaviour (like option "conformant" and M2V_HEADER_TRUE): the module takes Q_LEVEL as a
+ * parameter and holds it for good.  The stream stays a legal one: the level appears in one place only, the quantiser_scale_code of
+ * every slice header (2 << level as the 5-bit code's value, RTL:2708-2710), which ISO/IEC 13818-2 lets change from slice to slice; the
+ * sequence header does not depend on it; and GOPs are closed, so a GOP coded at level q is, byte for byte, that GOP of the same clip
+ * encoded whole at Q_LEVEL = q.
+ *
+ * m2v_set_gop_levels: GOP k of every sequence STARTED afterwards is coded at levels[min(k, n - 1)], k = frame number /
+ * (pframes_count + 1).  Values are 1..4; anything else answers M2V_E_PARAM and the previous setting stays.  n == 0 or levels == NULL
+ * clears the setting (every GOP at the handle's Q_LEVEL again).  Entries past the sequence's last GOP are ignored.  The array is
+ * copied: it is the caller's again on return.  The setting is sampled when a sequence starts (where xsize16 / ysize16 /
+ * pframes_count are), stays until it is changed and survives m2v_reset.  It holds for the port path and every resident entry, for
+ * any "batch_frames" and "split_streams" (a GOP that continues in the next chunk keeps its level).  A schedule whose every used entry
+ * equals Q_LEVEL gives exactly the launches and the stream of a handle without one.  While a schedule or a cap is set every
+ * m2v_strip_* entry that starts something answers M2V_E_STATE - the rule "stats" and a set frame size follow.
+ */
+int m2v_set_gop_levels(m2v_enc *e, const uint8_t *levels, size_t n);
+
+/*
+ * Option "gop_bytes_max" = B > 0, resident entries (m2v_encode_resident*, also _begin / _end).
+ * The size of a GOP is its bytes in the stream, from its group_start_code (00 00 01 B8) up to the next one or to the
+ * sequence_end_code: the headers of its pictures (25 bytes for the I picture with the GOP header, 18 for a P picture) plus the bytes
+ * of their slices.  The sequence header is not part of GOP 0, the end code and the final padding not of the last one.
+ * GOP k is coded at the smallest level q >= start_k whose size is <= B; if none is, at 4.  start_k is the schedule's entry for k
+ * (m2v_set_gop_levels), or the handle's Q_LEVEL without a schedule.  The search goes upwards one level at a time and stops at the
+ * first fit, so "smallest" is well defined even where sizes are not monotone in q.  The result depends on the clip alone: not on
+ * "batch_frames", "split_streams" or "cu_pack".
+ * A chunk has to hold whole GOPs: with pframes_count + 1 > "batch_frames" the call that starts the sequence answers M2V_E_PARAM.
+ * The GOPs over the cap are encoded again on the device, up to three more times; the host waits for the device's verdict after each
+ * try (at most three waits per chunk, and only with the option on).  m2v_encode_resident*_begin does these waits INSIDE _begin: with
+ * the cap on, _begin returns with the sequence's last chunk enqueued, not with nothing waited for.
+ * The m2v_push_* calls that start a sequence answer M2V_E_STATE while the cap is set (the schedule does work there).
+ * With "stats" on, the picture records of a GOP that went again are those of its final level.
+ */
+typedef struct m2v_gop_stat {
+    uint32_t gop;            /* index of the GOP in its sequence                                             */
+    uint32_t first_frame;    /* its first picture, and how many it has (the last GOP may be cut short)       */
+    uint32_t frames;
+    uint32_t level;          /* the level it is coded at in the stream, 1..4                                  */
+    uint64_t bytes;          /* its size at that level, as defined above                                      */
+    uint32_t tries;          /* encodes of this GOP, 1..4                                                     */
+    uint32_t over;           /* 1 = even the final size exceeds B (level is then 4)                           */
+} m2v_gop_stat;              /* 32 bytes */
+/* Pops up to `cap` records, oldest first, into dst and returns how many it wrote; dst == NULL returns how many are waiting.  After
+ * m2v_encode_resident* or m2v_encode_resident_end has returned one record per GOP of that sequence is waiting.  Records still
+ * unread when the next sequence starts, or at m2v_reset, are dropped.  A sequence coded with the cap off leaves none: the answer is 0.
+ * Waits for nothing. */
+long long m2v_gop_report(m2v_enc *e, m2v_gop_stat *dst, size_t cap);
 
 /*
  * Per-picture statistics, computed on the device while a chunk is encoded (option "stats" = 1): the squared error of the
