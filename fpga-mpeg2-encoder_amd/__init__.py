@@ -41,6 +41,7 @@ EXPORTS = [
     "m2v_rgb_matrix", "m2v_push_rgb", "m2v_push_rgb_pull", "m2v_encode_resident_rgb", "m2v_encode_resident_rgb_begin",
     "m2v_set_frame_size", "m2v_fit_size", "m2v_picture_stats",
     "m2v_set_gop_levels", "m2v_gop_report",
+    "m2v_set_gop_starts", "m2v_gop_layout", "m2v_scene_report",
 ]
 
 # the 4:2:0 entry points (kept apart: tests/test_abi.py matches EXPORTS against names of letters and underscores only)
@@ -83,6 +84,30 @@ class GopStat(ctypes.Structure):
 # the same record as a numpy structured dtype (Mpeg2Encoder.gop_report)
 GOP_STAT_DTYPE = np.dtype([("gop", "<u4"), ("first_frame", "<u4"), ("frames", "<u4"), ("level", "<u4"), ("bytes", "<u8"), ("tries", "<u4"),
                            ("over", "<u4")])
+
+
+class SceneStat(ctypes.Structure):
+    """m2v_scene_stat (include/m2v_mi355x.h): one picture's record of m2v_set_gop_starts / option "scene_cut", 16 bytes"""
+    _fields_ = [("frame", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("diff", ctypes.c_uint64)]
+
+
+# the same record as a numpy structured dtype (Mpeg2Encoder.scene_report)
+SCENE_STAT_DTYPE = np.dtype([("frame", "<u4"), ("flags", "<u4"), ("diff", "<u8")])
+GOP_FIRST, GOP_CADENCE, GOP_LIST, GOP_CUT = 1, 2, 4, 8           # M2V_GOP_*
+
+
+def gop_layout(pframes_count, starts, nframes):
+    """m2v_gop_layout: (the M2V_GOP_* reasons of each of nframes frames as a uint8 array - non-zero where a GOP starts -, the number
+    of GOPs) for pframes_count and the list `starts` (strictly ascending, ValueError otherwise).  Plain arithmetic, no GPU."""
+    st = [] if starts is None else [int(v) for v in starts]
+    if any(v < 0 or v > 0xFFFFFFFF for v in st):
+        raise ValueError("gop_layout: a frame number is 0 .. 2^32 - 1")
+    buf = (ctypes.c_uint32 * max(1, len(st)))(*st)
+    flags = np.zeros(int(nframes), np.uint8)
+    n = lib().m2v_gop_layout(int(pframes_count), buf if st else None, len(st), int(nframes), flags.ctypes.data if nframes else None)
+    if n < 0:
+        raise ValueError("gop_layout: the list must be strictly ascending")
+    return flags, int(n)
 
 
 def psnr_from_sse(sse, samples):
@@ -213,6 +238,11 @@ def lib(debug=False):
             L.m2v_set_gop_levels.argtypes = [vp, vp, sz]
             L.m2v_gop_report.restype = ctypes.c_longlong
             L.m2v_gop_report.argtypes = [vp, vp, sz]
+            L.m2v_set_gop_starts.argtypes = [vp, vp, sz]
+            L.m2v_gop_layout.restype = ctypes.c_longlong
+            L.m2v_gop_layout.argtypes = [u32, vp, sz, sz, vp]
+            L.m2v_scene_report.restype = ctypes.c_longlong
+            L.m2v_scene_report.argtypes = [vp, vp, sz]
         except AttributeError:
             # an OLDER build handed in through M2V_LIB for a same-box A/B (tools/ab.sh) may lack the newer entry points; the library of
             # this tree must have every one of them (tests/test_abi.py)
@@ -412,6 +442,30 @@ class Mpeg2Encoder:
             self._stats = bool(value)
         if name == "gop_bytes_max":
             self._gop_cap = int(value)
+        if name == "scene_cut":
+            self._scene_cut = int(value)
+
+    def set_gop_starts(self, frames):
+        """m2v_set_gop_starts: in every sequence started from now on a GOP also starts at each of these frame numbers (strictly
+        ascending; M2VError otherwise, and the previous setting stays); None or an empty sequence clears the setting.  Not the
+        module's behaviour."""
+        st = [] if frames is None else [int(v) for v in frames]
+        if any(v < 0 or v > 0xFFFFFFFF for v in st):
+            raise M2VError("m2v_set_gop_starts failed (-1): a frame number is 0 .. 2^32 - 1")
+        buf = (ctypes.c_uint32 * max(1, len(st)))(*st)
+        self._chk(self._L.m2v_set_gop_starts(self._h, buf if st else None, len(st)), "m2v_set_gop_starts")
+        self._gop_starts = st or None
+
+    def scene_report(self, max_records=None):
+        """Pops the waiting records of m2v_scene_report, oldest first, at most max_records of them: a numpy structured array of
+        SCENE_STAT_DTYPE - one per picture of a sequence that had a list of GOP starts or option "scene_cut", empty otherwise."""
+        n = self._chk(self._L.m2v_scene_report(self._h, None, 0), "m2v_scene_report")
+        if max_records is not None:
+            n = min(n, int(max_records))
+        out = np.zeros(n, SCENE_STAT_DTYPE)
+        if n:
+            n = self._chk(self._L.m2v_scene_report(self._h, out.ctypes.data, n), "m2v_scene_report")
+        return out[:n]
 
     def set_gop_levels(self, levels):
         """m2v_set_gop_levels: GOP k of every sequence started from now on is coded at levels[min(k, len - 1)], each 1..4 (M2VError
@@ -665,7 +719,7 @@ class Mpeg2Encoder:
         return out[:n]
 
     def encode_tensor(self, frames, pframes_count, order="rgb", matrix="bt601", out=None, header=None, stats=False, gop_levels=None,
-                      gop_bytes_max=0):
+                      gop_bytes_max=0, gop_starts=None, scene_cut=0):
         """One whole sequence from a torch image tensor on the handle's device, in one call: contiguous uint8 [N, H, W, 3] (order
         "rgb" / "bgr"), [N, H, W, 4] ("rgbx" / "bgrx" / "xrgb" / "xbgr") or [N, 3, H, W] ("rgb": planar).  Runs
         m2v_encode_resident_rgb on torch's current stream and returns the stream bytes as a uint8 device tensor (a view of `out` when
@@ -679,7 +733,9 @@ class Mpeg2Encoder:
         call, the handle's own setting is back afterwards).
         gop_levels = a sequence of levels 1..4, gop_bytes_max = B > 0: a level per GOP and a byte cap per GOP for this call
         (set_gop_levels, option "gop_bytes_max"; the handle's own settings are back afterwards).  The cap's records wait for
-        gop_report()."""
+        gop_report().
+        gop_starts = a strictly ascending sequence of frame numbers, scene_cut = T > 0: where GOPs start in this call besides the cadence
+        (set_gop_starts, option "scene_cut"; the handle's own settings are back afterwards).  The records wait for scene_report()."""
         import torch
         if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4:
             raise ValueError("encode_tensor: a uint8 tensor of 4 dimensions is required")
@@ -718,11 +774,16 @@ class Mpeg2Encoder:
         if stats and not stats_before:
             self.set_option("stats", 1)
         levels_before, cap_before = getattr(self, "_gop_levels", None), getattr(self, "_gop_cap", 0)
+        starts_before, cut_before = getattr(self, "_gop_starts", None), getattr(self, "_scene_cut", 0)
         try:
             if gop_levels is not None:
                 self.set_gop_levels(gop_levels)
             if gop_bytes_max:
                 self.set_option("gop_bytes_max", gop_bytes_max)
+            if gop_starts is not None:
+                self.set_gop_starts(gop_starts)
+            if scene_cut:
+                self.set_option("scene_cut", scene_cut)
             nb = self.encode_resident_rgb(frames.data_ptr(), N, out.data_ptr(), out.numel(), xs, ys, pframes_count, layout, matrix,
                                           stream=torch.cuda.current_stream(frames.device).cuda_stream)
             records = self.picture_stats() if stats else None
@@ -735,6 +796,10 @@ class Mpeg2Encoder:
                 self.set_gop_levels(levels_before)
             if gop_bytes_max:
                 self.set_option("gop_bytes_max", cap_before)
+            if gop_starts is not None:
+                self.set_gop_starts(starts_before)
+            if scene_cut:
+                self.set_option("scene_cut", cut_before)
         return (out[:nb], records) if stats else out[:nb]
 
     def encode_resident_end(self):

@@ -101,10 +101,20 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
     // ---- per-frame jobs, GOP segments, reconstruction slots ----
     std::vector<FrameJob> jobs(nf);
     std::vector<int> seg_start;                   // chunk-frame index where each GOP segment starts
+    // where GOPs start: the fixed cadence, or - with a list or the detector's flags - the rule stepped on from where the last chunk left it
+    const bool layout = seq_has_layout(e);
+    GopRule rule{e->pframes, e->seq_starts.data(), e->seq_starts.size(), 0, e->gop_s, e->gop_k};
+    if (layout) e->st().scene.clear();
     for (size_t k = 0; k < nf; ++k) {
         const size_t n = e->frames_total + k;
         jobs[k].in = d_frames + k * frame_bytes;
         jobs[k].i_frame = (int32_t)(n % gop);
+        if (layout) {
+            const bool det = e->seq_cut != 0;
+            const uint32_t fl = rule.step(n, det && e->chunk_cut[k]);
+            jobs[k].i_frame = (int32_t)(n - rule.s);
+            e->st().scene.push_back(m2v_scene_stat{(uint32_t)n, fl, det ? e->chunk_diff[k] : 0ull});
+        }
         jobs[k].n = (uint32_t)n;
         jobs[k].valid_beats = (last && k == nf - 1) ? last_valid_beats : bpf;
         jobs[k].ref = nullptr;
@@ -112,11 +122,14 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
         jobs[k].fidx = 0;
         jobs[k].hidx = -1;
         jobs[k].rhidx = -1;
-        jobs[k].q = (uint32_t)level_of_frame(e, n);       // (a GOP that continues across a chunk boundary keeps its level: n counts from the sequence's start)
+        // (a GOP that continues across a chunk boundary keeps its level: n counts from the sequence's start, and so does the rule's k)
+        jobs[k].q = (uint32_t)(layout ? level_of_gop(e, rule.k - 1) : level_of_frame(e, n));
         jobs[k].pad = 0;
         if (k == 0 || jobs[k].i_frame == 0) seg_start.push_back((int)k);
     }
     const size_t nseg = seg_start.size();
+    e->gop_s = rule.s;
+    e->gop_k = rule.k;
     e->rec_bytes = (size_t)g.rysz * 3 / 2;           // tiled, with one extra tile column (rec_luma_off)
     // option "stats" measures every picture against its reconstruction: the unreferenced ones get a slot too (k_mb's need_rec is the
     // runtime test job.rec != nullptr).  The two alternating slots of a segment still do: frame k writes slot k & 1 and reads (k - 1) & 1,
@@ -146,7 +159,13 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
             for (size_t k = a; k < b; ++k) {
                 // a frame's reconstruction is needed iff a P frame of the same GOP follows (ref(f+1) = recon(f))
                 const bool known_last = last && k == nf - 1;
-                const bool followed = (uint32_t)jobs[k].i_frame < e->pframes && !known_last;
+                bool followed = (uint32_t)jobs[k].i_frame < e->pframes && !known_last;
+                if (layout) {
+                    // ... which a start from the list, or a cut, ends early.  The next chunk's cuts are not known yet: its first frame may
+                    // turn out not to need this one
+                    if (k + 1 < nf) followed = jobs[k + 1].i_frame != 0;
+                    else if (std::binary_search(e->seq_starts.begin(), e->seq_starts.end(), (uint32_t)(e->frames_total + nf))) followed = false;
+                }
                 int prev = (k == a) ? (jobs[k].i_frame != 0 ? e->persist_slot : -1) : rec_slot[k - 1];
                 if (jobs[k].i_frame != 0) {
                     if (prev < 0) throw HipError{hipErrorInvalidValue, "P frame without a reference"};
@@ -519,6 +538,7 @@ void m2v_destroy(m2v_enc *e)
     e->d_jobs.release(); e->d_lists.release(); e->d_joblist.release(); e->d_ctl.release(); e->d_segs.release(); e->d_x444.release(); e->d_fit.release();
     e->d_pstat.release();
     e->d_gop.release();
+    scene_release(e);
     if (e->ev_gop) (void)hipEventDestroy(e->ev_gop);
     if (e->h_redo) (void)hipHostFree(e->h_redo);
     for (auto p : e->rec_pool) (void)hipFree(p);
@@ -588,6 +608,7 @@ int m2v_reset(m2v_enc *e)
     e->fifo.clear(); e->fifo_rd = 0; e->end_pending = false;
     stats_drop(e);
     gop_drop(e);
+    scene_drop(e);
     // a strip sequence abandoned between m2v_strip_begin and m2v_strip_finish: back to the full frame
     e->strip_active = false;
     e->strip_inflight = false;
@@ -685,6 +706,12 @@ int m2v_set_option(m2v_enc *e, const char *name, long long value)
         e->gop_bytes_max = (unsigned long long)value;
         return M2V_OK;
     }
+    if (!strcmp(name, "scene_cut")) {
+        if (e->state != m2v_enc::IDLE) { e->set_err("m2v_set_option: \"scene_cut\" can be set only while the handle is idle"); return M2V_E_STATE; }
+        if (value < 0 || value > 65280) { e->set_err("m2v_set_option: scene_cut is a threshold 1..65280, 0 = off"); return M2V_E_PARAM; }
+        e->scene_cut = (uint32_t)value;
+        return M2V_OK;
+    }
     if (!strcmp(name, "dct_mfma")) { e->dct_mfma = value != 0; return M2V_OK; }
     if (!strcmp(name, "strip_graph")) { e->strip_graph_opt = value < 0 ? -1 : value != 0; return M2V_OK; }
     if (!strcmp(name, "stream_priority")) {
@@ -724,7 +751,7 @@ int m2v_set_option(m2v_enc *e, const char *name, long long value)
 
 int m2v_kernel_stats(const m2v_enc *e, int kernel, double *ms, double *units)
 {
-    if (!e || kernel < 0 || kernel > 4) return M2V_E_PARAM;
+    if (!e || kernel < 0 || kernel > 5) return M2V_E_PARAM;
     if (ms) *ms = e->stats[kernel].ms;
     if (units) *units = e->stats[kernel].units;
     return e->stats[kernel].launches;

@@ -11,6 +11,9 @@
 //   m2v_strips.hip    strip mode (BASELINE config c5) and the communicators of m2v_comm.hpp
 //   m2v_gop.hip       a level per GOP: the caller's schedule (m2v_set_gop_levels) and option "gop_bytes_max", the byte cap the device judges
 //                     (k_gop_judge, m2v_gop_kernels.hpp, launched from m2v_launch.hip) and the host's redo loop; m2v_gop_report
+//   m2v_scene.hip     where GOPs start: the rule (gop_layout_run, m2v_gop_layout), the caller's list (m2v_set_gop_starts), option
+//                     "scene_cut" - the detector's buffers, its launches (k_mbsum, k_scene_judge, m2v_scene_kernels.hpp, launched from
+//                     m2v_launch.hip) and the host's one wait per chunk - and m2v_scene_report
 //   m2v_stats.hip     option "stats": the per-picture records of m2v_picture_stats - their buffers, their way to the host and the queue
 //                     they wait in (the kernels that fill them, m2v_stats_kernels.hpp, need m2v_kernels.hpp and so belong to m2v_launch.hip)
 #pragma once
@@ -137,6 +140,7 @@ struct m2v_enc {
         m2v_gop_stat *h_gop = nullptr;        // pinned: the chunk's GOP records (option "gop_bytes_max"), written by k_gop_judge itself
         size_t h_gop_cap = 0;
         size_t ngop = 0;                      // records of the submitted chunk that gop_collect has not moved to the handle's queue yet
+        std::vector<m2v_scene_stat> scene;    // the submitted chunk's records of m2v_scene_report (plan_chunk makes them on the host)
         int stage = 0;                        // 0 free, 1 encode submitted, 2 stream read-back submitted
         bool last = false;
         size_t bytes = 0;
@@ -282,12 +286,28 @@ struct m2v_enc {
     uint8_t *h_redo = nullptr;            // pinned staging of the redo lists
     size_t h_redo_cap = 0;
 
+    // where GOPs start (m2v_scene.hip): the caller's list and the detector's threshold - the settings, and what the sequence in progress
+    // sampled from them when it started (seq_starts empty and seq_cut 0: the fixed cadence, nothing below is touched)
+    std::vector<uint32_t> gop_starts, seq_starts;
+    uint32_t scene_cut = 0, seq_cut = 0;
+    size_t gop_s = 0, gop_k = 0;          // the GOP in progress at frames_total: the frame number of its I picture, and its ordinal
+    std::vector<uint8_t> chunk_cut;       // the detector's flag of every frame of the chunk about to be planned (scene_detect -> plan_chunk)
+    std::vector<unsigned long long> chunk_diff;       // ... and D(n)
+    std::deque<m2v_scene_stat> scene_q;   // completed pictures' records nobody has popped yet
+    DevBuf<uint32_t> d_mbsum;             // [frame][mb] luma sums of the chunk
+    DevBuf<uint32_t> d_carry;             // 2 x [mb]: the sums of the last frame of the previous chunk, and where this chunk leaves its own
+    int carry_cur = -1;                   // which half holds the previous chunk's (-1: the sequence starts with this chunk)
+    DevBuf<uint8_t> d_scene;              // SceneRec of every frame of the chunk
+    uint8_t *h_scene = nullptr;           // pinned: the same records, written by k_scene_judge itself
+    size_t h_scene_cap = 0;
+    hipEvent_t ev_scene = nullptr;        // behind the k_scene_judge whose flags the host needs
+
     // debug bookkeeping of the last resident encode
     size_t dbg_frames = 0;
     std::vector<int> dbg_rec_slot;
 
     // profiling
-    KStat stats[5];
+    KStat stats[6];
     std::vector<TimedLaunch> timed;
     std::vector<hipEvent_t> ev_pool;      // timing events, reused from step to step
     size_t ev_used = 0;
@@ -397,17 +417,25 @@ inline bool strip_refuses(m2v_enc *e, const char *fn)
         e->set_err("%s: a level per GOP is set (m2v_set_gop_levels or option \"gop_bytes_max\"): a strip is coded at the handle's Q_LEVEL", fn);
         return true;
     }
+    if (!e->gop_starts.empty() || e->scene_cut) {
+        e->set_err("%s: GOP starts are set (m2v_set_gop_starts or option \"scene_cut\"): the strips of a frame run at the fixed cadence", fn);
+        return true;
+    }
     e->seq_levels.clear();      // (what an earlier whole-frame sequence sampled)
     e->seq_cap = 0;
+    e->seq_starts.clear();
+    e->seq_cut = 0;
     return false;
 }
 // ---- m2v_gop.hip ----
-// the level frame n of the sequence in progress is coded at, before the cap has had its say
-inline int level_of_frame(const m2v_enc *e, size_t n)
+// the level GOP number k of the sequence in progress is coded at, before the cap has had its say
+inline int level_of_gop(const m2v_enc *e, size_t k)
 {
     if (e->seq_levels.empty()) return e->Q;
-    return e->seq_levels[std::min(n / (e->pframes + 1u), e->seq_levels.size() - 1)];
+    return e->seq_levels[std::min(k, e->seq_levels.size() - 1)];
 }
+// ... and frame n of a sequence at the fixed cadence (with a list or the detector plan_chunk counts the GOPs itself)
+inline int level_of_frame(const m2v_enc *e, size_t n) { return level_of_gop(e, n / (e->pframes + 1u)); }
 // the start of a sequence samples the schedule and the cap (where sample_frame_size is called; with_cap: the resident entries)
 void sample_gop_levels(m2v_enc *e, bool with_cap);
 // the chunk's steps have been enqueued and every group has joined s: slice scan, k_gop_judge, and the GOPs over the cap again at the next
@@ -422,6 +450,37 @@ inline bool cap_refuses(m2v_enc *e, const char *fn)
     e->set_err("%s: option \"gop_bytes_max\" is set: the cap needs whole GOPs in a chunk, which only the resident entries give", fn);
     return true;
 }
+
+// ---- m2v_scene.hip ----
+// The rule of include/m2v_mi355x.h, frame by frame: s = the I picture of the GOP in progress, k = GOP starts so far, list / at = the
+// caller's list and the first entry not yet passed.  step(n, cut) answers frame n's M2V_GOP_* bits (0: the GOP goes on) and moves on.
+struct GopRule {
+    uint32_t pf; const uint32_t *list; size_t nlist, at; size_t s, k;
+    uint32_t step(size_t n, bool cut)
+    {
+        uint32_t fl = 0;
+        if (n == 0) fl |= M2V_GOP_FIRST;
+        else if (n - s == (size_t)pf + 1) fl |= M2V_GOP_CADENCE;
+        while (at < nlist && list[at] < n) ++at;
+        if (at < nlist && list[at] == n) fl |= M2V_GOP_LIST;
+        if (cut) fl |= M2V_GOP_CUT;
+        if (fl) { s = n; ++k; }
+        return fl;
+    }
+};
+inline bool seq_has_layout(const m2v_enc *e) { return !e->seq_starts.empty() || e->seq_cut; }
+// the start of a sequence samples the list and the threshold (where sample_gop_levels is called; with_cut: the resident entries)
+void sample_gop_starts(m2v_enc *e, bool with_cut);
+// a sequence start with the cap and a list or the detector together: true = refused (M2V_E_STATE)
+bool layout_refuses_cap(m2v_enc *e, const char *fn);
+// the port entries that start a sequence: true = refused (M2V_E_STATE) because option "scene_cut" is set
+bool cut_refuses(m2v_enc *e, const char *fn);
+// option "scene_cut", in front of plan_chunk: k_mbsum and k_scene_judge over the chunk's nf frames on s, then the one wait; leaves
+// e->chunk_cut / e->chunk_diff
+void scene_detect(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf);
+void scene_collect(m2v_enc *e, m2v_enc::HostStage &h);
+void scene_drop(m2v_enc *e);
+void scene_release(m2v_enc *e);
 
 // PkFrame::layout of a planar 4:4:4 frame of a sequence that pads its frames (no other planar frame travels as a run)
 constexpr int kPk444 = 8;
@@ -508,6 +567,10 @@ void launch_picstat_mb(m2v_enc *e, hipStream_t s, size_t nf);
 // option "gop_bytes_max": one block per GOP of the chunk's nf frames (whole GOPs of gop frames, the last one may be cut short) sums the
 // GOP's bytes, writes its record to e->d_gop and to h_recs (pinned) and raises FrameJob::q of a GOP over the cap (k_gop_judge)
 void launch_gop_judge(m2v_enc *e, hipStream_t s, size_t nf, uint32_t gop, unsigned long long cap, m2v_gop_stat *h_recs);
+// option "scene_cut": luma sums of the macroblocks of nf planar 4:4:4 frames into e->d_mbsum (k_mbsum), then one block per frame judges
+// the difference to the frame before against limit = T * mbs and writes its record to e->d_scene and to h_recs (pinned; k_scene_judge)
+void launch_mbsum(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf);
+void launch_scene_judge(m2v_enc *e, hipStream_t s, size_t nf, unsigned long long limit, const uint32_t *carry_in, uint32_t *carry_out, void *h_recs);
 int debug_table(int which, int i, int j);
 
 }  // namespace m2v

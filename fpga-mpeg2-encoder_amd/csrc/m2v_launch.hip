@@ -8,6 +8,7 @@
 #include "m2v_kernels.hpp"
 #include "m2v_stats_kernels.hpp"
 #include "m2v_gop_kernels.hpp"
+#include "m2v_scene_kernels.hpp"
 
 namespace m2v {
 
@@ -429,6 +430,25 @@ void launch_gop_judge(m2v_enc *e, hipStream_t s, size_t nf, uint32_t gop, unsign
     const size_t nseg = (nf + gop - 1) / gop;
     hipLaunchKernelGGL(k_gop_judge, dim3((unsigned)nseg), dim3(kJudgeThreads), 0, s, e->d_jobs.p, e->g, (int)nf, (int)gop, e->d_slice_bytes.p, cap,
                        e->d_gop.p, h_recs);
+    HIPCHK(hipGetLastError());
+}
+
+// option "scene_cut": one wavefront per 16 rows x 256 columns of luma.  The 16-byte loads only where every row starts on a 16-byte
+// boundary: the width is whole macroblocks, so that is the first frame's address alone
+void launch_mbsum(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf)
+{
+    const Geom &g = e->g;
+    const int units_x = (g.mbw + 15) / 16;
+    const dim3 grid((unsigned)(nf * (size_t)g.mbh * (size_t)units_x));
+    if (((uintptr_t)d_frames & 15) == 0) hipLaunchKernelGGL(k_mbsum<true>, grid, dim3(64), 0, s, d_frames, g, units_x, e->d_mbsum.p);
+    else hipLaunchKernelGGL(k_mbsum<false>, grid, dim3(64), 0, s, d_frames, g, units_x, e->d_mbsum.p);
+    HIPCHK(hipGetLastError());
+}
+
+void launch_scene_judge(m2v_enc *e, hipStream_t s, size_t nf, unsigned long long limit, const uint32_t *carry_in, uint32_t *carry_out, void *h_recs)
+{
+    hipLaunchKernelGGL(k_scene_judge, dim3((unsigned)nf), dim3(kSceneThreads), 0, s, e->d_mbsum.p, e->g.mbs, (int)nf, limit, carry_in, carry_out,
+                       (SceneRec *)e->d_scene.p, (SceneRec *)h_recs);
     HIPCHK(hipGetLastError());
 }
 

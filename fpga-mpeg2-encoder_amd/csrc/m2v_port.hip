@@ -475,6 +475,7 @@ void progress(m2v_enc *e, bool block, int until = -1, PullSink *sink = nullptr)
         e->stream_bytes += h.bytes;
         if (h.last) e->end_pending = true;
         stats_collect(e, h);            // (the chunk's picture records came back in front of its control word)
+        scene_collect(e, h);
         h.stage = 0;
         e->pending.pop_front();
         if (idx == until) break;
@@ -578,6 +579,7 @@ void start_sequence(m2v_enc *e, uint32_t xs, uint32_t ys, uint32_t pf)
     e->g = make_geom(e, xs, ys);            // latched on the first beat (RTL:1060-1065)
     e->pframes = pf & 0xFFu;
     sample_gop_levels(e, false);            // (the schedule; the cap is the resident entries': the callers refuse with it set)
+    sample_gop_starts(e, false);            // (the list; the detector likewise)
     e->state = m2v_enc::DURING;
     e->frames_total = 0;
     e->first_chunk = true;
@@ -593,6 +595,7 @@ void start_sequence(m2v_enc *e, uint32_t xs, uint32_t ys, uint32_t pf)
     e->stream_bytes = 0;
     stats_drop(e);
     gop_drop(e);
+    scene_drop(e);
     for (auto &st : e->stats) st = KStat{};
     ensure_staging(e);
 }
@@ -695,7 +698,7 @@ static int push_beats_impl(m2v_enc *e, void *argp)
         return M2V_OK;
     }
     if (e->state == m2v_enc::IDLE) {
-        if (cap_refuses(e, "m2v_push_beats")) return M2V_E_STATE;
+        if (cap_refuses(e, "m2v_push_beats") || cut_refuses(e, "m2v_push_beats")) return M2V_E_STATE;
         start_sequence(e, a->xs, a->ys, a->pf);
     }
     const Geom &g = e->g;
@@ -849,7 +852,7 @@ static int push_frames_impl(m2v_enc *e, void *argp)
     };
     if (e->state == m2v_enc::ENDED || a->n == 0) { settle_deferred(); return M2V_OK; }
     if (e->state == m2v_enc::IDLE) {
-        if (cap_refuses(e, "m2v_push_frames")) { settle_deferred(); return M2V_E_STATE; }
+        if (cap_refuses(e, "m2v_push_frames") || cut_refuses(e, "m2v_push_frames")) { settle_deferred(); return M2V_E_STATE; }
         if (!sample_frame_size(e, "m2v_push_frames", a->xs, a->ys)) { settle_deferred(); return M2V_E_PARAM; }
         start_sequence(e, a->xs, a->ys, a->pf);
     }

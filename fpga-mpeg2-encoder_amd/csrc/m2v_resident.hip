@@ -19,6 +19,7 @@ static int resident_end_impl(m2v_enc *e, void *argp)
     collect_timers(e);
     stats_collect(e, e->st());
     gop_collect(e, e->st());
+    scene_collect(e, e->st());
     if (e->st().h_ctl->overflow) { e->set_err("output buffer too small"); return M2V_E_OVERFLOW; }
     if (bytes) *bytes = (size_t)e->st().h_ctl->total_bytes;
     return M2V_OK;
@@ -31,11 +32,13 @@ static int resident_impl(m2v_enc *e, void *argp)
     e->resident_empty = false;
     stats_drop(e);                                      // (the previous sequence's unread picture records)
     gop_drop(e);
+    scene_drop(e);
     if (a->n == 0) {                                    // no beat: the sequence never starts
         if (a->bytes) *a->bytes = 0;
         e->resident_empty = a->async;                   // only _begin leaves an _end to answer
         return M2V_OK;
     }
+    if (layout_refuses_cap(e, "m2v_encode_resident")) return M2V_E_STATE;
     if (!sample_frame_size(e, "m2v_encode_resident", a->xs, a->ys)) return M2V_E_PARAM;
     if (e->gop_bytes_max && (size_t)(a->pf & 0xFFu) + 1 > e->batch_frames) {
         e->set_err("m2v_encode_resident: option \"gop_bytes_max\" needs whole GOPs in a chunk: pframes_count + 1 = %u is more than batch_frames = %zu",
@@ -46,6 +49,7 @@ static int resident_impl(m2v_enc *e, void *argp)
     e->g = make_geom(e, a->xs, a->ys);
     e->pframes = a->pf & 0xFFu;
     sample_gop_levels(e, true);
+    sample_gop_starts(e, true);
     e->frames_total = 0;
     e->persist_slot = -1;
     for (auto &st : e->stats) st = KStat{};
@@ -77,8 +81,9 @@ static int resident_impl(m2v_enc *e, void *argp)
             e->x444_bytes = nf * fb;
             frames = e->d_x444.p;
         }
+        if (e->seq_cut) scene_detect(e, s, frames, nf);        // option "scene_cut": the chunk's flags in front of its plan (waits for the device)
         encode_chunk(e, s, frames, nf, first, last, g.ysz / 4, a->d_out, /*advance=*/k > 0);
-        if (!last) { HIPCHK(hipStreamSynchronize(s)); stats_collect(e, e->st()); gop_collect(e, e->st()); }    // the per-chunk work buffers are reused
+        if (!last) { HIPCHK(hipStreamSynchronize(s)); stats_collect(e, e->st()); gop_collect(e, e->st()); scene_collect(e, e->st()); }    // the per-chunk work buffers are reused
     }
     HIPCHK(hipMemcpyAsync(e->st().h_ctl, e->d_ctl.p, sizeof(StreamCtl), hipMemcpyDeviceToHost, s));
     e->resident_inflight = true;

@@ -2,7 +2,7 @@
 //
 //   m2v_tb [-XL n] [-YL n] [-VL n] [-Q n] [-p pframes] [-d device] [-bubbles] [-conformant] [-ps] [-ts]
 //          [-i420 | -yv12 | -nv12 | -nv21 | -rgb24 | -bgr24 | -rgbx | -bgrx | -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f]
-//          [-pad | -truesize] [-stats] [-qgop q0,q1,...]
+//          [-pad | -truesize] [-stats] [-qgop q0,q1,...] [-istart n0,n1,...] [-scenecut T]
 //          in.yuv W H out.m2v  [in2.yuv W2 H2 out2.m2v ...]
 //
 // -pad: W, H are any size from 49 up; the files hold frames of that size in the chosen format, which are padded to whole macroblocks on
@@ -19,6 +19,11 @@
 // include/m2v_mi355x.h says what that means without -conformant).
 // -qgop 1,4,3: a level per GOP (m2v_set_gop_levels): GOP k of every video at the k-th value, the last value for the GOPs beyond; NOT
 // the module's behaviour, -Q stays the handle's level.
+// -istart 5,9,40: a GOP also starts at each of these frame numbers of every video (m2v_set_gop_starts; strictly ascending); NOT the
+// module's behaviour.  The port path takes it.
+// -scenecut T: option "scene_cut" = T, 1..65280: a GOP also starts where the device finds a scene cut; NOT the module's behaviour.  The
+// detector belongs to the resident entries, so with this flag - and only with it - every file's frames are staged in device memory
+// whole and encoded by one m2v_encode_resident* call instead of going through the port.  Does not go with -bubbles.
 // -conformant switches the encoder's option "conformant" on (ISO reconstruction loop; NOT byte-identical to the RTL).
 // -ps / -ts additionally write out.m2v.mpg / out.m2v.ts: the same elementary stream in an MPEG-2 program / transport
 // stream (include/m2v_container.h), so the result plays in an ordinary player.
@@ -36,6 +41,8 @@
 #include <string>
 #include <vector>
 
+#include <hip/hip_runtime_api.h>
+
 #include "../../include/m2v_container.h"
 #include "../../include/m2v_mi355x.h"
 
@@ -43,7 +50,10 @@ int main(int argc, char **argv)
 {
     int XL = 7, YL = 6, VL = 3, Q = 2, pf = 23, dev = 0, bubbles = 0, conformant = 0, want_ps = 0, want_ts = 0, layout420 = -1, layouts = 0, rgb = -1, matrix = M2V_RGB_BT601,
         bad_matrix = 0, pad = 0, truesize = 0, stats = 0;
+    long long scenecut = 0;
     std::vector<uint8_t> qgop;
+    std::vector<uint32_t> istart;
+    bool have_istart = false;
     int i = 1;
     for (; i < argc && argv[i][0] == '-'; ++i) {
         if (!strcmp(argv[i], "-bubbles")) { bubbles = 1; continue; }
@@ -69,6 +79,17 @@ int main(int argc, char **argv)
             ++i;
             continue;
         }
+        if (!strcmp(argv[i], "-istart")) {
+            have_istart = true;
+            for (const char *c = argv[i + 1]; *c;) {
+                if (*c >= '0' && *c <= '9') { char *end = nullptr; istart.push_back((uint32_t)strtoul(c, &end, 10)); c = end; }
+                else if (*c == ',') ++c;
+                else { istart.assign(2, 0); break; }                // (not a list: m2v_set_gop_starts says so)
+            }
+            ++i;
+            continue;
+        }
+        if (!strcmp(argv[i], "-scenecut")) { scenecut = atoll(argv[i + 1]); ++i; continue; }
         if (!strcmp(argv[i], "-matrix")) {
             static const char *const names[] = {"bt601", "bt709", "bt601f", "bt709f"};
             for (k = 0; k < 4 && strcmp(argv[i + 1], names[k]); ++k) {}
@@ -83,9 +104,10 @@ int main(int argc, char **argv)
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
         ++i;
     }
-    if ((argc - i) < 4 || (argc - i) % 4 || layouts > 1 || bad_matrix || ((layouts || pad) && bubbles)) {          // (there are no 4:2:0 or RGB beats)
+    if ((argc - i) < 4 || (argc - i) % 4 || layouts > 1 || bad_matrix || ((layouts || pad || scenecut) && bubbles)) {          // (there are no 4:2:0 or RGB beats)
         fprintf(stderr, "usage: %s [-XL n] [-YL n] [-VL n] [-Q n] [-p pframes] [-d dev] [-i420 | -yv12 | -nv12 | -nv21 | -rgb24 | -bgr24 | -rgbx | -bgrx |"
-                        " -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f] [-pad | -truesize] [-stats] [-qgop q0,q1,...] in.yuv W H out.m2v ...\n", argv[0]);
+                        " -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f] [-pad | -truesize] [-stats] [-qgop q0,q1,...] [-istart n0,n1,...] [-scenecut T] in.yuv W H out.m2v ...\n"
+                        "  -scenecut T stages every file's frames in device memory and encodes them with one resident call (the detector needs it)\n", argv[0]);
         return 2;
     }
     int err = 0;
@@ -94,6 +116,8 @@ int main(int argc, char **argv)
     if (conformant) m2v_set_option(e, "conformant", 1);
     if (stats && m2v_set_option(e, "stats", 1) < 0) { fprintf(stderr, "*** m2v_set_option(stats): %s\n", m2v_last_error(e)); return 1; }
     if (!qgop.empty() && m2v_set_gop_levels(e, qgop.data(), qgop.size()) < 0) { fprintf(stderr, "*** m2v_set_gop_levels: %s\n", m2v_last_error(e)); return 1; }
+    if (have_istart && m2v_set_gop_starts(e, istart.data(), istart.size()) < 0) { fprintf(stderr, "*** m2v_set_gop_starts: %s\n", m2v_last_error(e)); return 1; }
+    if (scenecut && m2v_set_option(e, "scene_cut", scenecut) < 0) { fprintf(stderr, "*** m2v_set_option(scene_cut): %s\n", m2v_last_error(e)); return 1; }
     int num_video = 0;
     for (; i + 3 < argc; i += 4) {
         ++num_video;
@@ -140,7 +164,32 @@ int main(int argc, char **argv)
                 if (until_last && n == 0 && !m2v_busy(e)) break;
             }
         };
-        while (fread(frame.data(), 1, fb, fi) == fb) {                                         // complete frames only (TB:220)
+        if (scenecut) {
+            // the detector runs in front of a chunk's plan on the resident entries: the file's complete frames go to device memory whole
+            std::vector<uint8_t> all;
+            while (fread(frame.data(), 1, fb, fi) == fb) { all.insert(all.end(), frame.begin(), frame.end()); ++frames; }
+            const size_t cap = frames * ((size_t)xs16 * ys16 * 1216 + (size_t)ys16 * 8 + 64) + 256;
+            void *d_in = nullptr, *d_out = nullptr;
+            size_t nb = 0;
+            if (frames) {
+                if (hipSetDevice(dev) != hipSuccess || hipMalloc(&d_in, all.size()) != hipSuccess || hipMalloc(&d_out, cap) != hipSuccess ||
+                    hipMemcpy(d_in, all.data(), all.size(), hipMemcpyHostToDevice) != hipSuccess) {
+                    fprintf(stderr, "*** staging %zu frames in device memory failed\n", frames);
+                    return 1;
+                }
+                const int r = rgb >= 0 ? m2v_encode_resident_rgb(e, xs16, ys16, (uint32_t)pf, d_in, frames, rgb, matrix, d_out, cap, &nb, nullptr)
+                            : layout420 >= 0 ? m2v_encode_resident420(e, xs16, ys16, (uint32_t)pf, d_in, frames, layout420, d_out, cap, &nb, nullptr)
+                                             : m2v_encode_resident(e, xs16, ys16, (uint32_t)pf, d_in, frames, d_out, cap, &nb, nullptr);
+                if (r < 0) { fprintf(stderr, "*** resident encode failed: %s\n", m2v_last_error(e)); return 1; }
+                es.resize(nb);
+                if (hipMemcpy(es.data(), d_out, nb, hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "*** read-back failed\n"); return 1; }
+                fwrite(es.data(), 1, nb, fo);
+                bytes = nb;
+                (void)hipFree(d_in);
+                (void)hipFree(d_out);
+            }
+        }
+        while (!scenecut && fread(frame.data(), 1, fb, fi) == fb) {                            // complete frames only (TB:220)
             printf("  start to encode video %d frame %3zu\n", num_video, frames);
             int r;
             if (rgb >= 0) {
@@ -165,8 +214,10 @@ int main(int argc, char **argv)
             ++frames;
             drain(false);
         }
-        if (m2v_sequence_stop(e) < 0) { fprintf(stderr, "*** stop failed: %s\n", m2v_last_error(e)); return 1; }
-        drain(true);
+        if (!scenecut) {
+            if (m2v_sequence_stop(e) < 0) { fprintf(stderr, "*** stop failed: %s\n", m2v_last_error(e)); return 1; }
+            drain(true);
+        }
         const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         fclose(fi);
         fclose(fo);

@@ -74,6 +74,10 @@ struct FrameJob {           // one per frame of the chunk (device memory)
     uint32_t       pad;     // (the structure is compared and copied as whole dwords: no unnamed padding)
 };
 
+// what k_scene_judge leaves per frame of a chunk, on the device and in pinned memory (option "scene_cut")
+struct SceneRec { unsigned long long diff; uint32_t flag; uint32_t pad; };
+static_assert(sizeof(SceneRec) == 16, "k_scene_judge writes the record in place");
+
 struct StreamCtl {          // device-resident stream bookkeeping, carried across chunks
     unsigned long long base_bytes;   // bytes of the stream already produced before this chunk
     unsigned long long total_bytes;  // bytes after this chunk (incl. final padding when last)

@@ -514,7 +514,9 @@ int m2v_strip_graph_stats(const m2v_enc *e, int *last_call_was_graph, int *recor
  * record for m2v_picture_stats, see there: the same stream, one reconstruction more per GOP and a pass over source and reconstruction
  * per GOP step.  Only while idle, M2V_E_STATE otherwise),
  * "gop_bytes_max" (default 0 = off.  B > 0 = NOT the module's behaviour: a byte cap per GOP, held on the device - see m2v_gop_report.
- * Only while idle, M2V_E_STATE otherwise; a negative value is M2V_E_PARAM). */
+ * Only while idle, M2V_E_STATE otherwise; a negative value is M2V_E_PARAM),
+ * "scene_cut" (default 0 = off.  T = 1..65280 = NOT the module's behaviour: a GOP starts where the device finds a scene cut - see
+ * m2v_set_gop_starts.  Only while idle, M2V_E_STATE otherwise; a value outside 0..65280 is M2V_E_PARAM). */
 int m2v_set_option(m2v_enc *e, const char *name, long long value);
 
 /*
@@ -567,6 +569,57 @@ typedef struct m2v_gop_stat {
 long long m2v_gop_report(m2v_enc *e, m2v_gop_stat *dst, size_t cap);
 
 /*
+ * Where GOPs start.  NOT the module's behaviour (like option "conformant" and a level per GOP): the module starts a GOP every
+ * pframes_count + 1 frames, counted from frame 0.  The stream stays a legal one: GOPs are closed, an I picture resets
+ * temporal_reference, and the GOP header's time code is a function of the frame number alone - so a GOP [s, s + L) is, byte for byte,
+ * GOP 0 of the frames s .. s + L - 1 encoded alone, with the time code of frame s.
+ *
+ * The rule.  With pf = pframes_count & 0xFF and s = the frame number of the I picture of the GOP in progress, frame n starts a GOP
+ * iff any of these holds:
+ *   M2V_GOP_FIRST    n = 0
+ *   M2V_GOP_CADENCE  n - s = pf + 1
+ *   M2V_GOP_LIST     n is in the caller's list (m2v_set_gop_starts)
+ *   M2V_GOP_CUT      option "scene_cut" is on and the detector flags n
+ * The cadence counts from the last I picture, whatever caused it: no GOP is longer than pf + 1.  The picture's place in its GOP is
+ * n - s, and a level schedule (m2v_set_gop_levels) goes by the GOP's ordinal, the count of GOP starts before n.  With neither list nor
+ * detector that is n / (pf + 1), and the launches and the stream are exactly those of a handle that never heard of either.
+ *
+ * m2v_set_gop_starts: the list, strictly ascending frame numbers; anything else answers M2V_E_PARAM and the previous setting stays.
+ * n == 0 or frames == NULL clears it.  The list is copied, sampled when a sequence starts (where xsize16 / ysize16 / pframes_count and
+ * the level schedule are), stays until changed and survives m2v_reset.  Entries past the sequence's end are ignored, and 0 and
+ * cadence positions change nothing.  It holds on the port path and on every resident entry, for any "batch_frames", "split_streams",
+ * "stats", "conformant", input format and set frame size.
+ *
+ * m2v_gop_layout: the rule as plain arithmetic (no GPU, no handle; the function the encoder itself plans with): writes the reasons
+ * (M2V_GOP_FIRST / CADENCE / LIST, never CUT) of each of nframes frames to flags_out (may be NULL) and returns the number of GOPs;
+ * M2V_E_PARAM for a list that is not strictly ascending.
+ *
+ * Option "scene_cut" = T, 1..65280, resident entries.  Integers only: S_n(mb) = the sum of the 256 luma samples of macroblock mb of
+ * picture n AS CODED - after the 4:2:0 expansion or RGB conversion, padding of a set frame size included; D(n) = the sum over all
+ * macroblocks of |S_n - S_(n-1)| for n >= 1, D(0) = 0; frame n is flagged iff D(n) > T * (macroblocks of a picture).  In words: the
+ * macroblocks' mean luma moved by more than T / 256 grey levels on average.  The result depends on the pictures alone, not on
+ * "batch_frames" or "split_streams".  Per chunk the host waits once for the device's flags before it plans the chunk (only with the
+ * option on); m2v_encode_resident*_begin does these waits INSIDE _begin, as with the cap.
+ *
+ * Refusals (m2v_last_error names the reason): an m2v_push_* call that starts a sequence while "scene_cut" is set answers M2V_E_STATE
+ * (the list does work there); every m2v_strip_* entry that starts something while a list or "scene_cut" is set answers M2V_E_STATE;
+ * a sequence that starts with "gop_bytes_max" set together with a list or "scene_cut" answers M2V_E_STATE with nothing started (the
+ * cap judges GOPs of the fixed cadence).
+ */
+enum { M2V_GOP_FIRST = 1, M2V_GOP_CADENCE = 2, M2V_GOP_LIST = 4, M2V_GOP_CUT = 8 };
+int m2v_set_gop_starts(m2v_enc *e, const uint32_t *frames, size_t n);
+long long m2v_gop_layout(uint32_t pframes_count, const uint32_t *starts, size_t n, size_t nframes, uint8_t *flags_out);
+typedef struct m2v_scene_stat {
+    uint32_t frame;          /* index of the picture in its sequence                                          */
+    uint32_t flags;          /* M2V_GOP_*: every reason that applies; the picture starts a GOP iff flags != 0  */
+    uint64_t diff;           /* D(n) as defined above; 0 with the detector off                                */
+} m2v_scene_stat;            /* 16 bytes */
+/* Pops up to `cap` records, oldest first, into dst and returns how many it wrote; dst == NULL returns how many are waiting: one per
+ * picture of a sequence that had a list or the detector, none otherwise.  They arrive as m2v_picture_stats' records do, are dropped
+ * when the next sequence starts and at m2v_reset.  Waits for nothing. */
+long long m2v_scene_report(m2v_enc *e, m2v_scene_stat *dst, size_t cap);
+
+/*
  * Per-picture statistics, computed on the device while a chunk is encoded (option "stats" = 1): the squared error of the
  * reconstruction against the source, the bits of the macroblock layer and the macroblock decisions.
  *
@@ -606,7 +659,8 @@ long long m2v_picture_stats(m2v_enc *e, m2v_picture_stat *dst, size_t cap);
 
 /* Per-kernel statistics of the last m2v_encode_resident call with "profile" = 1.
  * kernel: 0 = macroblock kernel on P frames, 1 = macroblock kernel on I frames,
- * 2 = strip mode's final assembly (k_strip_layout + k_strip_assemble), 3 = slice assembly (k_assemble), 4 = scans.
+ * 2 = strip mode's final assembly (k_strip_layout + k_strip_assemble), 3 = slice assembly (k_assemble), 4 = scans,
+ * 5 = the cut detector of option "scene_cut" (k_mbsum + k_scene_judge).
  * Returns launches; *ms = summed duration, *units = luma pixels processed. */
 int m2v_kernel_stats(const m2v_enc *e, int kernel, double *ms, double *units);
 

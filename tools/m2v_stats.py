@@ -6,9 +6,13 @@ PSNR), optional PSNR against the source through the repo's decoder, optional PS 
     python tools/m2v_stats.py out.m2v --yuv src.yuv --device [--VL 3] [--Q 2] [--pframes N] [--conformant]
     python tools/m2v_stats.py out.m2v --yuv src.rgb [--rgb24 | --bgr24 | --rgbx | --bgrx | --xrgb | --xbgr | --rgbp] [--matrix bt601]
     python tools/m2v_stats.py out.m2v --levels
+    python tools/m2v_stats.py out.m2v --gops
 
 --levels: the level every GOP was coded at (m2v_set_gop_levels, option "gop_bytes_max"), read from the quantiser_scale_code of its slice
 headers by the repo's decoder (Decoded.slice_qcodes; the Python decoder walks the whole stream: slow at full size).
+
+--gops: start frame and length of every GOP (m2v_set_gop_starts, option "scene_cut"), read from the stream's start codes on the CPU
+(the container scan: fast at any size).
 
 --device: the PSNR comes from the encoder itself (option "stats", m2v_picture_stats) instead of the Python decoder, which takes minutes
 per second of full-size video: the source is encoded again on the GPU with the given parameters, must give the file's stream byte for
@@ -38,6 +42,7 @@ def main():
     ap.add_argument("--ts", help="write an MPEG-2 transport stream")
     ap.add_argument("--pictures", action="store_true", help="one line per picture")
     ap.add_argument("--levels", action="store_true", help="one line per GOP: the level in its slice headers, its pictures, its bytes")
+    ap.add_argument("--gops", action="store_true", help="one line per GOP: its start frame, its length, its bytes")
     ap.add_argument("--device", action="store_true", help="PSNR from the encoder's own statistics: --yuv is encoded again on the GPU and must give this stream")
     ap.add_argument("--VL", type=int, default=3, help="--device: VECTOR_LEVEL the stream was made with")
     ap.add_argument("--Q", type=int, default=2, help="--device: Q_LEVEL the stream was made with")
@@ -72,6 +77,10 @@ def main():
             codes = sorted({c for row in qc[a:b] for c in row})
             names = ["%d" % (c.bit_length() - 1) if c & (c - 1) == 0 and 2 <= c <= 16 else "code %d" % c for c in codes]
             print("  GOP %4d  level %s  pictures %d..%d  %8d bytes" % (g, " + ".join(names), a, b - 1, sum(p.bytes for p in pics[a:b])))
+    if args.gops:
+        starts = [k for k, p in enumerate(pics) if p.gop_start] + [len(pics)]
+        for g, (a, b) in enumerate(zip(starts, starts[1:])):
+            print("  GOP %4d  start %6d  length %4d  %8d bytes" % (g, a, b - a, sum(p.bytes for p in pics[a:b])))
     if args.yuv and args.device:
         W, H = info.width, info.height
         xs, ys = M.fit_size(W, H)
