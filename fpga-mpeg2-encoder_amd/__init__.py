@@ -42,6 +42,7 @@ EXPORTS = [
     "m2v_set_frame_size", "m2v_fit_size", "m2v_picture_stats",
     "m2v_set_gop_levels", "m2v_gop_report",
     "m2v_set_gop_starts", "m2v_gop_layout", "m2v_scene_report",
+    "m2v_set_recon_out",
 ]
 
 # the 4:2:0 entry points (kept apart: tests/test_abi.py matches EXPORTS against names of letters and underscores only)
@@ -243,6 +244,7 @@ def lib(debug=False):
             L.m2v_gop_layout.argtypes = [u32, vp, sz, sz, vp]
             L.m2v_scene_report.restype = ctypes.c_longlong
             L.m2v_scene_report.argtypes = [vp, vp, sz]
+            L.m2v_set_recon_out.argtypes = [vp, vp, sz, ci]
         except AttributeError:
             # an OLDER build handed in through M2V_LIB for a same-box A/B (tools/ab.sh) may lack the newer entry points; the library of
             # this tree must have every one of them (tests/test_abi.py)
@@ -384,6 +386,24 @@ def pad_frames(frames, w, h, kind):
     return np.ascontiguousarray(np.concatenate(out, axis=1))
 
 
+def planes_of_recon(buf, w, h, layout="i420"):
+    """Frames of m2v_set_recon_out (`buf`: a numpy array or torch tensor of n * frame_bytes(w, h, layout) bytes, w x h the size set or the
+    coded size) -> (Y [n, h, w], U, V [n, (h + 1) / 2, (w + 1) / 2]): views where the layout allows it (the interleaved ones are strided)."""
+    name = layout if isinstance(layout, str) else {v: k for k, v in LAYOUTS_420.items()}[int(layout)]
+    if name not in LAYOUTS_420:
+        raise ValueError("planes_of_recon: unknown layout %r" % (layout,))
+    cw, ch = (w + 1) // 2, (h + 1) // 2
+    f = buf.reshape(-1, frame_bytes(w, h, name))
+    n = f.shape[0]
+    y = f[:, :w * h].reshape(n, h, w)
+    if name in ("i420", "yv12"):
+        a, b = f[:, w * h:w * h + cw * ch].reshape(n, ch, cw), f[:, w * h + cw * ch:].reshape(n, ch, cw)
+    else:
+        uv = f[:, w * h:].reshape(n, ch, cw, 2)
+        a, b = uv[..., 0], uv[..., 1]
+    return (y, a, b) if name in ("i420", "nv12") else (y, b, a)
+
+
 def set_header_size(stream, w, h):
     """a copy of an encoder stream (bytes) with the four size fields rewritten: horizontal / vertical size of sequence_header (12 + 12
     bits, bytes 4 - 6) and display size of sequence_display_extension (14 + 1 + 14 bits from byte 30).  What M2V_HEADER_TRUE writes."""
@@ -487,6 +507,13 @@ class Mpeg2Encoder:
         if n:
             n = self._chk(self._L.m2v_gop_report(self._h, out.ctypes.data, n), "m2v_gop_report")
         return out[:n]
+
+    def set_recon_out(self, ptr, cap, layout="i420"):
+        """m2v_set_recon_out: every resident sequence started from now on writes its reconstructed pictures, frame n at
+        ptr + n * frame_bytes(w, h, layout), into the `cap` bytes of device memory at `ptr`; ptr = None or 0 clears the setting.  Idle
+        handles only.  planes_of_recon takes the buffer apart."""
+        self._chk(self._L.m2v_set_recon_out(self._h, ptr or None, int(cap), _layout420(layout)), "m2v_set_recon_out")
+        self._recon_out = (int(ptr), int(cap), layout) if ptr else None
 
     def set_frame_size(self, w, h, header="module"):
         """m2v_set_frame_size: from now on every whole-frame entry takes w x h frames in its own format and pads them on the device;
@@ -719,7 +746,7 @@ class Mpeg2Encoder:
         return out[:n]
 
     def encode_tensor(self, frames, pframes_count, order="rgb", matrix="bt601", out=None, header=None, stats=False, gop_levels=None,
-                      gop_bytes_max=0, gop_starts=None, scene_cut=0):
+                      gop_bytes_max=0, gop_starts=None, scene_cut=0, recon=None):
         """One whole sequence from a torch image tensor on the handle's device, in one call: contiguous uint8 [N, H, W, 3] (order
         "rgb" / "bgr"), [N, H, W, 4] ("rgbx" / "bgrx" / "xrgb" / "xbgr") or [N, 3, H, W] ("rgb": planar).  Runs
         m2v_encode_resident_rgb on torch's current stream and returns the stream bytes as a uint8 device tensor (a view of `out` when
@@ -735,7 +762,10 @@ class Mpeg2Encoder:
         (set_gop_levels, option "gop_bytes_max"; the handle's own settings are back afterwards).  The cap's records wait for
         gop_report().
         gop_starts = a strictly ascending sequence of frame numbers, scene_cut = T > 0: where GOPs start in this call besides the cadence
-        (set_gop_starts, option "scene_cut"; the handle's own settings are back afterwards).  The records wait for scene_report()."""
+        (set_gop_starts, option "scene_cut"; the handle's own settings are back afterwards).  The records wait for scene_report().
+        recon = "i420", "yv12", "nv12" or "nv21": the reconstructed pictures too, as a uint8 tensor [N, frame_bytes(W, H, recon)] on the
+        frames' device, returned after the stream (and after the records with stats=True); planes_of_recon takes it apart
+        (set_recon_out for the duration of the call; the handle's own setting is back afterwards)."""
         import torch
         if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4:
             raise ValueError("encode_tensor: a uint8 tensor of 4 dimensions is required")
@@ -756,6 +786,8 @@ class Mpeg2Encoder:
             raise ValueError("encode_tensor: shape %r does not go with order %r" % (tuple(frames.shape), order))
         if header is not None and header not in HEADER_MODES:
             raise ValueError("encode_tensor: unknown header %r" % (header,))
+        if recon is not None and recon not in LAYOUTS_420:
+            raise ValueError("encode_tensor: unknown recon layout %r" % (recon,))
         xs, ys = (W + 15) // 16, (H + 15) // 16
         if header is None and (H % 16 or W % 16):
             raise ValueError("encode_tensor: %d x %d is not whole macroblocks; header=\"true\" or \"module\" pads it on the device" % (W, H))
@@ -766,6 +798,8 @@ class Mpeg2Encoder:
             out = torch.empty(N * 3 * 256 * xs * ys + (1 << 16), dtype=torch.uint8, device=frames.device)
         elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != frames.device or not out.is_contiguous() or out.dim() != 1:
             raise ValueError("encode_tensor: out must be a contiguous one-dimensional uint8 tensor on the frames' device")
+        rec = torch.empty((N, frame_bytes(W, H, recon)), dtype=torch.uint8, device=frames.device) if recon is not None else None
+        recon_before = getattr(self, "_recon_out", None)
         before = self.frame_size
         fit = bool(W % 16 or H % 16)
         if fit or before:
@@ -784,10 +818,14 @@ class Mpeg2Encoder:
                 self.set_gop_starts(gop_starts)
             if scene_cut:
                 self.set_option("scene_cut", scene_cut)
+            if rec is not None:
+                self.set_recon_out(rec.data_ptr(), rec.numel(), recon)
             nb = self.encode_resident_rgb(frames.data_ptr(), N, out.data_ptr(), out.numel(), xs, ys, pframes_count, layout, matrix,
                                           stream=torch.cuda.current_stream(frames.device).cuda_stream)
             records = self.picture_stats() if stats else None
         finally:
+            if rec is not None:
+                self.set_recon_out(*(recon_before or (None, 0)))
             if fit or before:
                 self.set_frame_size(*(before or (0, 0, 0)))
             if stats and not stats_before:
@@ -800,7 +838,8 @@ class Mpeg2Encoder:
                 self.set_gop_starts(starts_before)
             if scene_cut:
                 self.set_option("scene_cut", cut_before)
-        return (out[:nb], records) if stats else out[:nb]
+        res = (out[:nb],) + ((records,) if stats else ()) + ((rec,) if rec is not None else ())
+        return res if len(res) > 1 else res[0]
 
     def encode_resident_end(self):
         n = ctypes.c_size_t(0)

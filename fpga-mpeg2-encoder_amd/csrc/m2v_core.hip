@@ -134,7 +134,9 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
     // option "stats" measures every picture against its reconstruction: the unreferenced ones get a slot too (k_mb's need_rec is the
     // runtime test job.rec != nullptr).  The two alternating slots of a segment still do: frame k writes slot k & 1 and reads (k - 1) & 1,
     // and k_picstat reads frame k's slot on the segment's stream before frame k + 1 - let alone k + 2 - is launched.
-    const bool need_any_rec = e->pframes > 0 || e->stats_on;
+    // A buffer for the reconstruction (m2v_set_recon_out) asks for the same, and k_recon_out reads a slot where k_picstat does.
+    const bool every_rec = e->stats_on || e->seq_recon.p != nullptr;
+    const bool need_any_rec = e->pframes > 0 || every_rec;
     std::vector<int> rec_slot(nf, -1);
     if (need_any_rec) {
         if (e->rec_pool_bytes < e->rec_bytes) {       // geometry grew since the pool was allocated (new sequence)
@@ -171,7 +173,7 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
                     if (prev < 0) throw HipError{hipErrorInvalidValue, "P frame without a reference"};
                     jobs[k].ref = e->rec_pool[prev];
                 }
-                if (followed || e->stats_on) {
+                if (followed || every_rec) {
                     int sl;
                     if (e->keep_recon) sl = free_slots[fs++];
                     else {
@@ -405,6 +407,10 @@ void encode_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf,
                     launch_picstat(e, sk, e->d_lists.p + st.off_i + st.cut_i[k], st.cut_i[k + 1] - st.cut_i[k]);
                     launch_picstat(e, sk, e->d_lists.p + st.off_p + st.cut_p[k], st.cut_p[k + 1] - st.cut_p[k]);
                 }
+                if (e->seq_recon.p) {   // the same place, the same reason
+                    launch_recon_out(e, sk, e->d_lists.p + st.off_i + st.cut_i[k], st.cut_i[k + 1] - st.cut_i[k]);
+                    launch_recon_out(e, sk, e->d_lists.p + st.off_p + st.cut_p[k], st.cut_p[k + 1] - st.cut_p[k]);
+                }
             }
         }
         // every group scans its own slices right behind its last macroblock kernel (nothing in k_slice_scan looks beyond a
@@ -420,11 +426,15 @@ void encode_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf,
         e->timer_merge = true;          // (option profile: the steps' launches of one kind as one timed interval)
         for (size_t j = 0; j < e->plan_steps.size(); ++j) {
             run_step(e, s, j);
+            const m2v_enc::Step &st = e->plan_steps[j];
             if (e->stats_on) {
-                const m2v_enc::Step &st = e->plan_steps[j];
                 timer_break(e);         // (untimed work between two steps: the open interval ends here)
                 launch_picstat(e, s, e->d_lists.p + st.off_i, st.n_i);
                 launch_picstat(e, s, e->d_lists.p + st.off_p, st.n_p);
+            }
+            if (e->seq_recon.p) {       // (timed: kernel 6 of m2v_kernel_stats)
+                launch_recon_out(e, s, e->d_lists.p + st.off_i, st.n_i);
+                launch_recon_out(e, s, e->d_lists.p + st.off_p, st.n_p);
             }
         }
         e->timer_merge = false;
@@ -751,7 +761,7 @@ int m2v_set_option(m2v_enc *e, const char *name, long long value)
 
 int m2v_kernel_stats(const m2v_enc *e, int kernel, double *ms, double *units)
 {
-    if (!e || kernel < 0 || kernel > 5) return M2V_E_PARAM;
+    if (!e || kernel < 0 || kernel > 6) return M2V_E_PARAM;
     if (ms) *ms = e->stats[kernel].ms;
     if (units) *units = e->stats[kernel].units;
     return e->stats[kernel].launches;

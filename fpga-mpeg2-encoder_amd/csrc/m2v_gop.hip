@@ -115,6 +115,11 @@ void gop_cap_chunk(m2v_enc *e, hipStream_t s)
                 launch_picstat(e, s, e->d_lists.p + r.off_i, r.n_i);
                 launch_picstat(e, s, e->d_lists.p + r.off_p, r.n_p);
             }
+            // m2v_set_recon_out: the frames of a GOP that goes again are overwritten by those of its final level
+            if (e->seq_recon.p) {
+                launch_recon_out(e, s, e->d_lists.p + r.off_i, r.n_i);
+                launch_recon_out(e, s, e->d_lists.p + r.off_p, r.n_p);
+            }
         }
         timer_break(e);
         for (int sg : open) {

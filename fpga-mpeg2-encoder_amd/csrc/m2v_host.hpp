@@ -16,6 +16,8 @@
 //                     m2v_launch.hip) and the host's one wait per chunk - and m2v_scene_report
 //   m2v_stats.hip     option "stats": the per-picture records of m2v_picture_stats - their buffers, their way to the host and the queue
 //                     they wait in (the kernels that fill them, m2v_stats_kernels.hpp, need m2v_kernels.hpp and so belong to m2v_launch.hip)
+//   m2v_recon.hip     m2v_set_recon_out: the setting, what a resident sequence samples from it when it starts, the capacity check and
+//                     the refusals (the kernel, m2v_recon_kernels.hpp, is launched from m2v_launch.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -274,6 +276,10 @@ struct m2v_enc {
     DevBuf<m2v_picture_stat> d_pstat;
     std::deque<m2v_picture_stat> pstat_q;
 
+    // m2v_set_recon_out (m2v_recon.hip): the setting (p == nullptr: off), and what the resident sequence in progress sampled from it when
+    // it started - fb = bytes of one frame in the caller's buffer.  plan_chunk and the launch sites look at seq_recon only
+    struct ReconDst { uint8_t *p = nullptr; size_t cap = 0; int layout = 0; size_t fb = 0; } recon_out, seq_recon;
+
     // a level per GOP (m2v_gop.hip): the caller's schedule and the byte cap - the settings, and what the sequence in progress sampled
     // from them when it started (seq_levels empty: every GOP at Q; seq_cap 0: no cap)
     std::vector<uint8_t> gop_levels, seq_levels;
@@ -307,7 +313,7 @@ struct m2v_enc {
     std::vector<int> dbg_rec_slot;
 
     // profiling
-    KStat stats[6];
+    KStat stats[7];
     std::vector<TimedLaunch> timed;
     std::vector<hipEvent_t> ev_pool;      // timing events, reused from step to step
     size_t ev_used = 0;
@@ -405,10 +411,15 @@ inline bool size_refuses(m2v_enc *e, const char *fn, const char *why)
 }
 constexpr const char *kNoBeats = "the port has no partial macroblock, push whole frames";
 constexpr const char *kNoStrips = "strips take whole padded frames";
-// the strip entries that start something: true = refused (M2V_E_STATE) because a size is set or option "stats" is on
+// the strip entries that start something: true = refused (M2V_E_STATE) because a size is set, option "stats" is on or a buffer for the
+// reconstruction is set
 inline bool strip_refuses(m2v_enc *e, const char *fn)
 {
     if (size_refuses(e, fn, kNoStrips)) return true;
+    if (e->recon_out.p) {
+        e->set_err("%s: a buffer for the reconstruction is set (m2v_set_recon_out): a strip holds part of a picture, and nothing gathers the parts", fn);
+        return true;
+    }
     if (e->stats_on) {
         e->set_err("%s: option \"stats\" is on: a strip holds part of a picture, and nothing sums the records across ranks", fn);
         return true;
@@ -518,6 +529,15 @@ void stats_collect(m2v_enc *e, m2v_enc::HostStage &h);
 // a new sequence, or m2v_reset: nothing waits any more
 void stats_drop(m2v_enc *e);
 
+// ---- m2v_recon.hip: m2v_set_recon_out ----
+// a resident sequence of nframes frames of xs x ys macroblocks is about to start: true = refused (M2V_E_OVERFLOW) because the frames do
+// not fit the caller's buffer.  Reads the settings only: called before the start writes anything into the handle
+bool recon_overflows(m2v_enc *e, const char *fn, uint32_t xs, uint32_t ys, size_t nframes);
+// the start of a resident sequence samples the setting (where sample_frame_size is called)
+void sample_recon_out(m2v_enc *e, uint32_t xs, uint32_t ys);
+// the port entries that start a sequence: true = refused (M2V_E_STATE) because a buffer is set
+bool recon_refuses(m2v_enc *e, const char *fn);
+
 // ---- m2v_launch.hip: everything that touches device code ----
 // The constant tables live in each device's copy of the code object: uploaded once per device, whichever thread creates the first
 // handle there (config c4 creates 8 handles from 8 threads).
@@ -564,6 +584,9 @@ void launch_strip_assemble(m2v_enc *e, hipStream_t s, const Geom &g, uint32_t go
 // e->d_pstat, behind their k_mb launch on s (k_picstat); the rest of the records of the chunk's nf frames, behind its scans (k_picstat_mb)
 void launch_picstat(m2v_enc *e, hipStream_t s, const int *d_list, int count);
 void launch_picstat_mb(m2v_enc *e, hipStream_t s, size_t nf);
+// m2v_set_recon_out: the reconstruction of the `count` frames of a launch list (k_mb's own) as 4:2:0 frames into the buffer the sequence
+// sampled, behind their k_mb launch on s (k_recon_out)
+void launch_recon_out(m2v_enc *e, hipStream_t s, const int *d_list, int count);
 // option "gop_bytes_max": one block per GOP of the chunk's nf frames (whole GOPs of gop frames, the last one may be cut short) sums the
 // GOP's bytes, writes its record to e->d_gop and to h_recs (pinned) and raises FrameJob::q of a GOP over the cap (k_gop_judge)
 void launch_gop_judge(m2v_enc *e, hipStream_t s, size_t nf, uint32_t gop, unsigned long long cap, m2v_gop_stat *h_recs);

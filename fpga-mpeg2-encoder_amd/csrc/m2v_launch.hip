@@ -1,5 +1,6 @@
 // m2v_launch.hip — the one translation unit of libm2v_mi355x.so that contains device code: it includes m2v_kernels.hpp (and, for
-// option "stats", m2v_stats_kernels.hpp, for option "gop_bytes_max", m2v_gop_kernels.hpp behind it), uploads the
+// option "stats", m2v_stats_kernels.hpp, for option "gop_bytes_max", m2v_gop_kernels.hpp, for m2v_set_recon_out,
+// m2v_recon_kernels.hpp behind it), uploads the
 // constant tables into this code object's device globals and offers one plain C++ launch function per kernel to the host units
 // (m2v_host.hpp).  Kernel template arguments are chosen here from the handle's parameters (VECTOR_LEVEL, options).
 #include <mutex>
@@ -9,6 +10,7 @@
 #include "m2v_stats_kernels.hpp"
 #include "m2v_gop_kernels.hpp"
 #include "m2v_scene_kernels.hpp"
+#include "m2v_recon_kernels.hpp"
 
 namespace m2v {
 
@@ -422,6 +424,38 @@ void launch_picstat_mb(m2v_enc *e, hipStream_t s, size_t nf)
 {
     hipLaunchKernelGGL(k_picstat_mb, dim3((unsigned)nf), dim3(kStatThreads), 0, s, e->d_jobs.p, e->g, e->d_mbinfo.p, e->d_mblen.p, e->d_pstat.p);
     HIPCHK(hipGetLastError());
+}
+
+// m2v_set_recon_out: the `count` pictures of a launch list (k_mb's own), every plane, into their frames of the caller's buffer
+void launch_recon_out(m2v_enc *e, hipStream_t s, const int *d_list, int count)
+{
+    if (count <= 0) return;
+    const Geom &g = e->g;
+    const m2v_enc::ReconDst &d = e->seq_recon;
+    ReconOut m{};
+    m.w = e->fit.w ? e->fit.w : g.W;
+    m.h = e->fit.w ? e->fit.h : g.H;
+    m.cw = (m.w + 1) / 2;
+    m.ch = (m.h + 1) / 2;
+    auto magic = [](uint32_t d) { return (uint32_t)std::min<unsigned long long>(0x100000000ull / d, 0xFFFFFFFFull); };
+    m.grp_y = ((uint32_t)m.w + 127u) / 128u;
+    m.grp_c = ((uint32_t)m.cw + 63u) / 64u;
+    m.magic_y = magic(m.grp_y);
+    m.magic_c = magic(m.grp_c);
+    m.n_y = 64u * m.grp_y * (((uint32_t)m.h + 7u) / 8u);           // a wavefront per band of 8 rows x 128 luma columns
+    m.n_c = 64u * m.grp_c * (((uint32_t)m.ch + 7u) / 8u);          // ... x 64 chroma columns, both planes
+    const uint32_t units = m.n_y + m.n_c;
+    const dim3 grid((units + kReconThreads - 1) / kReconThreads, (unsigned)count), block(kReconThreads);
+    const FrameJob *const jl = e->d_joblist.p + (d_list - e->d_lists.p);
+    Timer t(e, s, 6, (double)count * g.ysz);
+    switch (d.layout) {
+    case M2V_420_I420: hipLaunchKernelGGL(k_recon_out<M2V_420_I420>, grid, block, 0, s, jl, g, m, d.p, d.fb); break;
+    case M2V_420_YV12: hipLaunchKernelGGL(k_recon_out<M2V_420_YV12>, grid, block, 0, s, jl, g, m, d.p, d.fb); break;
+    case M2V_420_NV12: hipLaunchKernelGGL(k_recon_out<M2V_420_NV12>, grid, block, 0, s, jl, g, m, d.p, d.fb); break;
+    default: hipLaunchKernelGGL(k_recon_out<M2V_420_NV21>, grid, block, 0, s, jl, g, m, d.p, d.fb); break;
+    }
+    HIPCHK(hipGetLastError());
+    t.stop();
 }
 
 // option "gop_bytes_max": every GOP of the chunk against the cap (behind k_slice_scan of all its frames)

@@ -39,6 +39,7 @@ static int resident_impl(m2v_enc *e, void *argp)
         return M2V_OK;
     }
     if (layout_refuses_cap(e, "m2v_encode_resident")) return M2V_E_STATE;
+    if (recon_overflows(e, "m2v_encode_resident", a->xs, a->ys, a->n)) return M2V_E_OVERFLOW;      // (nothing of the handle has changed)
     if (!sample_frame_size(e, "m2v_encode_resident", a->xs, a->ys)) return M2V_E_PARAM;
     if (e->gop_bytes_max && (size_t)(a->pf & 0xFFu) + 1 > e->batch_frames) {
         e->set_err("m2v_encode_resident: option \"gop_bytes_max\" needs whole GOPs in a chunk: pframes_count + 1 = %u is more than batch_frames = %zu",
@@ -48,6 +49,7 @@ static int resident_impl(m2v_enc *e, void *argp)
     hipStream_t s = a->s ? a->s : e->stream;
     e->g = make_geom(e, a->xs, a->ys);
     e->pframes = a->pf & 0xFFu;
+    sample_recon_out(e, a->xs, a->ys);
     sample_gop_levels(e, true);
     sample_gop_starts(e, true);
     e->frames_total = 0;

@@ -2,7 +2,7 @@
 //
 //   m2v_tb [-XL n] [-YL n] [-VL n] [-Q n] [-p pframes] [-d device] [-bubbles] [-conformant] [-ps] [-ts]
 //          [-i420 | -yv12 | -nv12 | -nv21 | -rgb24 | -bgr24 | -rgbx | -bgrx | -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f]
-//          [-pad | -truesize] [-stats] [-qgop q0,q1,...] [-istart n0,n1,...] [-scenecut T]
+//          [-pad | -truesize] [-stats] [-qgop q0,q1,...] [-istart n0,n1,...] [-scenecut T] [-recon out.yuv [-reconfmt i420|yv12|nv12|nv21]]
 //          in.yuv W H out.m2v  [in2.yuv W2 H2 out2.m2v ...]
 //
 // -pad: W, H are any size from 49 up; the files hold frames of that size in the chosen format, which are padded to whole macroblocks on
@@ -24,6 +24,9 @@
 // -scenecut T: option "scene_cut" = T, 1..65280: a GOP also starts where the device finds a scene cut; NOT the module's behaviour.  The
 // detector belongs to the resident entries, so with this flag - and only with it - every file's frames are staged in device memory
 // whole and encoded by one m2v_encode_resident* call instead of going through the port.  Does not go with -bubbles.
+// -recon out.yuv: the reconstructed pictures of every video, frame behind frame, as 4:2:0 frames of W x H (the file's size under -pad too)
+// in -reconfmt (default i420): m2v_set_recon_out, read back after each video - a file for ffplay -f rawvideo or tools/m2v_stats.py --yuv.
+// The buffer is the resident entries', so it needs the resident mode that -scenecut selects (-scenecut 65280 never finds a cut).
 // -conformant switches the encoder's option "conformant" on (ISO reconstruction loop; NOT byte-identical to the RTL).
 // -ps / -ts additionally write out.m2v.mpg / out.m2v.ts: the same elementary stream in an MPEG-2 program / transport
 // stream (include/m2v_container.h), so the result plays in an ordinary player.
@@ -49,7 +52,8 @@
 int main(int argc, char **argv)
 {
     int XL = 7, YL = 6, VL = 3, Q = 2, pf = 23, dev = 0, bubbles = 0, conformant = 0, want_ps = 0, want_ts = 0, layout420 = -1, layouts = 0, rgb = -1, matrix = M2V_RGB_BT601,
-        bad_matrix = 0, pad = 0, truesize = 0, stats = 0;
+        bad_matrix = 0, pad = 0, truesize = 0, stats = 0, reconfmt = M2V_420_I420;
+    const char *recon = nullptr;
     long long scenecut = 0;
     std::vector<uint8_t> qgop;
     std::vector<uint32_t> istart;
@@ -71,7 +75,7 @@ int main(int argc, char **argv)
         int k = 0;
         for (; k < 7 && strcmp(argv[i], rgb_opts[k]); ++k) {}
         if (k < 7) { rgb = k; ++layouts; continue; }
-        if (i + 1 >= argc) break;
+        if (i + 1 >= argc) break;                                   // (an option that takes a value is never the last argument)
         if (!strcmp(argv[i], "-qgop")) {
             for (const char *c = argv[i + 1]; *c; ++c)
                 if (*c >= '0' && *c <= '9') qgop.push_back((uint8_t)(*c - '0'));
@@ -90,6 +94,14 @@ int main(int argc, char **argv)
             continue;
         }
         if (!strcmp(argv[i], "-scenecut")) { scenecut = atoll(argv[i + 1]); ++i; continue; }
+        if (!strcmp(argv[i], "-recon")) { recon = argv[i + 1]; ++i; continue; }
+        if (!strcmp(argv[i], "-reconfmt")) {
+            static const char *const names[] = {"i420", "yv12", "nv12", "nv21"};
+            for (k = 0; k < 4 && strcmp(argv[i + 1], names[k]); ++k) {}
+            reconfmt = k;                                           // (4 = not a layout: m2v_set_recon_out says so)
+            ++i;
+            continue;
+        }
         if (!strcmp(argv[i], "-matrix")) {
             static const char *const names[] = {"bt601", "bt709", "bt601f", "bt709f"};
             for (k = 0; k < 4 && strcmp(argv[i + 1], names[k]); ++k) {}
@@ -106,10 +118,18 @@ int main(int argc, char **argv)
     }
     if ((argc - i) < 4 || (argc - i) % 4 || layouts > 1 || bad_matrix || ((layouts || pad || scenecut) && bubbles)) {          // (there are no 4:2:0 or RGB beats)
         fprintf(stderr, "usage: %s [-XL n] [-YL n] [-VL n] [-Q n] [-p pframes] [-d dev] [-i420 | -yv12 | -nv12 | -nv21 | -rgb24 | -bgr24 | -rgbx | -bgrx |"
-                        " -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f] [-pad | -truesize] [-stats] [-qgop q0,q1,...] [-istart n0,n1,...] [-scenecut T] in.yuv W H out.m2v ...\n"
+                        " -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f] [-pad | -truesize] [-stats] [-qgop q0,q1,...] [-istart n0,n1,...] [-scenecut T] [-recon out.yuv [-reconfmt i420|yv12|nv12|nv21]]"
+                        " in.yuv W H out.m2v ...\n"
                         "  -scenecut T stages every file's frames in device memory and encodes them with one resident call (the detector needs it)\n", argv[0]);
         return 2;
     }
+    if (recon && !scenecut) {
+        fprintf(stderr, "*** -recon needs the resident mode: the reconstruction is written to device memory by the resident entries, and only -scenecut T "
+                        "stages the frames there (-scenecut 65280 never finds a cut)\n");
+        return 2;
+    }
+    FILE *fr = nullptr;
+    if (recon && !(fr = fopen(recon, "wb"))) { printf("*** couldn't open %s\n", recon); return 1; }
     int err = 0;
     m2v_enc *e = m2v_create(XL, YL, VL, Q, dev, &err);
     if (!e) { fprintf(stderr, "*** m2v_create failed (%d): an MI355X is required, there is no CPU fallback\n", err); return 1; }
@@ -169,9 +189,16 @@ int main(int argc, char **argv)
             std::vector<uint8_t> all;
             while (fread(frame.data(), 1, fb, fi) == fb) { all.insert(all.end(), frame.begin(), frame.end()); ++frames; }
             const size_t cap = frames * ((size_t)xs16 * ys16 * 1216 + (size_t)ys16 * 8 + 64) + 256;
-            void *d_in = nullptr, *d_out = nullptr;
+            void *d_in = nullptr, *d_out = nullptr, *d_rec = nullptr;
             size_t nb = 0;
+            // a reconstructed frame is of the file's size: the coded size, or under -pad the size set
+            const size_t rb = frames * ((size_t)xsize * ysize + 2 * (size_t)((xsize + 1) / 2) * (size_t)((ysize + 1) / 2));
             if (frames) {
+                if (fr && (hipSetDevice(dev) != hipSuccess || hipMalloc(&d_rec, rb) != hipSuccess)) {
+                    fprintf(stderr, "*** %zu bytes of device memory for the reconstruction: allocation failed\n", rb);
+                    return 1;
+                }
+                if (fr && m2v_set_recon_out(e, d_rec, rb, reconfmt) < 0) { fprintf(stderr, "*** m2v_set_recon_out: %s\n", m2v_last_error(e)); return 1; }
                 if (hipSetDevice(dev) != hipSuccess || hipMalloc(&d_in, all.size()) != hipSuccess || hipMalloc(&d_out, cap) != hipSuccess ||
                     hipMemcpy(d_in, all.data(), all.size(), hipMemcpyHostToDevice) != hipSuccess) {
                     fprintf(stderr, "*** staging %zu frames in device memory failed\n", frames);
@@ -185,6 +212,14 @@ int main(int argc, char **argv)
                 if (hipMemcpy(es.data(), d_out, nb, hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "*** read-back failed\n"); return 1; }
                 fwrite(es.data(), 1, nb, fo);
                 bytes = nb;
+                if (fr) {
+                    std::vector<uint8_t> rec(rb);
+                    if (hipMemcpy(rec.data(), d_rec, rb, hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "*** read-back failed\n"); return 1; }
+                    fwrite(rec.data(), 1, rb, fr);
+                    m2v_set_recon_out(e, nullptr, 0, 0);
+                    (void)hipFree(d_rec);
+                    printf("  %s: %zu frames, %zu bytes\n", recon, frames, rb);
+                }
                 (void)hipFree(d_in);
                 (void)hipFree(d_out);
             }
@@ -267,6 +302,7 @@ int main(int argc, char **argv)
         printf("end of video %d: %zu frames -> %zu bytes, %.3f s, %.1f MPixels/s incl. file I/O and PCIe\n", num_video, frames,
                bytes, s, (double)frames * xsize * ysize / s * 1e-6);
     }
+    if (fr) fclose(fr);
     m2v_destroy(e);
     return 0;
 }

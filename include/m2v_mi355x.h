@@ -657,10 +657,41 @@ typedef struct m2v_picture_stat {
  * "stats" = 0 the answer is 0.  Waits for nothing. */
 long long m2v_picture_stats(m2v_enc *e, m2v_picture_stat *dst, size_t cap);
 
+/*
+ * Reconstructed pictures out: every coded picture of a resident sequence as a plain 4:2:0 frame in a device buffer of the caller's.
+ *
+ * m2v_set_recon_out(e, d_dst, cap, layout): frame n of every sequence started afterwards by a resident entry (m2v_encode_resident,
+ * m2v_encode_resident420, m2v_encode_resident_rgb, each also as _begin / _end) is written to d_dst + n * frame_bytes in `layout`
+ * (M2V_420_I420 / YV12 / NV12 / NV21), n being the frame's number from the sequence's start.
+ * What is written: the picture the module's reference memory would hold for that frame - what m2v_picture_stats measures against -
+ * for every picture, the ones no P picture refers to included (the last of every GOP; every one with pframes_count = 0).  With option
+ * "conformant" = 1 it is byte for byte the picture a standard decoder shows.  WITHOUT it a standard decoder drifts away from it inside a
+ * GOP (see "conformant"): the frames then show the MODULE's loop, not what a player displays.
+ * Frame size: without a frame size set W x H of luma and W/2 x H/2 of each chroma plane, frame_bytes = W * H * 3 / 2.  With
+ * m2v_set_frame_size(width, height, ...) the top-left width x height of luma and cw x ch = (width + 1) / 2 x (height + 1) / 2 of each
+ * chroma plane, frame_bytes = width * height + 2 * cw * ch: the cropped picture a player of an M2V_HEADER_TRUE stream displays, and the
+ * region "stats" measures.  Either way the frames are packed exactly as frames of that size and layout are on the way in: rows of
+ * width (cw, or interleaved 2 * cw) bytes without padding, frame behind frame.  d_dst needs no alignment.  No byte outside
+ * [n * frame_bytes, (n + 1) * frame_bytes) of a coded frame n is touched.
+ * When the data is complete: the writes are ordered on the call's stream - complete when the blocking call or _end has returned, and
+ * for work queued on that stream afterwards.  The buffer stays the caller's and must stay valid until then.
+ * The setting is sampled when a sequence starts (where a frame size and a level schedule are), stays until changed and survives
+ * m2v_reset; d_dst == NULL clears it.  Only while idle, M2V_E_STATE otherwise; a layout outside 0..3 is M2V_E_PARAM.  A sequence start
+ * whose nframes * frame_bytes exceeds cap answers M2V_E_OVERFLOW before anything is launched.
+ * The stream is byte for byte the stream without the setting, and with no buffer set the launches, buffers and plan are exactly
+ * those of a handle that never heard of it.  With one set every picture keeps a reconstruction slot (one more per GOP, as with
+ * "stats") and one kernel per GOP step moves 3 bytes per pixel.  It goes with "stats", m2v_set_gop_levels, "gop_bytes_max" (a GOP that
+ * is coded again leaves the frames of its final level), m2v_set_gop_starts, "scene_cut", any "batch_frames" and "split_streams",
+ * "conformant", every input format and a set frame size.
+ * Refusals: while a buffer is set every m2v_push_* call that starts a sequence answers M2V_E_STATE (a read-back over the link is another
+ * feature), and so does every m2v_strip_* entry that starts something - the rule "stats" follows.
+ */
+int m2v_set_recon_out(m2v_enc *e, void *d_dst, size_t cap, int layout);   /* layout: M2V_420_I420 | YV12 | NV12 | NV21 */
+
 /* Per-kernel statistics of the last m2v_encode_resident call with "profile" = 1.
  * kernel: 0 = macroblock kernel on P frames, 1 = macroblock kernel on I frames,
  * 2 = strip mode's final assembly (k_strip_layout + k_strip_assemble), 3 = slice assembly (k_assemble), 4 = scans,
- * 5 = the cut detector of option "scene_cut" (k_mbsum + k_scene_judge).
+ * 5 = the cut detector of option "scene_cut" (k_mbsum + k_scene_judge), 6 = the reconstruction out of m2v_set_recon_out (k_recon_out).
  * Returns launches; *ms = summed duration, *units = luma pixels processed. */
 int m2v_kernel_stats(const m2v_enc *e, int kernel, double *ms, double *units);
 
