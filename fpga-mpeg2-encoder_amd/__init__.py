@@ -43,6 +43,7 @@ EXPORTS = [
     "m2v_set_gop_levels", "m2v_gop_report",
     "m2v_set_gop_starts", "m2v_gop_layout", "m2v_scene_report",
     "m2v_set_recon_out",
+    "m2v_stream_desc_module", "m2v_set_stream_desc", "m2v_frame_rate_code", "m2v_time_code",
 ]
 
 # the 4:2:0 entry points (kept apart: tests/test_abi.py matches EXPORTS against names of letters and underscores only)
@@ -95,6 +96,74 @@ class SceneStat(ctypes.Structure):
 # the same record as a numpy structured dtype (Mpeg2Encoder.scene_report)
 SCENE_STAT_DTYPE = np.dtype([("frame", "<u4"), ("flags", "<u4"), ("diff", "<u8")])
 GOP_FIRST, GOP_CADENCE, GOP_LIST, GOP_CUT = 1, 2, 4, 8           # M2V_GOP_*
+
+
+class StreamDesc(ctypes.Structure):
+    """m2v_stream_desc (include/m2v_mi355x.h): what the stream says about itself, 48 bytes"""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("frame_rate_code", "aspect_ratio_information", "bit_rate_400", "vbv_buffer_size_16k",
+                                               "video_format", "colour_primaries", "transfer_characteristics", "matrix_coefficients",
+                                               "display_width", "display_height", "repeat_headers", "reserved")]
+
+    def __repr__(self):
+        return "StreamDesc(%s)" % ", ".join("%s=%d" % (k, getattr(self, k)) for k, _ in self._fields_)
+
+
+FRAME_RATES = {1: (24000, 1001), 2: (24, 1), 3: (25, 1), 4: (30000, 1001), 5: (30, 1), 6: (50, 1), 7: (60000, 1001), 8: (60, 1)}   # table 6-4
+ASPECTS = {"1:1": 1, "4:3": 2, "16:9": 3, "2.21:1": 4}                                                                             # table 6-3
+COLOURS = {"bt709": (1, 1, 1), "bt601": (5, 5, 5)}              # colour_primaries, transfer_characteristics, matrix_coefficients
+
+
+def frame_rate_code(num, den=1):
+    """m2v_frame_rate_code: 1..8 for a rational equal to an entry of table 6-4, ValueError otherwise.  Plain arithmetic, no GPU."""
+    r = lib().m2v_frame_rate_code(int(num), int(den)) if 0 <= int(num) <= 0xFFFFFFFF and 0 <= int(den) <= 0xFFFFFFFF else -1
+    if r < 0:
+        raise ValueError("frame_rate_code: %r/%r is not a frame rate of ISO/IEC 13818-2 table 6-4" % (num, den))
+    return r
+
+
+def time_code(n, code=2):
+    """m2v_time_code: the four bytes behind 00 00 01 B8 for a GOP that starts at frame n, at frame_rate_code `code`.  No GPU."""
+    out = (ctypes.c_uint8 * 4)()
+    if lib().m2v_time_code(int(code), int(n) & 0xFFFFFFFF, out) < 0:
+        raise ValueError("time_code: frame_rate_code %r is not 1..8" % (code,))
+    return bytes(out)
+
+
+def stream_desc(fps=None, aspect=None, bit_rate=None, vbv_bits=None, video_format=None, colour=None, display=None, repeat_headers=False):
+    """A StreamDesc for Mpeg2Encoder.set_stream_desc: the module's values (m2v_stream_desc_module) with the given ones replaced.
+    fps: a (num, den) pair equal to an entry of table 6-4, or a number within 1e-3 of one;  aspect: "1:1", "4:3", "16:9" or "2.21:1";
+    bit_rate: bit/s, rounded up to units of 400;  vbv_bits: bits, rounded up to units of 16384;  video_format: 0..5;
+    colour: "bt709" (1 / 1 / 1), "bt601" (5 / 5 / 5) or a triple of codes, taken as is;  display: (width, height);
+    repeat_headers: the sequence headers again in front of every GOP after the first.  ValueError for what names no value; the ranges
+    are m2v_set_stream_desc's to check."""
+    d = StreamDesc()
+    lib().m2v_stream_desc_module(ctypes.byref(d))
+    if fps is not None:
+        if isinstance(fps, (tuple, list)):
+            d.frame_rate_code = frame_rate_code(*fps)
+        else:
+            near = [c for c, (n, m) in FRAME_RATES.items() if abs(float(fps) - n / m) <= 1e-3]
+            if not near:
+                raise ValueError("stream_desc: fps %r is not within 1e-3 of a frame rate of table 6-4" % (fps,))
+            d.frame_rate_code = near[0]
+    if aspect is not None:
+        if aspect not in ASPECTS:
+            raise ValueError("stream_desc: unknown aspect %r" % (aspect,))
+        d.aspect_ratio_information = ASPECTS[aspect]
+    if bit_rate is not None:
+        d.bit_rate_400 = -(-int(bit_rate) // 400)
+    if vbv_bits is not None:
+        d.vbv_buffer_size_16k = -(-int(vbv_bits) // 16384)
+    if video_format is not None:
+        d.video_format = int(video_format)
+    if colour is not None:
+        if isinstance(colour, str) and colour not in COLOURS:
+            raise ValueError("stream_desc: unknown colour %r" % (colour,))
+        d.colour_primaries, d.transfer_characteristics, d.matrix_coefficients = COLOURS[colour] if isinstance(colour, str) else colour
+    if display is not None:
+        d.display_width, d.display_height = display
+    d.repeat_headers = 1 if repeat_headers else 0
+    return d
 
 
 def gop_layout(pframes_count, starts, nframes):
@@ -245,6 +314,11 @@ def lib(debug=False):
             L.m2v_scene_report.restype = ctypes.c_longlong
             L.m2v_scene_report.argtypes = [vp, vp, sz]
             L.m2v_set_recon_out.argtypes = [vp, vp, sz, ci]
+            L.m2v_stream_desc_module.restype = None
+            L.m2v_stream_desc_module.argtypes = [ctypes.POINTER(StreamDesc)]
+            L.m2v_set_stream_desc.argtypes = [vp, ctypes.POINTER(StreamDesc)]
+            L.m2v_frame_rate_code.argtypes = [u32, u32]
+            L.m2v_time_code.argtypes = [u32, u32, ctypes.POINTER(ctypes.c_uint8)]
         except AttributeError:
             # an OLDER build handed in through M2V_LIB for a same-box A/B (tools/ab.sh) may lack the newer entry points; the library of
             # this tree must have every one of them (tests/test_abi.py)
@@ -515,6 +589,15 @@ class Mpeg2Encoder:
         self._chk(self._L.m2v_set_recon_out(self._h, ptr or None, int(cap), _layout420(layout)), "m2v_set_recon_out")
         self._recon_out = (int(ptr), int(cap), layout) if ptr else None
 
+    def set_stream_desc(self, desc):
+        """m2v_set_stream_desc: what every sequence started from now on says about itself in its sequence headers and time codes - a
+        StreamDesc (stream_desc builds one); None sets the module's values again.  Idle handles only; M2VError for a value out of
+        range, and the previous setting stays.  Not the module's behaviour."""
+        if desc is not None and not isinstance(desc, StreamDesc):
+            raise M2VError("m2v_set_stream_desc failed (-1): a StreamDesc or None is required")
+        self._chk(self._L.m2v_set_stream_desc(self._h, ctypes.byref(desc) if desc is not None else None), "m2v_set_stream_desc")
+        self._desc = StreamDesc.from_buffer_copy(desc) if desc is not None else None
+
     def set_frame_size(self, w, h, header="module"):
         """m2v_set_frame_size: from now on every whole-frame entry takes w x h frames in its own format and pads them on the device;
         header "module" (the padded size in the stream's headers) or "true" (w x h).  (0, 0) switches it off.  Idle handles only."""
@@ -746,7 +829,7 @@ class Mpeg2Encoder:
         return out[:n]
 
     def encode_tensor(self, frames, pframes_count, order="rgb", matrix="bt601", out=None, header=None, stats=False, gop_levels=None,
-                      gop_bytes_max=0, gop_starts=None, scene_cut=0, recon=None):
+                      gop_bytes_max=0, gop_starts=None, scene_cut=0, recon=None, desc=None):
         """One whole sequence from a torch image tensor on the handle's device, in one call: contiguous uint8 [N, H, W, 3] (order
         "rgb" / "bgr"), [N, H, W, 4] ("rgbx" / "bgrx" / "xrgb" / "xbgr") or [N, 3, H, W] ("rgb": planar).  Runs
         m2v_encode_resident_rgb on torch's current stream and returns the stream bytes as a uint8 device tensor (a view of `out` when
@@ -765,7 +848,9 @@ class Mpeg2Encoder:
         (set_gop_starts, option "scene_cut"; the handle's own settings are back afterwards).  The records wait for scene_report().
         recon = "i420", "yv12", "nv12" or "nv21": the reconstructed pictures too, as a uint8 tensor [N, frame_bytes(W, H, recon)] on the
         frames' device, returned after the stream (and after the records with stats=True); planes_of_recon takes it apart
-        (set_recon_out for the duration of the call; the handle's own setting is back afterwards)."""
+        (set_recon_out for the duration of the call; the handle's own setting is back afterwards).
+        desc = a StreamDesc (stream_desc): what the stream says about itself, for this call (set_stream_desc; the handle's own setting
+        is back afterwards).  The matrix does not set it: matrix="bt709" goes with desc=stream_desc(colour="bt709")."""
         import torch
         if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4:
             raise ValueError("encode_tensor: a uint8 tensor of 4 dimensions is required")
@@ -795,7 +880,7 @@ class Mpeg2Encoder:
             raise ValueError("encode_tensor: %d x %d does not pad to a size of this handle (64 ... %d x 64 ... %d)"
                              % (W, H, 16 << self.params[0], 16 << self.params[1]))
         if out is None:
-            out = torch.empty(N * 3 * 256 * xs * ys + (1 << 16), dtype=torch.uint8, device=frames.device)
+            out = torch.empty(N * (3 * 256 * xs * ys + 34) + (1 << 16), dtype=torch.uint8, device=frames.device)     # (34: repeat_headers)
         elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != frames.device or not out.is_contiguous() or out.dim() != 1:
             raise ValueError("encode_tensor: out must be a contiguous one-dimensional uint8 tensor on the frames' device")
         rec = torch.empty((N, frame_bytes(W, H, recon)), dtype=torch.uint8, device=frames.device) if recon is not None else None
@@ -809,7 +894,10 @@ class Mpeg2Encoder:
             self.set_option("stats", 1)
         levels_before, cap_before = getattr(self, "_gop_levels", None), getattr(self, "_gop_cap", 0)
         starts_before, cut_before = getattr(self, "_gop_starts", None), getattr(self, "_scene_cut", 0)
+        desc_before = getattr(self, "_desc", None)
         try:
+            if desc is not None:
+                self.set_stream_desc(desc)
             if gop_levels is not None:
                 self.set_gop_levels(gop_levels)
             if gop_bytes_max:
@@ -838,6 +926,8 @@ class Mpeg2Encoder:
                 self.set_gop_starts(starts_before)
             if scene_cut:
                 self.set_option("scene_cut", cut_before)
+            if desc is not None:
+                self.set_stream_desc(desc_before)
         res = (out[:nb],) + ((records,) if stats else ()) + ((rec,) if rec is not None else ())
         return res if len(res) > 1 else res[0]
 

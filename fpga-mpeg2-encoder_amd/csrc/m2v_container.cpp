@@ -38,15 +38,22 @@ int scan(const uint8_t *es, size_t n, Scan &s)
     in.frame_rate_code = es[7] & 15;
     in.bit_rate_400 = ((uint32_t)es[8] << 10) | ((uint32_t)es[9] << 2) | (es[10] >> 6);
     size_t p = 0, pending_start = (size_t)-1;                      // pending_start: GOP header waiting for its picture
-    bool gop_pending = false;
+    bool gop_pending = false, seq_pending = false;                 // seq_pending: a repeated sequence header waiting for its GOP header
     size_t end = n;
     while ((p = next_start_code(es, n, p)) < n) {
         const uint8_t code = es[p + 3];
-        if (code == 0xB8) {                                        // group_of_pictures_header
+        if (code == 0xB3 && p > 0) {
+            // a sequence header repeated in front of a GOP (ISO/IEC 13818-2 6.1.1.6) opens that GOP's first access unit: the picture
+            // before it ends here, and the GOP's I picture starts here
+            if (!s.pics.empty() && s.pics.back().bytes == 0) s.pics.back().bytes = p - s.pics.back().offset;
+            seq_pending = true;
+            pending_start = p;
+        } else if (code == 0xB8) {                                 // group_of_pictures_header
             if (!s.pics.empty() && s.pics.back().bytes == 0) s.pics.back().bytes = p - s.pics.back().offset;
             in.gops++;
             gop_pending = true;
-            pending_start = p;
+            if (!seq_pending) pending_start = p;
+            seq_pending = false;
         } else if (code == 0x00) {                                 // picture_header
             if (p + 6 > n) return M2VC_E_SYNTAX;
             if (!s.pics.empty() && s.pics.back().bytes == 0) s.pics.back().bytes = p - s.pics.back().offset;

@@ -14,7 +14,8 @@ constexpr int kJudgeThreads = 256;
 
 // One block per GOP of the chunk: GOP sg = frames [sg * gop, min((sg + 1) * gop, nf)) - with the cap on a chunk holds whole GOPs, only
 // the sequence's last one may be cut short.  Its size is what k_frame_scan will add up for these frames: their headers
-// (frame_header_bytes; the sequence header is not a GOP's) and the bytes of their slices (k_slice_scan).  A GOP whose record says it is
+// (frame_header_bytes; the sequence header is not a GOP's, and neither is a copy of it that repeat_headers of m2v_set_stream_desc puts in
+// front of the GOP) and the bytes of their slices (k_slice_scan).  A GOP whose record says it is
 // settled - it fitted, or it was coded at level 4 - is left alone; the others are measured, and one that is over the cap below level 4
 // gets FrameJob::q of its frames raised by one: the host (gop_cap_chunk) reads the record in pinned memory and codes it again.
 // Integers only, one block per GOP: the verdict depends on nothing but the GOP's own bytes.

@@ -16,6 +16,9 @@
 //                     m2v_launch.hip) and the host's one wait per chunk - and m2v_scene_report
 //   m2v_stats.hip     option "stats": the per-picture records of m2v_picture_stats - their buffers, their way to the host and the queue
 //                     they wait in (the kernels that fill them, m2v_stats_kernels.hpp, need m2v_kernels.hpp and so belong to m2v_launch.hip)
+//   m2v_desc.hip      m2v_set_stream_desc: what the stream says about itself - the setting, its validation, what a sequence samples from it
+//                     when it starts (the SeqDesc the header writers of m2v_kernels.hpp take by value) - and the plain arithmetic of
+//                     m2v_frame_rate_code and m2v_time_code
 //   m2v_recon.hip     m2v_set_recon_out: the setting, what a resident sequence samples from it when it starts, the capacity check and
 //                     the refusals (the kernel, m2v_recon_kernels.hpp, is launched from m2v_launch.hip)
 #pragma once
@@ -308,6 +311,12 @@ struct m2v_enc {
     size_t h_scene_cap = 0;
     hipEvent_t ev_scene = nullptr;        // behind the k_scene_judge whose flags the host needs
 
+    // what the stream says about itself (m2v_desc.hip): the setting, whether it differs from the module's, and what the sequence in
+    // progress sampled from it when it started - launch_frame_scan and launch_assemble look at seq_desc only
+    m2v_stream_desc desc{};
+    bool desc_set = false;
+    SeqDesc seq_desc = seq_desc_module();
+
     // debug bookkeeping of the last resident encode
     size_t dbg_frames = 0;
     std::vector<int> dbg_rec_slot;
@@ -432,6 +441,11 @@ inline bool strip_refuses(m2v_enc *e, const char *fn)
         e->set_err("%s: GOP starts are set (m2v_set_gop_starts or option \"scene_cut\"): the strips of a frame run at the fixed cadence", fn);
         return true;
     }
+    if (e->desc_set) {
+        e->set_err("%s: a stream description is set (m2v_set_stream_desc): the strip assembly writes the module's headers", fn);
+        return true;
+    }
+    e->seq_desc = seq_desc_module();
     e->seq_levels.clear();      // (what an earlier whole-frame sequence sampled)
     e->seq_cap = 0;
     e->seq_starts.clear();
@@ -461,6 +475,10 @@ inline bool cap_refuses(m2v_enc *e, const char *fn)
     e->set_err("%s: option \"gop_bytes_max\" is set: the cap needs whole GOPs in a chunk, which only the resident entries give", fn);
     return true;
 }
+
+// ---- m2v_desc.hip ----
+// the start of a sequence samples the description (where sample_gop_levels is called)
+void sample_stream_desc(m2v_enc *e);
 
 // ---- m2v_scene.hip ----
 // The rule of include/m2v_mi355x.h, frame by frame: s = the I picture of the GOP in progress, k = GOP starts so far, list / at = the

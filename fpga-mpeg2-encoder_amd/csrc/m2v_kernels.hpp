@@ -1891,21 +1891,14 @@ struct ByteWriter {
 
 
 // [group_of_pictures_header] picture_header picture_coding_extension of one frame (RTL:2645-2698)
-__device__ inline void write_frame_headers(uint8_t *p, const FrameJob &job)
+// F: frames per second of the time code (time_code_rate of the stream's frame_rate_code; the module's 24)
+__device__ inline void write_frame_headers(uint8_t *p, const FrameJob &job, uint32_t F)
 {
     ByteWriter w{p, 0u, 0};
     if (job.i_frame == 0) {
-        // group_of_pictures_header, closed_gop = 1; time code of frame n at 24 fps (RTL:2645-2656, 2685-2698)
-        const uint32_t n = job.n;
-        const uint32_t hh = n / 86400u;
+        // group_of_pictures_header, closed_gop = 1; time code of frame n (RTL:2645-2656, 2685-2698; m2v_types.hpp, time_code)
         w.put(0x000001B8u, 32);
-        w.put(hh > 63u ? 63u : hh, 6);
-        w.put((n / 1440u) % 60u, 6);
-        w.put(1u, 1);
-        w.put((n / 24u) % 60u, 6);
-        w.put(n % 24u, 6);
-        w.put(2u, 2);
-        w.align();
+        w.put(time_code(F, job.n), 32);
     }
     // picture_header + picture_coding_extension (RTL:2670-2682)
     w.put(0x00000100u, 32);
@@ -1925,18 +1918,21 @@ __device__ inline void write_frame_headers(uint8_t *p, const FrameJob &job)
 
 // sequence_header + sequence_extension + sequence_display_extension (RTL:2598-2617)
 // width, height: the sizes to print - the coded W x H, or the source's where the caller asked for it (m2v_set_frame_size)
-__device__ inline void write_sequence_headers(uint8_t *p, int width, int height)
+// d: what else the stream says about itself (m2v_set_stream_desc); seq_desc_module() gives the module's 34 bytes
+__device__ inline void write_sequence_headers(uint8_t *p, int width, int height, const SeqDesc &d)
 {
     ByteWriter w{p, 0u, 0};
+    const uint32_t dw = d.display ? d.display & 0x3FFFu : (uint32_t)width, dh = d.display ? d.display >> 16 : (uint32_t)height;
     w.put(0x000001B3u, 32);
     w.put((uint32_t)width, 12); w.put((uint32_t)height, 12);
-    w.put(1u, 4); w.put(2u, 4); w.put(10000u, 18); w.put(1u, 1); w.put(0u, 10); w.put(0u, 3);
+    w.put(d.aspect(), 4); w.put(d.rate_code(), 4); w.put(d.bit_rate & 0x3FFFFu, 18); w.put(1u, 1); w.put(d.vbv() & 0x3FFu, 10); w.put(0u, 3);
     w.put(0x000001B5u, 32);
-    w.put(1u, 4); w.put(0x44u, 8); w.put(0u, 1); w.put(1u, 2); w.put(0u, 4); w.put(0u, 12); w.put(1u, 1);
-    w.put(0u, 8); w.put(0u, 8);
+    w.put(1u, 4); w.put(0x44u, 8); w.put(0u, 1); w.put(1u, 2); w.put(0u, 4); w.put(d.bit_rate >> 18, 12); w.put(1u, 1);
+    w.put(d.vbv() >> 10, 8); w.put(0u, 8);
     w.put(0x000001B5u, 32);
-    w.put(2u, 4); w.put(1u, 3); w.put(1u, 1); w.put(5u, 8); w.put(5u, 8); w.put(5u, 8);
-    w.put((uint32_t)width, 14); w.put(1u, 1); w.put((uint32_t)height, 14);
+    w.put(2u, 4); w.put(d.video_format(), 3); w.put(1u, 1);
+    w.put(d.colour & 0xFFu, 8); w.put((d.colour >> 8) & 0xFFu, 8); w.put((d.colour >> 16) & 0xFFu, 8);
+    w.put(dw, 14); w.put(1u, 1); w.put(dh, 14);
     w.align();
 }
 
@@ -1984,7 +1980,7 @@ __global__ __launch_bounds__(kAsmThreads, 8) void k_assemble(const FrameJob *__r
                                                  const unsigned long long *__restrict__ slice_off,
                                                  uint32_t *__restrict__ out32, const StreamCtl *__restrict__ ctl,
                                                  int first, int last, const unsigned long long *__restrict__ frame_off,
-                                                 const uint32_t *__restrict__ slice_bytes, int hdr_w, int hdr_h)
+                                                 const uint32_t *__restrict__ slice_bytes, int hdr_w, int hdr_h, SeqDesc desc)
 {
     __shared__ uint32_t s_img[kAsmImageWords];
     __shared__ uint32_t s_slot[kAsmStageWords];
@@ -2119,11 +2115,14 @@ __global__ __launch_bounds__(kAsmThreads, 8) void k_assemble(const FrameJob *__r
     // The frame's headers travel with its first slice and the sequence end code with the very last one: plain byte
     // stores by one thread.  A header byte may share a dword with a slice's boundary word; that dword was cleared by
     // k_frame_scan, the atomic OR above only adds the slice's own bits and the byte store only touches its byte.
+    // The sequence headers stand in front of the stream's first frame and, with repeat_headers (m2v_set_stream_desc), in front of every
+    // later GOP: k_frame_scan left their kSeqHeaderBytes free in front of frame_off[f].
     if (!g.strip && tid == 0) {
         uint8_t *const out8 = (uint8_t *)out32 + ctl->base_bytes;
         if (by == g.row0) {
-            if (first && f == 0) write_sequence_headers(out8, hdr_w, hdr_h);
-            write_frame_headers(out8 + frame_off[f], jobs[f]);
+            const unsigned long long fo = frame_off[f];
+            if ((first && f == 0) || (desc.repeat() && i_frame == 0)) write_sequence_headers(out8 + fo - kSeqHeaderBytes, hdr_w, hdr_h, desc);
+            write_frame_headers(out8 + fo, jobs[f], time_code_rate(desc.rate_code()));
         }
         if (last && f == nframes - 1 && by == g.row1 - 1) {
             uint8_t *e = out8 + slice_off[(size_t)f * g.mbh + by] + slice_bytes[(size_t)f * g.mbh + by];
@@ -2157,7 +2156,8 @@ __global__ __launch_bounds__(1024) void k_frame_scan(const FrameJob *__restrict_
                                                      const uint32_t *__restrict__ slice_bytes,
                                                      unsigned long long *__restrict__ slice_off,
                                                      unsigned long long *__restrict__ frame_off, StreamCtl *ctl,
-                                                     int advance, uint32_t *__restrict__ out32, int ctl_init, unsigned long long ctl_cap, PeerScan px)
+                                                     int advance, uint32_t *__restrict__ out32, int ctl_init, unsigned long long ctl_cap, PeerScan px,
+                                                     int repeat)
 {
     __shared__ unsigned long long s_base;
     __shared__ unsigned long long s_wtot[16];
@@ -2183,7 +2183,9 @@ __global__ __launch_bounds__(1024) void k_frame_scan(const FrameJob *__restrict_
     const int i0 = tid * K, i1 = i0 + K < S ? i0 + K : S;
     auto header_bytes = [&](int f) -> unsigned long long {     // bytes in front of the first slice of frame f
         if (g.strip) return 0ull;
-        return (unsigned long long)frame_header_bytes(jobs[f].i_frame) + (first && f == 0 ? kSeqHeaderBytes : 0u);
+        // (the sequence headers: in front of the stream's first frame, and with repeat_headers in front of every later GOP)
+        const int i_frame = jobs[f].i_frame;
+        return (unsigned long long)frame_header_bytes(i_frame) + ((first && f == 0) || (repeat && i_frame == 0) ? kSeqHeaderBytes : 0u);
     };
     // The thread's first kCached items are fetched in one go (all loads in flight together: this single workgroup is pure
     // latency) and kept for the second pass; longer lists (more than 8192 slices in a chunk) walk the rest one by one.
@@ -2239,7 +2241,8 @@ __global__ __launch_bounds__(1024) void k_frame_scan(const FrameJob *__restrict_
     unsigned long long run = incl - sum;
     auto place = [&](int f, int r, uint32_t sb, uint32_t hb) {
         if (r == 0) {
-            frame_off[f] = run + (!g.strip && first && f == 0 ? kSeqHeaderBytes : 0u);   // the frame's own headers start here
+            // the frame's own headers start here: behind the sequence headers where hb holds them (more than any frame's own headers)
+            frame_off[f] = run + (hb > kGopHeaderBytes + 17u ? kSeqHeaderBytes : 0u);
             run += hb;
         }
         slice_off[(size_t)f * g.mbh + g.row0 + r] = run;
@@ -2426,9 +2429,9 @@ __global__ __launch_bounds__(kCopyThreads) void k_strip_assemble(const CopySeg *
             FrameJob job{};
             job.i_frame = (int32_t)((uint32_t)f % gop);
             job.n = (uint32_t)f;
-            write_frame_headers(out + frame_pos[f], job);
+            write_frame_headers(out + frame_pos[f], job, time_code_rate(seq_desc_module().rate_code()));
         }
-        if (f == 0) write_sequence_headers(out, g.W, g.H);
+        if (f == 0) write_sequence_headers(out, g.W, g.H, seq_desc_module());
         return;
     }
     // trailer: sequence_end_code + zero padding up to the stream length (RTL:2621-2628, 2932-2937)

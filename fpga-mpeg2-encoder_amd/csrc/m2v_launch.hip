@@ -366,7 +366,7 @@ void launch_frame_scan(m2v_enc *e, hipStream_t s, const Geom &g, size_t nf, bool
     }
     hipLaunchKernelGGL(k_frame_scan, dim3(1), dim3(1024), 0, s, e->d_jobs.p, g, (int)nf, first ? 1 : 0, last ? 1 : 0,
                        e->d_slice_bytes.p, e->d_slice_off.p, e->d_frame_off.p, e->d_ctl.p, advance ? 1 : 0, (uint32_t *)d_stream,
-                       e->ctl_init, e->ctl_cap, px);
+                       e->ctl_init, e->ctl_cap, px, (int)e->seq_desc.repeat());
     e->ctl_init = 0;
 }
 
@@ -379,7 +379,7 @@ void launch_assemble(m2v_enc *e, hipStream_t s, const Geom &g, size_t nf, bool f
     hipLaunchKernelGGL(k_assemble, dim3((unsigned)(nf * rows)), dim3(kAsmThreads), 0, s, e->d_jobs.p, g, (int)nf,
                        e->d_mbinfo.p, e->d_mbaux.p, e->d_slots_small.p, e->d_slots.p, e->d_slice_off.p,
                        (uint32_t *)d_stream, e->d_ctl.p, first ? 1 : 0, last ? 1 : 0, e->d_frame_off.p, e->d_slice_bytes.p,
-                       true_size ? e->fit.w : g.W, true_size ? e->fit.h : g.H);
+                       true_size ? e->fit.w : g.W, true_size ? e->fit.h : g.H, e->seq_desc);
 }
 
 void launch_halo_pack(m2v_enc *e, hipStream_t s, const int *d_list, int count, uint8_t *up, uint8_t *down)

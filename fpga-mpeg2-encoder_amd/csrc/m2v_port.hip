@@ -580,6 +580,7 @@ void start_sequence(m2v_enc *e, uint32_t xs, uint32_t ys, uint32_t pf)
     e->pframes = pf & 0xFFu;
     sample_gop_levels(e, false);            // (the schedule; the cap is the resident entries': the callers refuse with it set)
     sample_gop_starts(e, false);            // (the list; the detector likewise)
+    sample_stream_desc(e);
     e->state = m2v_enc::DURING;
     e->frames_total = 0;
     e->first_chunk = true;

@@ -52,6 +52,7 @@ static int resident_impl(m2v_enc *e, void *argp)
     sample_recon_out(e, a->xs, a->ys);
     sample_gop_levels(e, true);
     sample_gop_starts(e, true);
+    sample_stream_desc(e);
     e->frames_total = 0;
     e->persist_slot = -1;
     for (auto &st : e->stats) st = KStat{};

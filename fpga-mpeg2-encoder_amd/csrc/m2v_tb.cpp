@@ -3,6 +3,7 @@
 //   m2v_tb [-XL n] [-YL n] [-VL n] [-Q n] [-p pframes] [-d device] [-bubbles] [-conformant] [-ps] [-ts]
 //          [-i420 | -yv12 | -nv12 | -nv21 | -rgb24 | -bgr24 | -rgbx | -bgrx | -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f]
 //          [-pad | -truesize] [-stats] [-qgop q0,q1,...] [-istart n0,n1,...] [-scenecut T] [-recon out.yuv [-reconfmt i420|yv12|nv12|nv21]]
+//          [-fps N/D] [-aspect 1:1|4:3|16:9|2.21:1] [-bitrate B] [-vbv K] [-colour bt601|bt709|P,T,M] [-repeat-headers]
 //          in.yuv W H out.m2v  [in2.yuv W2 H2 out2.m2v ...]
 //
 // -pad: W, H are any size from 49 up; the files hold frames of that size in the chosen format, which are padded to whole macroblocks on
@@ -27,6 +28,12 @@
 // -recon out.yuv: the reconstructed pictures of every video, frame behind frame, as 4:2:0 frames of W x H (the file's size under -pad too)
 // in -reconfmt (default i420): m2v_set_recon_out, read back after each video - a file for ffplay -f rawvideo or tools/m2v_stats.py --yuv.
 // The buffer is the resident entries', so it needs the resident mode that -scenecut selects (-scenecut 65280 never finds a cut).
+// -fps N/D, -aspect A, -bitrate B, -vbv K, -colour C, -repeat-headers: what the stream says about itself (m2v_set_stream_desc); NOT the
+// module's behaviour.  N/D: a rational equal to a frame rate of ISO/IEC 13818-2 table 6-4 (24000/1001, 24, 25, 30000/1001, 30, 50,
+// 60000/1001, 60; "/D" may be left out), which the GOP headers' time codes then count at; B: bit/s, rounded up to units of 400; K: the
+// vbv buffer size in its own units of 16384 bits; C: bt601 (5,5,5), bt709 (1,1,1) or colour_primaries,transfer_characteristics,
+// matrix_coefficients, each 1..255 - the label only, -matrix is what converts; -repeat-headers: the sequence headers again in front of every
+// GOP after the first, so that a player can start there.  A bad value ends with the usage text and exit status 2 before the device is touched.
 // -conformant switches the encoder's option "conformant" on (ISO reconstruction loop; NOT byte-identical to the RTL).
 // -ps / -ts additionally write out.m2v.mpg / out.m2v.ts: the same elementary stream in an MPEG-2 program / transport
 // stream (include/m2v_container.h), so the result plays in an ordinary player.
@@ -58,6 +65,9 @@ int main(int argc, char **argv)
     std::vector<uint8_t> qgop;
     std::vector<uint32_t> istart;
     bool have_istart = false;
+    m2v_stream_desc desc;
+    m2v_stream_desc_module(&desc);
+    int bad_desc = 0;
     int i = 1;
     for (; i < argc && argv[i][0] == '-'; ++i) {
         if (!strcmp(argv[i], "-bubbles")) { bubbles = 1; continue; }
@@ -67,6 +77,7 @@ int main(int argc, char **argv)
         if (!strcmp(argv[i], "-pad")) { pad = 1; continue; }
         if (!strcmp(argv[i], "-stats")) { stats = 1; continue; }
         if (!strcmp(argv[i], "-truesize")) { pad = truesize = 1; continue; }
+        if (!strcmp(argv[i], "-repeat-headers")) { desc.repeat_headers = 1; continue; }
         if (!strcmp(argv[i], "-i420")) { layout420 = M2V_420_I420; ++layouts; continue; }
         if (!strcmp(argv[i], "-yv12")) { layout420 = M2V_420_YV12; ++layouts; continue; }
         if (!strcmp(argv[i], "-nv12")) { layout420 = M2V_420_NV12; ++layouts; continue; }
@@ -93,6 +104,45 @@ int main(int argc, char **argv)
             ++i;
             continue;
         }
+        if (!strcmp(argv[i], "-fps")) {
+            char *end = nullptr;
+            const unsigned long long num = strtoull(argv[i + 1], &end, 10);
+            unsigned long long den = 1;
+            bool ok = end != argv[i + 1] && argv[i + 1][0] != '-';
+            if (ok && *end == '/') { const char *d = end + 1; den = strtoull(d, &end, 10); ok = end != d && *d != '-'; }
+            const int code = ok && !*end && num <= 0xFFFFFFFFull && den <= 0xFFFFFFFFull ? m2v_frame_rate_code((uint32_t)num, (uint32_t)den) : -1;
+            if (code < 0) bad_desc = 1; else desc.frame_rate_code = (uint32_t)code;
+            ++i;
+            continue;
+        }
+        if (!strcmp(argv[i], "-aspect")) {
+            static const char *const names[] = {"1:1", "4:3", "16:9", "2.21:1"};
+            for (k = 0; k < 4 && strcmp(argv[i + 1], names[k]); ++k) {}
+            if (k < 4) desc.aspect_ratio_information = (uint32_t)k + 1; else bad_desc = 1;
+            ++i;
+            continue;
+        }
+        if (!strcmp(argv[i], "-bitrate") || !strcmp(argv[i], "-vbv")) {
+            const bool rate = argv[i][1] == 'b';
+            char *end = nullptr;
+            const unsigned long long v = strtoull(argv[i + 1], &end, 10);
+            const unsigned long long units = rate ? (v + 399) / 400 : v;
+            if (end == argv[i + 1] || *end || argv[i + 1][0] == '-' || v > (1ull << 40) || units < (rate ? 1u : 0u) || units > (rate ? 0x3FFFFFFFull : 0x3FFFFull)) bad_desc = 1;
+            else (rate ? desc.bit_rate_400 : desc.vbv_buffer_size_16k) = (uint32_t)units;
+            ++i;
+            continue;
+        }
+        if (!strcmp(argv[i], "-colour")) {
+            unsigned c[3] = {0, 0, 0};
+            char tail = 0;
+            if (!strcmp(argv[i + 1], "bt601")) c[0] = c[1] = c[2] = 5;
+            else if (!strcmp(argv[i + 1], "bt709")) c[0] = c[1] = c[2] = 1;
+            else if (sscanf(argv[i + 1], "%3u,%3u,%3u%c", &c[0], &c[1], &c[2], &tail) != 3) c[0] = 0;
+            if (c[0] < 1 || c[0] > 255 || c[1] < 1 || c[1] > 255 || c[2] < 1 || c[2] > 255) bad_desc = 1;
+            else { desc.colour_primaries = c[0]; desc.transfer_characteristics = c[1]; desc.matrix_coefficients = c[2]; }
+            ++i;
+            continue;
+        }
         if (!strcmp(argv[i], "-scenecut")) { scenecut = atoll(argv[i + 1]); ++i; continue; }
         if (!strcmp(argv[i], "-recon")) { recon = argv[i + 1]; ++i; continue; }
         if (!strcmp(argv[i], "-reconfmt")) {
@@ -116,10 +166,12 @@ int main(int argc, char **argv)
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
         ++i;
     }
-    if ((argc - i) < 4 || (argc - i) % 4 || layouts > 1 || bad_matrix || ((layouts || pad || scenecut) && bubbles)) {          // (there are no 4:2:0 or RGB beats)
+    if ((argc - i) < 4 || (argc - i) % 4 || layouts > 1 || bad_matrix || bad_desc || ((layouts || pad || scenecut) && bubbles)) {          // (there are no 4:2:0 or RGB beats)
         fprintf(stderr, "usage: %s [-XL n] [-YL n] [-VL n] [-Q n] [-p pframes] [-d dev] [-i420 | -yv12 | -nv12 | -nv21 | -rgb24 | -bgr24 | -rgbx | -bgrx |"
                         " -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f] [-pad | -truesize] [-stats] [-qgop q0,q1,...] [-istart n0,n1,...] [-scenecut T] [-recon out.yuv [-reconfmt i420|yv12|nv12|nv21]]"
+                        " [-fps N/D] [-aspect 1:1|4:3|16:9|2.21:1] [-bitrate bit/s] [-vbv units of 16384 bits] [-colour bt601|bt709|P,T,M] [-repeat-headers]"
                         " in.yuv W H out.m2v ...\n"
+                        "  -fps takes a frame rate of ISO/IEC 13818-2 table 6-4: 24000/1001, 24, 25, 30000/1001, 30, 50, 60000/1001, 60\n"
                         "  -scenecut T stages every file's frames in device memory and encodes them with one resident call (the detector needs it)\n", argv[0]);
         return 2;
     }
@@ -137,6 +189,7 @@ int main(int argc, char **argv)
     if (stats && m2v_set_option(e, "stats", 1) < 0) { fprintf(stderr, "*** m2v_set_option(stats): %s\n", m2v_last_error(e)); return 1; }
     if (!qgop.empty() && m2v_set_gop_levels(e, qgop.data(), qgop.size()) < 0) { fprintf(stderr, "*** m2v_set_gop_levels: %s\n", m2v_last_error(e)); return 1; }
     if (have_istart && m2v_set_gop_starts(e, istart.data(), istart.size()) < 0) { fprintf(stderr, "*** m2v_set_gop_starts: %s\n", m2v_last_error(e)); return 1; }
+    if (m2v_set_stream_desc(e, &desc) < 0) { fprintf(stderr, "*** m2v_set_stream_desc: %s\n", m2v_last_error(e)); return 1; }
     if (scenecut && m2v_set_option(e, "scene_cut", scenecut) < 0) { fprintf(stderr, "*** m2v_set_option(scene_cut): %s\n", m2v_last_error(e)); return 1; }
     int num_video = 0;
     for (; i + 3 < argc; i += 4) {

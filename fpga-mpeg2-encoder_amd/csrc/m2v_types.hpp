@@ -129,4 +129,37 @@ constexpr int kMaxStripRanks = 16;
 constexpr uint32_t kSeqHeaderBytes = 34;   // 269 bits + alignment (RTL:2598-2617)
 constexpr uint32_t kGopHeaderBytes = 8;    // 59 bits + alignment  (RTL:2650-2656)
 
+#ifdef __HIPCC__
+#define M2V_HD __host__ __device__
+#else
+#define M2V_HD
+#endif
+
+// What the stream says about itself (m2v_set_stream_desc, m2v_desc.hip), as the header writers take it: a by-value kernel argument.
+// The module's stream is the writers with seq_desc_module().
+struct SeqDesc {
+    uint32_t a;         // frame_rate_code | aspect_ratio_information << 4 | video_format << 8 | repeat_headers << 11 | vbv_buffer_size (18 bits) << 12
+    uint32_t bit_rate;  // 30 bits, units of 400 bit/s
+    uint32_t colour;    // colour_primaries | transfer_characteristics << 8 | matrix_coefficients << 16
+    uint32_t display;   // display width | height << 16; 0 = the size sequence_header prints
+    M2V_HD uint32_t rate_code() const { return a & 15u; }
+    M2V_HD uint32_t aspect() const { return (a >> 4) & 15u; }
+    M2V_HD uint32_t video_format() const { return (a >> 8) & 7u; }
+    M2V_HD uint32_t repeat() const { return (a >> 11) & 1u; }
+    M2V_HD uint32_t vbv() const { return a >> 12; }
+};
+constexpr SeqDesc seq_desc_module() { return SeqDesc{2u | 1u << 4 | 1u << 8, 10000u, 5u | 5u << 8 | 5u << 16, 0u}; }   // RTL:2598-2617
+
+// frames per second the time code counts at for frame_rate_code 1..8 (table 6-4, rounded up: no drop-frame counting)
+M2V_HD inline uint32_t time_code_rate(uint32_t code) { return (uint32_t)(0x3C3C321E1E191818ull >> (8u * ((code - 1u) & 7u))) & 0xFFu; }
+// The 32 bits behind the group_start_code for a GOP whose I picture is frame n, counted at F frames per second: the module's formula
+// (RTL:2685-2698) with its 24 replaced by F.  The six bits in front - drop_frame_flag and hours - hold min(n / 3600F, 63): the module's
+// saturation, and its spill into drop_frame_flag from 32 hours on.  Then marker, seconds, pictures, closed_gop = 1, broken_link = 0.
+// The one definition: write_frame_headers prints it, m2v_time_code exports it.
+M2V_HD inline uint32_t time_code(uint32_t F, uint32_t n)
+{
+    const uint32_t hh = n / (3600u * F);
+    return (hh > 63u ? 63u : hh) << 26 | ((n / (60u * F)) % 60u) << 20 | 1u << 19 | ((n / F) % 60u) << 13 | (n % F) << 7 | 2u << 5;
+}
+
 }  // namespace m2v

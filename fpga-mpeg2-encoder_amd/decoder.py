@@ -234,16 +234,18 @@ class Decoded:
         self.width = self.height = 0
         self.gops = []
         self.slice_qcodes = []      # per picture: the quantiser_scale_code of every slice, top to bottom (1 << level: a level per GOP)
+        self.sequence = {}          # fields of sequence_header, sequence_extension and sequence_display_extension
+        self.repeated_headers = 0   # sequence headers met again in front of a GOP header (each equal to the first)
 
 
-def decode(data, quirks=True):
-    T = tables()
-    br = BitReader(data)
-    out = Decoded()
+def _sequence_headers(br):
+    """sequence_header + sequence_extension + sequence_display_extension at the reader's position -> (width, height, fields).
+    bit_rate is the 30-bit value (units of 400 bit/s: 18 bits of the header, 12 of the extension), vbv the 18-bit one (units of 16384
+    bits: 10 + 8)."""
     # ---- sequence_header ----
     assert br.next_start_code() == 0xB3
     br.bits(32)
-    out.width, out.height = br.bits(12), br.bits(12)
+    width, height = br.bits(12), br.bits(12)
     hdr = dict(aspect=br.bits(4), frame_rate_code=br.bits(4), bit_rate=br.bits(18))
     assert br.bits(1) == 1
     hdr.update(vbv=br.bits(10), constrained=br.bits(1))
@@ -253,22 +255,38 @@ def decode(data, quirks=True):
     br.bits(32)
     assert br.bits(4) == 1
     hdr.update(profile_level=br.bits(8), progressive_sequence=br.bits(1), chroma_format=br.bits(2))
-    assert br.bits(2) == 0 and br.bits(2) == 0 and br.bits(12) == 0 and br.bits(1) == 1
-    br.bits(8)
+    assert br.bits(2) == 0 and br.bits(2) == 0                  # horizontal / vertical size extension
+    hdr["bit_rate"] |= br.bits(12) << 18
+    assert br.bits(1) == 1
+    hdr["vbv"] |= br.bits(8) << 10
     hdr.update(low_delay=br.bits(1))
     br.bits(7)
     assert hdr["chroma_format"] == 1
+    assert 1 <= hdr["aspect"] <= 4 and 1 <= hdr["frame_rate_code"] <= 8 and hdr["bit_rate"] != 0, "forbidden or reserved value"
     # ---- sequence_display_extension ----
     assert br.next_start_code() == 0xB5
     br.bits(32)
     assert br.bits(4) == 2
-    br.bits(3)
+    hdr.update(video_format=br.bits(3), colour_primaries=None, transfer_characteristics=None, matrix_coefficients=None)
     if br.bits(1):
-        br.bits(24)
+        hdr.update(colour_primaries=br.bits(8), transfer_characteristics=br.bits(8), matrix_coefficients=br.bits(8))
+        assert hdr["colour_primaries"] and hdr["transfer_characteristics"] and hdr["matrix_coefficients"], "0 is forbidden"
     dw = br.bits(14)
     assert br.bits(1) == 1
-    dh = br.bits(14)
-    assert (dw, dh) == (out.width, out.height)
+    hdr["display_size"] = (dw, br.bits(14))
+    return width, height, hdr
+
+
+def sequence_headers(data):
+    """(width, height, fields) of the sequence headers at the start of a stream, without decoding a picture"""
+    return _sequence_headers(BitReader(data))
+
+
+def decode(data, quirks=True):
+    T = tables()
+    br = BitReader(data)
+    out = Decoded()
+    out.width, out.height, hdr = _sequence_headers(br)
     out.sequence = hdr
     # the header sizes are the displayable ones (6.3.3): the macroblock count rounds them up, the pictures are coded at whole
     # macroblocks and handed out cropped to width x height (chroma to the halves, rounded up)
@@ -283,6 +301,13 @@ def decode(data, quirks=True):
             br.bits(32)
             ended = True
             break
+        if code == 0xB3:
+            # a repeated sequence header (6.1.1.6): only in front of a GOP, and it says what the first one said
+            again = _sequence_headers(br)
+            assert again == (out.width, out.height, out.sequence), "a repeated sequence header differs from the first"
+            out.repeated_headers += 1
+            code = br.next_start_code()
+            assert code == 0xB8, "a repeated sequence header must be followed by a GOP header"
         if code == 0xB8:                                        # group_of_pictures_header
             br.bits(32)
             tc = dict(drop=br.bits(1), hours=br.bits(5), minutes=br.bits(6))

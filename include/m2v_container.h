@@ -36,7 +36,7 @@ typedef struct {
 } m2vc_stream_info;
 
 typedef struct {
-    uint64_t offset;                 /* byte offset of the picture's first start code (GOP header if one precedes it) */
+    uint64_t offset;                 /* byte offset of the picture's first start code (GOP header if one precedes it; a sequence header repeated in front of that GOP header if there is one) */
     uint64_t bytes;                  /* up to the next picture / sequence end */
     uint32_t coding_type;            /* 1 = I, 2 = P */
     uint32_t temporal_reference;

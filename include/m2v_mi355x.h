@@ -134,8 +134,10 @@ int m2v_push_frames420(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t 
  * purpose: every grey gives exactly 128 / 128 and white exactly 235 (or 255).  The result is within 0.508 of the real-valued
  * transform for every input; the clamp only ever acts in the two full-range matrices (Cb / Cr of pure blue / pure red reach 256).
  *
- * The stream carries NO colour description (the module writes no sequence_display_extension, RTL:2590-2716, and the stream stays what
- * the module would emit for those samples): the caller picks the matrix its player will assume.
+ * The stream DOES carry a colour description: the module writes a sequence_display_extension (RTL:2612-2617) whose colour_primaries /
+ * transfer_characteristics / matrix_coefficients are 5 / 5 / 5 (BT.470BG, BT.601), whatever matrix made the samples.  The conversion
+ * does not change it - the stream stays what the module would emit for those samples -, so a caller that converts with M2V_RGB_BT709
+ * says so itself: m2v_set_stream_desc with 1 / 1 / 1.
  */
 enum {
     M2V_RGB_BT601 = 0,
@@ -541,7 +543,8 @@ int m2v_set_gop_levels(m2v_enc *e, const uint8_t *levels, size_t n);
  * Option "gop_bytes_max" = B > 0, resident entries (m2v_encode_resident*, also _begin / _end).
  * The size of a GOP is its bytes in the stream, from its group_start_code (00 00 01 B8) up to the next one or to the
  * sequence_end_code: the headers of its pictures (25 bytes for the I picture with the GOP header, 18 for a P picture) plus the bytes
- * of their slices.  The sequence header is not part of GOP 0, the end code and the final padding not of the last one.
+ * of their slices.  The sequence header is not part of GOP 0, the end code and the final padding not of the last one.  A sequence header
+ * repeated in front of a later GOP (repeat_headers of m2v_set_stream_desc) is not part of any GOP either: neither bytes nor the cap count it.
  * GOP k is coded at the smallest level q >= start_k whose size is <= B; if none is, at 4.  start_k is the schedule's entry for k
  * (m2v_set_gop_levels), or the handle's Q_LEVEL without a schedule.  The search goes upwards one level at a time and stops at the
  * first fit, so "smallest" is well defined even where sizes are not monotone in q.  The result depends on the clip alone: not on
@@ -687,6 +690,56 @@ long long m2v_picture_stats(m2v_enc *e, m2v_picture_stat *dst, size_t cap);
  * feature), and so does every m2v_strip_* entry that starts something - the rule "stats" follows.
  */
 int m2v_set_recon_out(m2v_enc *e, void *d_dst, size_t cap, int layout);   /* layout: M2V_420_I420 | YV12 | NV12 | NV21 */
+
+/*
+ * What the stream says about itself.  NOT the module's behaviour (like option "conformant", M2V_HEADER_TRUE, a level per GOP and GOP
+ * starts): the module hard-wires the 34 bytes of its sequence headers (RTL:2598-2617) and counts its time code at 24 frames per second
+ * (RTL:2685-2698).  With a description set the stream stays a legal ISO/IEC 13818-2 one; with none, or one equal to the module's, the
+ * stream, the launches and the kernel arguments' values are the module's.
+ *
+ * The bytes.  The 34 bytes of sequence_header + sequence_extension + sequence_display_extension with these fields substituted, widths in
+ * order:  sequence_header 32, 12, 12, 4 aspect, 4 rate, 18 bit rate low, marker, 10 vbv low, 3 zero;  sequence_extension 32, 4 = 1,
+ * 8 = 0x44, 1 = 0, 2 = 1, 4 zero, 12 bit rate high, marker, 8 vbv high, 8 zero;  sequence_display_extension 32, 4 = 2, 3 video_format,
+ * 1 = 1, 8, 8, 8 colour, 14 display width, marker, 14 display height, zero bits to the byte.  profile_and_level, progressive_sequence,
+ * low_delay, frame_rate_extension_n / _d and the matrix flags do not change.
+ * The time code of frame n (the four bytes behind every 00 00 01 B8): with F = 24, 24, 25, 30, 30, 50, 60, 60 for frame_rate_code 1..8
+ * it is the module's formula with 24 replaced by F - pictures = n mod F, seconds = (n / F) mod 60, minutes = (n / 60F) mod 60, and the six
+ * bits the module writes in front hold min(n / 3600F, 63): the module's saturation, and its spill into drop_frame_flag from 32 hours on.
+ * Then the marker, closed_gop = 1, broken_link = 0.  Code 2 gives the module's bytes.  There is no true drop-frame counting.
+ * repeat_headers = 1: the same 34 bytes, printed and display sizes included, also stand in front of the group_start_code of every GOP
+ * after the first, whatever started it - cadence, m2v_set_gop_starts or "scene_cut" (ISO 6.1.1.6 allows it): a player can start at any
+ * GOP.  m2v_gop_stat.bytes and the cap's verdict do not count them, mb_bits of "stats" is untouched.
+ *
+ * m2v_set_stream_desc: any field out of range, one display size zero and the other not, reserved != 0 or repeat_headers > 1 answers
+ * M2V_E_PARAM and the previous setting stays.  d == NULL sets the module's values again.  Only while the handle is idle, M2V_E_STATE
+ * otherwise (between _begin and _end, during a port sequence).  The structure is copied, sampled when a sequence starts (where a level
+ * schedule is), stays until changed and survives m2v_reset.  It holds on every whole-frame path - the port path in all its forms and
+ * every resident entry - with any "batch_frames", "split_streams", "stats", "conformant", input format, set frame size, level schedule,
+ * "gop_bytes_max", GOP list, "scene_cut" and m2v_set_recon_out.  While a description that differs from the module's is set every
+ * m2v_strip_* entry that starts something answers M2V_E_STATE - the rule "stats", a frame size, a schedule and a list follow.
+ */
+typedef struct m2v_stream_desc {
+    uint32_t frame_rate_code;           /* 1..8, table 6-4                                        module: 2     */
+    uint32_t aspect_ratio_information;  /* 1..4, table 6-3                                        module: 1     */
+    uint32_t bit_rate_400;              /* 1..2^30-1, units of 400 bit/s: low 18 bits in
+                                           sequence_header, high 12 in sequence_extension         module: 10000 */
+    uint32_t vbv_buffer_size_16k;       /* 0..2^18-1, units of 16384 bits: low 10 / high 8 bits   module: 0     */
+    uint32_t video_format;              /* 0..5                                                   module: 1     */
+    uint32_t colour_primaries;          /* 1..255 (0 is forbidden)                                module: 5     */
+    uint32_t transfer_characteristics;  /* 1..255                                                 module: 5     */
+    uint32_t matrix_coefficients;       /* 1..255                                                 module: 5     */
+    uint32_t display_width;             /* both 0 = the size sequence_header prints (today's rule, M2V_HEADER_TRUE */
+    uint32_t display_height;            /* included); else both 1..16383                                           */
+    uint32_t repeat_headers;            /* 0 | 1                                                  module: 0     */
+    uint32_t reserved;                  /* 0 */
+} m2v_stream_desc;                      /* 48 bytes */
+void m2v_stream_desc_module(m2v_stream_desc *d);                 /* the module's values */
+int m2v_set_stream_desc(m2v_enc *e, const m2v_stream_desc *d);   /* NULL = the module's again */
+/* 1..8 for a rational EQUAL to one of table 6-4 (30000/1000 is 30), else M2V_E_PARAM.  Plain arithmetic. */
+int m2v_frame_rate_code(uint32_t num, uint32_t den);
+/* the four bytes behind 00 00 01 B8 for frame n at frame_rate_code 1..8 (M2V_E_PARAM otherwise): the function the encoder prints; no GPU,
+ * no handle */
+int m2v_time_code(uint32_t frame_rate_code, uint32_t n, uint8_t out[4]);
 
 /* Per-kernel statistics of the last m2v_encode_resident call with "profile" = 1.
  * kernel: 0 = macroblock kernel on P frames, 1 = macroblock kernel on I frames,

@@ -61,6 +61,15 @@ def main():
     print("  %d bytes (+%d padding) = %.4f bit/pixel, %.1f kbit/s; I pictures %.1f %% of the bytes" % (
         info.bytes, info.padding_bytes, info.bytes * 8 / px, info.bytes * 8 / secs / 1e3,
         100.0 * sum(p.bytes for p in pics if p.coding_type == 1) / max(info.bytes, 1)))
+    # what the stream says about itself (m2v_set_stream_desc), and whether its sequence headers come again in front of later GOPs
+    # (start codes cannot occur inside the coded data, so counting them is exact)
+    seq = M.decoder.sequence_headers(es)[2]
+    repeats = es[:info.bytes].count(b"\x00\x00\x01\xb3") - 1
+    colour = (seq["colour_primaries"], seq["transfer_characteristics"], seq["matrix_coefficients"])
+    print("  description: aspect code %d, bit rate %d bit/s, vbv %d bits, video_format %d, colour %s, display %dx%d" % (
+        seq["aspect"], seq["bit_rate"] * 400, seq["vbv"] * 16384, seq["video_format"],
+        {v: k for k, v in M.COLOURS.items()}.get(colour, "%s/%s/%s" % colour), seq["display_size"][0], seq["display_size"][1]))
+    print("  sequence headers: %s" % ("repeated in front of %d of %d later GOPs" % (repeats, info.gops - 1) if repeats else "once, at byte 0"))
     sizes = np.array([p.bytes for p in pics], dtype=np.float64)
     for name, t in (("I", 1), ("P", 2)):
         s = sizes[[p.coding_type == t for p in pics]]
@@ -96,6 +105,11 @@ def main():
             enc.set_option("conformant", int(args.conformant))
             if W % 16 or H % 16:
                 enc.set_frame_size(W, H, "true")
+            d = M.StreamDesc(seq["frame_rate_code"], seq["aspect"], seq["bit_rate"], seq["vbv"], seq["video_format"], *colour,
+                             *seq["display_size"], 1 if repeats else 0, 0)
+            if seq["display_size"] == (W, H):
+                d.display_width = d.display_height = 0
+            enc.set_stream_desc(d)
             got = enc.encode(src[:n * fb], xs, ys, pf, layout=args.layout, matrix=args.matrix)
             rec = enc.picture_stats()
         finally:
