@@ -44,6 +44,7 @@ EXPORTS = [
     "m2v_set_gop_starts", "m2v_gop_layout", "m2v_scene_report",
     "m2v_set_recon_out",
     "m2v_stream_desc_module", "m2v_set_stream_desc", "m2v_frame_rate_code", "m2v_time_code",
+    "m2v_set_sequences", "m2v_sequence_report",
 ]
 
 # the 4:2:0 entry points (kept apart: tests/test_abi.py matches EXPORTS against names of letters and underscores only)
@@ -96,6 +97,28 @@ class SceneStat(ctypes.Structure):
 # the same record as a numpy structured dtype (Mpeg2Encoder.scene_report)
 SCENE_STAT_DTYPE = np.dtype([("frame", "<u4"), ("flags", "<u4"), ("diff", "<u8")])
 GOP_FIRST, GOP_CADENCE, GOP_LIST, GOP_CUT = 1, 2, 4, 8           # M2V_GOP_*
+
+
+class SequenceStat(ctypes.Structure):
+    """m2v_sequence_stat (include/m2v_mi355x.h): one clip's record of a batch (m2v_set_sequences), 32 bytes"""
+    _fields_ = [("offset", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("first_frame", ctypes.c_uint32), ("frames", ctypes.c_uint32),
+                ("gops", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+# the same record as a numpy structured dtype (Mpeg2Encoder.sequence_report)
+SEQUENCE_STAT_DTYPE = np.dtype([("offset", "<u8"), ("bytes", "<u8"), ("first_frame", "<u4"), ("frames", "<u4"), ("gops", "<u4"),
+                                ("reserved", "<u4")])
+
+
+def check_sequences(lengths, nframes):
+    """the rule of m2v_set_sequences for a call of nframes frames, as plain arithmetic: the list of ints, or ValueError for an entry
+    below 1 or a sum that is not nframes"""
+    ln = [int(v) for v in lengths]
+    if any(v < 1 or v > 0xFFFFFFFF for v in ln):
+        raise ValueError("sequences: every entry is 1 .. 2^32 - 1 frames, got %r" % (ln,))
+    if sum(ln) != int(nframes):
+        raise ValueError("sequences: the entries add up to %d, the call has %d frames" % (sum(ln), int(nframes)))
+    return ln
 
 
 class StreamDesc(ctypes.Structure):
@@ -319,6 +342,8 @@ def lib(debug=False):
             L.m2v_set_stream_desc.argtypes = [vp, ctypes.POINTER(StreamDesc)]
             L.m2v_frame_rate_code.argtypes = [u32, u32]
             L.m2v_time_code.argtypes = [u32, u32, ctypes.POINTER(ctypes.c_uint8)]
+            L.m2v_set_sequences.argtypes = [vp, vp, sz]
+            L.m2v_sequence_report.argtypes = [vp, vp, sz]
         except AttributeError:
             # an OLDER build handed in through M2V_LIB for a same-box A/B (tools/ab.sh) may lack the newer entry points; the library of
             # this tree must have every one of them (tests/test_abi.py)
@@ -559,6 +584,28 @@ class Mpeg2Encoder:
         out = np.zeros(n, SCENE_STAT_DTYPE)
         if n:
             n = self._chk(self._L.m2v_scene_report(self._h, out.ctypes.data, n), "m2v_scene_report")
+        return out[:n]
+
+    def set_sequences(self, lengths):
+        """m2v_set_sequences: the frames of every resident call started from now on are len(lengths) clips of these many frames, each
+        coded as a stream of its own (sequence_report says where); None or an empty sequence clears the setting.  A call whose frames
+        are not the sum of the entries, or an entry of 0, fails with M2VError when it starts."""
+        ln = [] if lengths is None else [int(v) for v in lengths]
+        if any(v < 0 or v > 0xFFFFFFFF for v in ln):
+            raise M2VError("m2v_set_sequences failed (-1): an entry is 1 .. 2^32 - 1 frames")
+        buf = (ctypes.c_uint32 * max(1, len(ln)))(*ln)
+        self._chk(self._L.m2v_set_sequences(self._h, buf if ln else None, len(ln)), "m2v_set_sequences")
+        self._sequences = ln or None
+
+    def sequence_report(self, max_records=None):
+        """Pops the waiting records of m2v_sequence_report, oldest first, at most max_records of them: a numpy structured array of
+        SEQUENCE_STAT_DTYPE - one per clip of the last resident call that had a list of two or more entries, empty otherwise."""
+        n = self._chk(self._L.m2v_sequence_report(self._h, None, 0), "m2v_sequence_report")
+        if max_records is not None:
+            n = min(n, int(max_records))
+        out = np.zeros(n, SEQUENCE_STAT_DTYPE)
+        if n:
+            n = self._chk(self._L.m2v_sequence_report(self._h, out.ctypes.data, n), "m2v_sequence_report")
         return out[:n]
 
     def set_gop_levels(self, levels):
@@ -829,7 +876,7 @@ class Mpeg2Encoder:
         return out[:n]
 
     def encode_tensor(self, frames, pframes_count, order="rgb", matrix="bt601", out=None, header=None, stats=False, gop_levels=None,
-                      gop_bytes_max=0, gop_starts=None, scene_cut=0, recon=None, desc=None):
+                      gop_bytes_max=0, gop_starts=None, scene_cut=0, recon=None, desc=None, sequences=None):
         """One whole sequence from a torch image tensor on the handle's device, in one call: contiguous uint8 [N, H, W, 3] (order
         "rgb" / "bgr"), [N, H, W, 4] ("rgbx" / "bgrx" / "xrgb" / "xbgr") or [N, 3, H, W] ("rgb": planar).  Runs
         m2v_encode_resident_rgb on torch's current stream and returns the stream bytes as a uint8 device tensor (a view of `out` when
@@ -850,7 +897,10 @@ class Mpeg2Encoder:
         frames' device, returned after the stream (and after the records with stats=True); planes_of_recon takes it apart
         (set_recon_out for the duration of the call; the handle's own setting is back afterwards).
         desc = a StreamDesc (stream_desc): what the stream says about itself, for this call (set_stream_desc; the handle's own setting
-        is back afterwards).  The matrix does not set it: matrix="bt709" goes with desc=stream_desc(colour="bt709")."""
+        is back afterwards).  The matrix does not set it: matrix="bt709" goes with desc=stream_desc(colour="bt709").
+        sequences = a list of frame counts that add up to N (ValueError otherwise): the frames are that many clips, each coded as a
+        stream of its own, one behind the other on 32-byte boundaries in the tensor returned (set_sequences for the duration of the
+        call; the handle's own setting is back afterwards).  sequence_report() says where each one is; encode_batch does both."""
         import torch
         if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4:
             raise ValueError("encode_tensor: a uint8 tensor of 4 dimensions is required")
@@ -861,6 +911,8 @@ class Mpeg2Encoder:
         if matrix not in MATRICES_RGB:
             raise ValueError("encode_tensor: unknown matrix %r" % (matrix,))
         N, d1, d2, d3 = frames.shape
+        if sequences is not None:
+            sequences = check_sequences(sequences, N)
         if order in ("rgb", "bgr") and d3 == 3:
             layout, H, W = order + "24", d1, d2
         elif order in ("rgbx", "bgrx", "xrgb", "xbgr") and d3 == 4:
@@ -880,7 +932,7 @@ class Mpeg2Encoder:
             raise ValueError("encode_tensor: %d x %d does not pad to a size of this handle (64 ... %d x 64 ... %d)"
                              % (W, H, 16 << self.params[0], 16 << self.params[1]))
         if out is None:
-            out = torch.empty(N * (3 * 256 * xs * ys + 34) + (1 << 16), dtype=torch.uint8, device=frames.device)     # (34: repeat_headers)
+            out = torch.empty(N * (3 * 256 * xs * ys + 34) + (1 << 16) + 64 * len(sequences or ()), dtype=torch.uint8, device=frames.device)     # (34: repeat_headers)
         elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != frames.device or not out.is_contiguous() or out.dim() != 1:
             raise ValueError("encode_tensor: out must be a contiguous one-dimensional uint8 tensor on the frames' device")
         rec = torch.empty((N, frame_bytes(W, H, recon)), dtype=torch.uint8, device=frames.device) if recon is not None else None
@@ -895,7 +947,10 @@ class Mpeg2Encoder:
         levels_before, cap_before = getattr(self, "_gop_levels", None), getattr(self, "_gop_cap", 0)
         starts_before, cut_before = getattr(self, "_gop_starts", None), getattr(self, "_scene_cut", 0)
         desc_before = getattr(self, "_desc", None)
+        seq_before = getattr(self, "_sequences", None)
         try:
+            if sequences is not None:
+                self.set_sequences(sequences)
             if desc is not None:
                 self.set_stream_desc(desc)
             if gop_levels is not None:
@@ -928,8 +983,37 @@ class Mpeg2Encoder:
                 self.set_option("scene_cut", cut_before)
             if desc is not None:
                 self.set_stream_desc(desc_before)
+            if sequences is not None:
+                self.set_sequences(seq_before)
         res = (out[:nb],) + ((records,) if stats else ()) + ((rec,) if rec is not None else ())
         return res if len(res) > 1 else res[0]
+
+    def encode_batch(self, frames, pframes_count, lengths=None, **kw):
+        """A batch of clips in one call, one stream per clip: a uint8 tensor [B, N, H, W, C] (or [B, N, 3, H, W]) on the handle's
+        device - B clips of N frames - or a 4-D tensor of frames as encode_tensor takes it with lengths = the clips' frame counts.
+        Returns (stream_tensor, offsets): clip b's stream is stream_tensor[offsets[b]:offsets[b + 1]], offsets a list of B + 1 ints,
+        every one a multiple of 32.  Keywords as encode_tensor's; with stats or recon the first element of its tuple is the stream."""
+        import torch
+        if not isinstance(frames, torch.Tensor) or frames.dim() not in (4, 5):
+            raise ValueError("encode_batch: a uint8 tensor of 4 or 5 dimensions is required")
+        if frames.dim() == 5:
+            if lengths is not None:
+                raise ValueError("encode_batch: lengths go with a 4-D tensor; a 5-D one says them itself")
+            if not frames.is_contiguous():
+                raise ValueError("encode_batch: the tensor must be contiguous")
+            lengths = [frames.shape[1]] * frames.shape[0]
+            frames = frames.reshape((frames.shape[0] * frames.shape[1],) + tuple(frames.shape[2:]))
+        elif lengths is None:
+            raise ValueError("encode_batch: a 4-D tensor needs lengths")
+        lengths = check_sequences(lengths, frames.shape[0])
+        res = self.encode_tensor(frames, pframes_count, sequences=lengths, **kw)
+        stream = res[0] if isinstance(res, tuple) else res
+        if len(lengths) < 2:             # (a list of one entry is no batch: one stream, from 0 to its end)
+            offsets = [0, int(stream.numel())]
+        else:
+            rec = self.sequence_report()
+            offsets = [int(v) for v in rec["offset"]] + [int(rec["offset"][-1] + rec["bytes"][-1])]
+        return ((stream, offsets) + tuple(res[1:])) if isinstance(res, tuple) else (stream, offsets)
 
     def encode_resident_end(self):
         n = ctypes.c_size_t(0)

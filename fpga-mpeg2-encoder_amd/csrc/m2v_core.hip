@@ -105,8 +105,19 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
     const bool layout = seq_has_layout(e);
     GopRule rule{e->pframes, e->seq_starts.data(), e->seq_starts.size(), 0, e->gop_s, e->gop_k};
     if (layout) e->st().scene.clear();
+    // a batch (m2v_set_sequences): a frame counts from its own sequence's first frame, and says in FrameJob::pad where it stands
+    const bool batch = seq_batch(e);
+    size_t sq_at = e->seq_at, sq_f0 = e->seq_f0;
+    uint32_t sq_ord = 0;
     for (size_t k = 0; k < nf; ++k) {
-        const size_t n = e->frames_total + k;
+        size_t n = e->frames_total + k;
+        uint32_t sq_flags = 0;
+        if (batch) {
+            if (n == sq_f0 + e->seq_lens[sq_at]) { sq_f0 = n; ++sq_at; if (k) ++sq_ord; }
+            if (k == 0) e->plan_seq0 = sq_at;
+            n -= sq_f0;
+            sq_flags = (n == 0 ? kSeqFirst : 0u) | (n + 1 == e->seq_lens[sq_at] ? kSeqLast : 0u) | sq_ord << kSeqOrdShift;
+        }
         jobs[k].in = d_frames + k * frame_bytes;
         jobs[k].i_frame = (int32_t)(n % gop);
         if (layout) {
@@ -124,12 +135,15 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
         jobs[k].rhidx = -1;
         // (a GOP that continues across a chunk boundary keeps its level: n counts from the sequence's start, and so does the rule's k)
         jobs[k].q = (uint32_t)(layout ? level_of_gop(e, rule.k - 1) : level_of_frame(e, n));
-        jobs[k].pad = 0;
+        jobs[k].pad = sq_flags;
         if (k == 0 || jobs[k].i_frame == 0) seg_start.push_back((int)k);
     }
     const size_t nseg = seg_start.size();
     e->gop_s = rule.s;
     e->gop_k = rule.k;
+    e->seq_at = sq_at;
+    e->seq_f0 = sq_f0;
+    e->plan_nsq = (size_t)sq_ord + 1;
     e->rec_bytes = (size_t)g.rysz * 3 / 2;           // tiled, with one extra tile column (rec_luma_off)
     // option "stats" measures every picture against its reconstruction: the unreferenced ones get a slot too (k_mb's need_rec is the
     // runtime test job.rec != nullptr).  The two alternating slots of a segment still do: frame k writes slot k & 1 and reads (k - 1) & 1,
@@ -161,7 +175,7 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
             for (size_t k = a; k < b; ++k) {
                 // a frame's reconstruction is needed iff a P frame of the same GOP follows (ref(f+1) = recon(f))
                 const bool known_last = last && k == nf - 1;
-                bool followed = (uint32_t)jobs[k].i_frame < e->pframes && !known_last;
+                bool followed = (uint32_t)jobs[k].i_frame < e->pframes && !known_last && !(jobs[k].pad & kSeqLast);
                 if (layout) {
                     // ... which a start from the list, or a cut, ends early.  The next chunk's cuts are not known yet: its first frame may
                     // turn out not to need this one
@@ -276,7 +290,7 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
         e->st().h_lists_cap = lists.size();
     }
     const bool on_device = e->dev_jobs_p == e->d_jobs.p && e->dev_lists_p == e->d_lists.p && e->dev_joblist_p == e->d_joblist.p &&
-                           e->dev_jobs.size() == nf && e->dev_lists.size() == lists.size() &&
+                           e->dev_jobs.size() == nf && e->dev_lists.size() == lists.size() && (!batch || e->dev_base == e->frames_total) &&
                            !memcmp(e->dev_jobs.data(), jobs.data(), nf * sizeof(FrameJob)) &&
                            !memcmp(e->dev_lists.data(), lists.data(), lists.size() * sizeof(int));
     if (!on_device) {
@@ -285,6 +299,8 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
         for (size_t i = 0; i < lists.size(); ++i) {
             e->st().h_joblist[i] = jobs[(size_t)lists[i]];
             e->st().h_joblist[i].fidx = (uint32_t)lists[i];
+            // (k_recon_out goes by the CALL's frame number; FrameJob::n is that unless the call is a batch)
+            if (batch) e->st().h_joblist[i].n = (uint32_t)(e->frames_total + (size_t)lists[i]);
         }
         // The plan goes up through ONE small kernel that reads the pinned staging itself (host memory is mapped into the device's
         // address space), not through three copy-engine transfers: on the port path those queue on the engine behind the NEXT chunk's
@@ -293,6 +309,7 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
         e->dev_jobs = jobs;
         e->dev_lists = lists;
         e->dev_jobs_p = e->d_jobs.p; e->dev_lists_p = e->d_lists.p; e->dev_joblist_p = e->d_joblist.p;
+        e->dev_base = e->frames_total;
     }
     if (e->stats_on) stats_begin_chunk(e, s, nf);
     e->plan_nf = nf;
@@ -365,7 +382,8 @@ void finish_chunk(m2v_enc *e, hipStream_t s, bool first, bool last, uint8_t *d_s
         Timer t(e, s, 4, (double)nf * g.ysz);
         if (!e->slice_scan_done) launch_slice_scan(e, s, g, 0, (int)nf);
         e->slice_scan_done = false;
-        launch_frame_scan(e, s, g, nf, first, last, advance, d_stream);
+        if (seq_batch(e)) launch_seq_scan(e, s, g, nf, advance, d_stream);
+        else launch_frame_scan(e, s, g, nf, first, last, advance, d_stream);
         HIPCHK(hipGetLastError());
         t.stop();
     }
@@ -549,6 +567,7 @@ void m2v_destroy(m2v_enc *e)
     e->d_pstat.release();
     e->d_gop.release();
     scene_release(e);
+    seq_release(e);
     if (e->ev_gop) (void)hipEventDestroy(e->ev_gop);
     if (e->h_redo) (void)hipHostFree(e->h_redo);
     for (auto p : e->rec_pool) (void)hipFree(p);
@@ -619,6 +638,7 @@ int m2v_reset(m2v_enc *e)
     stats_drop(e);
     gop_drop(e);
     scene_drop(e);
+    seq_drop(e);
     // a strip sequence abandoned between m2v_strip_begin and m2v_strip_finish: back to the full frame
     e->strip_active = false;
     e->strip_inflight = false;

@@ -21,6 +21,9 @@
 //                     m2v_frame_rate_code and m2v_time_code
 //   m2v_recon.hip     m2v_set_recon_out: the setting, what a resident sequence samples from it when it starts, the capacity check and
 //                     the refusals (the kernel, m2v_recon_kernels.hpp, is launched from m2v_launch.hip)
+//   m2v_sequences.hip m2v_set_sequences: a batch of sequences in one resident call - the setting, what a call samples from it, the
+//                     refusals, the records' way to the host and m2v_sequence_report (the scan that places the streams, k_seq_scan in
+//                     m2v_seq_kernels.hpp, is launched from m2v_launch.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -317,6 +320,19 @@ struct m2v_enc {
     bool desc_set = false;
     SeqDesc seq_desc = seq_desc_module();
 
+    // a batch of sequences (m2v_sequences.hip): the setting, and what the resident call in progress sampled from it when it started
+    // (seq_lens empty: one sequence, nothing below is touched).  seq_at / seq_f0: the sequence open at frames_total and the call frame it
+    // starts at, carried across chunks; plan_seq0 / plan_nsq: the sequence of the planned chunk's first frame, and how many it touches
+    std::vector<uint32_t> sequences, seq_lens;
+    size_t seq_at = 0, seq_f0 = 0, plan_seq0 = 0, plan_nsq = 0;
+    size_t dev_base = 0;                  // frames_total of the plan d_joblist holds (a batch's copies there carry the CALL's frame number)
+    DevBuf<m2v_sequence_stat> d_seq;      // the call's records on the device: offset and bytes of the open sequence travel from chunk to chunk here
+    DevBuf<unsigned long long> d_seqtmp;  // k_seq_scan's raw starts and deltas of the chunk's sequences
+    m2v_sequence_stat *h_seq = nullptr;   // pinned: the same records, written by k_seq_scan itself
+    size_t h_seq_cap = 0;
+    bool seq_pending = false;             // a batch is in flight or has just completed: its records have not moved to seq_q yet
+    std::deque<m2v_sequence_stat> seq_q;  // the last call's records nobody has popped yet
+
     // debug bookkeeping of the last resident encode
     size_t dbg_frames = 0;
     std::vector<int> dbg_rec_slot;
@@ -425,6 +441,10 @@ constexpr const char *kNoStrips = "strips take whole padded frames";
 inline bool strip_refuses(m2v_enc *e, const char *fn)
 {
     if (size_refuses(e, fn, kNoStrips)) return true;
+    if (!e->sequences.empty()) {
+        e->set_err("%s: a batch of sequences is set (m2v_set_sequences): the strip assembly writes one stream", fn);
+        return true;
+    }
     if (e->recon_out.p) {
         e->set_err("%s: a buffer for the reconstruction is set (m2v_set_recon_out): a strip holds part of a picture, and nothing gathers the parts", fn);
         return true;
@@ -450,6 +470,7 @@ inline bool strip_refuses(m2v_enc *e, const char *fn)
     e->seq_cap = 0;
     e->seq_starts.clear();
     e->seq_cut = 0;
+    e->seq_lens.clear();
     return false;
 }
 // ---- m2v_gop.hip ----
@@ -556,6 +577,20 @@ void sample_recon_out(m2v_enc *e, uint32_t xs, uint32_t ys);
 // the port entries that start a sequence: true = refused (M2V_E_STATE) because a buffer is set
 bool recon_refuses(m2v_enc *e, const char *fn);
 
+// ---- m2v_sequences.hip: m2v_set_sequences ----
+inline bool seq_batch(const m2v_enc *e) { return !e->seq_lens.empty(); }
+// a resident call of nframes frames is about to start: M2V_OK, or M2V_E_PARAM (the list does not add up to nframes, or holds a 0) or
+// M2V_E_STATE (a batch together with a GOP list, the detector or the cap).  Reads the settings only
+int seq_check(m2v_enc *e, const char *fn, size_t nframes);
+// the start of a resident call samples the list (where sample_gop_starts is called) and writes what the host knows of a batch's records
+void sample_sequences(m2v_enc *e);
+// the port entries that start a sequence: true = refused (M2V_E_STATE) because a list is set
+bool seq_refuses(m2v_enc *e, const char *fn);
+// a completed call's records (its stream has been waited for) to the handle's queue; ok = false: the call overflowed, there are none
+void seq_collect(m2v_enc *e, bool ok);
+void seq_drop(m2v_enc *e);
+void seq_release(m2v_enc *e);
+
 // ---- m2v_launch.hip: everything that touches device code ----
 // The constant tables live in each device's copy of the code object: uploaded once per device, whichever thread creates the first
 // handle there (config c4 creates 8 handles from 8 threads).
@@ -592,6 +627,8 @@ void launch_plan_upload(m2v_enc *e, hipStream_t s, const FrameJob *h_jobs, size_
 // neighbour-dependent codes + bit offsets of the slices of frames [f0, f1) of the chunk (one block per slice)
 void launch_slice_scan(m2v_enc *e, hipStream_t s, const Geom &g, int f0, int f1);
 void launch_frame_scan(m2v_enc *e, hipStream_t s, const Geom &g, size_t nf, bool first, bool last, bool advance, uint8_t *d_stream);
+// a batch's chunk (m2v_set_sequences): the same, with every sequence that ends in the chunk padded on its own, and the records (k_seq_scan)
+void launch_seq_scan(m2v_enc *e, hipStream_t s, const Geom &g, size_t nf, bool advance, uint8_t *d_stream);
 void launch_assemble(m2v_enc *e, hipStream_t s, const Geom &g, size_t nf, bool first, bool last, uint8_t *d_stream);
 void launch_halo_pack(m2v_enc *e, hipStream_t s, const int *d_list, int count, uint8_t *up, uint8_t *down);
 void launch_halo_unpack(m2v_enc *e, hipStream_t s, const int *d_list, int count, const uint8_t *from_up, const uint8_t *from_down);

@@ -2121,10 +2121,10 @@ __global__ __launch_bounds__(kAsmThreads, 8) void k_assemble(const FrameJob *__r
         uint8_t *const out8 = (uint8_t *)out32 + ctl->base_bytes;
         if (by == g.row0) {
             const unsigned long long fo = frame_off[f];
-            if ((first && f == 0) || (desc.repeat() && i_frame == 0)) write_sequence_headers(out8 + fo - kSeqHeaderBytes, hdr_w, hdr_h, desc);
+            if ((first && f == 0) || (jobs[f].pad & kSeqFirst) || (desc.repeat() && i_frame == 0)) write_sequence_headers(out8 + fo - kSeqHeaderBytes, hdr_w, hdr_h, desc);
             write_frame_headers(out8 + fo, jobs[f], time_code_rate(desc.rate_code()));
         }
-        if (last && f == nframes - 1 && by == g.row1 - 1) {
+        if (((last && f == nframes - 1) || (jobs[f].pad & kSeqLast)) && by == g.row1 - 1) {
             uint8_t *e = out8 + slice_off[(size_t)f * g.mbh + by] + slice_bytes[(size_t)f * g.mbh + by];
             e[0] = 0x00; e[1] = 0x00; e[2] = 0x01; e[3] = 0xB7;       // sequence_end_code (RTL:2625-2628)
         }

@@ -1,6 +1,6 @@
 // m2v_launch.hip — the one translation unit of libm2v_mi355x.so that contains device code: it includes m2v_kernels.hpp (and, for
 // option "stats", m2v_stats_kernels.hpp, for option "gop_bytes_max", m2v_gop_kernels.hpp, for m2v_set_recon_out,
-// m2v_recon_kernels.hpp behind it), uploads the
+// m2v_recon_kernels.hpp, for m2v_set_sequences, m2v_seq_kernels.hpp behind it), uploads the
 // constant tables into this code object's device globals and offers one plain C++ launch function per kernel to the host units
 // (m2v_host.hpp).  Kernel template arguments are chosen here from the handle's parameters (VECTOR_LEVEL, options).
 #include <mutex>
@@ -11,6 +11,7 @@
 #include "m2v_gop_kernels.hpp"
 #include "m2v_scene_kernels.hpp"
 #include "m2v_recon_kernels.hpp"
+#include "m2v_seq_kernels.hpp"
 
 namespace m2v {
 
@@ -367,6 +368,16 @@ void launch_frame_scan(m2v_enc *e, hipStream_t s, const Geom &g, size_t nf, bool
     hipLaunchKernelGGL(k_frame_scan, dim3(1), dim3(1024), 0, s, e->d_jobs.p, g, (int)nf, first ? 1 : 0, last ? 1 : 0,
                        e->d_slice_bytes.p, e->d_slice_off.p, e->d_frame_off.p, e->d_ctl.p, advance ? 1 : 0, (uint32_t *)d_stream,
                        e->ctl_init, e->ctl_cap, px, (int)e->seq_desc.repeat());
+    e->ctl_init = 0;
+}
+
+void launch_seq_scan(m2v_enc *e, hipStream_t s, const Geom &g, size_t nf, bool advance, uint8_t *d_stream)
+{
+    e->d_seqtmp.recorded = false;
+    e->d_seqtmp.ensure(2 * e->plan_nsq + 1);
+    hipLaunchKernelGGL(k_seq_scan, dim3(1), dim3(kSeqThreads), 0, s, e->d_jobs.p, g, (int)nf, e->d_slice_bytes.p, e->d_slice_off.p,
+                       e->d_frame_off.p, e->d_ctl.p, advance ? 1 : 0, (uint32_t *)d_stream, e->ctl_init, e->ctl_cap,
+                       (int)e->seq_desc.repeat(), e->d_seqtmp.p, e->d_seq.p, e->h_seq, (int)e->plan_seq0);
     e->ctl_init = 0;
 }
 

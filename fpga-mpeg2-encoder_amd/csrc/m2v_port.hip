@@ -580,6 +580,7 @@ void start_sequence(m2v_enc *e, uint32_t xs, uint32_t ys, uint32_t pf)
     e->pframes = pf & 0xFFu;
     sample_gop_levels(e, false);            // (the schedule; the cap is the resident entries': the callers refuse with it set)
     sample_gop_starts(e, false);            // (the list; the detector likewise)
+    e->seq_lens.clear();                    // (a batch is the resident entries': the callers refuse with a list set)
     sample_stream_desc(e);
     e->state = m2v_enc::DURING;
     e->frames_total = 0;
@@ -699,7 +700,7 @@ static int push_beats_impl(m2v_enc *e, void *argp)
         return M2V_OK;
     }
     if (e->state == m2v_enc::IDLE) {
-        if (cap_refuses(e, "m2v_push_beats") || cut_refuses(e, "m2v_push_beats") || recon_refuses(e, "m2v_push_beats")) return M2V_E_STATE;
+        if (cap_refuses(e, "m2v_push_beats") || cut_refuses(e, "m2v_push_beats") || seq_refuses(e, "m2v_push_beats") || recon_refuses(e, "m2v_push_beats")) return M2V_E_STATE;
         start_sequence(e, a->xs, a->ys, a->pf);
     }
     const Geom &g = e->g;
@@ -853,7 +854,7 @@ static int push_frames_impl(m2v_enc *e, void *argp)
     };
     if (e->state == m2v_enc::ENDED || a->n == 0) { settle_deferred(); return M2V_OK; }
     if (e->state == m2v_enc::IDLE) {
-        if (cap_refuses(e, "m2v_push_frames") || cut_refuses(e, "m2v_push_frames") || recon_refuses(e, "m2v_push_frames")) { settle_deferred(); return M2V_E_STATE; }
+        if (cap_refuses(e, "m2v_push_frames") || cut_refuses(e, "m2v_push_frames") || seq_refuses(e, "m2v_push_frames") || recon_refuses(e, "m2v_push_frames")) { settle_deferred(); return M2V_E_STATE; }
         if (!sample_frame_size(e, "m2v_push_frames", a->xs, a->ys)) { settle_deferred(); return M2V_E_PARAM; }
         start_sequence(e, a->xs, a->ys, a->pf);
     }

@@ -20,6 +20,7 @@ static int resident_end_impl(m2v_enc *e, void *argp)
     stats_collect(e, e->st());
     gop_collect(e, e->st());
     scene_collect(e, e->st());
+    seq_collect(e, !e->st().h_ctl->overflow);
     if (e->st().h_ctl->overflow) { e->set_err("output buffer too small"); return M2V_E_OVERFLOW; }
     if (bytes) *bytes = (size_t)e->st().h_ctl->total_bytes;
     return M2V_OK;
@@ -29,10 +30,12 @@ static int resident_impl(m2v_enc *e, void *argp)
 {
     auto *a = (ResidentArgs *)argp;
     if (e->state != m2v_enc::IDLE || e->strip_active || e->resident_inflight || e->strip_inflight) { e->set_err("m2v_encode_resident: encoder busy"); return M2V_E_STATE; }
+    if (const int r = seq_check(e, "m2v_encode_resident", a->n)) return r;      // (nothing of the handle has changed)
     e->resident_empty = false;
     stats_drop(e);                                      // (the previous sequence's unread picture records)
     gop_drop(e);
     scene_drop(e);
+    seq_drop(e);
     if (a->n == 0) {                                    // no beat: the sequence never starts
         if (a->bytes) *a->bytes = 0;
         e->resident_empty = a->async;                   // only _begin leaves an _end to answer
@@ -53,6 +56,7 @@ static int resident_impl(m2v_enc *e, void *argp)
     sample_gop_levels(e, true);
     sample_gop_starts(e, true);
     sample_stream_desc(e);
+    sample_sequences(e);
     e->frames_total = 0;
     e->persist_slot = -1;
     for (auto &st : e->stats) st = KStat{};
@@ -65,6 +69,7 @@ static int resident_impl(m2v_enc *e, void *argp)
     // align chunks to GOP boundaries so every chunk starts with an I frame where possible
     const size_t gop = e->pframes + 1u;
     size_t step = chunk >= gop ? chunk / gop * gop : chunk;
+    if (seq_batch(e)) step = chunk;               // (a batch's GOPs count from their sequences' starts: there is no grid to align to)
     const int kind = a->kind < 0 && e->fit.w ? kPk444 : a->kind;       // (planar 4:4:4 frames that have to be padded: through the handle's buffer too)
     const bool is420 = kind >= 0;                 // (or RGB)
     const size_t fb420 = is420 ? pk_frame_bytes(kind, g, e->fit) : 0;

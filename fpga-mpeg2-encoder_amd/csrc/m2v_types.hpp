@@ -71,8 +71,13 @@ struct FrameJob {           // one per frame of the chunk (device memory)
     int32_t        rhidx;   // ... and that of its reference frame in the previous step's list (where the neighbours' rows of it were received)
     uint32_t       q;       // the level (1..4) the frame's GOP is coded at: the handle's Q_LEVEL, or m2v_set_gop_levels' entry; k_assemble prints it
                             // in the slice headers, k_gop_judge raises it (k_mb takes the level from its launch's Geom::Q, not from here)
-    uint32_t       pad;     // (the structure is compared and copied as whole dwords: no unnamed padding)
+    uint32_t       pad;     // 0 in a call of one sequence.  In a batch (m2v_set_sequences) a flags word: kSeqFirst / kSeqLast, and from bit
+                            // kSeqOrdShift on the ordinal of the frame's sequence among those the chunk touches (k_seq_scan, k_assemble)
+                            // (the structure is compared and copied as whole dwords: no unnamed padding)
 };
+constexpr uint32_t kSeqFirst = 1u;      // the frame is the first of its sequence: the sequence headers stand in front of it
+constexpr uint32_t kSeqLast = 2u;       // ... the last: sequence_end_code and the final word's padding follow it
+constexpr int kSeqOrdShift = 2;
 
 // what k_scene_judge leaves per frame of a chunk, on the device and in pinned memory (option "scene_cut")
 struct SceneRec { unsigned long long diff; uint32_t flag; uint32_t pad; };

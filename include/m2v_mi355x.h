@@ -741,6 +741,43 @@ int m2v_frame_rate_code(uint32_t num, uint32_t den);
  * no handle */
 int m2v_time_code(uint32_t frame_rate_code, uint32_t n, uint8_t out[4]);
 
+/*
+ * A batch of sequences in one resident call: one stream per clip.  NOT the module's behaviour as a call - the module codes one sequence -
+ * but every stream in the output is the module's: with the setting, the bytes at [off[b], off[b + 1]) of d_out are the stream of clip b
+ * encoded alone by m2v_encode_resident with the same handle settings.
+ *
+ * m2v_set_sequences(e, frames_per_sequence, n): the frames of every resident call started afterwards are n clips, clip b being the
+ * frames [F_b, F_b + L_b) of the call with L_b = frames_per_sequence[b] and F_b the sum of the entries before it.  NULL or n == 0
+ * clears the setting.  The list is copied, sampled when a call starts (where the list of m2v_set_gop_starts is), stays until changed and
+ * survives m2v_reset.  Only while idle, M2V_E_STATE otherwise.  Every resident entry takes it - m2v_encode_resident,
+ * m2v_encode_resident420, m2v_encode_resident_rgb, blocking and as _begin / _end.  The call's nframes must equal the sum of the
+ * entries and no entry may be 0: otherwise the call answers M2V_E_PARAM before anything of the handle changes.  A list of ONE entry
+ * samples as "none": the plan, the launches, the kernel arguments' values and the stream are exactly those of a handle with nothing set.
+ *
+ * Clip b: its first frame is an I picture and frame number 0 - time codes, temporal_reference, the cadence pframes_count + 1, the
+ * ordinal a level schedule (m2v_set_gop_levels) goes by and m2v_picture_stat.frame all count from F_b.
+ * Layout: off[0] = 0, off[b + 1] = off[b] + len_b, where len_b follows the module's final-word rule applied to the clip alone:
+ * ((B + 4) / 32 + 1) * 32 for B bytes in front of its sequence_end_code (RTL:2621-2628, 2932-2937).  Every stream therefore starts on a
+ * 32-byte boundary; its sequence headers (with the description of m2v_set_stream_desc, and with repeat_headers in front of each of its
+ * later GOPs too) stand in front of its first frame, and its sequence_end_code and zero padding end it.  *out_bytes is off[n];
+ * cap < off[n] answers M2V_E_OVERFLOW as ever.
+ * It holds with every input format, a set frame size, "conformant", a level schedule, a stream description, any "batch_frames" and
+ * "split_streams" (a chunk may cut a clip anywhere, hold many clips, and a clip may span several chunks), "stats" (the records are those
+ * of each clip alone, in batch order) and m2v_set_recon_out (frame n OF THE CALL lands at n * frame_bytes).
+ *
+ * m2v_sequence_report: pops up to `max` records, oldest first, into out and returns how many it wrote; out == NULL returns how many are
+ * waiting.  After a call with the setting (or its _end) has returned, one record per clip is waiting: offset = off[b], bytes = len_b,
+ * first_frame = F_b, frames = L_b, gops = GOPs of the clip.  The device writes them into pinned memory with the scan of every chunk, they
+ * are complete where the control word is: no wait is added.  Dropped when the next call starts and at m2v_reset.
+ *
+ * Refusals (M2V_E_STATE, m2v_last_error names the reason) while a list is set: every m2v_push_* call that starts a sequence, every
+ * m2v_strip_* entry that starts something, and a resident call that starts with a list of two or more entries together with
+ * m2v_set_gop_starts, "scene_cut" or "gop_bytes_max".  Their host sides count one sequence: these are the follow-ups.
+ */
+int m2v_set_sequences(m2v_enc *e, const uint32_t *frames_per_sequence, size_t n);   /* NULL / 0: none */
+typedef struct m2v_sequence_stat { unsigned long long offset, bytes; uint32_t first_frame, frames; uint32_t gops, reserved; } m2v_sequence_stat;  /* 32 bytes */
+int m2v_sequence_report(m2v_enc *e, m2v_sequence_stat *out, size_t max);   /* returns the count, like m2v_gop_report */
+
 /* Per-kernel statistics of the last m2v_encode_resident call with "profile" = 1.
  * kernel: 0 = macroblock kernel on P frames, 1 = macroblock kernel on I frames,
  * 2 = strip mode's final assembly (k_strip_layout + k_strip_assemble), 3 = slice assembly (k_assemble), 4 = scans,
