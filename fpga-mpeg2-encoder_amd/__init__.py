@@ -45,6 +45,7 @@ EXPORTS = [
     "m2v_set_recon_out",
     "m2v_stream_desc_module", "m2v_set_stream_desc", "m2v_frame_rate_code", "m2v_time_code",
     "m2v_set_sequences", "m2v_sequence_report",
+    "m2v_mux_bound", "m2v_set_mux_out", "m2v_mux_report", "m2v_mux_device", "m2v_mux_scan_tile",
 ]
 
 # the 4:2:0 entry points (kept apart: tests/test_abi.py matches EXPORTS against names of letters and underscores only)
@@ -108,6 +109,31 @@ class SequenceStat(ctypes.Structure):
 # the same record as a numpy structured dtype (Mpeg2Encoder.sequence_report)
 SEQUENCE_STAT_DTYPE = np.dtype([("offset", "<u8"), ("bytes", "<u8"), ("first_frame", "<u4"), ("frames", "<u4"), ("gops", "<u4"),
                                 ("reserved", "<u4")])
+
+
+# m2v_mux_stat (include/m2v_mi355x.h): one container's record of m2v_set_mux_out / m2v_mux_device, 40 bytes (Mpeg2Encoder.mux_report)
+MUX_STAT_DTYPE = np.dtype([("es_offset", "<u8"), ("es_bytes", "<u8"), ("out_offset", "<u8"), ("out_bytes", "<u8"), ("pictures", "<u4"),
+                           ("status", "<i4")])
+MUX_KINDS = {"ts": 1, "ps": 2}                                   # M2V_MUX_*
+MUX_OK, MUX_SYNTAX, MUX_OVERFLOW = 0, -2, -3
+
+
+def _mux_kind(kind):
+    if isinstance(kind, str):
+        if kind not in MUX_KINDS:
+            raise ValueError("unknown container %r (one of %s)" % (kind, ", ".join(MUX_KINDS)))
+        return MUX_KINDS[kind]
+    return int(kind)
+
+
+def mux_bound(kind, es_bytes, pictures):
+    """m2v_mux_bound: bytes that always suffice for the container of a stream of es_bytes bytes and `pictures` pictures"""
+    return int(lib().m2v_mux_bound(_mux_kind(kind), int(es_bytes), int(pictures)))
+
+
+def mux_scan_tile():
+    """m2v_mux_scan_tile: the byte span after which the device muxer's start-code scan hands over to another workgroup"""
+    return int(lib().m2v_mux_scan_tile())
 
 
 def check_sequences(lengths, nframes):
@@ -344,6 +370,12 @@ def lib(debug=False):
             L.m2v_time_code.argtypes = [u32, u32, ctypes.POINTER(ctypes.c_uint8)]
             L.m2v_set_sequences.argtypes = [vp, vp, sz]
             L.m2v_sequence_report.argtypes = [vp, vp, sz]
+            L.m2v_mux_bound.restype = sz
+            L.m2v_mux_bound.argtypes = [ci, sz, sz]
+            L.m2v_set_mux_out.argtypes = [vp, ci, vp, sz]
+            L.m2v_mux_report.argtypes = [vp, vp, sz]
+            L.m2v_mux_device.argtypes = [vp, ci, vp, vp, vp, sz, vp, sz, vp]
+            L.m2v_mux_scan_tile.argtypes = []
         except AttributeError:
             # an OLDER build handed in through M2V_LIB for a same-box A/B (tools/ab.sh) may lack the newer entry points; the library of
             # this tree must have every one of them (tests/test_abi.py)
@@ -636,6 +668,57 @@ class Mpeg2Encoder:
         self._chk(self._L.m2v_set_recon_out(self._h, ptr or None, int(cap), _layout420(layout)), "m2v_set_recon_out")
         self._recon_out = (int(ptr), int(cap), layout) if ptr else None
 
+    def set_mux_out(self, kind, ptr=None, cap=0):
+        """m2v_set_mux_out: every resident call started from now on also leaves its stream as a transport ("ts") or program ("ps")
+        stream in the `cap` bytes of device memory at `ptr` - one container per clip of a batch, each on a 32-byte boundary;
+        mux_report says where.  kind = None or 0 clears the setting.  Idle handles only."""
+        k = _mux_kind(kind) if kind else 0
+        self._chk(self._L.m2v_set_mux_out(self._h, k, (ptr or None) if k else None, int(cap) if k else 0), "m2v_set_mux_out")
+        self._mux_out = (k, int(ptr), int(cap)) if k else None
+
+    def mux_report(self, max_records=None):
+        """Pops the waiting records of m2v_mux_report, oldest first, at most max_records of them: a numpy structured array of
+        MUX_STAT_DTYPE - one per container of the last resident call that had a container buffer set, or of the last mux_device."""
+        n = self._chk(self._L.m2v_mux_report(self._h, None, 0), "m2v_mux_report")
+        if max_records is not None:
+            n = min(n, int(max_records))
+        out = np.zeros(n, MUX_STAT_DTYPE)
+        if n:
+            n = self._chk(self._L.m2v_mux_report(self._h, out.ctypes.data, n), "m2v_mux_report")
+        return out[:n]
+
+    def mux_device(self, es, kind, segments=None, out=None, cap=None, pictures=None):
+        """m2v_mux_device: the elementary streams in the uint8 device tensor `es` - the whole tensor, or the (offset, bytes) pairs of
+        `segments`, at any byte alignment - as transport ("ts") or program ("ps") streams, muxed on the device.  Returns
+        (out, records): the containers in the one-dimensional uint8 tensor `out` on es's device (allocated from m2v_mux_bound when not
+        given; `pictures` = an upper bound of the pictures of all streams together, counted on the device when not given), of which at
+        most `cap` bytes are written (default: all of it), and their records (mux_report): container b is
+        out[out_offset : out_offset + out_bytes] where status is MUX_OK."""
+        import torch
+        if not isinstance(es, torch.Tensor) or es.dtype != torch.uint8 or es.dim() != 1 or not es.is_cuda or es.device.index != self.device:
+            raise ValueError("mux_device: a one-dimensional uint8 tensor on the handle's device is required")
+        if es.stride(0) != 1:
+            raise ValueError("mux_device: the tensor must be contiguous")
+        k = _mux_kind(kind)
+        seg = [(0, es.numel())] if segments is None else [(int(a), int(b)) for a, b in segments]
+        if not seg or any(a < 0 or b < 0 or a + b > es.numel() for a, b in seg):
+            raise ValueError("mux_device: a segment lies outside the tensor, or there is none")
+        if out is None:
+            if pictures is None and es.numel() >= 4:       # picture_start_codes anywhere in the tensor: an upper bound of the pictures
+                pictures = int(((es[:-3] == 0) & (es[1:-2] == 0) & (es[2:-1] == 1) & (es[3:] == 0)).sum().item())
+            total = sum(b for _, b in seg)
+            out = torch.empty(mux_bound(k, total, pictures or 1) + (32 + 1024) * len(seg), dtype=torch.uint8, device=es.device)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != es.device or out.dim() != 1 or out.stride(0) != 1:
+            raise ValueError("mux_device: out must be a contiguous one-dimensional uint8 tensor on the stream's device")
+        cap = out.numel() if cap is None else int(cap)
+        if cap < 0 or cap > out.numel():
+            raise ValueError("mux_device: cap is 0 .. out.numel()")
+        off = (ctypes.c_uint64 * len(seg))(*[a for a, _ in seg])
+        nb = (ctypes.c_uint64 * len(seg))(*[b for _, b in seg])
+        self._chk(self._L.m2v_mux_device(self._h, k, es.data_ptr(), off, nb, len(seg), out.data_ptr(), cap,
+                                         torch.cuda.current_stream(es.device).cuda_stream), "m2v_mux_device")
+        return out, self.mux_report()
+
     def set_stream_desc(self, desc):
         """m2v_set_stream_desc: what every sequence started from now on says about itself in its sequence headers and time codes - a
         StreamDesc (stream_desc builds one); None sets the module's values again.  Idle handles only; M2VError for a value out of
@@ -876,7 +959,7 @@ class Mpeg2Encoder:
         return out[:n]
 
     def encode_tensor(self, frames, pframes_count, order="rgb", matrix="bt601", out=None, header=None, stats=False, gop_levels=None,
-                      gop_bytes_max=0, gop_starts=None, scene_cut=0, recon=None, desc=None, sequences=None):
+                      gop_bytes_max=0, gop_starts=None, scene_cut=0, recon=None, desc=None, sequences=None, container=None):
         """One whole sequence from a torch image tensor on the handle's device, in one call: contiguous uint8 [N, H, W, 3] (order
         "rgb" / "bgr"), [N, H, W, 4] ("rgbx" / "bgrx" / "xrgb" / "xbgr") or [N, 3, H, W] ("rgb": planar).  Runs
         m2v_encode_resident_rgb on torch's current stream and returns the stream bytes as a uint8 device tensor (a view of `out` when
@@ -900,7 +983,11 @@ class Mpeg2Encoder:
         is back afterwards).  The matrix does not set it: matrix="bt709" goes with desc=stream_desc(colour="bt709").
         sequences = a list of frame counts that add up to N (ValueError otherwise): the frames are that many clips, each coded as a
         stream of its own, one behind the other on 32-byte boundaries in the tensor returned (set_sequences for the duration of the
-        call; the handle's own setting is back afterwards).  sequence_report() says where each one is; encode_batch does both."""
+        call; the handle's own setting is back afterwards).  sequence_report() says where each one is; encode_batch does both.
+        container = "ts" or "ps": the first element returned is the transport or program stream, muxed on the device, instead of the
+        elementary stream (set_mux_out for the duration of the call; the handle's own setting is back afterwards): the bytes of
+        container.mux_ts / mux_ps of the elementary stream.  With sequences the tensor holds one container per clip and mux_report()
+        says where each one is; encode_batch does both.  M2VError if the muxer refuses the stream."""
         import torch
         if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4:
             raise ValueError("encode_tensor: a uint8 tensor of 4 dimensions is required")
@@ -936,6 +1023,11 @@ class Mpeg2Encoder:
         elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != frames.device or not out.is_contiguous() or out.dim() != 1:
             raise ValueError("encode_tensor: out must be a contiguous one-dimensional uint8 tensor on the frames' device")
         rec = torch.empty((N, frame_bytes(W, H, recon)), dtype=torch.uint8, device=frames.device) if recon is not None else None
+        mux = None
+        if container is not None:
+            nclips = len(sequences or ()) or 1
+            mux = torch.empty(mux_bound(container, out.numel(), N) + 32 * nclips, dtype=torch.uint8, device=frames.device)
+        mux_before = getattr(self, "_mux_out", None)
         recon_before = getattr(self, "_recon_out", None)
         before = self.frame_size
         fit = bool(W % 16 or H % 16)
@@ -963,12 +1055,16 @@ class Mpeg2Encoder:
                 self.set_option("scene_cut", scene_cut)
             if rec is not None:
                 self.set_recon_out(rec.data_ptr(), rec.numel(), recon)
+            if mux is not None:
+                self.set_mux_out(container, mux.data_ptr(), mux.numel())
             nb = self.encode_resident_rgb(frames.data_ptr(), N, out.data_ptr(), out.numel(), xs, ys, pframes_count, layout, matrix,
                                           stream=torch.cuda.current_stream(frames.device).cuda_stream)
             records = self.picture_stats() if stats else None
         finally:
             if rec is not None:
                 self.set_recon_out(*(recon_before or (None, 0)))
+            if mux is not None:
+                self.set_mux_out(*(mux_before or (None,)))
             if fit or before:
                 self.set_frame_size(*(before or (0, 0, 0)))
             if stats and not stats_before:
@@ -985,14 +1081,26 @@ class Mpeg2Encoder:
                 self.set_stream_desc(desc_before)
             if sequences is not None:
                 self.set_sequences(seq_before)
-        res = (out[:nb],) + ((records,) if stats else ()) + ((rec,) if rec is not None else ())
+        first = out[:nb]
+        if mux is not None:
+            r = self.mux_report()
+            if len(r) == 0 or (r["status"] != MUX_OK).any():
+                raise M2VError("encode_tensor: the muxer refused the stream (status %r)" % (r["status"].tolist(),))
+            if sequences is None or len(sequences) < 2:
+                first = mux[:int(r["out_bytes"][0])]
+            else:
+                self._mux_records = r
+                first = mux[:int(r["out_offset"][-1] + r["out_bytes"][-1])]
+        res = (first,) + ((records,) if stats else ()) + ((rec,) if rec is not None else ())
         return res if len(res) > 1 else res[0]
 
     def encode_batch(self, frames, pframes_count, lengths=None, **kw):
         """A batch of clips in one call, one stream per clip: a uint8 tensor [B, N, H, W, C] (or [B, N, 3, H, W]) on the handle's
         device - B clips of N frames - or a 4-D tensor of frames as encode_tensor takes it with lengths = the clips' frame counts.
         Returns (stream_tensor, offsets): clip b's stream is stream_tensor[offsets[b]:offsets[b + 1]], offsets a list of B + 1 ints,
-        every one a multiple of 32.  Keywords as encode_tensor's; with stats or recon the first element of its tuple is the stream."""
+        every one a multiple of 32.  Keywords as encode_tensor's; with stats or recon the first element of its tuple is the stream.
+        With container = "ts" or "ps" the tensor holds the clips' containers instead and the second element is a list of
+        (offset, bytes) per clip: clip b's container is stream_tensor[offset:offset + bytes], every offset a multiple of 32."""
         import torch
         if not isinstance(frames, torch.Tensor) or frames.dim() not in (4, 5):
             raise ValueError("encode_batch: a uint8 tensor of 4 or 5 dimensions is required")
@@ -1008,7 +1116,10 @@ class Mpeg2Encoder:
         lengths = check_sequences(lengths, frames.shape[0])
         res = self.encode_tensor(frames, pframes_count, sequences=lengths, **kw)
         stream = res[0] if isinstance(res, tuple) else res
-        if len(lengths) < 2:             # (a list of one entry is no batch: one stream, from 0 to its end)
+        if kw.get("container") is not None:
+            offsets = [(0, int(stream.numel()))] if len(lengths) < 2 else [(int(o), int(b)) for o, b in zip(self._mux_records["out_offset"],
+                                                                                                          self._mux_records["out_bytes"])]
+        elif len(lengths) < 2:           # (a list of one entry is no batch: one stream, from 0 to its end)
             offsets = [0, int(stream.numel())]
         else:
             rec = self.sequence_report()

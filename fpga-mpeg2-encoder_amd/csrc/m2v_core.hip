@@ -568,6 +568,7 @@ void m2v_destroy(m2v_enc *e)
     e->d_gop.release();
     scene_release(e);
     seq_release(e);
+    mux_release(e);
     if (e->ev_gop) (void)hipEventDestroy(e->ev_gop);
     if (e->h_redo) (void)hipHostFree(e->h_redo);
     for (auto p : e->rec_pool) (void)hipFree(p);
@@ -639,6 +640,7 @@ int m2v_reset(m2v_enc *e)
     gop_drop(e);
     scene_drop(e);
     seq_drop(e);
+    mux_drop(e);
     // a strip sequence abandoned between m2v_strip_begin and m2v_strip_finish: back to the full frame
     e->strip_active = false;
     e->strip_inflight = false;

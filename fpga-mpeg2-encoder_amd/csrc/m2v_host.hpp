@@ -24,6 +24,9 @@
 //   m2v_sequences.hip m2v_set_sequences: a batch of sequences in one resident call - the setting, what a call samples from it, the
 //                     refusals, the records' way to the host and m2v_sequence_report (the scan that places the streams, k_seq_scan in
 //                     m2v_seq_kernels.hpp, is launched from m2v_launch.hip)
+//   m2v_mux.hip       m2v_set_mux_out / m2v_mux_device: transport or program stream out of the stream in HBM.  Its three kernels touch no
+//                     device global and nothing of m2v_kernels.hpp, so they live in their own unit with their launches (m2v_mux_kernels.hpp
+//                     holds the arithmetic, for the device and the host alike)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -333,6 +336,18 @@ struct m2v_enc {
     bool seq_pending = false;             // a batch is in flight or has just completed: its records have not moved to seq_q yet
     std::deque<m2v_sequence_stat> seq_q;  // the last call's records nobody has popped yet
 
+    // a container out of the stream (m2v_mux.hip): the setting (kind 0: off), what the resident call in progress sampled from it when it
+    // started, the muxer's work buffers - the streams' state, their start-code events, the picture tables; no recording references
+    // them - and the records: written into pinned memory by k_mux_plan itself, complete where the control word is
+    struct MuxDst { int kind = 0; uint8_t *p = nullptr; size_t cap = 0; } mux_out, seq_mux;
+    DevBuf<uint8_t> d_mux_st, d_mux_pic;
+    DevBuf<unsigned long long> d_mux_ev;
+    uint8_t *h_mux = nullptr;             // pinned: the streams' initial state on its way up, then the records
+    size_t h_mux_cap = 0;
+    size_t mux_n = 0;                     // streams of the last mux
+    bool mux_pending = false;             // a resident call with a container is in flight: its records have not moved to mux_q yet
+    std::deque<m2v_mux_stat> mux_q;       // the last mux's records nobody has popped yet
+
     // debug bookkeeping of the last resident encode
     size_t dbg_frames = 0;
     std::vector<int> dbg_rec_slot;
@@ -443,6 +458,10 @@ inline bool strip_refuses(m2v_enc *e, const char *fn)
     if (size_refuses(e, fn, kNoStrips)) return true;
     if (!e->sequences.empty()) {
         e->set_err("%s: a batch of sequences is set (m2v_set_sequences): the strip assembly writes one stream", fn);
+        return true;
+    }
+    if (e->mux_out.kind) {
+        e->set_err("%s: a container buffer is set (m2v_set_mux_out): the muxer follows the resident entries' stream", fn);
         return true;
     }
     if (e->recon_out.p) {
@@ -590,6 +609,20 @@ bool seq_refuses(m2v_enc *e, const char *fn);
 void seq_collect(m2v_enc *e, bool ok);
 void seq_drop(m2v_enc *e);
 void seq_release(m2v_enc *e);
+
+// ---- m2v_mux.hip: m2v_set_mux_out ----
+// the start of a resident call samples the setting (where sample_recon_out is called)
+void sample_mux_out(m2v_enc *e);
+// a resident call is about to start: true = refused (M2V_E_PARAM) because a container is set and the batch has more clips than a launch takes
+bool mux_too_many(m2v_enc *e, const char *fn);
+// the port entries that start a sequence: true = refused (M2V_E_STATE) because a buffer is set
+bool mux_refuses(m2v_enc *e, const char *fn);
+// behind the last chunk's assembly on s, in front of the control word's copy: the three kernels over the call's stream(s) in d_out
+void mux_resident(m2v_enc *e, hipStream_t s, const uint8_t *d_out, size_t cap, size_t nframes);
+// a completed call's records (its stream has been waited for) to the handle's queue
+void mux_collect(m2v_enc *e);
+void mux_drop(m2v_enc *e);
+void mux_release(m2v_enc *e);
 
 // ---- m2v_launch.hip: everything that touches device code ----
 // The constant tables live in each device's copy of the code object: uploaded once per device, whichever thread creates the first

@@ -700,7 +700,7 @@ static int push_beats_impl(m2v_enc *e, void *argp)
         return M2V_OK;
     }
     if (e->state == m2v_enc::IDLE) {
-        if (cap_refuses(e, "m2v_push_beats") || cut_refuses(e, "m2v_push_beats") || seq_refuses(e, "m2v_push_beats") || recon_refuses(e, "m2v_push_beats")) return M2V_E_STATE;
+        if (cap_refuses(e, "m2v_push_beats") || cut_refuses(e, "m2v_push_beats") || seq_refuses(e, "m2v_push_beats") || recon_refuses(e, "m2v_push_beats") || mux_refuses(e, "m2v_push_beats")) return M2V_E_STATE;
         start_sequence(e, a->xs, a->ys, a->pf);
     }
     const Geom &g = e->g;
@@ -854,7 +854,7 @@ static int push_frames_impl(m2v_enc *e, void *argp)
     };
     if (e->state == m2v_enc::ENDED || a->n == 0) { settle_deferred(); return M2V_OK; }
     if (e->state == m2v_enc::IDLE) {
-        if (cap_refuses(e, "m2v_push_frames") || cut_refuses(e, "m2v_push_frames") || seq_refuses(e, "m2v_push_frames") || recon_refuses(e, "m2v_push_frames")) { settle_deferred(); return M2V_E_STATE; }
+        if (cap_refuses(e, "m2v_push_frames") || cut_refuses(e, "m2v_push_frames") || seq_refuses(e, "m2v_push_frames") || recon_refuses(e, "m2v_push_frames") || mux_refuses(e, "m2v_push_frames")) { settle_deferred(); return M2V_E_STATE; }
         if (!sample_frame_size(e, "m2v_push_frames", a->xs, a->ys)) { settle_deferred(); return M2V_E_PARAM; }
         start_sequence(e, a->xs, a->ys, a->pf);
     }

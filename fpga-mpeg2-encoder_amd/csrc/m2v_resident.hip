@@ -21,6 +21,7 @@ static int resident_end_impl(m2v_enc *e, void *argp)
     gop_collect(e, e->st());
     scene_collect(e, e->st());
     seq_collect(e, !e->st().h_ctl->overflow);
+    mux_collect(e);
     if (e->st().h_ctl->overflow) { e->set_err("output buffer too small"); return M2V_E_OVERFLOW; }
     if (bytes) *bytes = (size_t)e->st().h_ctl->total_bytes;
     return M2V_OK;
@@ -36,12 +37,14 @@ static int resident_impl(m2v_enc *e, void *argp)
     gop_drop(e);
     scene_drop(e);
     seq_drop(e);
+    mux_drop(e);
     if (a->n == 0) {                                    // no beat: the sequence never starts
         if (a->bytes) *a->bytes = 0;
         e->resident_empty = a->async;                   // only _begin leaves an _end to answer
         return M2V_OK;
     }
     if (layout_refuses_cap(e, "m2v_encode_resident")) return M2V_E_STATE;
+    if (mux_too_many(e, "m2v_encode_resident")) return M2V_E_PARAM;
     if (recon_overflows(e, "m2v_encode_resident", a->xs, a->ys, a->n)) return M2V_E_OVERFLOW;      // (nothing of the handle has changed)
     if (!sample_frame_size(e, "m2v_encode_resident", a->xs, a->ys)) return M2V_E_PARAM;
     if (e->gop_bytes_max && (size_t)(a->pf & 0xFFu) + 1 > e->batch_frames) {
@@ -53,6 +56,7 @@ static int resident_impl(m2v_enc *e, void *argp)
     e->g = make_geom(e, a->xs, a->ys);
     e->pframes = a->pf & 0xFFu;
     sample_recon_out(e, a->xs, a->ys);
+    sample_mux_out(e);
     sample_gop_levels(e, true);
     sample_gop_starts(e, true);
     sample_stream_desc(e);
@@ -93,6 +97,7 @@ static int resident_impl(m2v_enc *e, void *argp)
         encode_chunk(e, s, frames, nf, first, last, g.ysz / 4, a->d_out, /*advance=*/k > 0);
         if (!last) { HIPCHK(hipStreamSynchronize(s)); stats_collect(e, e->st()); gop_collect(e, e->st()); scene_collect(e, e->st()); }    // the per-chunk work buffers are reused
     }
+    mux_resident(e, s, a->d_out, a->cap, a->n);         // m2v_set_mux_out: the container out of the finished stream (nothing with no buffer set)
     HIPCHK(hipMemcpyAsync(e->st().h_ctl, e->d_ctl.p, sizeof(StreamCtl), hipMemcpyDeviceToHost, s));
     e->resident_inflight = true;
     e->resident_stream = s;

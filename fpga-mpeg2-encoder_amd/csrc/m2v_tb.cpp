@@ -1,6 +1,6 @@
 // m2v_tb — file-to-file driver over the C-ABI; the counterpart of SIM/tb_mpeg2encoder.v.
 //
-//   m2v_tb [-XL n] [-YL n] [-VL n] [-Q n] [-p pframes] [-d device] [-bubbles] [-conformant] [-ps] [-ts]
+//   m2v_tb [-XL n] [-YL n] [-VL n] [-Q n] [-p pframes] [-d device] [-bubbles] [-conformant] [-ps] [-ts] [-devmux]
 //          [-i420 | -yv12 | -nv12 | -nv21 | -rgb24 | -bgr24 | -rgbx | -bgrx | -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f]
 //          [-pad | -truesize] [-stats] [-qgop q0,q1,...] [-istart n0,n1,...] [-scenecut T] [-recon out.yuv [-reconfmt i420|yv12|nv12|nv21]]
 //          [-fps N/D] [-aspect 1:1|4:3|16:9|2.21:1] [-bitrate B] [-vbv K] [-colour bt601|bt709|P,T,M] [-repeat-headers]
@@ -36,7 +36,8 @@
 // GOP after the first, so that a player can start there.  A bad value ends with the usage text and exit status 2 before the device is touched.
 // -conformant switches the encoder's option "conformant" on (ISO reconstruction loop; NOT byte-identical to the RTL).
 // -ps / -ts additionally write out.m2v.mpg / out.m2v.ts: the same elementary stream in an MPEG-2 program / transport
-// stream (include/m2v_container.h), so the result plays in an ordinary player.
+// stream (include/m2v_container.h), so the result plays in an ordinary player.  -devmux: those files come from the device muxer
+// (m2v_mux_device over the stream in device memory) instead of the CPU's - the same bytes.
 //
 // Like the testbench it encodes the listed videos back to back on ONE encoder instance (TB:150:
 // "verify the module can end a sequence and start the next"), pushes only the complete frames of
@@ -59,7 +60,7 @@
 int main(int argc, char **argv)
 {
     int XL = 7, YL = 6, VL = 3, Q = 2, pf = 23, dev = 0, bubbles = 0, conformant = 0, want_ps = 0, want_ts = 0, layout420 = -1, layouts = 0, rgb = -1, matrix = M2V_RGB_BT601,
-        bad_matrix = 0, pad = 0, truesize = 0, stats = 0, reconfmt = M2V_420_I420;
+        bad_matrix = 0, pad = 0, truesize = 0, stats = 0, reconfmt = M2V_420_I420, devmux = 0;
     const char *recon = nullptr;
     long long scenecut = 0;
     std::vector<uint8_t> qgop;
@@ -74,6 +75,7 @@ int main(int argc, char **argv)
         if (!strcmp(argv[i], "-conformant")) { conformant = 1; continue; }
         if (!strcmp(argv[i], "-ps")) { want_ps = 1; continue; }
         if (!strcmp(argv[i], "-ts")) { want_ts = 1; continue; }
+        if (!strcmp(argv[i], "-devmux")) { devmux = 1; continue; }
         if (!strcmp(argv[i], "-pad")) { pad = 1; continue; }
         if (!strcmp(argv[i], "-stats")) { stats = 1; continue; }
         if (!strcmp(argv[i], "-truesize")) { pad = truesize = 1; continue; }
@@ -169,7 +171,7 @@ int main(int argc, char **argv)
     if ((argc - i) < 4 || (argc - i) % 4 || layouts > 1 || bad_matrix || bad_desc || ((layouts || pad || scenecut) && bubbles)) {          // (there are no 4:2:0 or RGB beats)
         fprintf(stderr, "usage: %s [-XL n] [-YL n] [-VL n] [-Q n] [-p pframes] [-d dev] [-i420 | -yv12 | -nv12 | -nv21 | -rgb24 | -bgr24 | -rgbx | -bgrx |"
                         " -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f] [-pad | -truesize] [-stats] [-qgop q0,q1,...] [-istart n0,n1,...] [-scenecut T] [-recon out.yuv [-reconfmt i420|yv12|nv12|nv21]]"
-                        " [-fps N/D] [-aspect 1:1|4:3|16:9|2.21:1] [-bitrate bit/s] [-vbv units of 16384 bits] [-colour bt601|bt709|P,T,M] [-repeat-headers]"
+                        " [-fps N/D] [-aspect 1:1|4:3|16:9|2.21:1] [-bitrate bit/s] [-vbv units of 16384 bits] [-colour bt601|bt709|P,T,M] [-repeat-headers] [-ps] [-ts] [-devmux]"
                         " in.yuv W H out.m2v ...\n"
                         "  -fps takes a frame rate of ISO/IEC 13818-2 table 6-4: 24000/1001, 24, 25, 30000/1001, 30, 50, 60000/1001, 60\n"
                         "  -scenecut T stages every file's frames in device memory and encodes them with one resident call (the detector needs it)\n", argv[0]);
@@ -312,10 +314,32 @@ int main(int argc, char **argv)
         for (int kind = 0; kind < 2; ++kind) {
             if (!(kind ? want_ts : want_ps) || es.empty()) continue;
             size_t need = 0;
-            int r = kind ? m2vc_mux_ts(es.data(), es.size(), nullptr, 0, &need) : m2vc_mux_ps(es.data(), es.size(), nullptr, 0, &need);
-            std::vector<uint8_t> mux(need);
-            if (r == 0) r = kind ? m2vc_mux_ts(es.data(), es.size(), mux.data(), mux.size(), &need)
-                                 : m2vc_mux_ps(es.data(), es.size(), mux.data(), mux.size(), &need);
+            int r = 0;
+            std::vector<uint8_t> mux;
+            if (devmux) {
+                // the stream back in device memory, muxed there (a resident caller sets m2v_set_mux_out and never leaves the device)
+                const uint64_t off = 0, nb = es.size();
+                const size_t room = m2v_mux_bound(kind ? M2V_MUX_TS : M2V_MUX_PS, es.size(), frames);
+                void *d_es = nullptr, *d_mux = nullptr;
+                m2v_mux_stat rec{};
+                if (hipSetDevice(dev) != hipSuccess || hipMalloc(&d_es, es.size()) != hipSuccess || hipMalloc(&d_mux, room) != hipSuccess ||
+                    hipMemcpy(d_es, es.data(), es.size(), hipMemcpyHostToDevice) != hipSuccess) { fprintf(stderr, "*** staging the stream in device memory failed\n"); return 1; }
+                if (m2v_mux_device(e, kind ? M2V_MUX_TS : M2V_MUX_PS, d_es, &off, &nb, 1, d_mux, room, nullptr) < 0 || m2v_mux_report(e, &rec, 1) != 1) {
+                    fprintf(stderr, "*** m2v_mux_device: %s\n", m2v_last_error(e));
+                    return 1;
+                }
+                r = rec.status;
+                need = (size_t)rec.out_bytes;
+                mux.resize(need);
+                if (r == 0 && hipMemcpy(mux.data(), d_mux, need, hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "*** read-back failed\n"); return 1; }
+                (void)hipFree(d_es);
+                (void)hipFree(d_mux);
+            } else {
+                r = kind ? m2vc_mux_ts(es.data(), es.size(), nullptr, 0, &need) : m2vc_mux_ps(es.data(), es.size(), nullptr, 0, &need);
+                mux.resize(need);
+                if (r == 0) r = kind ? m2vc_mux_ts(es.data(), es.size(), mux.data(), mux.size(), &need)
+                                     : m2vc_mux_ps(es.data(), es.size(), mux.data(), mux.size(), &need);
+            }
             if (r < 0) { fprintf(stderr, "*** multiplexer failed (%d)\n", r); return 1; }
             const std::string name = std::string(out) + (kind ? ".ts" : ".mpg");
             FILE *fm = fopen(name.c_str(), "wb");

@@ -778,6 +778,65 @@ int m2v_set_sequences(m2v_enc *e, const uint32_t *frames_per_sequence, size_t n)
 typedef struct m2v_sequence_stat { unsigned long long offset, bytes; uint32_t first_frame, frames; uint32_t gops, reserved; } m2v_sequence_stat;  /* 32 bytes */
 int m2v_sequence_report(m2v_enc *e, m2v_sequence_stat *out, size_t max);   /* returns the count, like m2v_gop_report */
 
+/*
+ * Transport and program stream out of the resident call, muxed on the device.  The bytes are exactly those m2vc_mux_ts / m2vc_mux_ps
+ * (include/m2v_container.h) return for the same elementary stream - csrc/m2v_container.cpp is the specification: the zero padding after
+ * sequence_end_code is dropped, the sequence headers travel in picture 0's PES packet, a repeated sequence header opens its GOP's access
+ * unit, PTS = pts0 + i * 90000 * den / num with the frame rate the stream states, the same rates, PAT / PMT, PCR, stuffing, packs, SCR and
+ * system header.  File playback only, as there: nothing is paced against the T-STD / P-STD buffer models.
+ *
+ * m2v_set_mux_out(e, kind, d_dst, cap): every resident call started afterwards (m2v_encode_resident, m2v_encode_resident420,
+ * m2v_encode_resident_rgb, each also as _begin / _end) also leaves its stream as a container of `kind` in the `cap` bytes of device memory
+ * at d_dst (no alignment needed).  Three kernels follow the last chunk's assembly on the call's stream and take the stream's length
+ * from the device: no wait is added, and the data is complete where the stream is - when the blocking call or _end has returned, and for
+ * work queued on that stream afterwards.  The elementary stream in d_out is byte for byte what it is without the setting, and with
+ * nothing set the launches are exactly those of a handle that never heard of it.  With m2v_set_sequences there is one container per clip:
+ * container 0 starts at d_dst, container b at the next multiple of 32 bytes after the end of container b - 1; the gaps are not touched.
+ * Nothing past cap is ever written, and a stream whose status is not M2V_MUX_OK writes nothing at all.
+ * It holds with a frame size, "conformant", levels per GOP, "gop_bytes_max" (the mux runs once, after the final redo), GOP starts,
+ * "scene_cut", "stats", m2v_set_recon_out, a stream description (its frame_rate_code sets the PTS step; with repeat_headers a player
+ * can join the transport stream at any GOP), any "batch_frames", "split_streams" and input format.
+ * The setting is sampled when a call starts, stays until changed and survives m2v_reset; kind = M2V_MUX_NONE clears it.  Only while idle,
+ * M2V_E_STATE otherwise; an unknown kind, or a kind with d_dst == NULL, is M2V_E_PARAM.  While a buffer is set every m2v_push_* call that
+ * starts a sequence and every m2v_strip_* entry that starts something answers M2V_E_STATE - the rule m2v_set_recon_out follows - and a
+ * batch of more than 65535 clips answers M2V_E_PARAM when the call starts.
+ *
+ * m2v_mux_report: pops up to `max` records, oldest first, into out and returns how many it wrote; out == NULL returns how many are
+ * waiting.  After a call with the setting (or its _end) or m2v_mux_device has returned, one record per stream is waiting: where the
+ * elementary stream is in its buffer, where the container is in d_dst (out_bytes = 0 unless status is M2V_MUX_OK), the pictures, and
+ * status = M2V_MUX_OK, M2V_MUX_SYNTAX (not a stream as this encoder writes it: it does not begin with a sequence header, a picture is
+ * neither I nor P, something other than zeros follows the end code, the frame_rate_code is reserved, there is no picture) or
+ * M2V_MUX_OVERFLOW (the container does not fit what is left of cap: it takes no room, and a later one of the call that fits is
+ * written where it would have started - or the elementary stream itself overflowed d_out: then every record says so).  The device writes them into pinned memory; no wait is added.  Dropped when the next
+ * resident call starts, at the next m2v_mux_device and at m2v_reset.
+ *
+ * m2v_mux_device: the same kernels over nstreams streams already in device memory - stream i is the es_bytes[i] bytes at
+ * d_es + es_off[i], at any byte alignment (port-path output, a strip result, a splice); es_off / es_bytes are host arrays.  The call
+ * blocks (hip_stream or the handle's stream is waited for), the records come through m2v_mux_report, and the function's own answer is
+ * M2V_OK whenever the kernels ran.  M2V_E_STATE while a sequence is in progress or a resident call in flight; at most 65535 streams.
+ *
+ * m2v_mux_bound(kind, es_bytes, pictures): a capacity that always suffices for a stream of es_bytes bytes (padding included) and
+ * `pictures` pictures; 0 for an unknown kind.  From the packet geometry:
+ *   TS  a picture of b bytes is a PES packet of 14 + b bytes; its first transport packet carries 176 of them behind the PCR, every other
+ *       one 184: 1 + ceil((b - 162) / 184) <= b / 184 + 2 packets.  A PAT / PMT pair precedes a picture at most: 2 more.  Over all
+ *       pictures: 188 * (es_bytes / 184 + 4 * pictures + 1).
+ *   PS  a picture's first pack spends 28 bytes on pack and PES header with PTS, every further one (each carries 2025 bytes) 23:
+ *       at most 28 + 23 * (b / 2025 + 1) a picture; 15 for the system header and 4 for MPEG_program_end_code once:
+ *       es_bytes + 23 * (es_bytes / 2025) + 51 * pictures + 19.
+ * For a batch add 31 bytes per clip for the 32-byte boundaries.
+ *
+ * m2v_mux_scan_tile: the byte span after which the start-code scan hands over to another workgroup (a test aims headers at its multiples).
+ */
+enum { M2V_MUX_NONE = 0, M2V_MUX_TS = 1, M2V_MUX_PS = 2 };
+enum { M2V_MUX_OK = 0, M2V_MUX_SYNTAX = -2, M2V_MUX_OVERFLOW = -3 };      /* the values of M2VC_E_SYNTAX / M2VC_E_OVERFLOW */
+typedef struct { uint64_t es_offset, es_bytes, out_offset, out_bytes; uint32_t pictures; int32_t status; } m2v_mux_stat;   /* 40 bytes */
+size_t m2v_mux_bound(int kind, size_t es_bytes, size_t pictures);
+int m2v_set_mux_out(m2v_enc *e, int kind, void *d_dst, size_t cap);
+int m2v_mux_report(m2v_enc *e, m2v_mux_stat *out, size_t max);   /* returns the count, like m2v_sequence_report */
+int m2v_mux_device(m2v_enc *e, int kind, const void *d_es, const uint64_t *es_off, const uint64_t *es_bytes, size_t nstreams, void *d_dst,
+                   size_t cap, void *hip_stream);
+int m2v_mux_scan_tile(void);
+
 /* Per-kernel statistics of the last m2v_encode_resident call with "profile" = 1.
  * kernel: 0 = macroblock kernel on P frames, 1 = macroblock kernel on I frames,
  * 2 = strip mode's final assembly (k_strip_layout + k_strip_assemble), 3 = slice assembly (k_assemble), 4 = scans,
