@@ -854,8 +854,9 @@ static int push_frames_impl(m2v_enc *e, void *argp)
     };
     if (e->state == m2v_enc::ENDED || a->n == 0) { settle_deferred(); return M2V_OK; }
     if (e->state == m2v_enc::IDLE) {
-        if (cap_refuses(e, "m2v_push_frames") || cut_refuses(e, "m2v_push_frames") || seq_refuses(e, "m2v_push_frames") || recon_refuses(e, "m2v_push_frames") || mux_refuses(e, "m2v_push_frames")) { settle_deferred(); return M2V_E_STATE; }
-        if (!sample_frame_size(e, "m2v_push_frames", a->xs, a->ys)) { settle_deferred(); return M2V_E_PARAM; }
+        const char *fn = a->kind < 0 ? "m2v_push_frames" : a->kind >= kPkRgb ? "m2v_push_rgb" : "m2v_push_frames420";      // (the entry a refusal names)
+        if (cap_refuses(e, fn) || cut_refuses(e, fn) || seq_refuses(e, fn) || recon_refuses(e, fn) || mux_refuses(e, fn)) { settle_deferred(); return M2V_E_STATE; }
+        if (!sample_frame_size(e, fn, a->xs, a->ys)) { settle_deferred(); return M2V_E_PARAM; }
         start_sequence(e, a->xs, a->ys, a->pf);
     }
     const Geom &g = e->g;

@@ -31,7 +31,9 @@ static int resident_impl(m2v_enc *e, void *argp)
 {
     auto *a = (ResidentArgs *)argp;
     if (e->state != m2v_enc::IDLE || e->strip_active || e->resident_inflight || e->strip_inflight) { e->set_err("m2v_encode_resident: encoder busy"); return M2V_E_STATE; }
-    if (const int r = seq_check(e, "m2v_encode_resident", a->n)) return r;      // (nothing of the handle has changed)
+    // (the entry a refusal names: the _begin halves share the prefix)
+    const char *fn = a->kind < 0 ? "m2v_encode_resident" : a->kind >= kPkRgb ? "m2v_encode_resident_rgb" : "m2v_encode_resident420";
+    if (const int r = seq_check(e, fn, a->n)) return r;      // (nothing of the handle has changed)
     e->resident_empty = false;
     stats_drop(e);                                      // (the previous sequence's unread picture records)
     gop_drop(e);
@@ -43,10 +45,10 @@ static int resident_impl(m2v_enc *e, void *argp)
         e->resident_empty = a->async;                   // only _begin leaves an _end to answer
         return M2V_OK;
     }
-    if (layout_refuses_cap(e, "m2v_encode_resident")) return M2V_E_STATE;
-    if (mux_too_many(e, "m2v_encode_resident")) return M2V_E_PARAM;
-    if (recon_overflows(e, "m2v_encode_resident", a->xs, a->ys, a->n)) return M2V_E_OVERFLOW;      // (nothing of the handle has changed)
-    if (!sample_frame_size(e, "m2v_encode_resident", a->xs, a->ys)) return M2V_E_PARAM;
+    if (layout_refuses_cap(e, fn)) return M2V_E_STATE;
+    if (mux_too_many(e, fn)) return M2V_E_PARAM;
+    if (recon_overflows(e, fn, a->xs, a->ys, a->n)) return M2V_E_OVERFLOW;      // (nothing of the handle has changed)
+    if (!sample_frame_size(e, fn, a->xs, a->ys)) return M2V_E_PARAM;
     if (e->gop_bytes_max && (size_t)(a->pf & 0xFFu) + 1 > e->batch_frames) {
         e->set_err("m2v_encode_resident: option \"gop_bytes_max\" needs whole GOPs in a chunk: pframes_count + 1 = %u is more than batch_frames = %zu",
                    (a->pf & 0xFFu) + 1u, e->batch_frames);

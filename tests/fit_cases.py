@@ -31,10 +31,11 @@ def _base(w, h, n, seed, noise):
     return a
 
 
-def source(w, h, n, kind, seed=0, noise=False):
-    """n source frames of w x h in `kind`, [n, frame bytes] uint8: the three planes of _base as Y, U, V (chroma: every second sample of
-    every second row) or as R, G, B; the ignored byte of the 32-bit layouts is noise"""
-    p = _base(w, h, n, seed, noise)
+def source(w, h, n, kind, seed=0, noise=False, base=None):
+    """n source frames of w x h in `kind`, [n, frame bytes] uint8: the three planes of _base (or of `base` [n, 3, h, w]) as Y, U, V
+    (chroma: every second sample of every second row) or as R, G, B; the ignored byte of the 32-bit layouts is noise"""
+    p = _base(w, h, n, seed, noise) if base is None else base
+    assert p.shape == (n, 3, h, w)
     if kind in ("444", "rgbp"):
         return np.ascontiguousarray(p).reshape(n, -1)
     if kind in KINDS_420:
