@@ -5,6 +5,7 @@ C-ABI of include/m2v_mi355x.h) through ctypes and mirrors the module's port cont
 (parameters XL/YL/VECTOR_LEVEL/Q_LEVEL; beats in; 32-byte stream words out).  There is no CPU
 fallback: without the built library or without a GPU every entry point raises.
 """
+import contextlib
 import ctypes
 import os
 import sys
@@ -215,15 +216,21 @@ def stream_desc(fps=None, aspect=None, bit_rate=None, vbv_bits=None, video_forma
     return d
 
 
+def _uint_list(values, ctype, error):
+    """`values` (None: none) for the ABI: (the list of ints, a ctypes array of ctype - None for an empty list, which clears a setting);
+    raises `error` for an entry that does not fit ctype"""
+    v = [] if values is None else [int(x) for x in values]
+    if any(x < 0 or x >> (8 * ctypes.sizeof(ctype)) for x in v):
+        raise error
+    return v, (ctype * len(v))(*v) if v else None
+
+
 def gop_layout(pframes_count, starts, nframes):
     """m2v_gop_layout: (the M2V_GOP_* reasons of each of nframes frames as a uint8 array - non-zero where a GOP starts -, the number
     of GOPs) for pframes_count and the list `starts` (strictly ascending, ValueError otherwise).  Plain arithmetic, no GPU."""
-    st = [] if starts is None else [int(v) for v in starts]
-    if any(v < 0 or v > 0xFFFFFFFF for v in st):
-        raise ValueError("gop_layout: a frame number is 0 .. 2^32 - 1")
-    buf = (ctypes.c_uint32 * max(1, len(st)))(*st)
+    st, buf = _uint_list(starts, ctypes.c_uint32, ValueError("gop_layout: a frame number is 0 .. 2^32 - 1"))
     flags = np.zeros(int(nframes), np.uint8)
-    n = lib().m2v_gop_layout(int(pframes_count), buf if st else None, len(st), int(nframes), flags.ctypes.data if nframes else None)
+    n = lib().m2v_gop_layout(int(pframes_count), buf, len(st), int(nframes), flags.ctypes.data if nframes else None)
     if n < 0:
         raise ValueError("gop_layout: the list must be strictly ascending")
     return flags, int(n)
@@ -564,6 +571,9 @@ class Mpeg2Encoder:
         self.params = (XL, YL, VECTOR_LEVEL, Q_LEVEL)
         self.device = device
         self._geom = {}
+        # what is set on the handle, as the setters below take it back (_for_call): the three options, the lists, the buffers, the size
+        self._set = {"stats": False, "gop_bytes_max": 0, "scene_cut": 0, "gop_levels": None, "gop_starts": None, "sequences": None,
+                     "stream_desc": None, "recon_out": None, "mux_out": None, "frame_size": None}
         err = ctypes.c_int(0)
         self._L = lib(debug)
         self._h = self._L.m2v_create(XL, YL, VECTOR_LEVEL, Q_LEVEL, device, ctypes.byref(err))
@@ -590,83 +600,89 @@ class Mpeg2Encoder:
     def set_option(self, name, value):
         self._chk(self._L.m2v_set_option(self._h, name.encode(), int(value)), "m2v_set_option(%s)" % name)
         if name == "stats":
-            self._stats = bool(value)
-        if name == "gop_bytes_max":
-            self._gop_cap = int(value)
-        if name == "scene_cut":
-            self._scene_cut = int(value)
+            self._set[name] = bool(value)
+        if name in ("gop_bytes_max", "scene_cut"):
+            self._set[name] = int(value)
+
+    def _set_list(self, key, values, ctype, what):
+        """a setter that takes a list of unsigned integers; None or an empty list clears it"""
+        name = "m2v_set_" + key
+        v, buf = _uint_list(values, ctype, M2VError("%s failed (-1): %s" % (name, what)))
+        self._chk(getattr(self._L, name)(self._h, buf, len(v)), name)
+        self._set[key] = v or None
+
+    def _pop(self, fn, dtype, max_records):
+        """the waiting records of one report function, oldest first, at most max_records of them, as a numpy structured array"""
+        report = getattr(self._L, fn)
+        n = self._chk(report(self._h, None, 0), fn)
+        if max_records is not None:
+            n = min(n, int(max_records))
+        out = np.zeros(n, dtype)
+        if n:
+            n = self._chk(report(self._h, out.ctypes.data, n), fn)
+        return out[:n]
+
+    @contextlib.contextmanager
+    def _for_call(self, settings):
+        """`settings` (keys of self._set, values as the setters take them) for the duration of a call: the handle's own are back afterwards"""
+        def apply(key, v):
+            if key in ("stats", "gop_bytes_max", "scene_cut"):
+                self.set_option(key, v)
+            elif key == "frame_size":
+                self.set_frame_size(*(v or (0, 0, 0)))
+            elif key == "recon_out":
+                self.set_recon_out(*(v or (None, 0)))
+            elif key == "mux_out":
+                self.set_mux_out(*(v or (None,)))
+            else:
+                getattr(self, "set_" + key)(v)
+        before = {key: self._set[key] for key in settings}
+        try:
+            for key, v in settings.items():
+                apply(key, v)
+            yield
+        finally:
+            for key, v in before.items():
+                apply(key, v)
 
     def set_gop_starts(self, frames):
         """m2v_set_gop_starts: in every sequence started from now on a GOP also starts at each of these frame numbers (strictly
         ascending; M2VError otherwise, and the previous setting stays); None or an empty sequence clears the setting.  Not the
         module's behaviour."""
-        st = [] if frames is None else [int(v) for v in frames]
-        if any(v < 0 or v > 0xFFFFFFFF for v in st):
-            raise M2VError("m2v_set_gop_starts failed (-1): a frame number is 0 .. 2^32 - 1")
-        buf = (ctypes.c_uint32 * max(1, len(st)))(*st)
-        self._chk(self._L.m2v_set_gop_starts(self._h, buf if st else None, len(st)), "m2v_set_gop_starts")
-        self._gop_starts = st or None
+        self._set_list("gop_starts", frames, ctypes.c_uint32, "a frame number is 0 .. 2^32 - 1")
 
     def scene_report(self, max_records=None):
         """Pops the waiting records of m2v_scene_report, oldest first, at most max_records of them: a numpy structured array of
         SCENE_STAT_DTYPE - one per picture of a sequence that had a list of GOP starts or option "scene_cut", empty otherwise."""
-        n = self._chk(self._L.m2v_scene_report(self._h, None, 0), "m2v_scene_report")
-        if max_records is not None:
-            n = min(n, int(max_records))
-        out = np.zeros(n, SCENE_STAT_DTYPE)
-        if n:
-            n = self._chk(self._L.m2v_scene_report(self._h, out.ctypes.data, n), "m2v_scene_report")
-        return out[:n]
+        return self._pop("m2v_scene_report", SCENE_STAT_DTYPE, max_records)
 
     def set_sequences(self, lengths):
         """m2v_set_sequences: the frames of every resident call started from now on are len(lengths) clips of these many frames, each
         coded as a stream of its own (sequence_report says where); None or an empty sequence clears the setting.  A call whose frames
         are not the sum of the entries, or an entry of 0, fails with M2VError when it starts."""
-        ln = [] if lengths is None else [int(v) for v in lengths]
-        if any(v < 0 or v > 0xFFFFFFFF for v in ln):
-            raise M2VError("m2v_set_sequences failed (-1): an entry is 1 .. 2^32 - 1 frames")
-        buf = (ctypes.c_uint32 * max(1, len(ln)))(*ln)
-        self._chk(self._L.m2v_set_sequences(self._h, buf if ln else None, len(ln)), "m2v_set_sequences")
-        self._sequences = ln or None
+        self._set_list("sequences", lengths, ctypes.c_uint32, "an entry is 1 .. 2^32 - 1 frames")
 
     def sequence_report(self, max_records=None):
         """Pops the waiting records of m2v_sequence_report, oldest first, at most max_records of them: a numpy structured array of
         SEQUENCE_STAT_DTYPE - one per clip of the last resident call that had a list of two or more entries, empty otherwise."""
-        n = self._chk(self._L.m2v_sequence_report(self._h, None, 0), "m2v_sequence_report")
-        if max_records is not None:
-            n = min(n, int(max_records))
-        out = np.zeros(n, SEQUENCE_STAT_DTYPE)
-        if n:
-            n = self._chk(self._L.m2v_sequence_report(self._h, out.ctypes.data, n), "m2v_sequence_report")
-        return out[:n]
+        return self._pop("m2v_sequence_report", SEQUENCE_STAT_DTYPE, max_records)
 
     def set_gop_levels(self, levels):
         """m2v_set_gop_levels: GOP k of every sequence started from now on is coded at levels[min(k, len - 1)], each 1..4 (M2VError
         otherwise, and the previous setting stays); None or an empty sequence clears the setting.  Not the module's behaviour."""
-        lv = [] if levels is None else [int(v) for v in levels]
-        if any(v < 0 or v > 255 for v in lv):
-            raise M2VError("m2v_set_gop_levels failed (-1): a level is 1..4")
-        buf = (ctypes.c_uint8 * max(1, len(lv)))(*lv)
-        self._chk(self._L.m2v_set_gop_levels(self._h, buf if lv else None, len(lv)), "m2v_set_gop_levels")
-        self._gop_levels = lv or None
+        self._set_list("gop_levels", levels, ctypes.c_uint8, "a level is 1..4")
 
     def gop_report(self, max_records=None):
         """Pops the waiting records of option "gop_bytes_max" (m2v_gop_report), oldest first, at most max_records of them: a numpy
         structured array of GOP_STAT_DTYPE, empty while the cap is off."""
-        n = self._chk(self._L.m2v_gop_report(self._h, None, 0), "m2v_gop_report")
-        if max_records is not None:
-            n = min(n, int(max_records))
-        out = np.zeros(n, GOP_STAT_DTYPE)
-        if n:
-            n = self._chk(self._L.m2v_gop_report(self._h, out.ctypes.data, n), "m2v_gop_report")
-        return out[:n]
+        return self._pop("m2v_gop_report", GOP_STAT_DTYPE, max_records)
 
     def set_recon_out(self, ptr, cap, layout="i420"):
         """m2v_set_recon_out: every resident sequence started from now on writes its reconstructed pictures, frame n at
         ptr + n * frame_bytes(w, h, layout), into the `cap` bytes of device memory at `ptr`; ptr = None or 0 clears the setting.  Idle
         handles only.  planes_of_recon takes the buffer apart."""
         self._chk(self._L.m2v_set_recon_out(self._h, ptr or None, int(cap), _layout420(layout)), "m2v_set_recon_out")
-        self._recon_out = (int(ptr), int(cap), layout) if ptr else None
+        self._set["recon_out"] = (int(ptr), int(cap), layout) if ptr else None
 
     def set_mux_out(self, kind, ptr=None, cap=0):
         """m2v_set_mux_out: every resident call started from now on also leaves its stream as a transport ("ts") or program ("ps")
@@ -674,18 +690,12 @@ class Mpeg2Encoder:
         mux_report says where.  kind = None or 0 clears the setting.  Idle handles only."""
         k = _mux_kind(kind) if kind else 0
         self._chk(self._L.m2v_set_mux_out(self._h, k, (ptr or None) if k else None, int(cap) if k else 0), "m2v_set_mux_out")
-        self._mux_out = (k, int(ptr), int(cap)) if k else None
+        self._set["mux_out"] = (k, int(ptr), int(cap)) if k else None
 
     def mux_report(self, max_records=None):
         """Pops the waiting records of m2v_mux_report, oldest first, at most max_records of them: a numpy structured array of
         MUX_STAT_DTYPE - one per container of the last resident call that had a container buffer set, or of the last mux_device."""
-        n = self._chk(self._L.m2v_mux_report(self._h, None, 0), "m2v_mux_report")
-        if max_records is not None:
-            n = min(n, int(max_records))
-        out = np.zeros(n, MUX_STAT_DTYPE)
-        if n:
-            n = self._chk(self._L.m2v_mux_report(self._h, out.ctypes.data, n), "m2v_mux_report")
-        return out[:n]
+        return self._pop("m2v_mux_report", MUX_STAT_DTYPE, max_records)
 
     def mux_device(self, es, kind, segments=None, out=None, cap=None, pictures=None):
         """m2v_mux_device: the elementary streams in the uint8 device tensor `es` - the whole tensor, or the (offset, bytes) pairs of
@@ -726,23 +736,23 @@ class Mpeg2Encoder:
         if desc is not None and not isinstance(desc, StreamDesc):
             raise M2VError("m2v_set_stream_desc failed (-1): a StreamDesc or None is required")
         self._chk(self._L.m2v_set_stream_desc(self._h, ctypes.byref(desc) if desc is not None else None), "m2v_set_stream_desc")
-        self._desc = StreamDesc.from_buffer_copy(desc) if desc is not None else None
+        self._set["stream_desc"] = StreamDesc.from_buffer_copy(desc) if desc is not None else None
 
     def set_frame_size(self, w, h, header="module"):
         """m2v_set_frame_size: from now on every whole-frame entry takes w x h frames in its own format and pads them on the device;
         header "module" (the padded size in the stream's headers) or "true" (w x h).  (0, 0) switches it off.  Idle handles only."""
         code = HEADER_MODES[header] if isinstance(header, str) else int(header)
         self._chk(self._L.m2v_set_frame_size(self._h, int(w), int(h), code), "m2v_set_frame_size")
-        self._size = (int(w), int(h), code) if w or h else None
+        self._set["frame_size"] = (int(w), int(h), code) if w or h else None
 
     @property
     def frame_size(self):
         """(w, h, header code) set by set_frame_size, or None"""
-        return getattr(self, "_size", None)
+        return self._set["frame_size"]
 
     def _fb(self, xsize16, ysize16, kind):
         """bytes of one frame a whole-frame entry takes: of the size set, else of the clamped geometry"""
-        w, h = self._size[:2] if getattr(self, "_size", None) else self.geometry(xsize16, ysize16)
+        w, h = self.frame_size[:2] if self.frame_size else self.geometry(xsize16, ysize16)
         return frame_bytes(w, h, kind)
 
     def geometry(self, xsize16, ysize16):
@@ -890,7 +900,7 @@ class Mpeg2Encoder:
                 self.push_frames420(xsize16, ysize16, pframes_count, frames444, layout)
             self.sequence_stop()
             return self.pull_all()
-        if getattr(self, "_size", None):
+        if self.frame_size:
             assert nbeats is None, "there are no partial frames while a frame size is set"
             self.push_frames(xsize16, ysize16, pframes_count, frames444)
             self.sequence_stop()
@@ -950,13 +960,7 @@ class Mpeg2Encoder:
     def picture_stats(self, max_records=None):
         """Pops the waiting records of option "stats" (m2v_picture_stats), oldest first, at most max_records of them: a numpy structured
         array of PICTURE_STAT_DTYPE, empty while the option is off."""
-        n = self._chk(self._L.m2v_picture_stats(self._h, None, 0), "m2v_picture_stats")
-        if max_records is not None:
-            n = min(n, int(max_records))
-        out = np.zeros(n, PICTURE_STAT_DTYPE)
-        if n:
-            n = self._chk(self._L.m2v_picture_stats(self._h, out.ctypes.data, n), "m2v_picture_stats")
-        return out[:n]
+        return self._pop("m2v_picture_stats", PICTURE_STAT_DTYPE, max_records)
 
     def encode_tensor(self, frames, pframes_count, order="rgb", matrix="bt601", out=None, header=None, stats=False, gop_levels=None,
                       gop_bytes_max=0, gop_starts=None, scene_cut=0, recon=None, desc=None, sequences=None, container=None):
@@ -1027,60 +1031,33 @@ class Mpeg2Encoder:
         if container is not None:
             nclips = len(sequences or ()) or 1
             mux = torch.empty(mux_bound(container, out.numel(), N) + 32 * nclips, dtype=torch.uint8, device=frames.device)
-        mux_before = getattr(self, "_mux_out", None)
-        recon_before = getattr(self, "_recon_out", None)
-        before = self.frame_size
+        # what the call sets, in the cases it always has: a tensor of whole macroblocks clears a size the handle holds
         fit = bool(W % 16 or H % 16)
-        if fit or before:
-            self.set_frame_size(W if fit else 0, H if fit else 0, header if fit else "module")
-        stats_before = getattr(self, "_stats", False)
-        if stats and not stats_before:
-            self.set_option("stats", 1)
-        levels_before, cap_before = getattr(self, "_gop_levels", None), getattr(self, "_gop_cap", 0)
-        starts_before, cut_before = getattr(self, "_gop_starts", None), getattr(self, "_scene_cut", 0)
-        desc_before = getattr(self, "_desc", None)
-        seq_before = getattr(self, "_sequences", None)
-        try:
-            if sequences is not None:
-                self.set_sequences(sequences)
-            if desc is not None:
-                self.set_stream_desc(desc)
-            if gop_levels is not None:
-                self.set_gop_levels(gop_levels)
-            if gop_bytes_max:
-                self.set_option("gop_bytes_max", gop_bytes_max)
-            if gop_starts is not None:
-                self.set_gop_starts(gop_starts)
-            if scene_cut:
-                self.set_option("scene_cut", scene_cut)
-            if rec is not None:
-                self.set_recon_out(rec.data_ptr(), rec.numel(), recon)
-            if mux is not None:
-                self.set_mux_out(container, mux.data_ptr(), mux.numel())
+        call = {}
+        if fit or self.frame_size:
+            call["frame_size"] = (W, H, header) if fit else None
+        if stats and not self._set["stats"]:
+            call["stats"] = 1
+        if sequences is not None:
+            call["sequences"] = sequences
+        if desc is not None:
+            call["stream_desc"] = desc
+        if gop_levels is not None:
+            call["gop_levels"] = gop_levels
+        if gop_bytes_max:
+            call["gop_bytes_max"] = gop_bytes_max
+        if gop_starts is not None:
+            call["gop_starts"] = gop_starts
+        if scene_cut:
+            call["scene_cut"] = scene_cut
+        if rec is not None:
+            call["recon_out"] = (rec.data_ptr(), rec.numel(), recon)
+        if mux is not None:
+            call["mux_out"] = (container, mux.data_ptr(), mux.numel())
+        with self._for_call(call):
             nb = self.encode_resident_rgb(frames.data_ptr(), N, out.data_ptr(), out.numel(), xs, ys, pframes_count, layout, matrix,
                                           stream=torch.cuda.current_stream(frames.device).cuda_stream)
             records = self.picture_stats() if stats else None
-        finally:
-            if rec is not None:
-                self.set_recon_out(*(recon_before or (None, 0)))
-            if mux is not None:
-                self.set_mux_out(*(mux_before or (None,)))
-            if fit or before:
-                self.set_frame_size(*(before or (0, 0, 0)))
-            if stats and not stats_before:
-                self.set_option("stats", 0)
-            if gop_levels is not None:
-                self.set_gop_levels(levels_before)
-            if gop_bytes_max:
-                self.set_option("gop_bytes_max", cap_before)
-            if gop_starts is not None:
-                self.set_gop_starts(starts_before)
-            if scene_cut:
-                self.set_option("scene_cut", cut_before)
-            if desc is not None:
-                self.set_stream_desc(desc_before)
-            if sequences is not None:
-                self.set_sequences(seq_before)
         first = out[:nb]
         if mux is not None:
             r = self.mux_report()

@@ -103,7 +103,7 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
     std::vector<int> seg_start;                   // chunk-frame index where each GOP segment starts
     // where GOPs start: the fixed cadence, or - with a list or the detector's flags - the rule stepped on from where the last chunk left it
     const bool layout = seq_has_layout(e);
-    GopRule rule{e->pframes, e->seq_starts.data(), e->seq_starts.size(), 0, e->gop_s, e->gop_k};
+    GopRule rule{e->pframes, e->seq.starts.data(), e->seq.starts.size(), 0, e->gop_s, e->gop_k};
     if (layout) e->st().scene.clear();
     // a batch (m2v_set_sequences): a frame counts from its own sequence's first frame, and says in FrameJob::pad where it stands
     const bool batch = seq_batch(e);
@@ -113,15 +113,15 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
         size_t n = e->frames_total + k;
         uint32_t sq_flags = 0;
         if (batch) {
-            if (n == sq_f0 + e->seq_lens[sq_at]) { sq_f0 = n; ++sq_at; if (k) ++sq_ord; }
+            if (n == sq_f0 + e->seq.lens[sq_at]) { sq_f0 = n; ++sq_at; if (k) ++sq_ord; }
             if (k == 0) e->plan_seq0 = sq_at;
             n -= sq_f0;
-            sq_flags = (n == 0 ? kSeqFirst : 0u) | (n + 1 == e->seq_lens[sq_at] ? kSeqLast : 0u) | sq_ord << kSeqOrdShift;
+            sq_flags = (n == 0 ? kSeqFirst : 0u) | (n + 1 == e->seq.lens[sq_at] ? kSeqLast : 0u) | sq_ord << kSeqOrdShift;
         }
         jobs[k].in = d_frames + k * frame_bytes;
         jobs[k].i_frame = (int32_t)(n % gop);
         if (layout) {
-            const bool det = e->seq_cut != 0;
+            const bool det = e->seq.cut != 0;
             const uint32_t fl = rule.step(n, det && e->chunk_cut[k]);
             jobs[k].i_frame = (int32_t)(n - rule.s);
             e->st().scene.push_back(m2v_scene_stat{(uint32_t)n, fl, det ? e->chunk_diff[k] : 0ull});
@@ -149,7 +149,7 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
     // runtime test job.rec != nullptr).  The two alternating slots of a segment still do: frame k writes slot k & 1 and reads (k - 1) & 1,
     // and k_picstat reads frame k's slot on the segment's stream before frame k + 1 - let alone k + 2 - is launched.
     // A buffer for the reconstruction (m2v_set_recon_out) asks for the same, and k_recon_out reads a slot where k_picstat does.
-    const bool every_rec = e->stats_on || e->seq_recon.p != nullptr;
+    const bool every_rec = e->stats_on || e->seq.recon.p != nullptr;
     const bool need_any_rec = e->pframes > 0 || every_rec;
     std::vector<int> rec_slot(nf, -1);
     if (need_any_rec) {
@@ -180,7 +180,7 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
                     // ... which a start from the list, or a cut, ends early.  The next chunk's cuts are not known yet: its first frame may
                     // turn out not to need this one
                     if (k + 1 < nf) followed = jobs[k + 1].i_frame != 0;
-                    else if (std::binary_search(e->seq_starts.begin(), e->seq_starts.end(), (uint32_t)(e->frames_total + nf))) followed = false;
+                    else if (std::binary_search(e->seq.starts.begin(), e->seq.starts.end(), (uint32_t)(e->frames_total + nf))) followed = false;
                 }
                 int prev = (k == a) ? (jobs[k].i_frame != 0 ? e->persist_slot : -1) : rec_slot[k - 1];
                 if (jobs[k].i_frame != 0) {
@@ -253,7 +253,7 @@ void plan_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf, b
     }
 
     e->plan_nlists = lists.size();
-    const size_t redo_room = e->seq_cap ? nf : 0;        // the cap's redo lists follow the plan's (gop_cap_chunk): every frame at most once per try
+    const size_t redo_room = e->seq.cap ? nf : 0;        // the cap's redo lists follow the plan's (gop_cap_chunk): every frame at most once per try
     e->plan_list_q.assign(lists.size() + redo_room, (uint8_t)e->Q);
     for (size_t i = 0; i < lists.size(); ++i) e->plan_list_q[i] = (uint8_t)jobs[(size_t)lists[i]].q;
 
@@ -425,7 +425,7 @@ void encode_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf,
                     launch_picstat(e, sk, e->d_lists.p + st.off_i + st.cut_i[k], st.cut_i[k + 1] - st.cut_i[k]);
                     launch_picstat(e, sk, e->d_lists.p + st.off_p + st.cut_p[k], st.cut_p[k + 1] - st.cut_p[k]);
                 }
-                if (e->seq_recon.p) {   // the same place, the same reason
+                if (e->seq.recon.p) {   // the same place, the same reason
                     launch_recon_out(e, sk, e->d_lists.p + st.off_i + st.cut_i[k], st.cut_i[k + 1] - st.cut_i[k]);
                     launch_recon_out(e, sk, e->d_lists.p + st.off_p + st.cut_p[k], st.cut_p[k + 1] - st.cut_p[k]);
                 }
@@ -450,7 +450,7 @@ void encode_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf,
                 launch_picstat(e, s, e->d_lists.p + st.off_i, st.n_i);
                 launch_picstat(e, s, e->d_lists.p + st.off_p, st.n_p);
             }
-            if (e->seq_recon.p) {       // (timed: kernel 6 of m2v_kernel_stats)
+            if (e->seq.recon.p) {       // (timed: kernel 6 of m2v_kernel_stats)
                 launch_recon_out(e, s, e->d_lists.p + st.off_i, st.n_i);
                 launch_recon_out(e, s, e->d_lists.p + st.off_p, st.n_p);
             }
@@ -458,7 +458,7 @@ void encode_chunk(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf,
         e->timer_merge = false;
         timer_break(e);
     }
-    if (e->seq_cap) gop_cap_chunk(e, s);          // option "gop_bytes_max": the GOPs over the cap again, coarser (waits for the device)
+    if (e->seq.cap) gop_cap_chunk(e, s);          // option "gop_bytes_max": the GOPs over the cap again, coarser (waits for the device)
     finish_chunk(e, s, first, last, d_stream, advance);
     if (e->stats_on) stats_finish_chunk(e, s);
 }
@@ -523,7 +523,7 @@ m2v_enc *m2v_create(int XL, int YL, int VECTOR_LEVEL, int Q_LEVEL, int device, i
     try {
         HIPCHK(hipSetDevice(device));
         HIPCHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-        // the port path's upload and read-back streams are created with its first sequence (start_sequence): HIP spreads a process's
+        // the port path's upload and read-back streams are created with its first sequence (open_port): HIP spreads a process's
         // streams over a handful of hardware queues in creation order, and a handle that only ever runs the resident entry should not
         // push its own two GOP-group streams - or another handle's - onto the same queue (three handles with three streams each did
         // exactly that: the two groups of one handle serialised, 1.08 -> 1.20 ms per step)
@@ -636,11 +636,7 @@ int m2v_reset(m2v_enc *e)
     e->buffered = 0; e->beat_pos = 0; e->frames_total = 0; e->persist_slot = -1;
     e->first_chunk = true; e->stream_bytes = 0; e->cur = 0;
     e->fifo.clear(); e->fifo_rd = 0; e->end_pending = false;
-    stats_drop(e);
-    gop_drop(e);
-    scene_drop(e);
-    seq_drop(e);
-    mux_drop(e);
+    drop_records(e);
     // a strip sequence abandoned between m2v_strip_begin and m2v_strip_finish: back to the full frame
     e->strip_active = false;
     e->strip_inflight = false;
@@ -680,22 +676,19 @@ int m2v_fit_size(int width, int height, uint32_t *xsize16, uint32_t *ysize16)
 int m2v_set_frame_size(m2v_enc *e, int width, int height, int header)
 {
     if (!e) return M2V_E_PARAM;
-    if (e->state != m2v_enc::IDLE || e->resident_inflight || e->strip_active || e->strip_inflight) {
-        e->set_err("m2v_set_frame_size: a sequence is in progress (the size is sampled when a sequence starts)");
-        return M2V_E_STATE;
-    }
+    if (in_progress(e, "m2v_set_frame_size", "the size is sampled when a sequence starts")) return M2V_E_STATE;
     if (header != M2V_HEADER_MODULE && header != M2V_HEADER_TRUE) { e->set_err("m2v_set_frame_size: unknown header %d", header); return M2V_E_PARAM; }
-    // (what the last sequence sampled goes with the old setting: a sequence that beats start samples nothing, and only runs with no size set)
-    e->fit = SrcSize{};
-    e->hdr_true = false;
-    if (width == 0 && height == 0) { e->src_size = SrcSize{}; e->src_header = M2V_HEADER_MODULE; return M2V_OK; }
+    // (what the last sequence sampled goes with the old setting)
+    e->seq.fit = SrcSize{};
+    e->seq.hdr_true = false;
+    if (width == 0 && height == 0) { e->set.size = SrcSize{}; e->set.header = M2V_HEADER_MODULE; return M2V_OK; }
     uint32_t xs = 0, ys = 0;
     if (m2v_fit_size(width, height, &xs, &ys) != M2V_OK || xs < 4 || ys < 4 || xs > (1u << e->XL) || ys > (1u << e->YL)) {
         e->set_err("m2v_set_frame_size: %d x %d does not pad to a size of this handle (64 ... %d by 64 ... %d)", width, height, 16 << e->XL, 16 << e->YL);
         return M2V_E_PARAM;
     }
-    e->src_size = SrcSize{width, height};
-    e->src_header = header;
+    e->set.size = SrcSize{width, height};
+    e->set.header = header;
     return M2V_OK;
 }
 
@@ -729,19 +722,19 @@ int m2v_set_option(m2v_enc *e, const char *name, long long value)
     if (!strcmp(name, "stats")) {
         if (e->state != m2v_enc::IDLE) { e->set_err("m2v_set_option: \"stats\" can be set only while the handle is idle"); return M2V_E_STATE; }
         e->stats_on = value != 0;
-        if (!e->stats_on) stats_drop(e);
+        if (!e->stats_on) { e->pstat_q.clear(); for (auto &h : e->hs) h.nstat = 0; }
         return M2V_OK;
     }
     if (!strcmp(name, "gop_bytes_max")) {
         if (e->state != m2v_enc::IDLE) { e->set_err("m2v_set_option: \"gop_bytes_max\" can be set only while the handle is idle"); return M2V_E_STATE; }
         if (value < 0) { e->set_err("m2v_set_option: gop_bytes_max is a byte count, 0 = off"); return M2V_E_PARAM; }
-        e->gop_bytes_max = (unsigned long long)value;
+        e->set.gop_bytes_max = (unsigned long long)value;
         return M2V_OK;
     }
     if (!strcmp(name, "scene_cut")) {
         if (e->state != m2v_enc::IDLE) { e->set_err("m2v_set_option: \"scene_cut\" can be set only while the handle is idle"); return M2V_E_STATE; }
         if (value < 0 || value > 65280) { e->set_err("m2v_set_option: scene_cut is a threshold 1..65280, 0 = off"); return M2V_E_PARAM; }
-        e->scene_cut = (uint32_t)value;
+        e->set.scene_cut = (uint32_t)value;
         return M2V_OK;
     }
     if (!strcmp(name, "dct_mfma")) { e->dct_mfma = value != 0; return M2V_OK; }

@@ -39,16 +39,11 @@ static const char *desc_fault(const m2v_stream_desc &d)
     return nullptr;
 }
 
-static SeqDesc pack(const m2v_stream_desc &d)
+SeqDesc pack_desc(const m2v_stream_desc &d)
 {
     return SeqDesc{d.frame_rate_code | d.aspect_ratio_information << 4 | d.video_format << 8 | d.repeat_headers << 11 | d.vbv_buffer_size_16k << 12,
                    d.bit_rate_400, d.colour_primaries | d.transfer_characteristics << 8 | d.matrix_coefficients << 16,
                    d.display_width | d.display_height << 16};
-}
-
-void sample_stream_desc(m2v_enc *e)
-{
-    e->seq_desc = e->desc_set ? pack(e->desc) : seq_desc_module();
 }
 
 }  // namespace m2v
@@ -63,17 +58,14 @@ void m2v_stream_desc_module(m2v_stream_desc *d)
 int m2v_set_stream_desc(m2v_enc *e, const m2v_stream_desc *d)
 {
     if (!e) return M2V_E_PARAM;
-    if (e->state != m2v_enc::IDLE || e->resident_inflight || e->strip_active || e->strip_inflight) {
-        e->set_err("m2v_set_stream_desc: a sequence is in progress (the description is sampled when a sequence starts)");
-        return M2V_E_STATE;
-    }
-    if (!d) { e->desc_set = false; return M2V_OK; }
+    if (in_progress(e, "m2v_set_stream_desc", "the description is sampled when a sequence starts")) return M2V_E_STATE;
+    if (!d) { e->set.desc_set = false; return M2V_OK; }
     if (const char *why = desc_fault(*d)) {
         e->set_err("m2v_set_stream_desc: %s (the previous setting stays)", why);
         return M2V_E_PARAM;
     }
-    e->desc = *d;
-    e->desc_set = memcmp(d, &kModuleDesc, sizeof *d) != 0;
+    e->set.desc = *d;
+    e->set.desc_set = memcmp(d, &kModuleDesc, sizeof *d) != 0;
     return M2V_OK;
 }
 

@@ -18,24 +18,6 @@ static_assert(sizeof(m2v_gop_stat) == 32, "the record of include/m2v_mi355x.h is
 
 namespace m2v {
 
-void sample_gop_levels(m2v_enc *e, bool with_cap)
-{
-    e->seq_levels = e->gop_levels;
-    e->seq_cap = with_cap ? e->gop_bytes_max : 0;
-}
-
-void gop_collect(m2v_enc *e, m2v_enc::HostStage &h)
-{
-    e->gop_q.insert(e->gop_q.end(), h.h_gop, h.h_gop + h.ngop);
-    h.ngop = 0;
-}
-
-void gop_drop(m2v_enc *e)
-{
-    e->gop_q.clear();
-    for (auto &h : e->hs) h.ngop = 0;
-}
-
 void gop_cap_chunk(m2v_enc *e, hipStream_t s)
 {
     const Geom &g = e->g;
@@ -61,7 +43,7 @@ void gop_cap_chunk(m2v_enc *e, hipStream_t s)
     for (size_t sg = 0; sg < nseg; ++sg) { open[sg] = (int)sg; level[sg] = (uint8_t)e->dev_jobs[sg * gop].q; }
     const size_t base = e->plan_nlists;
     for (;;) {
-        launch_gop_judge(e, s, nf, (uint32_t)gop, e->seq_cap, h.h_gop);
+        launch_gop_judge(e, s, nf, (uint32_t)gop, e->seq.cap, h.h_gop);
         // nothing to wait for once every open GOP is at level 4: whatever the verdict, it stays (the records travel with the chunk)
         open.erase(std::remove_if(open.begin(), open.end(), [&](int sg) { return level[(size_t)sg] >= 4; }), open.end());
         if (open.empty()) break;
@@ -116,7 +98,7 @@ void gop_cap_chunk(m2v_enc *e, hipStream_t s)
                 launch_picstat(e, s, e->d_lists.p + r.off_p, r.n_p);
             }
             // m2v_set_recon_out: the frames of a GOP that goes again are overwritten by those of its final level
-            if (e->seq_recon.p) {
+            if (e->seq.recon.p) {
                 launch_recon_out(e, s, e->d_lists.p + r.off_i, r.n_i);
                 launch_recon_out(e, s, e->d_lists.p + r.off_p, r.n_p);
             }
@@ -137,13 +119,13 @@ extern "C" {
 int m2v_set_gop_levels(m2v_enc *e, const uint8_t *levels, size_t n)
 {
     if (!e) return M2V_E_PARAM;
-    if (!levels || !n) { e->gop_levels.clear(); return M2V_OK; }
+    if (!levels || !n) { e->set.gop_levels.clear(); return M2V_OK; }
     for (size_t k = 0; k < n; ++k)
         if (levels[k] < 1 || levels[k] > 4) {
             e->set_err("m2v_set_gop_levels: levels[%zu] = %u, a level is 1..4 (the previous setting stays)", k, (unsigned)levels[k]);
             return M2V_E_PARAM;
         }
-    try { e->gop_levels.assign(levels, levels + n); }
+    try { e->set.gop_levels.assign(levels, levels + n); }
     catch (...) { e->set_err("m2v_set_gop_levels: host allocation failed"); return M2V_E_NOMEM; }
     return M2V_OK;
 }
@@ -151,11 +133,7 @@ int m2v_set_gop_levels(m2v_enc *e, const uint8_t *levels, size_t n)
 long long m2v_gop_report(m2v_enc *e, m2v_gop_stat *dst, size_t cap)
 {
     if (!e) return M2V_E_PARAM;
-    if (!dst) return (long long)e->gop_q.size();
-    const size_t n = std::min(cap, e->gop_q.size());
-    std::copy(e->gop_q.begin(), e->gop_q.begin() + (std::ptrdiff_t)n, dst);
-    e->gop_q.erase(e->gop_q.begin(), e->gop_q.begin() + (std::ptrdiff_t)n);
-    return (long long)n;
+    return (long long)e->gop_q.pop(dst, cap);
 }
 
 }  // extern "C"

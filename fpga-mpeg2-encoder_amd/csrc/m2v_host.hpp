@@ -9,20 +9,23 @@
 //                     conversions in front of a chunk (k_unpack444, k_fit, k_expand420, k_rgb2yuv: no device globals, so they can live here)
 //   m2v_resident.hip  whole sequences resident in HBM (what bench.py times), one or several per call
 //   m2v_strips.hip    strip mode (BASELINE config c5) and the communicators of m2v_comm.hpp
+//   m2v_begin.hip     where a sequence starts, for every entry: what may run with what (begin_refusal), what the sequence samples from
+//                     the settings (begin_sequence: all of m2v_enc::seq, nowhere else), and the records' way from a chunk or a call to
+//                     the queues the report functions pop (collect_chunk, collect_call, drop_records)
 //   m2v_gop.hip       a level per GOP: the caller's schedule (m2v_set_gop_levels) and option "gop_bytes_max", the byte cap the device judges
 //                     (k_gop_judge, m2v_gop_kernels.hpp, launched from m2v_launch.hip) and the host's redo loop; m2v_gop_report
 //   m2v_scene.hip     where GOPs start: the rule (gop_layout_run, m2v_gop_layout), the caller's list (m2v_set_gop_starts), option
 //                     "scene_cut" - the detector's buffers, its launches (k_mbsum, k_scene_judge, m2v_scene_kernels.hpp, launched from
 //                     m2v_launch.hip) and the host's one wait per chunk - and m2v_scene_report
-//   m2v_stats.hip     option "stats": the per-picture records of m2v_picture_stats - their buffers, their way to the host and the queue
-//                     they wait in (the kernels that fill them, m2v_stats_kernels.hpp, need m2v_kernels.hpp and so belong to m2v_launch.hip)
-//   m2v_desc.hip      m2v_set_stream_desc: what the stream says about itself - the setting, its validation, what a sequence samples from it
-//                     when it starts (the SeqDesc the header writers of m2v_kernels.hpp take by value) - and the plain arithmetic of
-//                     m2v_frame_rate_code and m2v_time_code
-//   m2v_recon.hip     m2v_set_recon_out: the setting, what a resident sequence samples from it when it starts, the capacity check and
-//                     the refusals (the kernel, m2v_recon_kernels.hpp, is launched from m2v_launch.hip)
-//   m2v_sequences.hip m2v_set_sequences: a batch of sequences in one resident call - the setting, what a call samples from it, the
-//                     refusals, the records' way to the host and m2v_sequence_report (the scan that places the streams, k_seq_scan in
+//   m2v_stats.hip     option "stats": the per-picture records of m2v_picture_stats - their buffers and their way to the host (the
+//                     kernels that fill them, m2v_stats_kernels.hpp, need m2v_kernels.hpp and so belong to m2v_launch.hip)
+//   m2v_desc.hip      m2v_set_stream_desc: what the stream says about itself - the setting, its validation, its packed form (the SeqDesc
+//                     the header writers of m2v_kernels.hpp take by value) - and the plain arithmetic of m2v_frame_rate_code and
+//                     m2v_time_code
+//   m2v_recon.hip     m2v_set_recon_out: the setting and the size of a frame in the caller's buffer (the kernel, m2v_recon_kernels.hpp,
+//                     is launched from m2v_launch.hip)
+//   m2v_sequences.hip m2v_set_sequences: a batch of sequences in one resident call - the setting, what the host knows of a batch's
+//                     records when the call starts, and m2v_sequence_report (the scan that places the streams, k_seq_scan in
 //                     m2v_seq_kernels.hpp, is launched from m2v_launch.hip)
 //   m2v_mux.hip       m2v_set_mux_out / m2v_mux_device: transport or program stream out of the stream in HBM.  Its three kernels touch no
 //                     device global and nothing of m2v_kernels.hpp, so they live in their own unit with their launches (m2v_mux_kernels.hpp
@@ -76,6 +79,25 @@ struct DevBuf {
         n = count;
     }
     void release() { if (p) { if (recorded) ++alloc_generation(); (void)hipFree(p); } p = nullptr; n = 0; }
+};
+
+// Records waiting for a report function (m2v_picture_stats, m2v_gop_report, ...): oldest first
+template <typename T>
+struct Records {
+    std::deque<T> q;
+    void push(const T *first, const T *last) { q.insert(q.end(), first, last); }
+    void clear() { q.clear(); }
+    // up to max records into out, which leave the queue; out == nullptr: how many are waiting
+    size_t pop(T *out, size_t max)
+    {
+        if (!out) return q.size();
+        const size_t n = std::min(max, q.size());
+        std::copy(q.begin(), q.begin() + (std::ptrdiff_t)n, out);
+        q.erase(q.begin(), q.begin() + (std::ptrdiff_t)n);
+        return n;
+    }
+    // ... for the report functions that answer an int
+    int pop31(T *out, size_t max) { return (int)std::min<size_t>(pop(out, std::min<size_t>(max, 0x7FFFFFFF)), 0x7FFFFFFF); }
 };
 
 struct KStat { int launches = 0; double ms = 0, units = 0; };
@@ -147,10 +169,10 @@ struct m2v_enc {
                                               // caller memory goes to the device directly, without the pinned staging copy)
         m2v_picture_stat *h_pstat = nullptr;  // pinned: the chunk's picture records (option "stats"), read back in front of the control word
         size_t h_pstat_cap = 0;
-        size_t nstat = 0;                     // records of the submitted chunk that stats_collect has not moved to the handle's queue yet
+        size_t nstat = 0;                     // records of the submitted chunk that collect_chunk has not moved to the handle's queue yet
         m2v_gop_stat *h_gop = nullptr;        // pinned: the chunk's GOP records (option "gop_bytes_max"), written by k_gop_judge itself
         size_t h_gop_cap = 0;
-        size_t ngop = 0;                      // records of the submitted chunk that gop_collect has not moved to the handle's queue yet
+        size_t ngop = 0;                      // records of the submitted chunk that collect_chunk has not moved to the handle's queue yet
         std::vector<m2v_scene_stat> scene;    // the submitted chunk's records of m2v_scene_report (plan_chunk makes them on the host)
         int stage = 0;                        // 0 free, 1 encode submitted, 2 stream read-back submitted
         bool last = false;
@@ -271,44 +293,60 @@ struct m2v_enc {
     DevBuf<uint8_t> d_x444;
     size_t x444_bytes = 0;                // ... what the last call's last chunk left there (m2v_debug_read, what = 4)
 
-    // m2v_set_frame_size: the setting (0 x 0 = off), and what the sequence in progress sampled from it when it started: fit = the source
-    // size when the frames have to be padded (0 x 0 when not: no size set, or one of whole macroblocks), hdr_true = the headers say it
-    SrcSize src_size;
-    int src_header = M2V_HEADER_MODULE;
-    SrcSize fit;
-    bool hdr_true = false;
+    // What the setters write, on idle handles only, and what the sequence in progress runs with.  begin_sequence (m2v_begin.hip) decides
+    // from `set` whether an entry may start and writes ALL of `seq`, for every entry: a setting the entry does not take samples as off.
+    // Besides it only m2v_set_frame_size, m2v_set_recon_out and m2v_set_mux_out write `seq`: they clear what goes with the old setting.
+    // plan_chunk, the launch sites and the feature units read `seq` only.
+    struct ReconDst { uint8_t *p = nullptr; size_t cap = 0; int layout = 0; size_t fb = 0; };      // fb (seq only): bytes of one frame in the caller's buffer
+    struct MuxDst { int kind = 0; uint8_t *p = nullptr; size_t cap = 0; };
+    struct Settings {
+        SrcSize size;                           // m2v_set_frame_size (0 x 0 = off) ...
+        int header = M2V_HEADER_MODULE;         // ... and what the headers say
+        std::vector<uint8_t> gop_levels;        // m2v_set_gop_levels
+        unsigned long long gop_bytes_max = 0;   // option "gop_bytes_max"
+        std::vector<uint32_t> gop_starts;       // m2v_set_gop_starts
+        uint32_t scene_cut = 0;                 // option "scene_cut"
+        m2v_stream_desc desc{};                 // m2v_set_stream_desc ...
+        bool desc_set = false;                  // ... and whether it differs from the module's
+        std::vector<uint32_t> sequences;        // m2v_set_sequences
+        ReconDst recon;                         // m2v_set_recon_out (p == nullptr: off)
+        MuxDst mux;                             // m2v_set_mux_out (kind 0: off)
+    } set;
+    struct Sampled {
+        SrcSize fit;                            // the source size when the frames have to be padded (0 x 0 when not: no size set, or one of whole macroblocks)
+        bool hdr_true = false;                  // the headers say it
+        std::vector<uint8_t> levels;            // empty: every GOP at Q
+        unsigned long long cap = 0;             // 0: no cap
+        std::vector<uint32_t> starts;           // empty and cut 0: the fixed cadence, nothing of m2v_scene.hip is touched
+        uint32_t cut = 0;
+        SeqDesc desc = seq_desc_module();       // launch_frame_scan and launch_assemble take it by value
+        std::vector<uint32_t> lens;             // empty: one sequence, nothing of m2v_sequences.hip is touched
+        ReconDst recon;
+        MuxDst mux;
+    } seq;
+
     DevBuf<uint8_t> d_fit;                // padded frames in their own format, between k_fit and the conversion (no recording references it)
 
     // option "stats" (m2v_stats.hip): the chunk's records on the device - k_picstat and k_picstat_mb fill them in place - and the
     // completed pictures' records nobody has popped yet
     bool stats_on = false;
     DevBuf<m2v_picture_stat> d_pstat;
-    std::deque<m2v_picture_stat> pstat_q;
+    Records<m2v_picture_stat> pstat_q;
 
-    // m2v_set_recon_out (m2v_recon.hip): the setting (p == nullptr: off), and what the resident sequence in progress sampled from it when
-    // it started - fb = bytes of one frame in the caller's buffer.  plan_chunk and the launch sites look at seq_recon only
-    struct ReconDst { uint8_t *p = nullptr; size_t cap = 0; int layout = 0; size_t fb = 0; } recon_out, seq_recon;
-
-    // a level per GOP (m2v_gop.hip): the caller's schedule and the byte cap - the settings, and what the sequence in progress sampled
-    // from them when it started (seq_levels empty: every GOP at Q; seq_cap 0: no cap)
-    std::vector<uint8_t> gop_levels, seq_levels;
-    unsigned long long gop_bytes_max = 0, seq_cap = 0;
+    // a level per GOP (m2v_gop.hip)
     std::vector<uint8_t> plan_list_q;     // the level of every entry of the plan's launch lists (the redo lists of the cap follow the plan's)
     size_t plan_nlists = 0;               // entries of the plan's own lists in d_lists / d_joblist
     DevBuf<m2v_gop_stat> d_gop;           // the chunk's GOP records on the device (k_gop_judge reads its own verdict of the previous try there)
-    std::deque<m2v_gop_stat> gop_q;       // completed GOPs' records nobody has popped yet
+    Records<m2v_gop_stat> gop_q;        // completed GOPs' records nobody has popped yet
     hipEvent_t ev_gop = nullptr;          // behind a k_gop_judge whose verdict the host needs
     uint8_t *h_redo = nullptr;            // pinned staging of the redo lists
     size_t h_redo_cap = 0;
 
-    // where GOPs start (m2v_scene.hip): the caller's list and the detector's threshold - the settings, and what the sequence in progress
-    // sampled from them when it started (seq_starts empty and seq_cut 0: the fixed cadence, nothing below is touched)
-    std::vector<uint32_t> gop_starts, seq_starts;
-    uint32_t scene_cut = 0, seq_cut = 0;
+    // where GOPs start (m2v_scene.hip)
     size_t gop_s = 0, gop_k = 0;          // the GOP in progress at frames_total: the frame number of its I picture, and its ordinal
     std::vector<uint8_t> chunk_cut;       // the detector's flag of every frame of the chunk about to be planned (scene_detect -> plan_chunk)
     std::vector<unsigned long long> chunk_diff;       // ... and D(n)
-    std::deque<m2v_scene_stat> scene_q;   // completed pictures' records nobody has popped yet
+    Records<m2v_scene_stat> scene_q;    // completed pictures' records nobody has popped yet
     DevBuf<uint32_t> d_mbsum;             // [frame][mb] luma sums of the chunk
     DevBuf<uint32_t> d_carry;             // 2 x [mb]: the sums of the last frame of the previous chunk, and where this chunk leaves its own
     int carry_cur = -1;                   // which half holds the previous chunk's (-1: the sequence starts with this chunk)
@@ -317,16 +355,8 @@ struct m2v_enc {
     size_t h_scene_cap = 0;
     hipEvent_t ev_scene = nullptr;        // behind the k_scene_judge whose flags the host needs
 
-    // what the stream says about itself (m2v_desc.hip): the setting, whether it differs from the module's, and what the sequence in
-    // progress sampled from it when it started - launch_frame_scan and launch_assemble look at seq_desc only
-    m2v_stream_desc desc{};
-    bool desc_set = false;
-    SeqDesc seq_desc = seq_desc_module();
-
-    // a batch of sequences (m2v_sequences.hip): the setting, and what the resident call in progress sampled from it when it started
-    // (seq_lens empty: one sequence, nothing below is touched).  seq_at / seq_f0: the sequence open at frames_total and the call frame it
-    // starts at, carried across chunks; plan_seq0 / plan_nsq: the sequence of the planned chunk's first frame, and how many it touches
-    std::vector<uint32_t> sequences, seq_lens;
+    // a batch of sequences (m2v_sequences.hip).  seq_at / seq_f0: the sequence open at frames_total and the call frame it starts at,
+    // carried across chunks; plan_seq0 / plan_nsq: the sequence of the planned chunk's first frame, and how many it touches
     size_t seq_at = 0, seq_f0 = 0, plan_seq0 = 0, plan_nsq = 0;
     size_t dev_base = 0;                  // frames_total of the plan d_joblist holds (a batch's copies there carry the CALL's frame number)
     DevBuf<m2v_sequence_stat> d_seq;      // the call's records on the device: offset and bytes of the open sequence travel from chunk to chunk here
@@ -334,19 +364,18 @@ struct m2v_enc {
     m2v_sequence_stat *h_seq = nullptr;   // pinned: the same records, written by k_seq_scan itself
     size_t h_seq_cap = 0;
     bool seq_pending = false;             // a batch is in flight or has just completed: its records have not moved to seq_q yet
-    std::deque<m2v_sequence_stat> seq_q;  // the last call's records nobody has popped yet
+    Records<m2v_sequence_stat> seq_q;   // the last call's records nobody has popped yet
 
-    // a container out of the stream (m2v_mux.hip): the setting (kind 0: off), what the resident call in progress sampled from it when it
-    // started, the muxer's work buffers - the streams' state, their start-code events, the picture tables; no recording references
-    // them - and the records: written into pinned memory by k_mux_plan itself, complete where the control word is
-    struct MuxDst { int kind = 0; uint8_t *p = nullptr; size_t cap = 0; } mux_out, seq_mux;
+    // a container out of the stream (m2v_mux.hip): the muxer's work buffers - the streams' state, their start-code events, the picture
+    // tables; no recording references them - and the records: written into pinned memory by k_mux_plan itself, complete where the
+    // control word is
     DevBuf<uint8_t> d_mux_st, d_mux_pic;
     DevBuf<unsigned long long> d_mux_ev;
     uint8_t *h_mux = nullptr;             // pinned: the streams' initial state on its way up, then the records
     size_t h_mux_cap = 0;
     size_t mux_n = 0;                     // streams of the last mux
     bool mux_pending = false;             // a resident call with a container is in flight: its records have not moved to mux_q yet
-    std::deque<m2v_mux_stat> mux_q;       // the last mux's records nobody has popped yet
+    Records<m2v_mux_stat> mux_q;        // the last mux's records nobody has popped yet
 
     // debug bookkeeping of the last resident encode
     size_t dbg_frames = 0;
@@ -438,87 +467,43 @@ struct Timer {
     }
 };
 
-// ---- m2v_port.hip ----
-// m2v_set_frame_size at the start of a sequence: false (M2V_E_PARAM, nothing started) when xs, ys are not m2v_fit_size's for the size set;
-// else samples e->fit / e->hdr_true
-bool sample_frame_size(m2v_enc *e, const char *fn, uint32_t xs, uint32_t ys);
-// the entries that take no frames of another size: true = refused (M2V_E_STATE) because a size is set
-inline bool size_refuses(m2v_enc *e, const char *fn, const char *why)
-{
-    if (!e->src_size.w) return false;
-    e->set_err("%s: a frame size is set (m2v_set_frame_size): %s", fn, why);
-    return true;
-}
-constexpr const char *kNoBeats = "the port has no partial macroblock, push whole frames";
-constexpr const char *kNoStrips = "strips take whole padded frames";
-// the strip entries that start something: true = refused (M2V_E_STATE) because a size is set, option "stats" is on or a buffer for the
-// reconstruction is set
-inline bool strip_refuses(m2v_enc *e, const char *fn)
-{
-    if (size_refuses(e, fn, kNoStrips)) return true;
-    if (!e->sequences.empty()) {
-        e->set_err("%s: a batch of sequences is set (m2v_set_sequences): the strip assembly writes one stream", fn);
-        return true;
-    }
-    if (e->mux_out.kind) {
-        e->set_err("%s: a container buffer is set (m2v_set_mux_out): the muxer follows the resident entries' stream", fn);
-        return true;
-    }
-    if (e->recon_out.p) {
-        e->set_err("%s: a buffer for the reconstruction is set (m2v_set_recon_out): a strip holds part of a picture, and nothing gathers the parts", fn);
-        return true;
-    }
-    if (e->stats_on) {
-        e->set_err("%s: option \"stats\" is on: a strip holds part of a picture, and nothing sums the records across ranks", fn);
-        return true;
-    }
-    if (!e->gop_levels.empty() || e->gop_bytes_max) {
-        e->set_err("%s: a level per GOP is set (m2v_set_gop_levels or option \"gop_bytes_max\"): a strip is coded at the handle's Q_LEVEL", fn);
-        return true;
-    }
-    if (!e->gop_starts.empty() || e->scene_cut) {
-        e->set_err("%s: GOP starts are set (m2v_set_gop_starts or option \"scene_cut\"): the strips of a frame run at the fixed cadence", fn);
-        return true;
-    }
-    if (e->desc_set) {
-        e->set_err("%s: a stream description is set (m2v_set_stream_desc): the strip assembly writes the module's headers", fn);
-        return true;
-    }
-    e->seq_desc = seq_desc_module();
-    e->seq_levels.clear();      // (what an earlier whole-frame sequence sampled)
-    e->seq_cap = 0;
-    e->seq_starts.clear();
-    e->seq_cut = 0;
-    e->seq_lens.clear();
-    return false;
-}
+// ---- m2v_begin.hip: where a sequence starts, and its records ----
+// The entries that start something.  Beats: m2v_push_beats, m2v_push_packed; Frames: m2v_push_frames / 420 / rgb and their _pull forms;
+// Resident: the six m2v_encode_resident* entries; Strip: m2v_strip_begin, m2v_strip_encode(_begin) and, for the rule alone, m2v_strip_assemble
+enum class Entry { Beats, Frames, Resident, Strip };
+// The rule of what may run with what, in one place: M2V_OK, or the code of the first refusal with its text in the handle (fn: the entry
+// it names).  Reads the handle and writes nothing but that text
+int begin_refusal(m2v_enc *e, const char *fn, Entry en, uint32_t xs, uint32_t ys, uint32_t pf, size_t nframes);
+// ... and the start itself: the rule, then all of e->seq, the geometry, the record queues emptied and the per-sequence counters reset.
+// nframes == 0 (a resident call without frames) answers M2V_OK with nothing sampled
+int begin_sequence(m2v_enc *e, const char *fn, Entry en, uint32_t xs, uint32_t ys, uint32_t pf, size_t nframes);
+// the setters of what a sequence samples, and m2v_mux_device: true = refused (M2V_E_STATE) because the handle is not idle
+bool in_progress(m2v_enc *e, const char *fn, const char *why);
+// the beat entries take no frames of another size, in any state: true = refused (M2V_E_STATE) because a size is set
+bool size_refuses_beats(m2v_enc *e, const char *fn);
+// a completed chunk's picture, GOP and scene records (its stream has been waited for) from the stage to the handle's queues
+void collect_chunk(m2v_enc *e, m2v_enc::HostStage &h);
+// a completed call's sequence and container records to the handle's queues; ok = false: the call overflowed, a batch has none
+void collect_call(m2v_enc *e, bool ok);
+// a new sequence, or m2v_reset: all five queues empty, and nothing waits in a stage or for a call any more
+void drop_records(m2v_enc *e);
+
 // ---- m2v_gop.hip ----
 // the level GOP number k of the sequence in progress is coded at, before the cap has had its say
 inline int level_of_gop(const m2v_enc *e, size_t k)
 {
-    if (e->seq_levels.empty()) return e->Q;
-    return e->seq_levels[std::min(k, e->seq_levels.size() - 1)];
+    if (e->seq.levels.empty()) return e->Q;
+    return e->seq.levels[std::min(k, e->seq.levels.size() - 1)];
 }
 // ... and frame n of a sequence at the fixed cadence (with a list or the detector plan_chunk counts the GOPs itself)
 inline int level_of_frame(const m2v_enc *e, size_t n) { return level_of_gop(e, n / (e->pframes + 1u)); }
-// the start of a sequence samples the schedule and the cap (where sample_frame_size is called; with_cap: the resident entries)
-void sample_gop_levels(m2v_enc *e, bool with_cap);
 // the chunk's steps have been enqueued and every group has joined s: slice scan, k_gop_judge, and the GOPs over the cap again at the next
 // level until every GOP fits or is at level 4.  Waits for the device, at most three times (encode_chunk, only with the cap on)
 void gop_cap_chunk(m2v_enc *e, hipStream_t s);
-void gop_collect(m2v_enc *e, m2v_enc::HostStage &h);
-void gop_drop(m2v_enc *e);
-// the port entries that start a sequence: true = refused (M2V_E_STATE) because option "gop_bytes_max" is set
-inline bool cap_refuses(m2v_enc *e, const char *fn)
-{
-    if (!e->gop_bytes_max) return false;
-    e->set_err("%s: option \"gop_bytes_max\" is set: the cap needs whole GOPs in a chunk, which only the resident entries give", fn);
-    return true;
-}
 
 // ---- m2v_desc.hip ----
-// the start of a sequence samples the description (where sample_gop_levels is called)
-void sample_stream_desc(m2v_enc *e);
+// the description as the header writers take it
+SeqDesc pack_desc(const m2v_stream_desc &d);
 
 // ---- m2v_scene.hip ----
 // The rule of include/m2v_mi355x.h, frame by frame: s = the I picture of the GOP in progress, k = GOP starts so far, list / at = the
@@ -537,20 +522,13 @@ struct GopRule {
         return fl;
     }
 };
-inline bool seq_has_layout(const m2v_enc *e) { return !e->seq_starts.empty() || e->seq_cut; }
-// the start of a sequence samples the list and the threshold (where sample_gop_levels is called; with_cut: the resident entries)
-void sample_gop_starts(m2v_enc *e, bool with_cut);
-// a sequence start with the cap and a list or the detector together: true = refused (M2V_E_STATE)
-bool layout_refuses_cap(m2v_enc *e, const char *fn);
-// the port entries that start a sequence: true = refused (M2V_E_STATE) because option "scene_cut" is set
-bool cut_refuses(m2v_enc *e, const char *fn);
+inline bool seq_has_layout(const m2v_enc *e) { return !e->seq.starts.empty() || e->seq.cut; }
 // option "scene_cut", in front of plan_chunk: k_mbsum and k_scene_judge over the chunk's nf frames on s, then the one wait; leaves
 // e->chunk_cut / e->chunk_diff
 void scene_detect(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf);
-void scene_collect(m2v_enc *e, m2v_enc::HostStage &h);
-void scene_drop(m2v_enc *e);
 void scene_release(m2v_enc *e);
 
+// ---- m2v_port.hip ----
 // PkFrame::layout of a planar 4:4:4 frame of a sequence that pads its frames (no other planar frame travels as a run)
 constexpr int kPk444 = 8;
 // PkFrame::layout of a 4:2:0 frame is kPk420 + M2V_420_*
@@ -568,7 +546,7 @@ inline int rgb_bpp(int layout) { return layout >= M2V_RGB_RGBX32 && layout <= M2
 // source bytes of one frame of a run kind (PkFrame::layout) whose frames are sz (0 x 0: W x H)
 size_t pk_frame_bytes(int kind, const Geom &g, SrcSize sz);
 // the frames of a 4:4:4 (kPk444), 4:2:0 or RGB run kind (back to back at src) -> planar 4:4:4 frames of 3 * ysz bytes at dst (16-byte
-// aligned).  e->fit set: the frames are of that size and are padded first (k_fit; src at any address), into e->d_fit or, 4:4:4, straight
+// aligned).  e->seq.fit set: the frames are of that size and are padded first (k_fit; src at any address), into e->d_fit or, 4:4:4, straight
 // into dst.  Else src is 16-byte aligned.
 void launch_convert(m2v_enc *e, hipStream_t s, int kind, const uint8_t *src, uint8_t *dst, uint32_t nframes);
 // nframes RGB frames (ysz * rgb_bpp(layout) bytes each) -> planar 4:4:4 by the integer transform of include/m2v_mi355x.h (k_rgb2yuv)
@@ -582,46 +560,22 @@ void strip_flight_release(m2v_enc *e);
 void stats_begin_chunk(m2v_enc *e, hipStream_t s, size_t nf);
 // behind the chunk's scans: macroblock counts and bits of its plan_nf frames, then the records into the current stage's pinned memory
 void stats_finish_chunk(m2v_enc *e, hipStream_t s);
-// a completed chunk's records (its stream has been waited for) from the stage to the handle's queue
-void stats_collect(m2v_enc *e, m2v_enc::HostStage &h);
-// a new sequence, or m2v_reset: nothing waits any more
-void stats_drop(m2v_enc *e);
 
 // ---- m2v_recon.hip: m2v_set_recon_out ----
-// a resident sequence of nframes frames of xs x ys macroblocks is about to start: true = refused (M2V_E_OVERFLOW) because the frames do
-// not fit the caller's buffer.  Reads the settings only: called before the start writes anything into the handle
-bool recon_overflows(m2v_enc *e, const char *fn, uint32_t xs, uint32_t ys, size_t nframes);
-// the start of a resident sequence samples the setting (where sample_frame_size is called)
-void sample_recon_out(m2v_enc *e, uint32_t xs, uint32_t ys);
-// the port entries that start a sequence: true = refused (M2V_E_STATE) because a buffer is set
-bool recon_refuses(m2v_enc *e, const char *fn);
+// bytes of one frame k_recon_out writes for a sequence of xs x ys macroblocks
+size_t recon_frame_bytes(const m2v_enc *e, uint32_t xs, uint32_t ys);
 
 // ---- m2v_sequences.hip: m2v_set_sequences ----
-inline bool seq_batch(const m2v_enc *e) { return !e->seq_lens.empty(); }
-// a resident call of nframes frames is about to start: M2V_OK, or M2V_E_PARAM (the list does not add up to nframes, or holds a 0) or
-// M2V_E_STATE (a batch together with a GOP list, the detector or the cap).  Reads the settings only
-int seq_check(m2v_enc *e, const char *fn, size_t nframes);
-// the start of a resident call samples the list (where sample_gop_starts is called) and writes what the host knows of a batch's records
-void sample_sequences(m2v_enc *e);
-// the port entries that start a sequence: true = refused (M2V_E_STATE) because a list is set
-bool seq_refuses(m2v_enc *e, const char *fn);
-// a completed call's records (its stream has been waited for) to the handle's queue; ok = false: the call overflowed, there are none
-void seq_collect(m2v_enc *e, bool ok);
-void seq_drop(m2v_enc *e);
+inline bool seq_batch(const m2v_enc *e) { return !e->seq.lens.empty(); }
+// a batch starts (e->seq.lens and e->pframes are sampled): room for its records, and what the host knows of them into pinned memory
+void seq_begin_call(m2v_enc *e);
 void seq_release(m2v_enc *e);
 
 // ---- m2v_mux.hip: m2v_set_mux_out ----
-// the start of a resident call samples the setting (where sample_recon_out is called)
-void sample_mux_out(m2v_enc *e);
-// a resident call is about to start: true = refused (M2V_E_PARAM) because a container is set and the batch has more clips than a launch takes
-bool mux_too_many(m2v_enc *e, const char *fn);
-// the port entries that start a sequence: true = refused (M2V_E_STATE) because a buffer is set
-bool mux_refuses(m2v_enc *e, const char *fn);
 // behind the last chunk's assembly on s, in front of the control word's copy: the three kernels over the call's stream(s) in d_out
 void mux_resident(m2v_enc *e, hipStream_t s, const uint8_t *d_out, size_t cap, size_t nframes);
-// a completed call's records (its stream has been waited for) to the handle's queue
+// a completed mux's records (its stream has been waited for) to the handle's queue
 void mux_collect(m2v_enc *e);
-void mux_drop(m2v_enc *e);
 void mux_release(m2v_enc *e);
 
 // ---- m2v_launch.hip: everything that touches device code ----

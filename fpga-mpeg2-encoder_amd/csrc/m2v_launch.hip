@@ -367,7 +367,7 @@ void launch_frame_scan(m2v_enc *e, hipStream_t s, const Geom &g, size_t nf, bool
     }
     hipLaunchKernelGGL(k_frame_scan, dim3(1), dim3(1024), 0, s, e->d_jobs.p, g, (int)nf, first ? 1 : 0, last ? 1 : 0,
                        e->d_slice_bytes.p, e->d_slice_off.p, e->d_frame_off.p, e->d_ctl.p, advance ? 1 : 0, (uint32_t *)d_stream,
-                       e->ctl_init, e->ctl_cap, px, (int)e->seq_desc.repeat());
+                       e->ctl_init, e->ctl_cap, px, (int)e->seq.desc.repeat());
     e->ctl_init = 0;
 }
 
@@ -377,7 +377,7 @@ void launch_seq_scan(m2v_enc *e, hipStream_t s, const Geom &g, size_t nf, bool a
     e->d_seqtmp.ensure(2 * e->plan_nsq + 1);
     hipLaunchKernelGGL(k_seq_scan, dim3(1), dim3(kSeqThreads), 0, s, e->d_jobs.p, g, (int)nf, e->d_slice_bytes.p, e->d_slice_off.p,
                        e->d_frame_off.p, e->d_ctl.p, advance ? 1 : 0, (uint32_t *)d_stream, e->ctl_init, e->ctl_cap,
-                       (int)e->seq_desc.repeat(), e->d_seqtmp.p, e->d_seq.p, e->h_seq, (int)e->plan_seq0);
+                       (int)e->seq.desc.repeat(), e->d_seqtmp.p, e->d_seq.p, e->h_seq, (int)e->plan_seq0);
     e->ctl_init = 0;
 }
 
@@ -386,11 +386,11 @@ void launch_assemble(m2v_enc *e, hipStream_t s, const Geom &g, size_t nf, bool f
 {
     const size_t rows = (size_t)(g.row1 - g.row0);
     // the size the sequence headers print: the coded one, or the source's (m2v_set_frame_size, M2V_HEADER_TRUE; never in strip mode)
-    const bool true_size = e->hdr_true && e->fit.w && !g.strip;
+    const bool true_size = e->seq.hdr_true && e->seq.fit.w && !g.strip;
     hipLaunchKernelGGL(k_assemble, dim3((unsigned)(nf * rows)), dim3(kAsmThreads), 0, s, e->d_jobs.p, g, (int)nf,
                        e->d_mbinfo.p, e->d_mbaux.p, e->d_slots_small.p, e->d_slots.p, e->d_slice_off.p,
                        (uint32_t *)d_stream, e->d_ctl.p, first ? 1 : 0, last ? 1 : 0, e->d_frame_off.p, e->d_slice_bytes.p,
-                       true_size ? e->fit.w : g.W, true_size ? e->fit.h : g.H, e->seq_desc);
+                       true_size ? e->seq.fit.w : g.W, true_size ? e->seq.fit.h : g.H, e->seq.desc);
 }
 
 void launch_halo_pack(m2v_enc *e, hipStream_t s, const int *d_list, int count, uint8_t *up, uint8_t *down)
@@ -425,7 +425,7 @@ void launch_picstat(m2v_enc *e, hipStream_t s, const int *d_list, int count)
     const dim3 grid((units + kStatWaves * kUnitsPerWave - 1) / (kStatWaves * kUnitsPerWave), (unsigned)count);
     // measured region: the source's size while the sequence pads its frames (m2v_set_frame_size), else the coded picture
     StatRegion m{g.W, g.H, g.cw, g.ch};
-    if (e->fit.w) m = StatRegion{e->fit.w, e->fit.h, (e->fit.w + 1) / 2, (e->fit.h + 1) / 2};
+    if (e->seq.fit.w) m = StatRegion{e->seq.fit.w, e->seq.fit.h, (e->seq.fit.w + 1) / 2, (e->seq.fit.h + 1) / 2};
     hipLaunchKernelGGL(k_picstat, grid, dim3(kStatThreads), 0, s, e->d_joblist.p + (d_list - e->d_lists.p), g, m, e->d_pstat.p);
     HIPCHK(hipGetLastError());
 }
@@ -442,10 +442,10 @@ void launch_recon_out(m2v_enc *e, hipStream_t s, const int *d_list, int count)
 {
     if (count <= 0) return;
     const Geom &g = e->g;
-    const m2v_enc::ReconDst &d = e->seq_recon;
+    const m2v_enc::ReconDst &d = e->seq.recon;
     ReconOut m{};
-    m.w = e->fit.w ? e->fit.w : g.W;
-    m.h = e->fit.w ? e->fit.h : g.H;
+    m.w = e->seq.fit.w ? e->seq.fit.w : g.W;
+    m.h = e->seq.fit.w ? e->seq.fit.h : g.H;
     m.cw = (m.w + 1) / 2;
     m.ch = (m.h + 1) / 2;
     auto magic = [](uint32_t d) { return (uint32_t)std::min<unsigned long long>(0x100000000ull / d, 0xFFFFFFFFull); };

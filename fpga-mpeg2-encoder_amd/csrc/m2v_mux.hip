@@ -242,36 +242,20 @@ static const m2v_mux_stat *mux_records(const m2v_enc *e)
     return (const m2v_mux_stat *)(e->h_mux + sizeof(MuxHead) + e->mux_n * sizeof(mux::Stream));
 }
 
-void sample_mux_out(m2v_enc *e) { e->seq_mux = e->mux_out; }
-
-bool mux_too_many(m2v_enc *e, const char *fn)
-{
-    if (!e->mux_out.kind || e->sequences.size() <= 65535) return false;
-    e->set_err("%s: a container buffer is set (m2v_set_mux_out): at most 65535 clips in a batch", fn);
-    return true;
-}
-
-bool mux_refuses(m2v_enc *e, const char *fn)
-{
-    if (!e->mux_out.kind) return false;
-    e->set_err("%s: a container buffer is set (m2v_set_mux_out): it is a device buffer, filled by the resident entries", fn);
-    return true;
-}
-
 // behind the last chunk's assembly, in front of the control word's copy: the call's stream, or one per clip of a batch
 void mux_resident(m2v_enc *e, hipStream_t s, const uint8_t *d_out, size_t cap, size_t nframes)
 {
-    if (!e->seq_mux.kind) return;
-    const size_t nstreams = seq_batch(e) ? e->seq_lens.size() : 1;
+    if (!e->seq.mux.kind) return;
+    const size_t nstreams = seq_batch(e) ? e->seq.lens.size() : 1;
     // (the encoder writes at most a sequence header, a GOP header and a picture header per picture, and one end code)
     std::vector<uint32_t> caps(nstreams);
-    for (size_t b = 0; b < nstreams; ++b) caps[b] = pow2_at_least(3 * (size_t)(seq_batch(e) ? e->seq_lens[b] : nframes) + 2);
+    for (size_t b = 0; b < nstreams; ++b) caps[b] = pow2_at_least(3 * (size_t)(seq_batch(e) ? e->seq.lens[b] : nframes) + 2);
     MuxSrc src{nullptr, &e->d_ctl.p->total_bytes, 0, &e->d_ctl.p->overflow};
     if (seq_batch(e)) {
         static_assert(sizeof(m2v_sequence_stat) == 32 && offsetof(m2v_sequence_stat, bytes) == 8, "offset and bytes of a batch's records");
         src = MuxSrc{&e->d_seq.p->offset, &e->d_seq.p->bytes, 4, &e->d_ctl.p->overflow};
     }
-    mux_enqueue(e, s, e->seq_mux.kind, nstreams, caps, nullptr, nullptr, src, d_out, e->seq_mux.p, e->seq_mux.cap, cap);
+    mux_enqueue(e, s, e->seq.mux.kind, nstreams, caps, nullptr, nullptr, src, d_out, e->seq.mux.p, e->seq.mux.cap, cap);
     e->mux_pending = true;
 }
 
@@ -280,14 +264,8 @@ void mux_collect(m2v_enc *e)
     if (!e->mux_pending) return;
     e->mux_pending = false;
     const m2v_mux_stat *r = mux_records(e);
-    e->mux_q.assign(r, r + e->mux_n);
-    for (auto &q : e->mux_q) if (q.status == mux::kEvents) q.status = M2V_MUX_SYNTAX;      // (more headers than the encoder writes)
-}
-
-void mux_drop(m2v_enc *e)
-{
-    e->mux_q.clear();
-    e->mux_pending = false;
+    e->mux_q.push(r, r + e->mux_n);               // (the queue was emptied when the call started)
+    for (auto &q : e->mux_q.q) if (q.status == mux::kEvents) q.status = M2V_MUX_SYNTAX;      // (more headers than the encoder writes)
 }
 
 void mux_release(m2v_enc *e)
@@ -305,7 +283,7 @@ static int mux_device_impl(m2v_enc *e, void *argp)
 {
     auto *a = (MuxDeviceArgs *)argp;
     hipStream_t s = a->s ? a->s : e->stream;
-    mux_drop(e);
+    e->mux_q.clear();
     size_t longest = 0;
     std::vector<uint32_t> caps(a->n);
     for (size_t b = 0; b < a->n; ++b) {
@@ -346,26 +324,19 @@ int m2v_mux_scan_tile(void) { return (int)mux::kScanTile; }
 int m2v_set_mux_out(m2v_enc *e, int kind, void *d_dst, size_t cap)
 {
     if (!e) return M2V_E_PARAM;
-    if (e->state != m2v_enc::IDLE || e->resident_inflight || e->strip_active || e->strip_inflight) {
-        e->set_err("m2v_set_mux_out: a sequence is in progress (the buffer is sampled when a sequence starts)");
-        return M2V_E_STATE;
-    }
+    if (in_progress(e, "m2v_set_mux_out", "the buffer is sampled when a sequence starts")) return M2V_E_STATE;
     if (kind != M2V_MUX_NONE && kind != M2V_MUX_TS && kind != M2V_MUX_PS) { e->set_err("m2v_set_mux_out: unknown kind %d", kind); return M2V_E_PARAM; }
     if (kind != M2V_MUX_NONE && !d_dst) { e->set_err("m2v_set_mux_out: d_dst is NULL"); return M2V_E_PARAM; }
-    e->seq_mux = m2v_enc::MuxDst{};
-    e->mux_out = m2v_enc::MuxDst{};
-    if (kind != M2V_MUX_NONE) { e->mux_out.kind = kind; e->mux_out.p = (uint8_t *)d_dst; e->mux_out.cap = cap; }
+    e->seq.mux = m2v_enc::MuxDst{};
+    e->set.mux = m2v_enc::MuxDst{};
+    if (kind != M2V_MUX_NONE) { e->set.mux.kind = kind; e->set.mux.p = (uint8_t *)d_dst; e->set.mux.cap = cap; }
     return M2V_OK;
 }
 
 int m2v_mux_report(m2v_enc *e, m2v_mux_stat *out, size_t max)
 {
     if (!e) return M2V_E_PARAM;
-    if (!out) return (int)std::min<size_t>(e->mux_q.size(), 0x7FFFFFFF);
-    const size_t n = std::min<size_t>({max, e->mux_q.size(), (size_t)0x7FFFFFFF});
-    std::copy(e->mux_q.begin(), e->mux_q.begin() + (std::ptrdiff_t)n, out);
-    e->mux_q.erase(e->mux_q.begin(), e->mux_q.begin() + (std::ptrdiff_t)n);
-    return (int)n;
+    return e->mux_q.pop31(out, max);
 }
 
 int m2v_mux_device(m2v_enc *e, int kind, const void *d_es, const uint64_t *es_off, const uint64_t *es_bytes, size_t nstreams, void *d_dst,
@@ -375,10 +346,7 @@ int m2v_mux_device(m2v_enc *e, int kind, const void *d_es, const uint64_t *es_of
     if (kind != M2V_MUX_TS && kind != M2V_MUX_PS) { e->set_err("m2v_mux_device: unknown kind %d", kind); return M2V_E_PARAM; }
     if (!d_es || !es_off || !es_bytes || !d_dst || !nstreams) { e->set_err("m2v_mux_device: a pointer is NULL or there is no stream"); return M2V_E_PARAM; }
     if (nstreams > 65535) { e->set_err("m2v_mux_device: at most 65535 streams in a call"); return M2V_E_PARAM; }
-    if (e->state != m2v_enc::IDLE || e->resident_inflight || e->strip_active || e->strip_inflight) {
-        e->set_err("m2v_mux_device: a sequence is in progress (m2v_encode_resident_end first)");
-        return M2V_E_STATE;
-    }
+    if (in_progress(e, "m2v_mux_device", "m2v_encode_resident_end first")) return M2V_E_STATE;
     MuxDeviceArgs a{kind, (const uint8_t *)d_es, es_off, es_bytes, nstreams, (uint8_t *)d_dst, cap, (hipStream_t)hip_stream};
     return guard(e, mux_device_impl, &a);
 }

@@ -365,35 +365,19 @@ static void convert_run(hipStream_t s, int kind, const uint8_t *src, uint8_t *ds
 void launch_convert(m2v_enc *e, hipStream_t s, int kind, const uint8_t *src, uint8_t *dst, uint32_t nframes)
 {
     const Geom &g = e->g;
-    if (!e->fit.w) { convert_run(s, kind, src, dst, g, nframes); return; }
-    if (kind == kPk444) { launch_fit_frames(s, kind, src, dst, g, e->fit, nframes); return; }
+    if (!e->seq.fit.w) { convert_run(s, kind, src, dst, g, nframes); return; }
+    if (kind == kPk444) { launch_fit_frames(s, kind, src, dst, g, e->seq.fit, nframes); return; }
     // the padded frames wait in a buffer of the handle's for the conversion behind them on the same stream; a long run takes turns in
     // 128 MB of it (twenty 1920 x 1088 RGB24 frames)
-    const size_t sfb = pk_frame_bytes(kind, g, e->fit), dfb = pk_frame_bytes(kind, g, SrcSize{});
+    const size_t sfb = pk_frame_bytes(kind, g, e->seq.fit), dfb = pk_frame_bytes(kind, g, SrcSize{});
     const uint32_t part = (uint32_t)std::min<size_t>(nframes, std::max<size_t>(1, ((size_t)128 << 20) / dfb));
     e->d_fit.recorded = false;
     e->d_fit.ensure((size_t)part * dfb);
     for (uint32_t k = 0; k < nframes; k += part) {
         const uint32_t n = std::min(part, nframes - k);
-        launch_fit_frames(s, kind, src + (size_t)k * sfb, e->d_fit.p, g, e->fit, n);
+        launch_fit_frames(s, kind, src + (size_t)k * sfb, e->d_fit.p, g, e->seq.fit, n);
         convert_run(s, kind, e->d_fit.p, dst + (size_t)k * g.ysz * 3, g, n);
     }
-}
-
-bool sample_frame_size(m2v_enc *e, const char *fn, uint32_t xs, uint32_t ys)
-{
-    e->fit = SrcSize{};
-    e->hdr_true = false;
-    const SrcSize z = e->src_size;
-    if (!z.w) return true;
-    uint32_t fx = 0, fy = 0;
-    (void)m2v_fit_size(z.w, z.h, &fx, &fy);
-    if (xs != fx || ys != fy) {
-        e->set_err("%s: xsize16, ysize16 = %u, %u, but the frame size set is %d x %d (m2v_fit_size: %u, %u)", fn, xs, ys, z.w, z.h, fx, fy);
-        return false;
-    }
-    if ((z.w | z.h) & 15) { e->fit = z; e->hdr_true = e->src_header == M2V_HEADER_TRUE; }
-    return true;
 }
 
 void launch_expand420(hipStream_t s, int layout, const uint8_t *src, uint8_t *dst, const Geom &g, uint32_t nframes)
@@ -474,8 +458,7 @@ void progress(m2v_enc *e, bool block, int until = -1, PullSink *sink = nullptr)
         e->fifo.insert(e->fifo.end(), h.h_out + direct, h.h_out + h.bytes);
         e->stream_bytes += h.bytes;
         if (h.last) e->end_pending = true;
-        stats_collect(e, h);            // (the chunk's picture records came back in front of its control word)
-        scene_collect(e, h);
+        collect_chunk(e, h);            // (the records came back in front of the control word; the port samples no cap, so a stage's GOP count is 0 here)
         h.stage = 0;
         e->pending.pop_front();
         if (idx == until) break;
@@ -534,7 +517,7 @@ void flush_buffered(m2v_enc *e, bool last)
         timer_break(e);
         for (size_t a = 0; a < h.pk.size();) {          // runs of consecutive frames of one layout: one launch each
             const int layout = h.pk[a].layout;
-            const size_t src_bytes = pk_frame_bytes(layout, g, e->fit);
+            const size_t src_bytes = pk_frame_bytes(layout, g, e->seq.fit);
             size_t b = a + 1;
             while (b < h.pk.size() && h.pk[b].layout == layout && h.pk[b].frame == h.pk[a].frame + (b - a) &&
                    h.pk[b].off == h.pk[a].off + (b - a) * src_bytes) ++b;
@@ -571,23 +554,16 @@ void flush_buffered(m2v_enc *e, bool last)
     progress(e, false);
 }
 
-void start_sequence(m2v_enc *e, uint32_t xs, uint32_t ys, uint32_t pf)
+// the port's own part of a sequence start (begin_sequence has sampled the settings and latched the geometry): streams, staging, FIFO
+void open_port(m2v_enc *e)
 {
     if (!e->copy_stream) HIPCHK(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
     if (!e->up_stream) HIPCHK(hipStreamCreateWithFlags(&e->up_stream, hipStreamNonBlocking));
     e->up_wait_ev = nullptr;
-    e->g = make_geom(e, xs, ys);            // latched on the first beat (RTL:1060-1065)
-    e->pframes = pf & 0xFFu;
-    sample_gop_levels(e, false);            // (the schedule; the cap is the resident entries': the callers refuse with it set)
-    sample_gop_starts(e, false);            // (the list; the detector likewise)
-    e->seq_lens.clear();                    // (a batch is the resident entries': the callers refuse with a list set)
-    sample_stream_desc(e);
     e->state = m2v_enc::DURING;
-    e->frames_total = 0;
     e->first_chunk = true;
     e->buffered = 0;
     e->beat_pos = 0;
-    e->persist_slot = -1;
     e->end_pending = false;
     e->last_frame_valid_beats = e->g.ysz / 4;
     for (auto &h : e->hs) { h.uploaded = 0; h.pk.clear(); h.pk_used = h.pk_valid = h.pk_up = 0; }
@@ -595,10 +571,6 @@ void start_sequence(m2v_enc *e, uint32_t xs, uint32_t ys, uint32_t pf)
     e->fifo.clear();
     e->fifo_rd = 0;
     e->stream_bytes = 0;
-    stats_drop(e);
-    gop_drop(e);
-    scene_drop(e);
-    for (auto &st : e->stats) st = KStat{};
     ensure_staging(e);
 }
 
@@ -689,7 +661,7 @@ static void pk_put(m2v_enc *e, m2v_enc::HostStage &h, size_t off, const uint8_t 
 static int push_beats_impl(m2v_enc *e, void *argp)
 {
     auto *a = (PushBeatsArgs *)argp;
-    if (size_refuses(e, a->src.kind ? "m2v_push_packed" : "m2v_push_beats", kNoBeats)) return M2V_E_STATE;
+    if (size_refuses_beats(e, a->src.kind ? "m2v_push_packed" : "m2v_push_beats")) return M2V_E_STATE;
     if (e->strip_active) { e->set_err("m2v_push_*: a strip sequence is open (m2v_strip_finish or m2v_reset first)"); return M2V_E_STATE; }
     if (e->resident_inflight) { e->set_err("m2v_push_*: a resident sequence is in flight (m2v_encode_resident_end first)"); return M2V_E_STATE; }
     if (e->strip_inflight) { e->set_err("m2v_push_*: a strip sequence is in flight (m2v_strip_encode_end first)"); return M2V_E_STATE; }
@@ -700,8 +672,8 @@ static int push_beats_impl(m2v_enc *e, void *argp)
         return M2V_OK;
     }
     if (e->state == m2v_enc::IDLE) {
-        if (cap_refuses(e, "m2v_push_beats") || cut_refuses(e, "m2v_push_beats") || seq_refuses(e, "m2v_push_beats") || recon_refuses(e, "m2v_push_beats") || mux_refuses(e, "m2v_push_beats")) return M2V_E_STATE;
-        start_sequence(e, a->xs, a->ys, a->pf);
+        if (const int r = begin_sequence(e, "m2v_push_beats", Entry::Beats, a->xs, a->ys, a->pf, a->n)) return r;
+        open_port(e);
     }
     const Geom &g = e->g;
     const size_t bpf = g.ysz / 4;
@@ -855,14 +827,13 @@ static int push_frames_impl(m2v_enc *e, void *argp)
     if (e->state == m2v_enc::ENDED || a->n == 0) { settle_deferred(); return M2V_OK; }
     if (e->state == m2v_enc::IDLE) {
         const char *fn = a->kind < 0 ? "m2v_push_frames" : a->kind >= kPkRgb ? "m2v_push_rgb" : "m2v_push_frames420";      // (the entry a refusal names)
-        if (cap_refuses(e, fn) || cut_refuses(e, fn) || seq_refuses(e, fn) || recon_refuses(e, fn) || mux_refuses(e, fn)) { settle_deferred(); return M2V_E_STATE; }
-        if (!sample_frame_size(e, fn, a->xs, a->ys)) { settle_deferred(); return M2V_E_PARAM; }
-        start_sequence(e, a->xs, a->ys, a->pf);
+        if (const int r = begin_sequence(e, fn, Entry::Frames, a->xs, a->ys, a->pf, a->n)) { settle_deferred(); return r; }
+        open_port(e);
     }
     const Geom &g = e->g;
-    const int kind = a->kind < 0 && e->fit.w ? kPk444 : a->kind;       // (planar 4:4:4 frames that have to be padded are a run too)
+    const int kind = a->kind < 0 && e->seq.fit.w ? kPk444 : a->kind;       // (planar 4:4:4 frames that have to be padded are a run too)
     const bool is420 = kind >= 0;                 // (or RGB: any kind that goes through the packed bytes)
-    const size_t fb = is420 ? pk_frame_bytes(kind, g, e->fit) : (size_t)g.ysz * 3;      // the caller's bytes per frame
+    const size_t fb = is420 ? pk_frame_bytes(kind, g, e->seq.fit) : (size_t)g.ysz * 3;      // the caller's bytes per frame
     if (e->beat_pos != 0) {
         settle_deferred();
         e->set_err("m2v_push_frames: a frame is partially filled by m2v_push_beats");

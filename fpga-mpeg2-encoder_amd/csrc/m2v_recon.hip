@@ -14,34 +14,11 @@ namespace m2v {
 
 // bytes of one frame k_recon_out writes: the size set (m2v_set_frame_size: the source's size while the sequence pads its frames, and the
 // coded size where it is whole macroblocks), else the coded picture of xs x ys macroblocks
-static size_t recon_frame_bytes(const m2v_enc *e, uint32_t xs, uint32_t ys)
+size_t recon_frame_bytes(const m2v_enc *e, uint32_t xs, uint32_t ys)
 {
     const Geom g = make_geom(e, xs, ys);
-    const size_t w = e->src_size.w ? (size_t)e->src_size.w : (size_t)g.W, h = e->src_size.w ? (size_t)e->src_size.h : (size_t)g.H;
+    const size_t w = e->set.size.w ? (size_t)e->set.size.w : (size_t)g.W, h = e->set.size.w ? (size_t)e->set.size.h : (size_t)g.H;
     return w * h + 2 * ((w + 1) / 2) * ((h + 1) / 2);
-}
-
-bool recon_overflows(m2v_enc *e, const char *fn, uint32_t xs, uint32_t ys, size_t nframes)
-{
-    const m2v_enc::ReconDst &d = e->recon_out;
-    if (!d.p) return false;
-    const size_t fb = recon_frame_bytes(e, xs, ys);
-    if (nframes <= d.cap / fb) return false;
-    e->set_err("%s: %zu frames of %zu bytes do not fit the buffer of m2v_set_recon_out (%zu bytes)", fn, nframes, fb, d.cap);
-    return true;
-}
-
-void sample_recon_out(m2v_enc *e, uint32_t xs, uint32_t ys)
-{
-    e->seq_recon = e->recon_out;
-    if (e->seq_recon.p) e->seq_recon.fb = recon_frame_bytes(e, xs, ys);
-}
-
-bool recon_refuses(m2v_enc *e, const char *fn)
-{
-    if (!e->recon_out.p) return false;
-    e->set_err("%s: a buffer for the reconstruction is set (m2v_set_recon_out): it is a device buffer, filled by the resident entries", fn);
-    return true;
 }
 
 }  // namespace m2v
@@ -49,14 +26,11 @@ bool recon_refuses(m2v_enc *e, const char *fn)
 extern "C" int m2v_set_recon_out(m2v_enc *e, void *d_dst, size_t cap, int layout)
 {
     if (!e) return M2V_E_PARAM;
-    if (e->state != m2v_enc::IDLE || e->resident_inflight || e->strip_active || e->strip_inflight) {
-        e->set_err("m2v_set_recon_out: a sequence is in progress (the buffer is sampled when a sequence starts)");
-        return M2V_E_STATE;
-    }
+    if (in_progress(e, "m2v_set_recon_out", "the buffer is sampled when a sequence starts")) return M2V_E_STATE;
     if (d_dst && !layout420_ok(layout)) { e->set_err("m2v_set_recon_out: unknown layout %d", layout); return M2V_E_PARAM; }
-    // (what the last sequence sampled goes with the old setting: the port and strip entries sample nothing, and only run with no buffer set)
-    e->seq_recon = m2v_enc::ReconDst{};
-    e->recon_out = m2v_enc::ReconDst{};
-    if (d_dst) { e->recon_out.p = (uint8_t *)d_dst; e->recon_out.cap = cap; e->recon_out.layout = layout; }
+    // (what the last sequence sampled goes with the old setting)
+    e->seq.recon = m2v_enc::ReconDst{};
+    e->set.recon = m2v_enc::ReconDst{};
+    if (d_dst) { e->set.recon.p = (uint8_t *)d_dst; e->set.recon.cap = cap; e->set.recon.layout = layout; }
     return M2V_OK;
 }

@@ -17,11 +17,8 @@ static int resident_end_impl(m2v_enc *e, void *argp)
     e->resident_inflight = false;
     HIPCHK(hipStreamSynchronize(e->resident_stream));
     collect_timers(e);
-    stats_collect(e, e->st());
-    gop_collect(e, e->st());
-    scene_collect(e, e->st());
-    seq_collect(e, !e->st().h_ctl->overflow);
-    mux_collect(e);
+    collect_chunk(e, e->st());
+    collect_call(e, !e->st().h_ctl->overflow);
     if (e->st().h_ctl->overflow) { e->set_err("output buffer too small"); return M2V_E_OVERFLOW; }
     if (bytes) *bytes = (size_t)e->st().h_ctl->total_bytes;
     return M2V_OK;
@@ -30,42 +27,15 @@ static int resident_end_impl(m2v_enc *e, void *argp)
 static int resident_impl(m2v_enc *e, void *argp)
 {
     auto *a = (ResidentArgs *)argp;
-    if (e->state != m2v_enc::IDLE || e->strip_active || e->resident_inflight || e->strip_inflight) { e->set_err("m2v_encode_resident: encoder busy"); return M2V_E_STATE; }
     // (the entry a refusal names: the _begin halves share the prefix)
     const char *fn = a->kind < 0 ? "m2v_encode_resident" : a->kind >= kPkRgb ? "m2v_encode_resident_rgb" : "m2v_encode_resident420";
-    if (const int r = seq_check(e, fn, a->n)) return r;      // (nothing of the handle has changed)
-    e->resident_empty = false;
-    stats_drop(e);                                      // (the previous sequence's unread picture records)
-    gop_drop(e);
-    scene_drop(e);
-    seq_drop(e);
-    mux_drop(e);
+    if (const int r = begin_sequence(e, fn, Entry::Resident, a->xs, a->ys, a->pf, a->n)) return r;
     if (a->n == 0) {                                    // no beat: the sequence never starts
         if (a->bytes) *a->bytes = 0;
         e->resident_empty = a->async;                   // only _begin leaves an _end to answer
         return M2V_OK;
     }
-    if (layout_refuses_cap(e, fn)) return M2V_E_STATE;
-    if (mux_too_many(e, fn)) return M2V_E_PARAM;
-    if (recon_overflows(e, fn, a->xs, a->ys, a->n)) return M2V_E_OVERFLOW;      // (nothing of the handle has changed)
-    if (!sample_frame_size(e, fn, a->xs, a->ys)) return M2V_E_PARAM;
-    if (e->gop_bytes_max && (size_t)(a->pf & 0xFFu) + 1 > e->batch_frames) {
-        e->set_err("m2v_encode_resident: option \"gop_bytes_max\" needs whole GOPs in a chunk: pframes_count + 1 = %u is more than batch_frames = %zu",
-                   (a->pf & 0xFFu) + 1u, e->batch_frames);
-        return M2V_E_PARAM;
-    }
     hipStream_t s = a->s ? a->s : e->stream;
-    e->g = make_geom(e, a->xs, a->ys);
-    e->pframes = a->pf & 0xFFu;
-    sample_recon_out(e, a->xs, a->ys);
-    sample_mux_out(e);
-    sample_gop_levels(e, true);
-    sample_gop_starts(e, true);
-    sample_stream_desc(e);
-    sample_sequences(e);
-    e->frames_total = 0;
-    e->persist_slot = -1;
-    for (auto &st : e->stats) st = KStat{};
     const Geom &g = e->g;
     const size_t fb = (size_t)g.ysz * 3;
     // the control word is set up by the first chunk's k_frame_scan (no launch, no copy in front of the first kernel)
@@ -76,9 +46,9 @@ static int resident_impl(m2v_enc *e, void *argp)
     const size_t gop = e->pframes + 1u;
     size_t step = chunk >= gop ? chunk / gop * gop : chunk;
     if (seq_batch(e)) step = chunk;               // (a batch's GOPs count from their sequences' starts: there is no grid to align to)
-    const int kind = a->kind < 0 && e->fit.w ? kPk444 : a->kind;       // (planar 4:4:4 frames that have to be padded: through the handle's buffer too)
+    const int kind = a->kind < 0 && e->seq.fit.w ? kPk444 : a->kind;       // (planar 4:4:4 frames that have to be padded: through the handle's buffer too)
     const bool is420 = kind >= 0;                 // (or RGB)
-    const size_t fb420 = is420 ? pk_frame_bytes(kind, g, e->fit) : 0;
+    const size_t fb420 = is420 ? pk_frame_bytes(kind, g, e->seq.fit) : 0;
     if (is420) {
         // each chunk's frames are expanded or converted into planar 4:4:4 in front of its kernels, on the same stream; one buffer is enough because
         // the chunks are synchronised below
@@ -95,9 +65,9 @@ static int resident_impl(m2v_enc *e, void *argp)
             e->x444_bytes = nf * fb;
             frames = e->d_x444.p;
         }
-        if (e->seq_cut) scene_detect(e, s, frames, nf);        // option "scene_cut": the chunk's flags in front of its plan (waits for the device)
+        if (e->seq.cut) scene_detect(e, s, frames, nf);        // option "scene_cut": the chunk's flags in front of its plan (waits for the device)
         encode_chunk(e, s, frames, nf, first, last, g.ysz / 4, a->d_out, /*advance=*/k > 0);
-        if (!last) { HIPCHK(hipStreamSynchronize(s)); stats_collect(e, e->st()); gop_collect(e, e->st()); scene_collect(e, e->st()); }    // the per-chunk work buffers are reused
+        if (!last) { HIPCHK(hipStreamSynchronize(s)); collect_chunk(e, e->st()); }    // the per-chunk work buffers are reused
     }
     mux_resident(e, s, a->d_out, a->cap, a->n);         // m2v_set_mux_out: the container out of the finished stream (nothing with no buffer set)
     HIPCHK(hipMemcpyAsync(e->st().h_ctl, e->d_ctl.p, sizeof(StreamCtl), hipMemcpyDeviceToHost, s));

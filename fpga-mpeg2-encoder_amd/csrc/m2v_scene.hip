@@ -17,32 +17,6 @@ static_assert(sizeof(m2v_scene_stat) == 16, "the record of include/m2v_mi355x.h 
 
 namespace m2v {
 
-void sample_gop_starts(m2v_enc *e, bool with_cut)
-{
-    e->seq_starts = e->gop_starts;
-    e->seq_cut = with_cut ? e->scene_cut : 0;
-    e->gop_s = 0;
-    e->gop_k = 0;
-    e->carry_cur = -1;
-    e->chunk_cut.clear();
-    e->chunk_diff.clear();
-}
-
-bool layout_refuses_cap(m2v_enc *e, const char *fn)
-{
-    if (!e->gop_bytes_max || (e->gop_starts.empty() && !e->scene_cut)) return false;
-    e->set_err("%s: option \"gop_bytes_max\" is set together with GOP starts (m2v_set_gop_starts or option \"scene_cut\"): the cap judges GOPs of "
-               "the fixed cadence", fn);
-    return true;
-}
-
-bool cut_refuses(m2v_enc *e, const char *fn)
-{
-    if (!e->scene_cut) return false;
-    e->set_err("%s: option \"scene_cut\" is set: the detector runs in front of a chunk's plan, which only the resident entries wait for", fn);
-    return true;
-}
-
 void scene_detect(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf)
 {
     const Geom &g = e->g;
@@ -64,7 +38,7 @@ void scene_detect(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf)
     {
         Timer t(e, s, 5, (double)nf * g.ysz);
         launch_mbsum(e, s, d_frames, nf);
-        launch_scene_judge(e, s, nf, (unsigned long long)e->seq_cut * (unsigned long long)g.mbs,
+        launch_scene_judge(e, s, nf, (unsigned long long)e->seq.cut * (unsigned long long)g.mbs,
                            e->carry_cur < 0 ? nullptr : e->d_carry.p + (size_t)e->carry_cur * (size_t)g.mbs,
                            e->d_carry.p + (size_t)out * (size_t)g.mbs, e->h_scene);
         t.stop();
@@ -77,18 +51,6 @@ void scene_detect(m2v_enc *e, hipStream_t s, const uint8_t *d_frames, size_t nf)
     e->chunk_cut.resize(nf);
     e->chunk_diff.resize(nf);
     for (size_t k = 0; k < nf; ++k) { e->chunk_cut[k] = (uint8_t)(r[k].flag != 0); e->chunk_diff[k] = r[k].diff; }
-}
-
-void scene_collect(m2v_enc *e, m2v_enc::HostStage &h)
-{
-    e->scene_q.insert(e->scene_q.end(), h.scene.begin(), h.scene.end());
-    h.scene.clear();
-}
-
-void scene_drop(m2v_enc *e)
-{
-    e->scene_q.clear();
-    for (auto &h : e->hs) h.scene.clear();
 }
 
 void scene_release(m2v_enc *e)
@@ -112,12 +74,12 @@ extern "C" {
 int m2v_set_gop_starts(m2v_enc *e, const uint32_t *frames, size_t n)
 {
     if (!e) return M2V_E_PARAM;
-    if (!frames || !n) { e->gop_starts.clear(); return M2V_OK; }
+    if (!frames || !n) { e->set.gop_starts.clear(); return M2V_OK; }
     if (!ascending(frames, n)) {
         e->set_err("m2v_set_gop_starts: the list must be strictly ascending frame numbers (the previous setting stays)");
         return M2V_E_PARAM;
     }
-    try { e->gop_starts.assign(frames, frames + n); }
+    try { e->set.gop_starts.assign(frames, frames + n); }
     catch (...) { e->set_err("m2v_set_gop_starts: host allocation failed"); return M2V_E_NOMEM; }
     return M2V_OK;
 }
@@ -137,11 +99,7 @@ long long m2v_gop_layout(uint32_t pframes_count, const uint32_t *starts, size_t 
 long long m2v_scene_report(m2v_enc *e, m2v_scene_stat *dst, size_t cap)
 {
     if (!e) return M2V_E_PARAM;
-    if (!dst) return (long long)e->scene_q.size();
-    const size_t n = std::min(cap, e->scene_q.size());
-    std::copy(e->scene_q.begin(), e->scene_q.begin() + (std::ptrdiff_t)n, dst);
-    e->scene_q.erase(e->scene_q.begin(), e->scene_q.begin() + (std::ptrdiff_t)n);
-    return (long long)n;
+    return (long long)e->scene_q.pop(dst, cap);
 }
 
 }  // extern "C"

@@ -38,26 +38,10 @@ void stats_finish_chunk(m2v_enc *e, hipStream_t s)
     h.nstat = nf;
 }
 
-void stats_collect(m2v_enc *e, m2v_enc::HostStage &h)
-{
-    e->pstat_q.insert(e->pstat_q.end(), h.h_pstat, h.h_pstat + h.nstat);
-    h.nstat = 0;
-}
-
-void stats_drop(m2v_enc *e)
-{
-    e->pstat_q.clear();
-    for (auto &h : e->hs) h.nstat = 0;
-}
-
 }  // namespace m2v
 
 extern "C" long long m2v_picture_stats(m2v_enc *e, m2v_picture_stat *dst, size_t cap)
 {
     if (!e) return M2V_E_PARAM;
-    if (!dst) return (long long)e->pstat_q.size();
-    const size_t n = std::min(cap, e->pstat_q.size());
-    std::copy(e->pstat_q.begin(), e->pstat_q.begin() + (std::ptrdiff_t)n, dst);
-    e->pstat_q.erase(e->pstat_q.begin(), e->pstat_q.begin() + (std::ptrdiff_t)n);
-    return (long long)n;
+    return (long long)e->pstat_q.pop(dst, cap);
 }

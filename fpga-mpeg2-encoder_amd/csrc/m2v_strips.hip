@@ -23,13 +23,11 @@ static int strip_begin_impl(m2v_enc *e, void *argp)
     if (e->state != m2v_enc::IDLE || e->strip_active || e->resident_inflight || e->strip_inflight) { e->set_err("m2v_strip_begin: encoder busy"); return M2V_E_STATE; }
     Geom g = make_geom(e, a->xs, a->ys);
     if (a->n == 0 || a->row0 < 0 || a->row1 > g.mbh || a->row0 >= a->row1) { e->set_err("m2v_strip_begin: bad rows / no frames"); return M2V_E_PARAM; }
+    // (the entry has answered the rule's refusals in front of the busy check: what is left of this is the start)
+    if (const int r = begin_sequence(e, "m2v_strip_begin", Entry::Strip, a->xs, a->ys, a->pf, a->n)) return r;
     g.row0 = a->row0; g.row1 = a->row1; g.strip = 1;
     geom_finish(g);
     e->g = g;
-    e->pframes = a->pf & 0xFFu;
-    e->frames_total = 0;
-    e->persist_slot = -1;
-    for (auto &st : e->stats) st = KStat{};
     e->strip_stream = a->s ? a->s : e->stream;
     e->scan_peer_gaveup = nullptr;                          // (left behind by a sequence that failed before its scans: not this one's)
     plan_chunk(e, e->strip_stream, a->d_in, a->n, true, g.ysz / 4);
@@ -41,7 +39,7 @@ int m2v_strip_begin(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t pfr
                     size_t nframes, int row0, int row1, void *hip_stream)
 {
     if (!e || !d_frames444) return M2V_E_PARAM;
-    if (strip_refuses(e, "m2v_strip_begin")) return M2V_E_STATE;
+    if (begin_refusal(e, "m2v_strip_begin", Entry::Strip, xsize16, ysize16, pframes_count, nframes)) return M2V_E_STATE;
     StripBeginArgs a{xsize16, ysize16, pframes_count, (const uint8_t *)d_frames444, nframes, row0, row1, (hipStream_t)hip_stream};
     return guard(e, strip_begin_impl, &a);
 }
@@ -259,7 +257,7 @@ int m2v_strip_assemble(m2v_enc *e, uint32_t xsize16, uint32_t ysize16, uint32_t 
                        size_t *out_bytes, void *hip_stream)
 {
     if (!e || !d_strips || !frame_off || !d_out || nranks < 1 || nframes == 0) return M2V_E_PARAM;
-    if (strip_refuses(e, "m2v_strip_assemble")) return M2V_E_STATE;
+    if (begin_refusal(e, "m2v_strip_assemble", Entry::Strip, xsize16, ysize16, pframes_count, nframes)) return M2V_E_STATE;      // (starts no sequence: the rule alone)
     StripAsmArgs a{xsize16, ysize16, pframes_count, nframes, nranks, d_strips, frame_off, (uint8_t *)d_out, cap, out_bytes,
                    (hipStream_t)hip_stream};
     return guard(e, strip_assemble_impl, &a);
@@ -880,7 +878,7 @@ int m2v_strip_encode(m2v_enc *e, m2v_comm *comm, int rank, int world, int dst_ra
                      void *hip_stream)
 {
     if (!e || !d_frames444 || nframes == 0) return M2V_E_PARAM;
-    if (strip_refuses(e, "m2v_strip_encode")) return M2V_E_STATE;       // (before anything starts: the communicator is not aborted)
+    if (begin_refusal(e, "m2v_strip_encode", Entry::Strip, xsize16, ysize16, pframes_count, nframes)) return M2V_E_STATE;       // (before anything starts: the communicator is not aborted)
     StripEncodeArgs a{comm, rank, world, dst_rank, xsize16, ysize16, pframes_count, (const uint8_t *)d_frames444, nframes, (uint8_t *)d_out, cap,
                       out_bytes, (hipStream_t)hip_stream};
     const bool was_inflight = e->strip_inflight;
@@ -895,7 +893,7 @@ int m2v_strip_encode_begin(m2v_enc *e, m2v_comm *comm, int rank, int world, int 
                            uint32_t pframes_count, const void *d_frames444, size_t nframes, void *d_out, size_t cap, void *hip_stream)
 {
     if (!e || !d_frames444 || nframes == 0) return M2V_E_PARAM;
-    if (strip_refuses(e, "m2v_strip_encode_begin")) return M2V_E_STATE;
+    if (begin_refusal(e, "m2v_strip_encode_begin", Entry::Strip, xsize16, ysize16, pframes_count, nframes)) return M2V_E_STATE;
     StripEncodeArgs a{comm, rank, world, dst_rank, xsize16, ysize16, pframes_count, (const uint8_t *)d_frames444, nframes, (uint8_t *)d_out, cap,
                       nullptr, (hipStream_t)hip_stream};
     const bool was_inflight = e->strip_inflight;

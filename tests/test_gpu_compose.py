@@ -187,6 +187,31 @@ def test_session_on_one_handle(seed, vlq):
         h.close()
 
 
+def test_strips_and_port_after_a_call_that_sampled_everything():
+    """one handle: after each maximal set's resident call everything is cleared, and the plain frames through the strip entries and
+    then through the port are the oracle's plain stream with all five report queues empty - no entry sees what another's sampled"""
+    import torch
+    plain = C.call()
+    frames = C.planes(plain)
+    want = G.encoded(frames, 96, 64, 2, 2, VL=3)[0]
+    d_clip = dev(frames)
+    h = Handle()
+    try:
+        for name, c in sorted(C.maximal().items()):
+            h.run(c, name)
+            h.apply(plain)
+            assert h.held == NOTHING
+            engine = M.parallel.GpuStripEngine(h.enc, d_clip, 6, 4, plain["pf"], "cuda:0")
+            out = M.parallel.encode_strips(engine, 0, 1)
+            torch.cuda.synchronize()
+            assert out.cpu().numpy().tobytes() == want, "strips after " + name
+            assert not any(len(v) for v in h.reports().values())
+            assert h.enc.encode(C.source(plain), 6, 4, plain["pf"]) == want, "the port after " + name
+            assert not any(len(v) for v in h.reports().values())
+    finally:
+        h.close()
+
+
 def test_two_handles_taking_turns():
     """_begin a, _begin b, _end a, _end b: different rows, different geometry, different buffers"""
     rows = C.session()
