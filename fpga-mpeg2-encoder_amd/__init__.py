@@ -7,6 +7,7 @@ fallback: without the built library or without a GPU every entry point raises.
 """
 import contextlib
 import ctypes
+import functools
 import os
 import sys
 import threading
@@ -47,6 +48,7 @@ EXPORTS = [
     "m2v_stream_desc_module", "m2v_set_stream_desc", "m2v_frame_rate_code", "m2v_time_code",
     "m2v_set_sequences", "m2v_sequence_report",
     "m2v_mux_bound", "m2v_set_mux_out", "m2v_mux_report", "m2v_mux_device", "m2v_mux_scan_tile",
+    "m2v_set_source_size", "m2v_scale_taps",
 ]
 
 # the 4:2:0 entry points (kept apart: tests/test_abi.py matches EXPORTS against names of letters and underscores only)
@@ -383,6 +385,8 @@ def lib(debug=False):
             L.m2v_mux_report.argtypes = [vp, vp, sz]
             L.m2v_mux_device.argtypes = [vp, ci, vp, vp, vp, sz, vp, sz, vp]
             L.m2v_mux_scan_tile.argtypes = []
+            L.m2v_set_source_size.argtypes = [vp, ci, ci, ci]
+            L.m2v_scale_taps.argtypes = [ci, ci, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_uint16)]
         except AttributeError:
             # an OLDER build handed in through M2V_LIB for a same-box A/B (tools/ab.sh) may lack the newer entry points; the library of
             # this tree must have every one of them (tests/test_abi.py)
@@ -524,6 +528,74 @@ def pad_frames(frames, w, h, kind):
     return np.ascontiguousarray(np.concatenate(out, axis=1))
 
 
+# ---- frames of another size, resampled (m2v_set_source_size, include/m2v_mi355x.h) ----
+SCALE_FILTERS = {"triangle": 0, "area": 1}       # M2V_SCALE_*
+SCALE_MAXTAPS = 16                               # M2V_SCALE_MAXTAPS
+SCALE_MAX_SIZE, SCALE_MAX_RATIO = 16384, 8
+
+
+def _scale_filter(filter):
+    code = SCALE_FILTERS.get(filter, filter)
+    if code not in SCALE_FILTERS.values() or isinstance(code, bool):
+        raise ValueError("unknown filter %r" % (filter,))
+    return code
+
+
+def scale_taps(filter, src, dst, x):
+    """(first, [c(first), c(first + 1), ...]): the taps of output sample x of dst samples made from src samples, as the header defines
+    them - weights a(i) > 0 of the triangle or the area, c(i) = floor(a(i) * 2^14 / sum a), the remainder onto the largest a(i) (the
+    lowest i among equals).  Python integers, written from the definition: m2v_scale_taps is held against it."""
+    code = _scale_filter(filter)
+    if not (1 <= src <= SCALE_MAX_SIZE and 1 <= dst <= SCALE_MAX_SIZE and 0 <= x < dst) or src > SCALE_MAX_RATIO * dst:
+        raise ValueError("scale_taps: %d -> %d, sample %d" % (src, dst, x))
+    if code == 0:
+        P, R = (2 * x + 1) * src - dst, 2 * max(src, dst)
+        a = [(i, R - abs(2 * dst * i - P)) for i in range((P - R) // (2 * dst), (P + R) // (2 * dst) + 2)]
+    else:
+        a = [(i, min((i + 1) * dst, (x + 1) * src) - max(i * dst, x * src)) for i in range(x * src // dst, (x + 1) * src // dst + 1)]
+    a = [(i, v) for i, v in a if v > 0]
+    assert a and all(j[0] == i[0] + 1 for i, j in zip(a, a[1:]))
+    A = sum(v for _, v in a)
+    c = [v * (1 << 14) // A for _, v in a]
+    c[max(range(len(a)), key=lambda k: (a[k][1], -k))] += (1 << 14) - sum(c)
+    return a[0][0], c
+
+
+@functools.lru_cache(maxsize=64)
+def _scale_table(code, src, dst):
+    """the taps of every output sample as arrays [dst, n]: the samples they read (clamped to the plane) and their coefficients (0
+    beyond a sample's own count)"""
+    taps = [scale_taps(code, src, dst, x) for x in range(dst)]
+    n = max(len(c) for _, c in taps)
+    idx, coef = np.zeros((dst, n), np.int64), np.zeros((dst, n), np.int64)
+    for x, (first, c) in enumerate(taps):
+        idx[x] = np.clip(first + np.arange(n), 0, src - 1)
+        coef[x, :len(c)] = c
+    return idx, coef
+
+
+def scale_frames(frames, sw, sh, w, h, kind, filter="triangle"):
+    """sw x sh frames of `kind` -> [n, bytes] frames of the same kind at w x h, every plane resampled on its own (4:2:0 chroma in the
+    4:2:0 domain), every byte of an element with its plane's taps: the horizontal pass on every source row,
+    t = (sum c * s + 128) >> 8, then the vertical pass, o = (sum d * t + 2^19) >> 20.  The frames whose padded form (pad_frames) an
+    encode with a source size set codes, by definition (include/m2v_mi355x.h).  numpy, host side: a reference, not a fast path."""
+    code = _scale_filter(filter)
+    f = np.ascontiguousarray(frames, np.uint8).reshape(-1, frame_bytes(sw, sh, kind))
+    n, out, at = f.shape[0], [], 0
+    for (es, c, r, _), (_, C, R, _) in zip(_planes(sw, sh, kind), _planes(w, h, kind)):
+        p = f[:, at:at + es * c * r].reshape(n, r, c, es).astype(np.int64)
+        at += es * c * r
+        ix, cx = _scale_table(code, c, C)
+        iy, cy = _scale_table(code, r, R)
+        t = sum(p[:, :, ix[:, k], :] * cx[None, None, :, k, None] for k in range(ix.shape[1]))
+        t = (t + 128) >> 8
+        o = sum(t[:, iy[:, k], :, :] * cy[None, :, k, None, None] for k in range(iy.shape[1]))
+        o = (o + (1 << 19)) >> 20
+        assert o.min() >= 0 and o.max() <= 255
+        out.append(o.astype(np.uint8).reshape(n, -1))
+    return np.ascontiguousarray(np.concatenate(out, axis=1))
+
+
 def planes_of_recon(buf, w, h, layout="i420"):
     """Frames of m2v_set_recon_out (`buf`: a numpy array or torch tensor of n * frame_bytes(w, h, layout) bytes, w x h the size set or the
     coded size) -> (Y [n, h, w], U, V [n, (h + 1) / 2, (w + 1) / 2]): views where the layout allows it (the interleaved ones are strided)."""
@@ -573,7 +645,7 @@ class Mpeg2Encoder:
         self._geom = {}
         # what is set on the handle, as the setters below take it back (_for_call): the three options, the lists, the buffers, the size
         self._set = {"stats": False, "gop_bytes_max": 0, "scene_cut": 0, "gop_levels": None, "gop_starts": None, "sequences": None,
-                     "stream_desc": None, "recon_out": None, "mux_out": None, "frame_size": None}
+                     "stream_desc": None, "recon_out": None, "mux_out": None, "frame_size": None, "source_size": None}
         err = ctypes.c_int(0)
         self._L = lib(debug)
         self._h = self._L.m2v_create(XL, YL, VECTOR_LEVEL, Q_LEVEL, device, ctypes.byref(err))
@@ -630,6 +702,8 @@ class Mpeg2Encoder:
                 self.set_option(key, v)
             elif key == "frame_size":
                 self.set_frame_size(*(v or (0, 0, 0)))
+            elif key == "source_size":
+                self.set_source_size(*(v or (0, 0, 0)))
             elif key == "recon_out":
                 self.set_recon_out(*(v or (None, 0)))
             elif key == "mux_out":
@@ -749,6 +823,19 @@ class Mpeg2Encoder:
     def frame_size(self):
         """(w, h, header code) set by set_frame_size, or None"""
         return self._set["frame_size"]
+
+    def set_source_size(self, sw, sh, filter="triangle"):
+        """m2v_set_source_size: from now on every resident whole-frame entry takes sw x sh frames in its own format and resamples them
+        on the device to the picture size - the size of set_frame_size, or of the call's xsize16, ysize16 - with filter "triangle" or
+        "area" (scale_frames says what comes out).  (0, 0) switches it off.  Idle handles only."""
+        code = SCALE_FILTERS[filter] if isinstance(filter, str) else int(filter)
+        self._chk(self._L.m2v_set_source_size(self._h, int(sw), int(sh), code), "m2v_set_source_size")
+        self._set["source_size"] = (int(sw), int(sh), code) if sw or sh else None
+
+    @property
+    def source_size(self):
+        """(sw, sh, filter code) set by set_source_size, or None"""
+        return self._set["source_size"]
 
     def _fb(self, xsize16, ysize16, kind):
         """bytes of one frame a whole-frame entry takes: of the size set, else of the clamped geometry"""
@@ -963,7 +1050,8 @@ class Mpeg2Encoder:
         return self._pop("m2v_picture_stats", PICTURE_STAT_DTYPE, max_records)
 
     def encode_tensor(self, frames, pframes_count, order="rgb", matrix="bt601", out=None, header=None, stats=False, gop_levels=None,
-                      gop_bytes_max=0, gop_starts=None, scene_cut=0, recon=None, desc=None, sequences=None, container=None):
+                      gop_bytes_max=0, gop_starts=None, scene_cut=0, recon=None, desc=None, sequences=None, container=None, size=None,
+                      filter="triangle"):
         """One whole sequence from a torch image tensor on the handle's device, in one call: contiguous uint8 [N, H, W, 3] (order
         "rgb" / "bgr"), [N, H, W, 4] ("rgbx" / "bgrx" / "xrgb" / "xbgr") or [N, 3, H, W] ("rgb": planar).  Runs
         m2v_encode_resident_rgb on torch's current stream and returns the stream bytes as a uint8 device tensor (a view of `out` when
@@ -991,7 +1079,11 @@ class Mpeg2Encoder:
         container = "ts" or "ps": the first element returned is the transport or program stream, muxed on the device, instead of the
         elementary stream (set_mux_out for the duration of the call; the handle's own setting is back afterwards): the bytes of
         container.mux_ts / mux_ps of the elementary stream.  With sequences the tensor holds one container per clip and mux_report()
-        says where each one is; encode_batch does both.  M2VError if the muxer refuses the stream."""
+        says where each one is; encode_batch does both.  M2VError if the muxer refuses the stream.
+        size = (w, h): the picture size; the tensor's own H, W are then a source size and its frames are resampled to w x h on the
+        device with filter = "triangle" or "area" (set_source_size for the duration of the call; the handle's own settings are back
+        afterwards).  header, recon and the stream's geometry go by w x h: a picture size that is not whole macroblocks still needs
+        header=.  Without the keyword the tensor is the picture, whatever source size the handle holds."""
         import torch
         if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4:
             raise ValueError("encode_tensor: a uint8 tensor of 4 dimensions is required")
@@ -1016,6 +1108,18 @@ class Mpeg2Encoder:
             raise ValueError("encode_tensor: unknown header %r" % (header,))
         if recon is not None and recon not in LAYOUTS_420:
             raise ValueError("encode_tensor: unknown recon layout %r" % (recon,))
+        if filter not in SCALE_FILTERS:
+            raise ValueError("encode_tensor: unknown filter %r" % (filter,))
+        source = None
+        if size is not None:
+            try:
+                pw, ph = (int(v) for v in size)
+            except (TypeError, ValueError):
+                raise ValueError("encode_tensor: size is (w, h), not %r" % (size,)) from None
+            if not (1 <= W <= SCALE_MAX_SIZE and 1 <= H <= SCALE_MAX_SIZE) or pw < 1 or ph < 1 or W > SCALE_MAX_RATIO * pw or H > SCALE_MAX_RATIO * ph:
+                raise ValueError("encode_tensor: %d x %d frames do not resample to %d x %d (1 ... %d either way, at most %d times the picture)"
+                                 % (W, H, pw, ph, SCALE_MAX_SIZE, SCALE_MAX_RATIO))
+            source, W, H = (W, H, filter), pw, ph
         xs, ys = (W + 15) // 16, (H + 15) // 16
         if header is None and (H % 16 or W % 16):
             raise ValueError("encode_tensor: %d x %d is not whole macroblocks; header=\"true\" or \"module\" pads it on the device" % (W, H))
@@ -1036,6 +1140,8 @@ class Mpeg2Encoder:
         call = {}
         if fit or self.frame_size:
             call["frame_size"] = (W, H, header) if fit else None
+        if source or self.source_size:
+            call["source_size"] = source
         if stats and not self._set["stats"]:
             call["stats"] = 1
         if sequences is not None:

@@ -39,6 +39,22 @@ static int size_refuses(m2v_enc *e, const char *fn, const char *why)
 
 bool size_refuses_beats(m2v_enc *e, const char *fn) { return size_refuses(e, fn, "the port has no partial macroblock, push whole frames") != M2V_OK; }
 
+// a source size is set (m2v_set_source_size) and the entry resamples nothing
+static int source_refuses(m2v_enc *e, const char *fn, const char *why)
+{
+    if (!e->set.src.w) return M2V_OK;
+    e->set_err("%s: a source size is set (m2v_set_source_size): %s", fn, why);
+    return M2V_E_STATE;
+}
+
+// the picture size of a sequence that starts with xs, ys: the size set, else W x H
+static SrcSize picture_size(m2v_enc *e, uint32_t xs, uint32_t ys)
+{
+    if (e->set.size.w) return e->set.size;
+    const Geom g = make_geom(e, xs, ys);
+    return SrcSize{g.W, g.H};
+}
+
 // xs, ys are not m2v_fit_size's for the size set
 static int size_mismatch(m2v_enc *e, const char *fn, uint32_t xs, uint32_t ys)
 {
@@ -55,6 +71,7 @@ static int size_mismatch(m2v_enc *e, const char *fn, uint32_t xs, uint32_t ys)
 static int port_refusal(m2v_enc *e, const char *fn)
 {
     const m2v_enc::Settings &set = e->set;
+    if (const int r = source_refuses(e, fn, "the stage's packed bytes are sized for frames of the coded size, the resident entries resample")) return r;
     if (set.gop_bytes_max) return refuse(e, M2V_E_STATE, fn, "option \"gop_bytes_max\" is set: the cap needs whole GOPs in a chunk, which only the resident entries give");
     if (set.scene_cut) return refuse(e, M2V_E_STATE, fn, "option \"scene_cut\" is set: the detector runs in front of a chunk's plan, which only the resident entries wait for");
     if (!set.sequences.empty()) return refuse(e, M2V_E_STATE, fn, "a batch of sequences is set (m2v_set_sequences): the port carries one sequence, the batch is the resident entries'");
@@ -68,6 +85,7 @@ static int strip_refusal(m2v_enc *e, const char *fn)
 {
     const m2v_enc::Settings &set = e->set;
     if (const int r = size_refuses(e, fn, "strips take whole padded frames")) return r;
+    if (const int r = source_refuses(e, fn, "strips take whole padded frames of the coded size")) return r;
     if (!set.sequences.empty()) return refuse(e, M2V_E_STATE, fn, "a batch of sequences is set (m2v_set_sequences): the strip assembly writes one stream");
     if (set.mux.kind) return refuse(e, M2V_E_STATE, fn, "a container buffer is set (m2v_set_mux_out): the muxer follows the resident entries' stream");
     if (set.recon.p) return refuse(e, M2V_E_STATE, fn, "a buffer for the reconstruction is set (m2v_set_recon_out): a strip holds part of a picture, and nothing gathers the parts");
@@ -121,6 +139,14 @@ static int resident_refusal_late(m2v_enc *e, const char *fn, uint32_t xs, uint32
         }
     }
     if (const int r = size_mismatch(e, fn, xs, ys)) return r;
+    if (set.src.w) {
+        const SrcSize pic = picture_size(e, xs, ys);
+        if (set.src.w > 8 * pic.w || set.src.h > 8 * pic.h) {
+            e->set_err("%s: the source size set (m2v_set_source_size) is %d x %d, more than 8 times the picture size %d x %d in a dimension", fn,
+                       set.src.w, set.src.h, pic.w, pic.h);
+            return M2V_E_PARAM;
+        }
+    }
     if (set.gop_bytes_max && (size_t)(pf & 0xFFu) + 1 > e->batch_frames) {
         e->set_err("m2v_encode_resident: option \"gop_bytes_max\" needs whole GOPs in a chunk: pframes_count + 1 = %u is more than batch_frames = %zu",
                    (pf & 0xFFu) + 1u, e->batch_frames);
@@ -165,6 +191,12 @@ int begin_sequence(m2v_enc *e, const char *fn, Entry en, uint32_t xs, uint32_t y
     const bool pad = set.size.w && ((set.size.w | set.size.h) & 15);
     seq.fit = pad ? set.size : SrcSize{};
     seq.hdr_true = pad && set.header == M2V_HEADER_TRUE;
+    // (a source of the picture size samples as none: the launches and buffers of a handle with nothing set)
+    seq.pic = picture_size(e, xs, ys);
+    const bool scaled = set.src.w && (set.src.w != seq.pic.w || set.src.h != seq.pic.h);
+    seq.src = scaled ? set.src : SrcSize{};
+    seq.filter = set.filter;
+    if (!scaled) seq.pic = SrcSize{};
     seq.levels = set.gop_levels;
     seq.cap = set.gop_bytes_max;
     seq.starts = set.gop_starts;

@@ -563,7 +563,7 @@ void m2v_destroy(m2v_enc *e)
     (void)hipGetLastError();            // (a caller's stream that no longer exists: tolerated above, and not left behind as HIP's last error)
     e->d_coef.release(); e->d_mbaux.release(); e->d_slots.release(); e->d_slots_small.release(); e->d_mbinfo.release(); e->d_mblen.release();
     e->d_slice_bytes.release(); e->d_slice_off.release(); e->d_frame_off.release();
-    e->d_jobs.release(); e->d_lists.release(); e->d_joblist.release(); e->d_ctl.release(); e->d_segs.release(); e->d_x444.release(); e->d_fit.release();
+    e->d_jobs.release(); e->d_lists.release(); e->d_joblist.release(); e->d_ctl.release(); e->d_segs.release(); e->d_x444.release(); e->d_fit.release(); scale_release(e);
     e->d_pstat.release();
     e->d_gop.release();
     scene_release(e);

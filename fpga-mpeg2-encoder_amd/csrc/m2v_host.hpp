@@ -30,6 +30,9 @@
 //   m2v_mux.hip       m2v_set_mux_out / m2v_mux_device: transport or program stream out of the stream in HBM.  Its three kernels touch no
 //                     device global and nothing of m2v_kernels.hpp, so they live in their own unit with their launches (m2v_mux_kernels.hpp
 //                     holds the arithmetic, for the device and the host alike)
+//   m2v_scale.hip     m2v_set_source_size: frames of another size resampled to the picture size in front of the conversions - the setting,
+//                     the tap tables (m2v_scale_taps), k_scale and its launch (m2v_scale_kernels.hpp holds the arithmetic, for the device
+//                     and the host alike; no device global, nothing of m2v_kernels.hpp)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -295,13 +298,16 @@ struct m2v_enc {
 
     // What the setters write, on idle handles only, and what the sequence in progress runs with.  begin_sequence (m2v_begin.hip) decides
     // from `set` whether an entry may start and writes ALL of `seq`, for every entry: a setting the entry does not take samples as off.
-    // Besides it only m2v_set_frame_size, m2v_set_recon_out and m2v_set_mux_out write `seq`: they clear what goes with the old setting.
+    // Besides it only m2v_set_frame_size, m2v_set_source_size, m2v_set_recon_out and m2v_set_mux_out write `seq`: they clear what goes with
+    // the old setting.
     // plan_chunk, the launch sites and the feature units read `seq` only.
     struct ReconDst { uint8_t *p = nullptr; size_t cap = 0; int layout = 0; size_t fb = 0; };      // fb (seq only): bytes of one frame in the caller's buffer
     struct MuxDst { int kind = 0; uint8_t *p = nullptr; size_t cap = 0; };
     struct Settings {
         SrcSize size;                           // m2v_set_frame_size (0 x 0 = off) ...
         int header = M2V_HEADER_MODULE;         // ... and what the headers say
+        SrcSize src;                            // m2v_set_source_size (0 x 0 = off) ...
+        int filter = M2V_SCALE_TRIANGLE;        // ... and its filter
         std::vector<uint8_t> gop_levels;        // m2v_set_gop_levels
         unsigned long long gop_bytes_max = 0;   // option "gop_bytes_max"
         std::vector<uint32_t> gop_starts;       // m2v_set_gop_starts
@@ -315,6 +321,9 @@ struct m2v_enc {
     struct Sampled {
         SrcSize fit;                            // the source size when the frames have to be padded (0 x 0 when not: no size set, or one of whole macroblocks)
         bool hdr_true = false;                  // the headers say it
+        SrcSize src;                            // the source size when the frames have to be resampled (0 x 0 when not: none set, or the picture size) ...
+        SrcSize pic;                            // ... the picture size they are resampled to, and the filter
+        int filter = M2V_SCALE_TRIANGLE;
         std::vector<uint8_t> levels;            // empty: every GOP at Q
         unsigned long long cap = 0;             // 0: no cap
         std::vector<uint32_t> starts;           // empty and cut 0: the fixed cadence, nothing of m2v_scene.hip is touched
@@ -325,7 +334,13 @@ struct m2v_enc {
         MuxDst mux;
     } seq;
 
-    DevBuf<uint8_t> d_fit;                // padded frames in their own format, between k_fit and the conversion (no recording references it)
+    DevBuf<uint8_t> d_fit;                // padded frames in their own format, between k_fit or k_scale and the conversion (no recording references it)
+    // m2v_set_source_size (m2v_scale.hip): the four tap tables of the last scaled sequence on the device, their pinned source, and what
+    // they were built for (source, picture, filter)
+    DevBuf<uint8_t> d_scale_tab;
+    uint8_t *h_scale_tab = nullptr;
+    size_t h_scale_cap = 0;
+    int scale_key[5] = {0, 0, 0, 0, 0};
 
     // option "stats" (m2v_stats.hip): the chunk's records on the device - k_picstat and k_picstat_mb fill them in place - and the
     // completed pictures' records nobody has popped yet
@@ -547,10 +562,20 @@ inline int rgb_bpp(int layout) { return layout >= M2V_RGB_RGBX32 && layout <= M2
 size_t pk_frame_bytes(int kind, const Geom &g, SrcSize sz);
 // the frames of a 4:4:4 (kPk444), 4:2:0 or RGB run kind (back to back at src) -> planar 4:4:4 frames of 3 * ysz bytes at dst (16-byte
 // aligned).  e->seq.fit set: the frames are of that size and are padded first (k_fit; src at any address), into e->d_fit or, 4:4:4, straight
-// into dst.  Else src is 16-byte aligned.
+// into dst; e->seq.src set: they are of that size and are resampled and padded by k_scale instead, the same way.  Else src is 16-byte aligned.
 void launch_convert(m2v_enc *e, hipStream_t s, int kind, const uint8_t *src, uint8_t *dst, uint32_t nframes);
 // nframes RGB frames (ysz * rgb_bpp(layout) bytes each) -> planar 4:4:4 by the integer transform of include/m2v_mi355x.h (k_rgb2yuv)
 void launch_rgb2yuv(hipStream_t s, int layout, int matrix, const uint8_t *src, uint8_t *dst, uint32_t ysz, uint32_t nframes);
+// the size of the frames a sequence's whole-frame entries take: the source size of a scaled sequence, else the size to pad, else 0 x 0 (W x H)
+inline SrcSize seq_frame_size(const m2v_enc *e) { return e->seq.src.w ? e->seq.src : e->seq.fit; }
+
+// ---- m2v_scale.hip: m2v_set_source_size ----
+// a scaled sequence has started (e->seq.src set): the tap tables for its sizes and filter, built and uploaded on s unless the handle holds them
+void scale_prepare(m2v_enc *e, hipStream_t s);
+// nframes frames of e->seq.src in the form of a run kind, back to back at src (any address) -> the same form at W x H, resampled to
+// e->seq.pic and padded, back to back at dst (16-byte aligned): one k_scale launch
+void launch_scale(m2v_enc *e, hipStream_t s, int kind, const uint8_t *src, uint8_t *dst, uint32_t nframes);
+void scale_release(m2v_enc *e);
 
 // ---- m2v_strips.hip ----
 void strip_flight_release(m2v_enc *e);

@@ -365,17 +365,24 @@ static void convert_run(hipStream_t s, int kind, const uint8_t *src, uint8_t *ds
 void launch_convert(m2v_enc *e, hipStream_t s, int kind, const uint8_t *src, uint8_t *dst, uint32_t nframes)
 {
     const Geom &g = e->g;
-    if (!e->seq.fit.w) { convert_run(s, kind, src, dst, g, nframes); return; }
-    if (kind == kPk444) { launch_fit_frames(s, kind, src, dst, g, e->seq.fit, nframes); return; }
+    const SrcSize in = seq_frame_size(e);
+    const bool scaled = e->seq.src.w != 0;
+    if (!in.w) { convert_run(s, kind, src, dst, g, nframes); return; }
+    if (kind == kPk444) {
+        if (scaled) launch_scale(e, s, kind, src, dst, nframes);
+        else launch_fit_frames(s, kind, src, dst, g, in, nframes);
+        return;
+    }
     // the padded frames wait in a buffer of the handle's for the conversion behind them on the same stream; a long run takes turns in
     // 128 MB of it (twenty 1920 x 1088 RGB24 frames)
-    const size_t sfb = pk_frame_bytes(kind, g, e->seq.fit), dfb = pk_frame_bytes(kind, g, SrcSize{});
+    const size_t sfb = pk_frame_bytes(kind, g, in), dfb = pk_frame_bytes(kind, g, SrcSize{});
     const uint32_t part = (uint32_t)std::min<size_t>(nframes, std::max<size_t>(1, ((size_t)128 << 20) / dfb));
     e->d_fit.recorded = false;
     e->d_fit.ensure((size_t)part * dfb);
     for (uint32_t k = 0; k < nframes; k += part) {
         const uint32_t n = std::min(part, nframes - k);
-        launch_fit_frames(s, kind, src + (size_t)k * sfb, e->d_fit.p, g, e->seq.fit, n);
+        if (scaled) launch_scale(e, s, kind, src + (size_t)k * sfb, e->d_fit.p, n);
+        else launch_fit_frames(s, kind, src + (size_t)k * sfb, e->d_fit.p, g, in, n);
         convert_run(s, kind, e->d_fit.p, dst + (size_t)k * g.ysz * 3, g, n);
     }
 }

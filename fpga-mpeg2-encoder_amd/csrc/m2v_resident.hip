@@ -46,9 +46,11 @@ static int resident_impl(m2v_enc *e, void *argp)
     const size_t gop = e->pframes + 1u;
     size_t step = chunk >= gop ? chunk / gop * gop : chunk;
     if (seq_batch(e)) step = chunk;               // (a batch's GOPs count from their sequences' starts: there is no grid to align to)
-    const int kind = a->kind < 0 && e->seq.fit.w ? kPk444 : a->kind;       // (planar 4:4:4 frames that have to be padded: through the handle's buffer too)
+    const SrcSize in = seq_frame_size(e);
+    const int kind = a->kind < 0 && in.w ? kPk444 : a->kind;       // (planar 4:4:4 frames that have to be padded or resampled: through the handle's buffer too)
     const bool is420 = kind >= 0;                 // (or RGB)
-    const size_t fb420 = is420 ? pk_frame_bytes(kind, g, e->seq.fit) : 0;
+    const size_t fb420 = is420 ? pk_frame_bytes(kind, g, in) : 0;
+    if (e->seq.src.w) scale_prepare(e, s);
     if (is420) {
         // each chunk's frames are expanded or converted into planar 4:4:4 in front of its kernels, on the same stream; one buffer is enough because
         // the chunks are synchronised below

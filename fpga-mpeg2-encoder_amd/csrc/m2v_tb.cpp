@@ -4,6 +4,7 @@
 //          [-i420 | -yv12 | -nv12 | -nv21 | -rgb24 | -bgr24 | -rgbx | -bgrx | -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f]
 //          [-pad | -truesize] [-stats] [-qgop q0,q1,...] [-istart n0,n1,...] [-scenecut T] [-recon out.yuv [-reconfmt i420|yv12|nv12|nv21]]
 //          [-fps N/D] [-aspect 1:1|4:3|16:9|2.21:1] [-bitrate B] [-vbv K] [-colour bt601|bt709|P,T,M] [-repeat-headers]
+//          [-scale SWxSH [-filter triangle|area]]
 //          in.yuv W H out.m2v  [in2.yuv W2 H2 out2.m2v ...]
 //
 // -pad: W, H are any size from 49 up; the files hold frames of that size in the chosen format, which are padded to whole macroblocks on
@@ -28,6 +29,9 @@
 // -recon out.yuv: the reconstructed pictures of every video, frame behind frame, as 4:2:0 frames of W x H (the file's size under -pad too)
 // in -reconfmt (default i420): m2v_set_recon_out, read back after each video - a file for ffplay -f rawvideo or tools/m2v_stats.py --yuv.
 // The buffer is the resident entries', so it needs the resident mode that -scenecut selects (-scenecut 65280 never finds a cut).
+// -scale SWxSH: the files hold frames of SW x SH in the chosen format; W H on the command line are the picture size they are resampled
+// to on the device (m2v_set_source_size) with -filter (default triangle), under -pad any size from 49 up.  The resident entries resample,
+// so the flag selects the resident mode that -scenecut selects.  Does not go with -bubbles.
 // -fps N/D, -aspect A, -bitrate B, -vbv K, -colour C, -repeat-headers: what the stream says about itself (m2v_set_stream_desc); NOT the
 // module's behaviour.  N/D: a rational equal to a frame rate of ISO/IEC 13818-2 table 6-4 (24000/1001, 24, 25, 30000/1001, 30, 50,
 // 60000/1001, 60; "/D" may be left out), which the GOP headers' time codes then count at; B: bit/s, rounded up to units of 400; K: the
@@ -63,6 +67,7 @@ int main(int argc, char **argv)
         bad_matrix = 0, pad = 0, truesize = 0, stats = 0, reconfmt = M2V_420_I420, devmux = 0;
     const char *recon = nullptr;
     long long scenecut = 0;
+    int ssw = 0, ssh = 0, filter = M2V_SCALE_TRIANGLE, bad_scale = 0;
     std::vector<uint8_t> qgop;
     std::vector<uint32_t> istart;
     bool have_istart = false;
@@ -146,6 +151,19 @@ int main(int argc, char **argv)
             continue;
         }
         if (!strcmp(argv[i], "-scenecut")) { scenecut = atoll(argv[i + 1]); ++i; continue; }
+        if (!strcmp(argv[i], "-scale")) {
+            char tail = 0;
+            if (sscanf(argv[i + 1], "%6dx%6d%c", &ssw, &ssh, &tail) != 2 || ssw < 1 || ssh < 1 || ssw > 16384 || ssh > 16384) bad_scale = 1;
+            ++i;
+            continue;
+        }
+        if (!strcmp(argv[i], "-filter")) {
+            if (!strcmp(argv[i + 1], "triangle")) filter = M2V_SCALE_TRIANGLE;
+            else if (!strcmp(argv[i + 1], "area")) filter = M2V_SCALE_AREA;
+            else bad_scale = 1;
+            ++i;
+            continue;
+        }
         if (!strcmp(argv[i], "-recon")) { recon = argv[i + 1]; ++i; continue; }
         if (!strcmp(argv[i], "-reconfmt")) {
             static const char *const names[] = {"i420", "yv12", "nv12", "nv21"};
@@ -168,16 +186,18 @@ int main(int argc, char **argv)
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
         ++i;
     }
-    if ((argc - i) < 4 || (argc - i) % 4 || layouts > 1 || bad_matrix || bad_desc || ((layouts || pad || scenecut) && bubbles)) {          // (there are no 4:2:0 or RGB beats)
+    if ((argc - i) < 4 || (argc - i) % 4 || layouts > 1 || bad_matrix || bad_desc || bad_scale || ((layouts || pad || scenecut || ssw) && bubbles)) {          // (there are no 4:2:0 or RGB beats)
         fprintf(stderr, "usage: %s [-XL n] [-YL n] [-VL n] [-Q n] [-p pframes] [-d dev] [-i420 | -yv12 | -nv12 | -nv21 | -rgb24 | -bgr24 | -rgbx | -bgrx |"
                         " -xrgb | -xbgr | -rgbp] [-matrix bt601|bt709|bt601f|bt709f] [-pad | -truesize] [-stats] [-qgop q0,q1,...] [-istart n0,n1,...] [-scenecut T] [-recon out.yuv [-reconfmt i420|yv12|nv12|nv21]]"
-                        " [-fps N/D] [-aspect 1:1|4:3|16:9|2.21:1] [-bitrate bit/s] [-vbv units of 16384 bits] [-colour bt601|bt709|P,T,M] [-repeat-headers] [-ps] [-ts] [-devmux]"
+                        " [-fps N/D] [-aspect 1:1|4:3|16:9|2.21:1] [-bitrate bit/s] [-vbv units of 16384 bits] [-colour bt601|bt709|P,T,M] [-repeat-headers] [-scale SWxSH [-filter triangle|area]] [-ps] [-ts] [-devmux]"
                         " in.yuv W H out.m2v ...\n"
                         "  -fps takes a frame rate of ISO/IEC 13818-2 table 6-4: 24000/1001, 24, 25, 30000/1001, 30, 50, 60000/1001, 60\n"
-                        "  -scenecut T stages every file's frames in device memory and encodes them with one resident call (the detector needs it)\n", argv[0]);
+                        "  -scenecut T stages every file's frames in device memory and encodes them with one resident call (the detector needs it)\n"
+                        "  -scale SWxSH: the files hold frames of SW x SH, resampled on the device to W x H; it selects the resident mode too\n", argv[0]);
         return 2;
     }
-    if (recon && !scenecut) {
+    const bool resident = scenecut || ssw;
+    if (recon && !resident) {
         fprintf(stderr, "*** -recon needs the resident mode: the reconstruction is written to device memory by the resident entries, and only -scenecut T "
                         "stages the frames there (-scenecut 65280 never finds a cut)\n");
         return 2;
@@ -193,6 +213,7 @@ int main(int argc, char **argv)
     if (have_istart && m2v_set_gop_starts(e, istart.data(), istart.size()) < 0) { fprintf(stderr, "*** m2v_set_gop_starts: %s\n", m2v_last_error(e)); return 1; }
     if (m2v_set_stream_desc(e, &desc) < 0) { fprintf(stderr, "*** m2v_set_stream_desc: %s\n", m2v_last_error(e)); return 1; }
     if (scenecut && m2v_set_option(e, "scene_cut", scenecut) < 0) { fprintf(stderr, "*** m2v_set_option(scene_cut): %s\n", m2v_last_error(e)); return 1; }
+    if (ssw && m2v_set_source_size(e, ssw, ssh, filter) < 0) { fprintf(stderr, "*** m2v_set_source_size: %s\n", m2v_last_error(e)); return 1; }
     int num_video = 0;
     for (; i + 3 < argc; i += 4) {
         ++num_video;
@@ -220,8 +241,9 @@ int main(int argc, char **argv)
             printf("*** ysize=%4d is invalid, which must in range [64,%4d], and must be a multiple of 16\n", ysize, 16 << YL);
             return 1;
         }
-        const size_t fb = layout420 >= 0 ? (size_t)xsize * ysize + 2 * (size_t)((xsize + 1) / 2) * (size_t)((ysize + 1) / 2)
-                                         : (size_t)xsize * ysize * (rgb >= M2V_RGB_RGBX32 && rgb <= M2V_RGB_XBGR32 ? 4 : 3);
+        const int fw = ssw ? ssw : xsize, fh = ssw ? ssh : ysize;                              // the size of the file's frames
+        const size_t fb = layout420 >= 0 ? (size_t)fw * fh + 2 * (size_t)((fw + 1) / 2) * (size_t)((fh + 1) / 2)
+                                         : (size_t)fw * fh * (rgb >= M2V_RGB_RGBX32 && rgb <= M2V_RGB_XBGR32 ? 4 : 3);
         std::vector<uint8_t> frame(fb), word(1 << 20), es;
         size_t frames = 0, bytes = 0;
         const auto t0 = std::chrono::steady_clock::now();
@@ -239,7 +261,7 @@ int main(int argc, char **argv)
                 if (until_last && n == 0 && !m2v_busy(e)) break;
             }
         };
-        if (scenecut) {
+        if (resident) {
             // the detector runs in front of a chunk's plan on the resident entries: the file's complete frames go to device memory whole
             std::vector<uint8_t> all;
             while (fread(frame.data(), 1, fb, fi) == fb) { all.insert(all.end(), frame.begin(), frame.end()); ++frames; }
@@ -279,7 +301,7 @@ int main(int argc, char **argv)
                 (void)hipFree(d_out);
             }
         }
-        while (!scenecut && fread(frame.data(), 1, fb, fi) == fb) {                            // complete frames only (TB:220)
+        while (!resident && fread(frame.data(), 1, fb, fi) == fb) {                            // complete frames only (TB:220)
             printf("  start to encode video %d frame %3zu\n", num_video, frames);
             int r;
             if (rgb >= 0) {
@@ -304,7 +326,7 @@ int main(int argc, char **argv)
             ++frames;
             drain(false);
         }
-        if (!scenecut) {
+        if (!resident) {
             if (m2v_sequence_stop(e) < 0) { fprintf(stderr, "*** stop failed: %s\n", m2v_last_error(e)); return 1; }
             drain(true);
         }

@@ -210,6 +210,71 @@ int m2v_set_frame_size(m2v_enc *e, int width, int height, int header);
 /* xsize16 = ceil(width / 16), ysize16 = ceil(height / 16): pure arithmetic, no GPU.  M2V_E_PARAM for a size below 1. */
 int m2v_fit_size(int width, int height, uint32_t *xsize16, uint32_t *ysize16);
 
+/*
+ * Frames of another size, resampled on the device.  The module's README tells its users to pad and says nothing about a source of
+ * another size, so - as with 4:2:0, RGB and padding - the behaviour is a definition of ours.  While a source size is set, every
+ * resident whole-frame entry - m2v_encode_resident, m2v_encode_resident420, m2v_encode_resident_rgb and their _begin forms - takes
+ * frames of src_width x src_height pixels in its own format and resamples them on the device (k_scale) in front of what it did before.
+ *
+ * DEFINITION.  The picture size w x h is the size set with m2v_set_frame_size, or W x H of the starting call's xsize16, ysize16 when
+ * none is set.  The stream is byte for byte the stream the same entry gives for the frames pad(scale(x)): every plane of the source
+ * frame is resampled to the picture size in the source's own format, the result is padded to whole macroblocks as m2v_set_frame_size
+ * defines, and that is converted as before.  Planes and elements are those of the table above, with sw x sh for width x height:
+ *
+ *     planar 4:4:4, RGBP  three planes of sw x sh bytes                                  -> w x h
+ *     I420 / YV12         Y: sw x sh; two chroma planes of scw x sch                     -> w x h; cw x ch
+ *     NV12 / NV21         Y: sw x sh; one plane of 2-byte pairs, scw x sch               -> w x h; cw x ch
+ *     RGB24 / BGR24       one plane of 3-byte pixels, sw x sh                            -> w x h
+ *     RGBX32 ... XBGR32   one plane of 4-byte pixels, sw x sh                            -> w x h
+ *
+ * scw = (sw + 1) / 2, sch = (sh + 1) / 2, cw = (w + 1) / 2, ch = (h + 1) / 2.  Every byte of an element is filtered on its own with its
+ * plane's taps; the ignored byte of a 32-bit pixel may hold anything afterwards, nothing reads it.  4:2:0 chroma is resampled in the
+ * 4:2:0 domain, plane by plane, centre-aligned like luma: CHROMA SITING IS NOT MODELLED (a left-sited source keeps its samples a
+ * fraction of a chroma sample from where MPEG-2 expects them, as every centre-aligned scaler leaves them).  A source frame is
+ * sw * sh + 2 * scw * sch bytes (4:2:0), sw * sh * 3 or sw * sh * 4; frames lie back to back at any address, only the base pointer of
+ * a resident 4:2:0 or RGB call keeps its 16-byte rule.
+ *
+ * Taps of one dimension, src samples to dst samples, output index x, all in integers, sample centres aligned:
+ *
+ *     M2V_SCALE_TRIANGLE  P = (2x + 1) * src - dst, R = 2 * max(src, dst), a(i) = R - |2 * dst * i - P| over every integer i with
+ *                         a(i) > 0 (i may lie below 0 or above src - 1): bilinear when enlarging, a triangle widened by the ratio
+ *                         when reducing
+ *     M2V_SCALE_AREA      a(i) = min((i + 1) * dst, (x + 1) * src) - max(i * dst, x * src) over every i with a(i) > 0: the exact area
+ *                         of source sample i under output sample x
+ *
+ * With first the smallest such i, n their count (they are contiguous) and A their sum: c(i) = floor(a(i) * 2^14 / A), and the remainder
+ * 2^14 - sum c(i) goes onto the tap with the largest a(i), the lowest i among equals.  A tap reads sample clamp(i, 0, src - 1): weight
+ * that falls outside the plane lands on its edge sample.  The horizontal pass comes first, on every source row r,
+ *
+ *     t[r][x] = (sum c_x(i) * s[r][clamp i] + 128) >> 8                 (0 ... 16320)
+ *
+ * and the vertical pass follows, with the taps d_y(j) of the other dimension:
+ *
+ *     o[y][x] = (sum d_y(j) * t[clamp j][x] + 2^19) >> 20
+ *
+ * There is no clamp of the result: the coefficients are not negative and sum to 2^14.  Equal sizes give the single tap (x, 2^14): the
+ * identity.  Every output lies within 1.45 of the same taps in real arithmetic (255 * 2 * 15 / 2^14 = 0.467 of coefficient error per
+ * pass, 1 / 128 of the first rounding, 0.5 of the second).
+ *
+ * Limits: 1 <= src_width, src_height <= 16384, and src_width <= 8 * w, src_height <= 8 * h (the chroma planes then stay within 8 as
+ * well), which bounds a tap list at M2V_SCALE_MAXTAPS; enlarging has no limit.  The call that starts a sequence checks the ratio
+ * against the picture size it now knows: M2V_E_PARAM with nothing started, the text names both sizes.
+ *
+ * Only while the handle is idle (M2V_E_STATE otherwise); the setting stays until it is changed, m2v_reset keeps it, (0, 0, x) switches
+ * it off.  M2V_E_PARAM for a negative size, for one size zero and the other not, for a size above 16384, and for an unknown filter.  A
+ * source size equal to the picture size launches no resampling pass and behaves as none set.  m2v_set_frame_size's header modes work
+ * as before: the picture size is theirs.  While a source size is set, m2v_push_frames / 420 / rgb and their _pull forms, m2v_push_beats,
+ * m2v_push_packed and every m2v_strip_* entry that starts something answer M2V_E_STATE: the port's staging is sized for frames of the
+ * coded size, and strips take whole padded frames.
+ */
+enum { M2V_SCALE_TRIANGLE = 0, M2V_SCALE_AREA = 1 };
+#define M2V_SCALE_MAXTAPS 16
+int m2v_set_source_size(m2v_enc *e, int src_width, int src_height, int filter);
+/* The taps of output sample x (0 ... dst - 1) by the definition above: returns n, *first = the first tap's sample index (may be negative),
+ * coeff[0 ... n - 1] = c(first) ..., the rest 0.  Pure arithmetic, no GPU; the single source of the tables the kernel reads.
+ * M2V_E_PARAM for an unknown filter, src or dst outside 1 ... 16384, src > 8 * dst, x outside the output.  first and coeff may be NULL. */
+int m2v_scale_taps(int filter, int src, int dst, int x, int *first, uint16_t coeff[M2V_SCALE_MAXTAPS]);
+
 /* `i_sequence_stop` pulse with i_en = 0 (RTL:1090-1091; SIM/tb_mpeg2encoder.v:249-252). A frame
  * in progress is completed with black pixels (RTL:1048-1056). No effect while idle. */
 int m2v_sequence_stop(m2v_enc *e);
