@@ -121,6 +121,20 @@ MUX_KINDS = {"ts": 1, "ps": 2}                                   # M2V_MUX_*
 MUX_OK, MUX_SYNTAX, MUX_OVERFLOW = 0, -2, -3
 
 
+# m2v_decode_stat (include/m2v_mi355x.h): the record of m2v_decode_device, 72 bytes (Mpeg2Encoder.decode_report)
+DECODE_STAT_DTYPE = np.dtype([("es_bytes", "<u8"), ("out_bytes", "<u8"), ("frame_bytes", "<u8"), ("err_offset", "<u8"), ("pictures", "<u4"),
+                              ("gops", "<u4"), ("width", "<u4"), ("height", "<u4"), ("repeated_headers", "<u4"), ("chains", "<u4"),
+                              ("status", "<i4"), ("reserved", "<u4", (3,))])
+DEC_MODES = {"iso": 0, "module": 1}                              # M2V_DEC_*
+DEC_OK, DEC_SYNTAX, DEC_OVERFLOW = 0, -2, -3
+DEC_STATUS = {0: "M2V_DEC_OK", -2: "M2V_DEC_SYNTAX", -3: "M2V_DEC_OVERFLOW"}
+
+
+def decode_scan_tile():
+    """m2v_decode_scan_tile: the byte span after which the device decoder's start-code scan hands over to another workgroup"""
+    return int(lib().m2v_decode_scan_tile())
+
+
 def _mux_kind(kind):
     if isinstance(kind, str):
         if kind not in MUX_KINDS:
@@ -386,6 +400,9 @@ def lib(debug=False):
             L.m2v_mux_device.argtypes = [vp, ci, vp, vp, vp, sz, vp, sz, vp]
             L.m2v_mux_scan_tile.argtypes = []
             L.m2v_set_source_size.argtypes = [vp, ci, ci, ci]
+            L.m2v_decode_device.argtypes = [vp, vp, sz, vp, sz, ci, ci, vp]
+            L.m2v_decode_report.argtypes = [vp, vp]
+            L.m2v_decode_scan_tile.argtypes = []
             L.m2v_scale_taps.argtypes = [ci, ci, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_uint16)]
         except AttributeError:
             # an OLDER build handed in through M2V_LIB for a same-box A/B (tools/ab.sh) may lack the newer entry points; the library of
@@ -802,6 +819,42 @@ class Mpeg2Encoder:
         self._chk(self._L.m2v_mux_device(self._h, k, es.data_ptr(), off, nb, len(seg), out.data_ptr(), cap,
                                          torch.cuda.current_stream(es.device).cuda_stream), "m2v_mux_device")
         return out, self.mux_report()
+
+    def decode_report(self):
+        """m2v_decode_report: the record of the last decode_device on this handle, a numpy record of DECODE_STAT_DTYPE"""
+        out = np.zeros(1, DECODE_STAT_DTYPE)
+        self._chk(self._L.m2v_decode_report(self._h, out.ctypes.data), "m2v_decode_report")
+        return out[0]
+
+    def decode_device(self, es, layout="i420", mode="iso", out=None):
+        """m2v_decode_device: the MPEG-2 elementary stream in the one-dimensional uint8 device tensor `es` (at any byte alignment) decoded
+        on the device to 4:2:0 frames in `layout`; mode "iso" is decoder.decode(quirks=False), "module" the module's own loop
+        (quirks=True).  Returns (frames [pictures, frame_bytes] uint8 on es's device, record).  out: a contiguous uint8 tensor to write into
+        (all of it is the capacity); None: the call probes the stream first and allocates.  A status other than M2V_DEC_OK raises
+        M2VError, whose text names the status and err_offset (decode_report still answers the record)."""
+        import torch
+        if not isinstance(es, torch.Tensor) or es.dtype != torch.uint8 or es.dim() != 1 or not es.is_cuda or es.device.index != self.device:
+            raise ValueError("decode_device: a one-dimensional uint8 tensor on the handle's device is required")
+        if es.stride(0) != 1 and es.numel() > 1:
+            raise ValueError("decode_device: the tensor must be contiguous")
+        code = _layout420(layout)
+        m = DEC_MODES[mode] if isinstance(mode, str) else int(mode)
+        stream = torch.cuda.current_stream(es.device).cuda_stream
+
+        def call(ptr, cap):
+            self._chk(self._L.m2v_decode_device(self._h, es.data_ptr(), es.numel(), ptr, cap, code, m, stream), "m2v_decode_device")
+            r = self.decode_report()
+            if r["status"] != DEC_OK:
+                raise M2VError("m2v_decode_device: %s (%d), err_offset %d" % (DEC_STATUS.get(int(r["status"]), "?"), r["status"], r["err_offset"]))
+            return r
+        if out is None:
+            r = call(None, 0)
+            out = torch.empty(int(r["pictures"]) * int(r["frame_bytes"]), dtype=torch.uint8, device=es.device)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != es.device or not out.is_contiguous():
+            raise ValueError("decode_device: out must be a contiguous uint8 tensor on the stream's device")
+        r = call(out.data_ptr() or None, out.numel()) if out.numel() else call(None, 0)
+        n, fb = int(r["pictures"]), int(r["frame_bytes"])
+        return out.reshape(-1)[:n * fb].reshape(n, fb), r
 
     def set_stream_desc(self, desc):
         """m2v_set_stream_desc: what every sequence started from now on says about itself in its sequence headers and time codes - a

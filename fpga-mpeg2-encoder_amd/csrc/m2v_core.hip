@@ -569,6 +569,7 @@ void m2v_destroy(m2v_enc *e)
     scene_release(e);
     seq_release(e);
     mux_release(e);
+    dec_release(e);
     if (e->ev_gop) (void)hipEventDestroy(e->ev_gop);
     if (e->h_redo) (void)hipHostFree(e->h_redo);
     for (auto p : e->rec_pool) (void)hipFree(p);
@@ -705,6 +706,11 @@ int m2v_set_option(m2v_enc *e, const char *name, long long value)
         // (a chunk's frames are buffered on the device: 65536 frames of the largest geometry would be 824 GB)
         if (value > 65536) { e->set_err("m2v_set_option: batch_frames is at most 65536"); return M2V_E_PARAM; }
         e->batch_frames = (size_t)value;
+        return M2V_OK;
+    }
+    if (!strcmp(name, "decode_batch")) {
+        if (value < 0 || value > 65536) { e->set_err("m2v_set_option: decode_batch is 0 (the default) .. 65536 pictures"); return M2V_E_PARAM; }
+        e->decode_batch = (size_t)value;
         return M2V_OK;
     }
     if (!strcmp(name, "profile")) { e->profile = value != 0; return M2V_OK; }

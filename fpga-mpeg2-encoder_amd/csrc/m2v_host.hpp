@@ -30,6 +30,9 @@
 //   m2v_mux.hip       m2v_set_mux_out / m2v_mux_device: transport or program stream out of the stream in HBM.  Its three kernels touch no
 //                     device global and nothing of m2v_kernels.hpp, so they live in their own unit with their launches (m2v_mux_kernels.hpp
 //                     holds the arithmetic, for the device and the host alike)
+//   m2v_decode.hip    m2v_decode_device: an elementary stream in HBM back to 4:2:0 frames.  Its kernels touch no device global and nothing of
+//                     m2v_kernels.hpp, so they live in their own unit with their launches (m2v_decode_kernels.hpp holds the arithmetic, for
+//                     the device and the host alike)
 //   m2v_scale.hip     m2v_set_source_size: frames of another size resampled to the picture size in front of the conversions - the setting,
 //                     the tap tables (m2v_scale_taps), k_scale and its launch (m2v_scale_kernels.hpp holds the arithmetic, for the device
 //                     and the host alike; no device global, nothing of m2v_kernels.hpp)
@@ -392,6 +395,19 @@ struct m2v_enc {
     bool mux_pending = false;             // a resident call with a container is in flight: its records have not moved to mux_q yet
     Records<m2v_mux_stat> mux_q;        // the last mux's records nobody has popped yet
 
+    // the decoder (m2v_decode.hip): its work buffers - state, tile counts, start-code events, picture table, the chunk's macroblock records,
+    // DC values, levels and planar pictures, the launch lists; no recording references them - allocated by the first decode, and the
+    // pinned memory the plan's record and picture types arrive in
+    DevBuf<uint8_t> d_dec_st, d_dec_pics, d_dec_mb, d_dec_buf;
+    DevBuf<uint32_t> d_dec_tiles, d_dec_list;
+    DevBuf<unsigned long long> d_dec_ev;
+    DevBuf<int32_t> d_dec_dc;
+    DevBuf<int16_t> d_dec_lv;
+    uint8_t *h_dec = nullptr;
+    size_t h_dec_cap = 0;
+    size_t decode_batch = 0;              // option "decode_batch": pictures per chunk (0: as many as keep the levels within 256 MiB, 256 at most)
+    m2v_decode_stat dec_rec{};            // the last call's record (m2v_decode_report)
+
     // debug bookkeeping of the last resident encode
     size_t dbg_frames = 0;
     std::vector<int> dbg_rec_slot;
@@ -602,6 +618,9 @@ void mux_resident(m2v_enc *e, hipStream_t s, const uint8_t *d_out, size_t cap, s
 // a completed mux's records (its stream has been waited for) to the handle's queue
 void mux_collect(m2v_enc *e);
 void mux_release(m2v_enc *e);
+
+// ---- m2v_decode.hip: m2v_decode_device ----
+void dec_release(m2v_enc *e);
 
 // ---- m2v_launch.hip: everything that touches device code ----
 // The constant tables live in each device's copy of the code object: uploaded once per device, whichever thread creates the first

@@ -6,7 +6,12 @@
 //          [-fps N/D] [-aspect 1:1|4:3|16:9|2.21:1] [-bitrate B] [-vbv K] [-colour bt601|bt709|P,T,M] [-repeat-headers]
 //          [-scale SWxSH [-filter triangle|area]]
 //          in.yuv W H out.m2v  [in2.yuv W2 H2 out2.m2v ...]
+//   m2v_tb -decode in.m2v out.yuv [-reconfmt i420|yv12|nv12|nv21] [-mode iso|module] [-d device]
 //
+// -decode: the other way - the elementary stream of in.m2v decoded on the device (m2v_decode_device: a probe for the size, then the
+// decode) into 4:2:0 frames of the header's size in -reconfmt (default i420), frame behind frame in out.yuv.  -mode iso (default): the
+// standard's reconstruction, for streams coded with -conformant; -mode module: the module's own loop, for every other stream of this
+// encoder.  A stream the decoder refuses ends with its status and the offset of the unit in error, exit status 1.
 // -pad: W, H are any size from 49 up; the files hold frames of that size in the chosen format, which are padded to whole macroblocks on
 // the device (m2v_set_frame_size) - the stream is the module's for the padded frames.  -truesize: -pad, and the stream's headers say
 // W x H instead of the padded size (M2V_HEADER_TRUE; not the module's header).  Neither goes with -bubbles: there are no partial macroblocks.
@@ -61,8 +66,70 @@
 #include "../../include/m2v_container.h"
 #include "../../include/m2v_mi355x.h"
 
+static int decode_main(int argc, char **argv)
+{
+    const char *in = argv[2], *out = argv[3];
+    int layout = M2V_420_I420, mode = M2V_DEC_ISO, dev = 0;
+    for (int i = 4; i < argc; ++i) {
+        const char *v = i + 1 < argc ? argv[i + 1] : "";
+        if (!strcmp(argv[i], "-reconfmt")) {
+            const char *names[4] = {"i420", "yv12", "nv12", "nv21"};
+            for (layout = 0; layout < 4 && strcmp(v, names[layout]); ++layout) {}
+            ++i;
+        } else if (!strcmp(argv[i], "-mode")) {
+            mode = !strcmp(v, "iso") ? M2V_DEC_ISO : !strcmp(v, "module") ? M2V_DEC_MODULE : -1;
+            ++i;
+        } else if (!strcmp(argv[i], "-d")) {
+            dev = atoi(v);
+            ++i;
+        } else {
+            fprintf(stderr, "m2v_tb -decode in.m2v out.yuv [-reconfmt i420|yv12|nv12|nv21] [-mode iso|module] [-d device]\n");
+            return 2;
+        }
+    }
+    FILE *f = fopen(in, "rb");
+    if (!f) { perror(in); return 1; }
+    std::vector<uint8_t> es;
+    uint8_t chunk[65536];
+    for (size_t n; (n = fread(chunk, 1, sizeof chunk, f)) > 0;) es.insert(es.end(), chunk, chunk + n);
+    fclose(f);
+    int err = 0;
+    m2v_enc *e = m2v_create(7, 7, 3, 2, dev, &err);
+    if (!e) { fprintf(stderr, "m2v_create: %s\n", m2v_last_error(nullptr)); return 1; }
+    void *d_es = nullptr, *d_out = nullptr;
+    m2v_decode_stat r;
+    int rc = 1;
+    if (hipMalloc(&d_es, es.size() + 1) != hipSuccess || hipMemcpy(d_es, es.data(), es.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        fprintf(stderr, "m2v_tb: no device memory for the stream\n");
+    } else if (m2v_decode_device(e, d_es, es.size(), nullptr, 0, layout, mode, nullptr) != M2V_OK || m2v_decode_report(e, &r) != M2V_OK) {
+        fprintf(stderr, "m2v_decode_device: %s\n", m2v_last_error(e));
+    } else if (r.status == M2V_DEC_OK && hipMalloc(&d_out, (size_t)r.out_bytes + 1) != hipSuccess) {
+        fprintf(stderr, "m2v_tb: no device memory for %llu bytes of frames\n", (unsigned long long)r.out_bytes);
+    } else if (r.status == M2V_DEC_OK && (m2v_decode_device(e, d_es, es.size(), d_out, (size_t)r.out_bytes, layout, mode, nullptr) != M2V_OK ||
+                                          m2v_decode_report(e, &r) != M2V_OK)) {
+        fprintf(stderr, "m2v_decode_device: %s\n", m2v_last_error(e));
+    } else if (r.status != M2V_DEC_OK) {
+        fprintf(stderr, "%s: not decoded: status %d, the unit at byte %llu\n", in, (int)r.status, (unsigned long long)r.err_offset);
+    } else {
+        std::vector<uint8_t> frames((size_t)r.out_bytes);
+        FILE *o = fopen(out, "wb");
+        if (hipMemcpy(frames.data(), d_out, frames.size(), hipMemcpyDeviceToHost) != hipSuccess || !o || fwrite(frames.data(), 1, frames.size(), o) != frames.size()) {
+            fprintf(stderr, "m2v_tb: cannot write %s\n", out);
+        } else {
+            printf("%s: %u pictures of %u x %u, %u GOPs -> %s (%llu bytes)\n", in, r.pictures, r.width, r.height, r.gops, out, (unsigned long long)r.out_bytes);
+            rc = 0;
+        }
+        if (o) fclose(o);
+    }
+    if (d_es) (void)hipFree(d_es);
+    if (d_out) (void)hipFree(d_out);
+    m2v_destroy(e);
+    return rc;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc >= 4 && !strcmp(argv[1], "-decode")) return decode_main(argc, argv);
     int XL = 7, YL = 6, VL = 3, Q = 2, pf = 23, dev = 0, bubbles = 0, conformant = 0, want_ps = 0, want_ts = 0, layout420 = -1, layouts = 0, rgb = -1, matrix = M2V_RGB_BT601,
         bad_matrix = 0, pad = 0, truesize = 0, stats = 0, reconfmt = M2V_420_I420, devmux = 0;
     const char *recon = nullptr;
