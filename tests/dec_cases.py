@@ -115,36 +115,43 @@ extern "C" unsigned dec_host_scan_tile(void) { return m2v::dec::kScanTile; }
 _host = None
 
 
+def build_host(kernels_dir=None):
+    """the harness above over tools/dec_host.hpp, compiled with g++ (no HIP) -> the library.  kernels_dir: a directory searched for
+    m2v_decode_kernels.hpp in front of csrc (tests/test_dec_cases.py compiles altered copies of the header from a temporary one)"""
+    d = tempfile.mkdtemp(prefix="m2v_dec_host_")
+    src, so = os.path.join(d, "dec_host.cpp"), os.path.join(d, "libdec_host.so")
+    with open(src, "w") as f:
+        f.write(_HARNESS)
+    inc = os.path.join(os.path.dirname(os.path.abspath(M.__file__)), "csrc")
+    first = ["-I", kernels_dir] if kernels_dir else []
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Werror"] + first + ["-I", inc, "-I", os.path.join(ROOT, "tools"), "-o", so, src])
+    L = ctypes.CDLL(so)
+    L.dec_host_decode.restype = ctypes.c_longlong
+    L.dec_host_decode.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(Stat)]
+    L.dec_host_vlc.restype = ctypes.c_uint
+    L.dec_host_vlc.argtypes = [ctypes.c_int, ctypes.c_uint]
+    L.dec_host_idct.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    L.dec_host_dequant.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    L.dec_host_dequant_many.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    L.dec_host_scan_tile.restype = ctypes.c_uint
+    return L
+
+
 def host_lib():
-    """the harness above, tools/dec_host.hpp and csrc/m2v_decode_kernels.hpp, compiled with g++ (no HIP)"""
+    """tools/dec_host.hpp and csrc/m2v_decode_kernels.hpp as they stand"""
     global _host
     if _host is None:
-        d = tempfile.mkdtemp(prefix="m2v_dec_host_")
-        src, so = os.path.join(d, "dec_host.cpp"), os.path.join(d, "libdec_host.so")
-        with open(src, "w") as f:
-            f.write(_HARNESS)
-        inc = os.path.join(os.path.dirname(os.path.abspath(M.__file__)), "csrc")
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Werror", "-I", inc, "-I", os.path.join(ROOT, "tools"), "-o", so, src])
-        L = ctypes.CDLL(so)
-        L.dec_host_decode.restype = ctypes.c_longlong
-        L.dec_host_decode.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(Stat)]
-        L.dec_host_vlc.restype = ctypes.c_uint
-        L.dec_host_vlc.argtypes = [ctypes.c_int, ctypes.c_uint]
-        L.dec_host_idct.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        L.dec_host_dequant.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-        L.dec_host_dequant_many.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-        L.dec_host_scan_tile.restype = ctypes.c_uint
-        _host = L
+        _host = build_host()
     return _host
 
 
-def host_decode(stream, layout="i420", mode="module", cap=None):
-    """-> (frames [n, frame bytes] or None, the record as a dict)"""
+def host_decode(stream, layout="i420", mode="module", cap=None, lib=None):
+    """-> (frames [n, frame bytes] or None, the record as a dict); lib: a library of build_host() other than host_lib()"""
     stream = bytes(stream)
     room = (1 << 26) if cap is None else cap
     out = np.zeros(room, np.uint8)
     rec = Stat()
-    host_lib().dec_host_decode(stream, len(stream), M.LAYOUTS_420[layout], MODES[mode], out.ctypes.data, room, ctypes.byref(rec))
+    (lib or host_lib()).dec_host_decode(stream, len(stream), M.LAYOUTS_420[layout], MODES[mode], out.ctypes.data, room, ctypes.byref(rec))
     r = {k: getattr(rec, k) for k in STAT_FIELDS}
     if r["status"] != OK:
         return None, r
@@ -458,18 +465,47 @@ def tile_streams(conformant=False):
                  for seed, n, pf in TILE_SEEDS)
 
 
-def tile_census(streams, T):
+UNIT_KINDS = ("sequence", "sequence_ext", "display_ext", "gop", "picture", "picture_ext", "slice", "end")
+
+
+def unit_kinds(stream):
+    """[(offset, kind)] of every start code: a B5 is what the codes in front of it make it, as in decoder.py"""
+    out, codes = [], []
+    for a, c in _units(stream):
+        if c == 0xB5:
+            kind = ("sequence_ext" if codes[-1:] == [0xB3] else "picture_ext" if codes[-1:] == [0x00] else
+                    "display_ext" if codes[-2:] == [0xB3, 0xB5] else "")
+        else:
+            kind = {0xB3: "sequence", 0xB8: "gop", 0x00: "picture", 0xB7: "end"}.get(c, "slice" if 1 <= c <= 0xAF else "")
+        codes.append(c)
+        out.append((a, kind))
+    return out
+
+
+def tile_census(streams, T, by_kind=False):
     """what the streams' start codes do at the multiples of T: the set of "T-3", "T-2", "T-1", "T" (a start code begins there) and of
-    "slice", "picture", "sequence" (such a unit begins in one tile and ends in the next)"""
+    "slice", "picture", "sequence" (such a unit begins in one tile and ends in the next).
+    by_kind: instead the set of (kind of unit, where it begins) over UNIT_KINDS, where = "T-3" .. "T" as above, "16-3" .. "16" (so far
+    from a multiple of 16 that is not within 16 bytes of a multiple of T), and of ("tile", k) for every tile k a start code begins in"""
     got = set()
     for s in streams:
         u = _units(s)
+        if by_kind:
+            for a, kind in unit_kinds(s):
+                if a >= T - 3:
+                    got.add((kind, {T - 3: "T-3", T - 2: "T-2", T - 1: "T-1", 0: "T"}.get(a % T, "")))
+                if 16 <= (a + 3) % T and (a + 3) % T < T - 16:
+                    got.add((kind, {13: "16-3", 14: "16-2", 15: "16-1", 0: "16"}.get(a % 16, "")))
+                got.add(("tile", a // T))
+            continue
         for k, (a, c) in enumerate(u):
             end = u[k + 1][0] if k + 1 < len(u) else len(s)
             if a >= T - 3:
                 got |= {{T - 3: "T-3", T - 2: "T-2", T - 1: "T-1", 0: "T"}.get(a % T, "")}
             if a // T != (end - 1) // T:
                 got.add("slice" if 1 <= c <= 0xAF else "picture" if c == 0 else "sequence" if c == 0xB3 else "")
+    if by_kind:
+        return {g for g in got if g[1] != "" and g[0] != ""}
     return got - {""}
 
 

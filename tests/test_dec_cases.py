@@ -2,7 +2,9 @@
 decoder.py - valid streams frame for frame and count for count, every VLC function, both inverse transforms, the dequantisers and the
 vector wrap unit by unit, refusals on altered streams exactly where the definition refuses, the scan's tile boundaries, and the whole
 host build once more under AddressSanitizer and UBSan as a stand-alone program.  tests/test_gpu_decode.py runs the same streams on the
-device."""
+device.  The streams of tests/dec_writer.py - what the oracle encoder never writes - are asserted here from the writer's log to hold
+what their names say, go through the same checks, and catch ten one-line changes of the header each by a named case;
+tests/test_gpu_decode_streams.py runs them on the device."""
 import ctypes
 import os
 import subprocess
@@ -11,6 +13,7 @@ import numpy as np
 import pytest
 
 import dec_cases as D
+import dec_writer as W
 import transform_clips as T
 
 M = D.M
@@ -249,6 +252,284 @@ def test_two_bad_slices():
         assert f is None and (r["status"], r["err_offset"], r["out_bytes"]) == (D.SYNTAX, at, 0)
 
 
+# ---- the written streams (tests/dec_writer.py): what the oracle encoder never writes ----
+BAD_SIZES = ((0, 32), (32, 0), (2049, 32), (32, 2049))
+
+
+def check_layouts(stream):
+    """decoder.py against the host build in both modes and all four layouts"""
+    check_valid(stream)
+    for mode, quirks in BOTH:
+        d = M.decoder.decode(stream, quirks=quirks)
+        for layout in D.LAYOUTS[1:]:
+            f, r = D.host_decode(stream, layout, mode)
+            assert r["status"] == D.OK and np.array_equal(f, D.frames_of(d, layout)), (mode, layout)
+
+
+def _dequantised(intra, k, lvl, code):
+    """7.4.2 in front of the saturation, for the coefficient at scan position k"""
+    t = W._tabs()
+    if intra:
+        return 2 * lvl * t["intra_w"][t["raster"][k]] * 2 * code / 32
+    return (2 * lvl + (1 if lvl > 0 else -1)) * 16 * 2 * code / 32
+
+
+def test_written_qcodes():
+    s, L = W.qcodes()
+    assert L["pictures"] == [1, 2] and L["qcodes"] == [list(range(32))] * 2 and [k for k, _ in L["units"]].count("slice") == 64
+    assert len(L["blocks"]) == 64 * 6
+    for n, (intra, comp, levels) in enumerate(L["blocks"]):
+        code = (n // 6) % 32
+        assert intra == (n < 32 * 6)
+        f = [_dequantised(intra, k, lvl, code) for k, lvl in levels]
+        if code >= 17:
+            assert max(f) > 2047 and min(f) < -2048 and sum(v > 2047 for v in f) >= 2 and sum(v < -2048 for v in f) >= 2
+        if 1 <= code <= 16:
+            assert abs(f[0]) <= 2047 and abs(f[1]) <= 2047 and f[0] == -f[1]      # the pair of +-61 / +-60 does not saturate up to code 16
+    check_layouts(s)
+    d = M.decoder.decode(s, quirks=True)
+    assert d.slice_qcodes == [list(range(32))] * 2
+
+
+def test_written_dc_range():
+    s, L = W.dc_range()
+    got = {(comp != 0, size, sign) for comp, size, sign, _, _, _ in L["dc"]}
+    assert got == {(c, size, sign) for c in (False, True) for size in range(1, 12) for sign in (-1, 1)} | {(False, 0, 0), (True, 0, 0)}
+    for comps in ((0,), (1, 2)):
+        behind = [p for comp, _, _, p, _, _ in L["dc"] if comp in comps]
+        assert max(behind) > 4096 and min(behind) < -4096
+    # the resets: behind a non-intra macroblock between two intra ones, and at a slice start
+    mbs = L["mbs"]
+    first = {m: [e for e in L["dc"] if e[5] == m][0] for m in range(len(mbs)) if mbs[m]["kind"] == "intra"}
+    last = {m: [e for e in L["dc"] if e[5] == m and e[0] == 0][-1] for m in first}
+    between = [m for m in first if m >= 2 and mbs[m]["col"] >= 2 and mbs[m - 1]["kind"] == "coded" and mbs[m - 2]["kind"] == "intra" and mbs[m]["pic"] == 1]
+    assert between and all(last[m - 2][3] != 0 and first[m][4] == 0 for m in between)
+    starts = [m for m in first if mbs[m]["col"] == 0 and mbs[m]["row"] == 1 and mbs[m - 1]["kind"] == "intra"]
+    assert len(starts) == 3 and all(last[m - 1][3] != 0 and first[m][4] == 0 for m in starts)
+    check_layouts(s)
+
+
+def test_written_escapes():
+    s, L = W.escapes()
+    esc = L["esc"]
+    assert {(run, lvl) for run, lvl, _, _, _, _ in esc} >= {(run, lvl) for run in range(64) for lvl in (1, -1, 2047, -2047)}
+    assert sum(coded for _, _, _, _, _, coded in esc) >= 64                       # escapes of pairs that have a table code
+    assert any(intra and k == 63 for _, _, intra, _, k, _ in esc) and any(not intra and k == 63 for _, _, intra, _, k, _ in esc)
+    assert sum(first and not intra for _, _, intra, first, _, _ in esc) >= 160 and sum(intra for _, _, intra, _, _, _ in esc) == 96
+    assert any(run == 63 and first for run, _, _, first, _, _ in esc)
+    check_layouts(s)
+
+
+def test_written_saturate():
+    s, L = W.saturate()
+    assert L["qcodes"] == [[1, 16, 31]] * 2 and len(L["blocks"]) == 36
+    raster = W._tabs()["raster"]
+    dcs = iter(L["dc"])
+    for n, (intra, comp, levels) in enumerate(L["blocks"]):
+        assert intra == (n < 18)
+        sign = list(W.SIGNS.values())[n % 6]
+        want = {k: 2047 * sign(raster[k] & 7, raster[k] >> 3) for k in range(64)}
+        have = dict(levels)
+        if intra:
+            e = next(dcs)
+            have[0] = e[2] * 2047
+            assert e[1] == 11
+        assert have == want
+    assert len({tuple(lvl for k, lvl in levels if k >= 4) for _, _, levels in L["blocks"]}) == 6
+    check_layouts(s)
+
+
+def test_written_pmv_chain():
+    s, L = W.pmv_chain()
+    mbs = L["mbs"]
+    assert L["pictures"] == [1, 2, 2] and len(mbs) == 27
+    assert {(c, m["wrap"][c]) for m in mbs for c in (0, 1) if m["wrap"][c]} == {(0, 1), (0, -1), (1, 1), (1, -1)}
+    assert any(m["wrap"][c] == 1 and m["pmv"][c] == 15 and m["delta"][c] > 0 for m in mbs for c in (0, 1))
+    assert any(m["wrap"][c] == -1 and m["pmv"][c] == -16 and m["delta"][c] < 0 for m in mbs for c in (0, 1))
+    moved = lambda m: m["kind"] != "intra" and m["mv"] != (0, 0)
+    carried = [k for k in range(1, 27) if mbs[k]["col"] and mbs[k]["kind"] == mbs[k - 1]["kind"] == "not_coded" and moved(mbs[k - 1]) and mbs[k]["pmv"] == mbs[k - 1]["mv"]]
+    assert len(carried) >= 3 and any(mbs[k]["delta"] == (0, 0) for k in carried)
+    behind_intra = [k for k in range(11, 27) if mbs[k]["col"] == 2 and mbs[k - 1]["kind"] == "intra" and moved(mbs[k - 2])]
+    assert behind_intra and all(mbs[k]["pmv"] == (0, 0) and moved(mbs[k]) for k in behind_intra)
+    starts = [k for k in range(10, 27) if mbs[k]["col"] == 0 and mbs[k]["row"] and moved(mbs[k - 1])]
+    assert len(starts) >= 3 and all(mbs[k]["pmv"] == (0, 0) and moved(mbs[k]) for k in starts)
+    check_layouts(s)
+    for quirks in (True, False):
+        assert [m["mv"] for m in sum(M.decoder.decode(s, quirks=quirks).mbs, [])] == [m["mv"] for m in mbs]
+
+
+@pytest.mark.parametrize("w,h", W.SIZES, ids=lambda v: str(v))
+def test_written_sizes(w, h):
+    s, L = W.sized(w, h)
+    mbw, mbh = (w + 15) // 16, (h + 15) // 16
+    assert [k for k, _ in L["units"]].count("slice") == mbh * len(L["pictures"]) and len(L["mbs"]) == mbw * mbh * len(L["pictures"])
+    assert M.decoder.sequence_headers(s)[:2] == (w, h)
+    if (w, h) == (1, 1):
+        assert len(L["pictures"]) >= 12 and M.frame_bytes(1, 1, "i420") == 3 and {1, 2} == set(L["pictures"])
+    check_layouts(s)
+
+
+def test_sizes_outside_the_device():
+    """0 and 2049 in either dimension: the device decodes 1 .. 2048 (include/m2v_mi355x.h), the host build says where"""
+    for w, h in BAD_SIZES:
+        x = W.bad_size(w, h)
+        for mode in ("module", "iso"):
+            f, r = D.host_decode(x, "i420", mode)
+            assert f is None and (r["status"], r["err_offset"], r["out_bytes"]) == (D.SYNTAX, 0, 0), (w, h, r)
+
+
+def test_written_many_pictures():
+    s, L = W.many_pictures()
+    assert len(L["pictures"]) == 400 > 256 and [k for k, t in enumerate(L["pictures"]) if t == 1] == list(W.MANY_I) and {255, 256, 257} <= set(W.MANY_I)
+    # more start codes than the event list decode_impl (csrc/m2v_decode.hip) guesses first: max(1024, n / 16 + 64) - the scan runs twice
+    assert len(L["units"]) == D.prefixes(s) > max(1024, len(s) // 16 + 64)
+    p = [m for m in L["mbs"] if L["pictures"][m["pic"]] == 2]
+    assert len(p) == 2 * (400 - len(W.MANY_I)) and all(m["kind"] == "not_coded" and m["mv"] != (0, 0) and abs(m["mv"][0]) <= 4 for m in p)
+    check_valid(s)
+    assert M.decoder.decode(s).repeated_headers == 2
+
+
+def _source(name):
+    return open(os.path.join(os.path.dirname(os.path.abspath(M.__file__)), "csrc", name)).read()
+
+
+def test_written_big_chunk():
+    """One default chunk of more than 8192 x 256 x 16 bytes.  decoder.py would need 200 s a mode for the 97 280 macroblocks, so: the
+    host build against decoder.py on the stream's first two pictures (the I picture and the first P picture, closed with an end code),
+    both modes; then the host build's frames 2, 3, 128 and 255 of the whole stream against decoder._predict applied to the frame in
+    front with the writer's vectors.  The GPU test takes the host build's frames"""
+    import re
+    s, L = W.big_chunk()
+    src = _source("m2v_decode.hip")
+    level_bytes = re.search(r"kDecLevelBytes = (\d+)u << (\d+);", src)
+    batch_max = int(re.search(r"kDecBatchMax = (\d+);", src).group(1))
+    level_bytes = int(level_bytes.group(1)) << int(level_bytes.group(2))
+    w, h, n = W.BIG["w"], W.BIG["h"], W.BIG["n"]
+    mbw, mbh = w // 16, h // 16
+    assert "std::min(kDecBatchMax, kDecLevelBytes / (mbs * 768))" in src
+    assert min(batch_max, level_bytes // (mbw * mbh * 768)) == 256 == n == len(L["pictures"])
+    assert n * M.frame_bytes(w, h, "i420") > 8192 * 256 * 16 and L["pictures"] == [1] + [2] * 255
+    assert len({tuple(m["mv"] for m in L["mbs"][k * mbw * mbh:(k + 1) * mbw * mbh]) for k in range(1, n)}) >= 5
+    s2, L2 = W.big_chunk(2)
+    assert s2[:len(s2) - 64] == s[:len(s2) - 64]
+    check_valid(s2)
+    for mode, quirks in BOTH:
+        f, r = D.host_decode(s, "i420", mode)
+        assert r["status"] == D.OK and f.shape == (n, M.frame_bytes(w, h, "i420"))
+        assert np.array_equal(f[:2], D.host_decode(s2, "i420", mode)[0])
+        for k in (2, 3, 128, 255):
+            y, u, v = (a.astype(np.int64) for a in M.planes_of_recon(f[k - 1:k], w, h, "i420"))
+            y, u, v = y[0], u[0], v[0]
+            Y, U, V = np.zeros_like(y), np.zeros_like(u), np.zeros_like(v)
+            for m in L["mbs"][k * mbw * mbh:(k + 1) * mbw * mbh]:
+                assert m["pic"] == k and m["kind"] == "not_coded"
+                col, row, mv = m["col"], m["row"], m["mv"]
+                cmv = (mv[0] >> 1, mv[1] >> 1) if quirks else (int(mv[0] / 2), int(mv[1] / 2))
+                Y[16 * row:16 * row + 16, 16 * col:16 * col + 16] = M.decoder._predict(y, 16 * col, 16 * row, mv[0], mv[1], 16, quirks)
+                U[8 * row:8 * row + 8, 8 * col:8 * col + 8] = M.decoder._predict(u, 8 * col, 8 * row, cmv[0], cmv[1], 8, quirks)
+                V[8 * row:8 * row + 8, 8 * col:8 * col + 8] = M.decoder._predict(v, 8 * col, 8 * row, cmv[0], cmv[1], 8, quirks)
+            assert np.array_equal(f[k], np.concatenate([Y.reshape(-1), U.reshape(-1), V.reshape(-1)]).astype(np.uint8)), (mode, k)
+
+
+def test_written_stuffed():
+    T = D.host_lib().dec_host_scan_tile()
+    streams = W.stuffed(T)
+    where = ("T-3", "T-2", "T-1", "T", "16-3", "16-2", "16-1", "16")
+    assert D.tile_census([s for s, _ in streams], T, by_kind=True) >= {(kind, at) for kind in D.UNIT_KINDS for at in where}
+    for j, (s, L) in enumerate(streams):
+        assert [a for _, a in L["units"]] == [a for a, _ in D._units(s)] and [k for k, _ in L["units"]] == [k for _, k in D.unit_kinds(s)]
+        for kind in D.UNIT_KINDS:                                # from the writer's log: the last unit of the kind is where stream j puts it
+            at = [a for k, a in L["units"] if k == kind][-1]
+            assert (at - (j % 4 - 3)) % (T if j < 4 else 16) == 0 and (j < 4) == ((at + 3) % T < 4)
+        check_valid(s)
+    # the existing census, on the new streams too
+    assert D.tile_census([s for s, _ in streams], T) >= {"T-3", "T-2", "T-1", "T"}
+
+
+def test_written_stuffed_2mib():
+    """The full stream through decoder.py in MODULE mode only (20 s of zeros); in ISO mode the host build on the full stream against
+    decoder.py on the same units written without stuffing"""
+    T = D.host_lib().dec_host_scan_tile()
+    s, L = W.stuffed_2mib(T)
+    assert len(s) > 2 << 20 and len(s) > 512 * T
+    tiles = {a // T for _, a in L["units"]}
+    assert min(tiles) == 0 and 511 in tiles and {512, 513, 514} <= tiles
+    assert [a // T for k, a in L["units"] if k == "sequence"] == [0, 514]
+    census = D.tile_census([s], T, by_kind=True)
+    assert ("picture", "T-3") in census and {("tile", 0), ("tile", 511), ("tile", 512), ("tile", 514)} <= census
+    check_valid(s, modes=BOTH[:1])
+    plain, _ = W.stuffed_2mib(T, stuffing=False)
+    assert len(plain) < 1024
+    check_valid(plain)
+    f, r = D.host_decode(s, "i420", "iso")
+    assert r["status"] == D.OK and r["repeated_headers"] == 1 and np.array_equal(f, D.frames_of(M.decoder.decode(plain, quirks=False)))
+
+
+def test_written_refusals():
+    """refused by the definition in both modes, and the host build names the unit the writer put the fault into"""
+    cases = list(W.refusals().items())
+    assert len(cases) == 17 and set(W.REFUSED_IN) | {"slice_code_mbh_plus_1", "p_behind_repeated_header", "p_pictures_only"} == set(W.refusals())
+    refused, accepted, _ = _judge(cases)
+    assert accepted == 0 and refused == 2 * len(cases)
+    for name, x in cases:
+        u = D._units(x)
+        if name.startswith("p_"):                                # no reference: the first picture header
+            want = [a for a, c in u if c == 0x00][0]
+            assert len(u) == (455 if name == "p_pictures_only" else 11)
+        elif name == "slice_code_mbh_plus_1":
+            want = [a for a, c in u if c == 3][0]
+        else:                                                    # the slice of (picture, row)
+            picture, row = W.REFUSED_IN[name]
+            want = [a for a, c in u if 1 <= c <= 0xAF][2 * picture + row]
+        for mode in ("module", "iso"):
+            r = D.host_decode(x, "i420", mode)[1]
+            assert (r["status"], r["err_offset"]) == (D.SYNTAX, want), (name, r)
+
+
+# ---- one textual change at a time in a copy of csrc/m2v_decode_kernels.hpp: each is caught by a named written case ----
+MUTANTS = (
+    ("index_63", "if (k >= 64 || b.err) return false;", "if (k >= 63 || b.err) return false;", "escapes"),
+    ("level_-2048", "if (lvl == 0 || lvl == -2048) return false;", "if (lvl == 0) return false;", "refusal:escape_level_-2048"),
+    ("iso_dc_clamp", "    return v < -2048 ? -2048 : v > 2047 ? 2047 : v;\n}", "    return v;\n}", "dc_range"),
+    ("wrap_14", "else if (v > 15) v -= 32;", "else if (v > 14) v -= 32;", "pmv_chain"),
+    ("chroma_width", "const uint32_t cw = (w + 1u) / 2u, ch = (h + 1u) / 2u, ysz = w * h;", "const uint32_t cw = w / 2u, ch = (h + 1u) / 2u, ysz = w * h;", "sizes:15x17"),
+    ("row_store_19", "v = (int32_t)((U)v << 14) >> 14;", "v = (int32_t)((U)v << 13) >> 13;", "saturate"),
+    ("module_floor", "const int32_t lo = mode == kModule ? -2047 : -2048;\n    return v < lo", "const int32_t lo = -2048;\n    return v < lo", "qcodes"),
+    ("dc_not_reset", "if (!intra) s.dc_pred[0] = s.dc_pred[1] = s.dc_pred[2] = 0;", "", "dc_range"),
+    ("first_escape", "if (first && (w >> 31)) {", "if (first && (w >> 31) && false) {", "escapes"),
+    ("qcode_0_as_1", "const uint32_t qcode = get(b, 5);", "uint32_t qcode = get(b, 5); if (!qcode) qcode = 1;", "qcodes"),
+)
+
+
+def _written(name):
+    if name.startswith("refusal:"):
+        return W.refusals()[name[8:]]
+    if name.startswith("sizes:"):
+        return W.sized(*[int(v) for v in name[6:].split("x")])[0]
+    return getattr(W, name)()[0]
+
+
+def _agrees(lib, stream):
+    """the library gives the definition's answer on a stream, both modes, I420 and NV21"""
+    for mode, quirks in BOTH:
+        d, _ = D.spec(stream, quirks)
+        for layout in ("i420", "nv21"):
+            f, r = D.host_decode(stream, layout, mode, lib=lib)
+            if (d is None) != (r["status"] == D.SYNTAX) or (d is not None and not np.array_equal(f, D.frames_of(d, layout))):
+                return False
+    return True
+
+
+@pytest.mark.parametrize("name,old,new,case", MUTANTS, ids=[m[0] for m in MUTANTS])
+def test_written_cases_catch_mutants(tmp_path, name, old, new, case):
+    text = _source("m2v_decode_kernels.hpp")
+    assert text.count(old) == 1, "the line this mutant changes is not there (once)"
+    (tmp_path / "m2v_decode_kernels.hpp").write_text(text.replace(old, new))
+    lib = D.build_host(str(tmp_path))
+    assert _agrees(D.host_lib(), _written(case))
+    assert not _agrees(lib, _written(case)), "mutant %s slipped past %s" % (name, case)
+
+
 # ---- the host build under the sanitizers, as a program of its own ----
 def test_standalone_sanitizer_program(tmp_path):
     s = D.small()
@@ -261,6 +542,11 @@ def test_standalone_sanitizer_program(tmp_path):
     items += [(x, m) for x in (D.described(), D.ionly_stream(), D.two_bad_slices()[0]) + D.tile_streams() + D.tile_streams(conformant=True)
               for m in ("module", "iso")]
     items += [(x, m) for x in D.twin_streams().values() for m in ("module", "iso")]
+    # the written streams (tests/dec_writer.py); the large ones through one mode
+    written = [W.qcodes()[0], W.dc_range()[0], W.escapes()[0], W.saturate()[0], W.pmv_chain()[0]] + [W.sized(w, h)[0] for w, h in W.SIZES]
+    written += [x for x, _ in W.stuffed()] + list(W.refusals().values()) + [W.bad_size(w, h) for w, h in BAD_SIZES]
+    items += [(x, m) for x in written for m in ("module", "iso")]
+    items += [(W.many_pictures()[0], "iso"), (W.big_chunk()[0], "module"), (W.stuffed_2mib()[0], "iso")]
     first_clip = len(items)
     # every table code, escape, DC size and vector delta: each clip in both encodings, each through both modes
     items += [(D.clip_stream(fc[0], fc[1], conformant), m) for fc in D.clip_cases() for conformant in (False, True) for m in ("module", "iso")]
@@ -277,7 +563,7 @@ def test_standalone_sanitizer_program(tmp_path):
     lines = p.stdout.decode().split("\n")[:-1]
     assert len(lines) == len(items)
     # the program's verdicts are the library's
-    for k in (0, 1, 2, 200, 401, first_clip - 1, first_clip, first_clip + 171, len(items) - 1):
+    for k in (0, 1, 2, 200, 401, first_clip - 3, first_clip - 1, first_clip, first_clip + 171, len(items) - 1):
         stream, mode = items[k]
         want = D.host_decode(stream, D.LAYOUTS[k & 3], mode)[1]
         assert [int(v) for v in lines[k].split()[:4]] == [k, want["status"], want["err_offset"], want["pictures"]]
