@@ -49,6 +49,7 @@ EXPORTS = [
     "m2v_set_sequences", "m2v_sequence_report",
     "m2v_mux_bound", "m2v_set_mux_out", "m2v_mux_report", "m2v_mux_device", "m2v_mux_scan_tile",
     "m2v_set_source_size", "m2v_scale_taps",
+    "m2v_demux_bound", "m2v_demux_device", "m2v_demux_report", "m2v_demux_scan_tile",
 ]
 
 # the 4:2:0 entry points (kept apart: tests/test_abi.py matches EXPORTS against names of letters and underscores only)
@@ -128,6 +129,28 @@ DECODE_STAT_DTYPE = np.dtype([("es_bytes", "<u8"), ("out_bytes", "<u8"), ("frame
 DEC_MODES = {"iso": 0, "module": 1}                              # M2V_DEC_*
 DEC_OK, DEC_SYNTAX, DEC_OVERFLOW = 0, -2, -3
 DEC_STATUS = {0: "M2V_DEC_OK", -2: "M2V_DEC_SYNTAX", -3: "M2V_DEC_OVERFLOW"}
+
+
+# m2v_demux_stat (include/m2v_mi355x.h): one container's record of m2v_demux_device, 64 bytes (Mpeg2Encoder.demux_report), and
+# m2v_demux_stamp: one PES packet of a demultiplexed stream, 32 bytes (pts / dts = DEMUX_ABSENT when the header carries none)
+DEMUX_STAT_DTYPE = np.dtype([("src_offset", "<u8"), ("src_bytes", "<u8"), ("out_offset", "<u8"), ("out_bytes", "<u8"), ("err_offset", "<u8"),
+                             ("pes_packets", "<u4"), ("packets", "<u4"), ("discontinuities", "<u4"), ("skipped", "<u4"), ("stream", "<u4"),
+                             ("status", "<i4")])
+DEMUX_STAMP_DTYPE = np.dtype([("es_offset", "<u8"), ("pts", "<u8"), ("dts", "<u8"), ("src_offset", "<u8")])
+DEMUX_OK, DEMUX_SYNTAX, DEMUX_OVERFLOW, DEMUX_NOSTREAM = 0, -2, -3, -4
+DEMUX_STATUS = {0: "M2V_DEMUX_OK", -2: "M2V_DEMUX_SYNTAX", -3: "M2V_DEMUX_OVERFLOW", -4: "M2V_DEMUX_NOSTREAM"}
+DEMUX_ABSENT = 0xFFFFFFFFFFFFFFFF
+
+
+def demux_scan_tile():
+    """m2v_demux_scan_tile: the bytes of a transport stream after which the device demultiplexer hands over to another workgroup"""
+    return int(lib().m2v_demux_scan_tile())
+
+
+def demux_bound(sizes):
+    """m2v_demux_bound: bytes that always suffice for the elementary streams of containers of these sizes"""
+    a = (ctypes.c_uint64 * max(len(sizes), 1))(*[int(b) for b in sizes])
+    return int(lib().m2v_demux_bound(a, len(sizes)))
 
 
 def decode_scan_tile():
@@ -400,6 +423,11 @@ def lib(debug=False):
             L.m2v_mux_device.argtypes = [vp, ci, vp, vp, vp, sz, vp, sz, vp]
             L.m2v_mux_scan_tile.argtypes = []
             L.m2v_set_source_size.argtypes = [vp, ci, ci, ci]
+            L.m2v_demux_bound.restype = sz
+            L.m2v_demux_bound.argtypes = [vp, sz]
+            L.m2v_demux_device.argtypes = [vp, ci, vp, vp, vp, sz, ci, vp, sz, vp, sz, vp]
+            L.m2v_demux_report.argtypes = [vp, vp, sz]
+            L.m2v_demux_scan_tile.argtypes = []
             L.m2v_decode_device.argtypes = [vp, vp, sz, vp, sz, ci, ci, vp]
             L.m2v_decode_report.argtypes = [vp, vp]
             L.m2v_decode_scan_tile.argtypes = []
@@ -820,19 +848,84 @@ class Mpeg2Encoder:
                                          torch.cuda.current_stream(es.device).cuda_stream), "m2v_mux_device")
         return out, self.mux_report()
 
+    def demux_report(self, max_records=None):
+        """Pops the waiting records of m2v_demux_report, oldest first, at most max_records of them: a numpy structured array of
+        DEMUX_STAT_DTYPE - one per container of the last demux_device."""
+        return self._pop("m2v_demux_report", DEMUX_STAT_DTYPE, max_records)
+
+    def demux_device(self, src, kind, segments=None, stream=None, out=None, stamps=False, cap=None, stamp_cap=None):
+        """m2v_demux_device: the transport ("ts") or program ("ps") streams in the uint8 device tensor `src` - the whole tensor, or the
+        (offset, bytes) pairs of `segments`, at any byte alignment - back to the video elementary stream of each, demultiplexed on the
+        device: the inverse of mux_device.  stream: the PID / stream_id to take, None: found in each container.  Returns (out, records)
+        or, with stamps, (out, records, stamps): the streams in the one-dimensional uint8 tensor `out` on src's device (allocated from
+        m2v_demux_bound when not given), of which at most `cap` bytes are written (default: all of it), their records (demux_report):
+        stream b is out[out_offset : out_offset + out_bytes] where status is DEMUX_OK, and one DEMUX_STAMP_DTYPE record per PES packet as
+        an int64 device tensor [n, 4] (es_offset, pts, dts, src_offset; -1 = absent), the containers' stamps one behind the other;
+        stamp_cap: room for that many (None: one per transport packet / per nine bytes of program stream, always enough)."""
+        import torch
+        if not isinstance(src, torch.Tensor) or src.dtype != torch.uint8 or src.dim() != 1 or not src.is_cuda or src.device.index != self.device:
+            raise ValueError("demux_device: a one-dimensional uint8 tensor on the handle's device is required")
+        if src.stride(0) != 1 and src.numel() > 1:
+            raise ValueError("demux_device: the tensor must be contiguous")
+        k = _mux_kind(kind)
+        seg = [(0, src.numel())] if segments is None else [(int(a), int(b)) for a, b in segments]
+        if not seg or any(a < 0 or b < 0 or a + b > src.numel() for a, b in seg):
+            raise ValueError("demux_device: a segment lies outside the tensor, or there is none")
+        if out is None:
+            out = torch.empty(max(demux_bound([b for _, b in seg]), 32), dtype=torch.uint8, device=src.device)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != src.device or out.dim() != 1 or out.stride(0) != 1:
+            raise ValueError("demux_device: out must be a contiguous one-dimensional uint8 tensor on the containers' device")
+        cap = out.numel() if cap is None else int(cap)
+        if cap < 0 or cap > out.numel():
+            raise ValueError("demux_device: cap is 0 .. out.numel()")
+        st = None
+        if stamps:
+            if stamp_cap is None:       # a PES packet starts in a transport packet of its own / takes at least nine bytes of a program stream
+                stamp_cap = sum(b // 188 + 1 if k == MUX_KINDS["ts"] else b // 9 + 1 for _, b in seg)
+            st = torch.empty((max(int(stamp_cap), 1), 4), dtype=torch.int64, device=src.device)
+        off = (ctypes.c_uint64 * len(seg))(*[a for a, _ in seg])
+        nb = (ctypes.c_uint64 * len(seg))(*[b for _, b in seg])
+        self._chk(self._L.m2v_demux_device(self._h, k, src.data_ptr() or None, off, nb, len(seg), -1 if stream is None else int(stream),
+                                           out.data_ptr(), cap, st.data_ptr() if st is not None else None, int(stamp_cap) if st is not None else 0,
+                                           torch.cuda.current_stream(src.device).cuda_stream), "m2v_demux_device")
+        r = self.demux_report()
+        if st is None:
+            return out, r
+        return out, r, st[:min(int(stamp_cap), int(r["pes_packets"].sum()))]
+
     def decode_report(self):
         """m2v_decode_report: the record of the last decode_device on this handle, a numpy record of DECODE_STAT_DTYPE"""
         out = np.zeros(1, DECODE_STAT_DTYPE)
         self._chk(self._L.m2v_decode_report(self._h, out.ctypes.data), "m2v_decode_report")
         return out[0]
 
-    def decode_device(self, es, layout="i420", mode="iso", out=None):
+    def decode_device(self, es, layout="i420", mode="iso", out=None, container=None, stream=None):
         """m2v_decode_device: the MPEG-2 elementary stream in the one-dimensional uint8 device tensor `es` (at any byte alignment) decoded
         on the device to 4:2:0 frames in `layout`; mode "iso" is decoder.decode(quirks=False), "module" the module's own loop
         (quirks=True).  Returns (frames [pictures, frame_bytes] uint8 on es's device, record).  out: a contiguous uint8 tensor to write into
         (all of it is the capacity); None: the call probes the stream first and allocates.  A status other than M2V_DEC_OK raises
-        M2VError, whose text names the status and err_offset (decode_report still answers the record)."""
+        M2VError, whose text names the status and err_offset (decode_report still answers the record).
+
+        container = "ts" or "ps": `es` is one transport or program stream; it is demultiplexed on the device (demux_device, `stream` as
+        there) into a scratch tensor on the same HIP stream, and that is decoded.  The demux record is read once before the decode
+        call: one host wait of 64 bytes, which the decode's own probe pays anyway.  A demux status other than DEMUX_OK raises M2VError
+        naming the status and err_offset.  The scratch tensor is zeroed first and the stream handed on with the zero padding to a whole
+        32-byte word that the encoder writes behind sequence_end_code and a muxer drops: the decoder's definition wants it.  Without
+        the keyword the function is exactly what it was."""
         import torch
+        if container is not None:
+            if not isinstance(es, torch.Tensor) or es.dtype != torch.uint8 or es.dim() != 1 or not es.is_cuda or es.device.index != self.device:
+                raise ValueError("decode_device: a one-dimensional uint8 tensor on the handle's device is required")
+            if es.stride(0) != 1 and es.numel() > 1:
+                raise ValueError("decode_device: the tensor must be contiguous")
+            scratch = torch.zeros(demux_bound([es.numel()]) + 32, dtype=torch.uint8, device=es.device)
+            _, r = self.demux_device(es, container, stream=stream, out=scratch)
+            if r["status"][0] != DEMUX_OK:
+                raise M2VError("m2v_demux_device: %s (%d), err_offset %d" % (DEMUX_STATUS.get(int(r["status"][0]), "?"), r["status"][0],
+                                                                            r["err_offset"][0]))
+            es = scratch[int(r["out_offset"][0]):int(r["out_offset"][0]) + (int(r["out_bytes"][0]) + 31) // 32 * 32]
+        elif stream is not None:
+            raise ValueError("decode_device: stream needs a container")
         if not isinstance(es, torch.Tensor) or es.dtype != torch.uint8 or es.dim() != 1 or not es.is_cuda or es.device.index != self.device:
             raise ValueError("decode_device: a one-dimensional uint8 tensor on the handle's device is required")
         if es.stride(0) != 1 and es.numel() > 1:

@@ -23,6 +23,21 @@ class Picture(ctypes.Structure):
                 ("temporal_reference", ctypes.c_uint32), ("gop_start", ctypes.c_uint32), ("slices", ctypes.c_uint32)]
 
 
+class Stamp(ctypes.Structure):
+    """m2vc_stamp: one PES packet of a demultiplexed stream; pts / dts = ABSENT when the header carries none"""
+    _fields_ = [("es_offset", ctypes.c_uint64), ("pts", ctypes.c_uint64), ("dts", ctypes.c_uint64), ("src_offset", ctypes.c_uint64)]
+
+
+class DemuxInfo(ctypes.Structure):
+    _fields_ = [("out_bytes", ctypes.c_uint64), ("err_offset", ctypes.c_uint64), ("pes_packets", ctypes.c_uint32),
+                ("packets", ctypes.c_uint32), ("discontinuities", ctypes.c_uint32), ("skipped", ctypes.c_uint32),
+                ("stream", ctypes.c_uint32), ("status", ctypes.c_int32)]
+
+
+ABSENT = 0xFFFFFFFFFFFFFFFF
+E_PARAM, E_SYNTAX, E_OVERFLOW, E_NOSTREAM = -1, -2, -3, -4
+
+
 class ContainerError(RuntimeError):
     pass
 
@@ -39,6 +54,8 @@ def lib():
         L.m2vc_scan.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(StreamInfo), vp, sz, ctypes.POINTER(sz)]
         for f in (L.m2vc_mux_ps, L.m2vc_mux_ts):
             f.argtypes = [ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(sz)]
+        for f in (L.m2vc_demux_ps, L.m2vc_demux_ts):
+            f.argtypes = [ctypes.c_char_p, sz, ctypes.c_int, vp, sz, vp, sz, ctypes.POINTER(DemuxInfo)]
         _L = L
     return _L
 
@@ -46,7 +63,7 @@ def lib():
 def _chk(r, what):
     if r < 0:
         raise ContainerError("%s failed: %s" % (what, {-1: "bad parameter", -2: "not an elementary stream of this encoder",
-                                                      -3: "buffer too small"}.get(r, r)))
+                                                      -3: "buffer too small", -4: "no video stream in the container"}.get(r, r)))
 
 
 def frame_rate(code):
@@ -82,3 +99,42 @@ def mux_ps(es):
 def mux_ts(es):
     """MPEG-2 Transport Stream around the elementary stream `es`."""
     return _mux(lib().m2vc_mux_ts, "m2vc_mux_ts", es)
+
+
+def demux_raw(kind, src, stream=None, cap=None, stamp_cap=None):
+    """m2vc_demux_ts ("ts") / m2vc_demux_ps ("ps") as they answer: -> (status, DemuxInfo, elementary bytes, [Stamp]).  stream: the PID /
+    stream_id, None: found in the container.  cap / stamp_cap: the capacities handed over (None: what the container needs)."""
+    fn = {"ts": lib().m2vc_demux_ts, "ps": lib().m2vc_demux_ps}[kind]
+    src = bytes(src)
+    sid = -1 if stream is None else int(stream)
+    info = DemuxInfo()
+    r = fn(src, len(src), sid, None, 0, None, 0, ctypes.byref(info))
+    if r != 0:
+        return r, info, b"", []
+    need, pes = info.out_bytes, info.pes_packets
+    cap = need if cap is None else int(cap)
+    stamp_cap = pes if stamp_cap is None else int(stamp_cap)
+    out = ctypes.create_string_buffer(max(cap, 1))
+    stamps = (Stamp * max(stamp_cap, 1))()
+    r = fn(src, len(src), sid, out, cap, stamps, stamp_cap, ctypes.byref(info))
+    if r != 0:
+        return r, info, b"", []
+    return r, info, out.raw[:info.out_bytes], list(stamps[:min(pes, stamp_cap)])
+
+
+def _demux(kind, src, stream):
+    r, info, es, stamps = demux_raw(kind, src, stream)
+    if r == E_SYNTAX:
+        raise ContainerError("m2vc_demux_%s failed: the container breaks a rule at offset %d" % (kind, info.err_offset))
+    _chk(r, "m2vc_demux_%s" % kind)
+    return es, stamps, info
+
+
+def demux_ts(ts, pid=None):
+    """The video elementary stream of a transport stream -> (bytes, [Stamp] one per PES packet, DemuxInfo).  pid None: through PAT / PMT."""
+    return _demux("ts", ts, pid)
+
+
+def demux_ps(ps, stream_id=None):
+    """The video elementary stream of a program stream -> (bytes, [Stamp], DemuxInfo).  stream_id None: the first video stream's."""
+    return _demux("ps", ps, stream_id)

@@ -4,6 +4,7 @@
 // pictures in display order (RTL:2670-2682: no B pictures), so DTS = PTS and no reordering is needed.
 #include "../../include/m2v_container.h"
 
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -383,6 +384,231 @@ int m2vc_mux_ts(const uint8_t *es, size_t es_bytes, uint8_t *out, size_t cap, si
         w.pes(hdr, es + a, b - a, (uint64_t)((double)v.size() / rate * 27000000.0));
     }
     return finish(v, out, cap, out_bytes);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// the inverse: transport / program stream -> the video elementary stream (include/m2v_container.h states every rule)
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+const uint64_t kAbsent = ~0ull;
+
+int demux_verdict(m2vc_demux_info *info, int status, uint64_t err, uint64_t need = 0)
+{
+    *info = m2vc_demux_info{};
+    info->status = status;
+    info->err_offset = status == M2VC_E_SYNTAX ? err : 0;
+    info->out_bytes = status == M2VC_E_OVERFLOW ? need : 0;
+    return status;
+}
+
+uint64_t stamp33(const uint8_t *b)
+{
+    return (uint64_t)((b[0] >> 1) & 7) << 30 | (uint64_t)b[1] << 22 | (uint64_t)(b[2] >> 1) << 15 | (uint64_t)b[3] << 7 | (uint64_t)(b[4] >> 1);
+}
+
+// the PES header at h, of which `avail` bytes may be looked at: false = it breaks a rule; head = 9 + PES_header_data_length
+bool pes_header(const uint8_t *h, size_t avail, uint32_t &head, uint64_t &pts, uint64_t &dts)
+{
+    pts = dts = kAbsent;
+    if (avail < 9 || h[0] != 0 || h[1] != 0 || h[2] != 1 || h[3] < 0xE0 || h[3] > 0xEF) return false;
+    if ((h[6] & 0xC0) != 0x80 || (h[6] & 0x30) != 0) return false;
+    const uint32_t hl = h[8], flags = h[7] >> 6;
+    head = 9 + hl;
+    if (head > avail || flags == 1) return false;
+    if (flags >= 2) {
+        if (hl < (flags == 3 ? 10u : 5u) || (uint32_t)(h[9] >> 4) != flags || !(h[9] & 1) || !(h[11] & 1) || !(h[13] & 1)) return false;
+        pts = stamp33(h + 9);
+    }
+    if (flags == 3) {
+        if ((h[14] >> 4) != 1 || !(h[14] & 1) || !(h[16] & 1) || !(h[18] & 1)) return false;
+        dts = stamp33(h + 14);
+    }
+    return true;
+}
+
+inline uint32_t ts_pid(const uint8_t *p) { return (uint32_t)(p[1] & 0x1F) << 8 | p[2]; }
+
+// the section of a PSI packet: pointer_field, table_id, section_syntax_indicator, wholly inside the packet, CRC 0; len = 3 + section_length
+bool psi_section(const uint8_t *p, uint32_t table_id, uint32_t min_length, const uint8_t *&sec, uint32_t &len)
+{
+    uint32_t at = 4;
+    if ((p[3] >> 4 & 3) == 3) {
+        if (p[4] > 182) return false;
+        at = 5 + p[4];
+    }
+    at += 1 + p[at];                                  // pointer_field
+    if (at + 3 > 188) return false;
+    sec = p + at;
+    const uint32_t sl = (uint32_t)(sec[1] & 15) << 8 | sec[2];
+    len = 3 + sl;
+    if (sec[0] != table_id || !(sec[1] & 0x80) || sl < min_length || at + len > 188) return false;
+    return crc32_mpeg(sec, len) == 0;
+}
+
+// the first packet of `pid` that starts a section and has a payload (transport errors ignored), or np
+size_t psi_packet(const uint8_t *src, size_t np, uint32_t pid)
+{
+    for (size_t k = 0; k < np; ++k) {
+        const uint8_t *p = src + 188 * k;
+        if (!(p[1] & 0x80) && (p[1] & 0x40) && (p[3] & 0x10) && ts_pid(p) == pid) return k;
+    }
+    return np;
+}
+
+// PAT -> PMT -> the video PID: M2VC_OK, M2VC_E_NOSTREAM, or M2VC_E_SYNTAX at packet `bad`
+int ts_discover(const uint8_t *src, size_t np, uint32_t &video, size_t &bad)
+{
+    const uint8_t *sec;
+    uint32_t len;
+    size_t k = psi_packet(src, np, 0);
+    if (k == np) return M2VC_E_NOSTREAM;
+    bad = k;
+    if (!psi_section(src + 188 * k, 0, 9, sec, len)) return M2VC_E_SYNTAX;
+    uint32_t program = 0, pmt = 0;
+    for (uint32_t i = 8; i + 4 <= len - 4 && !program; i += 4) {
+        program = (uint32_t)sec[i] << 8 | sec[i + 1];
+        pmt = (uint32_t)(sec[i + 2] & 0x1F) << 8 | sec[i + 3];
+    }
+    if (!program) return M2VC_E_NOSTREAM;
+    k = psi_packet(src, np, pmt);
+    if (k == np) return M2VC_E_NOSTREAM;
+    bad = k;
+    if (!psi_section(src + 188 * k, 2, 13, sec, len) || ((uint32_t)sec[3] << 8 | sec[4]) != program) return M2VC_E_SYNTAX;
+    uint32_t i = 12 + ((uint32_t)(sec[10] & 15) << 8 | sec[11]);
+    if (i > len - 4) return M2VC_E_SYNTAX;
+    for (; i + 5 <= len - 4; i += 5 + ((uint32_t)(sec[i + 3] & 15) << 8 | sec[i + 4]))
+        if (sec[i] == 1 || sec[i] == 2) { video = (uint32_t)(sec[i + 1] & 0x1F) << 8 | sec[i + 2]; return M2VC_OK; }
+    return M2VC_E_NOSTREAM;
+}
+
+struct DemuxOut {
+    uint8_t *out; m2vc_stamp *stamps; size_t stamp_cap;
+    uint64_t bytes = 0; uint32_t pes = 0;
+    void start(uint64_t pts, uint64_t dts, uint64_t src_offset)
+    {
+        if (stamps && pes < stamp_cap) stamps[pes] = m2vc_stamp{bytes, pts, dts, src_offset};
+        ++pes;
+    }
+    void put(const uint8_t *p, size_t n)
+    {
+        if (out && n) memcpy(out + bytes, p, n);
+        bytes += n;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int m2vc_demux_ts(const uint8_t *src, size_t n, int stream, uint8_t *out, size_t cap, m2vc_stamp *stamps, size_t stamp_cap,
+                  m2vc_demux_info *info)
+{
+    if ((!src && n) || !info || stream < -1 || stream > 0x1FFF) return M2VC_E_PARAM;
+    const size_t np = n / 188;
+    uint64_t err = n == 0 || n % 188 ? (uint64_t)188 * np : kAbsent;
+    for (size_t k = 0; k < np; ++k)
+        if (src[188 * k] != 0x47) { err = 188 * k; break; }
+    uint32_t pid = (uint32_t)stream;
+    if (stream < 0) {                                  // (discovery does not look at the sync bytes: the verdict above stands beside it)
+        size_t bad = 0;
+        const int r = ts_discover(src, np, pid, bad);
+        if (r == M2VC_E_SYNTAX) return demux_verdict(info, r, std::min<uint64_t>(err, 188 * bad));
+        if (r != M2VC_OK) return err != kAbsent ? demux_verdict(info, M2VC_E_SYNTAX, err) : demux_verdict(info, r, 0);
+    }
+    m2vc_demux_info I{};
+    // twice: the verdict and the sizes, then the bytes
+    for (int pass = 0; pass < 2; ++pass) {
+        DemuxOut o{pass ? out : nullptr, pass ? stamps : nullptr, stamp_cap};
+        I = m2vc_demux_info{};
+        int last_cc = -1;
+        bool started = false;
+        for (size_t k = 0; k < np; ++k) {
+            const uint8_t *p = src + 188 * k;
+            if ((p[1] & 0x80) || ts_pid(p) != pid) continue;
+            ++I.packets;
+            const uint32_t afc = p[3] >> 4 & 3;
+            uint32_t at = 4;
+            bool ok = !(p[3] >> 6) && afc != 0;
+            if (ok && afc == 2) { ok = p[4] == 183; at = 188; }
+            if (ok && afc == 3) { ok = p[4] <= 182; at = 5 + p[4]; }
+            uint32_t head = 0;
+            uint64_t pts = kAbsent, dts = kAbsent;
+            const bool pusi = p[1] & 0x40;
+            if (ok && pusi) ok = pes_header(p + at, 188 - at, head, pts, dts);
+            if (!ok) return demux_verdict(info, M2VC_E_SYNTAX, std::min<uint64_t>(err, 188 * k));
+            if (afc & 1) {
+                const int cc = p[3] & 15;
+                const bool di = afc == 3 && p[4] > 0 && (p[5] & 0x80);
+                if (last_cc >= 0 && cc != ((last_cc + 1) & 15) && !di) ++I.discontinuities;
+                last_cc = cc;
+            }
+            if (pusi) { started = true; o.start(pts, dts, 188 * k + at); }
+            if (!started) { ++I.skipped; continue; }
+            o.put(p + at + head, 188 - at - head);
+        }
+        if (err != kAbsent) return demux_verdict(info, M2VC_E_SYNTAX, err);
+        if (!o.pes) return demux_verdict(info, M2VC_E_NOSTREAM, 0);
+        if (pass == 0 && out && o.bytes > cap) return demux_verdict(info, M2VC_E_OVERFLOW, 0, o.bytes);
+        I.out_bytes = o.bytes; I.pes_packets = o.pes; I.stream = pid;
+        if (!out && !stamps) break;
+    }
+    *info = I;
+    return M2VC_OK;
+}
+
+int m2vc_demux_ps(const uint8_t *src, size_t n, int stream, uint8_t *out, size_t cap, m2vc_stamp *stamps, size_t stamp_cap,
+                  m2vc_demux_info *info)
+{
+    if ((!src && n) || !info || (stream != -1 && (stream < 0xE0 || stream > 0xEF))) return M2VC_E_PARAM;
+    m2vc_demux_info I{};
+    for (int pass = 0; pass < 2; ++pass) {
+        DemuxOut o{pass ? out : nullptr, pass ? stamps : nullptr, stamp_cap};
+        I = m2vc_demux_info{};
+        int sel = stream;
+        size_t p = 0;
+        while (p < n) {
+            if (n - p < 4 || src[p] != 0 || src[p + 1] != 0 || src[p + 2] != 1) return demux_verdict(info, M2VC_E_SYNTAX, p);
+            const uint32_t c = src[p + 3];
+            if (c == 0xB9) {                             // MPEG_program_end_code: only zeros may follow
+                for (size_t q = p + 4; q < n; ++q)
+                    if (src[q]) return demux_verdict(info, M2VC_E_SYNTAX, q);
+                break;
+            }
+            if (c == 0xBA) {
+                const uint8_t *h = src + p + 4;
+                if (n - p < 14 || (h[0] >> 6) != 1 || !(h[0] & 4) || !(h[2] & 4) || !(h[4] & 4) || !(h[5] & 1) || (h[8] & 3) != 3 ||
+                    n - p < 14u + (h[9] & 7))
+                    return demux_verdict(info, M2VC_E_SYNTAX, p);
+                ++I.packets;
+                p += 14u + (h[9] & 7);
+                continue;
+            }
+            if (c != 0xBB && c < 0xBC) return demux_verdict(info, M2VC_E_SYNTAX, p);
+            if (n - p < 6) return demux_verdict(info, M2VC_E_SYNTAX, p);
+            const size_t L = (size_t)src[p + 4] << 8 | src[p + 5];
+            if (n - p - 6 < L) return demux_verdict(info, M2VC_E_SYNTAX, p);
+            if (sel < 0 && c >= 0xE0 && c <= 0xEF) sel = (int)c;
+            if ((int)c == sel) {
+                uint32_t head;
+                uint64_t pts, dts;
+                if (!pes_header(src + p, 6 + L, head, pts, dts)) return demux_verdict(info, M2VC_E_SYNTAX, p);
+                o.start(pts, dts, p);
+                o.put(src + p + head, 6 + L - head);
+            } else {
+                ++I.skipped;
+            }
+            p += 6 + L;
+        }
+        if (!o.pes) return demux_verdict(info, M2VC_E_NOSTREAM, 0);
+        if (pass == 0 && out && o.bytes > cap) return demux_verdict(info, M2VC_E_OVERFLOW, 0, o.bytes);
+        I.out_bytes = o.bytes; I.pes_packets = o.pes; I.stream = (uint32_t)sel;
+        if (!out && !stamps) break;
+    }
+    *info = I;
+    return M2VC_OK;
 }
 
 }  // extern "C"

@@ -570,6 +570,7 @@ void m2v_destroy(m2v_enc *e)
     seq_release(e);
     mux_release(e);
     dec_release(e);
+    dmx_release(e);
     if (e->ev_gop) (void)hipEventDestroy(e->ev_gop);
     if (e->h_redo) (void)hipHostFree(e->h_redo);
     for (auto p : e->rec_pool) (void)hipFree(p);
@@ -711,6 +712,11 @@ int m2v_set_option(m2v_enc *e, const char *name, long long value)
     if (!strcmp(name, "decode_batch")) {
         if (value < 0 || value > 65536) { e->set_err("m2v_set_option: decode_batch is 0 (the default) .. 65536 pictures"); return M2V_E_PARAM; }
         e->decode_batch = (size_t)value;
+        return M2V_OK;
+    }
+    if (!strcmp(name, "demux_blocks")) {
+        if (value < 0 || value > 4096) { e->set_err("m2v_set_option: demux_blocks is 0 (the default: 4096) .. 4096 workgroups"); return M2V_E_PARAM; }
+        e->demux_blocks = (size_t)value;
         return M2V_OK;
     }
     if (!strcmp(name, "profile")) { e->profile = value != 0; return M2V_OK; }

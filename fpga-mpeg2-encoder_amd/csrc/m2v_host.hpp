@@ -33,6 +33,8 @@
 //   m2v_decode.hip    m2v_decode_device: an elementary stream in HBM back to 4:2:0 frames.  Its kernels touch no device global and nothing of
 //                     m2v_kernels.hpp, so they live in their own unit with their launches (m2v_decode_kernels.hpp holds the arithmetic, for
 //                     the device and the host alike)
+//   m2v_demux.hip     m2v_demux_device: transport / program streams in HBM back to the elementary stream, the inverse of m2v_mux.hip and like it
+//                     a unit of its own (m2v_demux_kernels.hpp holds the arithmetic, for the device and the host alike)
 //   m2v_scale.hip     m2v_set_source_size: frames of another size resampled to the picture size in front of the conversions - the setting,
 //                     the tap tables (m2v_scale_taps), k_scale and its launch (m2v_scale_kernels.hpp holds the arithmetic, for the device
 //                     and the host alike; no device global, nothing of m2v_kernels.hpp)
@@ -408,6 +410,14 @@ struct m2v_enc {
     size_t decode_batch = 0;              // option "decode_batch": pictures per chunk (0: as many as keep the levels within 256 MiB, 256 at most)
     m2v_decode_stat dec_rec{};            // the last call's record (m2v_decode_report)
 
+    // the demultiplexer (m2v_demux.hip): the containers' state, the tiles' sums, the tables of payload runs - no recording references
+    // them - allocated by the first m2v_demux_device, and the pinned memory the state goes up and the records arrive in
+    DevBuf<uint8_t> d_dmx_st, d_dmx_tiles, d_dmx_seg;
+    uint8_t *h_dmx = nullptr;
+    size_t h_dmx_cap = 0;
+    Records<m2v_demux_stat> dmx_q;        // the last demux's records nobody has popped yet
+    size_t demux_blocks = 0;              // option "demux_blocks": the most workgroups of one launch (0: 4096); what is left over goes round the kernels' loops
+
     // debug bookkeeping of the last resident encode
     size_t dbg_frames = 0;
     std::vector<int> dbg_rec_slot;
@@ -621,6 +631,8 @@ void mux_release(m2v_enc *e);
 
 // ---- m2v_decode.hip: m2v_decode_device ----
 void dec_release(m2v_enc *e);
+// ---- m2v_demux.hip ----
+void dmx_release(m2v_enc *e);
 
 // ---- m2v_launch.hip: everything that touches device code ----
 // The constant tables live in each device's copy of the code object: uploaded once per device, whichever thread creates the first

@@ -6,8 +6,13 @@
 //          [-fps N/D] [-aspect 1:1|4:3|16:9|2.21:1] [-bitrate B] [-vbv K] [-colour bt601|bt709|P,T,M] [-repeat-headers]
 //          [-scale SWxSH [-filter triangle|area]]
 //          in.yuv W H out.m2v  [in2.yuv W2 H2 out2.m2v ...]
-//   m2v_tb -decode in.m2v out.yuv [-reconfmt i420|yv12|nv12|nv21] [-mode iso|module] [-d device]
+//   m2v_tb -decode in.m2v out.yuv [-reconfmt i420|yv12|nv12|nv21] [-mode iso|module] [-container ts|ps [-pid N]] [-d device]
+//   m2v_tb -demux ts|ps in.ts out.m2v [-pid N] [-d device]
 //
+// -demux: the video elementary stream of a transport or program stream, demultiplexed on the device (m2v_demux_device), into out.m2v, with
+// one line about the container; -pid N: the PID / stream_id to take (default: found in the container).  -decode ... -container ts|ps:
+// in.m2v is such a container; it is demultiplexed on the device and the stream decoded from where it lands, without a trip to the host.
+// A container the demultiplexer refuses ends with its status and the offset of the packet or unit in error, exit status 1.
 // -decode: the other way - the elementary stream of in.m2v decoded on the device (m2v_decode_device: a probe for the size, then the
 // decode) into 4:2:0 frames of the header's size in -reconfmt (default i420), frame behind frame in out.yuv.  -mode iso (default): the
 // standard's reconstruction, for streams coded with -conformant; -mode module: the module's own loop, for every other stream of this
@@ -66,10 +71,82 @@
 #include "../../include/m2v_container.h"
 #include "../../include/m2v_mi355x.h"
 
+static bool read_file(const char *path, std::vector<uint8_t> &bytes)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) { perror(path); return false; }
+    uint8_t chunk[65536];
+    for (size_t n; (n = fread(chunk, 1, sizeof chunk, f)) > 0;) bytes.insert(bytes.end(), chunk, chunk + n);
+    fclose(f);
+    return true;
+}
+
+// the container of n bytes at d_src through m2v_demux_device into a new allocation *d_es, zeroed first so that the stream can be handed
+// on with the zero padding to a whole 32-byte word that a muxer drops behind sequence_end_code: 0, or 1 with the reason on stderr
+static int demux_to_device(m2v_enc *e, int kind, int pid, const void *d_src, size_t n, const char *name, void **d_es, m2v_demux_stat *r)
+{
+    const uint64_t off = 0, bytes = n;
+    const size_t cap = m2v_demux_bound(&bytes, 1);
+    if (hipMalloc(d_es, cap + 32) != hipSuccess || hipMemset(*d_es, 0, cap + 32) != hipSuccess) { fprintf(stderr, "m2v_tb: no device memory for the stream\n"); return 1; }
+    if (m2v_demux_device(e, kind, d_src, &off, &bytes, 1, pid, *d_es, cap, nullptr, 0, nullptr) != M2V_OK || m2v_demux_report(e, r, 1) != 1) {
+        fprintf(stderr, "m2v_demux_device: %s\n", m2v_last_error(e));
+        return 1;
+    }
+    if (r->status != M2V_DEMUX_OK) {
+        fprintf(stderr, "%s: not demultiplexed: status %d%s, the packet or unit at byte %llu\n", name, (int)r->status,
+                r->status == M2V_DEMUX_NOSTREAM ? " (no video stream)" : "", (unsigned long long)r->err_offset);
+        return 1;
+    }
+    return 0;
+}
+
+static int container_kind(const char *v) { return !strcmp(v, "ts") ? M2V_MUX_TS : !strcmp(v, "ps") ? M2V_MUX_PS : 0; }
+
+static int demux_main(int argc, char **argv)
+{
+    const int kind = container_kind(argv[2]);
+    const char *in = argv[3], *out = argv[4];
+    int pid = -1, dev = 0;
+    bool bad = !kind;
+    for (int i = 5; i < argc; i += 2) {
+        if (i + 1 < argc && !strcmp(argv[i], "-pid")) pid = (int)strtol(argv[i + 1], nullptr, 0);
+        else if (i + 1 < argc && !strcmp(argv[i], "-d")) dev = atoi(argv[i + 1]);
+        else bad = true;
+    }
+    if (bad) { fprintf(stderr, "m2v_tb -demux ts|ps in out.m2v [-pid N] [-d device]\n"); return 2; }
+    std::vector<uint8_t> box;
+    if (!read_file(in, box)) return 1;
+    int err = 0;
+    m2v_enc *e = m2v_create(7, 7, 3, 2, dev, &err);
+    if (!e) { fprintf(stderr, "m2v_create: %s\n", m2v_last_error(nullptr)); return 1; }
+    void *d_src = nullptr, *d_es = nullptr;
+    m2v_demux_stat r;
+    int rc = 1;
+    if (hipMalloc(&d_src, box.size() + 1) != hipSuccess || hipMemcpy(d_src, box.data(), box.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        fprintf(stderr, "m2v_tb: no device memory for the container\n");
+    } else if (demux_to_device(e, kind, pid, d_src, box.size(), in, &d_es, &r) == 0) {
+        std::vector<uint8_t> es((size_t)r.out_bytes);
+        FILE *o = fopen(out, "wb");
+        if (hipMemcpy(es.data(), (const uint8_t *)d_es + r.out_offset, es.size(), hipMemcpyDeviceToHost) != hipSuccess || !o || fwrite(es.data(), 1, es.size(), o) != es.size()) {
+            fprintf(stderr, "m2v_tb: cannot write %s\n", out);
+        } else {
+            printf("%s: stream 0x%x, %u PES packets in %u %s, %u skipped, %u discontinuities -> %s (%llu bytes)\n", in, r.stream, r.pes_packets, r.packets,
+                   kind == M2V_MUX_TS ? "packets" : "packs", r.skipped, r.discontinuities, out, (unsigned long long)r.out_bytes);
+            rc = 0;
+        }
+        if (o) fclose(o);
+    }
+    if (d_src) (void)hipFree(d_src);
+    if (d_es) (void)hipFree(d_es);
+    m2v_destroy(e);
+    return rc;
+}
+
 static int decode_main(int argc, char **argv)
 {
     const char *in = argv[2], *out = argv[3];
-    int layout = M2V_420_I420, mode = M2V_DEC_ISO, dev = 0;
+    int layout = M2V_420_I420, mode = M2V_DEC_ISO, dev = 0, container = 0, pid = -1;
+    bool bad = false;
     for (int i = 4; i < argc; ++i) {
         const char *v = i + 1 < argc ? argv[i + 1] : "";
         if (!strcmp(argv[i], "-reconfmt")) {
@@ -82,30 +159,47 @@ static int decode_main(int argc, char **argv)
         } else if (!strcmp(argv[i], "-d")) {
             dev = atoi(v);
             ++i;
+        } else if (!strcmp(argv[i], "-container")) {
+            container = container_kind(v);
+            bad = bad || !container;
+            ++i;
+        } else if (!strcmp(argv[i], "-pid")) {
+            pid = (int)strtol(v, nullptr, 0);
+            ++i;
         } else {
-            fprintf(stderr, "m2v_tb -decode in.m2v out.yuv [-reconfmt i420|yv12|nv12|nv21] [-mode iso|module] [-d device]\n");
-            return 2;
+            bad = true;
         }
     }
-    FILE *f = fopen(in, "rb");
-    if (!f) { perror(in); return 1; }
+    if (bad || (pid >= 0 && !container)) {
+        fprintf(stderr, "m2v_tb -decode in.m2v out.yuv [-reconfmt i420|yv12|nv12|nv21] [-mode iso|module] [-container ts|ps [-pid N]] [-d device]\n");
+        return 2;
+    }
     std::vector<uint8_t> es;
-    uint8_t chunk[65536];
-    for (size_t n; (n = fread(chunk, 1, sizeof chunk, f)) > 0;) es.insert(es.end(), chunk, chunk + n);
-    fclose(f);
+    if (!read_file(in, es)) return 1;
     int err = 0;
     m2v_enc *e = m2v_create(7, 7, 3, 2, dev, &err);
     if (!e) { fprintf(stderr, "m2v_create: %s\n", m2v_last_error(nullptr)); return 1; }
-    void *d_es = nullptr, *d_out = nullptr;
+    void *d_in = nullptr, *d_box = nullptr, *d_out = nullptr;
+    const void *d_es = nullptr;
+    size_t es_bytes = es.size();
     m2v_decode_stat r;
+    m2v_demux_stat dr;
     int rc = 1;
-    if (hipMalloc(&d_es, es.size() + 1) != hipSuccess || hipMemcpy(d_es, es.data(), es.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    if (hipMalloc(&d_in, es.size() + 1) != hipSuccess || hipMemcpy(d_in, es.data(), es.size(), hipMemcpyHostToDevice) != hipSuccess) {
         fprintf(stderr, "m2v_tb: no device memory for the stream\n");
-    } else if (m2v_decode_device(e, d_es, es.size(), nullptr, 0, layout, mode, nullptr) != M2V_OK || m2v_decode_report(e, &r) != M2V_OK) {
+    } else if (!container) {
+        d_es = d_in;
+    } else if (demux_to_device(e, container, pid, d_in, es.size(), in, &d_box, &dr) == 0) {
+        d_es = (const uint8_t *)d_box + dr.out_offset;      // the stream stays where the demultiplexer left it
+        es_bytes = ((size_t)dr.out_bytes + 31) / 32 * 32;   // (the decoder's definition wants whole words: the zeros are there)
+    }
+    if (!d_es) {
+        // (said)
+    } else if (m2v_decode_device(e, d_es, es_bytes, nullptr, 0, layout, mode, nullptr) != M2V_OK || m2v_decode_report(e, &r) != M2V_OK) {
         fprintf(stderr, "m2v_decode_device: %s\n", m2v_last_error(e));
     } else if (r.status == M2V_DEC_OK && hipMalloc(&d_out, (size_t)r.out_bytes + 1) != hipSuccess) {
         fprintf(stderr, "m2v_tb: no device memory for %llu bytes of frames\n", (unsigned long long)r.out_bytes);
-    } else if (r.status == M2V_DEC_OK && (m2v_decode_device(e, d_es, es.size(), d_out, (size_t)r.out_bytes, layout, mode, nullptr) != M2V_OK ||
+    } else if (r.status == M2V_DEC_OK && (m2v_decode_device(e, d_es, es_bytes, d_out, (size_t)r.out_bytes, layout, mode, nullptr) != M2V_OK ||
                                           m2v_decode_report(e, &r) != M2V_OK)) {
         fprintf(stderr, "m2v_decode_device: %s\n", m2v_last_error(e));
     } else if (r.status != M2V_DEC_OK) {
@@ -121,7 +215,8 @@ static int decode_main(int argc, char **argv)
         }
         if (o) fclose(o);
     }
-    if (d_es) (void)hipFree(d_es);
+    if (d_in) (void)hipFree(d_in);
+    if (d_box) (void)hipFree(d_box);
     if (d_out) (void)hipFree(d_out);
     m2v_destroy(e);
     return rc;
@@ -130,6 +225,7 @@ static int decode_main(int argc, char **argv)
 int main(int argc, char **argv)
 {
     if (argc >= 4 && !strcmp(argv[1], "-decode")) return decode_main(argc, argv);
+    if (argc >= 5 && !strcmp(argv[1], "-demux")) return demux_main(argc, argv);
     int XL = 7, YL = 6, VL = 3, Q = 2, pf = 23, dev = 0, bubbles = 0, conformant = 0, want_ps = 0, want_ts = 0, layout420 = -1, layouts = 0, rgb = -1, matrix = M2V_RGB_BT601,
         bad_matrix = 0, pad = 0, truesize = 0, stats = 0, reconfmt = M2V_420_I420, devmux = 0;
     const char *recon = nullptr;

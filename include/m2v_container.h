@@ -76,6 +76,63 @@ int m2vc_mux_ps(const uint8_t *es, size_t es_bytes, uint8_t *out, size_t cap, si
  */
 int m2vc_mux_ts(const uint8_t *es, size_t es_bytes, uint8_t *out, size_t cap, size_t *out_bytes);
 
+/*
+ * The inverse: one video elementary stream out of a transport or program stream - ours or an ordinary multiplexer's.  These two
+ * serial functions are the definition of what m2v_demux_device (include/m2v_mi355x.h) computes.  They never read outside
+ * [src, src + n) whatever the bytes are, and the payload is not assumed to be video: it may hold pack headers, PES headers, start
+ * codes and 0x47 at any place.
+ *
+ * out == NULL asks for the size (info->out_bytes); otherwise the elementary bytes go to out, M2VC_E_OVERFLOW if cap is too small
+ * (nothing is written; info->out_bytes = the need).  One m2vc_stamp per PES packet of the stream, in container order: at most
+ * stamp_cap are written (stamps may be NULL), info->pes_packets says how many there were.  The return value is info->status:
+ *   M2VC_OK
+ *   M2VC_E_SYNTAX    info->err_offset = the offset of the EARLIEST packet / unit that breaks a rule below
+ *   M2VC_E_NOSTREAM  no PAT / PMT / video entry, or no PES packet of the stream starts anywhere
+ *   M2VC_E_OVERFLOW
+ * (M2VC_E_PARAM for a NULL src / info or a `stream` out of range: info is not written.)  With a status other than OK every counter
+ * of info is 0 (out_bytes too, except for OVERFLOW), and err_offset is 0 unless the status is SYNTAX.
+ *
+ * Transport stream (188-byte packets; `stream` = the video PID 0 .. 0x1FFF, or -1: found through PAT and PMT).
+ *   n must be a positive multiple of 188 (else SYNTAX at 188 * (n / 188)) and byte 0 of every packet 0x47 (SYNTAX at that packet).  A
+ *   packet with transport_error_indicator set is ignored whatever its PID.  Discovery: the PAT is the first packet with PID 0,
+ *   payload_unit_start_indicator and a payload - pointer_field, then a section with table_id 0, section_syntax_indicator 1, wholly
+ *   inside that packet, CRC-32/MPEG 0 (else SYNTAX at the packet); its first entry with program_number != 0 names the PMT PID (none:
+ *   NOSTREAM); the PMT is the first such packet of that PID (table_id 2, the same checks, the same program_number); the first entry of
+ *   its stream loop with stream_type 1 or 2 names the video PID (none: NOSTREAM), which then holds for every packet of the input.
+ *   Discovery does not look at the sync bytes (they have their verdict anyway), and NOSTREAM is answered only where no rule is broken:
+ *   a broken rule anywhere is SYNTAX at the earliest one.
+ *   Packets of other PIDs are skipped and, beyond the sync byte, not validated.  A video packet: transport_scrambling_control != 0,
+ *   adaptation_field_control 0, control 2 with adaptation_field_length != 183 and control 3 with a length > 182 are SYNTAX; of the
+ *   adaptation field only discontinuity_indicator is read.  With payload_unit_start_indicator the payload starts with a PES header of
+ *   9 + hl bytes inside this packet (SYNTAX otherwise; see below) and the elementary bytes are the rest; without it the whole payload
+ *   is elementary bytes - except in front of the first packet with the indicator: those video packets are dropped and counted in
+ *   info->skipped (a stream may be joined in mid-packet).  PES_packet_length is not interpreted: a PES packet runs to the next one.
+ *   Continuity is looked at among the video packets that carry a payload, in order: a counter that is not the previous one + 1 mod 16
+ *   is counted in info->discontinuities unless that packet's discontinuity_indicator is set.  Nothing is dropped for it, and DUPLICATE
+ *   PACKETS ARE NOT REMOVED (a repeated packet's payload appears twice, and counts as a discontinuity).  info->packets = the video
+ *   packets (the skipped ones included), info->stream = the PID.
+ *
+ * Program stream: a serial chain from p = 0 (`stream` = the stream_id 0xE0 .. 0xEF, or -1: that of the chain's first video packet).
+ *   p == n ends it.  Otherwise src[p .. p+4) must be 00 00 01 c (else SYNTAX at p).  c == B9 ends the chain: every byte behind it must be
+ *   zero (SYNTAX at the first that is not).  c == BA: an MPEG-2 pack header of 14 bytes ('01' and the five marker bits, marker bits
+ *   '11' behind the rate; an MPEG-1 one is SYNTAX) and pack_stuffing_length 0 .. 7 bytes, all inside n.  c == BB or c >= BC: a unit
+ *   with a 16-bit length L at p + 4, p + 6 + L <= n (else SYNTAX at p); a packet of the selected stream has its PES header parsed
+ *   (L >= 3, hl <= L - 3), its elementary bytes are src[p + 9 + hl .. p + 6 + L); every other id is skipped by its length (counted in
+ *   info->skipped).  Any other c is SYNTAX at p.  No packet of the selected stream in the whole chain: NOSTREAM.  info->packets = the
+ *   pack headers, info->stream = the stream_id, info->discontinuities = 0.
+ *
+ * PES header (both kinds): 00 00 01, stream_id E0 .. EF, '10', PES_scrambling_control 0, hl = PES_header_data_length.
+ *   PTS_DTS_flags 2: hl >= 5, prefix '0010' and three marker bits; 3: hl >= 10, prefixes '0011' / '0001'; 0: neither; 1 is SYNTAX.  The
+ *   rest of the header is skipped by hl.
+ */
+#define M2VC_E_NOSTREAM (-4)
+typedef struct { uint64_t es_offset, pts, dts, src_offset; } m2vc_stamp;      /* 32 bytes; pts / dts = ~0 when absent; src_offset = the PES header's place */
+typedef struct { uint64_t out_bytes, err_offset; uint32_t pes_packets, packets, discontinuities, skipped, stream; int32_t status; } m2vc_demux_info;
+int m2vc_demux_ts(const uint8_t *src, size_t n, int stream, uint8_t *out, size_t cap, m2vc_stamp *stamps, size_t stamp_cap,
+                  m2vc_demux_info *info);
+int m2vc_demux_ps(const uint8_t *src, size_t n, int stream, uint8_t *out, size_t cap, m2vc_stamp *stamps, size_t stamp_cap,
+                  m2vc_demux_info *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -958,6 +958,41 @@ int m2v_decode_device(m2v_enc *e, const void *d_es, size_t es_bytes, void *d_dst
 int m2v_decode_report(m2v_enc *e, m2v_decode_stat *out);
 int m2v_decode_scan_tile(void);
 
+/*
+ * Demux on the device: the inverse of m2v_mux_device.  nstreams (1 .. 65535) transport (kind M2V_MUX_TS) or program (M2V_MUX_PS) streams
+ * in device memory - container i is the src_bytes[i] bytes at d_src + src_off[i], at ANY byte address - back to the video elementary
+ * stream of each, which m2v_decode_device takes.  `stream`: the PID (0 .. 0x1FFF) / stream_id (0xE0 .. 0xEF) to take in every container,
+ * or -1: found in each (PAT and PMT; the first video packet of the chain).  The bytes, the stamps and every field of a record are what
+ * m2vc_demux_ts / m2vc_demux_ps (include/m2v_container.h: the specification, with every rule) answer for that container, with the
+ * stream's place added.
+ *
+ * Stream i lands in d_dst (any byte address; at most cap bytes are used), one stream behind the other, each on a 32-byte boundary of the
+ * buffer: [out_offset, out_offset + out_bytes) of its record; bytes outside every such range are not written.  A container whose status
+ * is not M2V_DEMUX_OK has out_bytes 0, takes no room and no stamps, and its counters are 0; M2V_DEMUX_OVERFLOW: the stream did not fit
+ * into cap behind those before it (m2v_demux_bound - the sum of the sizes, each rounded up to 32 - is always enough).  d_stamps (on an
+ * 8-byte boundary; NULL with stamp_cap 0) receives one m2v_demux_stamp per PES packet, the containers' stamps one behind the other in
+ * container order: stream i's begin at the sum of the pes_packets before it; those at or past stamp_cap are left out.
+ *
+ * The call blocks until the records are complete (one wait, as m2v_mux_device); m2v_demux_report pops them, oldest first (out NULL:
+ * how many wait); they are dropped at the next m2v_demux_device.  M2V_E_STATE while a sequence is in progress or a resident call is in
+ * flight; M2V_E_PARAM for an unknown kind, a `stream` out of range, no or more than 65535 containers.  Work buffers (16 bytes per
+ * transport packet; 16 bytes per 9 bytes of a program stream) are allocated by the first call, by size, and freed with the handle.
+ * m2v_demux_scan_tile: the bytes of a transport stream after which the kernels hand over to another workgroup.
+ * Option "demux_blocks" (m2v_set_option): the most workgroups one launch of the demultiplexer's kernels has, 1 .. 4096; 0 (the default):
+ * 4096.  They are shared out among a call's containers, and what a launch does not cover at once goes round the kernels' loops: the
+ * result does not depend on it.  A caller that demultiplexes beside other work on the device can keep the footprint small with it; the
+ * tests use it to send small containers round every loop.
+ */
+enum { M2V_DEMUX_OK = 0, M2V_DEMUX_SYNTAX = -2, M2V_DEMUX_OVERFLOW = -3, M2V_DEMUX_NOSTREAM = -4 };
+typedef struct { uint64_t src_offset, src_bytes, out_offset, out_bytes, err_offset;
+                 uint32_t pes_packets, packets, discontinuities, skipped, stream; int32_t status; } m2v_demux_stat;      /* 64 bytes */
+typedef struct { uint64_t es_offset, pts, dts, src_offset; } m2v_demux_stamp;      /* 32 bytes; pts / dts = ~0 when absent; es_offset within the stream */
+size_t m2v_demux_bound(const uint64_t *src_bytes, size_t nstreams);
+int m2v_demux_device(m2v_enc *e, int kind, const void *d_src, const uint64_t *src_off, const uint64_t *src_bytes, size_t nstreams, int stream,
+                     void *d_dst, size_t cap, void *d_stamps, size_t stamp_cap, void *hip_stream);
+int m2v_demux_report(m2v_enc *e, m2v_demux_stat *out, size_t max);
+int m2v_demux_scan_tile(void);
+
 /* Per-kernel statistics of the last m2v_encode_resident call with "profile" = 1.
  * kernel: 0 = macroblock kernel on P frames, 1 = macroblock kernel on I frames,
  * 2 = strip mode's final assembly (k_strip_layout + k_strip_assemble), 3 = slice assembly (k_assemble), 4 = scans,
