@@ -50,6 +50,7 @@ EXPORTS = [
     "m2v_mux_bound", "m2v_set_mux_out", "m2v_mux_report", "m2v_mux_device", "m2v_mux_scan_tile",
     "m2v_set_source_size", "m2v_scale_taps",
     "m2v_demux_bound", "m2v_demux_device", "m2v_demux_report", "m2v_demux_scan_tile",
+    "m2v_decode_streams_device", "m2v_decode_streams_report",
 ]
 
 # the 4:2:0 entry points (kept apart: tests/test_abi.py matches EXPORTS against names of letters and underscores only)
@@ -126,6 +127,8 @@ MUX_OK, MUX_SYNTAX, MUX_OVERFLOW = 0, -2, -3
 DECODE_STAT_DTYPE = np.dtype([("es_bytes", "<u8"), ("out_bytes", "<u8"), ("frame_bytes", "<u8"), ("err_offset", "<u8"), ("pictures", "<u4"),
                               ("gops", "<u4"), ("width", "<u4"), ("height", "<u4"), ("repeated_headers", "<u4"), ("chains", "<u4"),
                               ("status", "<i4"), ("reserved", "<u4", (3,))])
+# m2v_decode_stream_stat: one stream's record of m2v_decode_streams_device, 88 bytes (Mpeg2Encoder.decode_streams_report)
+DECODE_STREAM_STAT_DTYPE = np.dtype([("es_offset", "<u8"), ("out_offset", "<u8"), ("rec", DECODE_STAT_DTYPE)])
 DEC_MODES = {"iso": 0, "module": 1}                              # M2V_DEC_*
 DEC_OK, DEC_SYNTAX, DEC_OVERFLOW = 0, -2, -3
 DEC_STATUS = {0: "M2V_DEC_OK", -2: "M2V_DEC_SYNTAX", -3: "M2V_DEC_OVERFLOW"}
@@ -156,6 +159,15 @@ def demux_bound(sizes):
 def decode_scan_tile():
     """m2v_decode_scan_tile: the byte span after which the device decoder's start-code scan hands over to another workgroup"""
     return int(lib().m2v_decode_scan_tile())
+
+
+def frames_of_stream(frames, rec):
+    """the [pictures, frame_bytes] view of one stream's frames in what decode_streams returned; rec: its record.  Empty where the
+    stream's status is not DEC_OK (out_bytes 0)"""
+    r = rec["rec"]
+    n, fb = (int(r["pictures"]), int(r["frame_bytes"])) if int(r["out_bytes"]) else (0, int(r["frame_bytes"]))
+    at = int(rec["out_offset"])
+    return frames[at:at + n * fb].reshape(n, fb)
 
 
 def _mux_kind(kind):
@@ -431,6 +443,8 @@ def lib(debug=False):
             L.m2v_decode_device.argtypes = [vp, vp, sz, vp, sz, ci, ci, vp]
             L.m2v_decode_report.argtypes = [vp, vp]
             L.m2v_decode_scan_tile.argtypes = []
+            L.m2v_decode_streams_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, ci, ci, vp]
+            L.m2v_decode_streams_report.argtypes = [vp, vp, sz]
             L.m2v_scale_taps.argtypes = [ci, ci, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_uint16)]
         except AttributeError:
             # an OLDER build handed in through M2V_LIB for a same-box A/B (tools/ab.sh) may lack the newer entry points; the library of
@@ -948,6 +962,63 @@ class Mpeg2Encoder:
         r = call(out.data_ptr() or None, out.numel()) if out.numel() else call(None, 0)
         n, fb = int(r["pictures"]), int(r["frame_bytes"])
         return out.reshape(-1)[:n * fb].reshape(n, fb), r
+
+    def decode_streams_report(self, max_records=None):
+        """Pops the waiting records of m2v_decode_streams_report, oldest first, at most max_records of them: a numpy structured array
+        of DECODE_STREAM_STAT_DTYPE - one per stream of the last decode_streams."""
+        return self._pop("m2v_decode_streams_report", DECODE_STREAM_STAT_DTYPE, max_records)
+
+    def decode_streams(self, es, segments, layout="i420", mode="iso", out=None, container=None, stream=None):
+        """m2v_decode_streams_device: the elementary streams at the (offset, bytes) pairs of `segments` in the one-dimensional uint8
+        device tensor `es` - at any byte alignment, of any picture sizes - decoded on the device in one call.  Returns (frames, records):
+        a one-dimensional uint8 tensor on es's device and a structured array of DECODE_STREAM_STAT_DTYPE, one record per stream;
+        frames_of_stream(frames, records[b]) is stream b's [pictures, frame_bytes] view.  A stream that is refused does NOT raise: its
+        record says so (rec.status, rec.err_offset relative to the stream), and the others are decoded.  out: a contiguous uint8
+        tensor to write into (all of it is the capacity; a stream whose room does not lie inside it is DEC_OVERFLOW); None: the call
+        probes the streams first and allocates.  ValueError for bad arguments.
+
+        container = "ts" or "ps": `es` and `segments` are containers; they go through demux_device (`stream` as there) in one call into
+        a zeroed scratch tensor, and every stream is handed on with the zero padding to a whole 32-byte word, as decode_device(container=)
+        does.  A container the demultiplexer refused comes back as DEC_SYNTAX with pictures 0."""
+        import torch
+        if not isinstance(es, torch.Tensor) or es.dtype != torch.uint8 or es.dim() != 1 or not es.is_cuda or es.device.index != self.device:
+            raise ValueError("decode_streams: a one-dimensional uint8 tensor on the handle's device is required")
+        if es.stride(0) != 1 and es.numel() > 1:
+            raise ValueError("decode_streams: the tensor must be contiguous")
+        try:
+            seg = [(int(a), int(b)) for a, b in segments]
+        except (TypeError, ValueError):
+            raise ValueError("decode_streams: segments are (offset, bytes) pairs")
+        if not 1 <= len(seg) <= 65535 or any(a < 0 or b < 0 or a + b > es.numel() for a, b in seg):
+            raise ValueError("decode_streams: 1 .. 65535 segments inside the tensor are required")
+        if container is not None:
+            scratch = torch.zeros(demux_bound([b for _, b in seg]) + 32, dtype=torch.uint8, device=es.device)
+            _, r = self.demux_device(es, container, segments=seg, stream=stream, out=scratch)
+            es = scratch
+            seg = [(int(q["out_offset"]), (int(q["out_bytes"]) + 31) // 32 * 32) if q["status"] == DEMUX_OK else (0, 0) for q in r]
+        elif stream is not None:
+            raise ValueError("decode_streams: stream needs a container")
+        if mode not in DEC_MODES and not isinstance(mode, int):
+            raise ValueError("decode_streams: mode is one of %s" % ", ".join(DEC_MODES))
+        if layout not in LAYOUTS_420 and not isinstance(layout, int):
+            raise ValueError("decode_streams: layout is one of %s" % ", ".join(LAYOUTS_420))
+        code = _layout420(layout)
+        m = DEC_MODES[mode] if isinstance(mode, str) else int(mode)
+        off = (ctypes.c_uint64 * len(seg))(*[a for a, _ in seg])
+        nb = (ctypes.c_uint64 * len(seg))(*[b for _, b in seg])
+        hip_stream = torch.cuda.current_stream(es.device).cuda_stream
+
+        def call(ptr, cap):
+            self._chk(self._L.m2v_decode_streams_device(self._h, es.data_ptr() or None, off, nb, len(seg), ptr, cap, code, m, hip_stream),
+                      "m2v_decode_streams_device")
+            return self.decode_streams_report()
+        if out is None:
+            r = call(None, 0)
+            out = torch.empty(int((r["out_offset"] + r["rec"]["out_bytes"]).max()), dtype=torch.uint8, device=es.device)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != es.device or not out.is_contiguous():
+            raise ValueError("decode_streams: out must be a contiguous uint8 tensor on the streams' device")
+        r = call(out.data_ptr() or None, out.numel()) if out.numel() else call(None, 0)
+        return out.reshape(-1), r
 
     def set_stream_desc(self, desc):
         """m2v_set_stream_desc: what every sequence started from now on says about itself in its sequence headers and time codes - a

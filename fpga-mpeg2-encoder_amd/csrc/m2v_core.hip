@@ -570,6 +570,7 @@ void m2v_destroy(m2v_enc *e)
     seq_release(e);
     mux_release(e);
     dec_release(e);
+    ds_release(e);
     dmx_release(e);
     if (e->ev_gop) (void)hipEventDestroy(e->ev_gop);
     if (e->h_redo) (void)hipHostFree(e->h_redo);

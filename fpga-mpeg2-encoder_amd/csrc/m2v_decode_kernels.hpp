@@ -679,5 +679,39 @@ M2V_HD inline uint8_t pic_sample(const uint8_t *pic, uint32_t W, uint32_t H, con
     return pic[(size_t)W * H + (size_t)(o.plane - 1u) * (W / 2u) * (H / 2u) + (size_t)o.y * (W / 2u) + o.x];
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// several streams per call (m2v_decode_streams_device): a chunk is a run of whole pictures in batch order, and its table holds one
+// entry per picture - everything a slice, a macroblock or an output byte needs of the stream its picture belongs to (the sizes differ
+// from stream to stream).  plan_streams (m2v_decode_streams.hpp) fills the tables
+// ---------------------------------------------------------------------------------------------------------------------------
+struct ChunkPic {
+    uint64_t out_off, fb;                                    // the frame's first byte in the output, and its bytes
+    uint64_t buf_off, ref_off;                               // the picture's planar slot in the chunk's buffer; the slot of the picture in front of it in ITS stream (0: the carried one)
+    uint64_t mb_base;                                        // its first macroblock in the chunk's records
+    uint32_t stream, pic, slice0, type, mbw, mbh, w, h;      // slice0: its first slice among the chunk's slices
+};
+
+// the picture slice g of a chunk belongs to: the last entry whose slice0 is not behind g (every picture has a slice: slice0 grows)
+M2V_HD inline uint32_t chunk_slice_pic(const ChunkPic *t, uint32_t n, uint32_t g)
+{
+    uint32_t a = 0, b = n;
+    while (b - a > 1u) { const uint32_t m = (a + b) / 2u; if (t[m].slice0 <= g) a = m; else b = m; }
+    return a;
+}
+
+// which picture, byte of its frame and sample output byte o is; o lies inside the chunk's range (the frames of a chunk follow each
+// other without a gap: out_off grows by fb)
+struct OutByte { uint32_t pic, q; OutAt at; };
+
+M2V_HD inline OutByte streams_out_locate(const ChunkPic *t, uint32_t n, uint64_t o, int layout)
+{
+    uint32_t a = 0, b = n;
+    while (b - a > 1u) { const uint32_t m = (a + b) / 2u; if (t[m].out_off <= o) a = m; else b = m; }
+    OutByte r;
+    r.pic = a; r.q = (uint32_t)(o - t[a].out_off);
+    r.at = out_locate(r.q, t[a].w, t[a].h, layout);
+    return r;
+}
+
 }  // namespace dec
 }  // namespace m2v

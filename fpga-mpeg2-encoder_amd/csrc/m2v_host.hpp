@@ -33,6 +33,8 @@
 //   m2v_decode.hip    m2v_decode_device: an elementary stream in HBM back to 4:2:0 frames.  Its kernels touch no device global and nothing of
 //                     m2v_kernels.hpp, so they live in their own unit with their launches (m2v_decode_kernels.hpp holds the arithmetic, for
 //                     the device and the host alike)
+//   m2v_decode_streams.hip   m2v_decode_streams_device: a batch of elementary streams of any sizes in one call - the same arithmetic over a
+//                     table of streams, in kernels of its own (m2v_decode_streams.hpp lays the batch out, for the host build too)
 //   m2v_demux.hip     m2v_demux_device: transport / program streams in HBM back to the elementary stream, the inverse of m2v_mux.hip and like it
 //                     a unit of its own (m2v_demux_kernels.hpp holds the arithmetic, for the device and the host alike)
 //   m2v_scale.hip     m2v_set_source_size: frames of another size resampled to the picture size in front of the conversions - the setting,
@@ -409,6 +411,12 @@ struct m2v_enc {
     size_t h_dec_cap = 0;
     size_t decode_batch = 0;              // option "decode_batch": pictures per chunk (0: as many as keep the levels within 256 MiB, 256 at most)
     m2v_decode_stat dec_rec{};            // the last call's record (m2v_decode_report)
+    // several streams per call (m2v_decode_streams.hip): the work buffers above serve it too; its own are the streams' table, the
+    // chunks' tables, and the pinned memory for both and for the records - allocated by the first m2v_decode_streams_device
+    DevBuf<uint8_t> d_ds_in, d_ds_tab;
+    uint8_t *h_ds = nullptr, *h_ds_tab = nullptr;
+    size_t h_ds_cap = 0, h_ds_tab_cap = 0;
+    Records<m2v_decode_stream_stat> ds_q; // the last call's records nobody has popped yet
 
     // the demultiplexer (m2v_demux.hip): the containers' state, the tiles' sums, the tables of payload runs - no recording references
     // them - allocated by the first m2v_demux_device, and the pinned memory the state goes up and the records arrive in
@@ -631,6 +639,8 @@ void mux_release(m2v_enc *e);
 
 // ---- m2v_decode.hip: m2v_decode_device ----
 void dec_release(m2v_enc *e);
+// ---- m2v_decode_streams.hip ----
+void ds_release(m2v_enc *e);
 // ---- m2v_demux.hip ----
 void dmx_release(m2v_enc *e);
 

@@ -946,8 +946,8 @@ int m2v_mux_scan_tile(void);
  * multiples).
  *
  * Out of scope, and M2V_DEC_SYNTAX by the definition: B pictures, field pictures, f_codes other than 1, skipped macroblocks, quantiser
- * matrices in the stream, intra_vlc_format 1, alternate scan.  Not offered: several streams per call (the `segments` of m2v_mux_device),
- * decode on the port path or in strips.
+ * matrices in the stream, intra_vlc_format 1, alternate scan.  Not offered: decode on the port path or in strips.  Several streams per call:
+ * m2v_decode_streams_device, below.
  */
 enum { M2V_DEC_ISO = 0, M2V_DEC_MODULE = 1 };
 enum { M2V_DEC_OK = 0, M2V_DEC_SYNTAX = -2, M2V_DEC_OVERFLOW = -3 };
@@ -957,6 +957,48 @@ typedef struct { uint64_t es_bytes, out_bytes, frame_bytes, err_offset;
 int m2v_decode_device(m2v_enc *e, const void *d_es, size_t es_bytes, void *d_dst, size_t cap, int layout, int mode, void *hip_stream);
 int m2v_decode_report(m2v_enc *e, m2v_decode_stat *out);
 int m2v_decode_scan_tile(void);
+
+/*
+ * Several streams per call: m2v_decode_streams_device decodes a batch of elementary streams of ANY picture sizes in one call, each judged
+ * alone, the frames packed one stream behind the other.  ("streams", not "batch": option "decode_batch" means pictures per chunk.)
+ *
+ * Segments.  nstreams is 1 .. 65535 (anything else: M2V_E_PARAM).  Stream b is the es_bytes[b] bytes at d_es + es_off[b], at any byte
+ * address; segments may touch or leave gaps.  Nothing outside a segment is read or interpreted: a start code in a gap, or one that
+ * straddles a segment's edge, does not exist.  layout and mode are the call's, as in m2v_decode_device.
+ *
+ * Each stream is judged alone.  `rec` is field for field what m2v_decode_device reports for that stream decoded by itself, err_offset
+ * relative to the stream's first byte; decoder.py stays the specification.  One stream's M2V_DEC_SYNTAX changes nothing about any other
+ * stream's frames or record.  A segment of fewer than 4 bytes is M2V_DEC_SYNTAX.  Streams of one call may have different picture sizes
+ * (the rendition ladder of m2v_set_source_size is the obvious batch).
+ *
+ * Layout of the output.  Frames are packed with no rounding between streams: stream b's picture n is at out_offset[b] + n * frame_bytes[b],
+ * and out_offset[b] is the sum of pictures * frame_bytes over the streams in front of it that the PROBE STAGE accepts - the headers and
+ * the grammar of the start codes: exactly what a call with d_dst == NULL finds.  A probe call (d_dst == NULL) reports out_offset and
+ * out_bytes per stream, and a decode has exactly the layout its probe reports, whatever cap is.  A stream refused at the probe stage takes
+ * no room (its out_offset is where it would have stood).  A stream refused inside a slice is found after the layout is fixed: it keeps
+ * its room, reports out_bytes 0, and not one byte of that room is written.  A stream whose room does not lie wholly inside cap is
+ * M2V_DEC_OVERFLOW, with nothing written; the others are written.  Nothing outside the rooms of OK streams is ever written.  With all
+ * streams OK and equal in size and length the output is a [B, N, frame_bytes] tensor, the mirror of encode_batch's input.
+ *
+ * The call blocks and answers M2V_OK once the kernels ran; the verdicts are in the records, which m2v_decode_streams_report pops, oldest
+ * first (out NULL: how many wait) and which are dropped at the next m2v_decode_streams_device.  M2V_E_STATE while a sequence is in
+ * progress or a resident call is in flight.  There are TWO host waits per call whatever nstreams is: one behind the plan - sizes, picture
+ * types, the layout - and one at the end (a third when a stream holds more start codes than its list was guessed to: the scan then runs
+ * again with the counts of the first run, as in m2v_decode_device).  An error the slice walk finds stays on the device.
+ *
+ * Chunks.  A chunk is a run of whole pictures in batch order; it may cut a stream between an I and a P picture, or end at a stream
+ * boundary.  Option "decode_batch", when set, is pictures per chunk, as before.  When it is 0 THIS entry's default is the 256 MiB bound on
+ * the chunk's levels alone, counted from each picture's own macroblocks (768 bytes each): there is no 256-picture ceiling here, because
+ * the batch of small clips - 64 clips x 9 pictures of 320 x 240 are one chunk - is the case this entry exists for.  The result does not
+ * depend on the chunks.  The slices of a stream that lies in more than one chunk are walked twice: once in front of all chunks for the
+ * verdict alone, so that a stream refused in a late slice has none of its early pictures written.
+ *
+ * m2v_decode_device is unchanged, and its kernels are its own: this entry runs kernels of its own over the same arithmetic.
+ */
+typedef struct { uint64_t es_offset, out_offset; m2v_decode_stat rec; } m2v_decode_stream_stat;   /* 88 bytes */
+int m2v_decode_streams_device(m2v_enc *e, const void *d_es, const uint64_t *es_off, const uint64_t *es_bytes, size_t nstreams,
+                              void *d_dst, size_t cap, int layout, int mode, void *hip_stream);
+int m2v_decode_streams_report(m2v_enc *e, m2v_decode_stream_stat *out, size_t max);   /* pops, oldest first; out NULL: how many wait */
 
 /*
  * Demux on the device: the inverse of m2v_mux_device.  nstreams (1 .. 65535) transport (kind M2V_MUX_TS) or program (M2V_MUX_PS) streams
