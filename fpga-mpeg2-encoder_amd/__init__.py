@@ -130,6 +130,7 @@ DECODE_STAT_DTYPE = np.dtype([("es_bytes", "<u8"), ("out_bytes", "<u8"), ("frame
 # m2v_decode_stream_stat: one stream's record of m2v_decode_streams_device, 88 bytes (Mpeg2Encoder.decode_streams_report)
 DECODE_STREAM_STAT_DTYPE = np.dtype([("es_offset", "<u8"), ("out_offset", "<u8"), ("rec", DECODE_STAT_DTYPE)])
 DEC_MODES = {"iso": 0, "module": 1}                              # M2V_DEC_*
+DEC_SYNTAXES = {"module": 0, "main": 1}                          # M2V_SYNTAX_*: option "decode_syntax"
 DEC_OK, DEC_SYNTAX, DEC_OVERFLOW = 0, -2, -3
 DEC_STATUS = {0: "M2V_DEC_OK", -2: "M2V_DEC_SYNTAX", -3: "M2V_DEC_OVERFLOW"}
 
@@ -732,7 +733,7 @@ class Mpeg2Encoder:
         self._chk(self._L.m2v_set_option(self._h, name.encode(), int(value)), "m2v_set_option(%s)" % name)
         if name == "stats":
             self._set[name] = bool(value)
-        if name in ("gop_bytes_max", "scene_cut"):
+        if name in ("gop_bytes_max", "scene_cut", "decode_syntax"):
             self._set[name] = int(value)
 
     def _set_list(self, key, values, ctype, what):
@@ -913,7 +914,7 @@ class Mpeg2Encoder:
         self._chk(self._L.m2v_decode_report(self._h, out.ctypes.data), "m2v_decode_report")
         return out[0]
 
-    def decode_device(self, es, layout="i420", mode="iso", out=None, container=None, stream=None):
+    def decode_device(self, es, layout="i420", mode="iso", out=None, container=None, stream=None, syntax="module"):
         """m2v_decode_device: the MPEG-2 elementary stream in the one-dimensional uint8 device tensor `es` (at any byte alignment) decoded
         on the device to 4:2:0 frames in `layout`; mode "iso" is decoder.decode(quirks=False), "module" the module's own loop
         (quirks=True).  Returns (frames [pictures, frame_bytes] uint8 on es's device, record).  out: a contiguous uint8 tensor to write into
@@ -925,8 +926,23 @@ class Mpeg2Encoder:
         call: one host wait of 64 bytes, which the decode's own probe pays anyway.  A demux status other than DEMUX_OK raises M2VError
         naming the status and err_offset.  The scratch tensor is zeroed first and the stream handed on with the zero padding to a whole
         32-byte word that the encoder writes behind sequence_end_code and a muxer drops: the decoder's definition wants it.  Without
-        the keyword the function is exactly what it was."""
+        the keyword the function is exactly what it was.
+
+        syntax = "module" (the default) or "main": the call decodes with that syntax whatever set_option("decode_syntax") left on the
+        handle - the option is set for this call and afterwards put back to the value it had.  "main": Main-Profile streams
+        of progressive I / P frame pictures from any encoder (decoder.decode(..., quirks=False, syntax="main") is the definition; mode
+        must be "iso").  It goes with container= as well: a transport stream from an ordinary multiplexer, demultiplexed and decoded
+        on the device."""
         import torch
+        if syntax not in DEC_SYNTAXES:
+            raise ValueError("decode_device: syntax is one of %s" % ", ".join(DEC_SYNTAXES))
+        held = self._set.get("decode_syntax", DEC_SYNTAXES["module"])      # what set_option("decode_syntax") left on the handle
+        if DEC_SYNTAXES[syntax] != held:
+            self.set_option("decode_syntax", DEC_SYNTAXES[syntax])
+            try:
+                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax)
+            finally:
+                self.set_option("decode_syntax", held)
         if container is not None:
             if not isinstance(es, torch.Tensor) or es.dtype != torch.uint8 or es.dim() != 1 or not es.is_cuda or es.device.index != self.device:
                 raise ValueError("decode_device: a one-dimensional uint8 tensor on the handle's device is required")

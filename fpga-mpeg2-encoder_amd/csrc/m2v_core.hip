@@ -715,6 +715,11 @@ int m2v_set_option(m2v_enc *e, const char *name, long long value)
         e->decode_batch = (size_t)value;
         return M2V_OK;
     }
+    if (!strcmp(name, "decode_syntax")) {
+        if (value != M2V_SYNTAX_MODULE && value != M2V_SYNTAX_MAIN) { e->set_err("m2v_set_option: decode_syntax is M2V_SYNTAX_MODULE (0) or M2V_SYNTAX_MAIN (1)"); return M2V_E_PARAM; }
+        e->decode_syntax = (int)value;
+        return M2V_OK;
+    }
     if (!strcmp(name, "demux_blocks")) {
         if (value < 0 || value > 4096) { e->set_err("m2v_set_option: demux_blocks is 0 (the default: 4096) .. 4096 workgroups"); return M2V_E_PARAM; }
         e->demux_blocks = (size_t)value;

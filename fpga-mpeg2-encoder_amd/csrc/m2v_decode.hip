@@ -31,8 +31,10 @@
 // the chunk are walked and the offset is the earliest whatever the scheduling; k_dec_judge, one lane behind them, turns it into the
 // status, the later kernels of the call read the status and return at once (a later chunk holds later offsets only), and k_dec_finish
 // copies the verdict into the pinned record behind the last chunk.  No encoder kernel is touched; a handle that never decodes allocates nothing here.
-#include "m2v_host.hpp"
-#include "m2v_decode_kernels.hpp"
+//
+// Option "decode_syntax" = M2V_SYNTAX_MAIN puts the main-syntax variants of k_dec_plan, k_dec_slices and k_dec_recon in their places
+// (m2v_decode_main.hip, a translation unit of its own: the three kernels here are what they were); the rest of the call is shared.
+#include "m2v_decode_state.hpp"
 
 static_assert(sizeof(m2v_decode_stat) == 72, "the record of include/m2v_mi355x.h is 72 bytes");
 static_assert(sizeof(dec::MbRec) == 16, "a macroblock's record is 16 bytes");
@@ -41,19 +43,9 @@ static_assert(M2V_DEC_ISO == dec::kIso && M2V_DEC_MODULE == dec::kModule && M2V_
 
 namespace m2v {
 
-constexpr int kDecThreads = 256;
 constexpr size_t kDecLevelBytes = 256u << 20;      // the default "decode_batch" keeps the chunk's levels within this
 constexpr size_t kDecBatchMax = 256;
 static_assert(dec::kScanTile == (uint32_t)kDecThreads * 16u, "a tile is one pass of a block");
-
-struct DecState {
-    unsigned long long err, last_nz;               // the earliest error's offset (dec::kNone: none); one past the last byte that is not zero
-    uint32_t nev, ev_cap;
-    int32_t status;
-    uint32_t npics, gops, reps, chains, width, height, mbw, mbh, pad;
-    unsigned long long frame_bytes;
-};
-struct DecPic { uint32_t ev, type, chain, step; };
 
 template <bool EMIT>
 __global__ __launch_bounds__(kDecThreads) void k_dec_scan(const uint8_t *__restrict__ es, unsigned long long n, DecState *st, uint32_t *__restrict__ tiles,
@@ -366,7 +358,7 @@ __global__ void k_dec_finish(const DecState *st, m2v_decode_stat *h_rec)
 void dec_release(m2v_enc *e)
 {
     e->d_dec_st.release(); e->d_dec_tiles.release(); e->d_dec_ev.release(); e->d_dec_pics.release(); e->d_dec_mb.release(); e->d_dec_dc.release();
-    e->d_dec_lv.release(); e->d_dec_buf.release(); e->d_dec_list.release();
+    e->d_dec_lv.release(); e->d_dec_buf.release(); e->d_dec_list.release(); e->d_dec_main.release();
     if (e->h_dec) (void)hipHostFree(e->h_dec);
     e->h_dec = nullptr; e->h_dec_cap = 0;
 }
@@ -385,7 +377,8 @@ static int decode_impl(m2v_enc *e, void *argp)
     R.es_bytes = n;
     if (n < 4) { R.status = M2V_DEC_SYNTAX; return M2V_OK; }          // not one start code
     e->d_dec_st.recorded = e->d_dec_ev.recorded = e->d_dec_pics.recorded = e->d_dec_mb.recorded = e->d_dec_dc.recorded = false;     // (no recorded graph references them)
-    e->d_dec_lv.recorded = e->d_dec_buf.recorded = e->d_dec_tiles.recorded = e->d_dec_list.recorded = false;
+    e->d_dec_lv.recorded = e->d_dec_buf.recorded = e->d_dec_tiles.recorded = e->d_dec_list.recorded = e->d_dec_main.recorded = false;
+    const bool main_syntax = e->decode_syntax == M2V_SYNTAX_MAIN;      // the main-syntax kernels in the places of k_dec_plan, k_dec_slices, k_dec_recon
     const size_t ntiles = (n + dec::kScanTile - 1) / dec::kScanTile;
     if (ntiles > 0x7FFFFFFFu) { e->set_err("m2v_decode_device: the stream is longer than 2^31 scan tiles"); return M2V_E_PARAM; }
     size_t ev_cap = std::max<size_t>(1024, n / 16 + 64);              // a guess: a second run takes the count of the first
@@ -413,9 +406,15 @@ static int decode_impl(m2v_enc *e, void *argp)
         HIPCHK(hipGetLastError());
         k_dec_scan<true><<<gx, kDecThreads, 0, s>>>(a->es, n, d_st, e->d_dec_tiles.p, e->d_dec_ev.p);
         HIPCHK(hipGetLastError());
-        k_dec_plan<<<1, kDecThreads, 0, s>>>(a->es, n, e->d_dec_ev.p, d_st, (DecPic *)e->d_dec_pics.p, (uint32_t)pic_cap, e->h_dec + rec_off + 128,
-                                             (unsigned long long)a->cap, a->dst ? 0 : 1, (m2v_decode_stat *)(e->h_dec + rec_off));
-        HIPCHK(hipGetLastError());
+        if (main_syntax) {
+            e->d_dec_main.ensure(kDecMainMatrices + pic_cap * sizeof(DecMainPic));
+            dec_main_plan(s, a->es, n, e->d_dec_ev.p, d_st, (DecPic *)e->d_dec_pics.p, (uint32_t)pic_cap, e->h_dec + rec_off + 128, (unsigned long long)a->cap,
+                          a->dst ? 0 : 1, (m2v_decode_stat *)(e->h_dec + rec_off), e->d_dec_main.p);
+        } else {
+            k_dec_plan<<<1, kDecThreads, 0, s>>>(a->es, n, e->d_dec_ev.p, d_st, (DecPic *)e->d_dec_pics.p, (uint32_t)pic_cap, e->h_dec + rec_off + 128,
+                                                 (unsigned long long)a->cap, a->dst ? 0 : 1, (m2v_decode_stat *)(e->h_dec + rec_off));
+            HIPCHK(hipGetLastError());
+        }
         HIPCHK(hipStreamSynchronize(s));                              // the call's one wait for the plan: pictures, size, types
         h_rec = (const m2v_decode_stat *)(e->h_dec + rec_off);
         if (h_rec->status != dec::kEvents) break;
@@ -458,12 +457,22 @@ static int decode_impl(m2v_enc *e, void *argp)
     for (size_t p0 = 0, c = 0; p0 < np; p0 += B, ++c) {
         const size_t nb = std::min(B, np - p0);
         HIPCHK(hipMemsetAsync(e->d_dec_lv.p, 0, nb * mbs * 768, s));
-        k_dec_slices<<<(unsigned)((nb * mbh + 63) / 64), 64, 0, s>>>(a->es, n, e->d_dec_ev.p, d_st, (const DecPic *)e->d_dec_pics.p, (uint32_t)p0, (uint32_t)nb,
-                                                                     a->mode, d_mb, e->d_dec_dc.p, e->d_dec_lv.p);
-        HIPCHK(hipGetLastError());
+        if (main_syntax) {
+            dec_main_slices(s, (unsigned)((nb * mbh + 63) / 64), a->es, n, e->d_dec_ev.p, d_st, (const DecPic *)e->d_dec_pics.p, e->d_dec_main.p, (uint32_t)p0,
+                            (uint32_t)nb, d_mb, e->d_dec_dc.p, e->d_dec_lv.p);
+        } else {
+            k_dec_slices<<<(unsigned)((nb * mbh + 63) / 64), 64, 0, s>>>(a->es, n, e->d_dec_ev.p, d_st, (const DecPic *)e->d_dec_pics.p, (uint32_t)p0, (uint32_t)nb,
+                                                                         a->mode, d_mb, e->d_dec_dc.p, e->d_dec_lv.p);
+            HIPCHK(hipGetLastError());
+        }
         k_dec_judge<<<1, 1, 0, s>>>(d_st);
         HIPCHK(hipGetLastError());
         for (const Launch &l : steps[c]) {
+            if (main_syntax) {
+                dec_main_recon(s, (unsigned)mbs, (unsigned)l.count, d_st, e->d_dec_list.p + l.off, (uint32_t)p0, e->d_dec_main.p, d_mb, e->d_dec_dc.p, e->d_dec_lv.p,
+                               e->d_dec_buf.p, psz);
+                continue;
+            }
             k_dec_recon<<<dim3((unsigned)mbs, (unsigned)l.count), 64, 0, s>>>(d_st, e->d_dec_list.p + l.off, (uint32_t)p0, a->mode, d_mb, e->d_dec_dc.p,
                                                                              e->d_dec_lv.p, e->d_dec_buf.p, psz);
             HIPCHK(hipGetLastError());
@@ -491,6 +500,10 @@ int m2v_decode_device(m2v_enc *e, const void *d_es, size_t es_bytes, void *d_dst
     if (!layout420_ok(layout)) { e->set_err("m2v_decode_device: unknown layout %d", layout); return M2V_E_PARAM; }
     if (mode != M2V_DEC_ISO && mode != M2V_DEC_MODULE) { e->set_err("m2v_decode_device: unknown mode %d", mode); return M2V_E_PARAM; }
     if (!d_es && es_bytes) { e->set_err("m2v_decode_device: d_es is NULL"); return M2V_E_PARAM; }
+    if (e->decode_syntax == M2V_SYNTAX_MAIN && mode != M2V_DEC_ISO) {
+        e->set_err("m2v_decode_device: with \"decode_syntax\" = main the mode is M2V_DEC_ISO (the module's deviations belong to its own syntax)");
+        return M2V_E_PARAM;
+    }
     if (in_progress(e, "m2v_decode_device", "m2v_encode_resident_end first")) return M2V_E_STATE;
     DecodeArgs a{(const uint8_t *)d_es, es_bytes, (uint8_t *)d_dst, cap, layout, mode, (hipStream_t)hip_stream};
     return guard(e, decode_impl, &a);

@@ -713,5 +713,381 @@ M2V_HD inline OutByte streams_out_locate(const ChunkPic *t, uint32_t n, uint64_t
     return r;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// the main syntax (option "decode_syntax" = M2V_SYNTAX_MAIN; decoder.decode_main is the definition): Main-Profile streams of
+// progressive frame pictures, I and P, from any encoder.  The functions above keep the module's syntax; these stand beside them and
+// use what is syntax-blind of them (bit reader, the five VLC tables, parse_block, vector_inside, the transform, the prediction).
+// The arithmetic is M2V_DEC_ISO's.
+//
+// The grammar stays a set of local rules although user_data, copyright_extension and picture_display_extension may stand between
+// the units that matter: every start code is significant or transparent by what it is (main_role: its code, and an extension's
+// identifier), a significant one is judged against the significant one in front of it (`prev`: the caller's prefix scan), a
+// transparent one by which significant one it stands behind.  A transparent unit still ends where the next start code begins.
+// ---------------------------------------------------------------------------------------------------------------------------
+enum { rUser = 9, rSkipExt = 10 };                               // behind rEnd: the transparent roles
+
+M2V_HD inline int main_role(const uint8_t *es, uint64_t n, uint64_t e)
+{
+    const uint32_t c = ev_code(e);
+    if (c == 0xB3) return rSeq;
+    if (c == 0xB8) return rGop;
+    if (c == 0xB7) return rEnd;
+    if (c == 0x00) return rPic;
+    if (c <= 0xAF) return rSlice;
+    if (c == 0xB2) return rUser;
+    if (c != 0xB5 || ev_pos(e) + 4 >= n) return rBad;
+    switch (es[ev_pos(e) + 4] >> 4) {                            // extension_start_code_identifier
+    case 1: return rSeqExt;
+    case 2: return rDisp;
+    case 8: return rPicExt;
+    case 4: case 7: return rSkipExt;                             // copyright_extension, picture_display_extension
+    default: return rBad;                                        // quant_matrix_extension and the scalable ones
+    }
+}
+
+M2V_HD inline bool main_significant(int role) { return role >= rSeq && role <= rEnd; }
+
+M2V_HD inline uint32_t zigzag_position(uint32_t i)               // figure 7-2 the other way: raster index -> zig-zag position
+{
+    static constexpr uint8_t kPos[64] = {
+        0, 1, 5, 6, 14, 15, 27, 28, 2, 4, 7, 13, 16, 26, 29, 42, 3, 8, 12, 17, 25, 30, 41, 43, 9, 11, 18, 24, 31, 40, 44, 53, 10, 19, 23, 32, 39, 45,
+        52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63
+    };
+    return kPos[i & 63u];
+}
+
+M2V_HD inline uint32_t alternate_to_raster(uint32_t k)           // figure 7-3: alternate scan position -> raster index
+{
+    static constexpr uint8_t kAlt[64] = {
+        0, 8, 16, 24, 1, 9, 2, 10, 17, 25, 32, 40, 48, 56, 57, 49, 41, 33, 26, 18, 3, 11, 4, 12, 19, 27, 34, 42, 50, 58, 35, 43, 51, 59, 20, 28, 5, 13,
+        6, 14, 21, 29, 36, 44, 52, 60, 37, 45, 53, 61, 22, 30, 7, 15, 23, 31, 38, 46, 54, 62, 39, 47, 55, 63
+    };
+    return kAlt[k & 63u];
+}
+
+M2V_HD inline int32_t main_scale(uint32_t qcode, uint32_t q_scale_type)      // table 7-6 (code 0 has no scale: 0 in both columns)
+{
+    static constexpr uint8_t kNonLinear[32] = {
+        0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 18, 20, 22, 24, 28, 32, 36, 40, 44, 48, 52, 56, 64, 72, 80, 88, 96, 104, 112
+    };
+    return q_scale_type ? (int32_t)kNonLinear[qcode & 31u] : 2 * (int32_t)(qcode & 31u);
+}
+
+// Table B-1 over the next 11 bits: length | increment << 8, increment 34 = macroblock_escape; 0 where no code begins the window
+M2V_HD inline uint32_t vlc_increment(uint32_t w11)
+{
+    if (w11 >> 10) return 1u | 1u << 8;
+    static constexpr uint16_t kCode[33] = {
+        0b011, 0b010, 0b0011, 0b0010, 0b00011, 0b00010, 0b0000111, 0b0000110, 0b00001011, 0b00001010, 0b00001001, 0b00001000, 0b00000111, 0b00000110,
+        0b0000010111, 0b0000010110, 0b0000010101, 0b0000010100, 0b0000010011, 0b0000010010, 0b00000100011, 0b00000100010, 0b00000100001,
+        0b00000100000, 0b00000011111, 0b00000011110, 0b00000011101, 0b00000011100, 0b00000011011, 0b00000011010, 0b00000011001, 0b00000011000,
+        0b00000001000
+    };
+    static constexpr uint8_t kLen[33] = {3, 3, 4, 4, 5, 5, 7, 7, 8, 8, 8, 8, 8, 8, 10, 10, 10, 10, 10, 10, 11, 11, 11, 11, 11, 11, 11, 11, 11, 11, 11, 11, 11};
+    for (uint32_t k = 0; k < 33u; ++k)
+        if ((w11 >> (11u - kLen[k])) == kCode[k]) return kLen[k] | (k + 2u) << 8;
+    return 0u;
+}
+
+// sequence_header with its matrices (raster order; the defaults where none is loaded), and whether a display extension stood behind
+struct MainSeq { SeqHdr h; uint32_t display; uint8_t wi[64], wn[64]; };
+
+// the header's fields into h; every weight of both matrices through weight(matrix 0 = intra / 1 = non-intra, raster index, value) -
+// the first header stores them, a repeated one compares them with the first's where they lie, without a copy of its own
+template <class Weight>
+M2V_HD inline bool main_sequence_header(const uint8_t *es, uint64_t start, uint64_t end, SeqHdr &h, Weight weight)
+{
+    Bits b = unit_bits(es, start, end);
+    h.width = get(b, 12); h.height = get(b, 12); h.aspect = get(b, 4); h.frame_rate_code = get(b, 4); h.bit_rate = get(b, 18);
+    bool ok = get(b, 1) == 1;
+    h.vbv = get(b, 10); h.constrained = get(b, 1);
+    for (int m = 0; m < 2; ++m) {                                // load_intra_quantiser_matrix, load_non_intra_quantiser_matrix
+        if (!get(b, 1)) {                                        // the default matrix
+            for (uint32_t i = 0; i < 64u; ++i) weight(m, i, m ? 16u : (uint32_t)intra_weight(i));
+            continue;
+        }
+        for (uint32_t k = 0; k < 64u; ++k) {                     // 64 bytes in zig-zag order, 0 forbidden
+            const uint32_t v = get(b, 8);
+            ok = ok && v != 0;
+            weight(m, scan_to_raster(k), v);
+        }
+    }
+    return ok && !b.err && tail_zero(b);
+}
+
+// the picture's parameters: what differs from picture to picture in the main syntax
+struct PicParams { uint32_t fh, fv, prec, qst, alt; };           // f_code[0][0], [0][1], intra_dc_precision, q_scale_type, alternate_scan
+
+M2V_HD inline uint32_t params_pack(const PicParams &p) { return p.fh | p.fv << 4 | p.prec << 8 | p.qst << 10 | p.alt << 11; }
+M2V_HD inline PicParams params_unpack(uint32_t v) { return PicParams{v & 15u, (v >> 4) & 15u, (v >> 8) & 3u, (v >> 10) & 1u, (v >> 11) & 1u}; }
+
+M2V_HD inline bool main_fcode_ok(uint32_t f, uint32_t ptype) { return (f >= 1 && f <= 9) || (ptype == 1 && f == 15); }      // 15: "not used" in an I picture
+
+M2V_HD inline bool main_picture_extension(const uint8_t *es, uint64_t start, uint64_t end, uint32_t ptype, PicParams &p)
+{
+    Bits b = unit_bits(es, start, end);
+    bool ok = get(b, 4) == 8;
+    p.fh = get(b, 4); p.fv = get(b, 4);
+    skip(b, 8);                                              // the backward ones
+    p.prec = get(b, 2);
+    ok = ok && get(b, 2) == 3;                               // frame picture
+    skip(b, 1);                                              // top_field_first
+    ok = ok && get(b, 1) == 1;                               // frame_pred_frame_dct
+    ok = ok && get(b, 1) == 0;                               // concealment_motion_vectors
+    p.qst = get(b, 1);
+    ok = ok && get(b, 1) == 0;                               // intra_vlc_format
+    p.alt = get(b, 1);
+    skip(b, 4);                                              // repeat_first_field, chroma_420_type, progressive_frame, composite_display_flag
+    ok = ok && main_fcode_ok(p.fh, ptype) && main_fcode_ok(p.fv, ptype);
+    return ok && !b.err && tail_zero(b);
+}
+
+// sequence_header at event i, sequence_extension at i + 1, then user_data and at most one sequence_display_extension: kNone, or the
+// start of the first unit that is wrong
+template <class Weight>
+M2V_HD inline uint64_t main_group(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, uint32_t i, SeqHdr &h, uint32_t &display, Weight weight)
+{
+    const uint64_t p0 = ev_pos(ev[i]);
+    if (main_role(es, n, ev[i]) != rSeq || i + 1 >= nev) return p0;
+    const uint64_t p1 = ev_pos(ev[i + 1]), p2 = i + 2 < nev ? ev_pos(ev[i + 2]) : n;
+    h = SeqHdr{};
+    display = 0;
+    if (!main_sequence_header(es, p0, p1, h, weight)) return p0;
+    if (main_role(es, n, ev[i + 1]) != rSeqExt || !parse_sequence_extension(es, p1, p2, h)) return p1;
+    uint32_t j = i + 2;
+    while (j < nev && main_role(es, n, ev[j]) == rUser) ++j;     // (bounded by the events)
+    if (j < nev && main_role(es, n, ev[j]) == rDisp) {
+        if (!parse_display_extension(es, ev_pos(ev[j]), j + 1 < nev ? ev_pos(ev[j + 1]) : n, h)) return ev_pos(ev[j]);
+        display = 1;
+    }
+    return kNone;
+}
+
+struct MainPlan { MainSeq seq; uint32_t mbw, mbh; };
+
+M2V_HD inline uint64_t main_first(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, MainPlan &P)
+{
+    if (!nev) return 0;
+    for (uint64_t k = 0, p0 = ev_pos(ev[0]); k < p0; k += 8) if (be64(es, k, p0)) return 0;
+    MainSeq &q = P.seq;
+    const uint64_t bad = main_group(es, n, ev, nev, 0, q.h, q.display, [&](int m, uint32_t i, uint32_t v) { (m ? q.wn : q.wi)[i & 63u] = (uint8_t)v; });
+    if (bad != kNone) return bad;
+    const SeqHdr &h = P.seq.h;
+    if (!h.width || !h.height || h.width > (uint32_t)kMaxSize || h.height > (uint32_t)kMaxSize) return ev_pos(ev[0]);
+    P.mbw = (h.width + 15u) / 16u; P.mbh = (h.height + 15u) / 16u;
+    return kNone;
+}
+
+// a picture may end here: behind the sequence headers, or behind the slice of the last macroblock row
+M2V_HD inline bool main_top(const uint8_t *es, uint64_t n, const uint64_t *ev, int prev, uint32_t mbh)
+{
+    if (prev < 0) return false;
+    const int role = main_role(es, n, ev[prev]);
+    return role == rSeqExt || role == rDisp || (role == rSlice && ev_code(ev[prev]) == mbh);
+}
+
+// event i by its own rule; prev: the significant event in front of it, -1: none
+M2V_HD inline EvInfo main_event(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, uint32_t i, const MainPlan &P, uint64_t last_nz, int prev)
+{
+    EvInfo r{kNone, 0, 0, 0, 0};
+    const uint64_t pos = ev_pos(ev[i]), end = i + 1 < nev ? ev_pos(ev[i + 1]) : n;
+    const int role = main_role(es, n, ev[i]);
+    const int prole = prev >= 0 ? main_role(es, n, ev[prev]) : rBad;
+    const int before = i ? main_role(es, n, ev[i - 1]) : rBad;      // the event right in front, transparent or not
+    const bool top = main_top(es, n, ev, prev, P.mbh);
+    bool ok = true;
+    switch (role) {
+    case rBad: ok = false; break;
+    case rSeq:
+        if (i) {
+            SeqHdr h;                                              // 6.1.1.6: it says what the first one said, matrices included
+            uint32_t display;
+            bool same = true;
+            const uint64_t bad = main_group(es, n, ev, nev, i, h, display,
+                                            [&](int m, uint32_t k, uint32_t v) { same = same && (m ? P.seq.wn : P.seq.wi)[k & 63u] == v; });
+            if (bad != kNone) r.bad = bad;
+            else { ok = top && same && seq_equal(h, P.seq.h) && display == P.seq.display; r.rep = 1; }
+        }
+        break;
+    case rSeqExt: ok = before == rSeq; break;                      // (read with its sequence header)
+    case rDisp: { SeqHdr h; ok = prole == rSeqExt && parse_display_extension(es, pos, end, h); break; }
+    case rUser: ok = prole == rSeqExt || prole == rDisp || prole == rGop || prole == rPicExt; break;
+    case rSkipExt: ok = prole == rPicExt; break;
+    case rGop: { const bool good = parse_gop_header(es, pos, end); ok = top && good; r.gop = good; break; }
+    case rPic: { const bool good = parse_picture_header(es, pos, end, r.type); ok = (top || prole == rGop) && good; r.pic = good; break; }
+    case rPicExt: {
+        PicParams p;
+        const uint64_t pp = i ? ev_pos(ev[i - 1]) : 0;
+        const uint32_t ptype = before == rPic && pp + 5 < n ? (es[pp + 5] >> 3) & 7u : 0u;
+        ok = before == rPic && main_picture_extension(es, pos, end, ptype, p);
+        break;
+    }
+    case rSlice: {
+        const uint32_t c = ev_code(ev[i]);
+        ok = c <= P.mbh && (c == 1 ? prole == rPicExt : prole == rSlice && ev_code(ev[prev]) == c - 1);
+        break;
+    }
+    default:                                                       // rEnd: the last code, zeros behind it
+        ok = top && i + 1 == nev && last_nz <= pos + 4;
+        break;
+    }
+    if (i + 1 == nev && role != rEnd && ok)                        // no sequence_end_code: the stream ends where a picture may end
+        ok = main_top(es, n, ev, main_significant(role) ? (int)i : prev, P.mbh);
+    if (!ok) r.bad = min64(r.bad, pos);
+    return r;
+}
+
+// the parameters of the picture whose header is event i of an accepted stream, and its first slice's event
+M2V_HD inline uint32_t main_picture_params(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, uint32_t i, uint32_t &slice0)
+{
+    PicParams p{1, 1, 0, 0, 0};
+    uint32_t j = i + 2;
+    if (i + 1 < nev) {
+        const uint64_t pos = ev_pos(ev[i]);
+        (void)main_picture_extension(es, ev_pos(ev[i + 1]), i + 2 < nev ? ev_pos(ev[i + 2]) : n, pos + 5 < n ? (es[pos + 5] >> 3) & 7u : 0u, p);
+    }
+    while (j < nev && !main_significant(main_role(es, n, ev[j]))) ++j;
+    slice0 = j;
+    return params_pack(p);
+}
+
+// ---- macroblock layer ----
+struct MainMb { uint8_t intra, mc, cbp, qcode; int16_t mvx, mvy; uint8_t skipped, reserved[7]; };      // MbRec with the vectors in 16 bits; mc 0: the zero vector
+
+// 7.6.3.1: the component from its prediction, the motion code, the residual and r_size = f_code - 1
+M2V_HD inline int32_t main_vector(int32_t pmv, int32_t code, int32_t residual, int r_size)
+{
+    const int32_t f = 1 << r_size;
+    int32_t delta = code;
+    if (f != 1 && code != 0) {
+        delta = ((code < 0 ? -code : code) - 1) * f + residual + 1;
+        if (code < 0) delta = -delta;
+    }
+    int32_t v = pmv + delta;
+    if (v < -16 * f) v += 32 * f; else if (v > 16 * f - 1) v -= 32 * f;
+    return v;
+}
+
+// one macroblock behind its address increment: tables B-2 / B-3, the quantiser, the vector, the pattern, the blocks.  qcode: the
+// slice's quantiser_scale_code, which a macroblock quantiser replaces.  false = refused
+template <class Put>
+M2V_HD inline bool main_macroblock(Bits &b, uint32_t ptype, const PicParams &pp, SliceState &s, uint32_t &qcode, MainMb &m, int32_t (&dc)[6], Put put)
+{
+    bool quant = false, mc = false, pattern = false, intra = false;
+    const uint32_t w = peek(b, 6);
+    int len;
+    if (ptype == 1) {
+        if (w >> 5) { len = 1; intra = true; }                                   // '1'      intra
+        else if (w >> 4) { len = 2; intra = quant = true; }                      // '01'     intra, quant
+        else return false;
+    }
+    else if (w >> 5) { len = 1; mc = pattern = true; }                           // '1'      MC, coded
+    else if (w >> 4) { len = 2; pattern = true; }                                // '01'     No MC, coded
+    else if (w >> 3) { len = 3; mc = true; }                                     // '001'    MC, not coded
+    else if ((w >> 1) == 3u) { len = 5; intra = true; }                          // '00011'  intra
+    else if ((w >> 1) == 2u) { len = 5; quant = mc = pattern = true; }           // '00010'  MC, coded, quant
+    else if ((w >> 1) == 1u) { len = 5; quant = pattern = true; }                // '00001'  No MC, coded, quant
+    else if (w == 1u) { len = 6; quant = intra = true; }                         // '000001' intra, quant
+    else return false;
+    skip(b, len);
+    if (quant) {
+        qcode = get(b, 5);
+        if (!qcode) return false;
+    }
+    int32_t mv[2] = {0, 0};
+    if (mc) {
+        for (int t = 0; t < 2; ++t) {
+            const int r_size = (int)(t ? pp.fv : pp.fh) - 1;
+            const uint32_t e = vlc_motion(peek(b, 32));
+            if (!e || r_size < 0 || r_size > 8) return false;
+            skip(b, (int)(e & 255u));
+            int32_t code = (int32_t)(e >> 8);
+            if (code && get(b, 1)) code = -code;
+            const int32_t residual = code && r_size ? (int32_t)get(b, r_size) : 0;
+            s.pmv[t] = mv[t] = main_vector(s.pmv[t], code, residual, r_size);
+        }
+    } else {
+        s.pmv[0] = s.pmv[1] = 0;                             // 7.6.3.4
+    }
+    uint32_t cbp = intra ? 63u : 0u;
+    if (pattern) {
+        const uint32_t e = vlc_cbp(peek(b, 32));
+        if (!e) return false;
+        skip(b, (int)(e & 255u));
+        cbp = e >> 8;
+    }
+    if (!intra) { for (int c = 0; c < 3; ++c) s.dc_pred[c] = 0; }    // 7.2.1: a macroblock that is not intra resets the DC predictors
+    m = MainMb{};
+    m.intra = intra; m.mc = mc; m.cbp = (uint8_t)cbp; m.mvx = (int16_t)mv[0]; m.mvy = (int16_t)mv[1];
+    for (int blk = 0; blk < 6; ++blk) {
+        dc[blk] = 0;
+        if (!((cbp >> (5 - blk)) & 1u)) continue;
+        // parse_block places through the zig-zag scan: with alternate_scan the same position through figure 7-3
+        if (!parse_block(b, intra, blk < 4 ? 0 : blk - 3, s, dc[blk],
+                         [&](uint32_t i, int32_t l) { put(blk, pp.alt ? alternate_to_raster(zigzag_position(i)) : i, l); })) return false;
+    }
+    return !b.err;
+}
+
+// the slice of macroblock row `row`: address increments with escapes, skipped macroblocks (P pictures, never the row's first or
+// last), mbw macroblocks in all through sink.mb(col, record, dc) and sink.level(col, block, raster index, level), then nothing but
+// zero stuffing.  Every pass of the loop moves col forward, an escape by 33: mbw passes at most
+template <class Sink>
+M2V_HD inline bool main_slice(const uint8_t *es, uint64_t start, uint64_t end, uint32_t ptype, const PicParams &pp, int mbw, int mbh, int row, Sink &sink)
+{
+    Bits b = unit_bits(es, start, end);
+    uint32_t qcode = get(b, 5);
+    if (get(b, 1) != 0) return false;                        // extra_bit_slice
+    SliceState s{{0, 0, 0}, {0, 0}};
+    int col = -1;
+    while (col < mbw - 1) {
+        int incr = 0;
+        uint32_t e;
+        for (;;) {
+            e = vlc_increment(peek(b, 11));
+            if (!e) return false;
+            skip(b, (int)(e & 255u));
+            if ((e >> 8) != 34u) break;
+            incr += 33;                                      // macroblock_escape
+            if (col + incr >= mbw) return false;
+        }
+        incr += (int)(e >> 8);
+        if ((col < 0 && incr != 1) || col + incr >= mbw || b.err) return false;
+        if (incr > 1) {                                      // 7.6.6: skipped - the zero vector, the predictors reset
+            if (ptype != 2) return false;
+            MainMb z{};
+            z.skipped = 1; z.qcode = (uint8_t)qcode;
+            const int32_t none[6] = {0, 0, 0, 0, 0, 0};
+            for (int k = 1; k < incr; ++k) sink.mb(col + k, z, none);
+            s = SliceState{{0, 0, 0}, {0, 0}};
+        }
+        col += incr;
+        MainMb m;
+        int32_t dc[6];
+        if (!main_macroblock(b, ptype, pp, s, qcode, m, dc, [&](int blk, uint32_t i, int32_t l) { sink.level(col, blk, i, l); })) return false;
+        if (m.mc && !vector_inside(col, row, m.mvx, m.mvy, mbw, mbh, kIso)) return false;
+        m.qcode = (uint8_t)qcode;
+        sink.mb(col, m, dc);
+    }
+    return !b.err && tail_zero(b);
+}
+
+// ---- reconstruction ----
+M2V_HD inline int32_t main_saturate(int32_t v) { return v > 2047 ? 2047 : v < -2048 ? -2048 : v; }      // 7.4.3
+
+// 7.4.2 with the stream's weight w for the coefficient and the picture's scale, saturated; the intra DC and mismatch control are
+// the caller's (main_dequant_dc, mismatch)
+M2V_HD inline int32_t main_dequant(int32_t q, int32_t w, bool intra, int32_t qscale)
+{
+    const int32_t v = (intra ? 2 * q : 2 * q + (q > 0 ? 1 : q < 0 ? -1 : 0)) * w * qscale / 32;
+    return main_saturate(v);
+}
+
+// the intra DC relative to its reset value, times intra_dc_mult = 8 >> precision (the offset of 1024 is the prediction's 128)
+M2V_HD inline int32_t main_dequant_dc(int32_t dc, uint32_t prec)
+{
+    return main_saturate((int32_t)((uint32_t)dc << (3u - (prec & 3u))));
+}
+
 }  // namespace dec
 }  // namespace m2v

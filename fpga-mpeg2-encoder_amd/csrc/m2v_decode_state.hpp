@@ -1,0 +1,33 @@
+// m2v_decode_state.hpp — what the two translation units of m2v_decode_device share: the call's state and picture table on the device
+// (m2v_decode.hip: the module syntax and everything syntax-blind) and the launchers of the main syntax's three kernels
+// (m2v_decode_main.hip).  The kernels of one unit are not touched by a change in the other.
+#pragma once
+#include "m2v_host.hpp"
+#include "m2v_decode_kernels.hpp"
+
+namespace m2v {
+
+constexpr int kDecThreads = 256;
+
+struct DecState {
+    unsigned long long err, last_nz;               // the earliest error's offset (dec::kNone: none); one past the last byte that is not zero
+    uint32_t nev, ev_cap;
+    int32_t status;
+    uint32_t npics, gops, reps, chains, width, height, mbw, mbh, pad;
+    unsigned long long frame_bytes;
+};
+struct DecPic { uint32_t ev, type, chain, step; };
+
+// the main syntax's share of the call's state (e->d_dec_main): the two matrices, raster order, then one entry per picture
+constexpr size_t kDecMainMatrices = 128;
+struct DecMainPic { uint32_t slice0, params; };    // the event of the picture's first slice; dec::params_pack of its coding extension
+
+// m2v_decode_main.hip: the main-syntax variants of k_dec_plan, k_dec_slices and k_dec_recon, launched where decode_impl launches those
+void dec_main_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long long *ev, DecState *st, DecPic *pics, uint32_t pic_cap, uint8_t *h_types,
+                   unsigned long long cap, int probe, m2v_decode_stat *h_rec, uint8_t *d_main);
+void dec_main_slices(hipStream_t s, unsigned blocks, const uint8_t *es, size_t n, const unsigned long long *ev, DecState *st, const DecPic *pics, const uint8_t *d_main,
+                     uint32_t p0, uint32_t np, dec::MbRec *mb, int32_t *dc, int16_t *lv);
+void dec_main_recon(hipStream_t s, unsigned mbs, unsigned count, const DecState *st, const uint32_t *list, uint32_t p0, const uint8_t *d_main, const dec::MbRec *mb,
+                    const int32_t *dc, const int16_t *lv, uint8_t *buf, size_t psz);
+
+}  // namespace m2v

@@ -558,6 +558,10 @@ int m2v_decode_streams_device(m2v_enc *e, const void *d_es, const uint64_t *es_o
     if (!layout420_ok(layout)) { e->set_err("m2v_decode_streams_device: unknown layout %d", layout); return M2V_E_PARAM; }
     if (mode != M2V_DEC_ISO && mode != M2V_DEC_MODULE) { e->set_err("m2v_decode_streams_device: unknown mode %d", mode); return M2V_E_PARAM; }
     if (!d_es) for (size_t b = 0; b < nstreams; ++b) if (es_bytes[b]) { e->set_err("m2v_decode_streams_device: d_es is NULL"); return M2V_E_PARAM; }
+    if (e->decode_syntax == M2V_SYNTAX_MAIN) {                   // (the batch entry of the main syntax is a follow-up: nothing is touched)
+        e->set_err("m2v_decode_streams_device: \"decode_syntax\" = main is m2v_decode_device's only; set it back to 0 for this entry");
+        return M2V_E_STATE;
+    }
     if (in_progress(e, "m2v_decode_streams_device", "m2v_encode_resident_end first")) return M2V_E_STATE;
     DecodeStreamsArgs a{(const uint8_t *)d_es, es_off, es_bytes, nstreams, (uint8_t *)d_dst, cap, layout, mode, (hipStream_t)hip_stream};
     return guard(e, decode_streams_impl, &a);

@@ -409,6 +409,8 @@ struct m2v_enc {
     DevBuf<int16_t> d_dec_lv;
     uint8_t *h_dec = nullptr;
     size_t h_dec_cap = 0;
+    DevBuf<uint8_t> d_dec_main;           // the main syntax's share of the state (m2v_decode_state.hpp): the matrices and the pictures' parameters
+    int decode_syntax = 0;                // option "decode_syntax": M2V_SYNTAX_MODULE / M2V_SYNTAX_MAIN
     size_t decode_batch = 0;              // option "decode_batch": pictures per chunk (0: as many as keep the levels within 256 MiB, 256 at most)
     m2v_decode_stat dec_rec{};            // the last call's record (m2v_decode_report)
     // several streams per call (m2v_decode_streams.hip): the work buffers above serve it too; its own are the streams' table, the

@@ -282,7 +282,14 @@ def sequence_headers(data):
     return _sequence_headers(BitReader(data))
 
 
-def decode(data, quirks=True):
+def decode(data, quirks=True, syntax="module"):
+    """syntax="module" (the default): the subset this encoder emits, as the head of this file says.  syntax="main": Main-Profile
+    streams of progressive frame pictures, I and P, 4:2:0, from any encoder (decode_main below); it needs quirks=False, and a
+    refusal is a Refused exception that names the unit."""
+    if syntax == "main":
+        assert not quirks, "the module's quirks have no meaning outside its own syntax"
+        return decode_main(data)
+    assert syntax == "module", syntax
     T = tables()
     br = BitReader(data)
     out = Decoded()
@@ -507,3 +514,456 @@ def _predict(plane, x0, y0, mvx, mvy, n, quirks):
 def psnr(a, b):
     mse = np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2)
     return 99.0 if mse == 0 else 10 * np.log10(255.0 ** 2 / mse)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# syntax="main": ordinary Main-Profile streams of progressive frame pictures, I and P, 4:2:0 - what another encoder writes.
+# Beyond the module's syntax: f_code 1 .. 9, intra_dc_precision 0 .. 3, both quantiser scale tables, both scans, matrices loaded in the
+# sequence header, every macroblock type of tables B-2 / B-3, macroblock quantisers, address increments with skipped macroblocks;
+# optional sequence_display_extension, GOP header and sequence_end_code; user_data, copyright_extension and
+# picture_display_extension skipped where 6.2.2.2 allows them; trailing zero bytes.  Still refused: B and D pictures, field pictures,
+# frame_pred_frame_dct 0, concealment vectors, intra_vlc_format 1, quant_matrix_extension, scalable and size extensions, sizes over
+# 2048, other chroma formats, several slices in a row, a first increment other than 1, skipped macroblocks in an I picture or at a row's
+# end, an increment past the row's end, composite_display_flag 1 (its 20 bits are not read: they fail the zero-stuffing check), a slice
+# with intra_slice_flag 1 (the bit behind quantiser_scale_code), vectors that read outside the picture.
+#
+# The stream is cut at its start codes first (a start code prefix is unique in a stream: 6.2.1), the units are judged by the grammar
+# of 6.2.2 - each by what it is and by the unit in front of it that is not skipped -, and then the pictures are decoded.  A refusal
+# names the unit: Refused.offset is the earliest unit the grammar refuses, or else the earliest slice that cannot be read.  The
+# arithmetic is the quirks=False one above - the intra DC relative to its reset value with a prediction of 128 (intra_dc_mult times
+# the reset value is 1024 at every precision), Chen-Wang, saturation, mismatch control - so every stream decode(quirks=False) accepts
+# decodes to the same frames here.
+# ---------------------------------------------------------------------------------------------------------------
+class Refused(Exception):
+    def __init__(self, offset, why=""):
+        Exception.__init__(self, "unit at byte %d: %s" % (offset, why))
+        self.offset = offset
+
+
+_B1_INCREMENT = """1:1 2:011 3:010 4:0011 5:0010 6:00011 7:00010 8:0000111 9:0000110 10:00001011 11:00001010 12:00001001 13:00001000
+14:00000111 15:00000110 16:0000010111 17:0000010110 18:0000010101 19:0000010100 20:0000010011 21:0000010010 22:00000100011
+23:00000100010 24:00000100001 25:00000100000 26:00000011111 27:00000011110 28:00000011101 29:00000011100 30:00000011011
+31:00000011010 32:00000011001 33:00000011000"""
+_B1_ESCAPE = "00000001000"
+# tables B-2 (I pictures) and B-3 (P pictures): code -> (macroblock_quant, macroblock_motion_forward, macroblock_pattern, macroblock_intra)
+_B2_TYPE_I = {"1": (0, 0, 0, 1), "01": (1, 0, 0, 1)}
+_B3_TYPE_P = {"1": (0, 1, 1, 0), "01": (0, 0, 1, 0), "001": (0, 1, 0, 0), "00011": (0, 0, 0, 1), "00010": (1, 1, 1, 0), "00001": (1, 0, 1, 0),
+              "000001": (1, 0, 0, 1)}
+# table 7-6, q_scale_type 1: quantiser_scale of quantiser_scale_code 1 .. 31 (code 0 is forbidden; a slice that carries it gets 0, as
+# with q_scale_type 0)
+_NONLINEAR_SCALE = [0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 18, 20, 22, 24, 28, 32, 36, 40, 44, 48, 52, 56, 64, 72, 80, 88, 96, 104, 112]
+# 7.3 figure 7-3: alternate scan, scan position of raster [v][u]
+_ALTERNATE = [0, 4, 6, 20, 22, 36, 38, 52, 1, 5, 7, 21, 23, 37, 39, 53, 2, 8, 19, 24, 34, 40, 50, 54, 3, 9, 18, 25, 35, 41, 51, 55,
+              10, 17, 26, 30, 42, 46, 56, 60, 11, 16, 27, 31, 43, 47, 57, 61, 12, 15, 28, 32, 44, 48, 58, 62, 13, 14, 29, 33, 45, 49, 59, 63]
+MAIN_MAX_SIZE = 2048
+
+
+def main_tables():
+    """the raw tables of the main syntax, for tests: B-1 as (code, length, increment), the scale table, the alternate scan"""
+    return dict(increment=_parse(_B1_INCREMENT), escape=_B1_ESCAPE, nonlinear=list(_NONLINEAR_SCALE), alternate=list(_ALTERNATE),
+                type_i=dict(_B2_TYPE_I), type_p=dict(_B3_TYPE_P))
+
+
+_TM = None
+
+
+def _main_tables():
+    global _TM
+    if _TM is None:
+        esc = (int(_B1_ESCAPE, 2), len(_B1_ESCAPE), "ESC")
+        alt = np.zeros(64, np.int64)
+        for raster, pos in enumerate(_ALTERNATE):
+            alt[pos] = raster
+        types = lambda t: _vlc_decoder([(int(bits, 2), len(bits), flags) for bits, flags in t.items()])
+        _TM = dict(incr=_vlc_decoder(_parse(_B1_INCREMENT) + [esc]), type_i=types(_B2_TYPE_I), type_p=types(_B3_TYPE_P), alt=alt)
+    return _TM
+
+
+class _UnitBits(BitReader):
+    """the bits of one unit: from behind its start code to where the next one begins; nothing is read beyond"""
+    def __init__(self, data, start, end):
+        BitReader.__init__(self, data)
+        self.pos, self.end = 8 * (start + 4), 8 * end
+
+    def bits(self, n):
+        if self.pos + n > self.end:
+            raise ValueError("the unit ends at bit %d" % self.end)
+        return BitReader.bits(self, n)
+
+    def rest_is_zero(self):
+        pad = (-self.pos) & 7
+        return (self.bits(pad) == 0 if pad else True) and not any(self.d[self.pos >> 3:self.end >> 3])
+
+
+def start_codes(data):
+    """[(offset, code)] of every 00 00 01 xx whose code byte lies inside the stream"""
+    out, at = [], data.find(b"\x00\x00\x01")
+    while at >= 0 and at + 3 < len(data):
+        out.append((at, data[at + 3]))
+        at = data.find(b"\x00\x00\x01", at + 3)
+    return out
+
+
+def _main_sequence_header(data, start, end):
+    br = _UnitBits(data, start, end)
+    h = dict(width=br.bits(12), height=br.bits(12), aspect=br.bits(4), frame_rate_code=br.bits(4), bit_rate=br.bits(18))
+    assert br.bits(1) == 1
+    h.update(vbv=br.bits(10), constrained=br.bits(1))
+    zz = tables()["zz"]
+    for name, default in (("intra_matrix", _INTRA_W), ("non_intra_matrix", [16] * 64)):
+        w = list(default)
+        if br.bits(1):                                          # load_..._quantiser_matrix: 64 bytes in zig-zag order (6.3.11)
+            for k in range(64):
+                w[int(zz[k])] = br.bits(8)
+                assert w[int(zz[k])] != 0, "a matrix weight of 0 is forbidden"
+        h[name] = w
+    assert br.rest_is_zero()
+    return h
+
+
+def _main_sequence_extension(data, start, end, h):
+    br = _UnitBits(data, start, end)
+    assert br.bits(4) == 1
+    h.update(profile_level=br.bits(8), progressive_sequence=br.bits(1), chroma_format=br.bits(2))
+    assert br.bits(2) == 0 and br.bits(2) == 0, "size extensions"
+    h["bit_rate"] |= br.bits(12) << 18
+    assert br.bits(1) == 1
+    h["vbv"] |= br.bits(8) << 10
+    h.update(low_delay=br.bits(1))
+    br.bits(7)
+    assert h["chroma_format"] == 1
+    assert 1 <= h["aspect"] <= 4 and 1 <= h["frame_rate_code"] <= 8 and h["bit_rate"] != 0, "forbidden or reserved value"
+    assert br.rest_is_zero()
+
+
+def _main_display_extension(data, start, end, h):
+    br = _UnitBits(data, start, end)
+    assert br.bits(4) == 2
+    h.update(video_format=br.bits(3), colour_primaries=None, transfer_characteristics=None, matrix_coefficients=None)
+    if br.bits(1):
+        h.update(colour_primaries=br.bits(8), transfer_characteristics=br.bits(8), matrix_coefficients=br.bits(8))
+        assert h["colour_primaries"] and h["transfer_characteristics"] and h["matrix_coefficients"], "0 is forbidden"
+    dw = br.bits(14)
+    assert br.bits(1) == 1
+    h["display_size"] = (dw, br.bits(14))
+    assert br.rest_is_zero()
+
+
+def _main_picture_extension(data, start, end, ptype):
+    br = _UnitBits(data, start, end)
+    assert br.bits(4) == 8
+    pic = dict(f_code=[br.bits(4) for _ in range(4)])
+    pic.update(intra_dc_precision=br.bits(2), picture_structure=br.bits(2), top_field_first=br.bits(1),
+               frame_pred_frame_dct=br.bits(1), concealment_motion_vectors=br.bits(1), q_scale_type=br.bits(1),
+               intra_vlc_format=br.bits(1), alternate_scan=br.bits(1), repeat_first_field=br.bits(1),
+               chroma_420_type=br.bits(1), progressive_frame=br.bits(1), composite_display_flag=br.bits(1))
+    assert pic["picture_structure"] == 3 and pic["frame_pred_frame_dct"] == 1
+    assert pic["concealment_motion_vectors"] == 0 and pic["intra_vlc_format"] == 0
+    for f in pic["f_code"][:2]:                                 # an I picture may carry 15, "not used" (6.3.10)
+        assert 1 <= f <= 9 or (ptype == 1 and f == 15), "f_code"
+    assert br.rest_is_zero()
+    return pic
+
+
+_SEQ, _SEQEXT, _DISP, _GOP, _PIC, _PICEXT, _SLICE, _END, _USER, _SKIPPED_EXT, _BAD = range(11)
+
+
+def _main_role(data, pos, code):
+    if code == 0xB3:
+        return _SEQ
+    if code == 0xB8:
+        return _GOP
+    if code == 0xB7:
+        return _END
+    if code == 0x00:
+        return _PIC
+    if 1 <= code <= 0xAF:
+        return _SLICE
+    if code == 0xB2:
+        return _USER
+    if code == 0xB5 and pos + 4 < len(data):                    # extension_start_code_identifier
+        return {1: _SEQEXT, 2: _DISP, 8: _PICEXT, 4: _SKIPPED_EXT, 7: _SKIPPED_EXT}.get(data[pos + 4] >> 4, _BAD)
+    return _BAD
+
+
+def _main_plan(data):
+    """the grammar over the start codes -> (sequence fields, pictures, gops, repeated headers, number of start codes)"""
+    n = len(data)
+    ev = start_codes(data)
+    if not ev or any(data[:ev[0][0]]):
+        raise Refused(0, "no start code, or something in front of the first")
+    ends = [p for p, _ in ev[1:]] + [n]
+    roles = [_main_role(data, p, c) for p, c in ev]
+    last_nz = len(data.rstrip(b"\x00"))                         # one past the last byte that is not zero
+
+    def group(i):
+        """sequence_header at unit i, sequence_extension behind it, sequence_display_extension behind that and any user_data:
+        -> the fields, or the offset of the first unit that is wrong"""
+        if roles[i] != _SEQ or i + 1 >= len(ev):
+            return ev[i][0]
+        try:
+            h = _main_sequence_header(data, ev[i][0], ends[i])
+        except Exception:
+            return ev[i][0]
+        try:
+            assert roles[i + 1] == _SEQEXT
+            _main_sequence_extension(data, ev[i + 1][0], ends[i + 1], h)
+        except Exception:
+            return ev[i + 1][0]
+        j = i + 2
+        while j < len(ev) and roles[j] == _USER:
+            j += 1
+        h["display"] = False
+        if j < len(ev) and roles[j] == _DISP:
+            try:
+                _main_display_extension(data, ev[j][0], ends[j], h)
+            except Exception:
+                return ev[j][0]
+            h["display"] = True
+        return h
+
+    first = group(0)
+    if not isinstance(first, dict):
+        raise Refused(first, "the sequence header")
+    if not (1 <= first["width"] <= MAIN_MAX_SIZE and 1 <= first["height"] <= MAIN_MAX_SIZE):
+        raise Refused(ev[0][0], "the size")
+    mbh = (first["height"] + 15) // 16
+    bad = []
+    pictures, gops, repeats = [], [], 0
+    prev = None                                                 # the unit in front that is not skipped
+    have_i = False
+    for i, (pos, code) in enumerate(ev):
+        role, end = roles[i], ends[i]
+        prole = roles[prev] if prev is not None else None
+        top = prole in (_SEQEXT, _DISP) or (prole == _SLICE and ev[prev][1] == mbh)
+        ok = True
+        try:
+            if role == _BAD:
+                ok = False
+            elif role == _SEQ:
+                if i:
+                    again = group(i)
+                    if not isinstance(again, dict):
+                        bad.append(again)
+                    else:
+                        ok = top and again == first             # 6.1.1.6: it says what the first one said, matrices included
+                        repeats += 1
+            elif role == _SEQEXT:
+                ok = i > 0 and roles[i - 1] == _SEQ             # (read with its sequence header)
+            elif role == _DISP:
+                ok = prole == _SEQEXT
+                _main_display_extension(data, pos, end, {})
+            elif role == _USER:                                 # extension_and_user_data(0), (1), (2)
+                ok = prole in (_SEQEXT, _DISP, _GOP, _PICEXT)
+            elif role == _SKIPPED_EXT:                          # extension_data(2): copyright_extension, picture_display_extension
+                ok = prole == _PICEXT
+            elif role == _GOP:
+                ok = top
+                br = _UnitBits(data, pos, end)
+                tc = dict(drop=br.bits(1), hours=br.bits(5), minutes=br.bits(6))
+                assert br.bits(1) == 1
+                tc.update(seconds=br.bits(6), pictures=br.bits(6), closed_gop=br.bits(1), broken_link=br.bits(1))
+                assert br.rest_is_zero()
+                gops.append(tc)
+            elif role == _PIC:
+                ok = top or prole == _GOP
+                br = _UnitBits(data, pos, end)
+                pic = dict(temporal_reference=br.bits(10), type=br.bits(3), vbv_delay=br.bits(16), unit=i, slices=[])
+                assert pic["type"] in (1, 2), "B and D pictures"
+                if pic["type"] == 2:
+                    assert br.bits(1) == 0
+                    pic["forward_f_code"] = br.bits(3)
+                assert br.bits(1) == 0                          # extra_bit_picture
+                assert br.rest_is_zero()
+                have_i = have_i or pic["type"] == 1
+                if not have_i:
+                    bad.append(pos)                             # a P picture without a reference
+                pictures.append(pic)
+            elif role == _PICEXT:
+                ok = i > 0 and roles[i - 1] == _PIC
+                ptype = (data[ev[i - 1][0] + 5] >> 3) & 7 if ok and ev[i - 1][0] + 5 < n else 0
+                ext = _main_picture_extension(data, pos, end, ptype)
+                if ok and pictures and pictures[-1]["unit"] == i - 1:
+                    pictures[-1].update(ext)
+            elif role == _SLICE:
+                ok = code <= mbh and (prole == _PICEXT if code == 1 else prole == _SLICE and ev[prev][1] == code - 1)
+                if ok and pictures:
+                    pictures[-1]["slices"].append(i)
+            else:                                               # sequence_end_code: the last one, only zeros behind it
+                ok = top and i + 1 == len(ev) and last_nz <= pos + 4
+        except Exception:
+            ok = False
+        if role not in (_USER, _SKIPPED_EXT, _BAD):
+            prev = i
+        if i + 1 == len(ev) and role != _END and ok:            # no sequence_end_code: the stream ends where a picture does
+            prole = roles[prev] if prev is not None else None
+            ok = prole in (_SEQEXT, _DISP) or (prole == _SLICE and ev[prev][1] == mbh)
+        if not ok:
+            bad.append(pos)
+    if bad:
+        raise Refused(min(bad), "the grammar of the start codes")
+    return first, pictures, gops, repeats, ev, ends
+
+
+def _main_dequant(QF, intra, qscale, W, dc_mult):
+    """7.4.2 with the stream's matrix, saturation (7.4.3) and mismatch control (7.4.4); an intra block's QF[0] is its DC relative to
+    the reset value"""
+    F = np.zeros(64, np.int64)
+    for i in range(64):
+        q = int(QF[i])
+        if intra and i == 0:
+            v = dc_mult * q
+        else:
+            v = 2 * q * int(W[i]) * qscale if intra else (2 * q + (1 if q > 0 else -1 if q < 0 else 0)) * int(W[i]) * qscale
+            v = -((-v) // 32) if v < 0 else v // 32             # toward zero
+        F[i] = v
+    F = np.clip(F, -2048, 2047)
+    if (int(F.sum()) & 1) == 0:
+        F[63] += -1 if F[63] & 1 else 1
+    return F
+
+
+def decode_main(data):
+    data = bytes(data)
+    T, TM = tables(), _main_tables()
+    hdr, pictures, gops, repeats, ev, ends = _main_plan(data)
+    out = Decoded()
+    out.width, out.height, out.sequence, out.gops, out.repeated_headers, out.units = hdr["width"], hdr["height"], hdr, gops, repeats, len(ev)
+    mbw, mbh = (out.width + 15) // 16, (out.height + 15) // 16
+    W, H = 16 * mbw, 16 * mbh
+    cw, ch = (out.width + 1) // 2, (out.height + 1) // 2
+    WI, WN = hdr["intra_matrix"], hdr["non_intra_matrix"]
+    ref = None
+    for pic in pictures:
+        out.pictures.append(pic)
+        scan = TM["alt"] if pic["alternate_scan"] else T["zz"]
+        dc_mult = 8 >> pic["intra_dc_precision"]
+        Y = np.zeros((H, W), np.int64)
+        U = np.zeros((H // 2, W // 2), np.int64)
+        V = np.zeros((H // 2, W // 2), np.int64)
+        mbs, qcodes = [], []
+
+        def predict_into(col, row, mv):
+            cmv = [int(mv[0] / 2), int(mv[1] / 2)]              # toward zero (7.6.3.7)
+            return (_predict(ref[0], 16 * col, 16 * row, mv[0], mv[1], 16, False), _predict(ref[1], 8 * col, 8 * row, cmv[0], cmv[1], 8, False),
+                    _predict(ref[2], 8 * col, 8 * row, cmv[0], cmv[1], 8, False))
+
+        def store(col, row, pred, res):
+            for b in range(6):
+                r = res[b].reshape(8, 8)
+                if b < 4:
+                    oy, ox = 8 * (b >> 1), 8 * (b & 1)
+                    Y[16 * row + oy:16 * row + oy + 8, 16 * col + ox:16 * col + ox + 8] = np.clip(pred[0][oy:oy + 8, ox:ox + 8] + r, 0, 255)
+                else:
+                    (U if b == 4 else V)[8 * row:8 * row + 8, 8 * col:8 * col + 8] = np.clip(pred[b - 3] + r, 0, 255)
+
+        for row, unit in enumerate(pic["slices"]):
+            pos = ev[unit][0]
+            try:
+                br = _UnitBits(data, pos, ends[unit])
+                qcode = br.bits(5)
+                qcodes.append(qcode)
+                assert br.bits(1) == 0                          # extra_bit_slice
+                dc_pred, pmv, col = [0, 0, 0], [0, 0], -1
+                while col < mbw - 1:
+                    incr = 0
+                    while True:                                 # macroblock_escape adds 33 (6.3.16)
+                        sym = TM["incr"](br)
+                        if sym != "ESC":
+                            break
+                        incr += 33
+                        assert col + incr < mbw, "an increment passes the row's end"
+                    incr += sym
+                    assert incr == 1 or col >= 0, "a slice starts at the row's first macroblock"
+                    assert col + incr < mbw, "an increment passes the row's end"
+                    for k in range(1, incr):                    # skipped macroblocks (7.6.6): zero vector, predictors reset
+                        assert pic["type"] == 2, "no macroblock is skipped in an I picture"
+                        dc_pred, pmv = [0, 0, 0], [0, 0]
+                        store(col + k, row, predict_into(col + k, row, (0, 0)), [np.zeros(64, np.int64)] * 6)
+                        mbs.append(dict(intra=False, mc=False, skipped=True, mv=(0, 0), cbp=0, qcode=qcode))
+                    col += incr
+                    quant, mc, pattern, intra = (TM["type_i"] if pic["type"] == 1 else TM["type_p"])(br)
+                    if quant:
+                        qcode = br.bits(5)
+                        assert qcode != 0, "quantiser_scale_code 0 is forbidden"
+                    mv = [0, 0]
+                    if mc:
+                        for t in range(2):                      # 7.6.3.1
+                            r_size = pic["f_code"][t] - 1
+                            f = 1 << r_size
+                            m = T["motion"](br)
+                            if m and br.bits(1):
+                                m = -m
+                            delta = m
+                            if f != 1 and m != 0:
+                                delta = (abs(m) - 1) * f + br.bits(r_size) + 1
+                                delta = -delta if m < 0 else delta
+                            v = pmv[t] + delta
+                            if v < -16 * f:
+                                v += 32 * f
+                            elif v > 16 * f - 1:
+                                v -= 32 * f
+                            pmv[t] = mv[t] = v
+                    else:
+                        pmv = [0, 0]                            # 7.6.3.4: an intra macroblock, or a P picture's without a vector
+                    cbp = 63 if intra else (T["cbp"](br) if pattern else 0)
+                    if intra:
+                        pred = (np.full((16, 16), 128, np.int64), np.full((8, 8), 128, np.int64), np.full((8, 8), 128, np.int64))
+                    else:
+                        dc_pred = [0, 0, 0]                     # 7.2.1
+                        pred = predict_into(col, row, mv)
+                    qscale = _NONLINEAR_SCALE[qcode] if pic["q_scale_type"] else 2 * qcode
+                    res = []
+                    for b in range(6):
+                        r = np.zeros(64, np.int64)
+                        if (cbp >> (5 - b)) & 1:
+                            QF = np.zeros(64, np.int64)
+                            k = 0
+                            comp = 0 if b < 4 else b - 3
+                            if intra:
+                                size = (T["dcy"] if b < 4 else T["dcc"])(br)
+                                diff = 0
+                                if size:
+                                    d = br.bits(size)
+                                    diff = d if d >> (size - 1) else d - (1 << size) + 1
+                                dc_pred[comp] += diff
+                                QF[0] = dc_pred[comp]
+                                k = 1
+                            first = not intra
+                            while True:
+                                if first and br.peek(1) == 1:
+                                    br.bits(1)
+                                    run, lvl = 0, (-1 if br.bits(1) else 1)
+                                else:
+                                    sym = T["ac"](br) if not (br.peek(2) == 0b11) else (br.bits(2), (0, 1))[1]
+                                    if sym == "EOB":
+                                        assert not first, "a coded non-intra block cannot start with EOB"
+                                        break
+                                    if sym == "ESC":
+                                        run = br.bits(6)
+                                        lvl = br.bits(12)
+                                        lvl = lvl - 4096 if lvl & 0x800 else lvl
+                                        assert lvl not in (0, -2048)
+                                    else:
+                                        run, lvl = sym
+                                        lvl = -lvl if br.bits(1) else lvl
+                                first = False
+                                k += run
+                                assert k < 64, "coefficient index beyond 63"
+                                QF[scan[k]] = lvl
+                                k += 1
+                            r = idct(_main_dequant(QF, intra, qscale, WI if intra else WN, dc_mult), False)
+                        res.append(r)
+                    store(col, row, pred, res)
+                    mbs.append(dict(intra=bool(intra), mc=bool(mc), skipped=False, mv=tuple(mv), cbp=cbp, qcode=qcode))
+                assert br.rest_is_zero(), "only zero stuffing may follow the row's last macroblock"
+            except Refused:
+                raise
+            except Exception as e:
+                raise Refused(pos, "slice: %s" % e)
+        ref = (Y, U, V)
+        out.frames.append(tuple(np.ascontiguousarray(p[:r, :c]).astype(np.uint8)
+                                for p, r, c in zip(ref, (out.height, ch, ch), (out.width, cw, cw))))
+        out.mbs.append(mbs)
+        out.slice_qcodes.append(qcodes)
+    return out

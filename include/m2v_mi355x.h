@@ -947,9 +947,37 @@ int m2v_mux_scan_tile(void);
  *
  * Out of scope, and M2V_DEC_SYNTAX by the definition: B pictures, field pictures, f_codes other than 1, skipped macroblocks, quantiser
  * matrices in the stream, intra_vlc_format 1, alternate scan.  Not offered: decode on the port path or in strips.  Several streams per call:
- * m2v_decode_streams_device, below.
+ * m2v_decode_streams_device, below.  That is the MODULE syntax, the default; most of the list is accepted by the main syntax:
+ *
+ * Option "decode_syntax" (m2v_set_option), per handle: M2V_SYNTAX_MODULE (0, the default) - everything above, bit for bit and launch
+ * for launch; M2V_SYNTAX_MAIN (1) - MPEG-2 Main-Profile streams of progressive frame pictures, I and P, 4:2:0, from any encoder.  The
+ * definition is decoder.decode(stream, quirks=False, syntax="main") (decoder.decode_main); every stream that M2V_DEC_ISO accepts in the
+ * module syntax decodes to the same frames and counts in the main syntax.  With it `mode` must be M2V_DEC_ISO (the module's four
+ * deviations belong to its own syntax: M2V_DEC_MODULE is M2V_E_PARAM), and m2v_decode_streams_device returns M2V_E_STATE and touches
+ * nothing.  The record, err_offset (the earliest unit the grammar refuses, else the earliest slice that cannot be read), the layouts,
+ * "decode_batch" and the container path (m2v_demux_device in front) are as above.  Accepted beyond the module syntax:
+ *   stream    sequence_display_extension and the GOP header are optional; repeated sequence headers, each equal to the first with
+ *             its matrices, wherever a GOP or picture header may stand; user_data behind sequence_extension, GOP header and
+ *             picture_coding_extension, copyright_extension and picture_display_extension behind picture_coding_extension - skipped;
+ *             sequence_end_code may be missing, zero bytes may follow the last unit, the length need not be a multiple of 32 (a last
+ *             picture with fewer slices than macroblock rows is refused); progressive_sequence may be anything
+ *   picture   f_code[0][0] and [0][1] 1 .. 9 (15 in an I picture) with motion_residual and the wrap of 7.6.3.1; intra_dc_precision
+ *             0 .. 3; q_scale_type 0 or 1 (table 7-6); alternate_scan 0 or 1 - each may change from picture to picture;
+ *             picture_structure 3 and frame_pred_frame_dct 1 are required
+ *   sequence  load_intra_quantiser_matrix / load_non_intra_quantiser_matrix: 64 bytes each, zig-zag order, 0 forbidden
+ *   macroblock  macroblock_address_increment (Table B-1) with macroblock_escape; skipped macroblocks in P pictures (7.6.6); all of
+ *             Tables B-2 and B-3; a macroblock's quantiser_scale_code replaces the slice's (0 is refused)
+ * Still M2V_DEC_SYNTAX in the main syntax, the follow-ups: B and D pictures; field pictures and frame_pred_frame_dct 0; concealment
+ * vectors; intra_vlc_format 1 (Table B-15 has no second source here to be checked against); quant_matrix_extension and every scalable
+ * extension; size extensions and sizes over 2048; chroma formats other than 4:2:0; more than one slice in a macroblock row, or a slice
+ * whose first increment is not 1; a skipped macroblock in an I picture or as the last of a row; an increment that passes the row's
+ * end; composite_display_flag 1 (its 20 bits behind the picture_coding_extension's flags are read as stuffing that is not zero);
+ * a slice with intra_slice_flag 1 (the bit behind quantiser_scale_code: intra_slice, reserved bits and extra information are not
+ * read) - ordinary encoders may write either; vectors that read outside the picture; and every check the module syntax makes on
+ * codes, coefficient indices and stuffing inside a slice.  Also a follow-up: the batch entry (m2v_decode_streams_device) for the main syntax.
  */
 enum { M2V_DEC_ISO = 0, M2V_DEC_MODULE = 1 };
+enum { M2V_SYNTAX_MODULE = 0, M2V_SYNTAX_MAIN = 1 };                            /* option "decode_syntax" */
 enum { M2V_DEC_OK = 0, M2V_DEC_SYNTAX = -2, M2V_DEC_OVERFLOW = -3 };
 typedef struct { uint64_t es_bytes, out_bytes, frame_bytes, err_offset;
                  uint32_t pictures, gops, width, height, repeated_headers, chains;

@@ -1,0 +1,145 @@
+// dec_main_host.hpp — the main syntax of the device decoder (the main_ functions of csrc/m2v_decode_kernels.hpp) run serially on a CPU,
+// as tools/dec_host.hpp runs the module's: scan, judge every event against the significant one in front of it, walk every slice,
+// reconstruct every macroblock, locate every output byte - in the order of decisions of m2v_decode_main.hip.  Plain C++; used by
+// tests/main_cases.py (as a shared library) and tools/dec_main_host_check.cpp (under the sanitizers).
+#pragma once
+#include "dec_host.hpp"
+
+namespace dec_main_host {
+using namespace m2v::dec;
+using dec_host::Record;
+
+struct Sink {
+    std::vector<MainMb> *mb_;
+    std::vector<int32_t> *dc_;
+    std::vector<int16_t> *lv_;
+    size_t base;                                             // the slice's first macroblock
+    void mb(int col, const MainMb &m, const int32_t (&dc)[6])
+    {
+        (*mb_)[base + col] = m;
+        for (int k = 0; k < 6; ++k) (*dc_)[(base + col) * 6 + k] = dc[k];
+    }
+    void level(int col, int blk, uint32_t i, int32_t l) { (*lv_)[((base + col) * 6 + blk) * 64 + i] = (int16_t)l; }
+};
+
+// the residual of one block (zero where it is not coded)
+inline void block_residual(const MainMb &m, const int32_t *dc, const int16_t *lv, int blk, const MainSeq &seq, const PicParams &pp, int32_t (&res)[64])
+{
+    for (int i = 0; i < 64; ++i) res[i] = 0;
+    if (!((m.cbp >> (5 - blk)) & 1)) return;
+    const int32_t qscale = main_scale(m.qcode, pp.qst);
+    int32_t sum = 0;
+    for (uint32_t i = 0; i < 64; ++i) {
+        res[i] = m.intra && i == 0 ? main_dequant_dc(dc[blk], pp.prec) : main_dequant(lv[blk * 64 + i], m.intra ? seq.wi[i] : seq.wn[i], m.intra != 0, qscale);
+        sum ^= res[i];
+    }
+    if (!(sum & 1)) res[63] = mismatch(res[63]);
+    for (int r = 0; r < 8; ++r) {
+        int32_t a[8];
+        for (int k = 0; k < 8; ++k) a[k] = res[r * 8 + k];
+        idct_1d(a, true, kIso);
+        for (int k = 0; k < 8; ++k) res[r * 8 + k] = a[k];
+    }
+    for (int c = 0; c < 8; ++c) {
+        int32_t a[8];
+        for (int k = 0; k < 8; ++k) a[k] = res[k * 8 + c];
+        idct_1d(a, false, kIso);
+        for (int k = 0; k < 8; ++k) res[k * 8 + c] = a[k];
+    }
+}
+
+struct Pic { uint32_t ev, type, slice0, params; };
+
+inline Record decode(const uint8_t *es, uint64_t n, int layout, uint64_t cap, std::vector<uint8_t> &out)
+{
+    out.clear();
+    Record R{};
+    R.es_bytes = n;
+    auto refuse = [&](uint64_t at) { R.status = kSyntax; R.err_offset = at; R.out_bytes = 0; out.clear(); return R; };
+    if (n < 4) return refuse(0);                             // not one start code
+    std::vector<uint64_t> ev;
+    uint64_t last_nz = 0;
+    for (uint64_t p0 = 0; p0 < n; p0 += 16) {
+        uint64_t w0, w1, w2;
+        m2v::mux::load24(es, p0, n, w0, w1, w2);
+        uint32_t cand = scan16(p0, n, w0, w1, w2, last_nz);
+        while (cand) {
+            const uint32_t j = (uint32_t)__builtin_ctz(cand);
+            cand &= cand - 1u;
+            ev.push_back((p0 + j) << 8 | m2v::mux::byte24(w0, w1, w2, j + 3));
+        }
+    }
+    const uint32_t nev = (uint32_t)ev.size();
+    MainPlan P{};
+    uint64_t bad = main_first(es, n, ev.data(), nev, P);
+    if (bad != kNone) return refuse(bad);
+    std::vector<Pic> pics;
+    long lastI = -1;
+    int prev = -1;
+    for (uint32_t i = 0; i < nev; ++i) {
+        const EvInfo f = main_event(es, n, ev.data(), nev, i, P, last_nz, prev);
+        if (main_significant(main_role(es, n, ev[i]))) prev = (int)i;
+        bad = min64(bad, f.bad);
+        R.gops += f.gop; R.repeated_headers += f.rep;
+        if (f.pic) {
+            if (f.type == 1) { lastI = (long)pics.size(); ++R.chains; }
+            if (lastI < 0) bad = min64(bad, ev_pos(ev[i]));            // a P picture without a reference
+            Pic p{i, f.type, 0, 0};
+            p.params = main_picture_params(es, n, ev.data(), nev, i, p.slice0);
+            pics.push_back(p);
+        }
+    }
+    if (bad != kNone) return refuse(bad);
+    const SeqHdr &h = P.seq.h;
+    R.width = h.width; R.height = h.height; R.pictures = (uint32_t)pics.size();
+    R.frame_bytes = frame_bytes(R.width, R.height);
+    const uint32_t W = 16 * P.mbw, H = 16 * P.mbh, mbs = P.mbw * P.mbh;
+    if (R.frame_bytes * pics.size() > cap) { R.status = kOverflow; return R; }
+    std::vector<MainMb> mb(mbs);
+    std::vector<int32_t> dc((size_t)mbs * 6);
+    std::vector<int16_t> lv((size_t)mbs * 384);
+    const size_t psz = (size_t)W * H * 3 / 2;
+    std::vector<uint8_t> cur(psz), ref(psz);
+    out.resize(R.frame_bytes * pics.size());
+    for (size_t p = 0; p < pics.size(); ++p) {
+        std::fill(lv.begin(), lv.end(), 0);
+        const PicParams pp = params_unpack(pics[p].params);
+        for (uint32_t row = 0; row < P.mbh; ++row) {
+            const uint32_t i = pics[p].slice0 + row;
+            Sink sink{&mb, &dc, &lv, (size_t)row * P.mbw};
+            if (!main_slice(es, ev_pos(ev[i]), i + 1 < nev ? ev_pos(ev[i + 1]) : n, pics[p].type, pp, (int)P.mbw, (int)P.mbh, (int)row, sink))
+                bad = min64(bad, ev_pos(ev[i]));
+        }
+        if (bad != kNone) continue;                          // (the other pictures' slices are still walked: the earliest error is reported)
+        for (uint32_t k = 0; k < mbs; ++k) {
+            const MainMb &m = mb[k];
+            const int col = (int)(k % P.mbw), row = (int)(k / P.mbw);
+            for (int blk = 0; blk < 6; ++blk) {
+                int32_t res[64];
+                block_residual(m, &dc[(size_t)k * 6], &lv[(size_t)k * 384], blk, P.seq, pp, res);
+                const bool luma = blk < 4;
+                const int pw = luma ? (int)W : (int)W / 2;
+                const size_t plane = luma ? 0 : (size_t)W * H + (size_t)(blk - 4) * (W / 2) * (H / 2);
+                const int x0 = luma ? 16 * col + 8 * (blk & 1) : 8 * col, y0 = luma ? 16 * row + 8 * (blk >> 1) : 8 * row;
+                const int mvx = luma ? m.mvx : chroma_vector(m.mvx, kIso), mvy = luma ? m.mvy : chroma_vector(m.mvy, kIso);
+                for (int y = 0; y < 8; ++y)
+                    for (int x = 0; x < 8; ++x) {
+                        const int32_t pred = m.intra ? 128 : predict(ref.data() + plane, pw, x0 + x + (mvx >> 1), y0 + y + (mvy >> 1), mvx & 1, mvy & 1, kIso);
+                        cur[plane + (size_t)(y0 + y) * pw + x0 + x] = clip255(pred + res[y * 8 + x]);
+                    }
+            }
+        }
+        uint8_t *o = out.data() + p * R.frame_bytes;
+        OutAt at{0, 0, 0, 0};
+        for (uint32_t q = 0; q < (uint32_t)R.frame_bytes; ++q) {
+            if (at.run > 1) out_step(at, layout); else at = out_locate(q, h.width, h.height, layout);
+            o[q] = pic_sample(cur.data(), W, H, at);
+        }
+        cur.swap(ref);
+    }
+    if (bad != kNone) return refuse(bad);
+    R.out_bytes = out.size();
+    return R;
+}
+
+}  // namespace dec_main_host
