@@ -34,6 +34,8 @@
 //
 // Option "decode_syntax" = M2V_SYNTAX_MAIN puts the main-syntax variants of k_dec_plan, k_dec_slices and k_dec_recon in their places
 // (m2v_decode_main.hip, a translation unit of its own: the three kernels here are what they were); the rest of the call is shared.
+// Option "decode_b_pictures" = 1 on top of that: B pictures, frames in display order.  The scan stays; the plan and everything behind
+// its wait are m2v_decode_b.hip's (dec_b_plan, dec_b_chunks), again a translation unit of its own.
 #include "m2v_decode_state.hpp"
 
 static_assert(sizeof(m2v_decode_stat) == 72, "the record of include/m2v_mi355x.h is 72 bytes");
@@ -379,6 +381,7 @@ static int decode_impl(m2v_enc *e, void *argp)
     e->d_dec_st.recorded = e->d_dec_ev.recorded = e->d_dec_pics.recorded = e->d_dec_mb.recorded = e->d_dec_dc.recorded = false;     // (no recorded graph references them)
     e->d_dec_lv.recorded = e->d_dec_buf.recorded = e->d_dec_tiles.recorded = e->d_dec_list.recorded = e->d_dec_main.recorded = false;
     const bool main_syntax = e->decode_syntax == M2V_SYNTAX_MAIN;      // the main-syntax kernels in the places of k_dec_plan, k_dec_slices, k_dec_recon
+    const bool b_pictures = e->decode_b_pictures != 0;                 // m2v_decode_b.hip: its plan, and everything behind the plan's wait
     const size_t ntiles = (n + dec::kScanTile - 1) / dec::kScanTile;
     if (ntiles > 0x7FFFFFFFu) { e->set_err("m2v_decode_device: the stream is longer than 2^31 scan tiles"); return M2V_E_PARAM; }
     size_t ev_cap = std::max<size_t>(1024, n / 16 + 64);              // a guess: a second run takes the count of the first
@@ -406,7 +409,11 @@ static int decode_impl(m2v_enc *e, void *argp)
         HIPCHK(hipGetLastError());
         k_dec_scan<true><<<gx, kDecThreads, 0, s>>>(a->es, n, d_st, e->d_dec_tiles.p, e->d_dec_ev.p);
         HIPCHK(hipGetLastError());
-        if (main_syntax) {
+        if (b_pictures) {
+            e->d_dec_main.ensure(kDecMainMatrices + pic_cap * sizeof(DecBPic));
+            dec_b_plan(s, a->es, n, e->d_dec_ev.p, d_st, (DecPic *)e->d_dec_pics.p, (uint32_t)pic_cap, e->h_dec + rec_off + 128, (unsigned long long)a->cap,
+                       a->dst ? 0 : 1, (m2v_decode_stat *)(e->h_dec + rec_off), e->d_dec_main.p);
+        } else if (main_syntax) {
             e->d_dec_main.ensure(kDecMainMatrices + pic_cap * sizeof(DecMainPic));
             dec_main_plan(s, a->es, n, e->d_dec_ev.p, d_st, (DecPic *)e->d_dec_pics.p, (uint32_t)pic_cap, e->h_dec + rec_off + 128, (unsigned long long)a->cap,
                           a->dst ? 0 : 1, (m2v_decode_stat *)(e->h_dec + rec_off), e->d_dec_main.p);
@@ -428,6 +435,11 @@ static int decode_impl(m2v_enc *e, void *argp)
     const size_t np = R.pictures, mbw = (R.width + 15) / 16, mbh = (R.height + 15) / 16, mbs = mbw * mbh, psz = mbs * 384;
     size_t B = e->decode_batch ? e->decode_batch : std::max<size_t>(1, std::min(kDecBatchMax, kDecLevelBytes / (mbs * 768)));
     B = std::min(B, np);
+    if (b_pictures) {                                                  // chunks of B pictures each, scheduled and run by m2v_decode_b.hip
+        dec_b_chunks(e, s, a->es, n, a->dst, a->layout, R, B, types, (uint32_t *)(e->h_dec + rec_off + 128 + ((pic_cap + 3) & ~(size_t)3)), (m2v_decode_stat *)(e->h_dec + rec_off));
+        R = *h_rec;
+        return M2V_OK;
+    }
     e->d_dec_mb.ensure(B * mbs * sizeof(dec::MbRec));
     e->d_dec_dc.ensure(B * mbs * 6);
     e->d_dec_lv.ensure(B * mbs * 384);
@@ -500,6 +512,10 @@ int m2v_decode_device(m2v_enc *e, const void *d_es, size_t es_bytes, void *d_dst
     if (!layout420_ok(layout)) { e->set_err("m2v_decode_device: unknown layout %d", layout); return M2V_E_PARAM; }
     if (mode != M2V_DEC_ISO && mode != M2V_DEC_MODULE) { e->set_err("m2v_decode_device: unknown mode %d", mode); return M2V_E_PARAM; }
     if (!d_es && es_bytes) { e->set_err("m2v_decode_device: d_es is NULL"); return M2V_E_PARAM; }
+    if (e->decode_b_pictures && (e->decode_syntax != M2V_SYNTAX_MAIN || mode != M2V_DEC_ISO)) {
+        e->set_err("m2v_decode_device: \"decode_b_pictures\" = 1 needs \"decode_syntax\" = main and the mode M2V_DEC_ISO");
+        return M2V_E_PARAM;
+    }
     if (e->decode_syntax == M2V_SYNTAX_MAIN && mode != M2V_DEC_ISO) {
         e->set_err("m2v_decode_device: with \"decode_syntax\" = main the mode is M2V_DEC_ISO (the module's deviations belong to its own syntax)");
         return M2V_E_PARAM;

@@ -1089,5 +1089,262 @@ M2V_HD inline int32_t main_dequant_dc(int32_t dc, uint32_t prec)
     return main_saturate((int32_t)((uint32_t)dc << (3u - (prec & 3u))));
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// B pictures (option "decode_b_pictures" on top of the main syntax; decoder.decode_main(b_pictures=True) is the definition).  The
+// main_ functions above keep their signatures and their meaning; these stand beside them: a picture header and coding extension that
+// know picture_coding_type 3, Table B-4, two vector predictors, a record with both vectors and the directions, the mean of two
+// predictions.  An I or P picture goes through main_slice as before and leaves the same kind of record (directions: forward).
+// ---------------------------------------------------------------------------------------------------------------------------
+enum { kFwd = 1, kBwd = 2 };                                     // the directions of a macroblock's prediction
+
+M2V_HD inline bool bp_picture_header(const uint8_t *es, uint64_t start, uint64_t end, uint32_t &type)
+{
+    Bits b = unit_bits(es, start, end);
+    skip(b, 10);
+    type = get(b, 3);
+    skip(b, 16);
+    bool ok = type >= 1 && type <= 3;                        // D pictures stay refused
+    if (type == 2 || type == 3) { ok = ok && get(b, 1) == 0; skip(b, 3); }     // full_pel_forward_vector, forward_f_code
+    if (type == 3) { ok = ok && get(b, 1) == 0; skip(b, 3); }                  // full_pel_backward_vector, backward_f_code
+    ok = ok && get(b, 1) == 0;                               // extra_bit_picture
+    return ok && !b.err && tail_zero(b);
+}
+
+// the picture's parameters with the backward f_codes, f_code[1][0] and [1][1]; packed above params_pack's twelve bits
+struct BPicParams { PicParams p; uint32_t bh, bv; };
+
+M2V_HD inline uint32_t bp_params_pack(const BPicParams &q) { return params_pack(q.p) | q.bh << 12 | q.bv << 16; }
+M2V_HD inline BPicParams bp_params_unpack(uint32_t v) { return BPicParams{params_unpack(v), (v >> 12) & 15u, (v >> 16) & 15u}; }
+
+M2V_HD inline bool bp_picture_extension(const uint8_t *es, uint64_t start, uint64_t end, uint32_t ptype, BPicParams &q)
+{
+    Bits b = unit_bits(es, start, end);
+    bool ok = get(b, 4) == 8;
+    q.p.fh = get(b, 4); q.p.fv = get(b, 4);
+    q.bh = get(b, 4); q.bv = get(b, 4);
+    q.p.prec = get(b, 2);
+    ok = ok && get(b, 2) == 3;                               // frame picture
+    skip(b, 1);                                              // top_field_first
+    ok = ok && get(b, 1) == 1;                               // frame_pred_frame_dct
+    ok = ok && get(b, 1) == 0;                               // concealment_motion_vectors
+    q.p.qst = get(b, 1);
+    ok = ok && get(b, 1) == 0;                               // intra_vlc_format
+    q.p.alt = get(b, 1);
+    skip(b, 4);                                              // repeat_first_field, chroma_420_type, progressive_frame, composite_display_flag
+    ok = ok && main_fcode_ok(q.p.fh, ptype) && main_fcode_ok(q.p.fv, ptype);
+    if (ptype == 3) ok = ok && q.bh >= 1 && q.bh <= 9 && q.bv >= 1 && q.bv <= 9;      // (an I or P picture's backward pair is not judged)
+    return ok && !b.err && tail_zero(b);
+}
+
+// event i by its own rule, as main_event: a picture header may be a B picture's, and its coding extension is judged as one
+M2V_HD inline EvInfo bp_event(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, uint32_t i, const MainPlan &P, uint64_t last_nz, int prev)
+{
+    const int role = main_role(es, n, ev[i]);
+    if (role != rPic && role != rPicExt) return main_event(es, n, ev, nev, i, P, last_nz, prev);
+    EvInfo r{kNone, 0, 0, 0, 0};
+    const uint64_t pos = ev_pos(ev[i]), end = i + 1 < nev ? ev_pos(ev[i + 1]) : n;
+    bool ok;
+    if (role == rPic) {
+        const int prole = prev >= 0 ? main_role(es, n, ev[prev]) : rBad;
+        const bool good = bp_picture_header(es, pos, end, r.type);
+        ok = (main_top(es, n, ev, prev, P.mbh) || prole == rGop) && good;
+        r.pic = good;
+    } else {
+        BPicParams q;
+        const int before = i ? main_role(es, n, ev[i - 1]) : rBad;
+        const uint64_t pp = i ? ev_pos(ev[i - 1]) : 0;
+        const uint32_t ptype = before == rPic && pp + 5 < n ? (es[pp + 5] >> 3) & 7u : 0u;
+        ok = before == rPic && bp_picture_extension(es, pos, end, ptype, q);
+    }
+    if (i + 1 == nev) ok = false;                            // no stream ends behind a picture header or its extension
+    if (!ok) r.bad = pos;
+    return r;
+}
+
+M2V_HD inline uint32_t bp_picture_params(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, uint32_t i, uint32_t &slice0)
+{
+    BPicParams q{PicParams{1, 1, 0, 0, 0}, 1, 1};
+    uint32_t j = i + 2;
+    if (i + 1 < nev) {
+        const uint64_t pos = ev_pos(ev[i]);
+        (void)bp_picture_extension(es, ev_pos(ev[i + 1]), i + 2 < nev ? ev_pos(ev[i + 2]) : n, pos + 5 < n ? (es[pos + 5] >> 3) & 7u : 0u, q);
+    }
+    while (j < nev && !main_significant(main_role(es, n, ev[j]))) ++j;
+    slice0 = j;
+    return bp_params_pack(q);
+}
+
+// the display index of an anchor at coded index p whose next anchor is at coded index next (the number of pictures where there is
+// none), and of a B picture at p
+M2V_HD inline uint32_t bp_display_anchor(uint32_t next) { return next - 1u; }
+M2V_HD inline uint32_t bp_display_b(uint32_t p) { return p - 1u; }
+
+// ---- macroblock layer ----
+// MainMb with the backward vector and the directions in its reserved bytes; mc = the forward direction, as there
+struct BMb { uint8_t intra, mc, cbp, qcode; int16_t mvx, mvy; uint8_t skipped, dirs; int16_t bvx, bvy; uint8_t reserved[2]; };
+
+// Table B-4 over the next 6 bits: length | flags << 8, flags = quant << 4 | forward << 3 | backward << 2 | pattern << 1 | intra; 0 where
+// no code begins the window
+M2V_HD inline uint32_t vlc_type_b(uint32_t w6)
+{
+    if ((w6 >> 4) == 2u) return 2u | 0x0Cu << 8;             // '10'     forward, backward
+    if ((w6 >> 4) == 3u) return 2u | 0x0Eu << 8;             // '11'     forward, backward, coded
+    if ((w6 >> 3) == 2u) return 3u | 0x04u << 8;             // '010'    backward
+    if ((w6 >> 3) == 3u) return 3u | 0x06u << 8;             // '011'    backward, coded
+    if ((w6 >> 2) == 2u) return 4u | 0x08u << 8;             // '0010'   forward
+    if ((w6 >> 2) == 3u) return 4u | 0x0Au << 8;             // '0011'   forward, coded
+    if ((w6 >> 1) == 3u) return 5u | 0x01u << 8;             // '00011'  intra
+    if ((w6 >> 1) == 2u) return 5u | 0x1Eu << 8;             // '00010'  forward, backward, coded, quant
+    if (w6 == 3u) return 6u | 0x1Au << 8;                    // '000011' forward, coded, quant
+    if (w6 == 2u) return 6u | 0x16u << 8;                    // '000010' backward, coded, quant
+    if (w6 == 1u) return 6u | 0x11u << 8;                    // '000001' intra, quant
+    return 0u;
+}
+
+// one vector component behind its predictor (7.6.3.1): motion_code, sign, motion_residual of r_size bits; false = refused
+M2V_HD inline bool bp_component(Bits &b, int32_t &pmv, int r_size)
+{
+    const uint32_t e = vlc_motion(peek(b, 32));
+    if (!e || r_size < 0 || r_size > 8) return false;
+    skip(b, (int)(e & 255u));
+    int32_t code = (int32_t)(e >> 8);
+    if (code && get(b, 1)) code = -code;
+    const int32_t residual = code && r_size ? (int32_t)get(b, r_size) : 0;
+    pmv = main_vector(pmv, code, residual, r_size);
+    return true;
+}
+
+// the vectors a record uses read inside the picture
+M2V_HD inline bool bp_inside(int col, int row, const BMb &m, int mbw, int mbh)
+{
+    return (!(m.dirs & kFwd) || vector_inside(col, row, m.mvx, m.mvy, mbw, mbh, kIso)) &&
+           (!(m.dirs & kBwd) || vector_inside(col, row, m.bvx, m.bvy, mbw, mbh, kIso));
+}
+
+// a record's vectors from the predictors of the directions it uses: s.pmv is PMV[0][0] (forward), bpmv PMV[0][1] (backward)
+M2V_HD inline void bp_vectors(BMb &m, uint32_t dirs, const SliceState &s, const int32_t (&bpmv)[2])
+{
+    m.dirs = (uint8_t)dirs; m.mc = (dirs & kFwd) != 0;
+    if (dirs & kFwd) { m.mvx = (int16_t)s.pmv[0]; m.mvy = (int16_t)s.pmv[1]; }
+    if (dirs & kBwd) { m.bvx = (int16_t)bpmv[0]; m.bvy = (int16_t)bpmv[1]; }
+}
+
+// one macroblock of a B picture behind its address increment; false = refused
+template <class Put>
+M2V_HD inline bool bp_macroblock(Bits &b, const BPicParams &pp, SliceState &s, int32_t (&bpmv)[2], uint32_t &qcode, BMb &m, int32_t (&dc)[6], Put put)
+{
+    const uint32_t e = vlc_type_b(peek(b, 6));
+    if (!e) return false;
+    skip(b, (int)(e & 255u));
+    const uint32_t flags = e >> 8;
+    const bool intra = (flags & 1u) != 0, pattern = ((flags >> 1) & 1u) != 0;
+    const uint32_t dirs = (((flags >> 3) & 1u) ? (uint32_t)kFwd : 0u) | (((flags >> 2) & 1u) ? (uint32_t)kBwd : 0u);
+    if (flags >> 4) {
+        qcode = get(b, 5);
+        if (!qcode) return false;
+    }
+    if (dirs & kFwd) { if (!bp_component(b, s.pmv[0], (int)pp.p.fh - 1) || !bp_component(b, s.pmv[1], (int)pp.p.fv - 1)) return false; }
+    if (dirs & kBwd) { if (!bp_component(b, bpmv[0], (int)pp.bh - 1) || !bp_component(b, bpmv[1], (int)pp.bv - 1)) return false; }
+    if (intra) { s.pmv[0] = s.pmv[1] = 0; bpmv[0] = bpmv[1] = 0; }      // 7.6.3.4; a direction that is not used keeps its predictor
+    uint32_t cbp = intra ? 63u : 0u;
+    if (pattern) {
+        const uint32_t c = vlc_cbp(peek(b, 32));
+        if (!c) return false;
+        skip(b, (int)(c & 255u));
+        cbp = c >> 8;
+    }
+    if (!intra) { for (int c = 0; c < 3; ++c) s.dc_pred[c] = 0; }       // 7.2.1
+    m = BMb{};
+    m.intra = intra; m.cbp = (uint8_t)cbp;
+    bp_vectors(m, dirs, s, bpmv);
+    for (int blk = 0; blk < 6; ++blk) {
+        dc[blk] = 0;
+        if (!((cbp >> (5 - blk)) & 1u)) continue;
+        if (!parse_block(b, intra, blk < 4 ? 0 : blk - 3, s, dc[blk],
+                         [&](uint32_t i, int32_t l) { put(blk, pp.p.alt ? alternate_to_raster(zigzag_position(i)) : i, l); })) return false;
+    }
+    return !b.err;
+}
+
+// main_slice's records as BMb: what is not intra predicts forward (a skipped or No-MC macroblock with the zero vector)
+template <class Sink>
+struct BpAnchorSink {
+    Sink &s;
+    M2V_HD void mb(int col, const MainMb &m, const int32_t (&dc)[6])
+    {
+        BMb r{};
+        r.intra = m.intra; r.mc = m.mc; r.cbp = m.cbp; r.qcode = m.qcode; r.mvx = m.mvx; r.mvy = m.mvy; r.skipped = m.skipped;
+        r.dirs = m.intra ? 0 : (uint8_t)kFwd;
+        s.mb(col, r, dc);
+    }
+    M2V_HD void level(int col, int blk, uint32_t i, int32_t l) { s.level(col, blk, i, l); }
+};
+
+// the slice of macroblock row `row` of a picture of any type through sink.mb(col, BMb, dc) and sink.level: an I or P picture's by
+// main_slice, a B picture's here - Table B-4, two predictors, skipped macroblocks that take the directions and vectors in front of
+// them (never behind an intra macroblock), every vector of either direction inside the picture.  Bounded as main_slice is
+template <class Sink>
+M2V_HD inline bool bp_slice(const uint8_t *es, uint64_t start, uint64_t end, uint32_t ptype, const BPicParams &pp, int mbw, int mbh, int row, Sink &sink)
+{
+    if (ptype != 3) {
+        BpAnchorSink<Sink> a{sink};
+        return main_slice(es, start, end, ptype, pp.p, mbw, mbh, row, a);
+    }
+    Bits b = unit_bits(es, start, end);
+    uint32_t qcode = get(b, 5);
+    if (get(b, 1) != 0) return false;                        // extra_bit_slice
+    SliceState s{{0, 0, 0}, {0, 0}};
+    int32_t bpmv[2] = {0, 0};
+    uint32_t dirs = 0;                                       // of the macroblock in front; 0: intra
+    int col = -1;
+    while (col < mbw - 1) {
+        int incr = 0;
+        uint32_t e;
+        for (;;) {
+            e = vlc_increment(peek(b, 11));
+            if (!e) return false;
+            skip(b, (int)(e & 255u));
+            if ((e >> 8) != 34u) break;
+            incr += 33;                                      // macroblock_escape
+            if (col + incr >= mbw) return false;
+        }
+        incr += (int)(e >> 8);
+        if ((col < 0 && incr != 1) || col + incr >= mbw || b.err) return false;
+        if (incr > 1) {                                      // 7.6.6: skipped - the directions in front, the predictors as vectors, no residual
+            if (!dirs) return false;
+            BMb z{};
+            z.skipped = 1; z.qcode = (uint8_t)qcode;
+            bp_vectors(z, dirs, s, bpmv);
+            const int32_t none[6] = {0, 0, 0, 0, 0, 0};
+            for (int k = 1; k < incr; ++k) {
+                if (!bp_inside(col + k, row, z, mbw, mbh)) return false;
+                sink.mb(col + k, z, none);
+            }
+            for (int c = 0; c < 3; ++c) s.dc_pred[c] = 0;
+        }
+        col += incr;
+        BMb m;
+        int32_t dc[6];
+        if (!bp_macroblock(b, pp, s, bpmv, qcode, m, dc, [&](int blk, uint32_t i, int32_t l) { sink.level(col, blk, i, l); })) return false;
+        if (!bp_inside(col, row, m, mbw, mbh)) return false;
+        m.qcode = (uint8_t)qcode;
+        dirs = m.dirs;
+        sink.mb(col, m, dc);
+    }
+    return !b.err && tail_zero(b);
+}
+
+// 7.6.7.1: the mean of the forward and the backward prediction, each rounded on its own before
+M2V_HD inline int32_t bp_mean(int32_t a, int32_t b) { return (a + b + 1) >> 1; }
+
+// the prediction of the sample at (x, y) of a plane for a record: lx, ly the sample's place, (fx, fy) / (bx, by) the plane's vectors
+M2V_HD inline int32_t bp_predict(const uint8_t *fwd, const uint8_t *bwd, int stride, int x, int y, uint32_t dirs, int fx, int fy, int bx, int by)
+{
+    int32_t a = 0, c = 0;
+    if (dirs & kFwd) a = predict(fwd, stride, x + (fx >> 1), y + (fy >> 1), fx & 1, fy & 1, kIso);
+    if (dirs & kBwd) c = predict(bwd, stride, x + (bx >> 1), y + (by >> 1), bx & 1, by & 1, kIso);
+    return dirs == (uint32_t)(kFwd | kBwd) ? bp_mean(a, c) : (dirs & kFwd) ? a : c;
+}
+
 }  // namespace dec
 }  // namespace m2v

@@ -1,6 +1,6 @@
-// m2v_decode_state.hpp — what the two translation units of m2v_decode_device share: the call's state and picture table on the device
-// (m2v_decode.hip: the module syntax and everything syntax-blind) and the launchers of the main syntax's three kernels
-// (m2v_decode_main.hip).  The kernels of one unit are not touched by a change in the other.
+// m2v_decode_state.hpp — what the three translation units of m2v_decode_device share: the call's state and picture table on the device
+// (m2v_decode.hip: the module syntax and everything syntax-blind), the launchers of the main syntax's three kernels
+// (m2v_decode_main.hip) and those of the B-picture path (m2v_decode_b.hip).  The kernels of one unit are not touched by a change in another.
 #pragma once
 #include "m2v_host.hpp"
 #include "m2v_decode_kernels.hpp"
@@ -29,5 +29,16 @@ void dec_main_slices(hipStream_t s, unsigned blocks, const uint8_t *es, size_t n
                      uint32_t p0, uint32_t np, dec::MbRec *mb, int32_t *dc, int16_t *lv);
 void dec_main_recon(hipStream_t s, unsigned mbs, unsigned count, const DecState *st, const uint32_t *list, uint32_t p0, const uint8_t *d_main, const dec::MbRec *mb,
                     const int32_t *dc, const int16_t *lv, uint8_t *buf, size_t psz);
+
+// B pictures (option "decode_b_pictures"; m2v_decode_b.hip): the table behind the matrices holds these instead of DecMainPic - the
+// picture's display index and the coded indices of its references (a P picture: fwd; a B picture: fwd and bwd; 0xFFFFFFFF: none)
+struct DecBPic { uint32_t slice0, params, display, fwd, bwd; };      // params: dec::bp_params_pack
+
+// m2v_decode_b.hip: the plan in k_dm_plan's place, and everything behind the plan's wait - the chunks with two carried anchors, the
+// anchors step by step, the chunk's B pictures in one launch, the pictures placed at their display indices, the verdict
+void dec_b_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long long *ev, DecState *st, DecPic *pics, uint32_t pic_cap, uint8_t *h_types,
+                unsigned long long cap, int probe, m2v_decode_stat *h_rec, uint8_t *d_main);
+void dec_b_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_t *dst, int layout, const m2v_decode_stat &R, size_t B, const uint8_t *types,
+                  uint32_t *h_list, m2v_decode_stat *h_rec);
 
 }  // namespace m2v

@@ -282,13 +282,16 @@ def sequence_headers(data):
     return _sequence_headers(BitReader(data))
 
 
-def decode(data, quirks=True, syntax="module"):
+def decode(data, quirks=True, syntax="module", b_pictures=False):
     """syntax="module" (the default): the subset this encoder emits, as the head of this file says.  syntax="main": Main-Profile
     streams of progressive frame pictures, I and P, 4:2:0, from any encoder (decode_main below); it needs quirks=False, and a
-    refusal is a Refused exception that names the unit."""
+    refusal is a Refused exception that names the unit.  b_pictures=True (syntax="main" only): B pictures too, and the frames in
+    display order (the section "B pictures" below); with False the function is what it was for every input."""
+    if b_pictures and syntax != "main":
+        raise ValueError("b_pictures goes with syntax=\"main\"")
     if syntax == "main":
         assert not quirks, "the module's quirks have no meaning outside its own syntax"
-        return decode_main(data)
+        return decode_main(data, b_pictures)
     assert syntax == "module", syntax
     T = tables()
     br = BitReader(data)
@@ -534,6 +537,28 @@ def psnr(a, b):
 # the reset value is 1024 at every precision), Chen-Wang, saturation, mismatch control - so every stream decode(quirks=False) accepts
 # decodes to the same frames here.
 # ---------------------------------------------------------------------------------------------------------------
+#
+# B pictures (b_pictures=True; option "decode_b_pictures" of the device decoder).  Everything above stays; added:
+#   headers     picture_coding_type 3, whose picture header carries full_pel_backward_vector (must be 0, as the forward one) and
+#               backward_f_code (read, not judged) behind the forward pair; D pictures stay refused.  In the picture_coding_extension
+#               of a B picture all four f_codes are 1 .. 9 (f_code[1][*] of an I or P picture is not judged).
+#   references  an anchor is an I or P picture.  A P picture predicts from the last anchor in front of it in coded order, a B picture
+#               forward from the anchor before the last one and backward from the last one, whatever GOP headers lie between.  A B
+#               picture with fewer than two anchors in front of it is refused at its picture header (the leading B pictures of an
+#               open GOP at the stream's start).
+#   macroblocks Table B-4; PMV[0][0] (forward) and PMV[0][1] (backward), both zero at the start of a slice and behind an intra
+#               macroblock, a direction the macroblock does not use keeps its predictor; forward vectors with f_code[0][t], backward
+#               with f_code[1][t]; chroma vectors halved toward zero per direction.  One direction: _predict from that anchor; both:
+#               each prediction formed and rounded on its own, then (a + b + 1) >> 1 per sample (7.6.7.1).  A skipped macroblock
+#               (7.6.6) takes the directions of the macroblock in front of it and the predictors as its vectors, has no residual and
+#               leaves the predictors alone; it is refused behind an intra macroblock.  A vector of either direction that reads
+#               outside the picture refuses the slice, a skipped macroblock's too (it carries the vector to another column).
+#   order       Decoded.frames is in display order, from coded order and types alone (temporal_reference is not consulted): a B
+#               picture is put out when decoded, an anchor when the next anchor arrives or at the end.  Decoded.display[p] is the
+#               display index of coded picture p: p - 1 for a B picture, (coded index of the next anchor) - 1 for an anchor, N - 1 for
+#               the last.  Decoded.pictures, .mbs and .slice_qcodes stay in coded order.
+# Every stream accepted with b_pictures=False decodes to the same frames and fields with True.
+# ---------------------------------------------------------------------------------------------------------------
 class Refused(Exception):
     def __init__(self, offset, why=""):
         Exception.__init__(self, "unit at byte %d: %s" % (offset, why))
@@ -549,6 +574,9 @@ _B1_ESCAPE = "00000001000"
 _B2_TYPE_I = {"1": (0, 0, 0, 1), "01": (1, 0, 0, 1)}
 _B3_TYPE_P = {"1": (0, 1, 1, 0), "01": (0, 0, 1, 0), "001": (0, 1, 0, 0), "00011": (0, 0, 0, 1), "00010": (1, 1, 1, 0), "00001": (1, 0, 1, 0),
               "000001": (1, 0, 0, 1)}
+# table B-4 (B pictures): code -> (macroblock_quant, macroblock_motion_forward, macroblock_motion_backward, macroblock_pattern, macroblock_intra)
+_B4_TYPE_B = {"10": (0, 1, 1, 0, 0), "11": (0, 1, 1, 1, 0), "010": (0, 0, 1, 0, 0), "011": (0, 0, 1, 1, 0), "0010": (0, 1, 0, 0, 0), "0011": (0, 1, 0, 1, 0),
+              "00011": (0, 0, 0, 0, 1), "00010": (1, 1, 1, 1, 0), "000011": (1, 1, 0, 1, 0), "000010": (1, 0, 1, 1, 0), "000001": (1, 0, 0, 0, 1)}
 # table 7-6, q_scale_type 1: quantiser_scale of quantiser_scale_code 1 .. 31 (code 0 is forbidden; a slice that carries it gets 0, as
 # with q_scale_type 0)
 _NONLINEAR_SCALE = [0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 18, 20, 22, 24, 28, 32, 36, 40, 44, 48, 52, 56, 64, 72, 80, 88, 96, 104, 112]
@@ -561,7 +589,7 @@ MAIN_MAX_SIZE = 2048
 def main_tables():
     """the raw tables of the main syntax, for tests: B-1 as (code, length, increment), the scale table, the alternate scan"""
     return dict(increment=_parse(_B1_INCREMENT), escape=_B1_ESCAPE, nonlinear=list(_NONLINEAR_SCALE), alternate=list(_ALTERNATE),
-                type_i=dict(_B2_TYPE_I), type_p=dict(_B3_TYPE_P))
+                type_i=dict(_B2_TYPE_I), type_p=dict(_B3_TYPE_P), type_b=dict(_B4_TYPE_B))
 
 
 _TM = None
@@ -575,7 +603,7 @@ def _main_tables():
         for raster, pos in enumerate(_ALTERNATE):
             alt[pos] = raster
         types = lambda t: _vlc_decoder([(int(bits, 2), len(bits), flags) for bits, flags in t.items()])
-        _TM = dict(incr=_vlc_decoder(_parse(_B1_INCREMENT) + [esc]), type_i=types(_B2_TYPE_I), type_p=types(_B3_TYPE_P), alt=alt)
+        _TM = dict(incr=_vlc_decoder(_parse(_B1_INCREMENT) + [esc]), type_i=types(_B2_TYPE_I), type_p=types(_B3_TYPE_P), type_b=types(_B4_TYPE_B), alt=alt)
     return _TM
 
 
@@ -649,7 +677,7 @@ def _main_display_extension(data, start, end, h):
     assert br.rest_is_zero()
 
 
-def _main_picture_extension(data, start, end, ptype):
+def _main_picture_extension(data, start, end, ptype, b_pictures=False):
     br = _UnitBits(data, start, end)
     assert br.bits(4) == 8
     pic = dict(f_code=[br.bits(4) for _ in range(4)])
@@ -661,6 +689,9 @@ def _main_picture_extension(data, start, end, ptype):
     assert pic["concealment_motion_vectors"] == 0 and pic["intra_vlc_format"] == 0
     for f in pic["f_code"][:2]:                                 # an I picture may carry 15, "not used" (6.3.10)
         assert 1 <= f <= 9 or (ptype == 1 and f == 15), "f_code"
+    if b_pictures and ptype == 3:
+        for f in pic["f_code"][2:]:
+            assert 1 <= f <= 9, "f_code"
     assert br.rest_is_zero()
     return pic
 
@@ -686,7 +717,7 @@ def _main_role(data, pos, code):
     return _BAD
 
 
-def _main_plan(data):
+def _main_plan(data, b_pictures=False):
     """the grammar over the start codes -> (sequence fields, pictures, gops, repeated headers, number of start codes)"""
     n = len(data)
     ev = start_codes(data)
@@ -732,6 +763,7 @@ def _main_plan(data):
     pictures, gops, repeats = [], [], 0
     prev = None                                                 # the unit in front that is not skipped
     have_i = False
+    anchors = 0
     for i, (pos, code) in enumerate(ev):
         role, end = roles[i], ends[i]
         prole = roles[prev] if prev is not None else None
@@ -769,20 +801,26 @@ def _main_plan(data):
                 ok = top or prole == _GOP
                 br = _UnitBits(data, pos, end)
                 pic = dict(temporal_reference=br.bits(10), type=br.bits(3), vbv_delay=br.bits(16), unit=i, slices=[])
-                assert pic["type"] in (1, 2), "B and D pictures"
-                if pic["type"] == 2:
+                assert pic["type"] in ((1, 2, 3) if b_pictures else (1, 2)), "B and D pictures"
+                if pic["type"] in (2, 3):
                     assert br.bits(1) == 0
                     pic["forward_f_code"] = br.bits(3)
+                if pic["type"] == 3:
+                    assert br.bits(1) == 0                      # full_pel_backward_vector
+                    pic["backward_f_code"] = br.bits(3)
                 assert br.bits(1) == 0                          # extra_bit_picture
                 assert br.rest_is_zero()
                 have_i = have_i or pic["type"] == 1
                 if not have_i:
                     bad.append(pos)                             # a P picture without a reference
+                if pic["type"] == 3 and anchors < 2:
+                    bad.append(pos)                             # a B picture without two anchors in front of it
+                anchors += pic["type"] != 3
                 pictures.append(pic)
             elif role == _PICEXT:
                 ok = i > 0 and roles[i - 1] == _PIC
                 ptype = (data[ev[i - 1][0] + 5] >> 3) & 7 if ok and ev[i - 1][0] + 5 < n else 0
-                ext = _main_picture_extension(data, pos, end, ptype)
+                ext = _main_picture_extension(data, pos, end, ptype, b_pictures)
                 if ok and pictures and pictures[-1]["unit"] == i - 1:
                     pictures[-1].update(ext)
             elif role == _SLICE:
@@ -823,10 +861,23 @@ def _main_dequant(QF, intra, qscale, W, dc_mult):
     return F
 
 
-def decode_main(data):
+def display_order(types):
+    """the display index of every coded picture from the picture types in coded order (3 = B): a B picture is put out when decoded,
+    an anchor when the next anchor arrives, or at the end"""
+    n = len(types)
+    out, nxt = [0] * n, n
+    for p in range(n - 1, -1, -1):
+        if types[p] == 3:
+            out[p] = p - 1
+        else:
+            out[p], nxt = nxt - 1, p
+    return out
+
+
+def decode_main(data, b_pictures=False):
     data = bytes(data)
     T, TM = tables(), _main_tables()
-    hdr, pictures, gops, repeats, ev, ends = _main_plan(data)
+    hdr, pictures, gops, repeats, ev, ends = _main_plan(data, b_pictures)
     out = Decoded()
     out.width, out.height, out.sequence, out.gops, out.repeated_headers, out.units = hdr["width"], hdr["height"], hdr, gops, repeats, len(ev)
     mbw, mbh = (out.width + 15) // 16, (out.height + 15) // 16
@@ -834,6 +885,7 @@ def decode_main(data):
     cw, ch = (out.width + 1) // 2, (out.height + 1) // 2
     WI, WN = hdr["intra_matrix"], hdr["non_intra_matrix"]
     ref = None
+    before = None                                               # the anchor before the last one: a B picture's forward reference
     for pic in pictures:
         out.pictures.append(pic)
         scan = TM["alt"] if pic["alternate_scan"] else T["zz"]
@@ -843,10 +895,33 @@ def decode_main(data):
         V = np.zeros((H // 2, W // 2), np.int64)
         mbs, qcodes = [], []
 
-        def predict_into(col, row, mv):
+        def predict_into(col, row, mv, ref=ref):
             cmv = [int(mv[0] / 2), int(mv[1] / 2)]              # toward zero (7.6.3.7)
             return (_predict(ref[0], 16 * col, 16 * row, mv[0], mv[1], 16, False), _predict(ref[1], 8 * col, 8 * row, cmv[0], cmv[1], 8, False),
                     _predict(ref[2], 8 * col, 8 * row, cmv[0], cmv[1], 8, False))
+
+        def predict_b(col, row, fwd, bwd, mvs):
+            """a B picture's prediction: from the anchor before the last (forward), the last one (backward), or the mean of both (7.6.7.1)"""
+            p = ([predict_into(col, row, mvs[0], before)] if fwd else []) + ([predict_into(col, row, mvs[1], ref)] if bwd else [])
+            return p[0] if len(p) == 1 else tuple((a + c + 1) >> 1 for a, c in zip(*p))
+
+        def vector(br, pmv, t, f_code):
+            """7.6.3.1: component t from its predictor, the motion code and the residual of f_code"""
+            r_size = f_code - 1
+            f = 1 << r_size
+            m = T["motion"](br)
+            if m and br.bits(1):
+                m = -m
+            delta = m
+            if f != 1 and m != 0:
+                delta = (abs(m) - 1) * f + br.bits(r_size) + 1
+                delta = -delta if m < 0 else delta
+            v = pmv[t] + delta
+            if v < -16 * f:
+                v += 32 * f
+            elif v > 16 * f - 1:
+                v -= 32 * f
+            pmv[t] = v
 
         def store(col, row, pred, res):
             for b in range(6):
@@ -865,6 +940,7 @@ def decode_main(data):
                 qcodes.append(qcode)
                 assert br.bits(1) == 0                          # extra_bit_slice
                 dc_pred, pmv, col = [0, 0, 0], [0, 0], -1
+                pmvs, dirs = [[0, 0], [0, 0]], None             # a B picture's two predictors; the directions of the macroblock in front (None: intra, or none)
                 while col < mbw - 1:
                     incr = 0
                     while True:                                 # macroblock_escape adds 33 (6.3.16)
@@ -876,18 +952,36 @@ def decode_main(data):
                     incr += sym
                     assert incr == 1 or col >= 0, "a slice starts at the row's first macroblock"
                     assert col + incr < mbw, "an increment passes the row's end"
-                    for k in range(1, incr):                    # skipped macroblocks (7.6.6): zero vector, predictors reset
+                    for k in range(1, incr) if pic["type"] == 3 else ():      # skipped in a B picture (7.6.6): the directions and vectors in front
+                        assert dirs is not None, "a skipped macroblock behind an intra macroblock"
+                        dc_pred = [0, 0, 0]
+                        store(col + k, row, predict_b(col + k, row, dirs[0], dirs[1], pmvs), [np.zeros(64, np.int64)] * 6)
+                        mbs.append(dict(intra=False, mc=bool(dirs[0]), skipped=True, mv=tuple(pmvs[0]) if dirs[0] else (0, 0), cbp=0, qcode=qcode,
+                                        fwd=bool(dirs[0]), bwd=bool(dirs[1]), mv_b=tuple(pmvs[1]) if dirs[1] else (0, 0)))
+                    for k in range(1, incr) if pic["type"] != 3 else ():      # skipped macroblocks (7.6.6): zero vector, predictors reset
                         assert pic["type"] == 2, "no macroblock is skipped in an I picture"
                         dc_pred, pmv = [0, 0, 0], [0, 0]
                         store(col + k, row, predict_into(col + k, row, (0, 0)), [np.zeros(64, np.int64)] * 6)
                         mbs.append(dict(intra=False, mc=False, skipped=True, mv=(0, 0), cbp=0, qcode=qcode))
                     col += incr
-                    quant, mc, pattern, intra = (TM["type_i"] if pic["type"] == 1 else TM["type_p"])(br)
+                    bwd = 0
+                    if pic["type"] == 3:
+                        quant, mc, bwd, pattern, intra = TM["type_b"](br)
+                    else:
+                        quant, mc, pattern, intra = (TM["type_i"] if pic["type"] == 1 else TM["type_p"])(br)
                     if quant:
                         qcode = br.bits(5)
                         assert qcode != 0, "quantiser_scale_code 0 is forbidden"
                     mv = [0, 0]
-                    if mc:
+                    if pic["type"] == 3:
+                        for d in (0, 1) if not intra else ():   # forward with f_code[0][t], backward with f_code[1][t]; an unused direction keeps its predictor
+                            for t in range(2) if (mc, bwd)[d] else ():
+                                vector(br, pmvs[d], t, pic["f_code"][2 * d + t])
+                        if intra:
+                            pmvs = [[0, 0], [0, 0]]             # 7.6.3.4
+                        dirs = None if intra else (mc, bwd)
+                        mv = list(pmvs[0]) if mc else [0, 0]
+                    elif mc:
                         for t in range(2):                      # 7.6.3.1
                             r_size = pic["f_code"][t] - 1
                             f = 1 << r_size
@@ -911,7 +1005,7 @@ def decode_main(data):
                         pred = (np.full((16, 16), 128, np.int64), np.full((8, 8), 128, np.int64), np.full((8, 8), 128, np.int64))
                     else:
                         dc_pred = [0, 0, 0]                     # 7.2.1
-                        pred = predict_into(col, row, mv)
+                        pred = predict_b(col, row, mc, bwd, pmvs) if pic["type"] == 3 else predict_into(col, row, mv)
                     qscale = _NONLINEAR_SCALE[qcode] if pic["q_scale_type"] else 2 * qcode
                     res = []
                     for b in range(6):
@@ -956,14 +1050,23 @@ def decode_main(data):
                         res.append(r)
                     store(col, row, pred, res)
                     mbs.append(dict(intra=bool(intra), mc=bool(mc), skipped=False, mv=tuple(mv), cbp=cbp, qcode=qcode))
+                    if pic["type"] == 3:
+                        mbs[-1].update(fwd=bool(mc), bwd=bool(bwd), mv_b=tuple(pmvs[1]) if bwd else (0, 0))
                 assert br.rest_is_zero(), "only zero stuffing may follow the row's last macroblock"
             except Refused:
                 raise
             except Exception as e:
                 raise Refused(pos, "slice: %s" % e)
-        ref = (Y, U, V)
+        if pic["type"] != 3:
+            before, ref = ref, (Y, U, V)
         out.frames.append(tuple(np.ascontiguousarray(p[:r, :c]).astype(np.uint8)
-                                for p, r, c in zip(ref, (out.height, ch, ch), (out.width, cw, cw))))
+                                for p, r, c in zip((Y, U, V), (out.height, ch, ch), (out.width, cw, cw))))
         out.mbs.append(mbs)
         out.slice_qcodes.append(qcodes)
+    if b_pictures:
+        out.display = display_order([p["type"] for p in pictures])
+        coded = out.frames
+        out.frames = [None] * len(coded)
+        for p, d in enumerate(out.display):
+            out.frames[d] = coded[p]
     return out

@@ -967,7 +967,8 @@ int m2v_mux_scan_tile(void);
  *   sequence  load_intra_quantiser_matrix / load_non_intra_quantiser_matrix: 64 bytes each, zig-zag order, 0 forbidden
  *   macroblock  macroblock_address_increment (Table B-1) with macroblock_escape; skipped macroblocks in P pictures (7.6.6); all of
  *             Tables B-2 and B-3; a macroblock's quantiser_scale_code replaces the slice's (0 is refused)
- * Still M2V_DEC_SYNTAX in the main syntax, the follow-ups: B and D pictures; field pictures and frame_pred_frame_dct 0; concealment
+ * Still M2V_DEC_SYNTAX in the main syntax, the follow-ups: B pictures with option "decode_b_pictures" off (below), leading B pictures
+ * (fewer than two anchors in front of them) with it on, and D pictures; field pictures and frame_pred_frame_dct 0; concealment
  * vectors; intra_vlc_format 1 (Table B-15 has no second source here to be checked against); quant_matrix_extension and every scalable
  * extension; size extensions and sizes over 2048; chroma formats other than 4:2:0; more than one slice in a macroblock row, or a slice
  * whose first increment is not 1; a skipped macroblock in an I picture or as the last of a row; an increment that passes the row's
@@ -975,6 +976,28 @@ int m2v_mux_scan_tile(void);
  * a slice with intra_slice_flag 1 (the bit behind quantiser_scale_code: intra_slice, reserved bits and extra information are not
  * read) - ordinary encoders may write either; vectors that read outside the picture; and every check the module syntax makes on
  * codes, coefficient indices and stuffing inside a slice.  Also a follow-up: the batch entry (m2v_decode_streams_device) for the main syntax.
+ *
+ * Option "decode_b_pictures" (m2v_set_option), per handle: 0 (the default) - everything above, bit for bit, launch for launch and
+ * refusal for refusal (a B picture is M2V_DEC_SYNTAX at its picture header); 1 - B pictures are decoded too, and the frames come out
+ * in DISPLAY order.  Any other value is M2V_E_PARAM.  With 1, "decode_syntax" must be M2V_SYNTAX_MAIN and `mode` M2V_DEC_ISO:
+ * otherwise m2v_decode_device returns M2V_E_PARAM, writes nothing and m2v_last_error names the option; m2v_decode_streams_device is
+ * what it was.  The definition is decoder.decode(stream, quirks=False, syntax="main", b_pictures=True); every stream the main syntax
+ * accepts with the option off decodes, with it on, to the same bytes and the same record.  Added to what the main syntax accepts:
+ *   picture   picture_coding_type 3, with full_pel_backward_vector 0 and backward_f_code (not judged) in the picture header and all four
+ *             f_codes 1 .. 9 in its coding extension.  An anchor is an I or P picture; a P picture predicts from the last anchor in
+ *             front of it in coded order, a B picture forward from the anchor before the last and backward from the last, whatever GOP
+ *             headers lie between (temporal_reference, closed_gop and broken_link are read and ignored)
+ *   macroblock  Table B-4; two vector predictors, both reset at the start of a slice and behind an intra macroblock, each kept by a
+ *             macroblock that does not use its direction; forward vectors with f_code[0][t], backward with f_code[1][t]; both
+ *             directions: each prediction rounded on its own, then (a + b + 1) >> 1; a skipped macroblock takes the directions and
+ *             vectors of the macroblock in front of it (refused behind an intra macroblock); a vector of either direction that reads
+ *             outside the picture refuses the slice, a skipped macroblock's included
+ *   order     display order from coded order and picture types alone: a B picture is put out when decoded, an anchor when the next
+ *             anchor arrives or at the end - coded picture p lies at display index p - 1 if it is a B picture, else at (coded index
+ *             of the next anchor) - 1, the last anchor at pictures - 1.  The picture with display index d lies at d * frame_bytes, in
+ *             every layout; a stream without B pictures has display = coded
+ * The record, err_offset, probe calls, M2V_DEC_OVERFLOW, "decode_batch" (the result does not depend on it) and the container path are
+ * unchanged; pictures of chunks in front of the one in which a slice is refused may have been written, at their display indices.
  */
 enum { M2V_DEC_ISO = 0, M2V_DEC_MODULE = 1 };
 enum { M2V_SYNTAX_MODULE = 0, M2V_SYNTAX_MAIN = 1 };                            /* option "decode_syntax" */
