@@ -35,7 +35,9 @@
 // Option "decode_syntax" = M2V_SYNTAX_MAIN puts the main-syntax variants of k_dec_plan, k_dec_slices and k_dec_recon in their places
 // (m2v_decode_main.hip, a translation unit of its own: the three kernels here are what they were); the rest of the call is shared.
 // Option "decode_b_pictures" = 1 on top of that: B pictures, frames in display order.  The scan stays; the plan and everything behind
-// its wait are m2v_decode_b.hip's (dec_b_plan, dec_b_chunks), again a translation unit of its own.
+// its wait are m2v_decode_b.hip's (dec_b_plan, dec_b_chunks), again a translation unit of its own.  Option "decode_interlaced" = 1,
+// with "decode_b_pictures" either way: frame pictures with frame_pred_frame_dct 0; the same two places go to m2v_decode_i.hip
+// (dec_i_plan, dec_i_chunks).
 #include "m2v_decode_state.hpp"
 
 static_assert(sizeof(m2v_decode_stat) == 72, "the record of include/m2v_mi355x.h is 72 bytes");
@@ -382,6 +384,7 @@ static int decode_impl(m2v_enc *e, void *argp)
     e->d_dec_lv.recorded = e->d_dec_buf.recorded = e->d_dec_tiles.recorded = e->d_dec_list.recorded = e->d_dec_main.recorded = false;
     const bool main_syntax = e->decode_syntax == M2V_SYNTAX_MAIN;      // the main-syntax kernels in the places of k_dec_plan, k_dec_slices, k_dec_recon
     const bool b_pictures = e->decode_b_pictures != 0;                 // m2v_decode_b.hip: its plan, and everything behind the plan's wait
+    const bool interlaced = e->decode_interlaced != 0;                 // m2v_decode_i.hip: the same two places, with b_pictures either way
     const size_t ntiles = (n + dec::kScanTile - 1) / dec::kScanTile;
     if (ntiles > 0x7FFFFFFFu) { e->set_err("m2v_decode_device: the stream is longer than 2^31 scan tiles"); return M2V_E_PARAM; }
     size_t ev_cap = std::max<size_t>(1024, n / 16 + 64);              // a guess: a second run takes the count of the first
@@ -409,7 +412,11 @@ static int decode_impl(m2v_enc *e, void *argp)
         HIPCHK(hipGetLastError());
         k_dec_scan<true><<<gx, kDecThreads, 0, s>>>(a->es, n, d_st, e->d_dec_tiles.p, e->d_dec_ev.p);
         HIPCHK(hipGetLastError());
-        if (b_pictures) {
+        if (interlaced) {
+            e->d_dec_main.ensure(kDecMainMatrices + pic_cap * sizeof(DecBPic));
+            dec_i_plan(s, a->es, n, e->d_dec_ev.p, d_st, (DecPic *)e->d_dec_pics.p, (uint32_t)pic_cap, e->h_dec + rec_off + 128, (unsigned long long)a->cap,
+                       a->dst ? 0 : 1, (m2v_decode_stat *)(e->h_dec + rec_off), e->d_dec_main.p, b_pictures ? 1 : 0, (uint32_t *)(e->h_dec + rec_off + 96));
+        } else if (b_pictures) {
             e->d_dec_main.ensure(kDecMainMatrices + pic_cap * sizeof(DecBPic));
             dec_b_plan(s, a->es, n, e->d_dec_ev.p, d_st, (DecPic *)e->d_dec_pics.p, (uint32_t)pic_cap, e->h_dec + rec_off + 128, (unsigned long long)a->cap,
                        a->dst ? 0 : 1, (m2v_decode_stat *)(e->h_dec + rec_off), e->d_dec_main.p);
@@ -435,7 +442,14 @@ static int decode_impl(m2v_enc *e, void *argp)
     const size_t np = R.pictures, mbw = (R.width + 15) / 16, mbh = (R.height + 15) / 16, mbs = mbw * mbh, psz = mbs * 384;
     size_t B = e->decode_batch ? e->decode_batch : std::max<size_t>(1, std::min(kDecBatchMax, kDecLevelBytes / (mbs * 768)));
     B = std::min(B, np);
-    if (b_pictures) {                                                  // chunks of B pictures each, scheduled and run by m2v_decode_b.hip
+    if (interlaced) {                                                  // m2v_decode_i.hip; the macroblock rows are the plan's (behind the record), not the height's
+        const size_t rows = *(const uint32_t *)(e->h_dec + rec_off + 96);
+        if (!e->decode_batch) B = std::min(np, std::max<size_t>(1, std::min(kDecBatchMax, kDecLevelBytes / (mbw * rows * 768))));
+        dec_i_chunks(e, s, a->es, n, a->dst, a->layout, R, rows, B, types, (uint32_t *)(e->h_dec + rec_off + 128 + ((pic_cap + 3) & ~(size_t)3)), (m2v_decode_stat *)(e->h_dec + rec_off));
+        R = *h_rec;
+        return M2V_OK;
+    }
+    if (b_pictures) {                                                 // chunks of B pictures each, scheduled and run by m2v_decode_b.hip
         dec_b_chunks(e, s, a->es, n, a->dst, a->layout, R, B, types, (uint32_t *)(e->h_dec + rec_off + 128 + ((pic_cap + 3) & ~(size_t)3)), (m2v_decode_stat *)(e->h_dec + rec_off));
         R = *h_rec;
         return M2V_OK;
@@ -514,6 +528,10 @@ int m2v_decode_device(m2v_enc *e, const void *d_es, size_t es_bytes, void *d_dst
     if (!d_es && es_bytes) { e->set_err("m2v_decode_device: d_es is NULL"); return M2V_E_PARAM; }
     if (e->decode_b_pictures && (e->decode_syntax != M2V_SYNTAX_MAIN || mode != M2V_DEC_ISO)) {
         e->set_err("m2v_decode_device: \"decode_b_pictures\" = 1 needs \"decode_syntax\" = main and the mode M2V_DEC_ISO");
+        return M2V_E_PARAM;
+    }
+    if (e->decode_interlaced && (e->decode_syntax != M2V_SYNTAX_MAIN || mode != M2V_DEC_ISO)) {
+        e->set_err("m2v_decode_device: \"decode_interlaced\" = 1 needs \"decode_syntax\" = main and the mode M2V_DEC_ISO");
         return M2V_E_PARAM;
     }
     if (e->decode_syntax == M2V_SYNTAX_MAIN && mode != M2V_DEC_ISO) {

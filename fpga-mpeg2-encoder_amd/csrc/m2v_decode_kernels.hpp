@@ -1346,5 +1346,329 @@ M2V_HD inline int32_t bp_predict(const uint8_t *fwd, const uint8_t *bwd, int str
     return dirs == (uint32_t)(kFwd | kBwd) ? bp_mean(a, c) : (dirs & kFwd) ? a : c;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Interlaced frame pictures (option "decode_interlaced" on top of the main syntax, "decode_b_pictures" either way;
+// decoder.decode_main(interlaced=True) is the definition).  The main_ and bp_ functions above keep their text; these stand beside
+// them: the macroblock rows of a sequence that is not progressive, a coding extension that knows frame_pred_frame_dct 0,
+// macroblock_modes(), two predictors per direction, field vectors and field prediction, the field-DCT row map, a record of 32 bytes.
+// A picture with frame_pred_frame_dct 1 goes through bp_slice / main_slice as before and leaves the same kind of record.
+// ---------------------------------------------------------------------------------------------------------------------------
+// 6.3.3: the macroblock rows of a frame picture
+M2V_HD inline uint32_t il_mbh(uint32_t height, uint32_t progressive_sequence)
+{
+    return progressive_sequence ? (height + 15u) / 16u : 2u * ((height + 31u) / 32u);
+}
+
+// main_first with that rule
+M2V_HD inline uint64_t il_first(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, MainPlan &P)
+{
+    const uint64_t bad = main_first(es, n, ev, nev, P);
+    if (bad == kNone) P.mbh = il_mbh(P.seq.h.height, P.seq.h.progressive);
+    return bad;
+}
+
+// the picture's parameters with `field`: frame_pred_frame_dct 0; packed above bp_params_pack's twenty bits
+struct IPicParams { BPicParams b; uint32_t field; };
+
+M2V_HD inline uint32_t il_params_pack(const IPicParams &q) { return bp_params_pack(q.b) | q.field << 20; }
+M2V_HD inline IPicParams il_params_unpack(uint32_t v) { return IPicParams{bp_params_unpack(v), (v >> 20) & 1u}; }
+
+// 6.3.10: frame_pred_frame_dct 0 only where neither the sequence nor the frame is progressive
+M2V_HD inline bool il_field_allowed(uint32_t progressive_sequence, uint32_t progressive_frame) { return !progressive_sequence && !progressive_frame; }
+
+// b_pictures: whether the backward f_codes of a B picture are judged, as bp_picture_extension does (off, its header is refused)
+M2V_HD inline bool il_picture_extension(const uint8_t *es, uint64_t start, uint64_t end, uint32_t ptype, bool b_pictures, uint32_t progressive_sequence,
+                                        IPicParams &q)
+{
+    Bits b = unit_bits(es, start, end);
+    bool ok = get(b, 4) == 8;
+    q.b.p.fh = get(b, 4); q.b.p.fv = get(b, 4);
+    q.b.bh = get(b, 4); q.b.bv = get(b, 4);
+    q.b.p.prec = get(b, 2);
+    ok = ok && get(b, 2) == 3;                               // frame picture
+    skip(b, 1);                                              // top_field_first: read, not acted on
+    q.field = get(b, 1) ^ 1u;                                // frame_pred_frame_dct
+    ok = ok && get(b, 1) == 0;                               // concealment_motion_vectors
+    q.b.p.qst = get(b, 1);
+    ok = ok && get(b, 1) == 0;                               // intra_vlc_format
+    q.b.p.alt = get(b, 1);
+    skip(b, 2);                                              // repeat_first_field, chroma_420_type: read, not acted on
+    const uint32_t progressive_frame = get(b, 1);
+    skip(b, 1);                                              // composite_display_flag
+    ok = ok && (!q.field || il_field_allowed(progressive_sequence, progressive_frame));
+    ok = ok && main_fcode_ok(q.b.p.fh, ptype) && main_fcode_ok(q.b.p.fv, ptype);
+    if (b_pictures && ptype == 3) ok = ok && q.b.bh >= 1 && q.b.bh <= 9 && q.b.bv >= 1 && q.b.bv <= 9;
+    return ok && !b.err && tail_zero(b);
+}
+
+// event i by its own rule: bp_event or main_event (P.mbh is il_first's), but a coding extension is judged by il_picture_extension
+M2V_HD inline EvInfo il_event(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, uint32_t i, const MainPlan &P, uint64_t last_nz, int prev,
+                              bool b_pictures)
+{
+    if (main_role(es, n, ev[i]) != rPicExt)
+        return b_pictures ? bp_event(es, n, ev, nev, i, P, last_nz, prev) : main_event(es, n, ev, nev, i, P, last_nz, prev);
+    EvInfo r{kNone, 0, 0, 0, 0};
+    const uint64_t pos = ev_pos(ev[i]), end = i + 1 < nev ? ev_pos(ev[i + 1]) : n;
+    IPicParams q;
+    const int before = i ? main_role(es, n, ev[i - 1]) : rBad;
+    const uint64_t pp = i ? ev_pos(ev[i - 1]) : 0;
+    const uint32_t ptype = before == rPic && pp + 5 < n ? (es[pp + 5] >> 3) & 7u : 0u;
+    bool ok = before == rPic && il_picture_extension(es, pos, end, ptype, b_pictures, P.seq.h.progressive, q);
+    if (i + 1 == nev) ok = false;                            // no stream ends behind a picture coding extension
+    if (!ok) r.bad = pos;
+    return r;
+}
+
+M2V_HD inline uint32_t il_picture_params(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, uint32_t i, bool b_pictures,
+                                         uint32_t progressive_sequence, uint32_t &slice0)
+{
+    IPicParams q{BPicParams{PicParams{1, 1, 0, 0, 0}, 1, 1}, 0};
+    uint32_t j = i + 2;
+    if (i + 1 < nev) {
+        const uint64_t pos = ev_pos(ev[i]);
+        (void)il_picture_extension(es, ev_pos(ev[i + 1]), i + 2 < nev ? ev_pos(ev[i + 2]) : n, pos + 5 < n ? (es[pos + 5] >> 3) & 7u : 0u, b_pictures,
+                                   progressive_sequence, q);
+    }
+    while (j < nev && !main_significant(main_role(es, n, ev[j]))) ++j;
+    slice0 = j;
+    return il_params_pack(q);
+}
+
+// ---- macroblock layer ----
+// BMb with its two reserved bytes given meaning, and sixteen more: the second vector of either direction (a field-based macroblock's
+// bottom-field lines; a frame-based one repeats the first) and the field selects, sel[2 * s + r]
+struct IMb {
+    uint8_t intra, mc, cbp, qcode; int16_t mvx, mvy; uint8_t skipped, dirs; int16_t bvx, bvy; uint8_t motion_type, dct_type;
+    int16_t mvx1, mvy1, bvx1, bvy1; uint8_t sel[4]; uint8_t reserved[4];
+};
+enum { kFieldBased = 1, kFrameBased = 2 };                   // frame_motion_type (0 reserved, 3 dual prime)
+
+// tables B-2 and B-3 over the next 6 bits in vlc_type_b's form: length | flags << 8; 0 where no code begins the window
+M2V_HD inline uint32_t il_type_ip(uint32_t w6, uint32_t ptype)
+{
+    if (ptype == 1) return (w6 >> 5) ? 1u | 0x01u << 8 : (w6 >> 4) ? 2u | 0x11u << 8 : 0u;      // '1' intra; '01' intra, quant
+    if (w6 >> 5) return 1u | 0x0Au << 8;                     // '1'      MC, coded
+    if (w6 >> 4) return 2u | 0x02u << 8;                     // '01'     No MC, coded
+    if (w6 >> 3) return 3u | 0x08u << 8;                     // '001'    MC, not coded
+    if ((w6 >> 1) == 3u) return 5u | 0x01u << 8;             // '00011'  intra
+    if ((w6 >> 1) == 2u) return 5u | 0x1Au << 8;             // '00010'  MC, coded, quant
+    if ((w6 >> 1) == 1u) return 5u | 0x12u << 8;             // '00001'  No MC, coded, quant
+    if (w6 == 1u) return 6u | 0x11u << 8;                    // '000001' intra, quant
+    return 0u;
+}
+
+// macroblock_modes() behind macroblock_type in a picture with frame_pred_frame_dct 0: frame_motion_type where the macroblock has a
+// vector, dct_type where it has blocks; false = refused (the reserved motion type, or dual prime)
+M2V_HD inline bool il_modes(Bits &b, bool has_vector, bool has_blocks, uint32_t &motion_type, uint32_t &dct_type)
+{
+    motion_type = kFrameBased; dct_type = 0;
+    if (has_vector) {
+        motion_type = get(b, 2);
+        if (motion_type != (uint32_t)kFieldBased && motion_type != (uint32_t)kFrameBased) return false;
+    }
+    if (has_blocks) dct_type = get(b, 1);
+    return !b.err;
+}
+
+// a field vector behind its select (7.6.3.1): the horizontal component as ever; the vertical one predicted from the predictor DIV 2,
+// the predictor twice the vector afterwards.  pmv: PMV[r][s]; false = refused
+M2V_HD inline bool il_field_vector(Bits &b, int32_t (&pmv)[2], int r_h, int r_v, int32_t &vx, int32_t &vy)
+{
+    if (!bp_component(b, pmv[0], r_h)) return false;
+    int32_t half = pmv[1] >> 1;
+    if (!bp_component(b, half, r_v)) return false;
+    pmv[1] = 2 * half;
+    vx = pmv[0]; vy = half;
+    return true;
+}
+
+// block_inside for a w x h block: a field prediction's 16 x 8 and 8 x 4
+M2V_HD inline bool il_block_inside(int x0, int y0, int mvx, int mvy, int w, int h, int pw, int ph)
+{
+    const int ix = mvx >> 1, iy = mvy >> 1, hx = mvx & 1, hy = mvy & 1;
+    return x0 + ix >= 0 && y0 + iy >= 0 && x0 + ix + w - 1 + hx < pw && y0 + iy + h - 1 + hy < ph;
+}
+
+// a field vector reads inside its field: luma 16 x 8 at (16 col, 8 row) of 16 mbw x 8 mbh, chroma 8 x 4 with the halved vector
+M2V_HD inline bool il_field_inside(int col, int row, int mvx, int mvy, int mbw, int mbh)
+{
+    return il_block_inside(16 * col, 8 * row, mvx, mvy, 16, 8, 16 * mbw, 8 * mbh) &&
+           il_block_inside(8 * col, 4 * row, chroma_vector(mvx, kIso), chroma_vector(mvy, kIso), 8, 4, 8 * mbw, 4 * mbh);
+}
+
+// the vectors a record uses read inside the picture: a frame-based one's as bp_inside, a field-based one's per field
+M2V_HD inline bool il_inside(int col, int row, const IMb &m, int mbw, int mbh)
+{
+    if (m.motion_type != kFieldBased)
+        return (!(m.dirs & kFwd) || vector_inside(col, row, m.mvx, m.mvy, mbw, mbh, kIso)) &&
+               (!(m.dirs & kBwd) || vector_inside(col, row, m.bvx, m.bvy, mbw, mbh, kIso));
+    return (!(m.dirs & kFwd) || (il_field_inside(col, row, m.mvx, m.mvy, mbw, mbh) && il_field_inside(col, row, m.mvx1, m.mvy1, mbw, mbh))) &&
+           (!(m.dirs & kBwd) || (il_field_inside(col, row, m.bvx, m.bvy, mbw, mbh) && il_field_inside(col, row, m.bvx1, m.bvy1, mbw, mbh)));
+}
+
+// a frame-based record's vectors of direction s from PMV[0][s]: both halves the same
+M2V_HD inline void il_frame_vectors(IMb &m, int s, const int32_t (&pmv)[2])
+{
+    if (s == 0) { m.mvx = m.mvx1 = (int16_t)pmv[0]; m.mvy = m.mvy1 = (int16_t)pmv[1]; }
+    else { m.bvx = m.bvx1 = (int16_t)pmv[0]; m.bvy = m.bvy1 = (int16_t)pmv[1]; }
+}
+
+// one macroblock of a picture with frame_pred_frame_dct 0 behind its address increment; pmv: PMV[r][s][t]; false = refused
+template <class Put>
+M2V_HD inline bool il_macroblock(Bits &b, uint32_t ptype, const IPicParams &pp, SliceState &s, int32_t (&pmv)[2][2][2], uint32_t &qcode, IMb &m, int32_t (&dc)[6],
+                                 Put put)
+{
+    const uint32_t e = ptype == 3 ? vlc_type_b(peek(b, 6)) : il_type_ip(peek(b, 6), ptype);
+    if (!e) return false;
+    skip(b, (int)(e & 255u));
+    const uint32_t flags = e >> 8;
+    const bool intra = (flags & 1u) != 0, pattern = ((flags >> 1) & 1u) != 0;
+    const uint32_t dirs = (((flags >> 3) & 1u) ? (uint32_t)kFwd : 0u) | (((flags >> 2) & 1u) ? (uint32_t)kBwd : 0u);
+    uint32_t motion_type, dct_type;
+    if (!il_modes(b, dirs != 0, intra || pattern, motion_type, dct_type)) return false;
+    if (flags >> 4) {
+        qcode = get(b, 5);
+        if (!qcode) return false;
+    }
+    m = IMb{};
+    for (int d = 0; d < 2; ++d) {
+        if (!(dirs & (d ? (uint32_t)kBwd : (uint32_t)kFwd))) continue;
+        const int r_h = (int)(d ? pp.b.bh : pp.b.p.fh) - 1, r_v = (int)(d ? pp.b.bv : pp.b.p.fv) - 1;
+        if (motion_type == (uint32_t)kFrameBased) {          // 7.6.3.3: both predictors of the direction follow a frame vector
+            if (!bp_component(b, pmv[0][d][0], r_h) || !bp_component(b, pmv[0][d][1], r_v)) return false;
+            pmv[1][d][0] = pmv[0][d][0]; pmv[1][d][1] = pmv[0][d][1];
+            il_frame_vectors(m, d, pmv[0][d]);
+            continue;
+        }
+        for (int r = 0; r < 2; ++r) {
+            int32_t vx, vy;
+            m.sel[2 * d + r] = (uint8_t)get(b, 1);           // motion_vertical_field_select[r][s]
+            if (!il_field_vector(b, pmv[r][d], r_h, r_v, vx, vy)) return false;
+            if (d == 0) { if (r == 0) { m.mvx = (int16_t)vx; m.mvy = (int16_t)vy; } else { m.mvx1 = (int16_t)vx; m.mvy1 = (int16_t)vy; } }
+            else { if (r == 0) { m.bvx = (int16_t)vx; m.bvy = (int16_t)vy; } else { m.bvx1 = (int16_t)vx; m.bvy1 = (int16_t)vy; } }
+        }
+    }
+    if (intra || (ptype == 2 && !(dirs & kFwd))) {           // 7.6.3.4: both r, both directions
+        for (int r = 0; r < 2; ++r) for (int d = 0; d < 2; ++d) pmv[r][d][0] = pmv[r][d][1] = 0;
+    }
+    uint32_t cbp = intra ? 63u : 0u;
+    if (pattern) {
+        const uint32_t c = vlc_cbp(peek(b, 32));
+        if (!c) return false;
+        skip(b, (int)(c & 255u));
+        cbp = c >> 8;
+    }
+    if (!intra) { for (int c = 0; c < 3; ++c) s.dc_pred[c] = 0; }       // 7.2.1
+    m.intra = intra; m.cbp = (uint8_t)cbp; m.mc = (dirs & kFwd) != 0;
+    m.dirs = (uint8_t)(intra ? 0u : ptype == 2 ? (uint32_t)kFwd : dirs);      // a P picture's macroblock without a vector: forward, the zero vector
+    m.motion_type = (uint8_t)motion_type; m.dct_type = (uint8_t)dct_type;
+    for (int blk = 0; blk < 6; ++blk) {
+        dc[blk] = 0;
+        if (!((cbp >> (5 - blk)) & 1u)) continue;
+        if (!parse_block(b, intra, blk < 4 ? 0 : blk - 3, s, dc[blk],
+                         [&](uint32_t i, int32_t l) { put(blk, pp.b.p.alt ? alternate_to_raster(zigzag_position(i)) : i, l); })) return false;
+    }
+    return !b.err;
+}
+
+// bp_slice's records as IMb: frame-based, frame DCT
+template <class Sink>
+struct IlFrameSink {
+    Sink &s;
+    M2V_HD void mb(int col, const BMb &m, const int32_t (&dc)[6])
+    {
+        IMb r{};
+        r.intra = m.intra; r.mc = m.mc; r.cbp = m.cbp; r.qcode = m.qcode; r.skipped = m.skipped; r.dirs = m.dirs;
+        r.mvx = r.mvx1 = m.mvx; r.mvy = r.mvy1 = m.mvy; r.bvx = r.bvx1 = m.bvx; r.bvy = r.bvy1 = m.bvy;
+        r.motion_type = (uint8_t)kFrameBased;
+        s.mb(col, r, dc);
+    }
+    M2V_HD void level(int col, int blk, uint32_t i, int32_t l) { s.level(col, blk, i, l); }
+};
+
+// the slice of macroblock row `row` of a picture of any type through sink.mb(col, IMb, dc) and sink.level: a picture with
+// frame_pred_frame_dct 1 by bp_slice (an I or P picture's by main_slice behind it); one with 0 here - macroblock_modes, two predictors
+// per direction, skipped macroblocks frame-predicted (a P picture's with the zero vector, a B picture's with PMV[0][s]), every vector
+// inside the picture or its field.  Bounded as main_slice is
+template <class Sink>
+M2V_HD inline bool il_slice(const uint8_t *es, uint64_t start, uint64_t end, uint32_t ptype, const IPicParams &pp, int mbw, int mbh, int row, Sink &sink)
+{
+    if (!pp.field) {
+        IlFrameSink<Sink> a{sink};
+        return bp_slice(es, start, end, ptype, pp.b, mbw, mbh, row, a);
+    }
+    Bits b = unit_bits(es, start, end);
+    uint32_t qcode = get(b, 5);
+    if (get(b, 1) != 0) return false;                        // extra_bit_slice
+    SliceState s{{0, 0, 0}, {0, 0}};
+    int32_t pmv[2][2][2] = {{{0, 0}, {0, 0}}, {{0, 0}, {0, 0}}};
+    uint32_t dirs = 0;                                       // of the macroblock in front; 0: intra
+    int col = -1;
+    while (col < mbw - 1) {
+        int incr = 0;
+        uint32_t e;
+        for (;;) {
+            e = vlc_increment(peek(b, 11));
+            if (!e) return false;
+            skip(b, (int)(e & 255u));
+            if ((e >> 8) != 34u) break;
+            incr += 33;                                      // macroblock_escape
+            if (col + incr >= mbw) return false;
+        }
+        incr += (int)(e >> 8);
+        if ((col < 0 && incr != 1) || col + incr >= mbw || b.err) return false;
+        if (incr > 1) {                                      // 7.6.6: skipped - frame prediction, no residual
+            if (ptype == 1) return false;
+            IMb z{};
+            z.skipped = 1; z.qcode = (uint8_t)qcode; z.motion_type = (uint8_t)kFrameBased;
+            if (ptype == 2) {                                // the zero vector, the predictors reset
+                z.dirs = (uint8_t)kFwd;
+                for (int r = 0; r < 2; ++r) for (int d = 0; d < 2; ++d) pmv[r][d][0] = pmv[r][d][1] = 0;
+            } else {                                         // the directions in front, PMV[0][s] as frame vectors
+                if (!dirs) return false;
+                z.dirs = (uint8_t)dirs; z.mc = (dirs & kFwd) != 0;
+                if (dirs & kFwd) il_frame_vectors(z, 0, pmv[0][0]);
+                if (dirs & kBwd) il_frame_vectors(z, 1, pmv[0][1]);
+            }
+            const int32_t none[6] = {0, 0, 0, 0, 0, 0};
+            for (int k = 1; k < incr; ++k) {
+                if (!il_inside(col + k, row, z, mbw, mbh)) return false;
+                sink.mb(col + k, z, none);
+            }
+            for (int c = 0; c < 3; ++c) s.dc_pred[c] = 0;
+        }
+        col += incr;
+        IMb m;
+        int32_t dc[6];
+        if (!il_macroblock(b, ptype, pp, s, pmv, qcode, m, dc, [&](int blk, uint32_t i, int32_t l) { sink.level(col, blk, i, l); })) return false;
+        if (!il_inside(col, row, m, mbw, mbh)) return false;
+        m.qcode = (uint8_t)qcode;
+        dirs = m.dirs;
+        sink.mb(col, m, dc);
+    }
+    return !b.err && tail_zero(b);
+}
+
+// the field-DCT row map: the luma block that holds sample (x, y) of a macroblock, and the row inside it
+M2V_HD inline uint32_t il_luma_block(uint32_t x, uint32_t y, uint32_t dct_type) { return (dct_type ? (y & 1u) : (y >> 3)) * 2u + (x >> 3); }
+M2V_HD inline uint32_t il_luma_row(uint32_t y, uint32_t dct_type) { return dct_type ? y >> 1 : y & 7u; }
+
+// the prediction of the sample at (x, y) of a plane for a record; chroma: the plane is a chroma plane, the vectors are halved toward
+// zero.  Frame-based: bp_predict.  Field-based (7.6.4): row y is a line of the field of its parity, predicted by the vector of that
+// parity from the field its select names - rows of one parity, twice the stride apart -, at field line y >> 1
+M2V_HD inline int32_t il_predict(const uint8_t *fwd, const uint8_t *bwd, int stride, int x, int y, const IMb &m, bool chroma)
+{
+    const int r = m.motion_type == kFieldBased ? (y & 1) : 0;
+    int fx = r ? m.mvx1 : m.mvx, fy = r ? m.mvy1 : m.mvy, bx = r ? m.bvx1 : m.bvx, by = r ? m.bvy1 : m.bvy;
+    if (chroma) { fx = chroma_vector(fx, kIso); fy = chroma_vector(fy, kIso); bx = chroma_vector(bx, kIso); by = chroma_vector(by, kIso); }
+    if (m.motion_type != kFieldBased) return bp_predict(fwd, bwd, stride, x, y, m.dirs, fx, fy, bx, by);
+    const int line = y >> 1;
+    const int sf = r ? m.sel[1] : m.sel[0], sb = r ? m.sel[3] : m.sel[2];      // (no index into the record: it stays in registers)
+    int32_t a = 0, c = 0;
+    if (m.dirs & kFwd) a = predict(fwd + (size_t)sf * stride, 2 * stride, x + (fx >> 1), line + (fy >> 1), fx & 1, fy & 1, kIso);
+    if (m.dirs & kBwd) c = predict(bwd + (size_t)sb * stride, 2 * stride, x + (bx >> 1), line + (by >> 1), bx & 1, by & 1, kIso);
+    return m.dirs == (kFwd | kBwd) ? bp_mean(a, c) : (m.dirs & kFwd) ? a : c;
+}
+
 }  // namespace dec
 }  // namespace m2v

@@ -41,4 +41,12 @@ void dec_b_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long 
 void dec_b_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_t *dst, int layout, const m2v_decode_stat &R, size_t B, const uint8_t *types,
                   uint32_t *h_list, m2v_decode_stat *h_rec);
 
+// Interlaced frame pictures (option "decode_interlaced"; m2v_decode_i.hip), with "decode_b_pictures" (b_pictures) 0 or 1: DecBPic again,
+// its params dec::il_params_pack.  The plan also leaves the picture's macroblock rows at h_mbh (pinned): a sequence that is not
+// progressive has 2 * ((height + 31) / 32) of them, and the chunks take them from there
+void dec_i_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long long *ev, DecState *st, DecPic *pics, uint32_t pic_cap, uint8_t *h_types,
+                unsigned long long cap, int probe, m2v_decode_stat *h_rec, uint8_t *d_main, int b_pictures, uint32_t *h_mbh);
+void dec_i_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_t *dst, int layout, const m2v_decode_stat &R, size_t mbh, size_t B,
+                  const uint8_t *types, uint32_t *h_list, m2v_decode_stat *h_rec);
+
 }  // namespace m2v

@@ -282,16 +282,20 @@ def sequence_headers(data):
     return _sequence_headers(BitReader(data))
 
 
-def decode(data, quirks=True, syntax="module", b_pictures=False):
+def decode(data, quirks=True, syntax="module", b_pictures=False, interlaced=False):
     """syntax="module" (the default): the subset this encoder emits, as the head of this file says.  syntax="main": Main-Profile
     streams of progressive frame pictures, I and P, 4:2:0, from any encoder (decode_main below); it needs quirks=False, and a
     refusal is a Refused exception that names the unit.  b_pictures=True (syntax="main" only): B pictures too, and the frames in
-    display order (the section "B pictures" below); with False the function is what it was for every input."""
+    display order (the section "B pictures" below); with False the function is what it was for every input.  interlaced=True
+    (syntax="main" only, with b_pictures either way): frame pictures with frame_pred_frame_dct 0 too (the section "Interlaced frame
+    pictures" below); with False the function is what it was for every input."""
     if b_pictures and syntax != "main":
         raise ValueError("b_pictures goes with syntax=\"main\"")
+    if interlaced and syntax != "main":
+        raise ValueError("interlaced goes with syntax=\"main\"")
     if syntax == "main":
         assert not quirks, "the module's quirks have no meaning outside its own syntax"
-        return decode_main(data, b_pictures)
+        return decode_main(data, b_pictures, interlaced)
     assert syntax == "module", syntax
     T = tables()
     br = BitReader(data)
@@ -514,6 +518,25 @@ def _predict(plane, x0, y0, mvx, mvy, n, quirks):
     return a
 
 
+def _predict_rect(plane, x0, y0, mvx, mvy, w, h):
+    """_predict(quirks=False) for a w x h block: a field prediction's 16 x 8 or 8 x 4 in one field of the reference"""
+    ix, iy, hx, hy = mvx >> 1, mvy >> 1, mvx & 1, mvy & 1
+    H, W = plane.shape
+    ys = np.arange(y0 + iy, y0 + iy + h + 1)
+    xs = np.arange(x0 + ix, x0 + ix + w + 1)
+    assert ys[0] >= 0 and xs[0] >= 0 and ys[h - 1 + hy] < H and xs[w - 1 + hx] < W, "vector points outside the field"
+    ys, xs = np.clip(ys, 0, H - 1), np.clip(xs, 0, W - 1)
+    p = plane[np.ix_(ys, xs)].astype(np.int64)
+    a, b, c, d = p[:h, :w], p[:h, 1:w + 1], p[1:h + 1, :w], p[1:h + 1, 1:w + 1]
+    if hx and hy:
+        return (a + b + c + d + 2) >> 2
+    if hx:
+        return (a + b + 1) >> 1
+    if hy:
+        return (a + c + 1) >> 1
+    return a
+
+
 def psnr(a, b):
     mse = np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2)
     return 99.0 if mse == 0 else 10 * np.log10(255.0 ** 2 / mse)
@@ -558,6 +581,34 @@ def psnr(a, b):
 #               display index of coded picture p: p - 1 for a B picture, (coded index of the next anchor) - 1 for an anchor, N - 1 for
 #               the last.  Decoded.pictures, .mbs and .slice_qcodes stay in coded order.
 # Every stream accepted with b_pictures=False decodes to the same frames and fields with True.
+# ---------------------------------------------------------------------------------------------------------------
+#
+# Interlaced frame pictures (interlaced=True; option "decode_interlaced" of the device decoder; b_pictures either way).  Added:
+#   sequence    with progressive_sequence 0 a picture has 2 * ((height + 31) // 32) macroblock rows (6.3.3), the slice codes run to
+#               that, and the coded picture is cropped to the header's size as always (_main_mbh).  A progressive_sequence 0 stream
+#               with an odd (height + 15) // 16 is therefore another stream with the option than without.
+#   extension   frame_pred_frame_dct 0 where progressive_sequence and progressive_frame are both 0 (6.3.10); top_field_first,
+#               repeat_first_field and chroma_420_type are read and not acted on: one coded picture is one frame, both fields woven.
+#               A picture with frame_pred_frame_dct 1 decodes as before.
+#   modes       in a picture with frame_pred_frame_dct 0, behind macroblock_type: frame_motion_type (2 bits) if the macroblock has a
+#               forward or a backward vector - 2 frame-based, 1 field-based, 0 (reserved) and 3 (dual prime) refuse the slice -, then
+#               dct_type (1 bit) if it is intra or has a pattern; then quantiser_scale_code and the rest.
+#   vectors     PMV[r][s], r = 0 / 1, s = forward / backward.  A frame vector is predicted from PMV[0][s] and sets PMV[1][s] to it
+#               (7.6.3.3).  A field-based macroblock carries, per direction, field_select and vector for r = 0, then for r = 1; vector r
+#               from PMV[r][s], the vertical component from PMV[r][s][1] >> 1, and PMV[r][s][1] = 2 * vector afterwards.  All of them
+#               are zero at a slice's start, behind an intra macroblock, behind a P picture's macroblock without a vector and behind a
+#               P picture's skipped macroblock.
+#   prediction  field-based (7.6.4): vector 0 forms the macroblock's top-field lines, vector 1 its bottom-field lines, each from the
+#               field of the anchor its select names (0: the even rows), the vector in half samples of that field: 16 x 8 at (16 col,
+#               8 row) of a 16 mbw x 8 mbh field, chroma 8 x 4 at (8 col, 4 row) with both components / 2 toward zero.  A vector that
+#               reads outside its field refuses the slice.  Both directions: each formed in full, then (a + b + 1) >> 1.
+#   dct_type 1  luma blocks 0 / 1 are the macroblock's top-field lines (row k of the block is row 2k), blocks 2 / 3 its bottom-field
+#               lines (row 2k + 1); chroma blocks are frame blocks.
+#   skipped     frame prediction: a P picture's with the zero vector; a B picture's in the directions of the macroblock in front with
+#               PMV[0][s] as frame vectors - behind a field-based macroblock twice its first field vector's vertical component.
+# Decoded.mbs of such a picture carry motion_type, dct_type, selects[s][r] and vectors[s][r] besides the fields above.  Still
+# refused: field pictures, dual prime, concealment vectors.  Every stream accepted with interlaced=False decodes to the same frames
+# and fields with True, but for the macroblock-row exception above.
 # ---------------------------------------------------------------------------------------------------------------
 class Refused(Exception):
     def __init__(self, offset, why=""):
@@ -677,7 +728,7 @@ def _main_display_extension(data, start, end, h):
     assert br.rest_is_zero()
 
 
-def _main_picture_extension(data, start, end, ptype, b_pictures=False):
+def _main_picture_extension(data, start, end, ptype, b_pictures=False, interlaced=False, progressive_sequence=1):
     br = _UnitBits(data, start, end)
     assert br.bits(4) == 8
     pic = dict(f_code=[br.bits(4) for _ in range(4)])
@@ -685,9 +736,11 @@ def _main_picture_extension(data, start, end, ptype, b_pictures=False):
                frame_pred_frame_dct=br.bits(1), concealment_motion_vectors=br.bits(1), q_scale_type=br.bits(1),
                intra_vlc_format=br.bits(1), alternate_scan=br.bits(1), repeat_first_field=br.bits(1),
                chroma_420_type=br.bits(1), progressive_frame=br.bits(1), composite_display_flag=br.bits(1))
-    assert pic["picture_structure"] == 3 and pic["frame_pred_frame_dct"] == 1
+    assert pic["picture_structure"] == 3
+    if pic["frame_pred_frame_dct"] != 1:                        # 6.3.10: 0 only where neither the sequence nor the frame is progressive
+        assert interlaced and not progressive_sequence and not pic["progressive_frame"], "frame_pred_frame_dct"
     assert pic["concealment_motion_vectors"] == 0 and pic["intra_vlc_format"] == 0
-    for f in pic["f_code"][:2]:                                 # an I picture may carry 15, "not used" (6.3.10)
+    for f in pic["f_code"][:2]:                               # an I picture may carry 15, "not used" (6.3.10)
         assert 1 <= f <= 9 or (ptype == 1 and f == 15), "f_code"
     if b_pictures and ptype == 3:
         for f in pic["f_code"][2:]:
@@ -717,7 +770,14 @@ def _main_role(data, pos, code):
     return _BAD
 
 
-def _main_plan(data, b_pictures=False):
+def _main_mbh(hdr, interlaced=False):
+    """macroblock rows of a frame picture (6.3.3): with interlaced=True a sequence that is not progressive has whole field macroblocks"""
+    if interlaced and not hdr["progressive_sequence"]:
+        return 2 * ((hdr["height"] + 31) // 32)
+    return (hdr["height"] + 15) // 16
+
+
+def _main_plan(data, b_pictures=False, interlaced=False):
     """the grammar over the start codes -> (sequence fields, pictures, gops, repeated headers, number of start codes)"""
     n = len(data)
     ev = start_codes(data)
@@ -758,7 +818,7 @@ def _main_plan(data, b_pictures=False):
         raise Refused(first, "the sequence header")
     if not (1 <= first["width"] <= MAIN_MAX_SIZE and 1 <= first["height"] <= MAIN_MAX_SIZE):
         raise Refused(ev[0][0], "the size")
-    mbh = (first["height"] + 15) // 16
+    mbh = _main_mbh(first, interlaced)
     bad = []
     pictures, gops, repeats = [], [], 0
     prev = None                                                 # the unit in front that is not skipped
@@ -820,7 +880,7 @@ def _main_plan(data, b_pictures=False):
             elif role == _PICEXT:
                 ok = i > 0 and roles[i - 1] == _PIC
                 ptype = (data[ev[i - 1][0] + 5] >> 3) & 7 if ok and ev[i - 1][0] + 5 < n else 0
-                ext = _main_picture_extension(data, pos, end, ptype, b_pictures)
+                ext = _main_picture_extension(data, pos, end, ptype, b_pictures, interlaced, first["progressive_sequence"])
                 if ok and pictures and pictures[-1]["unit"] == i - 1:
                     pictures[-1].update(ext)
             elif role == _SLICE:
@@ -874,13 +934,13 @@ def display_order(types):
     return out
 
 
-def decode_main(data, b_pictures=False):
+def decode_main(data, b_pictures=False, interlaced=False):
     data = bytes(data)
     T, TM = tables(), _main_tables()
-    hdr, pictures, gops, repeats, ev, ends = _main_plan(data, b_pictures)
+    hdr, pictures, gops, repeats, ev, ends = _main_plan(data, b_pictures, interlaced)
     out = Decoded()
     out.width, out.height, out.sequence, out.gops, out.repeated_headers, out.units = hdr["width"], hdr["height"], hdr, gops, repeats, len(ev)
-    mbw, mbh = (out.width + 15) // 16, (out.height + 15) // 16
+    mbw, mbh = (out.width + 15) // 16, _main_mbh(hdr, interlaced)
     W, H = 16 * mbw, 16 * mbh
     cw, ch = (out.width + 1) // 2, (out.height + 1) // 2
     WI, WN = hdr["intra_matrix"], hdr["non_intra_matrix"]
@@ -932,10 +992,187 @@ def decode_main(data, b_pictures=False):
                 else:
                     (U if b == 4 else V)[8 * row:8 * row + 8, 8 * col:8 * col + 8] = np.clip(pred[b - 3] + r, 0, 255)
 
+        def predict_field(col, row, vecs, sels, ref):
+            """7.6.4 for a field-based macroblock: vector r with field select r forms the lines of parity r - 16 x 8 luma at (16 col,
+            8 row) of the selected field, 8 x 4 chroma at (8 col, 4 row) with both components halved toward zero (7.6.3.7)"""
+            planes = []
+            for p, n in ((0, 16), (1, 8), (2, 8)):
+                block = np.zeros((n, n), np.int64)
+                for r in range(2):
+                    mv = vecs[r] if p == 0 else (int(vecs[r][0] / 2), int(vecs[r][1] / 2))
+                    block[r::2] = _predict_rect(ref[p][sels[r]::2], n * col, (n // 2) * row, mv[0], mv[1], n, n // 2)
+                planes.append(block)
+            return tuple(planes)
+
+        def store_il(col, row, pred, res, dct_type):
+            """store, or with dct_type 1: luma blocks 0 / 1 are the macroblock's top-field lines, 2 / 3 its bottom-field lines"""
+            if not dct_type:
+                return store(col, row, pred, res)
+            for b in range(6):
+                r = res[b].reshape(8, 8)
+                if b < 4:
+                    y0, ox = 16 * row + (b >> 1), 8 * (b & 1)
+                    Y[y0:y0 + 16:2, 16 * col + ox:16 * col + ox + 8] = np.clip(pred[0][(b >> 1)::2, ox:ox + 8] + r, 0, 255)
+                else:
+                    (U if b == 4 else V)[8 * row:8 * row + 8, 8 * col:8 * col + 8] = np.clip(pred[b - 3] + r, 0, 255)
+
+        def read_blocks(br, intra, cbp, dc_pred, qcode):
+            """the coded blocks of a macroblock -> six residuals (zeros where the pattern has none)"""
+            qscale = _NONLINEAR_SCALE[qcode] if pic["q_scale_type"] else 2 * qcode
+            res = []
+            for b in range(6):
+                r = np.zeros(64, np.int64)
+                if (cbp >> (5 - b)) & 1:
+                    QF = np.zeros(64, np.int64)
+                    k = 0
+                    comp = 0 if b < 4 else b - 3
+                    if intra:
+                        size = (T["dcy"] if b < 4 else T["dcc"])(br)
+                        diff = 0
+                        if size:
+                            d = br.bits(size)
+                            diff = d if d >> (size - 1) else d - (1 << size) + 1
+                        dc_pred[comp] += diff
+                        QF[0] = dc_pred[comp]
+                        k = 1
+                    first = not intra
+                    while True:
+                        if first and br.peek(1) == 1:
+                            br.bits(1)
+                            run, lvl = 0, (-1 if br.bits(1) else 1)
+                        else:
+                            sym = T["ac"](br) if not (br.peek(2) == 0b11) else (br.bits(2), (0, 1))[1]
+                            if sym == "EOB":
+                                assert not first, "a coded non-intra block cannot start with EOB"
+                                break
+                            if sym == "ESC":
+                                run = br.bits(6)
+                                lvl = br.bits(12)
+                                lvl = lvl - 4096 if lvl & 0x800 else lvl
+                                assert lvl not in (0, -2048)
+                            else:
+                                run, lvl = sym
+                                lvl = -lvl if br.bits(1) else lvl
+                        first = False
+                        k += run
+                        assert k < 64, "coefficient index beyond 63"
+                        QF[scan[k]] = lvl
+                        k += 1
+                    r = idct(_main_dequant(QF, intra, qscale, WI if intra else WN, dc_mult), False)
+                res.append(r)
+            return res
+
+        def il_slice(br, row):
+            """a slice of a picture with frame_pred_frame_dct 0, of any type (the section "Interlaced frame pictures" above)"""
+            qcode = br.bits(5)
+            qcodes.append(qcode)
+            assert br.bits(1) == 0                              # extra_bit_slice
+            ptype = pic["type"]
+            refs = (ref, None) if ptype == 2 else (before, ref)  # the anchor of direction s
+            dc_pred, col = [0, 0, 0], -1
+            PMV = [[[0, 0], [0, 0]], [[0, 0], [0, 0]]]          # PMV[r][s]
+            dirs = None                                         # the directions of the macroblock in front (None: intra, or none)
+            zero = [np.zeros(64, np.int64)] * 6
+
+            def frame_pred(col, used, vecs):
+                p = [predict_into(col, row, vecs[s], refs[s]) for s in (0, 1) if used[s]]
+                return p[0] if len(p) == 1 else tuple((a + c + 1) >> 1 for a, c in zip(*p))
+
+            def record(used, **kw):
+                """what every record of the main syntax carries, and motion_type, dct_type, selects[s][r], vectors[s][r]"""
+                m = dict(intra=False, mc=False, skipped=False, mv=(0, 0), cbp=0, qcode=qcode, motion_type=2, dct_type=0,
+                         selects=((0, 0), (0, 0)), vectors=(((0, 0), (0, 0)), ((0, 0), (0, 0))))
+                m.update(kw)
+                if ptype == 3:
+                    m.update(fwd=bool(used[0]), bwd=bool(used[1]), mv_b=m["vectors"][1][0] if used[1] else (0, 0))
+                mbs.append(m)
+
+            while col < mbw - 1:
+                incr = 0
+                while True:                                     # macroblock_escape adds 33 (6.3.16)
+                    sym = TM["incr"](br)
+                    if sym != "ESC":
+                        break
+                    incr += 33
+                    assert col + incr < mbw, "an increment passes the row's end"
+                incr += sym
+                assert incr == 1 or col >= 0, "a slice starts at the row's first macroblock"
+                assert col + incr < mbw, "an increment passes the row's end"
+                for k in range(1, incr):                        # 7.6.6: frame prediction, whatever the macroblock in front was
+                    assert ptype != 1, "no macroblock is skipped in an I picture"
+                    dc_pred = [0, 0, 0]
+                    if ptype == 2:                              # the zero vector; the predictors reset
+                        PMV = [[[0, 0], [0, 0]], [[0, 0], [0, 0]]]
+                        store(col + k, row, frame_pred(col + k, (1, 0), ((0, 0), None)), zero)
+                        record(skipped=True, used=(1, 0))
+                    else:                                       # the directions in front, PMV[0][s] read as frame vectors
+                        assert dirs is not None, "a skipped macroblock behind an intra macroblock"
+                        vecs = (tuple(PMV[0][0]), tuple(PMV[0][1]))
+                        store(col + k, row, frame_pred(col + k, dirs, vecs), zero)
+                        record(skipped=True, mc=bool(dirs[0]), mv=vecs[0] if dirs[0] else (0, 0), used=dirs,
+                               vectors=tuple((vecs[s], vecs[s]) if dirs[s] else ((0, 0), (0, 0)) for s in (0, 1)))
+                col += incr
+                bwd = 0
+                if ptype == 3:
+                    quant, mc, bwd, pattern, intra = TM["type_b"](br)
+                else:
+                    quant, mc, pattern, intra = (TM["type_i"] if ptype == 1 else TM["type_p"])(br)
+                motion_type, dct_type = 2, 0                    # macroblock_modes(): frame_motion_type, dct_type
+                if mc or bwd:
+                    motion_type = br.bits(2)
+                    assert motion_type in (1, 2), "frame_motion_type 0 is reserved, 3 is dual prime"
+                if intra or pattern:
+                    dct_type = br.bits(1)
+                if quant:
+                    qcode = br.bits(5)
+                    assert qcode != 0, "quantiser_scale_code 0 is forbidden"
+                sel = [[0, 0], [0, 0]]                          # [s][r]
+                vec = [[(0, 0), (0, 0)], [(0, 0), (0, 0)]]      # [s][r]
+                for s in (0, 1):
+                    if not (mc, bwd)[s]:
+                        continue
+                    fh, fv = pic["f_code"][2 * s:2 * s + 2]
+                    if motion_type == 2:                        # 7.6.3.3: both predictors of the direction follow a frame vector
+                        vector(br, PMV[0][s], 0, fh)
+                        vector(br, PMV[0][s], 1, fv)
+                        PMV[1][s] = list(PMV[0][s])
+                        vec[s] = [tuple(PMV[0][s])] * 2
+                    else:
+                        for r in (0, 1):                        # 7.6.3.1: the vertical predictor is in frame units - DIV 2 in, times 2 out
+                            sel[s][r] = br.bits(1)
+                            vector(br, PMV[r][s], 0, fh)
+                            half = [PMV[r][s][1] >> 1]
+                            vector(br, half, 0, fv)
+                            PMV[r][s][1] = 2 * half[0]
+                            vec[s][r] = (PMV[r][s][0], half[0])
+                if intra or (ptype == 2 and not mc):
+                    PMV = [[[0, 0], [0, 0]], [[0, 0], [0, 0]]]  # 7.6.3.4
+                cbp = 63 if intra else (T["cbp"](br) if pattern else 0)
+                used = (0, 0) if intra else (1, 0) if ptype == 2 else (mc, bwd)
+                if intra:
+                    pred = (np.full((16, 16), 128, np.int64), np.full((8, 8), 128, np.int64), np.full((8, 8), 128, np.int64))
+                    dirs = None
+                else:
+                    dc_pred = [0, 0, 0]                         # 7.2.1
+                    if motion_type == 2:
+                        pred = frame_pred(col, used, (vec[0][0], vec[1][0]))
+                    else:
+                        p = [predict_field(col, row, vec[s], sel[s], refs[s]) for s in (0, 1) if used[s]]
+                        pred = p[0] if len(p) == 1 else tuple((a + c + 1) >> 1 for a, c in zip(*p))
+                    dirs = used
+                res = read_blocks(br, intra, cbp, dc_pred, qcode)
+                store_il(col, row, pred, res, dct_type)
+                record(intra=bool(intra), mc=bool(mc), mv=vec[0][0] if mc else (0, 0), cbp=cbp, qcode=qcode, motion_type=motion_type, dct_type=dct_type,
+                       used=used, selects=tuple(tuple(x) for x in sel), vectors=tuple(tuple(x) for x in vec))
+
         for row, unit in enumerate(pic["slices"]):
             pos = ev[unit][0]
             try:
                 br = _UnitBits(data, pos, ends[unit])
+                if interlaced and not pic["frame_pred_frame_dct"]:
+                    il_slice(br, row)
+                    assert br.rest_is_zero(), "only zero stuffing may follow the row's last macroblock"
+                    continue
                 qcode = br.bits(5)
                 qcodes.append(qcode)
                 assert br.bits(1) == 0                          # extra_bit_slice

@@ -998,6 +998,43 @@ int m2v_mux_scan_tile(void);
  *             every layout; a stream without B pictures has display = coded
  * The record, err_offset, probe calls, M2V_DEC_OVERFLOW, "decode_batch" (the result does not depend on it) and the container path are
  * unchanged; pictures of chunks in front of the one in which a slice is refused may have been written, at their display indices.
+ *
+ * Option "decode_interlaced" (m2v_set_option), per handle: 0 (the default) - everything above, bit for bit, launch for launch and
+ * refusal for refusal (frame_pred_frame_dct 0 is M2V_DEC_SYNTAX at its picture coding extension); 1 - interlaced FRAME pictures are
+ * decoded too: field prediction and field DCT.  Any other value is M2V_E_PARAM.  With 1, "decode_syntax" must be M2V_SYNTAX_MAIN and
+ * `mode` M2V_DEC_ISO: otherwise m2v_decode_device returns M2V_E_PARAM, writes nothing and m2v_last_error names the option;
+ * m2v_decode_streams_device is what it was.  It combines with "decode_b_pictures" 0 (a B picture is still refused at its picture
+ * header, frames in coded order) or 1 (frames in display order, as above).  The definition is decoder.decode(stream, quirks=False,
+ * syntax="main", b_pictures=..., interlaced=True).  Every stream the main syntax accepts with the option off - "decode_b_pictures"
+ * either way - decodes, with it on, to the same bytes and the same record, with ONE exception: a stream with progressive_sequence 0
+ * whose (height + 15) / 16 is odd has one more macroblock row with the option on (first line below) and is another stream.  Added:
+ *   sequence  with progressive_sequence 0 a picture has 2 * ((height + 31) / 32) macroblock rows (6.3.3): slice codes run to that, the
+ *             coded picture is 16 times that many lines, cropped to the header's size as always (16 lines: two slices a picture).
+ *             With progressive_sequence 1 nothing changes
+ *   picture   frame_pred_frame_dct 0 where progressive_sequence and progressive_frame are both 0; refused at the extension where either
+ *             is 1 (6.3.10).  top_field_first, repeat_first_field and chroma_420_type are read and not acted on: one coded picture is
+ *             one output frame with both fields woven, whatever repeat_first_field says.  picture_structure stays 3; a picture
+ *             with frame_pred_frame_dct 1 decodes exactly as without the option
+ *   modes     in a picture with frame_pred_frame_dct 0: frame_motion_type (2 bits) behind macroblock_type where the macroblock has a
+ *             forward or backward vector, then dct_type (1 bit) where it is intra or has a pattern, then quantiser_scale_code and the
+ *             rest.  frame_motion_type 2 is frame-based, 1 field-based; 0 (reserved) and 3 (dual prime) refuse the slice
+ *   vectors   two predictors per direction, PMV[r][s].  A field-based macroblock carries, per direction it uses, field select and
+ *             vector for its top-field lines, then for its bottom-field lines; vector r from PMV[r][s], its vertical component from
+ *             PMV[r][s][1] >> 1 with the unchanged delta, wrap and range of f_code[s][1], and PMV[r][s][1] = 2 * vector afterwards.  A
+ *             frame vector is predicted from PMV[0][s] and sets PMV[1][s] to it.  All are reset at a slice's start, behind an intra
+ *             macroblock, behind a P picture's macroblock without a vector and behind a P picture's skipped macroblock
+ *   prediction  field-based (7.6.4): vector 0 predicts the macroblock's frame rows 0, 2 .. 14, vector 1 its rows 1, 3 .. 15, each from
+ *             the field of the reference its select names (0: the even rows), in half samples of that field: field line
+ *             8 * row + j + (vy >> 1), with vy & 1 the rounded mean with the next line of the same field; horizontally as ever.
+ *             Chroma: both components / 2 toward zero, four lines per field.  Both directions: each formed in full, then
+ *             (a + b + 1) >> 1.  A field vector that reads outside its field (16 x 8 luma at (16 col, 8 row) of 16 mbw x 8 mbh; chroma
+ *             8 x 4 with the halved vector) refuses the slice
+ *   dct_type 1  luma blocks 0 / 1 are the macroblock's top-field lines (row k of the block is row 2k), 2 / 3 its bottom-field lines
+ *             (row 2k + 1); chroma blocks are frame blocks; inverse quantisation, mismatch control and the IDCT are untouched
+ *   skipped   frame prediction: a P picture's with the zero vector; a B picture's in the directions of the macroblock in front with
+ *             PMV[0][s] read as frame vectors - behind a field-based macroblock twice its first field vector's vertical component
+ * Still M2V_DEC_SYNTAX with the option on, the follow-ups: field pictures (picture_structure 1 and 2); dual prime; concealment
+ * vectors; and everything else the main syntax refuses.
  */
 enum { M2V_DEC_ISO = 0, M2V_DEC_MODULE = 1 };
 enum { M2V_SYNTAX_MODULE = 0, M2V_SYNTAX_MAIN = 1 };                            /* option "decode_syntax" */
