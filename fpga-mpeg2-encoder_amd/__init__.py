@@ -50,7 +50,7 @@ EXPORTS = [
     "m2v_mux_bound", "m2v_set_mux_out", "m2v_mux_report", "m2v_mux_device", "m2v_mux_scan_tile",
     "m2v_set_source_size", "m2v_scale_taps",
     "m2v_demux_bound", "m2v_demux_device", "m2v_demux_report", "m2v_demux_scan_tile",
-    "m2v_decode_streams_device", "m2v_decode_streams_report",
+    "m2v_decode_streams_device", "m2v_decode_streams_report", "m2v_decode_streams_main_device",
 ]
 
 # the 4:2:0 entry points (kept apart: tests/test_abi.py matches EXPORTS against names of letters and underscores only)
@@ -131,6 +131,7 @@ DECODE_STAT_DTYPE = np.dtype([("es_bytes", "<u8"), ("out_bytes", "<u8"), ("frame
 DECODE_STREAM_STAT_DTYPE = np.dtype([("es_offset", "<u8"), ("out_offset", "<u8"), ("rec", DECODE_STAT_DTYPE)])
 DEC_MODES = {"iso": 0, "module": 1}                              # M2V_DEC_*
 DEC_SYNTAXES = {"module": 0, "main": 1}                          # M2V_SYNTAX_*: option "decode_syntax"
+DECS_B_PICTURES, DECS_INTERLACED = 1, 2                          # M2V_DECS_*: the flags of m2v_decode_streams_main_device
 DEC_OK, DEC_SYNTAX, DEC_OVERFLOW = 0, -2, -3
 DEC_STATUS = {0: "M2V_DEC_OK", -2: "M2V_DEC_SYNTAX", -3: "M2V_DEC_OVERFLOW"}
 
@@ -447,6 +448,7 @@ def lib(debug=False):
             L.m2v_decode_streams_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, ci, ci, vp]
             L.m2v_decode_streams_report.argtypes = [vp, vp, sz]
             L.m2v_scale_taps.argtypes = [ci, ci, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_uint16)]
+            L.m2v_decode_streams_main_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, ci, ctypes.c_uint, vp]
         except AttributeError:
             # an OLDER build handed in through M2V_LIB for a same-box A/B (tools/ab.sh) may lack the newer entry points; the library of
             # this tree must have every one of them (tests/test_abi.py)
@@ -1012,7 +1014,8 @@ class Mpeg2Encoder:
         of DECODE_STREAM_STAT_DTYPE - one per stream of the last decode_streams."""
         return self._pop("m2v_decode_streams_report", DECODE_STREAM_STAT_DTYPE, max_records)
 
-    def decode_streams(self, es, segments, layout="i420", mode="iso", out=None, container=None, stream=None):
+    def decode_streams(self, es, segments, layout="i420", mode="iso", out=None, container=None, stream=None, syntax="module", b_pictures=False,
+                       interlaced=False):
         """m2v_decode_streams_device: the elementary streams at the (offset, bytes) pairs of `segments` in the one-dimensional uint8
         device tensor `es` - at any byte alignment, of any picture sizes - decoded on the device in one call.  Returns (frames, records):
         a one-dimensional uint8 tensor on es's device and a structured array of DECODE_STREAM_STAT_DTYPE, one record per stream;
@@ -1023,8 +1026,19 @@ class Mpeg2Encoder:
 
         container = "ts" or "ps": `es` and `segments` are containers; they go through demux_device (`stream` as there) in one call into
         a zeroed scratch tensor, and every stream is handed on with the zero padding to a whole 32-byte word, as decode_device(container=)
-        does.  A container the demultiplexer refused comes back as DEC_SYNTAX with pictures 0."""
+        does.  A container the demultiplexer refused comes back as DEC_SYNTAX with pictures 0.
+
+        syntax = "main": m2v_decode_streams_main_device - the streams are main-syntax streams (what an ordinary multiplexer's
+        containers hold), each judged as decode_device(syntax="main", b_pictures=, interlaced=) judges it alone; with b_pictures the
+        frames of a stream are in display order.  The syntax is the call's: the handle's three decode options are neither read nor
+        changed.  The mode is "iso" there ("module" is a ValueError), and b_pictures / interlaced need syntax="main"."""
         import torch
+        if syntax not in ("module", "main"):
+            raise ValueError("decode_streams: syntax is \"module\" or \"main\"")
+        if syntax != "main" and (b_pictures or interlaced):
+            raise ValueError("decode_streams: b_pictures and interlaced need syntax=\"main\"")
+        if syntax == "main" and mode in ("module", DEC_MODES["module"]):
+            raise ValueError("decode_streams: with syntax=\"main\" the mode is \"iso\"")
         if not isinstance(es, torch.Tensor) or es.dtype != torch.uint8 or es.dim() != 1 or not es.is_cuda or es.device.index != self.device:
             raise ValueError("decode_streams: a one-dimensional uint8 tensor on the handle's device is required")
         if es.stride(0) != 1 and es.numel() > 1:
@@ -1052,9 +1066,15 @@ class Mpeg2Encoder:
         nb = (ctypes.c_uint64 * len(seg))(*[b for _, b in seg])
         hip_stream = torch.cuda.current_stream(es.device).cuda_stream
 
+        flags = (DECS_B_PICTURES if b_pictures else 0) | (DECS_INTERLACED if interlaced else 0)
+
         def call(ptr, cap):
-            self._chk(self._L.m2v_decode_streams_device(self._h, es.data_ptr() or None, off, nb, len(seg), ptr, cap, code, m, hip_stream),
-                      "m2v_decode_streams_device")
+            if syntax == "main":
+                self._chk(self._L.m2v_decode_streams_main_device(self._h, es.data_ptr() or None, off, nb, len(seg), ptr, cap, code, flags, hip_stream),
+                          "m2v_decode_streams_main_device")
+            else:
+                self._chk(self._L.m2v_decode_streams_device(self._h, es.data_ptr() or None, off, nb, len(seg), ptr, cap, code, m, hip_stream),
+                          "m2v_decode_streams_device")
             return self.decode_streams_report()
         if out is None:
             r = call(None, 0)

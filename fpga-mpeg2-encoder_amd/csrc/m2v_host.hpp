@@ -38,6 +38,8 @@
 //                     (option "decode_interlaced"); m2v_decode_state.hpp is what the four share
 //   m2v_decode_streams.hip   m2v_decode_streams_device: a batch of elementary streams of any sizes in one call - the same arithmetic over a
 //                     table of streams, in kernels of its own (m2v_decode_streams.hpp lays the batch out, for the host build too)
+//   m2v_decode_streams_main.hip   m2v_decode_streams_main_device: the same for main-syntax streams, B pictures and interlaced frame pictures
+//                     by the call's flags, again in kernels of its own (m2v_decode_streams_main.hpp lays the batch out)
 //   m2v_demux.hip     m2v_demux_device: transport / program streams in HBM back to the elementary stream, the inverse of m2v_mux.hip and like it
 //                     a unit of its own (m2v_demux_kernels.hpp holds the arithmetic, for the device and the host alike)
 //   m2v_scale.hip     m2v_set_source_size: frames of another size resampled to the picture size in front of the conversions - the setting,

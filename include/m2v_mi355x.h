@@ -975,7 +975,7 @@ int m2v_mux_scan_tile(void);
  * end; composite_display_flag 1 (its 20 bits behind the picture_coding_extension's flags are read as stuffing that is not zero);
  * a slice with intra_slice_flag 1 (the bit behind quantiser_scale_code: intra_slice, reserved bits and extra information are not
  * read) - ordinary encoders may write either; vectors that read outside the picture; and every check the module syntax makes on
- * codes, coefficient indices and stuffing inside a slice.  Also a follow-up: the batch entry (m2v_decode_streams_device) for the main syntax.
+ * codes, coefficient indices and stuffing inside a slice.  The batch entry for the main syntax is m2v_decode_streams_main_device, below.
  *
  * Option "decode_b_pictures" (m2v_set_option), per handle: 0 (the default) - everything above, bit for bit, launch for launch and
  * refusal for refusal (a B picture is M2V_DEC_SYNTAX at its picture header); 1 - B pictures are decoded too, and the frames come out
@@ -1087,6 +1087,45 @@ typedef struct { uint64_t es_offset, out_offset; m2v_decode_stat rec; } m2v_deco
 int m2v_decode_streams_device(m2v_enc *e, const void *d_es, const uint64_t *es_off, const uint64_t *es_bytes, size_t nstreams,
                               void *d_dst, size_t cap, int layout, int mode, void *hip_stream);
 int m2v_decode_streams_report(m2v_enc *e, m2v_decode_stream_stat *out, size_t max);   /* pops, oldest first; out NULL: how many wait */
+
+/*
+ * The batch entry of the MAIN syntax: m2v_decode_streams_main_device decodes a batch of main-syntax elementary streams - what
+ * m2v_demux_device extracts from an ordinary multiplexer's containers - in one call.  m2v_decode_streams_device does not move: it reads
+ * the module's dialect and still answers M2V_E_STATE while "decode_syntax" is main.
+ *
+ * The syntax is the CALL's, not the handle's: the entry neither reads nor changes "decode_syntax", "decode_b_pictures" or
+ * "decode_interlaced".  flags: M2V_DECS_B_PICTURES (1) accepts B pictures, M2V_DECS_INTERLACED (2) accepts frame pictures with
+ * frame_pred_frame_dct 0; any other bit is M2V_E_PARAM, m2v_last_error names the entry, nothing is touched.  The mode is M2V_DEC_ISO (the
+ * module's quirks have no meaning here).  It does read "decode_batch", as the module's entry does.
+ *
+ * Segments, nstreams 1 .. 65535, d_dst == NULL as a probe call, cap, layout, blocking, the two host waits per call (a third when a
+ * stream holds more start codes than guessed) and M2V_E_STATE while a sequence is in progress or a resident call is in flight are word
+ * for word m2v_decode_streams_device's contract, above.  The records are m2v_decode_stream_stat, popped through
+ * m2v_decode_streams_report: the same queue, dropped at the next call of EITHER batch entry.
+ *
+ * Each stream is judged alone.  `rec` is field for field what m2v_decode_device reports for that stream by itself with "decode_syntax" =
+ * main, "decode_b_pictures" = (flags & 1) and "decode_interlaced" = (flags >> 1 & 1): decoder.decode(stream, quirks=False,
+ * syntax="main", b_pictures=, interlaced=) is the definition, rec.err_offset is Refused.offset relative to the stream's first byte.
+ *
+ * Layout.  The rules are the module entry's: out_offset[b] sums pictures * frame_bytes over the streams in front that the probe stage
+ * accepts - the headers and the grammar of the start codes (decoder._main_plan does not raise).  A stream refused there takes no room.
+ * With flag 1 off a B picture is such a refusal at its picture header, with flag 2 off frame_pred_frame_dct 0 is one at its coding
+ * extension: the same batch has different layouts under different flags.  A stream refused inside a slice keeps its room and not one byte
+ * of it is written, in however many chunks it lies; a stream whose room does not lie inside cap is M2V_DEC_OVERFLOW; nothing outside
+ * the rooms of OK streams is ever written.
+ *
+ * Frame order.  With flag 1 on, a stream's frames are in DISPLAY order inside its room: coded picture p lies at out_offset +
+ * display[p] * frame_bytes, `display` as the B-picture paragraph above defines it.  With flag 1 off they are in coded order (the same
+ * thing: there is no B picture).  With flag 2 on a progressive_sequence 0 stream has 2 * ((height + 31) / 32) macroblock rows, the same
+ * stated exception as in the single-stream option.  The result does not depend on "decode_batch": a stream cut at a chunk's edge
+ * carries its last two anchors into the next chunk.
+ *
+ * Still M2V_DEC_SYNTAX, exactly where the single-stream decoder refuses them: intra_vlc_format 1 (Table B-15), quant_matrix_extension,
+ * several slices in a macroblock row, intra_slice_flag, field pictures, dual prime, concealment vectors.
+ */
+enum { M2V_DECS_B_PICTURES = 1, M2V_DECS_INTERLACED = 2 };
+int m2v_decode_streams_main_device(m2v_enc *e, const void *d_es, const uint64_t *es_off, const uint64_t *es_bytes, size_t nstreams,
+                                   void *d_dst, size_t cap, int layout, unsigned flags, void *hip_stream);
 
 /*
  * Demux on the device: the inverse of m2v_mux_device.  nstreams (1 .. 65535) transport (kind M2V_MUX_TS) or program (M2V_MUX_PS) streams
