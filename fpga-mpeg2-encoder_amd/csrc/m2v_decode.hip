@@ -37,7 +37,8 @@
 // Option "decode_b_pictures" = 1 on top of that: B pictures, frames in display order.  The scan stays; the plan and everything behind
 // its wait are m2v_decode_b.hip's (dec_b_plan, dec_b_chunks), again a translation unit of its own.  Option "decode_interlaced" = 1,
 // with "decode_b_pictures" either way: frame pictures with frame_pred_frame_dct 0; the same two places go to m2v_decode_i.hip
-// (dec_i_plan, dec_i_chunks).
+// (dec_i_plan, dec_i_chunks).  Option "decode_extended" = 1, with the other two either way: several slices a row, slice header extras,
+// quant_matrix_extension, composite_display_flag 1; the same two places go to m2v_decode_x.hip (dec_x_plan, dec_x_chunks).
 #include "m2v_decode_state.hpp"
 
 static_assert(sizeof(m2v_decode_stat) == 72, "the record of include/m2v_mi355x.h is 72 bytes");
@@ -362,7 +363,7 @@ __global__ void k_dec_finish(const DecState *st, m2v_decode_stat *h_rec)
 void dec_release(m2v_enc *e)
 {
     e->d_dec_st.release(); e->d_dec_tiles.release(); e->d_dec_ev.release(); e->d_dec_pics.release(); e->d_dec_mb.release(); e->d_dec_dc.release();
-    e->d_dec_lv.release(); e->d_dec_buf.release(); e->d_dec_list.release(); e->d_dec_main.release();
+    e->d_dec_lv.release(); e->d_dec_buf.release(); e->d_dec_list.release(); e->d_dec_main.release(); e->d_dec_x.release();
     if (e->h_dec) (void)hipHostFree(e->h_dec);
     e->h_dec = nullptr; e->h_dec_cap = 0;
 }
@@ -385,6 +386,8 @@ static int decode_impl(m2v_enc *e, void *argp)
     const bool main_syntax = e->decode_syntax == M2V_SYNTAX_MAIN;      // the main-syntax kernels in the places of k_dec_plan, k_dec_slices, k_dec_recon
     const bool b_pictures = e->decode_b_pictures != 0;                 // m2v_decode_b.hip: its plan, and everything behind the plan's wait
     const bool interlaced = e->decode_interlaced != 0;                 // m2v_decode_i.hip: the same two places, with b_pictures either way
+    const bool extended = e->decode_extended != 0;                     // m2v_decode_x.hip: the same two places, with the other two either way
+    e->d_dec_x.recorded = false;
     const size_t ntiles = (n + dec::kScanTile - 1) / dec::kScanTile;
     if (ntiles > 0x7FFFFFFFu) { e->set_err("m2v_decode_device: the stream is longer than 2^31 scan tiles"); return M2V_E_PARAM; }
     size_t ev_cap = std::max<size_t>(1024, n / 16 + 64);              // a guess: a second run takes the count of the first
@@ -399,7 +402,7 @@ static int decode_impl(m2v_enc *e, void *argp)
         e->d_dec_ev.ensure(ev_cap);
         e->d_dec_pics.ensure(pic_cap * sizeof(DecPic));
         rec_off = (sizeof(DecState) + 63) & ~(size_t)63;
-        ensure_pinned(e->h_dec, e->h_dec_cap, rec_off + 128 + pic_cap + 4 * pic_cap + 16);
+        ensure_pinned(e->h_dec, e->h_dec_cap, rec_off + 128 + pic_cap + 4 * pic_cap + 16 + (extended ? 4 * (pic_cap + 1) : 0));      // extended: the slices in front of every picture
         auto *init = (DecState *)e->h_dec;
         *init = DecState{};
         init->err = dec::kNone; init->ev_cap = (uint32_t)ev_cap;
@@ -412,7 +415,12 @@ static int decode_impl(m2v_enc *e, void *argp)
         HIPCHK(hipGetLastError());
         k_dec_scan<true><<<gx, kDecThreads, 0, s>>>(a->es, n, d_st, e->d_dec_tiles.p, e->d_dec_ev.p);
         HIPCHK(hipGetLastError());
-        if (interlaced) {
+        if (extended) {
+            e->d_dec_main.ensure(kDecMainMatrices + pic_cap * sizeof(DecXPic));
+            dec_x_plan(s, a->es, n, e->d_dec_ev.p, d_st, (DecPic *)e->d_dec_pics.p, (uint32_t)pic_cap, e->h_dec + rec_off + 128, (unsigned long long)a->cap,
+                       a->dst ? 0 : 1, (m2v_decode_stat *)(e->h_dec + rec_off), e->d_dec_main.p, b_pictures ? 1 : 0, interlaced ? 1 : 0,
+                       (uint32_t *)(e->h_dec + rec_off + 96), (uint32_t *)(e->h_dec + rec_off + 128 + ((pic_cap + 3) & ~(size_t)3) + 4 * pic_cap));
+        } else if (interlaced) {
             e->d_dec_main.ensure(kDecMainMatrices + pic_cap * sizeof(DecBPic));
             dec_i_plan(s, a->es, n, e->d_dec_ev.p, d_st, (DecPic *)e->d_dec_pics.p, (uint32_t)pic_cap, e->h_dec + rec_off + 128, (unsigned long long)a->cap,
                        a->dst ? 0 : 1, (m2v_decode_stat *)(e->h_dec + rec_off), e->d_dec_main.p, b_pictures ? 1 : 0, (uint32_t *)(e->h_dec + rec_off + 96));
@@ -442,6 +450,14 @@ static int decode_impl(m2v_enc *e, void *argp)
     const size_t np = R.pictures, mbw = (R.width + 15) / 16, mbh = (R.height + 15) / 16, mbs = mbw * mbh, psz = mbs * 384;
     size_t B = e->decode_batch ? e->decode_batch : std::max<size_t>(1, std::min(kDecBatchMax, kDecLevelBytes / (mbs * 768)));
     B = std::min(B, np);
+    if (extended) {                                                    // m2v_decode_x.hip; the macroblock rows and the slices in front of every picture are the plan's
+        const size_t rows = *(const uint32_t *)(e->h_dec + rec_off + 96);
+        if (!e->decode_batch) B = std::min(np, std::max<size_t>(1, std::min(kDecBatchMax, kDecLevelBytes / (mbw * rows * 768))));
+        auto *h_list = (uint32_t *)(e->h_dec + rec_off + 128 + ((pic_cap + 3) & ~(size_t)3));
+        dec_x_chunks(e, s, a->es, n, a->dst, a->layout, R, rows, B, types, h_list, h_list + pic_cap, (m2v_decode_stat *)(e->h_dec + rec_off));
+        R = *h_rec;
+        return M2V_OK;
+    }
     if (interlaced) {                                                  // m2v_decode_i.hip; the macroblock rows are the plan's (behind the record), not the height's
         const size_t rows = *(const uint32_t *)(e->h_dec + rec_off + 96);
         if (!e->decode_batch) B = std::min(np, std::max<size_t>(1, std::min(kDecBatchMax, kDecLevelBytes / (mbw * rows * 768))));
@@ -532,6 +548,10 @@ int m2v_decode_device(m2v_enc *e, const void *d_es, size_t es_bytes, void *d_dst
     }
     if (e->decode_interlaced && (e->decode_syntax != M2V_SYNTAX_MAIN || mode != M2V_DEC_ISO)) {
         e->set_err("m2v_decode_device: \"decode_interlaced\" = 1 needs \"decode_syntax\" = main and the mode M2V_DEC_ISO");
+        return M2V_E_PARAM;
+    }
+    if (e->decode_extended && (e->decode_syntax != M2V_SYNTAX_MAIN || mode != M2V_DEC_ISO)) {
+        e->set_err("m2v_decode_device: \"decode_extended\" = 1 needs \"decode_syntax\" = main and the mode M2V_DEC_ISO");
         return M2V_E_PARAM;
     }
     if (e->decode_syntax == M2V_SYNTAX_MAIN && mode != M2V_DEC_ISO) {

@@ -1670,5 +1670,323 @@ M2V_HD inline int32_t il_predict(const uint8_t *fwd, const uint8_t *bwd, int str
     return m.dirs == (kFwd | kBwd) ? bp_mean(a, c) : (m.dirs & kFwd) ? a : c;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Several slices a row (option "decode_extended" on top of the main syntax, "decode_b_pictures" and "decode_interlaced" either way;
+// decoder.decode_main(extended=True) is the definition).  The functions above keep their text; these stand beside them:
+//   slices      a picture is any number of slices, 1 <= code <= mbh: the first behind the picture's extensions has code 1, every
+//               further one its predecessor's code or that + 1, and a picture ends only behind code mbh (x_event).  The first
+//               macroblock_address_increment of a slice, escapes included, places it: column increment - 1, nothing skipped in front.
+//               The macroblock loop runs while anything but zero bits is left in the unit; a slice without a macroblock or one whose
+//               column passes mbw - 1 is refused.  All predictors reset at a slice's start (x_slice).
+//   continuity  judged behind the walk from what every slice leaves (x_span_pack): a row's first slice starts at column 0 and the row
+//               in front of it is full; a slice with its predecessor's code starts one column behind the predecessor's last; the
+//               picture's last slice ends at mbw - 1.  A slice that breaks one of these is refused at its own start code (x_continuous).
+//   header      behind quantiser_scale_code a bit 1 is intra_slice_flag: intra_slice and reserved_bits (8 bits, not judged), then
+//               extra_information_slice bytes, each behind an extra_bit_slice 1, then the closing 0.
+//   matrices    quant_matrix_extension (identifier 3) is a transparent unit behind a picture_coding_extension, one a picture at most:
+//               the two load flags with 64 bytes each in zig-zag order (a weight of 0 refuses it), the two chroma load flags 0, zero
+//               stuffing.  A loaded matrix is in force from its picture on, in coded order, each matrix on its own; every sequence
+//               header puts both back to the sequence's (x_mats_*).
+//   composite   composite_display_flag 1: the 20 bits behind it are read and not acted on (x_picture_extension).
+// ---------------------------------------------------------------------------------------------------------------------------
+enum { rQuant = 11 };                                            // quant_matrix_extension: transparent, as rUser and rSkipExt
+constexpr uint32_t kNoEvent = 0xFFFFFFFFu;
+
+M2V_HD inline int x_role(const uint8_t *es, uint64_t n, uint64_t e)
+{
+    const int r = main_role(es, n, e);
+    if (r == rBad && ev_code(e) == 0xB5 && ev_pos(e) + 4 < n && (es[ev_pos(e) + 4] >> 4) == 3u) return rQuant;
+    return r;
+}
+
+// quant_matrix_extension: loads = load_intra | load_non_intra << 1; every loaded weight through weight(matrix, raster index, value)
+template <class Weight>
+M2V_HD inline bool x_quant_extension(const uint8_t *es, uint64_t start, uint64_t end, uint32_t &loads, Weight weight)
+{
+    Bits b = unit_bits(es, start, end);
+    bool ok = get(b, 4) == 3;
+    loads = 0;
+    for (int m = 0; m < 2; ++m) {
+        if (!get(b, 1)) continue;
+        loads |= 1u << m;
+        for (uint32_t k = 0; k < 64u; ++k) {                     // 64 bytes in zig-zag order, 0 forbidden
+            const uint32_t v = get(b, 8);
+            ok = ok && v != 0;
+            weight(m, scan_to_raster(k), v);
+        }
+    }
+    ok = ok && get(b, 2) == 0;                                   // the chroma load flags: 4:2:0 has no chroma matrices
+    return ok && !b.err && tail_zero(b);
+}
+
+// the load flags of an extension the plan accepted, and the weight at zig-zag position k of its matrix m
+M2V_HD inline uint32_t x_quant_loads(const uint8_t *es, uint64_t start, uint64_t end)
+{
+    Bits b = unit_bits(es, start, end);
+    skip(b, 4);
+    const uint32_t li = get(b, 1);
+    if (li) skip(b, 512);
+    return li | get(b, 1) << 1;
+}
+
+M2V_HD inline uint32_t x_quant_weight(const uint8_t *es, uint64_t start, uint64_t end, int m, uint32_t k)
+{
+    Bits b = unit_bits(es, start, end);
+    skip(b, 4);
+    const uint32_t li = get(b, 1);
+    if (m) { if (li) skip(b, 512); skip(b, 1); }
+    skip(b, 8 * (int)(k & 63u));
+    return get(b, 8);
+}
+
+// the matrices in force, as the events that loaded them (kNoEvent: the sequence's): a sequence header puts both back, an accepted
+// quant_matrix_extension replaces what it loads
+struct XMats { uint32_t mi, mn; };
+
+M2V_HD inline void x_mats_event(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, uint32_t i, XMats &s)
+{
+    const int role = x_role(es, n, ev[i]);
+    if (role == rSeq) { s.mi = s.mn = kNoEvent; return; }
+    if (role != rQuant) return;
+    const uint32_t loads = x_quant_loads(es, ev_pos(ev[i]), i + 1 < nev ? ev_pos(ev[i + 1]) : n);
+    if (loads & 1u) s.mi = i;
+    if (loads & 2u) s.mn = i;
+}
+
+// a picture's matrices: what is in force in front of its header, then its own extension (quant: x_picture_params')
+M2V_HD inline XMats x_mats_picture(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, XMats s, uint32_t quant)
+{
+    if (quant != kNoEvent) x_mats_event(es, n, ev, nev, quant, s);
+    return s;
+}
+
+// the weight at raster index t of matrix m (0 intra, 1 non-intra) whose source is event src: a row of the matrix table
+M2V_HD inline uint32_t x_matrix_weight(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, uint32_t src, int m, uint32_t t, const uint8_t *seq_w)
+{
+    if (src == kNoEvent || src >= nev) return seq_w[t & 63u];
+    return x_quant_weight(es, ev_pos(ev[src]), src + 1 < nev ? ev_pos(ev[src + 1]) : n, m, zigzag_position(t));
+}
+
+// il_picture_extension with composite_display_flag 1: v_axis, field_sequence, sub_carrier, burst_amplitude, sub_carrier_phase follow
+M2V_HD inline bool x_picture_extension(const uint8_t *es, uint64_t start, uint64_t end, uint32_t ptype, bool b_pictures, bool interlaced,
+                                       uint32_t progressive_sequence, IPicParams &q)
+{
+    Bits b = unit_bits(es, start, end);
+    bool ok = get(b, 4) == 8;
+    q.b.p.fh = get(b, 4); q.b.p.fv = get(b, 4);
+    q.b.bh = get(b, 4); q.b.bv = get(b, 4);
+    q.b.p.prec = get(b, 2);
+    ok = ok && get(b, 2) == 3;                               // frame picture
+    skip(b, 1);                                              // top_field_first
+    q.field = get(b, 1) ^ 1u;                                // frame_pred_frame_dct
+    ok = ok && get(b, 1) == 0;                               // concealment_motion_vectors
+    q.b.p.qst = get(b, 1);
+    ok = ok && get(b, 1) == 0;                               // intra_vlc_format
+    q.b.p.alt = get(b, 1);
+    skip(b, 2);                                              // repeat_first_field, chroma_420_type
+    const uint32_t progressive_frame = get(b, 1);
+    if (get(b, 1)) skip(b, 20);                              // composite_display_flag and what it announces: read, not acted on
+    ok = ok && (!q.field || (interlaced && il_field_allowed(progressive_sequence, progressive_frame)));
+    ok = ok && main_fcode_ok(q.b.p.fh, ptype) && main_fcode_ok(q.b.p.fv, ptype);
+    if (b_pictures && ptype == 3) ok = ok && q.b.bh >= 1 && q.b.bh <= 9 && q.b.bv >= 1 && q.b.bv <= 9;
+    return ok && !b.err && tail_zero(b);
+}
+
+// event i by its own rule: il_event / bp_event / main_event as the other two options say (P.mbh is theirs), but a coding extension
+// by x_picture_extension, a slice by the grammar above, a quant_matrix_extension behind its picture's coding extension, once
+M2V_HD inline EvInfo x_event(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, uint32_t i, const MainPlan &P, uint64_t last_nz, int prev,
+                             bool b_pictures, bool interlaced)
+{
+    const int role = x_role(es, n, ev[i]);
+    if (role != rPicExt && role != rSlice && role != rQuant) {
+        if (interlaced) return il_event(es, n, ev, nev, i, P, last_nz, prev, b_pictures);
+        return b_pictures ? bp_event(es, n, ev, nev, i, P, last_nz, prev) : main_event(es, n, ev, nev, i, P, last_nz, prev);
+    }
+    EvInfo r{kNone, 0, 0, 0, 0};
+    const uint64_t pos = ev_pos(ev[i]), end = i + 1 < nev ? ev_pos(ev[i + 1]) : n;
+    const int prole = prev >= 0 ? main_role(es, n, ev[prev]) : rBad;
+    bool ok;
+    if (role == rPicExt) {
+        IPicParams q;
+        const int before = i ? main_role(es, n, ev[i - 1]) : rBad;
+        const uint64_t pp = i ? ev_pos(ev[i - 1]) : 0;
+        const uint32_t ptype = before == rPic && pp + 5 < n ? (es[pp + 5] >> 3) & 7u : 0u;
+        ok = before == rPic && x_picture_extension(es, pos, end, ptype, b_pictures, interlaced, P.seq.h.progressive, q) && i + 1 != nev;
+    } else if (role == rQuant) {
+        ok = prole == rPicExt && i + 1 != nev;
+        for (uint32_t j = i; ok && j > (uint32_t)(prev + 1); --j) ok = x_role(es, n, ev[j - 1]) != rQuant;      // (the units between are transparent; ends at the first one found)
+        uint32_t loads;
+        ok = x_quant_extension(es, pos, end, loads, [](int, uint32_t, uint32_t) {}) && ok;
+    } else {
+        const uint32_t c = ev_code(ev[i]), pc = prole == rSlice ? ev_code(ev[prev]) : 0u;
+        ok = c <= P.mbh && ((c == 1u && prole == rPicExt) || (prole == rSlice && (pc == c || pc + 1u == c)));
+        if (i + 1 == nev && ok) ok = main_top(es, n, ev, (int)i, P.mbh);      // no sequence_end_code: the stream ends where a picture may end
+    }
+    if (!ok) r.bad = pos;
+    return r;
+}
+
+// the parameters of the picture whose header is event i of an accepted stream, its first slice's event, its number of slices and
+// its quant_matrix_extension's event (kNoEvent: none)
+M2V_HD inline uint32_t x_picture_params(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, uint32_t i, bool b_pictures, bool interlaced,
+                                        uint32_t progressive_sequence, uint32_t &slice0, uint32_t &nslices, uint32_t &quant)
+{
+    IPicParams q{BPicParams{PicParams{1, 1, 0, 0, 0}, 1, 1}, 0};
+    uint32_t j = i + 2;
+    if (i + 1 < nev) {
+        const uint64_t pos = ev_pos(ev[i]);
+        (void)x_picture_extension(es, ev_pos(ev[i + 1]), i + 2 < nev ? ev_pos(ev[i + 2]) : n, pos + 5 < n ? (es[pos + 5] >> 3) & 7u : 0u, b_pictures, interlaced,
+                                  progressive_sequence, q);
+    }
+    quant = kNoEvent;
+    for (; j < nev && !main_significant(main_role(es, n, ev[j])); ++j)
+        if (quant == kNoEvent && x_role(es, n, ev[j]) == rQuant) quant = j;
+    slice0 = j;
+    for (; j < nev && main_role(es, n, ev[j]) == rSlice; ++j) {}
+    nslices = j - slice0;
+    return il_params_pack(q);
+}
+
+// the picture of slice g of a chunk whose pictures' entries are t[0 .. n) and the slice's number k inside it: the last entry whose
+// sbase (the slices in front of the picture) is not behind g - every picture has a slice, so sbase grows -, as chunk_slice_pic above
+template <class Pic>
+M2V_HD inline uint32_t x_slice_pic(const Pic *t, uint32_t n, uint32_t g, uint32_t &k)
+{
+    const uint32_t base = t[0].sbase;
+    uint32_t a = 0, b = n;
+    while (b - a > 1u) { const uint32_t m = (a + b) / 2u; if (t[m].sbase - base <= g) a = m; else b = m; }
+    k = g - (t[a].sbase - base);
+    return a;
+}
+
+// what a slice's walk leaves for the judge: ok << 31 | code << 16 | first column << 8 | last column (mbw <= 128, code <= 175)
+M2V_HD inline uint32_t x_span_pack(bool ok, uint32_t code, int first, int last)
+{
+    return (ok ? 1u << 31 : 0u) | (code & 255u) << 16 | ((uint32_t)first & 255u) << 8 | ((uint32_t)last & 255u);
+}
+
+// continuity of a readable slice `cur`, slice k of nslices of its picture, behind `front` (k > 0: the span of slice k - 1)
+M2V_HD inline bool x_continuous(uint32_t cur, uint32_t front, uint32_t k, uint32_t nslices, uint32_t mbw)
+{
+    const uint32_t code = (cur >> 16) & 255u, first = (cur >> 8) & 255u, last = cur & 255u;
+    const uint32_t fcode = (front >> 16) & 255u, flast = front & 255u;
+    bool ok;
+    if (k && fcode == code) ok = first == flast + 1u;
+    else ok = first == 0u && (!k || flast == mbw - 1u);
+    return ok && (k + 1u != nslices || last == mbw - 1u);
+}
+
+// main_slice's and bp_slice's records as IMb: frame-based, frame DCT (what BpAnchorSink and IlFrameSink make of them)
+M2V_HD inline IMb x_record(const BMb &m)
+{
+    IMb r{};
+    r.intra = m.intra; r.mc = m.mc; r.cbp = m.cbp; r.qcode = m.qcode; r.skipped = m.skipped; r.dirs = m.dirs;
+    r.mvx = r.mvx1 = m.mvx; r.mvy = r.mvy1 = m.mvy; r.bvx = r.bvx1 = m.bvx; r.bvy = r.bvy1 = m.bvy;
+    r.motion_type = (uint8_t)kFrameBased;
+    return r;
+}
+
+M2V_HD inline IMb x_record(const MainMb &m)
+{
+    BMb r{};
+    r.intra = m.intra; r.mc = m.mc; r.cbp = m.cbp; r.qcode = m.qcode; r.mvx = m.mvx; r.mvy = m.mvy; r.skipped = m.skipped;
+    r.dirs = m.intra ? 0 : (uint8_t)kFwd;
+    return x_record(r);
+}
+
+// one past the last bit that is 1 in bytes [from, end) of the stream, in bits; 8 * from where all are zero
+M2V_HD inline uint64_t x_last_one(const uint8_t *es, uint64_t from, uint64_t end)
+{
+    uint64_t k = end;
+    while (k >= from + 8 && !be64(es, k - 8, end)) k -= 8;   // (the stream's last slice may carry any number of trailing zero bytes)
+    while (k > from && !es[k - 1]) --k;
+    if (k == from) return 8 * from;
+    uint32_t v = es[k - 1], z = 0;
+    while (!(v & 1u)) { v >>= 1; ++z; }
+    return 8 * k - z;
+}
+
+// one slice of a picture of any type, anywhere in macroblock row `row`, through sink.mb(col, IMb, dc) and sink.level: the header with
+// its extras, the first increment as the slice's column, then macroblocks - main_macroblock, bp_macroblock or il_macroblock as the
+// picture says - while anything but zero bits is left.  first / last: the columns of its first and last macroblock.  Every pass moves
+// col forward and col stays below mbw: mbw passes at most
+template <class Sink>
+M2V_HD inline bool x_slice(const uint8_t *es, uint64_t start, uint64_t end, uint32_t ptype, const IPicParams &pp, int mbw, int mbh, int row, Sink &sink,
+                           int &first, int &last)
+{
+    first = last = -1;
+    if (end < start + 4) return false;
+    Bits b = unit_bits(es, start, end);
+    const uint64_t lim = x_last_one(es, start + 4, end);
+    uint32_t qcode = get(b, 5);
+    if (get(b, 1)) {                                         // intra_slice_flag
+        skip(b, 8);                                          // intra_slice, reserved_bits
+        while (get(b, 1)) skip(b, 8);                        // extra_bit_slice, extra_information_slice (a read past the unit is 0)
+    }
+    if (b.err) return false;
+    SliceState s{{0, 0, 0}, {0, 0}};                         // s.pmv: PMV[0][0] of a picture with frame_pred_frame_dct 1
+    int32_t pmv[2][2][2] = {{{0, 0}, {0, 0}}, {{0, 0}, {0, 0}}};      // PMV[r][s]; with frame_pred_frame_dct 1 only PMV[0][1] of it
+    uint32_t dirs = 0;                                       // of the macroblock in front; 0: intra
+    int col = -1;
+    const int32_t none[6] = {0, 0, 0, 0, 0, 0};
+    while (b.pos < lim) {
+        int incr = 0;
+        uint32_t e;
+        for (;;) {
+            e = vlc_increment(peek(b, 11));
+            if (!e) return false;
+            skip(b, (int)(e & 255u));
+            if ((e >> 8) != 34u) break;
+            incr += 33;                                      // macroblock_escape
+            if (col + incr >= mbw) return false;
+        }
+        incr += (int)(e >> 8);
+        if (col + incr >= mbw || b.err) return false;
+        if (col < 0) {                                       // the slice's place: nothing is skipped in front of it
+            first = incr - 1;
+        } else if (incr > 1) {                               // 7.6.6: skipped - frame prediction, no residual
+            if (ptype == 1) return false;
+            IMb z{};
+            z.skipped = 1; z.qcode = (uint8_t)qcode; z.motion_type = (uint8_t)kFrameBased;
+            if (ptype == 2) {                                // the zero vector, the predictors reset
+                z.dirs = (uint8_t)kFwd;
+                s.pmv[0] = s.pmv[1] = 0;
+                for (int r = 0; r < 2; ++r) for (int d = 0; d < 2; ++d) pmv[r][d][0] = pmv[r][d][1] = 0;
+            } else {                                         // the directions in front, PMV[0][s] as frame vectors
+                if (!dirs) return false;
+                z.dirs = (uint8_t)dirs; z.mc = (dirs & kFwd) != 0;
+                if (dirs & kFwd) il_frame_vectors(z, 0, pp.field ? pmv[0][0] : s.pmv);
+                if (dirs & kBwd) il_frame_vectors(z, 1, pmv[0][1]);
+            }
+            for (int k = 1; k < incr; ++k) {
+                if (!il_inside(col + k, row, z, mbw, mbh)) return false;
+                sink.mb(col + k, z, none);
+            }
+            for (int c = 0; c < 3; ++c) s.dc_pred[c] = 0;
+        }
+        col += incr;
+        IMb m;
+        int32_t dc[6];
+        auto put = [&](int blk, uint32_t i, int32_t l) { sink.level(col, blk, i, l); };
+        if (pp.field) {
+            if (!il_macroblock(b, ptype, pp, s, pmv, qcode, m, dc, put)) return false;
+        } else if (ptype == 3) {
+            BMb bm;
+            if (!bp_macroblock(b, pp.b, s, pmv[0][1], qcode, bm, dc, put)) return false;
+            m = x_record(bm);
+        } else {
+            MainMb mm;
+            if (!main_macroblock(b, ptype, pp.b.p, s, qcode, mm, dc, put)) return false;
+            m = x_record(mm);
+        }
+        if (!il_inside(col, row, m, mbw, mbh)) return false;
+        m.qcode = (uint8_t)qcode;
+        dirs = m.dirs;
+        sink.mb(col, m, dc);
+    }
+    last = col;
+    return !b.err && col >= 0;
+}
+
 }  // namespace dec
 }  // namespace m2v

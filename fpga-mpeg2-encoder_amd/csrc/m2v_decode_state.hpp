@@ -49,4 +49,17 @@ void dec_i_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long 
 void dec_i_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_t *dst, int layout, const m2v_decode_stat &R, size_t mbh, size_t B,
                   const uint8_t *types, uint32_t *h_list, m2v_decode_stat *h_rec);
 
+// Several slices a row, slice header extras, quant_matrix_extension, composite_display_flag 1 (option "decode_extended";
+// m2v_decode_x.hip), with "decode_b_pictures" and "decode_interlaced" 0 or 1 each: the table behind the matrices holds DecBPic's fields,
+// then the slice table - the picture's slices are the events [slice0, slice0 + nslices), sbase of them lie in front of it in the stream -
+// and the events whose quant_matrix_extension loaded the intra / non-intra matrix in force (0xFFFFFFFF: the sequence's).  The plan leaves
+// h_sl[p] = sbase of picture p and h_sl[pictures] = all slices (pinned): a chunk's slice walk is launched over its slices.  e->d_dec_x
+// holds the matrix table (128 bytes a picture) and the spans of the chunk's slices
+struct DecXPic { uint32_t slice0, params, display, fwd, bwd, nslices, sbase, mi, mn; };      // params: dec::il_params_pack
+
+void dec_x_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long long *ev, DecState *st, DecPic *pics, uint32_t pic_cap, uint8_t *h_types,
+                unsigned long long cap, int probe, m2v_decode_stat *h_rec, uint8_t *d_main, int b_pictures, int interlaced, uint32_t *h_mbh, uint32_t *h_sl);
+void dec_x_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_t *dst, int layout, const m2v_decode_stat &R, size_t mbh, size_t B,
+                  const uint8_t *types, uint32_t *h_list, const uint32_t *h_sl, m2v_decode_stat *h_rec);
+
 }  // namespace m2v

@@ -282,20 +282,24 @@ def sequence_headers(data):
     return _sequence_headers(BitReader(data))
 
 
-def decode(data, quirks=True, syntax="module", b_pictures=False, interlaced=False):
+def decode(data, quirks=True, syntax="module", b_pictures=False, interlaced=False, extended=False):
     """syntax="module" (the default): the subset this encoder emits, as the head of this file says.  syntax="main": Main-Profile
     streams of progressive frame pictures, I and P, 4:2:0, from any encoder (decode_main below); it needs quirks=False, and a
     refusal is a Refused exception that names the unit.  b_pictures=True (syntax="main" only): B pictures too, and the frames in
     display order (the section "B pictures" below); with False the function is what it was for every input.  interlaced=True
     (syntax="main" only, with b_pictures either way): frame pictures with frame_pred_frame_dct 0 too (the section "Interlaced frame
-    pictures" below); with False the function is what it was for every input."""
+    pictures" below); with False the function is what it was for every input.  extended=True (syntax="main" only, with the other two
+    either way): several slices in a macroblock row, slice headers with intra_slice_flag 1, quant_matrix_extension and
+    composite_display_flag 1 too (the section "Several slices a row" below); with False the function is what it was for every input."""
+    if extended and syntax != "main":
+        raise ValueError("extended goes with syntax=\"main\"")
     if b_pictures and syntax != "main":
         raise ValueError("b_pictures goes with syntax=\"main\"")
     if interlaced and syntax != "main":
         raise ValueError("interlaced goes with syntax=\"main\"")
     if syntax == "main":
         assert not quirks, "the module's quirks have no meaning outside its own syntax"
-        return decode_main(data, b_pictures, interlaced)
+        return decode_main(data, b_pictures, interlaced, extended)
     assert syntax == "module", syntax
     T = tables()
     br = BitReader(data)
@@ -547,11 +551,13 @@ def psnr(a, b):
 # Beyond the module's syntax: f_code 1 .. 9, intra_dc_precision 0 .. 3, both quantiser scale tables, both scans, matrices loaded in the
 # sequence header, every macroblock type of tables B-2 / B-3, macroblock quantisers, address increments with skipped macroblocks;
 # optional sequence_display_extension, GOP header and sequence_end_code; user_data, copyright_extension and
-# picture_display_extension skipped where 6.2.2.2 allows them; trailing zero bytes.  Still refused: B and D pictures, field pictures,
-# frame_pred_frame_dct 0, concealment vectors, intra_vlc_format 1, quant_matrix_extension, scalable and size extensions, sizes over
-# 2048, other chroma formats, several slices in a row, a first increment other than 1, skipped macroblocks in an I picture or at a row's
-# end, an increment past the row's end, composite_display_flag 1 (its 20 bits are not read: they fail the zero-stuffing check), a slice
-# with intra_slice_flag 1 (the bit behind quantiser_scale_code), vectors that read outside the picture.
+# picture_display_extension skipped where 6.2.2.2 allows them; trailing zero bytes.  Still refused: leading B and D pictures, field
+# pictures, dual prime, concealment vectors, intra_vlc_format 1, scalable and size extensions, sizes over 2048, other chroma formats,
+# skipped macroblocks in an I picture, an increment past the row's end, vectors that read outside the picture.  Refused unless their
+# keyword is on (the sections below): B pictures (b_pictures); frame_pred_frame_dct 0 (interlaced); several slices in a row, a first
+# increment other than 1, a row that ends short, a slice with intra_slice_flag 1 (the bit behind quantiser_scale_code),
+# quant_matrix_extension, composite_display_flag 1 - without the keyword its 20 bits are not read and fail the zero-stuffing check
+# (extended).
 #
 # The stream is cut at its start codes first (a start code prefix is unique in a stream: 6.2.1), the units are judged by the grammar
 # of 6.2.2 - each by what it is and by the unit in front of it that is not skipped -, and then the pictures are decoded.  A refusal
@@ -609,6 +615,35 @@ def psnr(a, b):
 # Decoded.mbs of such a picture carry motion_type, dct_type, selects[s][r] and vectors[s][r] besides the fields above.  Still
 # refused: field pictures, dual prime, concealment vectors.  Every stream accepted with interlaced=False decodes to the same frames
 # and fields with True, but for the macroblock-row exception above.
+# ---------------------------------------------------------------------------------------------------------------
+#
+# Several slices a row (extended=True; option "decode_extended" of the device decoder; b_pictures and interlaced either way).  Added
+# (6.2.4, 6.3.16: the restricted slice structure Main Profile requires; 6.2.3.2, 6.3.11):
+#   slices      a picture is any number of slices, 1 <= slice code <= mbh (mbh as the other options define it).  The grammar stays
+#               local: the first slice behind a picture's extensions has code 1, every further one its predecessor's code or that code
+#               + 1, and a picture may end only behind a slice with code mbh.  A slice's first macroblock_address_increment, escapes
+#               included, gives its first column as increment - 1; nothing is skipped in front of it.  The macroblock loop runs until
+#               nothing but zero bits is left in the unit (the standard's test of 23 zero bits gives the same verdict: 23 zero bits
+#               begin no macroblock).  A slice without a macroblock is refused, and one whose column passes mbw - 1.  DC predictors and
+#               all vector predictors reset at every slice start; skipped macroblocks inside a slice are what each picture type defines
+#   continuity  judged behind the walk: the first slice of a row starts at column 0 and the row in front of it is full; a slice with its
+#               predecessor's code starts at the predecessor's last column + 1; the picture's last slice ends at column mbw - 1.  A slice
+#               that breaks one of these is refused at its own start code.  Refused.offset stays the earliest unit the grammar refuses,
+#               else the earliest slice in error - one that cannot be read or one that breaks continuity (a slice behind an unreadable one
+#               is not judged: the unreadable one is earlier)
+#   header      behind quantiser_scale_code a bit 1 is intra_slice_flag: intra_slice (1 bit) and reserved_bits (7 bits) follow, read and
+#               not judged; then, while the next bit is 1, extra_bit_slice and extra_information_slice (8 bits, skipped); then the
+#               closing 0.  With intra_slice_flag 0 the header is as it was
+#   matrices    quant_matrix_extension (identifier 3) among the units that may follow a picture_coding_extension, in any order with
+#               user_data, copyright_extension and picture_display_extension; one a picture at most (a second is refused at the second),
+#               anywhere else refused at its start code.  load_intra_quantiser_matrix and load_non_intra_quantiser_matrix with 64 bytes
+#               each in zig-zag order (a weight of 0 refuses the unit), the two chroma load flags 0 (4:2:0 only), zero stuffing.  A
+#               loaded matrix is in force from that picture on in coded order, each matrix on its own; any sequence header, repeated
+#               ones included, puts both back to the sequence's
+#   composite   composite_display_flag 1: the 20 bits behind it are read and not acted on
+# Still refused: field pictures, dual prime, concealment vectors, Table B-15, leading B pictures, D pictures, and everything else the
+# main syntax refuses, where it is refused.  Every stream accepted with extended=False, under any setting of the other two, decodes to
+# the same frames and fields with True.
 # ---------------------------------------------------------------------------------------------------------------
 class Refused(Exception):
     def __init__(self, offset, why=""):
@@ -673,6 +708,13 @@ class _UnitBits(BitReader):
         pad = (-self.pos) & 7
         return (self.bits(pad) == 0 if pad else True) and not any(self.d[self.pos >> 3:self.end >> 3])
 
+    def only_zeros_left(self):
+        """rest_is_zero without moving: whether nothing but zero bits is left in the unit"""
+        at = self.pos
+        zero = self.rest_is_zero()
+        self.pos = at
+        return zero
+
 
 def start_codes(data):
     """[(offset, code)] of every 00 00 01 xx whose code byte lies inside the stream"""
@@ -728,7 +770,7 @@ def _main_display_extension(data, start, end, h):
     assert br.rest_is_zero()
 
 
-def _main_picture_extension(data, start, end, ptype, b_pictures=False, interlaced=False, progressive_sequence=1):
+def _main_picture_extension(data, start, end, ptype, b_pictures=False, interlaced=False, progressive_sequence=1, extended=False):
     br = _UnitBits(data, start, end)
     assert br.bits(4) == 8
     pic = dict(f_code=[br.bits(4) for _ in range(4)])
@@ -745,14 +787,34 @@ def _main_picture_extension(data, start, end, ptype, b_pictures=False, interlace
     if b_pictures and ptype == 3:
         for f in pic["f_code"][2:]:
             assert 1 <= f <= 9, "f_code"
+    if extended and pic["composite_display_flag"]:              # v_axis, field_sequence, sub_carrier, burst_amplitude, sub_carrier_phase
+        br.bits(20)
     assert br.rest_is_zero()
     return pic
 
 
-_SEQ, _SEQEXT, _DISP, _GOP, _PIC, _PICEXT, _SLICE, _END, _USER, _SKIPPED_EXT, _BAD = range(11)
+def _main_quant_extension(data, start, end):
+    """quant_matrix_extension (6.2.3.2) -> [intra matrix or None, non-intra matrix or None], raster order"""
+    br = _UnitBits(data, start, end)
+    assert br.bits(4) == 3
+    zz = tables()["zz"]
+    out = [None, None]
+    for m in range(2):
+        if br.bits(1):                                          # load_..._quantiser_matrix: 64 bytes in zig-zag order
+            w = [0] * 64
+            for k in range(64):
+                w[int(zz[k])] = br.bits(8)
+                assert w[int(zz[k])] != 0, "a matrix weight of 0 is forbidden"
+            out[m] = w
+    assert br.bits(1) == 0 and br.bits(1) == 0, "chroma matrices belong to 4:2:2 and 4:4:4"
+    assert br.rest_is_zero()
+    return out
 
 
-def _main_role(data, pos, code):
+_SEQ, _SEQEXT, _DISP, _GOP, _PIC, _PICEXT, _SLICE, _END, _USER, _SKIPPED_EXT, _BAD, _QUANT = range(12)
+
+
+def _main_role(data, pos, code, extended=False):
     if code == 0xB3:
         return _SEQ
     if code == 0xB8:
@@ -765,6 +827,8 @@ def _main_role(data, pos, code):
         return _SLICE
     if code == 0xB2:
         return _USER
+    if extended and code == 0xB5 and pos + 4 < len(data) and data[pos + 4] >> 4 == 3:
+        return _QUANT                                           # quant_matrix_extension
     if code == 0xB5 and pos + 4 < len(data):                    # extension_start_code_identifier
         return {1: _SEQEXT, 2: _DISP, 8: _PICEXT, 4: _SKIPPED_EXT, 7: _SKIPPED_EXT}.get(data[pos + 4] >> 4, _BAD)
     return _BAD
@@ -777,14 +841,14 @@ def _main_mbh(hdr, interlaced=False):
     return (hdr["height"] + 15) // 16
 
 
-def _main_plan(data, b_pictures=False, interlaced=False):
+def _main_plan(data, b_pictures=False, interlaced=False, extended=False):
     """the grammar over the start codes -> (sequence fields, pictures, gops, repeated headers, number of start codes)"""
     n = len(data)
     ev = start_codes(data)
     if not ev or any(data[:ev[0][0]]):
         raise Refused(0, "no start code, or something in front of the first")
     ends = [p for p, _ in ev[1:]] + [n]
-    roles = [_main_role(data, p, c) for p, c in ev]
+    roles = [_main_role(data, p, c, extended) for p, c in ev]
     last_nz = len(data.rstrip(b"\x00"))                         # one past the last byte that is not zero
 
     def group(i):
@@ -824,6 +888,8 @@ def _main_plan(data, b_pictures=False, interlaced=False):
     prev = None                                                 # the unit in front that is not skipped
     have_i = False
     anchors = 0
+    mats = [first["intra_matrix"], first["non_intra_matrix"]]   # the matrices in force (extended: a quant_matrix_extension replaces them)
+    quant_seen = False
     for i, (pos, code) in enumerate(ev):
         role, end = roles[i], ends[i]
         prole = roles[prev] if prev is not None else None
@@ -840,6 +906,7 @@ def _main_plan(data, b_pictures=False, interlaced=False):
                     else:
                         ok = top and again == first             # 6.1.1.6: it says what the first one said, matrices included
                         repeats += 1
+                        mats = [first["intra_matrix"], first["non_intra_matrix"]]
             elif role == _SEQEXT:
                 ok = i > 0 and roles[i - 1] == _SEQ             # (read with its sequence header)
             elif role == _DISP:
@@ -849,6 +916,13 @@ def _main_plan(data, b_pictures=False, interlaced=False):
                 ok = prole in (_SEQEXT, _DISP, _GOP, _PICEXT)
             elif role == _SKIPPED_EXT:                          # extension_data(2): copyright_extension, picture_display_extension
                 ok = prole == _PICEXT
+            elif role == _QUANT:                                # extension_data(2): at most one quant_matrix_extension a picture
+                ok = prole == _PICEXT and not quant_seen
+                quant_seen = True
+                loaded = _main_quant_extension(data, pos, end)
+                if ok and pictures:
+                    mats = [loaded[m] if loaded[m] is not None else mats[m] for m in range(2)]
+                    pictures[-1]["matrices"] = mats
             elif role == _GOP:
                 ok = top
                 br = _UnitBits(data, pos, end)
@@ -876,22 +950,26 @@ def _main_plan(data, b_pictures=False, interlaced=False):
                 if pic["type"] == 3 and anchors < 2:
                     bad.append(pos)                             # a B picture without two anchors in front of it
                 anchors += pic["type"] != 3
+                pic["matrices"] = mats
                 pictures.append(pic)
             elif role == _PICEXT:
                 ok = i > 0 and roles[i - 1] == _PIC
                 ptype = (data[ev[i - 1][0] + 5] >> 3) & 7 if ok and ev[i - 1][0] + 5 < n else 0
-                ext = _main_picture_extension(data, pos, end, ptype, b_pictures, interlaced, first["progressive_sequence"])
+                quant_seen = False
+                ext = _main_picture_extension(data, pos, end, ptype, b_pictures, interlaced, first["progressive_sequence"], extended)
                 if ok and pictures and pictures[-1]["unit"] == i - 1:
                     pictures[-1].update(ext)
             elif role == _SLICE:
                 ok = code <= mbh and (prole == _PICEXT if code == 1 else prole == _SLICE and ev[prev][1] == code - 1)
+                if extended:                                    # the first has code 1, a further one its predecessor's code or that + 1
+                    ok = code <= mbh and ((code == 1 and prole == _PICEXT) or (prole == _SLICE and ev[prev][1] in (code, code - 1)))
                 if ok and pictures:
                     pictures[-1]["slices"].append(i)
             else:                                               # sequence_end_code: the last one, only zeros behind it
                 ok = top and i + 1 == len(ev) and last_nz <= pos + 4
         except Exception:
             ok = False
-        if role not in (_USER, _SKIPPED_EXT, _BAD):
+        if role not in (_USER, _SKIPPED_EXT, _BAD, _QUANT):
             prev = i
         if i + 1 == len(ev) and role != _END and ok:            # no sequence_end_code: the stream ends where a picture does
             prole = roles[prev] if prev is not None else None
@@ -934,10 +1012,10 @@ def display_order(types):
     return out
 
 
-def decode_main(data, b_pictures=False, interlaced=False):
+def decode_main(data, b_pictures=False, interlaced=False, extended=False):
     data = bytes(data)
     T, TM = tables(), _main_tables()
-    hdr, pictures, gops, repeats, ev, ends = _main_plan(data, b_pictures, interlaced)
+    hdr, pictures, gops, repeats, ev, ends = _main_plan(data, b_pictures, interlaced, extended)
     out = Decoded()
     out.width, out.height, out.sequence, out.gops, out.repeated_headers, out.units = hdr["width"], hdr["height"], hdr, gops, repeats, len(ev)
     mbw, mbh = (out.width + 15) // 16, _main_mbh(hdr, interlaced)
@@ -948,6 +1026,8 @@ def decode_main(data, b_pictures=False, interlaced=False):
     before = None                                               # the anchor before the last one: a B picture's forward reference
     for pic in pictures:
         out.pictures.append(pic)
+        if extended:
+            WI, WN = pic["matrices"]
         scan = TM["alt"] if pic["alternate_scan"] else T["zz"]
         dc_mult = 8 >> pic["intra_dc_precision"]
         Y = np.zeros((H, W), np.int64)
@@ -1062,11 +1142,28 @@ def decode_main(data, b_pictures=False, interlaced=False):
                 res.append(r)
             return res
 
+        def slice_extras(br):
+            """behind quantiser_scale_code: extra_bit_slice 0 - or, extended, intra_slice_flag 1 with intra_slice, reserved_bits and
+            any number of extra_information_slice bytes, each behind an extra_bit_slice 1, closed by a 0"""
+            if not extended:
+                assert br.bits(1) == 0                          # extra_bit_slice
+                return
+            if br.bits(1):                                      # intra_slice_flag
+                br.bits(8)                                      # intra_slice, reserved_bits: read, not judged
+                while br.bits(1):
+                    br.bits(8)
+
+        def more(br, col):
+            """whether another macroblock follows: up to the row's end - or, extended, while anything but zero bits is left"""
+            return col < mbw - 1 if not extended else not br.only_zeros_left()
+
+        span = []                                               # extended: the columns of the slice's first and last macroblock
+
         def il_slice(br, row):
             """a slice of a picture with frame_pred_frame_dct 0, of any type (the section "Interlaced frame pictures" above)"""
             qcode = br.bits(5)
             qcodes.append(qcode)
-            assert br.bits(1) == 0                              # extra_bit_slice
+            slice_extras(br)
             ptype = pic["type"]
             refs = (ref, None) if ptype == 2 else (before, ref)  # the anchor of direction s
             dc_pred, col = [0, 0, 0], -1
@@ -1087,7 +1184,7 @@ def decode_main(data, b_pictures=False, interlaced=False):
                     m.update(fwd=bool(used[0]), bwd=bool(used[1]), mv_b=m["vectors"][1][0] if used[1] else (0, 0))
                 mbs.append(m)
 
-            while col < mbw - 1:
+            while more(br, col):
                 incr = 0
                 while True:                                     # macroblock_escape adds 33 (6.3.16)
                     sym = TM["incr"](br)
@@ -1096,8 +1193,11 @@ def decode_main(data, b_pictures=False, interlaced=False):
                     incr += 33
                     assert col + incr < mbw, "an increment passes the row's end"
                 incr += sym
-                assert incr == 1 or col >= 0, "a slice starts at the row's first macroblock"
+                assert extended or incr == 1 or col >= 0, "a slice starts at the row's first macroblock"
                 assert col + incr < mbw, "an increment passes the row's end"
+                if extended and col < 0:                        # the first increment places the slice: nothing is skipped in front of it
+                    col, incr = incr - 2, 1
+                    span[:] = [col + 1, col + 1]
                 for k in range(1, incr):                        # 7.6.6: frame prediction, whatever the macroblock in front was
                     assert ptype != 1, "no macroblock is skipped in an I picture"
                     dc_pred = [0, 0, 0]
@@ -1112,6 +1212,7 @@ def decode_main(data, b_pictures=False, interlaced=False):
                         record(skipped=True, mc=bool(dirs[0]), mv=vecs[0] if dirs[0] else (0, 0), used=dirs,
                                vectors=tuple((vecs[s], vecs[s]) if dirs[s] else ((0, 0), (0, 0)) for s in (0, 1)))
                 col += incr
+                span[1:] = [col]
                 bwd = 0
                 if ptype == 3:
                     quant, mc, bwd, pattern, intra = TM["type_b"](br)
@@ -1165,20 +1266,39 @@ def decode_main(data, b_pictures=False, interlaced=False):
                 record(intra=bool(intra), mc=bool(mc), mv=vec[0][0] if mc else (0, 0), cbp=cbp, qcode=qcode, motion_type=motion_type, dct_type=dct_type,
                        used=used, selects=tuple(tuple(x) for x in sel), vectors=tuple(tuple(x) for x in vec))
 
+        front = []                                              # extended: [code, last column] of the slice in front
+
+        def continuity(unit):
+            """extended, behind a slice's walk: it has a macroblock; the first slice of a row starts at column 0 behind a row that is
+            full, a further one where the slice in front ended; the picture's last slice ends the row"""
+            code = ev[unit][1]
+            assert span, "a slice without a macroblock"
+            if front and front[0] == code:
+                assert span[0] == front[1] + 1, "a gap or an overlap between two slices of a row"
+            else:
+                assert span[0] == 0 and (not front or front[1] == mbw - 1), "a row's first slice starts at column 0, behind a full row"
+            assert unit != pic["slices"][-1] or span[1] == mbw - 1, "the picture's last slice ends short"
+            front[:] = [code, span[1]]
+
         for row, unit in enumerate(pic["slices"]):
             pos = ev[unit][0]
+            if extended:                                        # the slice's code names its row
+                row = ev[unit][1] - 1
+                del span[:]
             try:
                 br = _UnitBits(data, pos, ends[unit])
                 if interlaced and not pic["frame_pred_frame_dct"]:
                     il_slice(br, row)
                     assert br.rest_is_zero(), "only zero stuffing may follow the row's last macroblock"
+                    if extended:
+                        continuity(unit)
                     continue
                 qcode = br.bits(5)
                 qcodes.append(qcode)
-                assert br.bits(1) == 0                          # extra_bit_slice
+                slice_extras(br)
                 dc_pred, pmv, col = [0, 0, 0], [0, 0], -1
                 pmvs, dirs = [[0, 0], [0, 0]], None             # a B picture's two predictors; the directions of the macroblock in front (None: intra, or none)
-                while col < mbw - 1:
+                while more(br, col):
                     incr = 0
                     while True:                                 # macroblock_escape adds 33 (6.3.16)
                         sym = TM["incr"](br)
@@ -1187,8 +1307,11 @@ def decode_main(data, b_pictures=False, interlaced=False):
                         incr += 33
                         assert col + incr < mbw, "an increment passes the row's end"
                     incr += sym
-                    assert incr == 1 or col >= 0, "a slice starts at the row's first macroblock"
+                    assert extended or incr == 1 or col >= 0, "a slice starts at the row's first macroblock"
                     assert col + incr < mbw, "an increment passes the row's end"
+                    if extended and col < 0:                    # the first increment places the slice: nothing is skipped in front of it
+                        col, incr = incr - 2, 1
+                        span[:] = [col + 1, col + 1]
                     for k in range(1, incr) if pic["type"] == 3 else ():      # skipped in a B picture (7.6.6): the directions and vectors in front
                         assert dirs is not None, "a skipped macroblock behind an intra macroblock"
                         dc_pred = [0, 0, 0]
@@ -1201,6 +1324,7 @@ def decode_main(data, b_pictures=False, interlaced=False):
                         store(col + k, row, predict_into(col + k, row, (0, 0)), [np.zeros(64, np.int64)] * 6)
                         mbs.append(dict(intra=False, mc=False, skipped=True, mv=(0, 0), cbp=0, qcode=qcode))
                     col += incr
+                    span[1:] = [col]
                     bwd = 0
                     if pic["type"] == 3:
                         quant, mc, bwd, pattern, intra = TM["type_b"](br)
@@ -1290,6 +1414,8 @@ def decode_main(data, b_pictures=False, interlaced=False):
                     if pic["type"] == 3:
                         mbs[-1].update(fwd=bool(mc), bwd=bool(bwd), mv_b=tuple(pmvs[1]) if bwd else (0, 0))
                 assert br.rest_is_zero(), "only zero stuffing may follow the row's last macroblock"
+                if extended:
+                    continuity(unit)
             except Refused:
                 raise
             except Exception as e:

@@ -967,15 +967,15 @@ int m2v_mux_scan_tile(void);
  *   sequence  load_intra_quantiser_matrix / load_non_intra_quantiser_matrix: 64 bytes each, zig-zag order, 0 forbidden
  *   macroblock  macroblock_address_increment (Table B-1) with macroblock_escape; skipped macroblocks in P pictures (7.6.6); all of
  *             Tables B-2 and B-3; a macroblock's quantiser_scale_code replaces the slice's (0 is refused)
- * Still M2V_DEC_SYNTAX in the main syntax, the follow-ups: B pictures with option "decode_b_pictures" off (below), leading B pictures
- * (fewer than two anchors in front of them) with it on, and D pictures; field pictures and frame_pred_frame_dct 0; concealment
- * vectors; intra_vlc_format 1 (Table B-15 has no second source here to be checked against); quant_matrix_extension and every scalable
- * extension; size extensions and sizes over 2048; chroma formats other than 4:2:0; more than one slice in a macroblock row, or a slice
- * whose first increment is not 1; a skipped macroblock in an I picture or as the last of a row; an increment that passes the row's
- * end; composite_display_flag 1 (its 20 bits behind the picture_coding_extension's flags are read as stuffing that is not zero);
- * a slice with intra_slice_flag 1 (the bit behind quantiser_scale_code: intra_slice, reserved bits and extra information are not
- * read) - ordinary encoders may write either; vectors that read outside the picture; and every check the module syntax makes on
- * codes, coefficient indices and stuffing inside a slice.  The batch entry for the main syntax is m2v_decode_streams_main_device, below.
+ * Still M2V_DEC_SYNTAX in the main syntax, the follow-ups: leading B pictures (fewer than two anchors in front of them) and D pictures;
+ * field pictures; dual prime; concealment vectors; intra_vlc_format 1 (Table B-15 has no second source here to be checked against);
+ * every scalable extension; size extensions and sizes over 2048; chroma formats other than 4:2:0; a skipped macroblock in an I picture;
+ * an increment that passes the row's end; vectors that read outside the picture; and every check the module syntax makes on codes,
+ * coefficient indices and stuffing inside a slice.  Refused unless their option is on (each below): B pictures ("decode_b_pictures");
+ * frame_pred_frame_dct 0 ("decode_interlaced"); more than one slice in a macroblock row, a slice whose first increment is not 1 or
+ * whose row ends short, a slice header with intra_slice_flag 1, quant_matrix_extension and composite_display_flag 1 (without the option
+ * its 20 bits are read as stuffing that is not zero) ("decode_extended").  The batch entry for the main syntax is
+ * m2v_decode_streams_main_device, below.
  *
  * Option "decode_b_pictures" (m2v_set_option), per handle: 0 (the default) - everything above, bit for bit, launch for launch and
  * refusal for refusal (a B picture is M2V_DEC_SYNTAX at its picture header); 1 - B pictures are decoded too, and the frames come out
@@ -1035,6 +1035,41 @@ int m2v_mux_scan_tile(void);
  *             PMV[0][s] read as frame vectors - behind a field-based macroblock twice its first field vector's vertical component
  * Still M2V_DEC_SYNTAX with the option on, the follow-ups: field pictures (picture_structure 1 and 2); dual prime; concealment
  * vectors; and everything else the main syntax refuses.
+ *
+ * Option "decode_extended" (m2v_set_option), per handle: 0 (the default) - everything above, bit for bit, launch for launch and
+ * refusal for refusal; 1 - several slices in a macroblock row, slice headers with intra_slice_flag 1, quant_matrix_extension and
+ * composite_display_flag 1 are read too.  Any other value is M2V_E_PARAM.  With 1, "decode_syntax" must be M2V_SYNTAX_MAIN and `mode`
+ * M2V_DEC_ISO: otherwise m2v_decode_device returns M2V_E_PARAM, writes nothing and m2v_last_error names the option;
+ * m2v_decode_streams_device is what it was.  It combines with "decode_b_pictures" and "decode_interlaced" in all four settings.  The
+ * definition is decoder.decode(stream, quirks=False, syntax="main", b_pictures=..., interlaced=..., extended=True).  Every stream the
+ * main syntax accepts with the option off, under any setting of the other two, decodes with it on to the same bytes and the same
+ * record.  Added (6.2.4, 6.3.16: the restricted slice structure Main Profile requires; 6.2.3.2, 6.3.11):
+ *   slices    a picture is any number of slices, 1 <= slice code <= the macroblock rows (as the other options define them).  The
+ *             grammar stays local: the first slice behind a picture's extensions has code 1, every further one its predecessor's
+ *             code or that code + 1, and a picture may end only behind a slice with the last row's code.  A slice's first
+ *             macroblock_address_increment, escapes included, gives its first column as increment - 1; nothing is skipped in front
+ *             of it.  The macroblock loop runs until nothing but zero bits is left in the unit (the standard's test of 23 zero bits
+ *             gives the same verdict: 23 zero bits begin no macroblock).  A slice without a macroblock is refused, and one whose
+ *             column passes the row's last.  DC predictors and all vector predictors reset at every slice start; skipped
+ *             macroblocks inside a slice are what each picture type defines above
+ *   continuity  judged behind the walk: the first slice of a row starts at column 0 and the row in front of it is full; a slice with
+ *             its predecessor's code starts at the predecessor's last column + 1; the picture's last slice ends at the row's last
+ *             column.  A slice that breaks one of these is refused at its own start code.  err_offset stays the earliest unit the
+ *             grammar refuses, else the earliest slice in error - one that cannot be read or one that breaks continuity (a slice behind
+ *             an unreadable one is not judged: the unreadable one is earlier).  Nothing of a chunk with such a slice is written
+ *   header    behind quantiser_scale_code a bit 1 is intra_slice_flag: intra_slice (1 bit) and reserved_bits (7 bits) follow, read
+ *             and not judged; then, while the next bit is 1, extra_bit_slice and extra_information_slice (8 bits, skipped); then the
+ *             closing 0.  With intra_slice_flag 0 the header is as above
+ *   matrices  quant_matrix_extension (identifier 3) among the units that may follow a picture_coding_extension, in any order with
+ *             user_data, copyright_extension and picture_display_extension; one a picture at most (a second is refused at the
+ *             second), anywhere else refused at its start code.  load_intra_quantiser_matrix and load_non_intra_quantiser_matrix
+ *             with 64 bytes each in zig-zag order (a weight of 0 refuses the unit), the two chroma load flags 0 (4:2:0 only), zero
+ *             stuffing.  A loaded matrix is in force from that picture on in CODED order, each matrix on its own; any sequence header,
+ *             repeated ones included, puts both back to the sequence's
+ *   composite  composite_display_flag 1: the 20 bits behind it are read and not acted on
+ * Out of scope, the follow-ups: m2v_decode_streams_main_device keeps its two flags (any other bit stays M2V_E_PARAM); field pictures,
+ * dual prime, concealment vectors, Table B-15, leading B pictures and D pictures stay refused, and everything else the main syntax
+ * refuses stays refused where it is refused without the option.
  */
 enum { M2V_DEC_ISO = 0, M2V_DEC_MODULE = 1 };
 enum { M2V_SYNTAX_MODULE = 0, M2V_SYNTAX_MAIN = 1 };                            /* option "decode_syntax" */
