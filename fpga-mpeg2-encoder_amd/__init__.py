@@ -735,7 +735,7 @@ class Mpeg2Encoder:
         self._chk(self._L.m2v_set_option(self._h, name.encode(), int(value)), "m2v_set_option(%s)" % name)
         if name == "stats":
             self._set[name] = bool(value)
-        if name in ("gop_bytes_max", "scene_cut", "decode_syntax", "decode_b_pictures", "decode_interlaced", "decode_extended"):
+        if name in ("gop_bytes_max", "scene_cut", "decode_syntax", "decode_b_pictures", "decode_interlaced", "decode_extended", "decode_mb_tools"):
             self._set[name] = int(value)
 
     def _set_list(self, key, values, ctype, what):
@@ -916,7 +916,7 @@ class Mpeg2Encoder:
         self._chk(self._L.m2v_decode_report(self._h, out.ctypes.data), "m2v_decode_report")
         return out[0]
 
-    def decode_device(self, es, layout="i420", mode="iso", out=None, container=None, stream=None, syntax="module", b_pictures=False, interlaced=False, extended=False):
+    def decode_device(self, es, layout="i420", mode="iso", out=None, container=None, stream=None, syntax="module", b_pictures=False, interlaced=False, extended=False, mb_tools=False):
         """m2v_decode_device: the MPEG-2 elementary stream in the one-dimensional uint8 device tensor `es` (at any byte alignment) decoded
         on the device to 4:2:0 frames in `layout`; mode "iso" is decoder.decode(quirks=False), "module" the module's own loop
         (quirks=True).  Returns (frames [pictures, frame_bytes] uint8 on es's device, record).  out: a contiguous uint8 tensor to write into
@@ -950,7 +950,12 @@ class Mpeg2Encoder:
         back afterwards as interlaced= is - several slices in a macroblock row, slice headers with intra_slice_flag 1,
         quant_matrix_extension and composite_display_flag 1 are read too (decoder.decode(..., quirks=False, syntax="main",
         extended=True) is the definition).  False, the default, decodes without the option whatever set_option("decode_extended")
-        left on the handle."""
+        left on the handle.
+
+        mb_tools = True (with extended=True; ValueError otherwise): option "decode_mb_tools" for this call, put back afterwards as
+        extended= is - Table B-15 for intra blocks (intra_vlc_format 1), concealment motion vectors and dual prime are read too
+        (decoder.decode(..., quirks=False, syntax="main", extended=True, mb_tools=True) is the definition).  False, the default,
+        decodes without the option whatever set_option("decode_mb_tools") left on the handle."""
         import torch
         if syntax not in DEC_SYNTAXES:
             raise ValueError("decode_device: syntax is one of %s" % ", ".join(DEC_SYNTAXES))
@@ -960,33 +965,43 @@ class Mpeg2Encoder:
             raise ValueError("decode_device: interlaced goes with syntax=\"main\"")
         if extended and syntax != "main":
             raise ValueError("decode_device: extended goes with syntax=\"main\"")
+        if mb_tools and not extended:
+            raise ValueError("decode_device: mb_tools goes with extended=True")
+        held_t = self._set.get("decode_mb_tools", 0)                       # what set_option("decode_mb_tools") left on the handle
+        if int(bool(mb_tools)) != held_t:
+            self.set_option("decode_mb_tools", int(bool(mb_tools)))
+            try:
+                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced,
+                                          extended=extended, mb_tools=mb_tools)
+            finally:
+                self.set_option("decode_mb_tools", held_t)
         held_x = self._set.get("decode_extended", 0)                       # what set_option("decode_extended") left on the handle
         if int(bool(extended)) != held_x:
             self.set_option("decode_extended", int(bool(extended)))
             try:
                 return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced,
-                                          extended=extended)
+                                          extended=extended, mb_tools=mb_tools)
             finally:
                 self.set_option("decode_extended", held_x)
         held_i = self._set.get("decode_interlaced", 0)                     # what set_option("decode_interlaced") left on the handle
         if int(bool(interlaced)) != held_i:
             self.set_option("decode_interlaced", int(bool(interlaced)))
             try:
-                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended)
+                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended, mb_tools=mb_tools)
             finally:
                 self.set_option("decode_interlaced", held_i)
         held_b = self._set.get("decode_b_pictures", 0)                     # what set_option("decode_b_pictures") left on the handle
         if int(bool(b_pictures)) != held_b:
             self.set_option("decode_b_pictures", int(bool(b_pictures)))
             try:
-                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended)
+                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended, mb_tools=mb_tools)
             finally:
                 self.set_option("decode_b_pictures", held_b)
         held = self._set.get("decode_syntax", DEC_SYNTAXES["module"])      # what set_option("decode_syntax") left on the handle
         if DEC_SYNTAXES[syntax] != held:
             self.set_option("decode_syntax", DEC_SYNTAXES[syntax])
             try:
-                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended)
+                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended, mb_tools=mb_tools)
             finally:
                 self.set_option("decode_syntax", held)
         if container is not None:

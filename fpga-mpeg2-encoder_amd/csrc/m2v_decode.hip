@@ -38,7 +38,9 @@
 // its wait are m2v_decode_b.hip's (dec_b_plan, dec_b_chunks), again a translation unit of its own.  Option "decode_interlaced" = 1,
 // with "decode_b_pictures" either way: frame pictures with frame_pred_frame_dct 0; the same two places go to m2v_decode_i.hip
 // (dec_i_plan, dec_i_chunks).  Option "decode_extended" = 1, with the other two either way: several slices a row, slice header extras,
-// quant_matrix_extension, composite_display_flag 1; the same two places go to m2v_decode_x.hip (dec_x_plan, dec_x_chunks).
+// quant_matrix_extension, composite_display_flag 1; the same two places go to m2v_decode_x.hip (dec_x_plan, dec_x_chunks).  Option
+// "decode_mb_tools" = 1 on top of "decode_extended": Table B-15, concealment motion vectors, dual prime; from the same two places to
+// m2v_decode_t.hip (dec_t_plan, dec_t_chunks).
 #include "m2v_decode_state.hpp"
 
 static_assert(sizeof(m2v_decode_stat) == 72, "the record of include/m2v_mi355x.h is 72 bytes");
@@ -387,6 +389,7 @@ static int decode_impl(m2v_enc *e, void *argp)
     const bool b_pictures = e->decode_b_pictures != 0;                 // m2v_decode_b.hip: its plan, and everything behind the plan's wait
     const bool interlaced = e->decode_interlaced != 0;                 // m2v_decode_i.hip: the same two places, with b_pictures either way
     const bool extended = e->decode_extended != 0;                     // m2v_decode_x.hip: the same two places, with the other two either way
+    const bool mb_tools = e->decode_mb_tools != 0;                     // m2v_decode_t.hip: in the places of dec_x_plan and dec_x_chunks
     e->d_dec_x.recorded = false;
     const size_t ntiles = (n + dec::kScanTile - 1) / dec::kScanTile;
     if (ntiles > 0x7FFFFFFFu) { e->set_err("m2v_decode_device: the stream is longer than 2^31 scan tiles"); return M2V_E_PARAM; }
@@ -417,7 +420,7 @@ static int decode_impl(m2v_enc *e, void *argp)
         HIPCHK(hipGetLastError());
         if (extended) {
             e->d_dec_main.ensure(kDecMainMatrices + pic_cap * sizeof(DecXPic));
-            dec_x_plan(s, a->es, n, e->d_dec_ev.p, d_st, (DecPic *)e->d_dec_pics.p, (uint32_t)pic_cap, e->h_dec + rec_off + 128, (unsigned long long)a->cap,
+            (mb_tools ? dec_t_plan : dec_x_plan)(s, a->es, n, e->d_dec_ev.p, d_st, (DecPic *)e->d_dec_pics.p, (uint32_t)pic_cap, e->h_dec + rec_off + 128, (unsigned long long)a->cap,
                        a->dst ? 0 : 1, (m2v_decode_stat *)(e->h_dec + rec_off), e->d_dec_main.p, b_pictures ? 1 : 0, interlaced ? 1 : 0,
                        (uint32_t *)(e->h_dec + rec_off + 96), (uint32_t *)(e->h_dec + rec_off + 128 + ((pic_cap + 3) & ~(size_t)3) + 4 * pic_cap));
         } else if (interlaced) {
@@ -454,7 +457,7 @@ static int decode_impl(m2v_enc *e, void *argp)
         const size_t rows = *(const uint32_t *)(e->h_dec + rec_off + 96);
         if (!e->decode_batch) B = std::min(np, std::max<size_t>(1, std::min(kDecBatchMax, kDecLevelBytes / (mbw * rows * 768))));
         auto *h_list = (uint32_t *)(e->h_dec + rec_off + 128 + ((pic_cap + 3) & ~(size_t)3));
-        dec_x_chunks(e, s, a->es, n, a->dst, a->layout, R, rows, B, types, h_list, h_list + pic_cap, (m2v_decode_stat *)(e->h_dec + rec_off));
+        (mb_tools ? dec_t_chunks : dec_x_chunks)(e, s, a->es, n, a->dst, a->layout, R, rows, B, types, h_list, h_list + pic_cap, (m2v_decode_stat *)(e->h_dec + rec_off));
         R = *h_rec;
         return M2V_OK;
     }
@@ -552,6 +555,10 @@ int m2v_decode_device(m2v_enc *e, const void *d_es, size_t es_bytes, void *d_dst
     }
     if (e->decode_extended && (e->decode_syntax != M2V_SYNTAX_MAIN || mode != M2V_DEC_ISO)) {
         e->set_err("m2v_decode_device: \"decode_extended\" = 1 needs \"decode_syntax\" = main and the mode M2V_DEC_ISO");
+        return M2V_E_PARAM;
+    }
+    if (e->decode_mb_tools && (e->decode_syntax != M2V_SYNTAX_MAIN || mode != M2V_DEC_ISO || !e->decode_extended)) {
+        e->set_err("m2v_decode_device: \"decode_mb_tools\" = 1 needs \"decode_syntax\" = main, the mode M2V_DEC_ISO and \"decode_extended\" = 1");
         return M2V_E_PARAM;
     }
     if (e->decode_syntax == M2V_SYNTAX_MAIN && mode != M2V_DEC_ISO) {

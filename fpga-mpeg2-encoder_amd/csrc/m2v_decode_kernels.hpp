@@ -1988,5 +1988,345 @@ M2V_HD inline bool x_slice(const uint8_t *es, uint64_t start, uint64_t end, uint
     return !b.err && col >= 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The macroblock tools (option "decode_mb_tools" on top of "decode_extended", "decode_b_pictures" and "decode_interlaced" either way;
+// decoder.decode_main(extended=True, mb_tools=True) is the definition).  The functions above keep their text; these stand beside them:
+//   Table B-15  with the picture's intra_vlc_format 1 the AC coefficients of intra blocks are read with vlc_ac15 (end of block '0110');
+//               non-intra blocks keep vlc_ac and the '1s' form (t_block).
+//   concealment with concealment_motion_vectors 1 an intra macroblock carries a forward frame vector with f_code[0][*] and a marker bit
+//               1 behind its quantiser: it sets PMV[0][0] and PMV[1][0], is not used and not judged against the edges, and such a
+//               macroblock does not reset the predictors.  An I picture with the flag carries f_codes 1 .. 9 (t_picture_extension).
+//   dual prime  frame_motion_type 3 in a P picture with frame_pred_frame_dct 0: one field vector without a select and a dmvector
+//               behind each component.  Its record is a field-based one with both directions whose "backward" picture is the forward
+//               reference: selects {0, 1} forward with the vector itself, {1, 0} backward with the derived vectors (t_dual_prime);
+//               il_inside judges all four reads, il_predict forms the means.
+// One macroblock function reads every picture kind (t_macroblock): a picture with frame_pred_frame_dct 1 has no macroblock_modes(),
+// and leaves the records main_macroblock and bp_macroblock leave through x_record.
+// ---------------------------------------------------------------------------------------------------------------------------
+struct TPicParams { IPicParams i; uint32_t ivf, cmv, tff; };     // intra_vlc_format, concealment_motion_vectors, top_field_first
+
+M2V_HD inline uint32_t t_params_pack(const TPicParams &q) { return il_params_pack(q.i) | q.ivf << 21 | q.cmv << 22 | q.tff << 23; }
+M2V_HD inline TPicParams t_params_unpack(uint32_t v) { return TPicParams{il_params_unpack(v), (v >> 21) & 1u, (v >> 22) & 1u, (v >> 23) & 1u}; }
+
+// x_picture_extension with the three flags kept, not refused
+M2V_HD inline bool t_picture_extension(const uint8_t *es, uint64_t start, uint64_t end, uint32_t ptype, bool b_pictures, bool interlaced,
+                                       uint32_t progressive_sequence, TPicParams &q)
+{
+    Bits b = unit_bits(es, start, end);
+    bool ok = get(b, 4) == 8;
+    q.i.b.p.fh = get(b, 4); q.i.b.p.fv = get(b, 4);
+    q.i.b.bh = get(b, 4); q.i.b.bv = get(b, 4);
+    q.i.b.p.prec = get(b, 2);
+    ok = ok && get(b, 2) == 3;                               // frame picture
+    q.tff = get(b, 1);                                       // top_field_first: the order of a dual-prime macroblock's derived vectors
+    q.i.field = get(b, 1) ^ 1u;                              // frame_pred_frame_dct
+    q.cmv = get(b, 1);                                       // concealment_motion_vectors
+    q.i.b.p.qst = get(b, 1);
+    q.ivf = get(b, 1);                                       // intra_vlc_format
+    q.i.b.p.alt = get(b, 1);
+    skip(b, 2);                                              // repeat_first_field, chroma_420_type
+    const uint32_t progressive_frame = get(b, 1);
+    if (get(b, 1)) skip(b, 20);                              // composite_display_flag and what it announces: read, not acted on
+    ok = ok && (!q.i.field || (interlaced && il_field_allowed(progressive_sequence, progressive_frame)));
+    const uint32_t ftype = q.cmv ? 0u : ptype;               // with concealment vectors an I picture's f_codes are used: 15 is not legal
+    ok = ok && main_fcode_ok(q.i.b.p.fh, ftype) && main_fcode_ok(q.i.b.p.fv, ftype);
+    if (b_pictures && ptype == 3) ok = ok && q.i.b.bh >= 1 && q.i.b.bh <= 9 && q.i.b.bv >= 1 && q.i.b.bv <= 9;
+    return ok && !b.err && tail_zero(b);
+}
+
+// Table B-15 without the sign bit, in vlc_ac's form: length | run << 8 | level << 16; level 0: run 0 = end of block, run 1 = escape.
+// A window that starts with 1 is classed by its leading ones (five at most, no terminator behind five), any other by its leading
+// zeros; behind seven zeros the entries are B-14's, but for the ten pairs whose codes moved: one path for every lane, and two
+// dependent table loads a code, as vlc_ac
+M2V_HD inline uint32_t vlc_ac15(uint32_t w)
+{
+    static constexpr uint16_t kAc15Tab[149] = {
+        0x0212, 0x0212, 0x0003, 0x0603, 0x0A17, 0x02B7, 0x1607, 0x1407, 0x02D7, 0x02C7, 0x0437, 0x0817, 0x0224, 0x0224, 0x0224, 0x0224, 0x0224,
+        0x0224, 0x0224, 0x0224, 0x0414, 0x0414, 0x0414, 0x0414, 0x0414, 0x0414, 0x0414, 0x0414, 0x0234, 0x0234, 0x0234, 0x0234, 0x0234, 0x0234,
+        0x0234, 0x0234, 0x0E05, 0x0C05, 0x0245, 0x0255, 0x0276, 0x0286, 0x0266, 0x0426, 0x0015, 0x0458, 0x0458, 0x02E8, 0x02E8, 0x0829, 0x0309,
+        0x02F8, 0x02F8, 0xFFFF, 0x048B, 0x064B, 0xFFFF, 0xFFFF, 0x047B, 0x035B, 0x034B, 0xFFFF, 0x033B, 0x032B, 0xFFFF, 0x063B, 0xFFFF, 0x046B,
+        0x031B, 0x04AC, 0x049C, 0x065C, 0x083C, 0x0A2C, 0x0E1C, 0x0C1C, 0xFFFF, 0xFFFF, 0xFFFF, 0xFFFF, 0x03AC, 0x039C, 0x038C, 0x037C, 0x036C,
+        0x3E0D, 0x3C0D, 0x3A0D, 0x380D, 0x360D, 0x340D, 0x320D, 0x300D, 0x2E0D, 0x2C0D, 0x2A0D, 0x280D, 0x260D, 0x240D, 0x220D, 0x200D, 0x500E,
+        0x4E0E, 0x4C0E, 0x4A0E, 0x480E, 0x460E, 0x440E, 0x420E, 0x400E, 0x1C1E, 0x1A1E, 0x181E, 0x161E, 0x141E, 0x121E, 0x101E, 0x241F, 0x221F,
+        0x201F, 0x1E1F, 0x066F, 0x050F, 0x04FF, 0x04EF, 0x04DF, 0x04CF, 0x04BF, 0x03FF, 0x03EF, 0x03DF, 0x03CF, 0x03BF, 0x0201, 0x0402, 0x0804,
+        0x0A04, 0x0296, 0x0616, 0x02A6, 0x1006, 0x1206, 0x1206, 0x1807, 0x1A07, 0x0627, 0x0447, 0x1C07, 0x1E07
+    };
+    static constexpr uint16_t kAc15Z[17] = {                 // leading zeros 1 .. 11, twelve and more, then leading ones 1 .. 5: first entry << 3 | index bits
+        0x0002, 0x0025, 0x0122, 0x0142, 0x0160, 0x016B, 0x01AC, 0x022C, 0x02AC, 0x032C, 0x03AC, 0xFFFF, 0x0428, 0x0430, 0x0439, 0x044A, 0x046B
+    };
+    const bool ones = (w >> 31) != 0;
+    const uint32_t v = ones ? ~w : w;
+    int z = v ? __builtin_clz(v) : 32;
+    if (z > (ones ? 5 : 12)) z = ones ? 5 : 12;
+    const int used = ones && z == 5 ? 5 : z + 1;             // the run and the bit that ends it
+    const uint32_t d = kAc15Z[ones ? 11 + z : z - 1];
+    if (d == 0xFFFFu) return 0u;
+    const uint32_t r = d & 7u;
+    const uint32_t idx = r ? (w << used) >> (32u - r) : 0u;
+    const uint32_t e = kAc15Tab[(d >> 3) + idx];
+    return e == 0xFFFFu ? 0u : ((e & 15u) + 1u) | ((e >> 4) & 31u) << 8 | (e >> 9) << 16;
+}
+
+// one coefficient of a block behind its DC, by Table B-15 where b15 says so, else by Table B-14 with its '1s' form for a first one:
+// 1 = (run, lvl) read, 0 = end of block, -1 = refused
+M2V_HD inline int t_coefficient(Bits &b, bool first, bool b15, uint32_t &run, int32_t &lvl)
+{
+    const uint32_t w = peek(b, 32);
+    if (first && !b15 && (int32_t)w < 0) {                   // '1s': run 0, level +-1
+        skip(b, 1);
+        run = 0;
+        lvl = get(b, 1) ? -1 : 1;
+        return 1;
+    }
+    const uint32_t e = b15 ? vlc_ac15(w) : vlc_ac(w);
+    if (!e) return -1;
+    skip(b, (int)(e & 255u));
+    run = (e >> 8) & 255u;
+    lvl = (int32_t)(e >> 16);
+    if (lvl) {
+        if (get(b, 1)) lvl = -lvl;
+        return 1;
+    }
+    if (!run) return 0;                                      // end of block
+    run = get(b, 6);                                         // escape: 6 bits of run, 12 of level, 0 and -2048 forbidden
+    lvl = (int32_t)(get(b, 12) ^ 0x800u) - 0x800;
+    return lvl && lvl != -2048 ? 1 : -1;
+}
+
+// parse_block over t_coefficient: Table B-15 for an intra block's AC coefficients where the picture says so (b15)
+template <class Put>
+M2V_HD inline bool t_block(Bits &b, bool intra, bool b15, int comp, SliceState &s, int32_t &dc, Put put)
+{
+    uint32_t k = 0;
+    if (intra) {
+        const uint32_t e = comp ? vlc_dc_chroma(peek(b, 32)) : vlc_dc_luma(peek(b, 32));
+        if (!e) return false;
+        skip(b, (int)(e & 255u));
+        const int size = (int)(e >> 8);
+        int32_t diff = 0;
+        if (size) {
+            const int32_t d = (int32_t)get(b, size);
+            diff = (d >> (size - 1)) ? d : d - (1 << size) + 1;
+        }
+        s.dc_pred[comp] = wrap_add(s.dc_pred[comp], diff);
+        dc = s.dc_pred[comp];
+        k = 1;
+    }
+    for (bool first = !intra; !b.err; first = false) {       // at most 64 coefficients: k grows with every one
+        uint32_t run;
+        int32_t lvl;
+        const int got = t_coefficient(b, first, intra && b15, run, lvl);
+        if (got < 0) return false;
+        if (!got) return !b.err;
+        k += run;
+        if (k > 63u || b.err) return false;
+        put(scan_to_raster(k), lvl);
+        ++k;
+    }
+    return false;
+}
+
+// division by 2 to the nearest integer, halves away from zero
+M2V_HD inline int32_t t_half(int32_t a) { return (a + (a > 0 ? 1 : 0)) >> 1; }
+
+// a dual-prime macroblock's record from its vector (vx, vy) and dmvector (d0, d1): field-based, both directions; forward the vector
+// itself from the field of the same parity, "backward" the derived vectors from the field of the opposite parity - T for the
+// top-field lines, B for the bottom-field lines, the factors 1 and 3 by top_field_first
+M2V_HD inline void t_dual_prime(IMb &m, int32_t vx, int32_t vy, int32_t d0, int32_t d1, uint32_t tff)
+{
+    const int32_t ft = tff ? 1 : 3, fb = tff ? 3 : 1;
+    m.mvx = m.mvx1 = (int16_t)vx; m.mvy = m.mvy1 = (int16_t)vy;
+    m.bvx = (int16_t)(t_half(ft * vx) + d0); m.bvy = (int16_t)(t_half(ft * vy) + d1 - 1);
+    m.bvx1 = (int16_t)(t_half(fb * vx) + d0); m.bvy1 = (int16_t)(t_half(fb * vy) + d1 + 1);
+    m.sel[0] = 0; m.sel[1] = 1; m.sel[2] = 1; m.sel[3] = 0;
+}
+
+// dmvector: '0' 0, '10' +1, '11' -1
+M2V_HD inline int32_t t_dmvector(Bits &b) { return get(b, 1) ? (get(b, 1) ? -1 : 1) : 0; }
+
+// one macroblock of a picture of any kind behind its address increment; pmv: PMV[r][s][t] (a picture with frame_pred_frame_dct 1 uses
+// PMV[0][s] only); false = refused
+template <class Put>
+M2V_HD inline bool t_macroblock(Bits &b, uint32_t ptype, const TPicParams &pp, SliceState &s, int32_t (&pmv)[2][2][2], uint32_t &qcode, IMb &m, int32_t (&dc)[6],
+                                Put put)
+{
+    const uint32_t e = ptype == 3 ? vlc_type_b(peek(b, 6)) : il_type_ip(peek(b, 6), ptype);
+    if (!e) return false;
+    skip(b, (int)(e & 255u));
+    const uint32_t flags = e >> 8;
+    const bool intra = (flags & 1u) != 0, pattern = ((flags >> 1) & 1u) != 0;
+    const uint32_t dirs = (((flags >> 3) & 1u) ? (uint32_t)kFwd : 0u) | (((flags >> 2) & 1u) ? (uint32_t)kBwd : 0u);
+    uint32_t motion_type = kFrameBased, dct_type = 0;
+    if (pp.i.field) {                                        // macroblock_modes(): 3 is dual prime, in a P picture only
+        if (dirs) {
+            motion_type = get(b, 2);
+            if (motion_type == 0u || (motion_type == 3u && ptype != 2)) return false;
+        }
+        if (intra || pattern) dct_type = get(b, 1);
+    }
+    if (flags >> 4) {
+        qcode = get(b, 5);
+        if (!qcode) return false;
+    }
+    m = IMb{};
+    bool dual = false;
+    if (motion_type == 3u) {                                 // dual prime (a P picture: forward only): component, dmvector, component, dmvector
+        if (!bp_component(b, pmv[0][0][0], (int)pp.i.b.p.fh - 1)) return false;
+        const int32_t d0 = t_dmvector(b);
+        int32_t half = pmv[0][0][1] >> 1;
+        if (!bp_component(b, half, (int)pp.i.b.p.fv - 1)) return false;
+        const int32_t d1 = t_dmvector(b);
+        pmv[0][0][1] = 2 * half;
+        pmv[1][0][0] = pmv[0][0][0]; pmv[1][0][1] = pmv[0][0][1];
+        t_dual_prime(m, pmv[0][0][0], half, d0, d1, pp.tff);
+        dual = true;
+    }
+    for (int d = 0; d < 2 && !dual; ++d) {
+        if (!(dirs & (d ? (uint32_t)kBwd : (uint32_t)kFwd))) continue;
+        const int r_h = (int)(d ? pp.i.b.bh : pp.i.b.p.fh) - 1, r_v = (int)(d ? pp.i.b.bv : pp.i.b.p.fv) - 1;
+        if (motion_type == (uint32_t)kFrameBased) {          // 7.6.3.3: both predictors of the direction follow a frame vector
+            if (!bp_component(b, pmv[0][d][0], r_h) || !bp_component(b, pmv[0][d][1], r_v)) return false;
+            pmv[1][d][0] = pmv[0][d][0]; pmv[1][d][1] = pmv[0][d][1];
+            il_frame_vectors(m, d, pmv[0][d]);
+            continue;
+        }
+        for (int r = 0; r < 2; ++r) {
+            int32_t vx, vy;
+            m.sel[2 * d + r] = (uint8_t)get(b, 1);           // motion_vertical_field_select[r][s]
+            if (!il_field_vector(b, pmv[r][d], r_h, r_v, vx, vy)) return false;
+            if (d == 0) { if (r == 0) { m.mvx = (int16_t)vx; m.mvy = (int16_t)vy; } else { m.mvx1 = (int16_t)vx; m.mvy1 = (int16_t)vy; } }
+            else { if (r == 0) { m.bvx = (int16_t)vx; m.bvy = (int16_t)vy; } else { m.bvx1 = (int16_t)vx; m.bvy1 = (int16_t)vy; } }
+        }
+    }
+    if (intra && pp.cmv) {                                   // a concealment vector: kept in the predictors, not used, not judged
+        if (!bp_component(b, pmv[0][0][0], (int)pp.i.b.p.fh - 1) || !bp_component(b, pmv[0][0][1], (int)pp.i.b.p.fv - 1)) return false;
+        pmv[1][0][0] = pmv[0][0][0]; pmv[1][0][1] = pmv[0][0][1];
+        if (!get(b, 1)) return false;                        // marker_bit
+    } else if (intra || (ptype == 2 && !(dirs & kFwd))) {    // 7.6.3.4: both r, both directions
+        for (int r = 0; r < 2; ++r) for (int d = 0; d < 2; ++d) pmv[r][d][0] = pmv[r][d][1] = 0;
+    }
+    uint32_t cbp = intra ? 63u : 0u;
+    if (pattern) {
+        const uint32_t c = vlc_cbp(peek(b, 32));
+        if (!c) return false;
+        skip(b, (int)(c & 255u));
+        cbp = c >> 8;
+    }
+    if (!intra) { for (int c = 0; c < 3; ++c) s.dc_pred[c] = 0; }       // 7.2.1
+    m.intra = intra; m.cbp = (uint8_t)cbp; m.mc = (dirs & kFwd) != 0;
+    m.dirs = (uint8_t)(intra ? 0u : dual ? (uint32_t)(kFwd | kBwd) : ptype == 2 ? (uint32_t)kFwd : dirs);
+    m.motion_type = (uint8_t)(dual ? (uint32_t)kFieldBased : motion_type); m.dct_type = (uint8_t)dct_type;
+    for (int blk = 0; blk < 6; ++blk) {
+        dc[blk] = 0;
+        if (!((cbp >> (5 - blk)) & 1u)) continue;
+        if (!t_block(b, intra, pp.ivf != 0, blk < 4 ? 0 : blk - 3, s, dc[blk],
+                     [&](uint32_t i, int32_t l) { put(blk, pp.i.b.p.alt ? alternate_to_raster(zigzag_position(i)) : i, l); })) return false;
+    }
+    return !b.err;
+}
+
+// x_slice over t_macroblock: every picture kind in one walk, the forward predictor PMV[0][0] for all of them
+template <class Sink>
+M2V_HD inline bool t_slice(const uint8_t *es, uint64_t start, uint64_t end, uint32_t ptype, const TPicParams &pp, int mbw, int mbh, int row, Sink &sink,
+                           int &first, int &last)
+{
+    first = last = -1;
+    if (end < start + 4) return false;
+    Bits b = unit_bits(es, start, end);
+    const uint64_t lim = x_last_one(es, start + 4, end);
+    uint32_t qcode = get(b, 5);
+    if (get(b, 1)) {                                         // intra_slice_flag
+        skip(b, 8);                                          // intra_slice, reserved_bits
+        while (get(b, 1)) skip(b, 8);                        // extra_bit_slice, extra_information_slice (a read past the unit is 0)
+    }
+    if (b.err) return false;
+    SliceState s{{0, 0, 0}, {0, 0}};
+    int32_t pmv[2][2][2] = {{{0, 0}, {0, 0}}, {{0, 0}, {0, 0}}};      // PMV[r][s]
+    uint32_t dirs = 0;                                       // of the macroblock in front; 0: intra
+    int col = -1;
+    const int32_t none[6] = {0, 0, 0, 0, 0, 0};
+    while (b.pos < lim) {
+        int incr = 0;
+        uint32_t e;
+        for (;;) {
+            e = vlc_increment(peek(b, 11));
+            if (!e) return false;
+            skip(b, (int)(e & 255u));
+            if ((e >> 8) != 34u) break;
+            incr += 33;                                      // macroblock_escape
+            if (col + incr >= mbw) return false;
+        }
+        incr += (int)(e >> 8);
+        if (col + incr >= mbw || b.err) return false;
+        if (col < 0) {                                       // the slice's place: nothing is skipped in front of it
+            first = incr - 1;
+        } else if (incr > 1) {                               // 7.6.6: skipped - frame prediction, no residual
+            if (ptype == 1) return false;
+            IMb z{};
+            z.skipped = 1; z.qcode = (uint8_t)qcode; z.motion_type = (uint8_t)kFrameBased;
+            if (ptype == 2) {                                // the zero vector, the predictors reset
+                z.dirs = (uint8_t)kFwd;
+                for (int r = 0; r < 2; ++r) for (int d = 0; d < 2; ++d) pmv[r][d][0] = pmv[r][d][1] = 0;
+            } else {                                         // the directions in front, PMV[0][s] as frame vectors
+                if (!dirs) return false;
+                z.dirs = (uint8_t)dirs; z.mc = (dirs & kFwd) != 0;
+                if (dirs & kFwd) il_frame_vectors(z, 0, pmv[0][0]);
+                if (dirs & kBwd) il_frame_vectors(z, 1, pmv[0][1]);
+            }
+            for (int k = 1; k < incr; ++k) {
+                if (!il_inside(col + k, row, z, mbw, mbh)) return false;
+                sink.mb(col + k, z, none);
+            }
+            for (int c = 0; c < 3; ++c) s.dc_pred[c] = 0;
+        }
+        col += incr;
+        IMb m;
+        int32_t dc[6];
+        if (!t_macroblock(b, ptype, pp, s, pmv, qcode, m, dc, [&](int blk, uint32_t i, int32_t l) { sink.level(col, blk, i, l); })) return false;
+        if (!il_inside(col, row, m, mbw, mbh)) return false;
+        m.qcode = (uint8_t)qcode;
+        dirs = m.dirs;
+        sink.mb(col, m, dc);
+    }
+    last = col;
+    return !b.err && col >= 0;
+}
+
+// x_event, but a coding extension is judged by t_picture_extension
+M2V_HD inline EvInfo t_event(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, uint32_t i, const MainPlan &P, uint64_t last_nz, int prev,
+                             bool b_pictures, bool interlaced)
+{
+    if (x_role(es, n, ev[i]) != rPicExt) return x_event(es, n, ev, nev, i, P, last_nz, prev, b_pictures, interlaced);
+    EvInfo r{kNone, 0, 0, 0, 0};
+    const uint64_t pos = ev_pos(ev[i]), end = i + 1 < nev ? ev_pos(ev[i + 1]) : n;
+    TPicParams q;
+    const int before = i ? main_role(es, n, ev[i - 1]) : rBad;
+    const uint64_t pp = i ? ev_pos(ev[i - 1]) : 0;
+    const uint32_t ptype = before == rPic && pp + 5 < n ? (es[pp + 5] >> 3) & 7u : 0u;
+    const bool ok = before == rPic && t_picture_extension(es, pos, end, ptype, b_pictures, interlaced, P.seq.h.progressive, q) && i + 1 != nev;
+    if (!ok) r.bad = pos;
+    return r;
+}
+
+// x_picture_params with t_picture_extension's parameters (t_params_pack)
+M2V_HD inline uint32_t t_picture_params(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, uint32_t i, bool b_pictures, bool interlaced,
+                                        uint32_t progressive_sequence, uint32_t &slice0, uint32_t &nslices, uint32_t &quant)
+{
+    TPicParams q{IPicParams{BPicParams{PicParams{1, 1, 0, 0, 0}, 1, 1}, 0}, 0, 0, 0};
+    uint32_t j = i + 2;
+    if (i + 1 < nev) {
+        const uint64_t pos = ev_pos(ev[i]);
+        (void)t_picture_extension(es, ev_pos(ev[i + 1]), i + 2 < nev ? ev_pos(ev[i + 2]) : n, pos + 5 < n ? (es[pos + 5] >> 3) & 7u : 0u, b_pictures, interlaced,
+                                  progressive_sequence, q);
+    }
+    quant = kNoEvent;
+    for (; j < nev && !main_significant(main_role(es, n, ev[j])); ++j)
+        if (quant == kNoEvent && x_role(es, n, ev[j]) == rQuant) quant = j;
+    slice0 = j;
+    for (; j < nev && main_role(es, n, ev[j]) == rSlice; ++j) {}
+    nslices = j - slice0;
+    return t_params_pack(q);
+}
+
 }  // namespace dec
 }  // namespace m2v

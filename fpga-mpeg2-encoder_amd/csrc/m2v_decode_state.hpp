@@ -62,4 +62,12 @@ void dec_x_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long 
 void dec_x_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_t *dst, int layout, const m2v_decode_stat &R, size_t mbh, size_t B,
                   const uint8_t *types, uint32_t *h_list, const uint32_t *h_sl, m2v_decode_stat *h_rec);
 
+// Table B-15, concealment motion vectors, dual prime (option "decode_mb_tools" on top of "decode_extended"; m2v_decode_t.hip): the tables
+// and buffers are those of dec_x_plan / dec_x_chunks.  DecXPic::params carries dec::t_params_pack's three flags above bit 20, and a P
+// picture's bwd is its fwd: a dual-prime macroblock's second prediction reads the same reference
+void dec_t_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long long *ev, DecState *st, DecPic *pics, uint32_t pic_cap, uint8_t *h_types,
+                unsigned long long cap, int probe, m2v_decode_stat *h_rec, uint8_t *d_main, int b_pictures, int interlaced, uint32_t *h_mbh, uint32_t *h_sl);
+void dec_t_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_t *dst, int layout, const m2v_decode_stat &R, size_t mbh, size_t B,
+                  const uint8_t *types, uint32_t *h_list, const uint32_t *h_sl, m2v_decode_stat *h_rec);
+
 }  // namespace m2v

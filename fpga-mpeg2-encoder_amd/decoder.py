@@ -113,6 +113,16 @@ _B14_AC = """0,1:11 1,1:011 0,2:0100 2,1:0101 0,3:00101 3,1:00111 4,1:00110 1,2:
 31,1:0000000000011011"""
 _B14_EOB, _B14_ESCAPE = "10", "000001"
 
+# Table B-15 (DCT coefficients table one, intra blocks of a picture with intra_vlc_format 1): the 41 codes that differ from B-14's;
+# every B-14 code that begins with seven zero bits is B-15's too, except those of _B15_MOVED, whose B-14 codewords begin no code here
+_B15_AC = """0,1:10 0,2:110 0,3:0111 0,4:11100 0,5:11101 0,6:000101 0,7:000100 0,8:1111011 0,9:1111100 0,10:00100011 0,11:00100010
+0,12:11111010 0,13:11111011 0,14:11111110 0,15:11111111 1,1:010 1,2:00110 1,3:1111001 1,4:00100111 1,5:00100000
+2,1:00101 2,2:0000111 2,3:11111100 2,4:0000001100 3,1:00111 3,2:00100110 4,1:000110 4,2:11111101 5,1:000111 5,2:000000100
+6,1:0000110 7,1:0000100 8,1:0000101 9,1:1111000 10,1:1111010 11,1:00100001 12,1:00100101 13,1:00100100
+14,1:000000101 15,1:000000111 16,1:0000001101"""
+_B15_EOB = "0110"
+_B15_MOVED = [(0, l) for l in range(8, 16)] + [(1, 5), (2, 4)]
+
 # 7.3 figure 7-2: zig-zag scan (alternate_scan = 0), scan position of raster [v][u]
 _ZIGZAG = [0, 1, 5, 6, 14, 15, 27, 28, 2, 4, 7, 13, 16, 26, 29, 42, 3, 8, 12, 17, 25, 30, 41, 43, 9, 11, 18, 24, 31, 40, 44, 53,
            10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63]
@@ -137,6 +147,14 @@ def iso_tables():
                 zigzag=list(_ZIGZAG), intra_w=list(_INTRA_W))
 
 
+def b15_table():
+    """Table B-15 as [(code, length, (run, level))], without end of block and escape"""
+    pair = lambda t: tuple(int(x) for x in t.split(","))
+    own = _parse(_B15_AC, key=pair)
+    shared = [e for e in _parse(_B14_AC, key=pair) if e[1] > 7 and e[0] >> (e[1] - 7) == 0 and e[2] not in _B15_MOVED]
+    return own + shared
+
+
 def _tables():
     t = iso_tables()
     ac = [e for e in t["ac"] if e[2] != (0, 1)]          # '11' is matched before the table look-up (see the block loop)
@@ -145,8 +163,9 @@ def _tables():
     zz = np.zeros(64, np.int64)                          # scan position -> raster index
     for raster, pos in enumerate(_ZIGZAG):
         zz[pos] = raster
+    ac15 = b15_table() + [(int(_B15_EOB, 2), len(_B15_EOB), "EOB"), (int(_B14_ESCAPE, 2), len(_B14_ESCAPE), "ESC")]
     return dict(motion=_vlc_decoder(t["motion"]), cbp=_vlc_decoder(t["cbp"]), dcy=_vlc_decoder(t["dcy"]),
-                dcc=_vlc_decoder(t["dcc"]), ac=_vlc_decoder(ac), zz=zz, W=np.array(_INTRA_W, np.int64))
+                dcc=_vlc_decoder(t["dcc"]), ac=_vlc_decoder(ac), ac15=_vlc_decoder(ac15), zz=zz, W=np.array(_INTRA_W, np.int64))
 
 
 _T = None
@@ -282,7 +301,7 @@ def sequence_headers(data):
     return _sequence_headers(BitReader(data))
 
 
-def decode(data, quirks=True, syntax="module", b_pictures=False, interlaced=False, extended=False):
+def decode(data, quirks=True, syntax="module", b_pictures=False, interlaced=False, extended=False, mb_tools=False):
     """syntax="module" (the default): the subset this encoder emits, as the head of this file says.  syntax="main": Main-Profile
     streams of progressive frame pictures, I and P, 4:2:0, from any encoder (decode_main below); it needs quirks=False, and a
     refusal is a Refused exception that names the unit.  b_pictures=True (syntax="main" only): B pictures too, and the frames in
@@ -290,7 +309,12 @@ def decode(data, quirks=True, syntax="module", b_pictures=False, interlaced=Fals
     (syntax="main" only, with b_pictures either way): frame pictures with frame_pred_frame_dct 0 too (the section "Interlaced frame
     pictures" below); with False the function is what it was for every input.  extended=True (syntax="main" only, with the other two
     either way): several slices in a macroblock row, slice headers with intra_slice_flag 1, quant_matrix_extension and
-    composite_display_flag 1 too (the section "Several slices a row" below); with False the function is what it was for every input."""
+    composite_display_flag 1 too (the section "Several slices a row" below); with False the function is what it was for every input.
+    mb_tools=True (with extended=True only, the other two either way): Table B-15 for the intra blocks of a picture with
+    intra_vlc_format 1, concealment motion vectors, and dual prime in a P picture with frame_pred_frame_dct 0 (the section "The
+    macroblock tools" below); with False the function is what it was for every input."""
+    if mb_tools and not extended:
+        raise ValueError("mb_tools goes with extended=True")
     if extended and syntax != "main":
         raise ValueError("extended goes with syntax=\"main\"")
     if b_pictures and syntax != "main":
@@ -299,7 +323,7 @@ def decode(data, quirks=True, syntax="module", b_pictures=False, interlaced=Fals
         raise ValueError("interlaced goes with syntax=\"main\"")
     if syntax == "main":
         assert not quirks, "the module's quirks have no meaning outside its own syntax"
-        return decode_main(data, b_pictures, interlaced, extended)
+        return decode_main(data, b_pictures, interlaced, extended, mb_tools)
     assert syntax == "module", syntax
     T = tables()
     br = BitReader(data)
@@ -641,9 +665,26 @@ def psnr(a, b):
 #               loaded matrix is in force from that picture on in coded order, each matrix on its own; any sequence header, repeated
 #               ones included, puts both back to the sequence's
 #   composite   composite_display_flag 1: the 20 bits behind it are read and not acted on
-# Still refused: field pictures, dual prime, concealment vectors, Table B-15, leading B pictures, D pictures, and everything else the
-# main syntax refuses, where it is refused.  Every stream accepted with extended=False, under any setting of the other two, decodes to
+# Still refused: field pictures, leading B pictures, D pictures - dual prime, concealment vectors and Table B-15 too without mb_tools,
+# below -, and everything else the main syntax refuses, where it is refused.  Every stream accepted with extended=False, under any setting of the other two, decodes to
 # the same frames and fields with True.
+#
+# The macroblock tools (decode(..., syntax="main", extended=True, mb_tools=True), b_pictures and interlaced either way): what is left of
+# the macroblock layer of frame pictures.
+#   Table B-15  with the picture's intra_vlc_format 1 the AC coefficients of INTRA blocks are read with Table B-15 (end of block
+#               '0110'); non-intra blocks keep B-14 with its '1s' form; DC sizes, the escape body and the scans do not change
+#   concealment with concealment_motion_vectors 1 an intra macroblock carries one forward frame vector (f_code[0][*], no motion type,
+#               no select) and a marker bit 1, behind the quantiser and in front of the blocks.  The vector sets PMV[0][0] and
+#               PMV[1][0]; it is not used and not judged against the picture's edges; such a macroblock does not reset the predictors.
+#               An I picture with the flag carries f_code[0][*] 1 .. 9
+#   dual prime  frame_motion_type 3 in a P picture with frame_pred_frame_dct 0: motion_code[0][0][0], dmvector[0], motion_code[0][0][1],
+#               dmvector[1] ('0' 0, '10' +1, '11' -1); the vertical component is a field vector (predicted from PMV[0][0][1] >> 1, the
+#               predictor twice the vector afterwards), PMV[1][0] = PMV[0][0].  With h(a) = (a + (a > 0)) >> 1 and top_field_first 1 the
+#               derived vectors are T = (h(vx) + d0, h(vy) + d1 - 1) and B = (h(3 vx) + d0, h(3 vy) + d1 + 1); with top_field_first 0
+#               the factors 1 and 3 change places.  Top-field lines: the mean of the top field by (vx, vy) and the bottom field by T;
+#               bottom-field lines: the mean of the bottom field by (vx, vy) and the top field by B; every read inside its field
+# Still refused: field pictures, leading B pictures, D pictures, dual prime in a B picture.  Every stream accepted with mb_tools=False
+# and extended=True decodes to the same frames with True.
 # ---------------------------------------------------------------------------------------------------------------
 class Refused(Exception):
     def __init__(self, offset, why=""):
@@ -770,7 +811,7 @@ def _main_display_extension(data, start, end, h):
     assert br.rest_is_zero()
 
 
-def _main_picture_extension(data, start, end, ptype, b_pictures=False, interlaced=False, progressive_sequence=1, extended=False):
+def _main_picture_extension(data, start, end, ptype, b_pictures=False, interlaced=False, progressive_sequence=1, extended=False, mb_tools=False):
     br = _UnitBits(data, start, end)
     assert br.bits(4) == 8
     pic = dict(f_code=[br.bits(4) for _ in range(4)])
@@ -781,9 +822,9 @@ def _main_picture_extension(data, start, end, ptype, b_pictures=False, interlace
     assert pic["picture_structure"] == 3
     if pic["frame_pred_frame_dct"] != 1:                        # 6.3.10: 0 only where neither the sequence nor the frame is progressive
         assert interlaced and not progressive_sequence and not pic["progressive_frame"], "frame_pred_frame_dct"
-    assert pic["concealment_motion_vectors"] == 0 and pic["intra_vlc_format"] == 0
-    for f in pic["f_code"][:2]:                               # an I picture may carry 15, "not used" (6.3.10)
-        assert 1 <= f <= 9 or (ptype == 1 and f == 15), "f_code"
+    assert mb_tools or (pic["concealment_motion_vectors"] == 0 and pic["intra_vlc_format"] == 0)
+    for f in pic["f_code"][:2]:                               # an I picture may carry 15, "not used" (6.3.10) - without concealment vectors
+        assert 1 <= f <= 9 or (ptype == 1 and f == 15 and not pic["concealment_motion_vectors"]), "f_code"
     if b_pictures and ptype == 3:
         for f in pic["f_code"][2:]:
             assert 1 <= f <= 9, "f_code"
@@ -841,7 +882,7 @@ def _main_mbh(hdr, interlaced=False):
     return (hdr["height"] + 15) // 16
 
 
-def _main_plan(data, b_pictures=False, interlaced=False, extended=False):
+def _main_plan(data, b_pictures=False, interlaced=False, extended=False, mb_tools=False):
     """the grammar over the start codes -> (sequence fields, pictures, gops, repeated headers, number of start codes)"""
     n = len(data)
     ev = start_codes(data)
@@ -956,7 +997,7 @@ def _main_plan(data, b_pictures=False, interlaced=False, extended=False):
                 ok = i > 0 and roles[i - 1] == _PIC
                 ptype = (data[ev[i - 1][0] + 5] >> 3) & 7 if ok and ev[i - 1][0] + 5 < n else 0
                 quant_seen = False
-                ext = _main_picture_extension(data, pos, end, ptype, b_pictures, interlaced, first["progressive_sequence"], extended)
+                ext = _main_picture_extension(data, pos, end, ptype, b_pictures, interlaced, first["progressive_sequence"], extended, mb_tools)
                 if ok and pictures and pictures[-1]["unit"] == i - 1:
                     pictures[-1].update(ext)
             elif role == _SLICE:
@@ -1012,10 +1053,10 @@ def display_order(types):
     return out
 
 
-def decode_main(data, b_pictures=False, interlaced=False, extended=False):
+def decode_main(data, b_pictures=False, interlaced=False, extended=False, mb_tools=False):
     data = bytes(data)
     T, TM = tables(), _main_tables()
-    hdr, pictures, gops, repeats, ev, ends = _main_plan(data, b_pictures, interlaced, extended)
+    hdr, pictures, gops, repeats, ev, ends = _main_plan(data, b_pictures, interlaced, extended, mb_tools)
     out = Decoded()
     out.width, out.height, out.sequence, out.gops, out.repeated_headers, out.units = hdr["width"], hdr["height"], hdr, gops, repeats, len(ev)
     mbw, mbh = (out.width + 15) // 16, _main_mbh(hdr, interlaced)
@@ -1116,12 +1157,13 @@ def decode_main(data, b_pictures=False, interlaced=False, extended=False):
                         QF[0] = dc_pred[comp]
                         k = 1
                     first = not intra
+                    b15 = mb_tools and intra and pic["intra_vlc_format"]
                     while True:
                         if first and br.peek(1) == 1:
                             br.bits(1)
                             run, lvl = 0, (-1 if br.bits(1) else 1)
                         else:
-                            sym = T["ac"](br) if not (br.peek(2) == 0b11) else (br.bits(2), (0, 1))[1]
+                            sym = T["ac15"](br) if b15 else T["ac"](br) if not (br.peek(2) == 0b11) else (br.bits(2), (0, 1))[1]
                             if sym == "EOB":
                                 assert not first, "a coded non-intra block cannot start with EOB"
                                 break
@@ -1160,7 +1202,10 @@ def decode_main(data, b_pictures=False, interlaced=False, extended=False):
         span = []                                               # extended: the columns of the slice's first and last macroblock
 
         def il_slice(br, row):
-            """a slice of a picture with frame_pred_frame_dct 0, of any type (the section "Interlaced frame pictures" above)"""
+            """a slice of a picture with frame_pred_frame_dct 0, of any type (the section "Interlaced frame pictures" above); with
+            mb_tools a slice of any picture: one with frame_pred_frame_dct 1 has no macroblock_modes() - frame prediction, frame DCT"""
+            modes = not pic["frame_pred_frame_dct"]
+            conceal = mb_tools and pic["concealment_motion_vectors"]
             qcode = br.bits(5)
             qcodes.append(qcode)
             slice_extras(br)
@@ -1219,10 +1264,10 @@ def decode_main(data, b_pictures=False, interlaced=False, extended=False):
                 else:
                     quant, mc, pattern, intra = (TM["type_i"] if ptype == 1 else TM["type_p"])(br)
                 motion_type, dct_type = 2, 0                    # macroblock_modes(): frame_motion_type, dct_type
-                if mc or bwd:
+                if modes and (mc or bwd):
                     motion_type = br.bits(2)
-                    assert motion_type in (1, 2), "frame_motion_type 0 is reserved, 3 is dual prime"
-                if intra or pattern:
+                    assert motion_type in (1, 2) or (mb_tools and motion_type == 3 and ptype == 2), "frame_motion_type 0 is reserved, 3 is dual prime"
+                if modes and (intra or pattern):
                     dct_type = br.bits(1)
                 if quant:
                     qcode = br.bits(5)
@@ -1238,6 +1283,21 @@ def decode_main(data, b_pictures=False, interlaced=False, extended=False):
                         vector(br, PMV[0][s], 1, fv)
                         PMV[1][s] = list(PMV[0][s])
                         vec[s] = [tuple(PMV[0][s])] * 2
+                    elif motion_type == 3:                      # dual prime: one field vector without a select, a dmvector behind each component
+                        dmv = [0, 0]
+                        vector(br, PMV[0][0], 0, fh)
+                        dmv[0] = (1 - 2 * br.bits(1)) if br.bits(1) else 0
+                        half = [PMV[0][0][1] >> 1]
+                        vector(br, half, 0, fv)
+                        dmv[1] = (1 - 2 * br.bits(1)) if br.bits(1) else 0
+                        PMV[0][0][1] = 2 * half[0]
+                        PMV[1][0] = list(PMV[0][0])
+                        vx, vy = PMV[0][0][0], half[0]
+                        near = lambda a: (a + (a > 0)) >> 1     # division by 2 to the nearest integer, halves away from zero
+                        mt, mb_ = (1, 3) if pic["top_field_first"] else (3, 1)
+                        vec[0] = [(vx, vy), (vx, vy)]           # the same parity: top from top, bottom from bottom
+                        vec[1] = [(near(mt * vx) + dmv[0], near(mt * vy) + dmv[1] - 1), (near(mb_ * vx) + dmv[0], near(mb_ * vy) + dmv[1] + 1)]
+                        sel = [[0, 1], [1, 0]]                  # the opposite parity, as a second direction from the same picture
                     else:
                         for r in (0, 1):                        # 7.6.3.1: the vertical predictor is in frame units - DIV 2 in, times 2 out
                             sel[s][r] = br.bits(1)
@@ -1246,10 +1306,15 @@ def decode_main(data, b_pictures=False, interlaced=False, extended=False):
                             vector(br, half, 0, fv)
                             PMV[r][s][1] = 2 * half[0]
                             vec[s][r] = (PMV[r][s][0], half[0])
-                if intra or (ptype == 2 and not mc):
+                if intra and conceal:                           # a frame vector with f_code[0][*] and a marker bit: kept in the predictors, not used
+                    vector(br, PMV[0][0], 0, pic["f_code"][0])
+                    vector(br, PMV[0][0], 1, pic["f_code"][1])
+                    PMV[1][0] = list(PMV[0][0])
+                    assert br.bits(1) == 1, "marker_bit"
+                elif intra or (ptype == 2 and not mc):
                     PMV = [[[0, 0], [0, 0]], [[0, 0], [0, 0]]]  # 7.6.3.4
                 cbp = 63 if intra else (T["cbp"](br) if pattern else 0)
-                used = (0, 0) if intra else (1, 0) if ptype == 2 else (mc, bwd)
+                used = (0, 0) if intra else (1, 1) if motion_type == 3 else (1, 0) if ptype == 2 else (mc, bwd)
                 if intra:
                     pred = (np.full((16, 16), 128, np.int64), np.full((8, 8), 128, np.int64), np.full((8, 8), 128, np.int64))
                     dirs = None
@@ -1258,9 +1323,9 @@ def decode_main(data, b_pictures=False, interlaced=False, extended=False):
                     if motion_type == 2:
                         pred = frame_pred(col, used, (vec[0][0], vec[1][0]))
                     else:
-                        p = [predict_field(col, row, vec[s], sel[s], refs[s]) for s in (0, 1) if used[s]]
+                        p = [predict_field(col, row, vec[s], sel[s], ref if motion_type == 3 else refs[s]) for s in (0, 1) if used[s]]
                         pred = p[0] if len(p) == 1 else tuple((a + c + 1) >> 1 for a, c in zip(*p))
-                    dirs = used
+                    dirs = used if motion_type != 3 else (1, 0)
                 res = read_blocks(br, intra, cbp, dc_pred, qcode)
                 store_il(col, row, pred, res, dct_type)
                 record(intra=bool(intra), mc=bool(mc), mv=vec[0][0] if mc else (0, 0), cbp=cbp, qcode=qcode, motion_type=motion_type, dct_type=dct_type,
@@ -1287,7 +1352,7 @@ def decode_main(data, b_pictures=False, interlaced=False, extended=False):
                 del span[:]
             try:
                 br = _UnitBits(data, pos, ends[unit])
-                if interlaced and not pic["frame_pred_frame_dct"]:
+                if mb_tools or (interlaced and not pic["frame_pred_frame_dct"]):
                     il_slice(br, row)
                     assert br.rest_is_zero(), "only zero stuffing may follow the row's last macroblock"
                     if extended:

@@ -968,13 +968,13 @@ int m2v_mux_scan_tile(void);
  *   macroblock  macroblock_address_increment (Table B-1) with macroblock_escape; skipped macroblocks in P pictures (7.6.6); all of
  *             Tables B-2 and B-3; a macroblock's quantiser_scale_code replaces the slice's (0 is refused)
  * Still M2V_DEC_SYNTAX in the main syntax, the follow-ups: leading B pictures (fewer than two anchors in front of them) and D pictures;
- * field pictures; dual prime; concealment vectors; intra_vlc_format 1 (Table B-15 has no second source here to be checked against);
- * every scalable extension; size extensions and sizes over 2048; chroma formats other than 4:2:0; a skipped macroblock in an I picture;
+ * field pictures; every scalable extension; size extensions and sizes over 2048; chroma formats other than 4:2:0; a skipped macroblock in an I picture;
  * an increment that passes the row's end; vectors that read outside the picture; and every check the module syntax makes on codes,
  * coefficient indices and stuffing inside a slice.  Refused unless their option is on (each below): B pictures ("decode_b_pictures");
  * frame_pred_frame_dct 0 ("decode_interlaced"); more than one slice in a macroblock row, a slice whose first increment is not 1 or
  * whose row ends short, a slice header with intra_slice_flag 1, quant_matrix_extension and composite_display_flag 1 (without the option
- * its 20 bits are read as stuffing that is not zero) ("decode_extended").  The batch entry for the main syntax is
+ * its 20 bits are read as stuffing that is not zero) ("decode_extended"); intra_vlc_format 1 (Table B-15), concealment_motion_vectors 1
+ * and dual prime ("decode_mb_tools" on top of "decode_extended").  The batch entry for the main syntax is
  * m2v_decode_streams_main_device, below.
  *
  * Option "decode_b_pictures" (m2v_set_option), per handle: 0 (the default) - everything above, bit for bit, launch for launch and
@@ -1033,8 +1033,8 @@ int m2v_mux_scan_tile(void);
  *             (row 2k + 1); chroma blocks are frame blocks; inverse quantisation, mismatch control and the IDCT are untouched
  *   skipped   frame prediction: a P picture's with the zero vector; a B picture's in the directions of the macroblock in front with
  *             PMV[0][s] read as frame vectors - behind a field-based macroblock twice its first field vector's vertical component
- * Still M2V_DEC_SYNTAX with the option on, the follow-ups: field pictures (picture_structure 1 and 2); dual prime; concealment
- * vectors; and everything else the main syntax refuses.
+ * Still M2V_DEC_SYNTAX with the option on: field pictures (picture_structure 1 and 2); dual prime and concealment vectors (option
+ * "decode_mb_tools" below reads them); and everything else the main syntax refuses.
  *
  * Option "decode_extended" (m2v_set_option), per handle: 0 (the default) - everything above, bit for bit, launch for launch and
  * refusal for refusal; 1 - several slices in a macroblock row, slice headers with intra_slice_flag 1, quant_matrix_extension and
@@ -1068,8 +1068,37 @@ int m2v_mux_scan_tile(void);
  *             repeated ones included, puts both back to the sequence's
  *   composite  composite_display_flag 1: the 20 bits behind it are read and not acted on
  * Out of scope, the follow-ups: m2v_decode_streams_main_device keeps its two flags (any other bit stays M2V_E_PARAM); field pictures,
- * dual prime, concealment vectors, Table B-15, leading B pictures and D pictures stay refused, and everything else the main syntax
- * refuses stays refused where it is refused without the option.
+ * leading B pictures and D pictures stay refused, dual prime, concealment vectors and Table B-15 too without option "decode_mb_tools",
+ * and everything else the main syntax refuses stays refused where it is refused without the option.
+ *
+ * Option "decode_mb_tools" (m2v_set_option), per handle: 0 (the default) - everything above, bit for bit, launch for launch and
+ * refusal for refusal; 1 - the rest of the macroblock layer of frame pictures is read too.  Any other value is M2V_E_PARAM.  With 1,
+ * "decode_syntax" must be M2V_SYNTAX_MAIN, `mode` M2V_DEC_ISO and "decode_extended" 1 (its slice walk is the one that reads every
+ * picture kind in one function, and its grammar is a superset: no stream is lost): otherwise m2v_decode_device returns M2V_E_PARAM,
+ * writes nothing and m2v_last_error names the option.  It combines with "decode_b_pictures" and "decode_interlaced" in all four
+ * settings.  The definition is decoder.decode(stream, quirks=False, syntax="main", b_pictures=..., interlaced=..., extended=True,
+ * mb_tools=True).  Every stream accepted with the option off decodes with it on to the same bytes and the same record; a stream it
+ * refuses is M2V_DEC_SYNTAX with the offset of the unit in error.  Added (6.3.10, 6.3.17.2, 7.2.2, 7.6.3.6, 7.6.3.9, Table B-15):
+ *   Table B-15  with a picture's intra_vlc_format 1 the AC coefficients of INTRA blocks are read with Table B-15 (end of block '0110',
+ *             escape '000001' with the same body); non-intra blocks keep Table B-14 and its '1s' first-coefficient form; DC sizes, the
+ *             scans and everything behind the level are unchanged.  A B-14 codeword that Table B-15 does not hold refuses the slice
+ *   concealment  with concealment_motion_vectors 1 an intra macroblock carries, behind its quantiser and in front of its blocks, one
+ *             forward frame vector (motion_code and residual, horizontal then vertical, f_code[0][*]; no frame_motion_type, no field
+ *             select) and a marker_bit that must be 1.  The vector sets PMV[0][0] and PMV[1][0]; it is not used in reconstruction
+ *             and not judged against the picture's edges; such a macroblock does not reset the vector predictors (one without
+ *             concealment vectors still does).  In an I picture with the flag f_code[0][0] and f_code[0][1] must be 1 .. 9
+ *   dual prime  frame_motion_type 3 in a P picture with frame_pred_frame_dct 0 ("decode_interlaced" on); in a B picture it stays
+ *             refused, and whether B pictures lie between the picture and its reference is not judged.  One vector without a field
+ *             select: motion_code[0][0][0], dmvector[0], motion_code[0][0][1], dmvector[1] (dmvector '0' 0, '10' +1, '11' -1); the
+ *             vertical component is a field vector, predicted from PMV[0][0][1] >> 1, the predictor twice the vector afterwards,
+ *             PMV[1][0] = PMV[0][0].  With h(a) = (a + (a > 0)) >> 1 and top_field_first 1, T = (h(vx) + d0, h(vy) + d1 - 1) and
+ *             B = (h(3 vx) + d0, h(3 vy) + d1 + 1); with top_field_first 0 the factors 1 and 3 change places.  Top-field lines are
+ *             the mean (a + b + 1) >> 1 of the reference's top field by (vx, vy) and its bottom field by T, bottom-field lines of
+ *             its bottom field by (vx, vy) and its top field by B; each a 16 x 8 field prediction with half-sample interpolation,
+ *             each vector halved toward zero on its own for chroma.  All four reads must lie inside their field, or the slice is
+ *             refused.  A skipped macroblock behind a dual-prime one is the zero vector, as ever
+ * Still M2V_DEC_SYNTAX with every option on: field pictures, leading B pictures, D pictures.  m2v_decode_streams_main_device takes
+ * neither "decode_extended" nor "decode_mb_tools" yet.
  */
 enum { M2V_DEC_ISO = 0, M2V_DEC_MODULE = 1 };
 enum { M2V_SYNTAX_MODULE = 0, M2V_SYNTAX_MAIN = 1 };                            /* option "decode_syntax" */
