@@ -50,7 +50,7 @@ EXPORTS = [
     "m2v_mux_bound", "m2v_set_mux_out", "m2v_mux_report", "m2v_mux_device", "m2v_mux_scan_tile",
     "m2v_set_source_size", "m2v_scale_taps",
     "m2v_demux_bound", "m2v_demux_device", "m2v_demux_report", "m2v_demux_scan_tile",
-    "m2v_decode_streams_device", "m2v_decode_streams_report", "m2v_decode_streams_main_device",
+    "m2v_decode_streams_device", "m2v_decode_streams_report", "m2v_decode_streams_main_device", "m2v_decode_streams_main_ex_device",
 ]
 
 # the 4:2:0 entry points (kept apart: tests/test_abi.py matches EXPORTS against names of letters and underscores only)
@@ -132,6 +132,7 @@ DECODE_STREAM_STAT_DTYPE = np.dtype([("es_offset", "<u8"), ("out_offset", "<u8")
 DEC_MODES = {"iso": 0, "module": 1}                              # M2V_DEC_*
 DEC_SYNTAXES = {"module": 0, "main": 1}                          # M2V_SYNTAX_*: option "decode_syntax"
 DECS_B_PICTURES, DECS_INTERLACED = 1, 2                          # M2V_DECS_*: the flags of m2v_decode_streams_main_device
+DECS_EXTENDED, DECS_MB_TOOLS = 4, 8                              # ... and the two further ones of m2v_decode_streams_main_ex_device
 DEC_OK, DEC_SYNTAX, DEC_OVERFLOW = 0, -2, -3
 DEC_STATUS = {0: "M2V_DEC_OK", -2: "M2V_DEC_SYNTAX", -3: "M2V_DEC_OVERFLOW"}
 
@@ -449,6 +450,7 @@ def lib(debug=False):
             L.m2v_decode_streams_report.argtypes = [vp, vp, sz]
             L.m2v_scale_taps.argtypes = [ci, ci, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_uint16)]
             L.m2v_decode_streams_main_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, ci, ctypes.c_uint, vp]
+            L.m2v_decode_streams_main_ex_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, ci, ctypes.c_uint, vp]
         except AttributeError:
             # an OLDER build handed in through M2V_LIB for a same-box A/B (tools/ab.sh) may lack the newer entry points; the library of
             # this tree must have every one of them (tests/test_abi.py)
@@ -1046,7 +1048,7 @@ class Mpeg2Encoder:
         return self._pop("m2v_decode_streams_report", DECODE_STREAM_STAT_DTYPE, max_records)
 
     def decode_streams(self, es, segments, layout="i420", mode="iso", out=None, container=None, stream=None, syntax="module", b_pictures=False,
-                       interlaced=False):
+                       interlaced=False, extended=False, mb_tools=False):
         """m2v_decode_streams_device: the elementary streams at the (offset, bytes) pairs of `segments` in the one-dimensional uint8
         device tensor `es` - at any byte alignment, of any picture sizes - decoded on the device in one call.  Returns (frames, records):
         a one-dimensional uint8 tensor on es's device and a structured array of DECODE_STREAM_STAT_DTYPE, one record per stream;
@@ -1062,12 +1064,21 @@ class Mpeg2Encoder:
         syntax = "main": m2v_decode_streams_main_device - the streams are main-syntax streams (what an ordinary multiplexer's
         containers hold), each judged as decode_device(syntax="main", b_pictures=, interlaced=) judges it alone; with b_pictures the
         frames of a stream are in display order.  The syntax is the call's: the handle's three decode options are neither read nor
-        changed.  The mode is "iso" there ("module" is a ValueError), and b_pictures / interlaced need syntax="main"."""
+        changed.  The mode is "iso" there ("module" is a ValueError), and b_pictures / interlaced need syntax="main".
+
+        extended / mb_tools: m2v_decode_streams_main_ex_device - each stream judged as decode_device(syntax="main", ..., extended=,
+        mb_tools=) judges it alone: several slices a row, slice header extras, quant_matrix_extension, composite_display_flag 1; on
+        top of those Table B-15, concealment vectors and dual prime.  extended needs syntax="main" and mb_tools needs extended
+        (ValueError); with both False the call is the one it was."""
         import torch
         if syntax not in ("module", "main"):
             raise ValueError("decode_streams: syntax is \"module\" or \"main\"")
         if syntax != "main" and (b_pictures or interlaced):
             raise ValueError("decode_streams: b_pictures and interlaced need syntax=\"main\"")
+        if extended and syntax != "main":
+            raise ValueError("decode_streams: extended needs syntax=\"main\"")
+        if mb_tools and not extended:
+            raise ValueError("decode_streams: mb_tools needs extended")
         if syntax == "main" and mode in ("module", DEC_MODES["module"]):
             raise ValueError("decode_streams: with syntax=\"main\" the mode is \"iso\"")
         if not isinstance(es, torch.Tensor) or es.dtype != torch.uint8 or es.dim() != 1 or not es.is_cuda or es.device.index != self.device:
@@ -1100,7 +1111,11 @@ class Mpeg2Encoder:
         flags = (DECS_B_PICTURES if b_pictures else 0) | (DECS_INTERLACED if interlaced else 0)
 
         def call(ptr, cap):
-            if syntax == "main":
+            if extended:
+                x = flags | DECS_EXTENDED | (DECS_MB_TOOLS if mb_tools else 0)
+                self._chk(self._L.m2v_decode_streams_main_ex_device(self._h, es.data_ptr() or None, off, nb, len(seg), ptr, cap, code, x, hip_stream),
+                          "m2v_decode_streams_main_ex_device")
+            elif syntax == "main":
                 self._chk(self._L.m2v_decode_streams_main_device(self._h, es.data_ptr() or None, off, nb, len(seg), ptr, cap, code, flags, hip_stream),
                           "m2v_decode_streams_main_device")
             else:

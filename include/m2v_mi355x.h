@@ -1098,7 +1098,7 @@ int m2v_mux_scan_tile(void);
  *             each vector halved toward zero on its own for chroma.  All four reads must lie inside their field, or the slice is
  *             refused.  A skipped macroblock behind a dual-prime one is the zero vector, as ever
  * Still M2V_DEC_SYNTAX with every option on: field pictures, leading B pictures, D pictures.  m2v_decode_streams_main_device takes
- * neither "decode_extended" nor "decode_mb_tools" yet.
+ * neither "decode_extended" nor "decode_mb_tools"; the batch entry that does is m2v_decode_streams_main_ex_device, below.
  */
 enum { M2V_DEC_ISO = 0, M2V_DEC_MODULE = 1 };
 enum { M2V_SYNTAX_MODULE = 0, M2V_SYNTAX_MAIN = 1 };                            /* option "decode_syntax" */
@@ -1190,6 +1190,39 @@ int m2v_decode_streams_report(m2v_enc *e, m2v_decode_stream_stat *out, size_t ma
 enum { M2V_DECS_B_PICTURES = 1, M2V_DECS_INTERLACED = 2 };
 int m2v_decode_streams_main_device(m2v_enc *e, const void *d_es, const uint64_t *es_off, const uint64_t *es_bytes, size_t nstreams,
                                    void *d_dst, size_t cap, int layout, unsigned flags, void *hip_stream);
+
+/*
+ * The batch entry of the main syntax WITH the extended options: m2v_decode_streams_main_ex_device is m2v_decode_streams_main_device with
+ * two further flags.  M2V_DECS_EXTENDED (4) is what "decode_extended" is to m2v_decode_device: several slices in a macroblock row,
+ * intra_slice_flag with its extras, quant_matrix_extension, composite_display_flag 1.  M2V_DECS_MB_TOOLS (8) is "decode_mb_tools":
+ * Table B-15, concealment motion vectors, dual prime.  m2v_decode_streams_main_device keeps its two flags and its kernels.
+ *
+ * The contract is m2v_decode_streams_main_device's, word for word: segments at any byte address, nstreams 1 .. 65535, d_dst == NULL as a
+ * probe call, cap, the packed layout with out_offset, display order with flag 1, blocking, two host waits per call (a third when a stream
+ * holds more start codes than guessed), M2V_E_STATE in the same situations, "decode_batch" read, the mode M2V_DEC_ISO.  The records are
+ * popped through the same m2v_decode_streams_report queue; a call of any of the three batch entries drops that queue.  None of the five
+ * decode_* options of the handle is read or changed.
+ *
+ * flags.  Any bit above 8 is M2V_E_PARAM, and so is M2V_DECS_MB_TOOLS without M2V_DECS_EXTENDED (the single-stream rule);
+ * m2v_last_error names the entry, nothing is touched.  With flags < 4 the entry runs m2v_decode_streams_main_device's implementation:
+ * the same bytes, the same records, the same launches.
+ *
+ * Each stream is judged alone.  `rec` is what m2v_decode_device reports for it with the four options set as the flags say:
+ * decoder.decode(stream, quirks=False, syntax="main", b_pictures=f & 1, interlaced=f & 2, extended=f & 4, mb_tools=f & 8) is the
+ * definition.  A refusal is at the probe stage - the stream takes no room - iff decoder._main_plan(stream, b, i, x, t) raises: so Table
+ * B-15, concealment vectors or dual prime's intra_vlc_format / concealment_motion_vectors under flags 4 .. 7 are a probe refusal at the
+ * picture coding extension, and the same batch has different layouts under different flags.  Every other refusal is at the slice stage,
+ * also that of a slice which breaks the continuity of its row or its picture (refused at its own start code): the stream keeps its
+ * room and not one byte of it is written, in however many chunks it lies.  M2V_DEC_OVERFLOW, and "nothing outside the rooms of OK
+ * streams is ever written", hold as before.  The result does not depend on "decode_batch": a quant_matrix_extension stays in force
+ * across chunks until a sequence header puts the sequence's matrices back, and a dual-prime P picture that is the first anchor of its
+ * chunk reads both predictions from the carried slot.
+ *
+ * Still M2V_DEC_SYNTAX, as in the single-stream decoder: field pictures, leading B pictures, D pictures.
+ */
+enum { M2V_DECS_EXTENDED = 4, M2V_DECS_MB_TOOLS = 8 };
+int m2v_decode_streams_main_ex_device(m2v_enc *e, const void *d_es, const uint64_t *es_off, const uint64_t *es_bytes, size_t nstreams,
+                                      void *d_dst, size_t cap, int layout, unsigned flags, void *hip_stream);
 
 /*
  * Demux on the device: the inverse of m2v_mux_device.  nstreams (1 .. 65535) transport (kind M2V_MUX_TS) or program (M2V_MUX_PS) streams
