@@ -737,7 +737,7 @@ class Mpeg2Encoder:
         self._chk(self._L.m2v_set_option(self._h, name.encode(), int(value)), "m2v_set_option(%s)" % name)
         if name == "stats":
             self._set[name] = bool(value)
-        if name in ("gop_bytes_max", "scene_cut", "decode_syntax", "decode_b_pictures", "decode_interlaced", "decode_extended", "decode_mb_tools"):
+        if name in ("gop_bytes_max", "scene_cut", "decode_syntax", "decode_b_pictures", "decode_interlaced", "decode_extended", "decode_mb_tools", "decode_field_pictures"):
             self._set[name] = int(value)
 
     def _set_list(self, key, values, ctype, what):
@@ -918,7 +918,7 @@ class Mpeg2Encoder:
         self._chk(self._L.m2v_decode_report(self._h, out.ctypes.data), "m2v_decode_report")
         return out[0]
 
-    def decode_device(self, es, layout="i420", mode="iso", out=None, container=None, stream=None, syntax="module", b_pictures=False, interlaced=False, extended=False, mb_tools=False):
+    def decode_device(self, es, layout="i420", mode="iso", out=None, container=None, stream=None, syntax="module", b_pictures=False, interlaced=False, extended=False, mb_tools=False, field_pictures=False):
         """m2v_decode_device: the MPEG-2 elementary stream in the one-dimensional uint8 device tensor `es` (at any byte alignment) decoded
         on the device to 4:2:0 frames in `layout`; mode "iso" is decoder.decode(quirks=False), "module" the module's own loop
         (quirks=True).  Returns (frames [pictures, frame_bytes] uint8 on es's device, record).  out: a contiguous uint8 tensor to write into
@@ -957,7 +957,13 @@ class Mpeg2Encoder:
         mb_tools = True (with extended=True; ValueError otherwise): option "decode_mb_tools" for this call, put back afterwards as
         extended= is - Table B-15 for intra blocks (intra_vlc_format 1), concealment motion vectors and dual prime are read too
         (decoder.decode(..., quirks=False, syntax="main", extended=True, mb_tools=True) is the definition).  False, the default,
-        decodes without the option whatever set_option("decode_mb_tools") left on the handle."""
+        decodes without the option whatever set_option("decode_mb_tools") left on the handle.
+
+        field_pictures = True (with interlaced=True, extended=True and mb_tools=True, b_pictures either way; ValueError otherwise): option
+        "decode_field_pictures" for this call, put back afterwards as mb_tools= is - pictures with picture_structure 1 / 2 are read too,
+        two field pictures woven into one frame, the record counted in frames (decoder.decode(..., quirks=False, syntax="main",
+        interlaced=True, extended=True, mb_tools=True, field_pictures=True) is the definition).  False, the default, decodes without the
+        option whatever set_option("decode_field_pictures") left on the handle."""
         import torch
         if syntax not in DEC_SYNTAXES:
             raise ValueError("decode_device: syntax is one of %s" % ", ".join(DEC_SYNTAXES))
@@ -969,12 +975,22 @@ class Mpeg2Encoder:
             raise ValueError("decode_device: extended goes with syntax=\"main\"")
         if mb_tools and not extended:
             raise ValueError("decode_device: mb_tools goes with extended=True")
+        if field_pictures and not (interlaced and extended and mb_tools):
+            raise ValueError("decode_device: field_pictures goes with interlaced=True, extended=True and mb_tools=True")
+        held_f = self._set.get("decode_field_pictures", 0)                 # what set_option("decode_field_pictures") left on the handle
+        if int(bool(field_pictures)) != held_f:
+            self.set_option("decode_field_pictures", int(bool(field_pictures)))
+            try:
+                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced,
+                                          extended=extended, mb_tools=mb_tools, field_pictures=field_pictures)
+            finally:
+                self.set_option("decode_field_pictures", held_f)
         held_t = self._set.get("decode_mb_tools", 0)                       # what set_option("decode_mb_tools") left on the handle
         if int(bool(mb_tools)) != held_t:
             self.set_option("decode_mb_tools", int(bool(mb_tools)))
             try:
                 return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced,
-                                          extended=extended, mb_tools=mb_tools)
+                                          extended=extended, mb_tools=mb_tools, field_pictures=field_pictures)
             finally:
                 self.set_option("decode_mb_tools", held_t)
         held_x = self._set.get("decode_extended", 0)                       # what set_option("decode_extended") left on the handle
@@ -982,28 +998,28 @@ class Mpeg2Encoder:
             self.set_option("decode_extended", int(bool(extended)))
             try:
                 return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced,
-                                          extended=extended, mb_tools=mb_tools)
+                                          extended=extended, mb_tools=mb_tools, field_pictures=field_pictures)
             finally:
                 self.set_option("decode_extended", held_x)
         held_i = self._set.get("decode_interlaced", 0)                     # what set_option("decode_interlaced") left on the handle
         if int(bool(interlaced)) != held_i:
             self.set_option("decode_interlaced", int(bool(interlaced)))
             try:
-                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended, mb_tools=mb_tools)
+                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended, mb_tools=mb_tools, field_pictures=field_pictures)
             finally:
                 self.set_option("decode_interlaced", held_i)
         held_b = self._set.get("decode_b_pictures", 0)                     # what set_option("decode_b_pictures") left on the handle
         if int(bool(b_pictures)) != held_b:
             self.set_option("decode_b_pictures", int(bool(b_pictures)))
             try:
-                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended, mb_tools=mb_tools)
+                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended, mb_tools=mb_tools, field_pictures=field_pictures)
             finally:
                 self.set_option("decode_b_pictures", held_b)
         held = self._set.get("decode_syntax", DEC_SYNTAXES["module"])      # what set_option("decode_syntax") left on the handle
         if DEC_SYNTAXES[syntax] != held:
             self.set_option("decode_syntax", DEC_SYNTAXES[syntax])
             try:
-                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended, mb_tools=mb_tools)
+                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended, mb_tools=mb_tools, field_pictures=field_pictures)
             finally:
                 self.set_option("decode_syntax", held)
         if container is not None:

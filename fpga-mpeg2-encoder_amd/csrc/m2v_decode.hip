@@ -41,6 +41,8 @@
 // quant_matrix_extension, composite_display_flag 1; the same two places go to m2v_decode_x.hip (dec_x_plan, dec_x_chunks).  Option
 // "decode_mb_tools" = 1 on top of "decode_extended": Table B-15, concealment motion vectors, dual prime; from the same two places to
 // m2v_decode_t.hip (dec_t_plan, dec_t_chunks).
+// "decode_field_pictures" = 1 on top of "decode_interlaced", "decode_extended" and "decode_mb_tools": picture_structure 1 / 2, two field
+// pictures a frame; from the same two places to m2v_decode_f.hip (dec_f_plan, dec_f_chunks), whose chunks are whole frames.
 #include "m2v_decode_state.hpp"
 
 static_assert(sizeof(m2v_decode_stat) == 72, "the record of include/m2v_mi355x.h is 72 bytes");
@@ -390,6 +392,7 @@ static int decode_impl(m2v_enc *e, void *argp)
     const bool interlaced = e->decode_interlaced != 0;                 // m2v_decode_i.hip: the same two places, with b_pictures either way
     const bool extended = e->decode_extended != 0;                     // m2v_decode_x.hip: the same two places, with the other two either way
     const bool mb_tools = e->decode_mb_tools != 0;                     // m2v_decode_t.hip: in the places of dec_x_plan and dec_x_chunks
+    const bool field_pictures = e->decode_field_pictures != 0;         // m2v_decode_f.hip: in the places of dec_t_plan and dec_t_chunks
     e->d_dec_x.recorded = false;
     const size_t ntiles = (n + dec::kScanTile - 1) / dec::kScanTile;
     if (ntiles > 0x7FFFFFFFu) { e->set_err("m2v_decode_device: the stream is longer than 2^31 scan tiles"); return M2V_E_PARAM; }
@@ -418,7 +421,12 @@ static int decode_impl(m2v_enc *e, void *argp)
         HIPCHK(hipGetLastError());
         k_dec_scan<true><<<gx, kDecThreads, 0, s>>>(a->es, n, d_st, e->d_dec_tiles.p, e->d_dec_ev.p);
         HIPCHK(hipGetLastError());
-        if (extended) {
+        if (field_pictures) {
+            e->d_dec_main.ensure(kDecMainMatrices + pic_cap * sizeof(DecFPic));
+            dec_f_plan(s, a->es, n, e->d_dec_ev.p, d_st, (DecPic *)e->d_dec_pics.p, (uint32_t)pic_cap, e->h_dec + rec_off + 128, (unsigned long long)a->cap, a->dst ? 0 : 1,
+                       (m2v_decode_stat *)(e->h_dec + rec_off), e->d_dec_main.p, b_pictures ? 1 : 0, (uint32_t *)(e->h_dec + rec_off + 96),
+                       (uint32_t *)(e->h_dec + rec_off + 128 + ((pic_cap + 3) & ~(size_t)3) + 4 * pic_cap));
+        } else if (extended) {
             e->d_dec_main.ensure(kDecMainMatrices + pic_cap * sizeof(DecXPic));
             (mb_tools ? dec_t_plan : dec_x_plan)(s, a->es, n, e->d_dec_ev.p, d_st, (DecPic *)e->d_dec_pics.p, (uint32_t)pic_cap, e->h_dec + rec_off + 128, (unsigned long long)a->cap,
                        a->dst ? 0 : 1, (m2v_decode_stat *)(e->h_dec + rec_off), e->d_dec_main.p, b_pictures ? 1 : 0, interlaced ? 1 : 0,
@@ -453,6 +461,14 @@ static int decode_impl(m2v_enc *e, void *argp)
     const size_t np = R.pictures, mbw = (R.width + 15) / 16, mbh = (R.height + 15) / 16, mbs = mbw * mbh, psz = mbs * 384;
     size_t B = e->decode_batch ? e->decode_batch : std::max<size_t>(1, std::min(kDecBatchMax, kDecLevelBytes / (mbs * 768)));
     B = std::min(B, np);
+    if (field_pictures) {                                              // m2v_decode_f.hip; the record's pictures are frames, and so is "decode_batch"
+        const size_t rows = *(const uint32_t *)(e->h_dec + rec_off + 96), ncp = *(const uint32_t *)(e->h_dec + rec_off + 100);
+        if (!e->decode_batch) B = std::min(np, std::max<size_t>(1, std::min(kDecBatchMax, kDecLevelBytes / (mbw * rows * 768))));
+        auto *h_list = (uint32_t *)(e->h_dec + rec_off + 128 + ((pic_cap + 3) & ~(size_t)3));
+        dec_f_chunks(e, s, a->es, n, a->dst, a->layout, R, rows, B, types, ncp, h_list, h_list + pic_cap, (m2v_decode_stat *)(e->h_dec + rec_off));
+        R = *h_rec;
+        return M2V_OK;
+    }
     if (extended) {                                                    // m2v_decode_x.hip; the macroblock rows and the slices in front of every picture are the plan's
         const size_t rows = *(const uint32_t *)(e->h_dec + rec_off + 96);
         if (!e->decode_batch) B = std::min(np, std::max<size_t>(1, std::min(kDecBatchMax, kDecLevelBytes / (mbw * rows * 768))));
@@ -545,6 +561,11 @@ int m2v_decode_device(m2v_enc *e, const void *d_es, size_t es_bytes, void *d_dst
     if (!layout420_ok(layout)) { e->set_err("m2v_decode_device: unknown layout %d", layout); return M2V_E_PARAM; }
     if (mode != M2V_DEC_ISO && mode != M2V_DEC_MODULE) { e->set_err("m2v_decode_device: unknown mode %d", mode); return M2V_E_PARAM; }
     if (!d_es && es_bytes) { e->set_err("m2v_decode_device: d_es is NULL"); return M2V_E_PARAM; }
+    if (e->decode_field_pictures && (e->decode_syntax != M2V_SYNTAX_MAIN || mode != M2V_DEC_ISO || !e->decode_interlaced || !e->decode_extended || !e->decode_mb_tools)) {
+        e->set_err("m2v_decode_device: \"decode_field_pictures\" = 1 needs \"decode_syntax\" = main, the mode M2V_DEC_ISO and \"decode_interlaced\", "
+                   "\"decode_extended\" and \"decode_mb_tools\" = 1");
+        return M2V_E_PARAM;
+    }
     if (e->decode_b_pictures && (e->decode_syntax != M2V_SYNTAX_MAIN || mode != M2V_DEC_ISO)) {
         e->set_err("m2v_decode_device: \"decode_b_pictures\" = 1 needs \"decode_syntax\" = main and the mode M2V_DEC_ISO");
         return M2V_E_PARAM;

@@ -2328,5 +2328,401 @@ M2V_HD inline uint32_t t_picture_params(const uint8_t *es, uint64_t n, const uin
     return t_params_pack(q);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Field pictures (option "decode_field_pictures" on top of "decode_interlaced", "decode_extended" and "decode_mb_tools",
+// "decode_b_pictures" either way; decoder.decode_main(..., field_pictures=True) is the definition).  The functions above keep their
+// text; these stand beside them:
+//   extension   picture_structure 1 / 2 where progressive_sequence, progressive_frame, frame_pred_frame_dct, top_field_first and
+//               repeat_first_field are 0 (fp_picture_extension); the structure, "second field of its frame" and "no field of the same
+//               parity in front" ride in bits 24 .. 27 of the packed parameters.
+//   rows        a field has mbh / 2 macroblock rows: a slice's code and the place where a picture may end are judged with the rows of
+//               the picture whose coding extension is the nearest in front (fp_field_at, fp_event with the two plans).
+//   pairs       a picture is a picture header that reads (fp_is_picture), its structure that of the coding extension right behind
+//               it.  A field no first field waits for is a first field; the next picture is its partner, whatever it is (fp_feed),
+//               refused unless fp_partner_ok.  The state that crosses a range of events is FpRange: a range is summed twice, once for
+//               either state in front of it (fp_range), and the sums are joined in order (fp_join) - a pair parted by a range's edge
+//               plans as one inside a range does.
+//   macroblocks field_motion_type 1 field-based, 2 16 x 8, 3 dual prime; a select in front of every vector of the first two kinds and
+//               of a concealment vector; no component halved; no dct_type (fp_macroblock).  A record is an IMb whose two vectors of a
+//               direction are those of the upper and the lower 16 x 8 (a 16 x 16 prediction says the same twice) and whose selects name
+//               the parity; dual prime is both directions, "backward" the other parity with the derived vector.
+//   prediction  fp_predict: a sample of a field from the field of parity sel[.] of the frame that direction and parity name (fp_ref).
+// ---------------------------------------------------------------------------------------------------------------------------
+struct FPicParams { TPicParams t; uint32_t ps, second, noref; }; // picture_structure; the second field of its frame; no field of its own parity in front
+
+M2V_HD inline uint32_t fp_params_pack(const FPicParams &q) { return t_params_pack(q.t) | q.ps << 24 | q.second << 26 | q.noref << 27; }
+M2V_HD inline FPicParams fp_params_unpack(uint32_t v) { return FPicParams{t_params_unpack(v), (v >> 24) & 3u, (v >> 26) & 1u, (v >> 27) & 1u}; }
+M2V_HD inline bool fp_is_field(uint32_t ps) { return ps == 1u || ps == 2u; }
+
+// t_picture_extension that knows picture_structure 1 and 2
+M2V_HD inline bool fp_picture_extension(const uint8_t *es, uint64_t start, uint64_t end, uint32_t ptype, bool b_pictures, uint32_t progressive_sequence, FPicParams &q)
+{
+    Bits b = unit_bits(es, start, end);
+    bool ok = get(b, 4) == 8;
+    TPicParams &t = q.t;
+    t.i.b.p.fh = get(b, 4); t.i.b.p.fv = get(b, 4);
+    t.i.b.bh = get(b, 4); t.i.b.bv = get(b, 4);
+    t.i.b.p.prec = get(b, 2);
+    q.ps = get(b, 2);
+    t.tff = get(b, 1);
+    t.i.field = get(b, 1) ^ 1u;                              // frame_pred_frame_dct
+    t.cmv = get(b, 1);
+    t.i.b.p.qst = get(b, 1);
+    t.ivf = get(b, 1);
+    t.i.b.p.alt = get(b, 1);
+    const uint32_t repeat_first_field = get(b, 1);
+    skip(b, 1);                                              // chroma_420_type
+    const uint32_t progressive_frame = get(b, 1);
+    if (get(b, 1)) skip(b, 20);                              // composite_display_flag and what it announces
+    if (fp_is_field(q.ps)) ok = ok && !progressive_sequence && !progressive_frame && t.i.field && !t.tff && !repeat_first_field;
+    else ok = ok && q.ps == 3u;
+    ok = ok && (!t.i.field || il_field_allowed(progressive_sequence, progressive_frame));
+    const uint32_t ftype = t.cmv ? 0u : ptype;
+    ok = ok && main_fcode_ok(t.i.b.p.fh, ftype) && main_fcode_ok(t.i.b.p.fv, ftype);
+    if (b_pictures && ptype == 3) ok = ok && t.i.b.bh >= 1 && t.i.b.bh <= 9 && t.i.b.bv >= 1 && t.i.b.bv <= 9;
+    return ok && !b.err && tail_zero(b);
+}
+
+// the picture_structure bits of the coding extension at event j (3 where they are not there)
+M2V_HD inline uint32_t fp_structure_bits(const uint8_t *es, uint64_t n, uint64_t e) { return ev_pos(e) + 6 < n ? es[ev_pos(e) + 6] & 3u : 3u; }
+
+// whether the slice at event j belongs to a field picture: the coding extension nearest in front says so (bounded by j)
+M2V_HD inline bool fp_field_at(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t j)
+{
+    for (uint32_t k = j; k > 0; --k)
+        if (main_role(es, n, ev[k - 1]) == rPicExt && ev_pos(ev[k - 1]) + 6 < n) return fp_is_field(fp_structure_bits(es, n, ev[k - 1]));
+    return false;
+}
+
+// event i by its own rule: t_event with the rows of the picture the event is judged against - its own where it is a slice, else that of
+// the slice in front (Pf: P with mbh / 2) -, a coding extension by fp_picture_extension
+M2V_HD inline EvInfo fp_event(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, uint32_t i, const MainPlan &P, const MainPlan &Pf, uint64_t last_nz,
+                              int prev, bool b_pictures)
+{
+    const int role = x_role(es, n, ev[i]);
+    if (role == rPicExt) {
+        EvInfo r{kNone, 0, 0, 0, 0};
+        const uint64_t pos = ev_pos(ev[i]), end = i + 1 < nev ? ev_pos(ev[i + 1]) : n;
+        FPicParams q;
+        const int before = i ? main_role(es, n, ev[i - 1]) : rBad;
+        const uint64_t pp = i ? ev_pos(ev[i - 1]) : 0;
+        const uint32_t ptype = before == rPic && pp + 5 < n ? (es[pp + 5] >> 3) & 7u : 0u;
+        const bool ok = before == rPic && fp_picture_extension(es, pos, end, ptype, b_pictures, P.seq.h.progressive, q) && i + 1 != nev;
+        if (!ok) r.bad = pos;
+        return r;
+    }
+    const int j = role == rSlice ? (int)i : prev >= 0 && main_role(es, n, ev[prev]) == rSlice ? prev : -1;
+    const bool field = j >= 0 && fp_field_at(es, n, ev, (uint32_t)j);
+    return t_event(es, n, ev, nev, i, field ? Pf : P, last_nz, prev, b_pictures, true);
+}
+
+// whether event i is a picture: its header reads (what t_event's EvInfo::pic says); its type, temporal_reference and the structure of
+// the coding extension right behind it (3: a frame picture, or none there)
+M2V_HD inline bool fp_is_picture(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, uint32_t i, bool b_pictures, uint32_t &type, uint32_t &tref, uint32_t &ps)
+{
+    if (ev_code(ev[i]) != 0x00u) return false;
+    const uint64_t pos = ev_pos(ev[i]), end = i + 1 < nev ? ev_pos(ev[i + 1]) : n;
+    if (!(b_pictures ? bp_picture_header(es, pos, end, type) : parse_picture_header(es, pos, end, type))) return false;
+    tref = (uint32_t)es[pos + 4] << 2 | es[pos + 5] >> 6;    // (the header read: its bytes are there)
+    ps = 3u;
+    if (i + 1 < nev && main_role(es, n, ev[i + 1]) == rPicExt) ps = fp_structure_bits(es, n, ev[i + 1]);
+    if (!ps) ps = 3u;
+    return true;
+}
+
+// a first field that waits for its partner: 0 none, else 1 << 31 | temporal_reference << 5 | type << 2 | structure
+M2V_HD inline uint32_t fp_open_pack(uint32_t ps, uint32_t type, uint32_t tref) { return 1u << 31 | tref << 5 | type << 2 | ps; }
+
+// the partner of the first field `open`: the other parity, the same temporal_reference, the same type or P behind I
+M2V_HD inline bool fp_partner_ok(uint32_t open, uint32_t ps, uint32_t type, uint32_t tref)
+{
+    const uint32_t ops = open & 3u, otype = (open >> 2) & 7u, otref = (open >> 5) & 1023u;
+    return fp_is_field(ps) && ps != ops && tref == otref && (type == otype || (otype == 1u && type == 2u));
+}
+
+// what a run of pictures leaves: frames begun, I frames, anchor frames; the last I frame, the last two anchor frames and the coded
+// index of the last one's first picture (-1: none; counted from the run's first frame / picture); the first field that waits, its frame
+struct FpRange { uint32_t frames, ni, na; int32_t last, a1, a2, a1cp; uint32_t open, openf; };
+
+M2V_HD inline FpRange fp_range_none() { return FpRange{0, 0, 0, -1, -1, -1, -1, 0, 0}; }
+
+// one picture, the cp-th of the run, into the run's sums: true = it begins a frame, false = it is the partner of the field that waited
+M2V_HD inline bool fp_feed(FpRange &r, uint32_t cp, uint32_t ps, uint32_t type, uint32_t tref)
+{
+    if (r.open) { r.open = 0; return false; }
+    const int32_t f = (int32_t)r.frames++;
+    if (type == 1u) { r.last = f; ++r.ni; }
+    if (type != 3u) { r.a2 = r.a1; r.a1 = f; r.a1cp = (int32_t)cp; ++r.na; }
+    if (fp_is_field(ps)) { r.open = fp_open_pack(ps, type, tref); r.openf = (uint32_t)f; }
+    return true;
+}
+
+// the pictures of events [a, b) summed twice: A with nothing waiting in front, B with a first field waiting (the first picture is its
+// partner); m: the pictures
+M2V_HD inline void fp_range(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, uint32_t a, uint32_t b, bool b_pictures, FpRange &A, FpRange &B, uint32_t &m)
+{
+    A = B = fp_range_none();
+    m = 0;
+    for (uint32_t i = a; i < b; ++i) {
+        uint32_t type, tref, ps;
+        if (!fp_is_picture(es, n, ev, nev, i, b_pictures, type, tref, ps)) continue;
+        (void)fp_feed(A, m, ps, type, tref);
+        if (m) (void)fp_feed(B, m, ps, type, tref);
+        ++m;
+    }
+}
+
+// `in`: the sums of everything in front (absolute), cp pictures; a range of m pictures follows - its sums A or B as `in` says
+M2V_HD inline void fp_join(FpRange &in, uint32_t &cp, const FpRange &A, const FpRange &B, uint32_t m)
+{
+    if (!m) return;                                          // (a field that waits goes on waiting)
+    const FpRange &r = in.open ? B : A;
+    const int32_t base = (int32_t)in.frames;
+    if (r.last >= 0) in.last = base + r.last;
+    if (r.na >= 2u) { in.a2 = base + r.a2; in.a1 = base + r.a1; }
+    else if (r.na == 1u) { in.a2 = in.a1; in.a1 = base + r.a1; }
+    if (r.na) in.a1cp = (int32_t)cp + r.a1cp;
+    in.frames += r.frames; in.ni += r.ni; in.na += r.na;
+    in.open = r.open; in.openf = (uint32_t)base + r.openf;
+    cp += m;
+}
+
+// what the plan knows of a coded picture beyond its parameters
+struct FpPlace { uint32_t frame, second, fwd, bwd; bool bad; };  // fwd / bwd: frames (0xFFFFFFFF: none)
+
+// picture (ps, type, tref) at coded index cp behind the sums `s` (absolute): its place, and s moved on.  bad: refused at its header - not
+// a legal partner, no I frame so far, a B picture without two anchor frames
+M2V_HD inline FpPlace fp_place(FpRange &s, uint32_t cp, uint32_t ps, uint32_t type, uint32_t tref)
+{
+    FpPlace q{0, 0, kNoEvent, kNoEvent, false};
+    const uint32_t open = s.open, openf = s.openf;
+    const int32_t a1 = s.a1, a2 = s.a2;                      // the anchor frames in front of this picture's frame, if it begins one
+    if (fp_feed(s, cp, ps, type, tref)) {
+        q.frame = s.frames - 1u;
+        if (type == 2u) q.fwd = q.bwd = (uint32_t)a1;        // (a dual-prime macroblock's second prediction reads the same frame)
+        if (type == 3u) { q.fwd = (uint32_t)a2; q.bwd = (uint32_t)a1; }
+    } else {
+        q.frame = openf; q.second = 1;
+        q.bad = !fp_partner_ok(open, ps, type, tref);
+        // the field of its own parity: in the anchor frame in front of its own frame (its own frame is s.a1 where it is an anchor)
+        if (type == 2u) q.fwd = q.bwd = (uint32_t)(s.a1 == (int32_t)openf ? s.a2 : s.a1);
+        if (type == 3u) { q.fwd = (uint32_t)s.a2; q.bwd = (uint32_t)s.a1; }
+    }
+    q.bad = q.bad || s.last < 0 || (type == 3u && s.na < 2u);
+    return q;
+}
+
+// fp_picture_params: t_picture_params with fp_picture_extension's parameters (the place's bits are the caller's)
+M2V_HD inline FPicParams fp_picture_params(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, uint32_t i, bool b_pictures, uint32_t progressive_sequence,
+                                           uint32_t &slice0, uint32_t &nslices, uint32_t &quant)
+{
+    FPicParams q{TPicParams{IPicParams{BPicParams{PicParams{1, 1, 0, 0, 0}, 1, 1}, 0}, 0, 0, 0}, 3, 0, 0};
+    uint32_t j = i + 2;
+    if (i + 1 < nev) {
+        const uint64_t pos = ev_pos(ev[i]);
+        (void)fp_picture_extension(es, ev_pos(ev[i + 1]), i + 2 < nev ? ev_pos(ev[i + 2]) : n, pos + 5 < n ? (es[pos + 5] >> 3) & 7u : 0u, b_pictures, progressive_sequence, q);
+    }
+    quant = kNoEvent;
+    for (; j < nev && !main_significant(main_role(es, n, ev[j])); ++j)
+        if (quant == kNoEvent && x_role(es, n, ev[j]) == rQuant) quant = j;
+    slice0 = j;
+    for (; j < nev && main_role(es, n, ev[j]) == rSlice; ++j) {}
+    nslices = j - slice0;
+    return q;
+}
+
+// ---- macroblock layer of a field picture ----
+// the two vectors of direction d (the upper and the lower 16 x 8) and their selects
+M2V_HD inline void fp_set_vector(IMb &m, int d, int r, int32_t vx, int32_t vy, uint32_t sel)
+{
+    if (d == 0) { if (r == 0) { m.mvx = (int16_t)vx; m.mvy = (int16_t)vy; } else { m.mvx1 = (int16_t)vx; m.mvy1 = (int16_t)vy; } }
+    else { if (r == 0) { m.bvx = (int16_t)vx; m.bvy = (int16_t)vy; } else { m.bvx1 = (int16_t)vx; m.bvy1 = (int16_t)vy; } }
+    m.sel[2 * d + r] = (uint8_t)sel;
+}
+
+// which reference fields a field picture has: bit 2 d + q, direction d, parity q.  A P field's "backward" fields are its forward ones
+M2V_HD inline uint32_t fp_have(uint32_t ptype, const FPicParams &pp)
+{
+    if (ptype == 1u) return 0u;
+    if (ptype == 3u) return 15u;
+    const uint32_t par = pp.ps - 1u;
+    const uint32_t f = pp.noref ? 1u << (par ^ 1u) : 3u;     // the second field of the stream's first frame: only its first field
+    return f | f << 2;
+}
+
+// the reads of a record lie inside fields that are there: both halves of either direction (a 16 x 16 read is inside where both of its
+// halves are, the vector being the same); rows: the field's macroblock rows
+M2V_HD inline bool fp_inside(int col, int row, const IMb &m, int mbw, int rows, uint32_t have)
+{
+    bool ok = true;
+    if (m.dirs & kFwd) ok = ok && ((have >> m.sel[0]) & 1u) && ((have >> m.sel[1]) & 1u) && il_field_inside(col, 2 * row, m.mvx, m.mvy, mbw, 2 * rows) &&
+                            il_field_inside(col, 2 * row + 1, m.mvx1, m.mvy1, mbw, 2 * rows);
+    if (m.dirs & kBwd) ok = ok && ((have >> (2u + m.sel[2])) & 1u) && ((have >> (2u + m.sel[3])) & 1u) && il_field_inside(col, 2 * row, m.bvx, m.bvy, mbw, 2 * rows) &&
+                            il_field_inside(col, 2 * row + 1, m.bvx1, m.bvy1, mbw, 2 * rows);
+    return ok;
+}
+
+// one macroblock of a field picture behind its address increment; pmv: PMV[r][s][t]; false = refused
+template <class Put>
+M2V_HD inline bool fp_macroblock(Bits &b, uint32_t ptype, const FPicParams &pp, SliceState &s, int32_t (&pmv)[2][2][2], uint32_t &qcode, IMb &m, int32_t (&dc)[6], Put put)
+{
+    const uint32_t e = ptype == 3 ? vlc_type_b(peek(b, 6)) : il_type_ip(peek(b, 6), ptype);
+    if (!e) return false;
+    skip(b, (int)(e & 255u));
+    const uint32_t flags = e >> 8;
+    const bool intra = (flags & 1u) != 0, pattern = ((flags >> 1) & 1u) != 0;
+    const uint32_t dirs = (((flags >> 3) & 1u) ? (uint32_t)kFwd : 0u) | (((flags >> 2) & 1u) ? (uint32_t)kBwd : 0u);
+    const uint32_t par = pp.ps - 1u;
+    const BPicParams &f = pp.t.i.b;
+    uint32_t motion_type = 1;                                // field_motion_type: 1 field-based, 2 16 x 8, 3 dual prime (a P field only)
+    if (dirs) {
+        motion_type = get(b, 2);
+        if (motion_type == 0u || (motion_type == 3u && ptype != 2)) return false;
+    }
+    if (flags >> 4) {
+        qcode = get(b, 5);
+        if (!qcode) return false;
+    }
+    m = IMb{};
+    for (int k = 0; k < 4; ++k) m.sel[k] = (uint8_t)par;
+    bool dual = false;
+    if (motion_type == 3u) {                                 // component, dmvector, component, dmvector; no select
+        if (!bp_component(b, pmv[0][0][0], (int)f.p.fh - 1)) return false;
+        const int32_t d0 = t_dmvector(b);
+        if (!bp_component(b, pmv[0][0][1], (int)f.p.fv - 1)) return false;
+        const int32_t d1 = t_dmvector(b);
+        pmv[1][0][0] = pmv[0][0][0]; pmv[1][0][1] = pmv[0][0][1];
+        const int32_t vx = pmv[0][0][0], vy = pmv[0][0][1];
+        const int32_t ox = t_half(vx) + d0, oy = t_half(vy) + d1 + (par ? 1 : -1);
+        for (int r = 0; r < 2; ++r) { fp_set_vector(m, 0, r, vx, vy, par); fp_set_vector(m, 1, r, ox, oy, par ^ 1u); }
+        dual = true;
+    }
+    for (int d = 0; d < 2 && !dual; ++d) {
+        if (!(dirs & (d ? (uint32_t)kBwd : (uint32_t)kFwd))) continue;
+        const int r_h = (int)(d ? f.bh : f.p.fh) - 1, r_v = (int)(d ? f.bv : f.p.fv) - 1;
+        if (motion_type == 1u) {                             // field-based: from PMV[0][s]; PMV[1][s] follows
+            const uint32_t sel = get(b, 1);
+            if (!bp_component(b, pmv[0][d][0], r_h) || !bp_component(b, pmv[0][d][1], r_v)) return false;
+            pmv[1][d][0] = pmv[0][d][0]; pmv[1][d][1] = pmv[0][d][1];
+            for (int r = 0; r < 2; ++r) fp_set_vector(m, d, r, pmv[0][d][0], pmv[0][d][1], sel);
+            continue;
+        }
+        for (int r = 0; r < 2; ++r) {                        // 16 x 8: vector r from and into PMV[r][s]
+            const uint32_t sel = get(b, 1);
+            if (!bp_component(b, pmv[r][d][0], r_h) || !bp_component(b, pmv[r][d][1], r_v)) return false;
+            fp_set_vector(m, d, r, pmv[r][d][0], pmv[r][d][1], sel);
+        }
+    }
+    if (intra && pp.t.cmv) {                                 // a concealment vector behind its select: kept in the predictors, not used
+        skip(b, 1);
+        if (!bp_component(b, pmv[0][0][0], (int)f.p.fh - 1) || !bp_component(b, pmv[0][0][1], (int)f.p.fv - 1)) return false;
+        pmv[1][0][0] = pmv[0][0][0]; pmv[1][0][1] = pmv[0][0][1];
+        if (!get(b, 1)) return false;                        // marker_bit
+    } else if (intra || (ptype == 2 && !(dirs & kFwd))) {    // 7.6.3.4
+        for (int r = 0; r < 2; ++r) for (int d = 0; d < 2; ++d) pmv[r][d][0] = pmv[r][d][1] = 0;
+    }
+    uint32_t cbp = intra ? 63u : 0u;
+    if (pattern) {
+        const uint32_t c = vlc_cbp(peek(b, 32));
+        if (!c) return false;
+        skip(b, (int)(c & 255u));
+        cbp = c >> 8;
+    }
+    if (!intra) { for (int c = 0; c < 3; ++c) s.dc_pred[c] = 0; }       // 7.2.1
+    m.intra = intra; m.cbp = (uint8_t)cbp; m.mc = (dirs & kFwd) != 0;
+    m.dirs = (uint8_t)(intra ? 0u : dual ? (uint32_t)(kFwd | kBwd) : ptype == 2 ? (uint32_t)kFwd : dirs);      // a P field's macroblock without a vector: the zero vector, its own parity
+    m.motion_type = (uint8_t)kFieldBased;
+    for (int blk = 0; blk < 6; ++blk) {
+        dc[blk] = 0;
+        if (!((cbp >> (5 - blk)) & 1u)) continue;
+        if (!t_block(b, intra, pp.t.ivf != 0, blk < 4 ? 0 : blk - 3, s, dc[blk],
+                     [&](uint32_t i, int32_t l) { put(blk, f.p.alt ? alternate_to_raster(zigzag_position(i)) : i, l); })) return false;
+    }
+    return !b.err;
+}
+
+// t_slice for a field picture: rows macroblock rows, fp_macroblock, skipped macroblocks field-predicted from the field of the same parity
+template <class Sink>
+M2V_HD inline bool fp_slice(const uint8_t *es, uint64_t start, uint64_t end, uint32_t ptype, const FPicParams &pp, int mbw, int rows, int row, Sink &sink,
+                            int &first, int &last)
+{
+    first = last = -1;
+    if (end < start + 4) return false;
+    Bits b = unit_bits(es, start, end);
+    const uint64_t lim = x_last_one(es, start + 4, end);
+    uint32_t qcode = get(b, 5);
+    if (get(b, 1)) {                                         // intra_slice_flag
+        skip(b, 8);
+        while (get(b, 1)) skip(b, 8);
+    }
+    if (b.err) return false;
+    const uint32_t have = fp_have(ptype, pp), par = pp.ps - 1u;
+    SliceState s{{0, 0, 0}, {0, 0}};
+    int32_t pmv[2][2][2] = {{{0, 0}, {0, 0}}, {{0, 0}, {0, 0}}};
+    uint32_t dirs = 0;
+    int col = -1;
+    const int32_t none[6] = {0, 0, 0, 0, 0, 0};
+    while (b.pos < lim) {
+        int incr = 0;
+        uint32_t e;
+        for (;;) {
+            e = vlc_increment(peek(b, 11));
+            if (!e) return false;
+            skip(b, (int)(e & 255u));
+            if ((e >> 8) != 34u) break;
+            incr += 33;                                      // macroblock_escape
+            if (col + incr >= mbw) return false;
+        }
+        incr += (int)(e >> 8);
+        if (col + incr >= mbw || b.err) return false;
+        if (col < 0) {
+            first = incr - 1;
+        } else if (incr > 1) {                               // 7.6.6: skipped - field prediction from the same parity, no residual
+            if (ptype == 1) return false;
+            IMb z{};
+            z.skipped = 1; z.qcode = (uint8_t)qcode; z.motion_type = (uint8_t)kFieldBased;
+            for (int k = 0; k < 4; ++k) z.sel[k] = (uint8_t)par;
+            if (ptype == 2) {                                // the zero vector, the predictors reset
+                z.dirs = (uint8_t)kFwd;
+                for (int r = 0; r < 2; ++r) for (int d = 0; d < 2; ++d) pmv[r][d][0] = pmv[r][d][1] = 0;
+            } else {                                         // the directions in front, PMV[0][s]
+                if (!dirs) return false;
+                z.dirs = (uint8_t)dirs; z.mc = (dirs & kFwd) != 0;
+                for (int d = 0; d < 2; ++d)
+                    if (dirs & (d ? (uint32_t)kBwd : (uint32_t)kFwd)) for (int r = 0; r < 2; ++r) fp_set_vector(z, d, r, pmv[0][d][0], pmv[0][d][1], par);
+            }
+            for (int k = 1; k < incr; ++k) {
+                if (!fp_inside(col + k, row, z, mbw, rows, have)) return false;
+                sink.mb(col + k, z, none);
+            }
+            for (int c = 0; c < 3; ++c) s.dc_pred[c] = 0;
+        }
+        col += incr;
+        IMb m;
+        int32_t dc[6];
+        if (!fp_macroblock(b, ptype, pp, s, pmv, qcode, m, dc, [&](int blk, uint32_t i, int32_t l) { sink.level(col, blk, i, l); })) return false;
+        if (!fp_inside(col, row, m, mbw, rows, have)) return false;
+        m.qcode = (uint8_t)qcode;
+        dirs = m.dirs;
+        sink.mb(col, m, dc);
+    }
+    last = col;
+    return !b.err && col >= 0;
+}
+
+// the prediction of the sample at (x, y) of a field for a record of a field picture: y is a line of the field, r the half of the
+// macroblock it lies in.  ref[2 d + q]: the frame plane that holds the field of parity q of direction d (the field is rows q, q + 2, ..
+// of it; stride: the frame's); chroma: the vectors are halved toward zero
+M2V_HD inline int32_t fp_predict(const uint8_t *const (&ref)[4], int stride, int x, int y, int r, const IMb &m, bool chroma)
+{
+    int fx = r ? m.mvx1 : m.mvx, fy = r ? m.mvy1 : m.mvy, bx = r ? m.bvx1 : m.bvx, by = r ? m.bvy1 : m.bvy;
+    if (chroma) { fx = chroma_vector(fx, kIso); fy = chroma_vector(fy, kIso); bx = chroma_vector(bx, kIso); by = chroma_vector(by, kIso); }
+    const int sf = r ? m.sel[1] : m.sel[0], sb = r ? m.sel[3] : m.sel[2];
+    int32_t a = 0, c = 0;
+    if (m.dirs & kFwd) a = predict((sf ? ref[1] : ref[0]) + (size_t)sf * stride, 2 * stride, x + (fx >> 1), y + (fy >> 1), fx & 1, fy & 1, kIso);
+    if (m.dirs & kBwd) c = predict((sb ? ref[3] : ref[2]) + (size_t)sb * stride, 2 * stride, x + (bx >> 1), y + (by >> 1), bx & 1, by & 1, kIso);
+    return m.dirs == (kFwd | kBwd) ? bp_mean(a, c) : (m.dirs & kFwd) ? a : c;
+}
+
 }  // namespace dec
 }  // namespace m2v

@@ -70,4 +70,17 @@ void dec_t_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long 
 void dec_t_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_t *dst, int layout, const m2v_decode_stat &R, size_t mbh, size_t B,
                   const uint8_t *types, uint32_t *h_list, const uint32_t *h_sl, m2v_decode_stat *h_rec);
 
+// Field pictures (option "decode_field_pictures" on top of "decode_interlaced", "decode_extended" and "decode_mb_tools";
+// m2v_decode_f.hip): the table behind the matrices holds one DecFPic a CODED PICTURE - a frame picture or one field -, DecXPic's fields
+// with display, fwd and bwd counted in FRAMES, and the picture's frame.  params: dec::fp_params_pack (the structure, "second field of its
+// frame" and "no field of its own parity in front" above bit 23).  The record counts frames; the plan leaves the coded pictures at
+// h_mbh[1], every coded picture's type | structure << 2 | second << 4 at h_types and the slices in front of it at h_sl.  A chunk is B
+// whole frames
+struct DecFPic { uint32_t slice0, params, display, fwd, bwd, nslices, sbase, mi, mn, frame; };
+
+void dec_f_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long long *ev, DecState *st, DecPic *pics, uint32_t pic_cap, uint8_t *h_types,
+                unsigned long long cap, int probe, m2v_decode_stat *h_rec, uint8_t *d_main, int b_pictures, uint32_t *h_mbh, uint32_t *h_sl);
+void dec_f_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_t *dst, int layout, const m2v_decode_stat &R, size_t mbh, size_t B,
+                  const uint8_t *types, size_t ncp, uint32_t *h_list, const uint32_t *h_sl, m2v_decode_stat *h_rec);
+
 }  // namespace m2v

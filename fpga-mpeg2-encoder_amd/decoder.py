@@ -301,7 +301,7 @@ def sequence_headers(data):
     return _sequence_headers(BitReader(data))
 
 
-def decode(data, quirks=True, syntax="module", b_pictures=False, interlaced=False, extended=False, mb_tools=False):
+def decode(data, quirks=True, syntax="module", b_pictures=False, interlaced=False, extended=False, mb_tools=False, field_pictures=False):
     """syntax="module" (the default): the subset this encoder emits, as the head of this file says.  syntax="main": Main-Profile
     streams of progressive frame pictures, I and P, 4:2:0, from any encoder (decode_main below); it needs quirks=False, and a
     refusal is a Refused exception that names the unit.  b_pictures=True (syntax="main" only): B pictures too, and the frames in
@@ -312,7 +312,11 @@ def decode(data, quirks=True, syntax="module", b_pictures=False, interlaced=Fals
     composite_display_flag 1 too (the section "Several slices a row" below); with False the function is what it was for every input.
     mb_tools=True (with extended=True only, the other two either way): Table B-15 for the intra blocks of a picture with
     intra_vlc_format 1, concealment motion vectors, and dual prime in a P picture with frame_pred_frame_dct 0 (the section "The
-    macroblock tools" below); with False the function is what it was for every input."""
+    macroblock tools" below); with False the function is what it was for every input.  field_pictures=True (with interlaced, extended
+    and mb_tools all True, b_pictures either way): pictures with picture_structure 1 / 2 too, two of them woven into one frame (the
+    section "Field pictures" below); with False the function is what it was for every input."""
+    if field_pictures and not (syntax == "main" and interlaced and extended and mb_tools):
+        raise ValueError("field_pictures goes with syntax=\"main\", interlaced=True, extended=True and mb_tools=True")
     if mb_tools and not extended:
         raise ValueError("mb_tools goes with extended=True")
     if extended and syntax != "main":
@@ -323,7 +327,7 @@ def decode(data, quirks=True, syntax="module", b_pictures=False, interlaced=Fals
         raise ValueError("interlaced goes with syntax=\"main\"")
     if syntax == "main":
         assert not quirks, "the module's quirks have no meaning outside its own syntax"
-        return decode_main(data, b_pictures, interlaced, extended, mb_tools)
+        return decode_main(data, b_pictures, interlaced, extended, mb_tools, field_pictures)
     assert syntax == "module", syntax
     T = tables()
     br = BitReader(data)
@@ -637,7 +641,7 @@ def psnr(a, b):
 #   skipped     frame prediction: a P picture's with the zero vector; a B picture's in the directions of the macroblock in front with
 #               PMV[0][s] as frame vectors - behind a field-based macroblock twice its first field vector's vertical component.
 # Decoded.mbs of such a picture carry motion_type, dct_type, selects[s][r] and vectors[s][r] besides the fields above.  Still
-# refused: field pictures, dual prime, concealment vectors.  Every stream accepted with interlaced=False decodes to the same frames
+# refused: field pictures (without field_pictures, below), dual prime, concealment vectors.  Every stream accepted with interlaced=False decodes to the same frames
 # and fields with True, but for the macroblock-row exception above.
 # ---------------------------------------------------------------------------------------------------------------
 #
@@ -665,7 +669,7 @@ def psnr(a, b):
 #               loaded matrix is in force from that picture on in coded order, each matrix on its own; any sequence header, repeated
 #               ones included, puts both back to the sequence's
 #   composite   composite_display_flag 1: the 20 bits behind it are read and not acted on
-# Still refused: field pictures, leading B pictures, D pictures - dual prime, concealment vectors and Table B-15 too without mb_tools,
+# Still refused: leading B pictures, D pictures - field pictures too without field_pictures, dual prime, concealment vectors and Table B-15 too without mb_tools,
 # below -, and everything else the main syntax refuses, where it is refused.  Every stream accepted with extended=False, under any setting of the other two, decodes to
 # the same frames and fields with True.
 #
@@ -683,8 +687,40 @@ def psnr(a, b):
 #               derived vectors are T = (h(vx) + d0, h(vy) + d1 - 1) and B = (h(3 vx) + d0, h(3 vy) + d1 + 1); with top_field_first 0
 #               the factors 1 and 3 change places.  Top-field lines: the mean of the top field by (vx, vy) and the bottom field by T;
 #               bottom-field lines: the mean of the bottom field by (vx, vy) and the top field by B; every read inside its field
-# Still refused: field pictures, leading B pictures, D pictures, dual prime in a B picture.  Every stream accepted with mb_tools=False
+# Still refused: leading B pictures, D pictures, dual prime in a B picture - field pictures too without field_pictures, below.  Every stream accepted with mb_tools=False
 # and extended=True decodes to the same frames with True.
+#
+# Field pictures (decode(..., syntax="main", interlaced=True, extended=True, mb_tools=True, field_pictures=True), b_pictures either way;
+# option "decode_field_pictures" of the device decoder; 6.1.1.4, 6.3.10, 6.3.17, 7.6.2 - 7.6.3.6, 7.6.6, 7.6.7).  Added:
+#   extension   picture_structure 1 (top field) and 2 (bottom field) where progressive_sequence, progressive_frame, frame_pred_frame_dct,
+#               top_field_first and repeat_first_field are all 0; 0 (reserved) stays refused, all at the coding extension
+#   pairs       a coded frame is one frame picture or two field pictures that follow each other in coded order.  A picture is a unit
+#               whose picture header reads; its structure is that of the coding extension right behind it (3 where there is none).  A
+#               field picture that no first field waits for is a first field; the next picture is its partner, whatever it is, and is
+#               refused at its picture header unless it is a field of the other parity with the same temporal_reference and the same
+#               picture_coding_type (or a P field behind an I field).  While a first field waits, a sequence header, a GOP header or a
+#               sequence_end_code is refused at its start code; a first field no picture follows is refused at its own picture header
+#   geometry    a field has mbh / 2 macroblock rows (mbh = 2 * ((height + 31) // 32)): the slice codes run to that, a field ends only
+#               behind that code, continuity is judged per field.  Row r, line k of the field of parity p is frame line 32 r + 2 k + p
+#   modes       field_motion_type (2 bits) where the macroblock has a vector: 1 field-based (one vector a direction), 2 16 x 8 (two), 3
+#               dual prime (a P field only), 0 refused; no dct_type.  motion_vertical_field_select in front of every vector of the first
+#               two kinds.  No component is halved or doubled.  Field-based: from PMV[0][s], PMV[1][s] = PMV[0][s] afterwards; 16 x 8:
+#               vector r from and into PMV[r][s]; dual prime: no select, a dmvector behind each component, PMV[1][0] = PMV[0][0].  A
+#               concealment vector carries a select (read, not used), sets PMV[0][0] and PMV[1][0], and its marker bit follows
+#   prediction  the field a select names is the most recently decoded anchor field of that parity: the fields of the anchor frame(s)
+#               - but for the second field of an anchor frame the field of the other parity is the first field of its own frame, and
+#               that of its own parity belongs to the anchor frame in front (none in the stream's first frame: such a select refuses
+#               the slice).  Field-based 16 x 16 (chroma 8 x 8, both components / 2 toward zero); 16 x 8: the upper half by vector 0, the
+#               lower by vector 1 (chroma 8 x 4 each); dual prime: (a + b + 1) >> 1 of the field of the same parity by (vx, vy) and the
+#               other one by (h(vx) + d0, h(vy) + d1 + e), h(a) = (a + (a > 0)) >> 1, e = -1 in a top field, +1 in a bottom field.  Every
+#               read inside its field.  A P field's macroblock without a vector and its skipped macroblock: the zero vector from the
+#               field of the same parity, the predictors reset; a B field's skipped macroblock: the directions in front, PMV[0][s],
+#               field-based from the same parity
+#   output      one frame a coded frame, both fields woven; a frame's type is its first field's (I + P is an I frame); display order,
+#               Decoded.pictures (the frame picture's or the first field's fields), gops and repeated_headers count frames;
+#               Decoded.fields, .mbs and .slice_qcodes are per coded picture.  A B frame needs two anchor frames in front of it
+# Still refused: leading B pictures, D pictures, dual prime in a B picture.  Every stream accepted with field_pictures=False and the
+# other three on decodes to the same frames with True.
 # ---------------------------------------------------------------------------------------------------------------
 class Refused(Exception):
     def __init__(self, offset, why=""):
@@ -811,7 +847,8 @@ def _main_display_extension(data, start, end, h):
     assert br.rest_is_zero()
 
 
-def _main_picture_extension(data, start, end, ptype, b_pictures=False, interlaced=False, progressive_sequence=1, extended=False, mb_tools=False):
+def _main_picture_extension(data, start, end, ptype, b_pictures=False, interlaced=False, progressive_sequence=1, extended=False, mb_tools=False,
+                            field_pictures=False):
     br = _UnitBits(data, start, end)
     assert br.bits(4) == 8
     pic = dict(f_code=[br.bits(4) for _ in range(4)])
@@ -819,7 +856,10 @@ def _main_picture_extension(data, start, end, ptype, b_pictures=False, interlace
                frame_pred_frame_dct=br.bits(1), concealment_motion_vectors=br.bits(1), q_scale_type=br.bits(1),
                intra_vlc_format=br.bits(1), alternate_scan=br.bits(1), repeat_first_field=br.bits(1),
                chroma_420_type=br.bits(1), progressive_frame=br.bits(1), composite_display_flag=br.bits(1))
-    assert pic["picture_structure"] == 3
+    if field_pictures and pic["picture_structure"] in (1, 2):   # a field picture: nothing progressive, no frame prediction, no field order
+        assert not (progressive_sequence or pic["progressive_frame"] or pic["frame_pred_frame_dct"] or pic["top_field_first"] or pic["repeat_first_field"])
+    else:
+        assert pic["picture_structure"] == 3
     if pic["frame_pred_frame_dct"] != 1:                        # 6.3.10: 0 only where neither the sequence nor the frame is progressive
         assert interlaced and not progressive_sequence and not pic["progressive_frame"], "frame_pred_frame_dct"
     assert mb_tools or (pic["concealment_motion_vectors"] == 0 and pic["intra_vlc_format"] == 0)
@@ -882,7 +922,7 @@ def _main_mbh(hdr, interlaced=False):
     return (hdr["height"] + 15) // 16
 
 
-def _main_plan(data, b_pictures=False, interlaced=False, extended=False, mb_tools=False):
+def _main_plan(data, b_pictures=False, interlaced=False, extended=False, mb_tools=False, field_pictures=False):
     """the grammar over the start codes -> (sequence fields, pictures, gops, repeated headers, number of start codes)"""
     n = len(data)
     ev = start_codes(data)
@@ -931,10 +971,17 @@ def _main_plan(data, b_pictures=False, interlaced=False, extended=False, mb_tool
     anchors = 0
     mats = [first["intra_matrix"], first["non_intra_matrix"]]   # the matrices in force (extended: a quant_matrix_extension replaces them)
     quant_seen = False
+    rows = mbh                                                  # field_pictures: the macroblock rows of the picture whose coding extension was the last
+    waiting = None                                              # field_pictures: the first field whose partner has not come
+    frames, frame_i, frame_anchors = 0, False, 0                # field_pictures: the frames, whether one of them is an I frame, the anchor frames
     for i, (pos, code) in enumerate(ev):
         role, end = roles[i], ends[i]
         prole = roles[prev] if prev is not None else None
         top = prole in (_SEQEXT, _DISP) or (prole == _SLICE and ev[prev][1] == mbh)
+        if field_pictures:                                      # a field ends behind the slice of its own last row
+            top = prole in (_SEQEXT, _DISP) or (prole == _SLICE and ev[prev][1] == rows)
+            if waiting is not None and role in (_SEQ, _GOP, _END):
+                bad.append(pos)                                 # between the two fields of a frame
         ok = True
         try:
             if role == _BAD:
@@ -993,17 +1040,41 @@ def _main_plan(data, b_pictures=False, interlaced=False, extended=False, mb_tool
                 anchors += pic["type"] != 3
                 pic["matrices"] = mats
                 pictures.append(pic)
+                if field_pictures:                              # the pairs; the two rules above once more, counted in frames
+                    ps = data[ev[i + 1][0] + 6] & 3 if i + 1 < len(ev) and roles[i + 1] == _PICEXT and ev[i + 1][0] + 6 < n else 3
+                    if waiting is not None:                     # the partner, whatever it is
+                        legal = ps in (1, 2) and ps != waiting["ps"] and pic["temporal_reference"] == waiting["temporal_reference"] and \
+                            (pic["type"] == waiting["type"] or (waiting["type"] == 1 and pic["type"] == 2))
+                        if not legal:
+                            bad.append(pos)
+                        pic.update(frame=waiting["frame"], second=True)
+                        waiting = None
+                    else:
+                        pic.update(frame=frames, second=False)
+                        frames += 1
+                        frame_i = frame_i or pic["type"] == 1
+                        if ps in (1, 2):
+                            waiting = dict(ps=ps, pos=pos, frame=pic["frame"], type=pic["type"], temporal_reference=pic["temporal_reference"])
+                    if not frame_i:
+                        bad.append(pos)                         # a P picture without a reference
+                    if pic["type"] == 3 and frame_anchors < 2:
+                        bad.append(pos)                         # a B picture without two anchor frames in front of it
+                    frame_anchors += pic["type"] != 3 and not pic["second"]
             elif role == _PICEXT:
                 ok = i > 0 and roles[i - 1] == _PIC
                 ptype = (data[ev[i - 1][0] + 5] >> 3) & 7 if ok and ev[i - 1][0] + 5 < n else 0
                 quant_seen = False
-                ext = _main_picture_extension(data, pos, end, ptype, b_pictures, interlaced, first["progressive_sequence"], extended, mb_tools)
+                if field_pictures and pos + 6 < n:              # the rows of this picture's slices, from the two bits alone
+                    rows = mbh // 2 if data[pos + 6] & 3 in (1, 2) else mbh
+                ext = _main_picture_extension(data, pos, end, ptype, b_pictures, interlaced, first["progressive_sequence"], extended, mb_tools, field_pictures)
                 if ok and pictures and pictures[-1]["unit"] == i - 1:
                     pictures[-1].update(ext)
             elif role == _SLICE:
                 ok = code <= mbh and (prole == _PICEXT if code == 1 else prole == _SLICE and ev[prev][1] == code - 1)
                 if extended:                                    # the first has code 1, a further one its predecessor's code or that + 1
                     ok = code <= mbh and ((code == 1 and prole == _PICEXT) or (prole == _SLICE and ev[prev][1] in (code, code - 1)))
+                if field_pictures:
+                    ok = ok and code <= rows
                 if ok and pictures:
                     pictures[-1]["slices"].append(i)
             else:                                               # sequence_end_code: the last one, only zeros behind it
@@ -1015,8 +1086,12 @@ def _main_plan(data, b_pictures=False, interlaced=False, extended=False, mb_tool
         if i + 1 == len(ev) and role != _END and ok:            # no sequence_end_code: the stream ends where a picture does
             prole = roles[prev] if prev is not None else None
             ok = prole in (_SEQEXT, _DISP) or (prole == _SLICE and ev[prev][1] == mbh)
+            if field_pictures:
+                ok = prole in (_SEQEXT, _DISP) or (prole == _SLICE and ev[prev][1] == rows)
         if not ok:
             bad.append(pos)
+    if waiting is not None:
+        bad.append(waiting["pos"])                              # a first field no picture follows
     if bad:
         raise Refused(min(bad), "the grammar of the start codes")
     return first, pictures, gops, repeats, ev, ends
@@ -1053,10 +1128,10 @@ def display_order(types):
     return out
 
 
-def decode_main(data, b_pictures=False, interlaced=False, extended=False, mb_tools=False):
+def decode_main(data, b_pictures=False, interlaced=False, extended=False, mb_tools=False, field_pictures=False):
     data = bytes(data)
     T, TM = tables(), _main_tables()
-    hdr, pictures, gops, repeats, ev, ends = _main_plan(data, b_pictures, interlaced, extended, mb_tools)
+    hdr, pictures, gops, repeats, ev, ends = _main_plan(data, b_pictures, interlaced, extended, mb_tools, field_pictures)
     out = Decoded()
     out.width, out.height, out.sequence, out.gops, out.repeated_headers, out.units = hdr["width"], hdr["height"], hdr, gops, repeats, len(ev)
     mbw, mbh = (out.width + 15) // 16, _main_mbh(hdr, interlaced)
@@ -1065,6 +1140,8 @@ def decode_main(data, b_pictures=False, interlaced=False, extended=False, mb_too
     WI, WN = hdr["intra_matrix"], hdr["non_intra_matrix"]
     ref = None
     before = None                                               # the anchor before the last one: a B picture's forward reference
+    held = None                                                 # field_pictures: the frame whose first field is decoded, and that field's type
+    out.fields = []                                             # field_pictures: every coded picture (out.pictures: one a frame)
     for pic in pictures:
         out.pictures.append(pic)
         if extended:
@@ -1075,6 +1152,12 @@ def decode_main(data, b_pictures=False, interlaced=False, extended=False, mb_too
         U = np.zeros((H // 2, W // 2), np.int64)
         V = np.zeros((H // 2, W // 2), np.int64)
         mbs, qcodes = [], []
+        fld = field_pictures and pic["picture_structure"] != 3
+        if field_pictures:
+            out.fields.append(pic)
+            if pic["second"]:                                   # the second field goes into its first field's frame
+                out.pictures.pop()
+                Y, U, V = held[0]
 
         def predict_into(col, row, mv, ref=ref):
             cmv = [int(mv[0] / 2), int(mv[1] / 2)]              # toward zero (7.6.3.7)
@@ -1331,6 +1414,160 @@ def decode_main(data, b_pictures=False, interlaced=False, extended=False, mb_too
                 record(intra=bool(intra), mc=bool(mc), mv=vec[0][0] if mc else (0, 0), cbp=cbp, qcode=qcode, motion_type=motion_type, dct_type=dct_type,
                        used=used, selects=tuple(tuple(x) for x in sel), vectors=tuple(tuple(x) for x in vec))
 
+        def fp_slice(br, row):
+            """a slice of a field picture (the section "Field pictures" above): the field is rows par, par + 2, ... of the frame's planes,
+            a reference field the rows of its parity of an anchor frame - or of this frame, for the second field of an anchor frame"""
+            par = pic["picture_structure"] - 1
+            ptype = pic["type"]
+            cur = tuple(p[par::2] for p in (Y, U, V))
+            fields_of = lambda frame: [None, None] if frame is None else [tuple(p[q::2] for p in frame) for q in (0, 1)]
+            if ptype == 3:
+                refs = (fields_of(before), fields_of(ref))
+            else:
+                refs = (fields_of(ref), [None, None])
+                if pic["second"]:                               # the other parity: the first field of this frame
+                    refs[0][1 - par] = tuple(p[(1 - par)::2] for p in (Y, U, V))
+            conceal = pic["concealment_motion_vectors"]
+            qcode = br.bits(5)
+            qcodes.append(qcode)
+            slice_extras(br)
+            dc_pred, col = [0, 0, 0], -1
+            PMV = [[[0, 0], [0, 0]], [[0, 0], [0, 0]]]          # PMV[r][s]
+            dirs = None                                         # the directions of the macroblock in front (None: intra, or none)
+            zero = [np.zeros(64, np.int64)] * 6
+
+            def part(field, col, mv, half):
+                """one prediction from one field: half None 16 x 16 (chroma 8 x 8), else the upper (0) or lower (1) 16 x 8 (chroma 8 x 4)"""
+                assert field is not None, "a select names a field that does not exist"
+                cmv = (int(mv[0] / 2), int(mv[1] / 2))          # toward zero (7.6.3.7)
+                h, y0 = (16, 0) if half is None else (8, 8 * half)
+                return (_predict_rect(field[0], 16 * col, 16 * row + y0, mv[0], mv[1], 16, h),
+                        _predict_rect(field[1], 8 * col, 8 * row + y0 // 2, cmv[0], cmv[1], 8, h // 2),
+                        _predict_rect(field[2], 8 * col, 8 * row + y0 // 2, cmv[0], cmv[1], 8, h // 2))
+
+            def mean(preds):
+                return preds[0] if len(preds) == 1 else tuple((a + c + 1) >> 1 for a, c in zip(*preds))
+
+            def whole(col, used, sel, vec):
+                """field-based: one vector a direction, 16 x 16 from the field its select names"""
+                return mean([part(refs[s][sel[s]], col, vec[s], None) for s in (0, 1) if used[s]])
+
+            def fstore(col, pred, res):
+                for b in range(6):
+                    r = res[b].reshape(8, 8)
+                    if b < 4:
+                        oy, ox = 8 * (b >> 1), 8 * (b & 1)
+                        cur[0][16 * row + oy:16 * row + oy + 8, 16 * col + ox:16 * col + ox + 8] = np.clip(pred[0][oy:oy + 8, ox:ox + 8] + r, 0, 255)
+                    else:
+                        cur[b - 3][8 * row:8 * row + 8, 8 * col:8 * col + 8] = np.clip(pred[b - 3] + r, 0, 255)
+
+            def record(**kw):
+                m = dict(intra=False, mc=False, skipped=False, mv=(0, 0), cbp=0, qcode=qcode, motion_type=1, dct_type=0,
+                         selects=((par, par), (par, par)), vectors=(((0, 0), (0, 0)), ((0, 0), (0, 0))))
+                m.update(kw)
+                mbs.append(m)
+
+            while more(br, col):
+                incr = 0
+                while True:                                     # macroblock_escape adds 33 (6.3.16)
+                    sym = TM["incr"](br)
+                    if sym != "ESC":
+                        break
+                    incr += 33
+                    assert col + incr < mbw, "an increment passes the row's end"
+                incr += sym
+                assert col + incr < mbw, "an increment passes the row's end"
+                if col < 0:                                     # the first increment places the slice: nothing is skipped in front of it
+                    col, incr = incr - 2, 1
+                    span[:] = [col + 1, col + 1]
+                for k in range(1, incr):                        # 7.6.6: field prediction from the field of the same parity
+                    assert ptype != 1, "no macroblock is skipped in an I picture"
+                    dc_pred = [0, 0, 0]
+                    if ptype == 2:                              # the zero vector; the predictors reset
+                        PMV = [[[0, 0], [0, 0]], [[0, 0], [0, 0]]]
+                        fstore(col + k, whole(col + k, (1, 0), (par, par), ((0, 0), (0, 0))), zero)
+                        record(skipped=True)
+                    else:                                       # the directions in front, the predictors as the vectors
+                        assert dirs is not None, "a skipped macroblock behind an intra macroblock"
+                        vecs = (tuple(PMV[0][0]), tuple(PMV[0][1]))
+                        fstore(col + k, whole(col + k, dirs, (par, par), vecs), zero)
+                        record(skipped=True, mc=bool(dirs[0]), mv=vecs[0] if dirs[0] else (0, 0), fwd=bool(dirs[0]), bwd=bool(dirs[1]))
+                col += incr
+                span[1:] = [col]
+                bwd = 0
+                if ptype == 3:
+                    quant, mc, bwd, pattern, intra = TM["type_b"](br)
+                else:
+                    quant, mc, pattern, intra = (TM["type_i"] if ptype == 1 else TM["type_p"])(br)
+                motion_type = 1                                 # macroblock_modes(): field_motion_type, no dct_type
+                if mc or bwd:
+                    motion_type = br.bits(2)
+                    assert motion_type in (1, 2) or (motion_type == 3 and ptype == 2), "field_motion_type 0 is reserved, 3 is dual prime"
+                if quant:
+                    qcode = br.bits(5)
+                    assert qcode != 0, "quantiser_scale_code 0 is forbidden"
+                preds = []                                      # the predictions to be formed: (field, vector, half)
+                sels, vecs = [[par, par], [par, par]], [[(0, 0), (0, 0)], [(0, 0), (0, 0)]]      # [s][r]
+                for s in (0, 1):
+                    if not (mc, bwd)[s]:
+                        continue
+                    fh, fv = pic["f_code"][2 * s:2 * s + 2]
+                    if motion_type == 1:                        # field-based: from PMV[0][s], PMV[1][s] follows
+                        sel = br.bits(1)
+                        vector(br, PMV[0][s], 0, fh)
+                        vector(br, PMV[0][s], 1, fv)
+                        PMV[1][s] = list(PMV[0][s])
+                        preds.append([(refs[s][sel], tuple(PMV[0][s]), None)])
+                        sels[s], vecs[s] = [sel, sel], [tuple(PMV[0][s])] * 2
+                    elif motion_type == 2:                      # 16 x 8: vector r from and into PMV[r][s]
+                        both = []
+                        for r in (0, 1):
+                            sel = br.bits(1)
+                            vector(br, PMV[r][s], 0, fh)
+                            vector(br, PMV[r][s], 1, fv)
+                            both.append((refs[s][sel], tuple(PMV[r][s]), r))
+                            sels[s][r], vecs[s][r] = sel, tuple(PMV[r][s])
+                        preds.append(both)
+                    else:                                       # dual prime: no select, a dmvector behind each component
+                        dmv = [0, 0]
+                        vector(br, PMV[0][0], 0, fh)
+                        dmv[0] = (1 - 2 * br.bits(1)) if br.bits(1) else 0
+                        vector(br, PMV[0][0], 1, fv)
+                        dmv[1] = (1 - 2 * br.bits(1)) if br.bits(1) else 0
+                        PMV[1][0] = list(PMV[0][0])
+                        vx, vy = PMV[0][0]
+                        near = lambda a: (a + (a > 0)) >> 1     # division by 2 to the nearest integer, halves away from zero
+                        other = (near(vx) + dmv[0], near(vy) + dmv[1] + (1 if par else -1))
+                        preds.append([(refs[0][par], (vx, vy), None)])
+                        preds.append([(refs[0][1 - par], other, None)])
+                        sels, vecs = [[par, par], [1 - par, 1 - par]], [[(vx, vy)] * 2, [other] * 2]
+                if intra and conceal:                           # a select and a vector: kept in the predictors, not used; then the marker bit
+                    br.bits(1)
+                    vector(br, PMV[0][0], 0, pic["f_code"][0])
+                    vector(br, PMV[0][0], 1, pic["f_code"][1])
+                    PMV[1][0] = list(PMV[0][0])
+                    assert br.bits(1) == 1, "marker_bit"
+                elif intra or (ptype == 2 and not mc):
+                    PMV = [[[0, 0], [0, 0]], [[0, 0], [0, 0]]]  # 7.6.3.4
+                cbp = 63 if intra else (T["cbp"](br) if pattern else 0)
+                if intra:
+                    pred = (np.full((16, 16), 128, np.int64), np.full((8, 8), 128, np.int64), np.full((8, 8), 128, np.int64))
+                    dirs = None
+                else:
+                    dc_pred = [0, 0, 0]                         # 7.2.1
+                    if not preds:                               # a P field's macroblock without a vector: the zero vector, the same parity
+                        preds = [[(refs[0][par], (0, 0), None)]]
+                    formed = []
+                    for group in preds:                         # a direction: one 16 x 16, or two 16 x 8 one above the other
+                        parts = [part(f, col, mv, half) for f, mv, half in group]
+                        formed.append(parts[0] if len(parts) == 1 else tuple(np.vstack((a, c)) for a, c in zip(*parts)))
+                    pred = mean(formed)
+                    dirs = (1, 0) if ptype == 2 else (mc, bwd)
+                res = read_blocks(br, intra, cbp, dc_pred, qcode)
+                fstore(col, pred, res)
+                record(intra=bool(intra), mc=bool(mc), mv=vecs[0][0] if mc else (0, 0), cbp=cbp, qcode=qcode, motion_type=motion_type,
+                       selects=tuple(tuple(x) for x in sels), vectors=tuple(tuple(x) for x in vecs), fwd=bool(mc), bwd=bool(bwd))
+
         front = []                                              # extended: [code, last column] of the slice in front
 
         def continuity(unit):
@@ -1352,6 +1589,11 @@ def decode_main(data, b_pictures=False, interlaced=False, extended=False, mb_too
                 del span[:]
             try:
                 br = _UnitBits(data, pos, ends[unit])
+                if fld:
+                    fp_slice(br, row)
+                    assert br.rest_is_zero(), "only zero stuffing may follow the row's last macroblock"
+                    continuity(unit)
+                    continue
                 if mb_tools or (interlaced and not pic["frame_pred_frame_dct"]):
                     il_slice(br, row)
                     assert br.rest_is_zero(), "only zero stuffing may follow the row's last macroblock"
@@ -1485,6 +1727,17 @@ def decode_main(data, b_pictures=False, interlaced=False, extended=False, mb_too
                 raise
             except Exception as e:
                 raise Refused(pos, "slice: %s" % e)
+        if field_pictures:                                      # a frame is done behind a frame picture or a second field; its type is its first picture's
+            out.mbs.append(mbs)
+            out.slice_qcodes.append(qcodes)
+            if fld and not pic["second"]:
+                held = ((Y, U, V), pic["type"])
+                continue
+            if (held[1] if fld else pic["type"]) != 3:
+                before, ref = ref, (Y, U, V)
+            out.frames.append(tuple(np.ascontiguousarray(p[:r, :c]).astype(np.uint8)
+                                    for p, r, c in zip((Y, U, V), (out.height, ch, ch), (out.width, cw, cw))))
+            continue
         if pic["type"] != 3:
             before, ref = ref, (Y, U, V)
         out.frames.append(tuple(np.ascontiguousarray(p[:r, :c]).astype(np.uint8)
@@ -1492,7 +1745,7 @@ def decode_main(data, b_pictures=False, interlaced=False, extended=False, mb_too
         out.mbs.append(mbs)
         out.slice_qcodes.append(qcodes)
     if b_pictures:
-        out.display = display_order([p["type"] for p in pictures])
+        out.display = display_order([p["type"] for p in (out.pictures if field_pictures else pictures)])
         coded = out.frames
         out.frames = [None] * len(coded)
         for p, d in enumerate(out.display):

@@ -1033,7 +1033,7 @@ int m2v_mux_scan_tile(void);
  *             (row 2k + 1); chroma blocks are frame blocks; inverse quantisation, mismatch control and the IDCT are untouched
  *   skipped   frame prediction: a P picture's with the zero vector; a B picture's in the directions of the macroblock in front with
  *             PMV[0][s] read as frame vectors - behind a field-based macroblock twice its first field vector's vertical component
- * Still M2V_DEC_SYNTAX with the option on: field pictures (picture_structure 1 and 2); dual prime and concealment vectors (option
+ * Still M2V_DEC_SYNTAX with the option on: field pictures (picture_structure 1 and 2: option "decode_field_pictures" below); dual prime and concealment vectors (option
  * "decode_mb_tools" below reads them); and everything else the main syntax refuses.
  *
  * Option "decode_extended" (m2v_set_option), per handle: 0 (the default) - everything above, bit for bit, launch for launch and
@@ -1067,8 +1067,8 @@ int m2v_mux_scan_tile(void);
  *             stuffing.  A loaded matrix is in force from that picture on in CODED order, each matrix on its own; any sequence header,
  *             repeated ones included, puts both back to the sequence's
  *   composite  composite_display_flag 1: the 20 bits behind it are read and not acted on
- * Out of scope, the follow-ups: m2v_decode_streams_main_device keeps its two flags (any other bit stays M2V_E_PARAM); field pictures,
- * leading B pictures and D pictures stay refused, dual prime, concealment vectors and Table B-15 too without option "decode_mb_tools",
+ * Out of scope, the follow-ups: m2v_decode_streams_main_device keeps its two flags (any other bit stays M2V_E_PARAM); field pictures
+ * (without option "decode_field_pictures"), leading B pictures and D pictures stay refused, dual prime, concealment vectors and Table B-15 too without option "decode_mb_tools",
  * and everything else the main syntax refuses stays refused where it is refused without the option.
  *
  * Option "decode_mb_tools" (m2v_set_option), per handle: 0 (the default) - everything above, bit for bit, launch for launch and
@@ -1097,8 +1097,46 @@ int m2v_mux_scan_tile(void);
  *             its bottom field by (vx, vy) and its top field by B; each a 16 x 8 field prediction with half-sample interpolation,
  *             each vector halved toward zero on its own for chroma.  All four reads must lie inside their field, or the slice is
  *             refused.  A skipped macroblock behind a dual-prime one is the zero vector, as ever
- * Still M2V_DEC_SYNTAX with every option on: field pictures, leading B pictures, D pictures.  m2v_decode_streams_main_device takes
- * neither "decode_extended" nor "decode_mb_tools"; the batch entry that does is m2v_decode_streams_main_ex_device, below.
+ * Still M2V_DEC_SYNTAX: leading B pictures, D pictures - field pictures too without option "decode_field_pictures", below.
+ * m2v_decode_streams_main_device takes neither "decode_extended" nor "decode_mb_tools"; the batch entry that does is
+ * m2v_decode_streams_main_ex_device, below.
+ *
+ * Option "decode_field_pictures" (m2v_set_option), per handle: 0 (the default) - everything above, bit for bit, launch for launch and
+ * refusal for refusal; 1 - field pictures are read too.  Any other value is M2V_E_PARAM.  With 1, "decode_syntax" must be
+ * M2V_SYNTAX_MAIN, `mode` M2V_DEC_ISO and "decode_interlaced", "decode_extended" and "decode_mb_tools" all 1 (that grammar is a
+ * superset - no stream is lost - and field pictures need its selects, dual prime and concealment vectors): otherwise
+ * m2v_decode_device returns M2V_E_PARAM, writes nothing and m2v_last_error names the option.  "decode_b_pictures" may be 0 or 1.  The
+ * definition is decoder.decode(stream, quirks=False, syntax="main", b_pictures=..., interlaced=True, extended=True, mb_tools=True,
+ * field_pictures=True).  Every stream accepted with the option off decodes with it on to the same bytes and the same record.  Added
+ * (6.1.1.4, 6.3.10, 6.3.17, 7.6.2 - 7.6.3.6, 7.6.6, 7.6.7):
+ *   extension  picture_structure 1 (top field) and 2 (bottom field) where progressive_sequence, progressive_frame,
+ *             frame_pred_frame_dct, top_field_first and repeat_first_field are all 0; value 0 is refused; all at the coding extension
+ *   pairs      a coded frame is one frame picture or two field pictures that follow each other in coded order: opposite parity in
+ *             either order, the same temporal_reference, the same picture_coding_type or a P field behind an I field.  A picture
+ *             behind a first field that is not such a partner - the same parity, a frame picture, another type, another
+ *             temporal_reference - is refused at its picture header; a sequence header, a GOP header or sequence_end_code between the
+ *             two fields at its start code (the second field's header, extensions, user_data and the transparent units may stand
+ *             there); a first field no picture follows at its own picture header.  Frame pictures and field pairs may be mixed
+ *   geometry   a field has (height + 31) / 32 macroblock rows, its slice codes run to that, continuity is judged per field; row r,
+ *             line k of the field of parity p is frame line 32 r + 2 k + p; the frame is cropped to the header's size as ever
+ *   modes      field_motion_type (2 bits) where the macroblock has a vector: 1 field-based (one vector a direction), 2 16 x 8 (two),
+ *             3 dual prime (a P field only), 0 refused; no dct_type.  motion_vertical_field_select in front of every vector of the
+ *             first two kinds.  No component is halved going in or doubled coming out.  Field-based: predicted from PMV[0][s],
+ *             PMV[1][s] = PMV[0][s] afterwards; 16 x 8: vector r from and into PMV[r][s]; dual prime: no select, dmvector behind each
+ *             component, PMV[1][0] = PMV[0][0].  A concealment vector carries a select (read, not used) and its marker bit
+ *   prediction the field a select names is the most recently decoded anchor field of that parity: the two fields of the anchor
+ *             frame(s) - but for the second field of an anchor frame the field of the other parity is the first field of its own
+ *             frame.  A select that names a field that does not exist (the field's own parity in the second field of the stream's first
+ *             frame) refuses the slice.  Field-based 16 x 16 (chroma 8 x 8); 16 x 8: the upper half by vector 0, the lower by vector
+ *             1 (chroma 8 x 4 each); dual prime: (a + b + 1) >> 1 of the same parity by (vx, vy) and the other parity by
+ *             (h(vx) + d0, h(vy) + d1 + e), e = -1 in a top field, + 1 in a bottom field.  Every read inside its field.  A P field's
+ *             macroblock without a vector and its skipped macroblock: the zero vector, its own parity, the predictors reset; a B
+ *             field's skipped macroblock: the directions in front, the predictors as vectors, field-based, its own parity
+ *   record     one output frame a coded frame, both fields woven; a frame's type is its first field's (I + P is an I frame);
+ *             pictures, gops, chains and repeated_headers count FRAMES, out_bytes = pictures * frame_bytes, "decode_batch" counts
+ *             frames (a chunk's edge never parts a pair).  A B pair needs two anchor frames in front of it
+ * Out of scope, the follow-ups: m2v_decode_streams_main_ex_device keeps its four flags (bit 16 stays M2V_E_PARAM); leading B pictures
+ * and D pictures stay refused; repeat_first_field and display timing.
  */
 enum { M2V_DEC_ISO = 0, M2V_DEC_MODULE = 1 };
 enum { M2V_SYNTAX_MODULE = 0, M2V_SYNTAX_MAIN = 1 };                            /* option "decode_syntax" */
