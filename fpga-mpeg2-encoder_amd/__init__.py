@@ -129,6 +129,9 @@ DECODE_STAT_DTYPE = np.dtype([("es_bytes", "<u8"), ("out_bytes", "<u8"), ("frame
                               ("status", "<i4"), ("reserved", "<u4", (3,))])
 # m2v_decode_stream_stat: one stream's record of m2v_decode_streams_device, 88 bytes (Mpeg2Encoder.decode_streams_report)
 DECODE_STREAM_STAT_DTYPE = np.dtype([("es_offset", "<u8"), ("out_offset", "<u8"), ("rec", DECODE_STAT_DTYPE)])
+# m2v_decode_join: the join record of the last decode_device, 32 bytes (Mpeg2Encoder.decode_join_report)
+DECODE_JOIN_DTYPE = np.dtype([("join_offset", "<u8"), ("tail_offset", "<u8"), ("dropped_leading", "<u4"), ("dropped_trailing", "<u4"), ("reserved", "<u4", (2,))])
+DEC_JOINS = {"head": 1, "tail": 2, "both": 3}                    # M2V_JOIN_*: option "decode_join"
 DEC_MODES = {"iso": 0, "module": 1}                              # M2V_DEC_*
 DEC_SYNTAXES = {"module": 0, "main": 1}                          # M2V_SYNTAX_*: option "decode_syntax"
 DECS_B_PICTURES, DECS_INTERLACED = 1, 2                          # M2V_DECS_*: the flags of m2v_decode_streams_main_device
@@ -445,6 +448,7 @@ def lib(debug=False):
             L.m2v_demux_scan_tile.argtypes = []
             L.m2v_decode_device.argtypes = [vp, vp, sz, vp, sz, ci, ci, vp]
             L.m2v_decode_report.argtypes = [vp, vp]
+            L.m2v_decode_join_report.argtypes = [vp, vp]
             L.m2v_decode_scan_tile.argtypes = []
             L.m2v_decode_streams_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, ci, ci, vp]
             L.m2v_decode_streams_report.argtypes = [vp, vp, sz]
@@ -737,7 +741,7 @@ class Mpeg2Encoder:
         self._chk(self._L.m2v_set_option(self._h, name.encode(), int(value)), "m2v_set_option(%s)" % name)
         if name == "stats":
             self._set[name] = bool(value)
-        if name in ("gop_bytes_max", "scene_cut", "decode_syntax", "decode_b_pictures", "decode_interlaced", "decode_extended", "decode_mb_tools", "decode_field_pictures"):
+        if name in ("gop_bytes_max", "scene_cut", "decode_syntax", "decode_b_pictures", "decode_interlaced", "decode_extended", "decode_mb_tools", "decode_field_pictures", "decode_join"):
             self._set[name] = int(value)
 
     def _set_list(self, key, values, ctype, what):
@@ -918,7 +922,15 @@ class Mpeg2Encoder:
         self._chk(self._L.m2v_decode_report(self._h, out.ctypes.data), "m2v_decode_report")
         return out[0]
 
-    def decode_device(self, es, layout="i420", mode="iso", out=None, container=None, stream=None, syntax="module", b_pictures=False, interlaced=False, extended=False, mb_tools=False, field_pictures=False):
+    def decode_join_report(self):
+        """m2v_decode_join_report: the join record of the last decode_device on this handle, a numpy record of DECODE_JOIN_DTYPE - the
+        join point, the offset the tail was cut at, the frames dropped in front and behind; 0, es_bytes, 0, 0 with option "decode_join"
+        off and for a refused stream"""
+        out = np.zeros(1, DECODE_JOIN_DTYPE)
+        self._chk(self._L.m2v_decode_join_report(self._h, out.ctypes.data), "m2v_decode_join_report")
+        return out[0]
+
+    def decode_device(self, es, layout="i420", mode="iso", out=None, container=None, stream=None, syntax="module", b_pictures=False, interlaced=False, extended=False, mb_tools=False, field_pictures=False, join=0):
         """m2v_decode_device: the MPEG-2 elementary stream in the one-dimensional uint8 device tensor `es` (at any byte alignment) decoded
         on the device to 4:2:0 frames in `layout`; mode "iso" is decoder.decode(quirks=False), "module" the module's own loop
         (quirks=True).  Returns (frames [pictures, frame_bytes] uint8 on es's device, record).  out: a contiguous uint8 tensor to write into
@@ -963,8 +975,24 @@ class Mpeg2Encoder:
         "decode_field_pictures" for this call, put back afterwards as mb_tools= is - pictures with picture_structure 1 / 2 are read too,
         two field pictures woven into one frame, the record counted in frames (decoder.decode(..., quirks=False, syntax="main",
         interlaced=True, extended=True, mb_tools=True, field_pictures=True) is the definition).  False, the default, decodes without the
-        option whatever set_option("decode_field_pictures") left on the handle."""
+        option whatever set_option("decode_field_pictures") left on the handle.
+
+        join = 0 .. 3, "head" (1), "tail" (2) or "both" (3) (other than 0 with field_pictures=True and what it needs; ValueError
+        otherwise): option "decode_join" for this call, put back afterwards as field_pictures= is - a stream cut from a running
+        broadcast: "head" reads from the first sequence header on and drops the B pictures whose anchors are not there, "tail" leaves
+        out the frame the stream breaks off in (decoder.decode(..., field_pictures=True, join=...) is the definition;
+        decode_join_report answers what was left out).  With container= the stream is what the demultiplexer extracts, and the join
+        record's offsets count in it.  0, the default, decodes without the option whatever set_option("decode_join") left on the
+        handle."""
         import torch
+        if isinstance(join, str):
+            if join not in DEC_JOINS:
+                raise ValueError("decode_device: join is 0 .. 3 or one of %s" % ", ".join(DEC_JOINS))
+            join = DEC_JOINS[join]
+        if join not in (0, 1, 2, 3):
+            raise ValueError("decode_device: join is 0 .. 3 or one of %s" % ", ".join(DEC_JOINS))
+        if join and not field_pictures:
+            raise ValueError("decode_device: join goes with field_pictures=True")
         if syntax not in DEC_SYNTAXES:
             raise ValueError("decode_device: syntax is one of %s" % ", ".join(DEC_SYNTAXES))
         if b_pictures and syntax != "main":
@@ -977,12 +1005,20 @@ class Mpeg2Encoder:
             raise ValueError("decode_device: mb_tools goes with extended=True")
         if field_pictures and not (interlaced and extended and mb_tools):
             raise ValueError("decode_device: field_pictures goes with interlaced=True, extended=True and mb_tools=True")
+        held_j = self._set.get("decode_join", 0)                           # what set_option("decode_join") left on the handle
+        if int(join) != held_j:
+            self.set_option("decode_join", int(join))
+            try:
+                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced,
+                                          extended=extended, mb_tools=mb_tools, field_pictures=field_pictures, join=join)
+            finally:
+                self.set_option("decode_join", held_j)
         held_f = self._set.get("decode_field_pictures", 0)                 # what set_option("decode_field_pictures") left on the handle
         if int(bool(field_pictures)) != held_f:
             self.set_option("decode_field_pictures", int(bool(field_pictures)))
             try:
                 return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced,
-                                          extended=extended, mb_tools=mb_tools, field_pictures=field_pictures)
+                                          extended=extended, mb_tools=mb_tools, field_pictures=field_pictures, join=join)
             finally:
                 self.set_option("decode_field_pictures", held_f)
         held_t = self._set.get("decode_mb_tools", 0)                       # what set_option("decode_mb_tools") left on the handle
@@ -990,7 +1026,7 @@ class Mpeg2Encoder:
             self.set_option("decode_mb_tools", int(bool(mb_tools)))
             try:
                 return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced,
-                                          extended=extended, mb_tools=mb_tools, field_pictures=field_pictures)
+                                          extended=extended, mb_tools=mb_tools, field_pictures=field_pictures, join=join)
             finally:
                 self.set_option("decode_mb_tools", held_t)
         held_x = self._set.get("decode_extended", 0)                       # what set_option("decode_extended") left on the handle
@@ -998,28 +1034,28 @@ class Mpeg2Encoder:
             self.set_option("decode_extended", int(bool(extended)))
             try:
                 return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced,
-                                          extended=extended, mb_tools=mb_tools, field_pictures=field_pictures)
+                                          extended=extended, mb_tools=mb_tools, field_pictures=field_pictures, join=join)
             finally:
                 self.set_option("decode_extended", held_x)
         held_i = self._set.get("decode_interlaced", 0)                     # what set_option("decode_interlaced") left on the handle
         if int(bool(interlaced)) != held_i:
             self.set_option("decode_interlaced", int(bool(interlaced)))
             try:
-                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended, mb_tools=mb_tools, field_pictures=field_pictures)
+                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended, mb_tools=mb_tools, field_pictures=field_pictures, join=join)
             finally:
                 self.set_option("decode_interlaced", held_i)
         held_b = self._set.get("decode_b_pictures", 0)                     # what set_option("decode_b_pictures") left on the handle
         if int(bool(b_pictures)) != held_b:
             self.set_option("decode_b_pictures", int(bool(b_pictures)))
             try:
-                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended, mb_tools=mb_tools, field_pictures=field_pictures)
+                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended, mb_tools=mb_tools, field_pictures=field_pictures, join=join)
             finally:
                 self.set_option("decode_b_pictures", held_b)
         held = self._set.get("decode_syntax", DEC_SYNTAXES["module"])      # what set_option("decode_syntax") left on the handle
         if DEC_SYNTAXES[syntax] != held:
             self.set_option("decode_syntax", DEC_SYNTAXES[syntax])
             try:
-                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended, mb_tools=mb_tools, field_pictures=field_pictures)
+                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended, mb_tools=mb_tools, field_pictures=field_pictures, join=join)
             finally:
                 self.set_option("decode_syntax", held)
         if container is not None:

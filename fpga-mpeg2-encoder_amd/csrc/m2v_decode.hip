@@ -43,9 +43,12 @@
 // m2v_decode_t.hip (dec_t_plan, dec_t_chunks).
 // "decode_field_pictures" = 1 on top of "decode_interlaced", "decode_extended" and "decode_mb_tools": picture_structure 1 / 2, two field
 // pictures a frame; from the same two places to m2v_decode_f.hip (dec_f_plan, dec_f_chunks), whose chunks are whole frames.
+// "decode_join" = 1 .. 3 on top of all of them: a stream that begins in front of its first sequence header, whose first B pictures lack
+// their anchors, or that breaks off inside a picture; the plan is m2v_decode_j.hip's (dec_j_plan), the chunks stay dec_f_chunks.
 #include "m2v_decode_state.hpp"
 
 static_assert(sizeof(m2v_decode_stat) == 72, "the record of include/m2v_mi355x.h is 72 bytes");
+static_assert(sizeof(m2v_decode_join) == 32, "the join record of include/m2v_mi355x.h is 32 bytes");
 static_assert(sizeof(dec::MbRec) == 16, "a macroblock's record is 16 bytes");
 static_assert(M2V_DEC_ISO == dec::kIso && M2V_DEC_MODULE == dec::kModule && M2V_DEC_SYNTAX == dec::kSyntax && M2V_DEC_OVERFLOW == dec::kOverflow,
               "m2v_decode_kernels.hpp repeats the values of include/m2v_mi355x.h");
@@ -384,6 +387,7 @@ static int decode_impl(m2v_enc *e, void *argp)
     m2v_decode_stat &R = e->dec_rec;
     R = m2v_decode_stat{};
     R.es_bytes = n;
+    e->dec_join = m2v_decode_join{0, n, 0, 0, {0, 0}};
     if (n < 4) { R.status = M2V_DEC_SYNTAX; return M2V_OK; }          // not one start code
     e->d_dec_st.recorded = e->d_dec_ev.recorded = e->d_dec_pics.recorded = e->d_dec_mb.recorded = e->d_dec_dc.recorded = false;     // (no recorded graph references them)
     e->d_dec_lv.recorded = e->d_dec_buf.recorded = e->d_dec_tiles.recorded = e->d_dec_list.recorded = e->d_dec_main.recorded = false;
@@ -393,6 +397,7 @@ static int decode_impl(m2v_enc *e, void *argp)
     const bool extended = e->decode_extended != 0;                     // m2v_decode_x.hip: the same two places, with the other two either way
     const bool mb_tools = e->decode_mb_tools != 0;                     // m2v_decode_t.hip: in the places of dec_x_plan and dec_x_chunks
     const bool field_pictures = e->decode_field_pictures != 0;         // m2v_decode_f.hip: in the places of dec_t_plan and dec_t_chunks
+    const int join = e->decode_join;                                   // m2v_decode_j.hip: its plan in the place of dec_f_plan, dec_f_chunks behind it
     e->d_dec_x.recorded = false;
     const size_t ntiles = (n + dec::kScanTile - 1) / dec::kScanTile;
     if (ntiles > 0x7FFFFFFFu) { e->set_err("m2v_decode_device: the stream is longer than 2^31 scan tiles"); return M2V_E_PARAM; }
@@ -421,7 +426,12 @@ static int decode_impl(m2v_enc *e, void *argp)
         HIPCHK(hipGetLastError());
         k_dec_scan<true><<<gx, kDecThreads, 0, s>>>(a->es, n, d_st, e->d_dec_tiles.p, e->d_dec_ev.p);
         HIPCHK(hipGetLastError());
-        if (field_pictures) {
+        if (join) {
+            e->d_dec_main.ensure(kDecMainMatrices + pic_cap * sizeof(DecFPic));
+            dec_j_plan(s, a->es, n, e->d_dec_ev.p, d_st, (DecPic *)e->d_dec_pics.p, (uint32_t)pic_cap, e->h_dec + rec_off + 128, (unsigned long long)a->cap, a->dst ? 0 : 1,
+                       (m2v_decode_stat *)(e->h_dec + rec_off), e->d_dec_main.p, b_pictures ? 1 : 0, join, (uint32_t *)(e->h_dec + rec_off + kDecPlanWords),
+                       (uint32_t *)(e->h_dec + rec_off + 128 + ((pic_cap + 3) & ~(size_t)3) + 4 * pic_cap));
+        } else if (field_pictures) {
             e->d_dec_main.ensure(kDecMainMatrices + pic_cap * sizeof(DecFPic));
             dec_f_plan(s, a->es, n, e->d_dec_ev.p, d_st, (DecPic *)e->d_dec_pics.p, (uint32_t)pic_cap, e->h_dec + rec_off + 128, (unsigned long long)a->cap, a->dst ? 0 : 1,
                        (m2v_decode_stat *)(e->h_dec + rec_off), e->d_dec_main.p, b_pictures ? 1 : 0, (uint32_t *)(e->h_dec + rec_off + 96),
@@ -455,6 +465,10 @@ static int decode_impl(m2v_enc *e, void *argp)
     }
     R = *h_rec;
     if (R.status == dec::kEvents) R.status = M2V_DEC_SYNTAX;
+    if (join && R.status != M2V_DEC_SYNTAX) {                          // the plan's join record, behind the macroblock rows and the coded pictures
+        const uint32_t *j = (const uint32_t *)(e->h_dec + rec_off + kDecPlanWords) + kDecJoinWord;
+        e->dec_join = m2v_decode_join{(uint64_t)j[1] << 32 | j[0], (uint64_t)j[3] << 32 | j[2], j[4], j[5], {0, 0}};
+    }
     if (R.status != M2V_DEC_OK || !a->dst || !R.pictures) return M2V_OK;
     // the chunks
     const uint8_t *types = e->h_dec + rec_off + 128;
@@ -467,6 +481,7 @@ static int decode_impl(m2v_enc *e, void *argp)
         auto *h_list = (uint32_t *)(e->h_dec + rec_off + 128 + ((pic_cap + 3) & ~(size_t)3));
         dec_f_chunks(e, s, a->es, n, a->dst, a->layout, R, rows, B, types, ncp, h_list, h_list + pic_cap, (m2v_decode_stat *)(e->h_dec + rec_off));
         R = *h_rec;
+        if (R.status == M2V_DEC_SYNTAX) e->dec_join = m2v_decode_join{0, n, 0, 0, {0, 0}};      // a slice refused the stream
         return M2V_OK;
     }
     if (extended) {                                                    // m2v_decode_x.hip; the macroblock rows and the slices in front of every picture are the plan's
@@ -561,6 +576,12 @@ int m2v_decode_device(m2v_enc *e, const void *d_es, size_t es_bytes, void *d_dst
     if (!layout420_ok(layout)) { e->set_err("m2v_decode_device: unknown layout %d", layout); return M2V_E_PARAM; }
     if (mode != M2V_DEC_ISO && mode != M2V_DEC_MODULE) { e->set_err("m2v_decode_device: unknown mode %d", mode); return M2V_E_PARAM; }
     if (!d_es && es_bytes) { e->set_err("m2v_decode_device: d_es is NULL"); return M2V_E_PARAM; }
+    if (e->decode_join && (e->decode_syntax != M2V_SYNTAX_MAIN || mode != M2V_DEC_ISO || !e->decode_interlaced || !e->decode_extended || !e->decode_mb_tools ||
+                           !e->decode_field_pictures)) {
+        e->set_err("m2v_decode_device: \"decode_join\" = 1 .. 3 needs \"decode_syntax\" = main, the mode M2V_DEC_ISO and \"decode_interlaced\", "
+                   "\"decode_extended\", \"decode_mb_tools\" and \"decode_field_pictures\" = 1");
+        return M2V_E_PARAM;
+    }
     if (e->decode_field_pictures && (e->decode_syntax != M2V_SYNTAX_MAIN || mode != M2V_DEC_ISO || !e->decode_interlaced || !e->decode_extended || !e->decode_mb_tools)) {
         e->set_err("m2v_decode_device: \"decode_field_pictures\" = 1 needs \"decode_syntax\" = main, the mode M2V_DEC_ISO and \"decode_interlaced\", "
                    "\"decode_extended\" and \"decode_mb_tools\" = 1");
@@ -595,6 +616,13 @@ int m2v_decode_report(m2v_enc *e, m2v_decode_stat *out)
 {
     if (!e || !out) return M2V_E_PARAM;
     *out = e->dec_rec;
+    return M2V_OK;
+}
+
+int m2v_decode_join_report(m2v_enc *e, m2v_decode_join *out)
+{
+    if (!e || !out) return M2V_E_PARAM;
+    *out = e->dec_join;
     return M2V_OK;
 }
 

@@ -2724,5 +2724,163 @@ M2V_HD inline int32_t fp_predict(const uint8_t *const (&ref)[4], int stride, int
     return m.dirs == (kFwd | kBwd) ? bp_mean(a, c) : (m.dirs & kFwd) ? a : c;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Streams cut from a broadcast (option "decode_join", bits kJoinHead and kJoinTail, on top of all of "decode_interlaced",
+// "decode_extended", "decode_mb_tools" and "decode_field_pictures", "decode_b_pictures" either way; decoder.decode(..., join=) is the
+// definition).  The functions above keep their text; these stand beside them:
+//   window      the stream is read as its bytes [J, T): J the first sequence_header_code (head; else 0), T the start of the frame the
+//               stream breaks off in (tail; else its end).  Everything above runs over the window's events with T as the stream's
+//               length - a plan hands them the event list from J's event on, and adds that event's index to what it stores.
+//   pairs       JPair is the pairing of fp_feed alone, over EVERY picture from J on, with the first picture of the frame a picture
+//               belongs to: a range of events is summed for either state in front of it (j_pair_range) and the sums are joined in
+//               order (j_pair_join), which also finds F - the last picture start code that begins a frame; one whose header does not
+//               read begins one unless a first field waits, and leaves the pairing alone - and E2, the picture that begins the second anchor frame behind J.
+//               No picture start code lies behind the window's last slice, so a picture of the window pairs as it does in the whole.
+//   tail        T is the first group_start_code or picture_start_code behind the last slice in front of F (j_last_slice, j_first_head)
+//   drop        a frame whose first picture is a B picture in front of E2 is dropped (j_dropped), its second field with it: its
+//               units are judged by fp_event as any, its partner by fp_partner_ok (j_place), and it is absent from the sums
+//               (j_keep_range), the tables, the slices counted in front of a picture and the record.  Dropped frames are whole, so
+//               what is kept pairs among itself; only a range's first picture may be the partner of a kept field in front of it.
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kJoinHead = 1u, kJoinTail = 2u;
+constexpr uint32_t kJInherit = 1u;                               // JSum::out.open: the field that waited in front still waits
+
+// the first sequence_header_code of events [a, b) (kNoEvent: none)
+M2V_HD inline uint32_t j_first_seq(const uint64_t *ev, uint32_t a, uint32_t b)
+{
+    for (uint32_t i = a; i < b; ++i) if (ev_code(ev[i]) == 0xB3u) return i;
+    return kNoEvent;
+}
+
+// il_first for a header group at J: nothing in front of it is judged
+M2V_HD inline uint64_t j_first(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, MainPlan &P)
+{
+    if (!nev) return 0;
+    MainSeq &q = P.seq;
+    const uint64_t bad = main_group(es, n, ev, nev, 0, q.h, q.display, [&](int m, uint32_t i, uint32_t v) { (m ? q.wn : q.wi)[i & 63u] = (uint8_t)v; });
+    if (bad != kNone) return bad;
+    const SeqHdr &h = P.seq.h;
+    if (!h.width || !h.height || h.width > (uint32_t)kMaxSize || h.height > (uint32_t)kMaxSize) return ev_pos(ev[0]);
+    P.mbw = (h.width + 15u) / 16u; P.mbh = il_mbh(h.height, h.progressive);
+    return kNone;
+}
+
+// open: fp_open_pack of the first field that waits (0: none); ff, fb: the event of the first picture of the frame the last picture
+// belongs to (kNoEvent: none so far) and whether it is a B picture
+struct JPair { uint32_t open, ff, fb; };
+// what a range of events leaves, the state behind it; the last picture start code that begins a frame; the first two that begin an anchor frame
+struct JSum { JPair out; uint32_t lastf, an1, an2; };
+// the join: the state in front of the next range; anchor frames so far (2: two or more); E2; F
+struct JScan { JPair in; uint32_t na, e2, f; };
+
+M2V_HD inline JScan j_scan_none() { return JScan{JPair{0, kNoEvent, 0}, 0, kNoEvent, kNoEvent}; }
+
+// the picture at event i into the pairing: true = it begins a frame
+M2V_HD inline bool j_pair_feed(JPair &w, uint32_t i, uint32_t ps, uint32_t type, uint32_t tref)
+{
+    if (w.open) { w.open = 0; return false; }
+    w.ff = i; w.fb = type == 3u;
+    if (fp_is_field(ps)) w.open = fp_open_pack(ps, type, tref);
+    return true;
+}
+
+// events [a, b) summed twice: A with nothing waiting in front, B with a first field waiting
+M2V_HD inline void j_pair_range(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, uint32_t a, uint32_t b, bool b_pictures, JSum &A, JSum &B)
+{
+    A = B = JSum{JPair{0, kNoEvent, 0}, kNoEvent, kNoEvent, kNoEvent};
+    B.out.open = kJInherit;
+    for (uint32_t i = a; i < b; ++i) {
+        if (ev_code(ev[i]) != 0x00u) continue;
+        uint32_t type, tref, ps;
+        if (!fp_is_picture(es, n, ev, nev, i, b_pictures, type, tref, ps)) {      // it begins a frame unless a field waits for it
+            if (!A.out.open) A.lastf = i;
+            if (!B.out.open) B.lastf = i;
+            continue;
+        }
+        for (int k = 0; k < 2; ++k) {
+            JSum &s = k ? B : A;
+            if (!j_pair_feed(s.out, i, ps, type, tref)) continue;
+            s.lastf = i;
+            if (type == 3u) continue;
+            if (s.an1 == kNoEvent) s.an1 = i;
+            else if (s.an2 == kNoEvent) s.an2 = i;
+        }
+    }
+}
+
+M2V_HD inline void j_pair_join(JScan &t, const JSum &A, const JSum &B)
+{
+    const JSum &r = t.in.open ? B : A;
+    if (r.lastf != kNoEvent) t.f = r.lastf;
+    if (t.na < 2u && r.an1 != kNoEvent) {
+        if (t.na == 1u) { t.e2 = r.an1; t.na = 2u; }
+        else if (r.an2 != kNoEvent) { t.e2 = r.an2; t.na = 2u; }
+        else t.na = 1u;
+    }
+    if (r.out.ff != kNoEvent) { t.in.ff = r.out.ff; t.in.fb = r.out.fb; }
+    if (r.out.open != kJInherit) t.in.open = r.out.open;
+}
+
+// the last slice of events [a, b), and the first group_start_code or picture_start_code (kNoEvent: none)
+M2V_HD inline uint32_t j_last_slice(const uint64_t *ev, uint32_t a, uint32_t b)
+{
+    for (uint32_t i = b; i > a; --i) { const uint32_t c = ev_code(ev[i - 1u]); if (c >= 1u && c <= 0xAFu) return i - 1u; }
+    return kNoEvent;
+}
+
+M2V_HD inline uint32_t j_first_head(const uint64_t *ev, uint32_t a, uint32_t b)
+{
+    for (uint32_t i = a; i < b; ++i) { const uint32_t c = ev_code(ev[i]); if (c == 0x00u || c == 0xB8u) return i; }
+    return kNoEvent;
+}
+
+// one past the last byte of [0, t) that is not zero, for the one rule that asks: a sequence_end_code as the window's last unit
+M2V_HD inline uint64_t j_last_nz(const uint8_t *es, uint64_t t, const uint64_t *ev, uint32_t nev)
+{
+    if (!nev || ev_code(ev[nev - 1u]) != 0xB7u) return t;
+    uint64_t k = t;
+    for (const uint64_t lo = ev_pos(ev[nev - 1u]) + 4u; k > lo && !es[k - 1u]; --k) {}
+    return k;
+}
+
+// whether the frame the pairing stands in is dropped: its first picture is a B picture in front of the second anchor frame
+M2V_HD inline bool j_dropped(const JPair &w, uint32_t e2, bool drop) { return drop && w.ff != kNoEvent && w.fb && w.ff < e2; }
+
+// the picture at event i behind the pairing w: whether it is dropped; bad: the second field of a dropped frame that is no legal partner
+M2V_HD inline bool j_place(JPair &w, uint32_t i, uint32_t ps, uint32_t type, uint32_t tref, uint32_t e2, bool drop, bool &bad)
+{
+    const uint32_t open = w.open;
+    const bool begins = j_pair_feed(w, i, ps, type, tref);
+    const bool gone = j_dropped(w, e2, drop);
+    bad = gone && !begins && !fp_partner_ok(open, ps, type, tref);
+    return gone;
+}
+
+// the kept pictures of events [a, b) behind the pairing w: their sums r (the first of them left out where it is the partner of a
+// field in front of the range, as fp_range's B), m of them, ns slices of theirs, and the frames dropped
+struct JKeep { FpRange r; uint32_t m, ns, dropped; };
+
+M2V_HD inline void j_keep_range(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, uint32_t a, uint32_t b, bool b_pictures, JPair w, uint32_t e2, bool drop,
+                                JKeep &k)
+{
+    k.r = fp_range_none();
+    k.m = k.ns = k.dropped = 0;
+    bool front = w.open != 0u, gone = j_dropped(w, e2, drop);
+    for (uint32_t i = a; i < b; ++i) {
+        const uint32_t code = ev_code(ev[i]);
+        if (code != 0x00u) { k.ns += code <= 0xAFu && !gone; continue; }
+        uint32_t type, tref, ps;
+        if (!fp_is_picture(es, n, ev, nev, i, b_pictures, type, tref, ps)) continue;
+        const bool begins = j_pair_feed(w, i, ps, type, tref);
+        gone = j_dropped(w, e2, drop);
+        if (gone) k.dropped += begins;
+        else {
+            if (begins || !front) (void)fp_feed(k.r, k.m, ps, type, tref);
+            ++k.m;
+        }
+        front = false;
+    }
+}
+
 }  // namespace dec
 }  // namespace m2v

@@ -83,4 +83,14 @@ void dec_f_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long 
 void dec_f_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_t *dst, int layout, const m2v_decode_stat &R, size_t mbh, size_t B,
                   const uint8_t *types, size_t ncp, uint32_t *h_list, const uint32_t *h_sl, m2v_decode_stat *h_rec);
 
+// Streams cut from a broadcast (option "decode_join" on top of "decode_field_pictures" and what it stands on; m2v_decode_j.hip): the
+// plan alone, in dec_f_plan's place, with its tables and for dec_f_chunks.  The pictures it drops are in no table, the kept pictures'
+// events keep their indices into the event list.  It leaves the join record behind the coded pictures: h_mbh[2 .. 7] = join_offset,
+// tail_offset (low word first), dropped_leading, dropped_trailing
+constexpr size_t kDecPlanWords = 96;               // the plan's words (h_mbh) in the pinned block, behind the record; the types begin at 128
+constexpr uint32_t kDecJoinWord = 2;               // h_mbh[kDecJoinWord .. kDecJoinWord + 6): the join record
+static_assert(kDecPlanWords + 4 * (kDecJoinWord + 6) <= 128, "the join record ends where the types begin");
+void dec_j_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long long *ev, DecState *st, DecPic *pics, uint32_t pic_cap, uint8_t *h_types,
+                unsigned long long cap, int probe, m2v_decode_stat *h_rec, uint8_t *d_main, int b_pictures, int join, uint32_t *h_mbh, uint32_t *h_sl);
+
 }  // namespace m2v

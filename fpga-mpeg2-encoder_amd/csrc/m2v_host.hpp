@@ -33,12 +33,12 @@
 //   m2v_decode.hip    m2v_decode_device: an elementary stream in HBM back to 4:2:0 frames.  Its kernels touch no device global and nothing of
 //                     m2v_kernels.hpp, so they live in their own unit with their launches (m2v_decode_kernels.hpp holds the arithmetic, for
 //                     the device and the host alike)
-//   m2v_decode_main.hip, m2v_decode_b.hip, m2v_decode_i.hip, m2v_decode_x.hip, m2v_decode_t.hip, m2v_decode_f.hip   m2v_decode_device's other syntaxes,
+//   m2v_decode_main.hip, m2v_decode_b.hip, m2v_decode_i.hip, m2v_decode_x.hip, m2v_decode_t.hip, m2v_decode_f.hip, m2v_decode_j.hip   m2v_decode_device's other syntaxes,
 //                     each in kernels of its own: the main syntax (option "decode_syntax"), B pictures on top of it (option
 //                     "decode_b_pictures"), interlaced frame pictures (option "decode_interlaced"), several slices a row, slice header
 //                     extras and quant_matrix_extension (option "decode_extended"), and Table B-15, concealment motion vectors and dual
-//                     prime (option "decode_mb_tools"), and field pictures, two a frame (option "decode_field_pictures");
-//                     m2v_decode_state.hpp is what the seven share
+//                     prime (option "decode_mb_tools"), field pictures, two a frame (option "decode_field_pictures"), and the plan for streams
+//                     cut from a broadcast (option "decode_join"); m2v_decode_state.hpp is what the eight share
 //   m2v_decode_streams.hip   m2v_decode_streams_device: a batch of elementary streams of any sizes in one call - the same arithmetic over a
 //                     table of streams, in kernels of its own (m2v_decode_streams.hpp lays the batch out, for the host build too)
 //   m2v_decode_streams_main.hip   m2v_decode_streams_main_device: the same for main-syntax streams, B pictures and interlaced frame pictures
@@ -425,6 +425,8 @@ struct m2v_enc {
     DevBuf<uint8_t> d_dec_x;              // its matrix table (128 bytes a picture) and the spans of a chunk's slices
     int decode_mb_tools = 0;              // option "decode_mb_tools": Table B-15, concealment vectors, dual prime on top of "decode_extended" (m2v_decode_t.hip)
     int decode_field_pictures = 0;        // option "decode_field_pictures": picture_structure 1 / 2, two fields a frame, on top of the three above it (m2v_decode_f.hip)
+    int decode_join = 0;                  // option "decode_join": M2V_JOIN_HEAD | M2V_JOIN_TAIL on top of the four above it (m2v_decode_j.hip)
+    m2v_decode_join dec_join{};           // the last call's join record (m2v_decode_join_report)
     size_t decode_batch = 0;              // option "decode_batch": pictures per chunk (0: as many as keep the levels within 256 MiB, 256 at most)
     m2v_decode_stat dec_rec{};            // the last call's record (m2v_decode_report)
     // several streams per call (m2v_decode_streams.hip): the work buffers above serve it too; its own are the streams' table, the

@@ -6,7 +6,7 @@
 //          [-fps N/D] [-aspect 1:1|4:3|16:9|2.21:1] [-bitrate B] [-vbv K] [-colour bt601|bt709|P,T,M] [-repeat-headers]
 //          [-scale SWxSH [-filter triangle|area]]
 //          in.yuv W H out.m2v  [in2.yuv W2 H2 out2.m2v ...]
-//   m2v_tb -decode in.m2v out.yuv [-reconfmt i420|yv12|nv12|nv21] [-mode iso|module] [-syntax module|main [-bpictures] [-interlaced] [-extended [-mbtools [-fieldpictures]]]] [-container ts|ps [-pid N]] [-d device]
+//   m2v_tb -decode in.m2v out.yuv [-reconfmt i420|yv12|nv12|nv21] [-mode iso|module] [-syntax module|main [-bpictures] [-interlaced] [-extended [-mbtools [-fieldpictures [-join head|tail|both]]]]] [-container ts|ps [-pid N]] [-d device]
 //   m2v_tb -demux ts|ps in.ts out.m2v [-pid N] [-d device]
 //
 // -demux: the video elementary stream of a transport or program stream, demultiplexed on the device (m2v_demux_device), into out.m2v, with
@@ -21,6 +21,7 @@
 // -extended with it: option "decode_extended" = 1, several slices a row, slice header extras, quant_matrix_extension, composite_display_flag 1.
 // -mbtools with -extended: option "decode_mb_tools" = 1, Table B-15, concealment motion vectors and dual prime.
 // -fieldpictures with -interlaced -extended -mbtools: option "decode_field_pictures" = 1, picture_structure 1 / 2 too, two field pictures a frame.
+// -join head|tail|both with -fieldpictures: option "decode_join" = 1 / 2 / 3, a stream cut from a broadcast; prints the join record.
 // -interlaced with it: option "decode_interlaced" = 1, frame pictures with field prediction and field DCT too, one frame per picture.
 // A stream the decoder refuses ends with its status and the offset of the unit in error, exit status 1.
 // -pad: W, H are any size from 49 up; the files hold frames of that size in the chosen format, which are padded to whole macroblocks on
@@ -151,7 +152,7 @@ static int demux_main(int argc, char **argv)
 static int decode_main(int argc, char **argv)
 {
     const char *in = argv[2], *out = argv[3];
-    int layout = M2V_420_I420, mode = M2V_DEC_ISO, dev = 0, container = 0, pid = -1, syntax = M2V_SYNTAX_MODULE, bpictures = 0, interlaced = 0, extended = 0, mbtools = 0, fieldpictures = 0;
+    int layout = M2V_420_I420, mode = M2V_DEC_ISO, dev = 0, container = 0, pid = -1, syntax = M2V_SYNTAX_MODULE, bpictures = 0, interlaced = 0, extended = 0, mbtools = 0, fieldpictures = 0, join = 0;
     bool bad = false;
     for (int i = 4; i < argc; ++i) {
         const char *v = i + 1 < argc ? argv[i + 1] : "";
@@ -176,6 +177,10 @@ static int decode_main(int argc, char **argv)
             mbtools = 1;
         } else if (!strcmp(argv[i], "-fieldpictures")) {
             fieldpictures = 1;
+        } else if (!strcmp(argv[i], "-join")) {
+            join = !strcmp(v, "head") ? M2V_JOIN_HEAD : !strcmp(v, "tail") ? M2V_JOIN_TAIL : !strcmp(v, "both") ? (M2V_JOIN_HEAD | M2V_JOIN_TAIL) : -1;
+            bad = bad || join < 0;
+            ++i;
         } else if (!strcmp(argv[i], "-d")) {
             dev = atoi(v);
             ++i;
@@ -191,7 +196,7 @@ static int decode_main(int argc, char **argv)
         }
     }
     if (bad || (pid >= 0 && !container)) {
-        fprintf(stderr, "m2v_tb -decode in.m2v out.yuv [-reconfmt i420|yv12|nv12|nv21] [-mode iso|module] [-syntax module|main [-bpictures] [-interlaced] [-extended [-mbtools [-fieldpictures]]]] [-container ts|ps [-pid N]] [-d device]\n");
+        fprintf(stderr, "m2v_tb -decode in.m2v out.yuv [-reconfmt i420|yv12|nv12|nv21] [-mode iso|module] [-syntax module|main [-bpictures] [-interlaced] [-extended [-mbtools [-fieldpictures [-join head|tail|both]]]]] [-container ts|ps [-pid N]] [-d device]\n");
         return 2;
     }
     std::vector<uint8_t> es;
@@ -217,7 +222,8 @@ static int decode_main(int argc, char **argv)
         // (said)
     } else if (m2v_set_option(e, "decode_syntax", syntax) != M2V_OK || m2v_set_option(e, "decode_b_pictures", bpictures) != M2V_OK ||
                m2v_set_option(e, "decode_interlaced", interlaced) != M2V_OK || m2v_set_option(e, "decode_extended", extended) != M2V_OK ||
-               m2v_set_option(e, "decode_mb_tools", mbtools) != M2V_OK || m2v_set_option(e, "decode_field_pictures", fieldpictures) != M2V_OK) {
+               m2v_set_option(e, "decode_mb_tools", mbtools) != M2V_OK || m2v_set_option(e, "decode_field_pictures", fieldpictures) != M2V_OK ||
+               m2v_set_option(e, "decode_join", join) != M2V_OK) {
         fprintf(stderr, "m2v_set_option: %s\n", m2v_last_error(e));
     } else if (m2v_decode_device(e, d_es, es_bytes, nullptr, 0, layout, mode, nullptr) != M2V_OK || m2v_decode_report(e, &r) != M2V_OK) {
         fprintf(stderr, "m2v_decode_device: %s\n", m2v_last_error(e));
@@ -235,6 +241,10 @@ static int decode_main(int argc, char **argv)
             fprintf(stderr, "m2v_tb: cannot write %s\n", out);
         } else {
             printf("%s: %u pictures of %u x %u, %u GOPs -> %s (%llu bytes)\n", in, r.pictures, r.width, r.height, r.gops, out, (unsigned long long)r.out_bytes);
+            m2v_decode_join j;
+            if (join && m2v_decode_join_report(e, &j) == M2V_OK)
+                printf("%s: joined at byte %llu, read up to byte %llu of %llu; %u frames dropped in front, %u behind\n", in, (unsigned long long)j.join_offset,
+                       (unsigned long long)j.tail_offset, (unsigned long long)r.es_bytes, j.dropped_leading, j.dropped_trailing);
             rc = 0;
         }
         if (o) fclose(o);

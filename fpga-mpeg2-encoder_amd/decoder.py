@@ -301,7 +301,7 @@ def sequence_headers(data):
     return _sequence_headers(BitReader(data))
 
 
-def decode(data, quirks=True, syntax="module", b_pictures=False, interlaced=False, extended=False, mb_tools=False, field_pictures=False):
+def decode(data, quirks=True, syntax="module", b_pictures=False, interlaced=False, extended=False, mb_tools=False, field_pictures=False, join=0):
     """syntax="module" (the default): the subset this encoder emits, as the head of this file says.  syntax="main": Main-Profile
     streams of progressive frame pictures, I and P, 4:2:0, from any encoder (decode_main below); it needs quirks=False, and a
     refusal is a Refused exception that names the unit.  b_pictures=True (syntax="main" only): B pictures too, and the frames in
@@ -314,7 +314,13 @@ def decode(data, quirks=True, syntax="module", b_pictures=False, interlaced=Fals
     intra_vlc_format 1, concealment motion vectors, and dual prime in a P picture with frame_pred_frame_dct 0 (the section "The
     macroblock tools" below); with False the function is what it was for every input.  field_pictures=True (with interlaced, extended
     and mb_tools all True, b_pictures either way): pictures with picture_structure 1 / 2 too, two of them woven into one frame (the
-    section "Field pictures" below); with False the function is what it was for every input."""
+    section "Field pictures" below); with False the function is what it was for every input.  join=1 .. 3 (JOIN_HEAD | JOIN_TAIL, with
+    the four keywords in front of it all True, b_pictures either way): a stream cut from a running broadcast (the section "Streams
+    cut from a broadcast" below); with 0 the function is what it was for every input."""
+    if join not in (0, 1, 2, 3):
+        raise ValueError("join is 0 or a mask of JOIN_HEAD (1) and JOIN_TAIL (2)")
+    if join and not (syntax == "main" and interlaced and extended and mb_tools and field_pictures):
+        raise ValueError("join goes with syntax=\"main\", interlaced=True, extended=True, mb_tools=True and field_pictures=True")
     if field_pictures and not (syntax == "main" and interlaced and extended and mb_tools):
         raise ValueError("field_pictures goes with syntax=\"main\", interlaced=True, extended=True and mb_tools=True")
     if mb_tools and not extended:
@@ -327,6 +333,8 @@ def decode(data, quirks=True, syntax="module", b_pictures=False, interlaced=Fals
         raise ValueError("interlaced goes with syntax=\"main\"")
     if syntax == "main":
         assert not quirks, "the module's quirks have no meaning outside its own syntax"
+        if join:
+            return decode_join(data, b_pictures, join)
         return decode_main(data, b_pictures, interlaced, extended, mb_tools, field_pictures)
     assert syntax == "module", syntax
     T = tables()
@@ -719,9 +727,36 @@ def psnr(a, b):
 #   output      one frame a coded frame, both fields woven; a frame's type is its first field's (I + P is an I frame); display order,
 #               Decoded.pictures (the frame picture's or the first field's fields), gops and repeated_headers count frames;
 #               Decoded.fields, .mbs and .slice_qcodes are per coded picture.  A B frame needs two anchor frames in front of it
-# Still refused: leading B pictures, D pictures, dual prime in a B picture.  Every stream accepted with field_pictures=False and the
-# other three on decodes to the same frames with True.
+# Still refused: leading B pictures (without join, below), D pictures, dual prime in a B picture.  Every stream accepted with
+# field_pictures=False and the other three on decodes to the same frames with True.
+#
+# Streams cut from a broadcast (decode(..., syntax="main", interlaced=True, extended=True, mb_tools=True, field_pictures=True,
+# join=JOIN_HEAD | JOIN_TAIL), b_pictures either way; option "decode_join" of the device decoder).  Such a stream begins wherever the
+# recording began, its GOPs are open, and it breaks off inside a picture.  Nothing above changes; decode_join reads the bytes [J, T) of
+# the stream exactly as a stream of their own, and every offset it reports counts from the first byte of the input:
+#   head (1)    J is the offset of the first sequence_header_code (00 00 01 B3) among the start codes; what lies in front of it is
+#               not read any further and not judged.  Without one: Refused(0).  The header group at J is "the first sequence header"
+#               of every rule above, and a wrong one is refused at its own unit - no later one is looked for.
+#               Leading B pictures (b_pictures only): a B picture that begins a frame while fewer than two anchor frames have begun
+#               since J is dropped where it was refused, a B field pair as a pair (the picture behind a first field is its partner).
+#               A dropped picture's units are judged by the grammar as a kept picture's are - header, coding extension, the rules of a
+#               pair, slice codes, one quant_matrix_extension at most - and a matrix it loads holds from that picture on; its slices
+#               are not walked.  It is in no list of the result and has no frame, no display index: those are the kept frames' alone.
+#               A P picture with no I frame in front of it since J stays refused
+#   tail (2)    where the last unit that is not skipped is sequence_end_code nothing is dropped.  Otherwise F is the last picture start
+#               code that begins a frame - paired as the plan pairs: the picture behind a waiting first field is its partner, whatever
+#               it is; a picture start code whose header does not read begins a frame unless a first field waits, and leaves the pairing alone - and T the offset
+#               of the first group_start_code or picture_start_code behind the last slice in front of F (behind the unit at J where
+#               there is no such slice).  The units from T on are not judged; one frame counts as dropped.  A frame is known by its picture
+#               start code alone: while the bytes behind the last whole frame hold none yet (a GOP header alone), that frame goes.  The rule is blunt: a
+#               complete stream without sequence_end_code loses its last frame, which is why the tail is a bit of its own
+# Decoded.join_offset = J (0 without bit 1), .tail_offset = T (len(data) where nothing was dropped behind), .dropped_leading and
+# .dropped_trailing count frames.  A stream in which no frame is left is a stream without pictures.  Every stream accepted with join=0
+# decodes to the same frames with join=1, and with join=2 or 3 where it ends with sequence_end_code.
 # ---------------------------------------------------------------------------------------------------------------
+JOIN_HEAD, JOIN_TAIL = 1, 2
+
+
 class Refused(Exception):
     def __init__(self, offset, why=""):
         Exception.__init__(self, "unit at byte %d: %s" % (offset, why))
@@ -922,8 +957,9 @@ def _main_mbh(hdr, interlaced=False):
     return (hdr["height"] + 15) // 16
 
 
-def _main_plan(data, b_pictures=False, interlaced=False, extended=False, mb_tools=False, field_pictures=False):
-    """the grammar over the start codes -> (sequence fields, pictures, gops, repeated headers, number of start codes)"""
+def _main_plan(data, b_pictures=False, interlaced=False, extended=False, mb_tools=False, field_pictures=False, dropped=None):
+    """the grammar over the start codes -> (sequence fields, pictures, gops, repeated headers, number of start codes).  dropped (a
+    list, with field_pictures): the leading B frames are dropped, not refused; their first pictures are appended to it"""
     n = len(data)
     ev = start_codes(data)
     if not ev or any(data[:ev[0][0]]):
@@ -1032,12 +1068,15 @@ def _main_plan(data, b_pictures=False, interlaced=False, extended=False, mb_tool
                     pic["backward_f_code"] = br.bits(3)
                 assert br.bits(1) == 0                          # extra_bit_picture
                 assert br.rest_is_zero()
-                have_i = have_i or pic["type"] == 1
-                if not have_i:
+                if dropped is not None and field_pictures:      # a leading B frame: its first picture, and the partner of such a one
+                    pic["gone"] = waiting["gone"] if waiting is not None else pic["type"] == 3 and frame_anchors < 2
+                gone = pic.get("gone", False)
+                have_i = have_i or (pic["type"] == 1 and not gone)
+                if not have_i and not gone:
                     bad.append(pos)                             # a P picture without a reference
-                if pic["type"] == 3 and anchors < 2:
+                if pic["type"] == 3 and anchors < 2 and not gone:
                     bad.append(pos)                             # a B picture without two anchors in front of it
-                anchors += pic["type"] != 3
+                anchors += pic["type"] != 3 and not gone
                 pic["matrices"] = mats
                 pictures.append(pic)
                 if field_pictures:                              # the pairs; the two rules above once more, counted in frames
@@ -1051,15 +1090,17 @@ def _main_plan(data, b_pictures=False, interlaced=False, extended=False, mb_tool
                         waiting = None
                     else:
                         pic.update(frame=frames, second=False)
-                        frames += 1
-                        frame_i = frame_i or pic["type"] == 1
+                        frames += not gone
+                        frame_i = frame_i or (pic["type"] == 1 and not gone)
                         if ps in (1, 2):
-                            waiting = dict(ps=ps, pos=pos, frame=pic["frame"], type=pic["type"], temporal_reference=pic["temporal_reference"])
-                    if not frame_i:
+                            waiting = dict(ps=ps, pos=pos, frame=pic["frame"], type=pic["type"], temporal_reference=pic["temporal_reference"], gone=gone)
+                    if gone:
+                        pass                                    # judged as a pair, and no more
+                    elif not frame_i:
                         bad.append(pos)                         # a P picture without a reference
-                    if pic["type"] == 3 and frame_anchors < 2:
+                    if pic["type"] == 3 and frame_anchors < 2 and not gone:
                         bad.append(pos)                         # a B picture without two anchor frames in front of it
-                    frame_anchors += pic["type"] != 3 and not pic["second"]
+                    frame_anchors += pic["type"] != 3 and not pic["second"] and not gone
             elif role == _PICEXT:
                 ok = i > 0 and roles[i - 1] == _PIC
                 ptype = (data[ev[i - 1][0] + 5] >> 3) & 7 if ok and ev[i - 1][0] + 5 < n else 0
@@ -1094,6 +1135,9 @@ def _main_plan(data, b_pictures=False, interlaced=False, extended=False, mb_tool
         bad.append(waiting["pos"])                              # a first field no picture follows
     if bad:
         raise Refused(min(bad), "the grammar of the start codes")
+    if dropped is not None:
+        dropped.extend(p for p in pictures if p.get("gone") and not p["second"])
+        pictures = [p for p in pictures if not p.get("gone")]
     return first, pictures, gops, repeats, ev, ends
 
 
@@ -1128,10 +1172,79 @@ def display_order(types):
     return out
 
 
-def decode_main(data, b_pictures=False, interlaced=False, extended=False, mb_tools=False, field_pictures=False):
+def _picture_reads(data, pos, end, b_pictures):
+    """whether the picture header of the unit at pos reads, as _main_plan judges it"""
+    try:
+        br = _UnitBits(data, pos, end)
+        br.bits(10)
+        ptype = br.bits(3)
+        br.bits(16)
+        assert ptype in ((1, 2, 3) if b_pictures else (1, 2))
+        for _ in range({1: 0, 2: 1, 3: 2}[ptype]):
+            assert br.bits(1) == 0
+            br.bits(3)
+        assert br.bits(1) == 0
+        return br.rest_is_zero()
+    except Exception:
+        return False
+
+
+def join_window(data, join, b_pictures=False):
+    """the window of a stream cut from a broadcast (the section "Streams cut from a broadcast") -> (J, T, frames dropped behind)"""
+    data = bytes(data)
+    n = len(data)
+    ev = start_codes(data)
+    j = 0                                                       # the unit at J
+    if join & JOIN_HEAD:
+        j = next((k for k, (_, code) in enumerate(ev) if code == 0xB3), None)
+        if j is None:
+            raise Refused(0, "no sequence header")
+    J = ev[j][0] if join & JOIN_HEAD else 0
+    if not join & JOIN_TAIL or not ev:
+        return J, n, 0
+    roles = [_main_role(data, p, c, True) for p, c in ev]
+    ends = [p for p, _ in ev[1:]] + [n]
+    significant = [k for k in range(j, len(ev)) if roles[k] not in (_USER, _SKIPPED_EXT, _BAD, _QUANT)]
+    if significant and roles[significant[-1]] == _END:
+        return J, n, 0
+    F, waiting = None, False
+    for k in range(j, len(ev)):
+        if roles[k] != _PIC:
+            continue
+        if not _picture_reads(data, ev[k][0], ends[k], b_pictures):
+            if not waiting:
+                F = k                                           # it begins a frame, and leaves the pairing alone
+            continue
+        if waiting:
+            waiting = False
+            continue
+        F = k
+        waiting = k + 1 < len(ev) and roles[k + 1] == _PICEXT and ev[k + 1][0] + 6 < n and data[ev[k + 1][0] + 6] & 3 in (1, 2)
+    if F is None:
+        return J, n, 0
+    s = max([k for k in range(j, F) if roles[k] == _SLICE], default=j)
+    t = next((k for k in range(s + 1, F + 1) if roles[k] in (_GOP, _PIC)), F)      # (F is the unit at J itself: nothing is left, Refused(0))
+    return J, ev[t][0], 1
+
+
+def decode_join(data, b_pictures=False, join=JOIN_HEAD | JOIN_TAIL):
+    """decode(..., join=): the bytes [J, T) as a stream of their own, its leading B frames dropped with JOIN_HEAD; offsets count from
+    the first byte of data"""
+    data = bytes(data)
+    J, T, trailing = join_window(data, join, b_pictures)
+    dropped = [] if join & JOIN_HEAD else None
+    try:
+        out = decode_main(data[J:T], b_pictures, True, True, True, True, dropped)
+    except Refused as r:
+        raise Refused(r.offset + J, "in the window [%d, %d): %s" % (J, T, r))
+    out.join_offset, out.tail_offset, out.dropped_leading, out.dropped_trailing = J, T, len(dropped or ()), trailing
+    return out
+
+
+def decode_main(data, b_pictures=False, interlaced=False, extended=False, mb_tools=False, field_pictures=False, dropped=None):
     data = bytes(data)
     T, TM = tables(), _main_tables()
-    hdr, pictures, gops, repeats, ev, ends = _main_plan(data, b_pictures, interlaced, extended, mb_tools, field_pictures)
+    hdr, pictures, gops, repeats, ev, ends = _main_plan(data, b_pictures, interlaced, extended, mb_tools, field_pictures, dropped)
     out = Decoded()
     out.width, out.height, out.sequence, out.gops, out.repeated_headers, out.units = hdr["width"], hdr["height"], hdr, gops, repeats, len(ev)
     mbw, mbh = (out.width + 15) // 16, _main_mbh(hdr, interlaced)

@@ -1136,7 +1136,47 @@ int m2v_mux_scan_tile(void);
  *             pictures, gops, chains and repeated_headers count FRAMES, out_bytes = pictures * frame_bytes, "decode_batch" counts
  *             frames (a chunk's edge never parts a pair).  A B pair needs two anchor frames in front of it
  * Out of scope, the follow-ups: m2v_decode_streams_main_ex_device keeps its four flags (bit 16 stays M2V_E_PARAM); leading B pictures
- * and D pictures stay refused; repeat_first_field and display timing.
+ * and D pictures stay refused (leading B pictures: option "decode_join", below); repeat_first_field and display timing.
+ *
+ * Option "decode_join" (m2v_set_option), per handle: a mask of M2V_JOIN_HEAD (1) and M2V_JOIN_TAIL (2), 0 .. 3; any other value is
+ * M2V_E_PARAM.  0 (the default) - everything above, bit for bit, launch for launch and refusal for refusal.  For a stream cut from a
+ * running broadcast: it begins wherever the recording began, its first B pictures refer to an anchor that is not there, and it breaks
+ * off inside a picture.  With a value other than 0, "decode_syntax" must be M2V_SYNTAX_MAIN, `mode` M2V_DEC_ISO and
+ * "decode_interlaced", "decode_extended", "decode_mb_tools" and "decode_field_pictures" all 1 (the superset once more: one plan learns
+ * this, not six): otherwise m2v_decode_device returns M2V_E_PARAM, writes nothing and m2v_last_error names the option.
+ * "decode_b_pictures" may be 0 or 1.  The batch entries neither read nor change the option.  The definition is
+ * decoder.decode(stream, quirks=False, syntax="main", b_pictures=..., interlaced=True, extended=True, mb_tools=True,
+ * field_pictures=True, join=1 .. 3).  Every stream accepted with the option off decodes with bit 1 on to the same bytes and the same
+ * record; with bit 2 on that holds for the streams that end with sequence_end_code - a complete stream without one loses its last
+ * frame (below), which is why the tail is a bit of its own: a file a tool cut at a GOP wants bit 1 alone.
+ *   head (1)   J is the offset of the first sequence_header_code the start-code scan finds.  Bytes and start codes in front of J are
+ *             not read any further and not judged; without one the stream is refused at offset 0.  The header group at J is "the
+ *             first sequence header" of every rule above - its size rules, the macroblock rows, what repeated headers must equal -
+ *             and a wrong one is refused at its own unit: no later one is looked for.  err_offset stays relative to the first byte of
+ *             the input, es_bytes is the whole input.
+ *             Leading B pictures (with "decode_b_pictures" 1; with 0 a B picture is refused at its header as ever): a B picture that
+ *             begins a frame while fewer than two anchor FRAMES have begun since J is dropped where it was refused, a B field pair
+ *             as a pair.  A dropped picture's units are judged by the grammar exactly as a kept picture's - header, coding
+ *             extension, the rules of a pair, slice codes, one quant_matrix_extension at most -, and a matrix it loads holds from that
+ *             picture on; its slices are not walked (no slice refusal, no continuity verdict).  It has no frame index, no display
+ *             index and no room in the output and is not counted in `pictures`: display indices are those of the kept frames.  A P
+ *             picture with no I frame in front of it since J stays refused at its header.
+ *   tail (2)   where the last significant unit is sequence_end_code nothing is dropped.  Otherwise F is the last picture start code
+ *             that begins a frame - pairs as above: the picture behind a waiting first field is its partner, whatever it is; a picture
+ *             start code whose header does not read begins a frame unless a first field waits -, and T the offset of the first group_start_code or
+ *             picture_start_code behind the last slice in front of F (behind the first unit read where there is no such slice).  The
+ *             stream is read as its bytes [J, T) (J = 0 without bit 1), exactly as a stream that ends at T; the units from T on are
+ *             not judged.  One frame counts as dropped.  A frame is known by its picture start code alone: while the bytes behind the
+ *             last whole frame hold none yet - fewer than four bytes of it, or a sequence or GOP header alone - F is that last whole
+ *             frame, and it goes.  The rule is blunt on purpose: the last picture of a recording is cut at an
+ *             arbitrary byte, and a cut inside its last row could only be found by the slice walk, after the layout is fixed.
+ *   A stream in which no frame is left is a stream without pictures: M2V_DEC_OK, pictures 0.
+ * m2v_decode_join_report describes the same call as m2v_decode_report: join_offset = J, tail_offset = T (es_bytes where nothing was
+ * dropped behind), the dropped FRAMES in front and behind (dropped_trailing is 0 or 1).  It answers 0, es_bytes, 0, 0 for a call with
+ * the option off and for a refused stream.  A caller who records in segments keeps the bytes [tail_offset, es_bytes) for the front of
+ * the next segment.  m2v_decode_stat is what it was, `reserved` 0.
+ * Out of scope: the batch entries; resynchronising behind damage in the middle of a stream; a sequence header that changes
+ * mid-stream; D pictures; repeat_first_field and display timing; the module syntax.
  */
 enum { M2V_DEC_ISO = 0, M2V_DEC_MODULE = 1 };
 enum { M2V_SYNTAX_MODULE = 0, M2V_SYNTAX_MAIN = 1 };                            /* option "decode_syntax" */
@@ -1146,6 +1186,9 @@ typedef struct { uint64_t es_bytes, out_bytes, frame_bytes, err_offset;
                  int32_t status; uint32_t reserved[3]; } m2v_decode_stat;      /* 72 bytes */
 int m2v_decode_device(m2v_enc *e, const void *d_es, size_t es_bytes, void *d_dst, size_t cap, int layout, int mode, void *hip_stream);
 int m2v_decode_report(m2v_enc *e, m2v_decode_stat *out);
+enum { M2V_JOIN_HEAD = 1, M2V_JOIN_TAIL = 2 };                                  /* option "decode_join" */
+typedef struct { uint64_t join_offset, tail_offset; uint32_t dropped_leading, dropped_trailing, reserved[2]; } m2v_decode_join;   /* 32 bytes */
+int m2v_decode_join_report(m2v_enc *e, m2v_decode_join *out);
 int m2v_decode_scan_tile(void);
 
 /*
