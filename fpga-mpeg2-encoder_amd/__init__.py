@@ -51,6 +51,7 @@ EXPORTS = [
     "m2v_set_source_size", "m2v_scale_taps",
     "m2v_demux_bound", "m2v_demux_device", "m2v_demux_report", "m2v_demux_scan_tile",
     "m2v_decode_streams_device", "m2v_decode_streams_report", "m2v_decode_streams_main_device", "m2v_decode_streams_main_ex_device",
+    "m2v_deinterlace_device", "m2v_deinterlace_bound", "m2v_deinterlace_tile",
 ]
 
 # the 4:2:0 entry points (kept apart: tests/test_abi.py matches EXPORTS against names of letters and underscores only)
@@ -455,6 +456,10 @@ def lib(debug=False):
             L.m2v_scale_taps.argtypes = [ci, ci, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_uint16)]
             L.m2v_decode_streams_main_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, ci, ctypes.c_uint, vp]
             L.m2v_decode_streams_main_ex_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, ci, ctypes.c_uint, vp]
+            L.m2v_deinterlace_device.argtypes = [vp, vp, sz, ci, ci, ci, ci, ci, ci, vp, sz, vp]
+            L.m2v_deinterlace_bound.restype = ctypes.c_ulonglong
+            L.m2v_deinterlace_bound.argtypes = [ci, ci, sz, ci]
+            L.m2v_deinterlace_tile.argtypes = [ctypes.POINTER(ci), ctypes.POINTER(ci)]
         except AttributeError:
             # an OLDER build handed in through M2V_LIB for a same-box A/B (tools/ab.sh) may lack the newer entry points; the library of
             # this tree must have every one of them (tests/test_abi.py)
@@ -661,6 +666,88 @@ def scale_frames(frames, sw, sh, w, h, kind, filter="triangle"):
         o = (o + (1 << 19)) >> 20
         assert o.min() >= 0 and o.max() <= 255
         out.append(o.astype(np.uint8).reshape(n, -1))
+    return np.ascontiguousarray(np.concatenate(out, axis=1))
+
+
+# ---- woven frames to progressive frames (m2v_deinterlace_device, include/m2v_mi355x.h) ----
+DEINT_MODES = {"line": 0, "adaptive": 1, "blend": 2}      # M2V_DEINT_LINE / ADAPTIVE / BLEND
+DEINT_RATES = {"frame": 0, "field": 1}                    # M2V_DEINT_FRAME_RATE / FIELD_RATE
+DEINT_ORDERS = {"tff": 0, "bff": 1}                       # M2V_DEINT_TFF / BFF
+DEINT_MAX_SIZE = 16384
+
+
+def _deint_code(table, what, value):
+    code = table.get(value, value) if isinstance(value, str) else value
+    if isinstance(code, bool) or code not in table.values():
+        raise ValueError("unknown %s %r" % (what, value))
+    return int(code)
+
+
+def deinterlace_bound(w, h, nframes, rate="frame"):
+    """m2v_deinterlace_bound: the bytes a deinterlace_device of nframes w x h frames writes; 0 for illegal arguments"""
+    return int(lib().m2v_deinterlace_bound(int(w), int(h), int(nframes), DEINT_RATES.get(rate, rate) if isinstance(rate, str) else int(rate)))
+
+
+def deinterlace_tile():
+    """m2v_deinterlace_tile: (bytes of a row, rows) after which the device deinterlacer hands over to another group of lanes"""
+    c, r = ctypes.c_int(0), ctypes.c_int(0)
+    lib().m2v_deinterlace_tile(ctypes.byref(c), ctypes.byref(r))
+    return int(c.value), int(r.value)
+
+
+def deinterlace_frames(frames, w, h, layout="i420", mode="adaptive", rate="frame", order="tff"):
+    """woven w x h 4:2:0 frames of `layout` -> [n or 2 n, bytes] progressive frames of the same size and layout, as the header defines
+    them: every plane alone and bytewise, row r of any plane in the field of parity r & 1; the fields of the call one sequence in time,
+    F[k] in frame k >> 1 with parity order ^ (k & 1), an absent field replaced by the nearest of its parity; the rows of the output
+    field's parity kept, the others sp = (c + e + 1) >> 1 of the kept rows beside them ("line"), sp clamped to d +- m around the mean
+    of the neighbouring fields by the motion found ("adaptive"), or every row (up + 2 s + down + 2) >> 2 ("blend", frame rate only).
+    The frames a deinterlace_device returns, by definition (include/m2v_mi355x.h).  numpy, host side: a reference, not a fast path."""
+    m, fr, o = _deint_code(DEINT_MODES, "mode", mode), _deint_code(DEINT_RATES, "rate", rate), _deint_code(DEINT_ORDERS, "order", order)
+    name = layout if isinstance(layout, str) else {v: k for k, v in LAYOUTS_420.items()}.get(int(layout))
+    if name not in LAYOUTS_420:
+        raise ValueError("unknown layout %r" % (layout,))
+    if m == 2 and fr == 1:
+        raise ValueError("deinterlace_frames: \"blend\" knows no fields, so it has no field rate")
+    if not (1 <= w <= DEINT_MAX_SIZE and 2 <= h <= DEINT_MAX_SIZE):
+        raise ValueError("deinterlace_frames: %d x %d" % (w, h))
+    f = np.ascontiguousarray(frames, np.uint8).reshape(-1, frame_bytes(w, h, name))
+    n, nf = f.shape[0], 2 * f.shape[0]
+    if not n:
+        return f.copy()
+    ks = range(0, nf, 1 if fr else 2)
+    out, at = [], 0
+
+    def sub(k):             # a field index outside the call: the nearest field of the same parity inside it
+        return k & 1 if k < 0 else nf - 2 + (k & 1) if k >= nf else k
+    for es, c, r, _ in _planes(w, h, name):
+        s = f[:, at:at + es * c * r].reshape(n, r, es * c).astype(np.int64)
+        at += es * c * r
+        if r < 2:
+            o_ = s[[k >> 1 for k in ks]]
+        elif m == 2:
+            o_ = (s[:, np.maximum(np.arange(r) - 1, 0)] + 2 * s + s[:, np.minimum(np.arange(r) + 1, r - 1)] + 2) >> 2
+        else:
+            rows = np.arange(r)
+            yc = np.where(rows - 1 >= 0, rows - 1, rows + 1)
+            ye = np.where(rows + 1 < r, rows + 1, rows - 1)
+            o_ = np.empty((len(ks), r, es * c), np.int64)
+            for j, k in enumerate(ks):
+                p = o ^ (k & 1)
+                cur = s[k >> 1]
+                C, E = cur[yc], cur[ye]
+                sp = (C + E + 1) >> 1
+                if m == 1:
+                    b, a = s[sub(k - 1) >> 1], s[sub(k + 1) >> 1]
+                    pp, nn = s[sub(k - 2) >> 1], s[sub(k + 2) >> 1]
+                    d = (b + a) >> 1
+                    t0 = np.abs(b - a) >> 1
+                    t1 = (np.abs(pp[yc] - C) + np.abs(pp[ye] - E)) >> 1
+                    t2 = (np.abs(nn[yc] - C) + np.abs(nn[ye] - E)) >> 1
+                    mm = np.maximum(t0, np.maximum(t1, t2))
+                    sp = np.minimum(np.maximum(sp, d - mm), d + mm)
+                o_[j] = np.where(((rows & 1) == p)[:, None], cur, sp)
+        assert o_.min() >= 0 and o_.max() <= 255
+        out.append(o_.astype(np.uint8).reshape(len(ks), -1))
     return np.ascontiguousarray(np.concatenate(out, axis=1))
 
 
@@ -1093,6 +1180,47 @@ class Mpeg2Encoder:
         r = call(out.data_ptr() or None, out.numel()) if out.numel() else call(None, 0)
         n, fb = int(r["pictures"]), int(r["frame_bytes"])
         return out.reshape(-1)[:n * fb].reshape(n, fb), r
+
+    def deinterlace_device(self, frames, width, height, layout="i420", mode="adaptive", rate="frame", order="tff", out=None, stream=None):
+        """m2v_deinterlace_device: the woven width x height 4:2:0 frames in the uint8 device tensor `frames` (whole frames of `layout` back
+        to back, as decode_device returns them; any byte alignment) deinterlaced on the device: mode "line", "adaptive" or "blend", rate
+        "frame" (a frame per frame) or "field" (a frame per field, in time order), order "tff" or "bff" (the parity of the field that is
+        first in time, for the whole call).  deinterlace_frames is the definition.  Returns the frames [n or 2 n, frame_bytes] as a uint8
+        tensor on the same device: `out` (a contiguous uint8 tensor, all of it the capacity) or a new one.  One launch, ordered on `stream` (a
+        torch stream; None: the current one) like any torch operation, no host wait."""
+        import torch
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or not frames.is_cuda or frames.device.index != self.device:
+            raise ValueError("deinterlace_device: a uint8 tensor on the handle's device is required")
+        if not frames.is_contiguous():
+            raise ValueError("deinterlace_device: the tensor must be contiguous")
+        m, fr, o = _deint_code(DEINT_MODES, "mode", mode), _deint_code(DEINT_RATES, "rate", rate), _deint_code(DEINT_ORDERS, "order", order)
+        code = _layout420(layout)
+        width, height = int(width), int(height)
+        fb = width * height + 2 * ((width + 1) // 2) * ((height + 1) // 2)
+        if width < 1 or height < 2 or frames.numel() % fb:
+            raise ValueError("deinterlace_device: %d bytes are no whole frames of %d x %d" % (frames.numel(), width, height))
+        n = frames.numel() // fb
+        nout = n * (2 if fr else 1)
+        if out is None:
+            out = torch.empty(nout * fb, dtype=torch.uint8, device=frames.device)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != frames.device or not out.is_contiguous():
+            raise ValueError("deinterlace_device: out must be a contiguous uint8 tensor on the frames' device")
+        s = torch.cuda.current_stream(frames.device) if stream is None else stream
+        run_on = s
+        if not s.cuda_stream:
+            # the null stream has no handle the entry could take (NULL there means the handle's own stream, which the null stream does not
+            # wait for): the launch goes to a stream of this object's that waits for the null stream, and the null stream then waits for it
+            if getattr(self, "_deint_stream", None) is None:
+                self._deint_stream = torch.cuda.Stream(frames.device)
+            run_on = self._deint_stream
+            run_on.wait_stream(s)
+        try:
+            self._chk(self._L.m2v_deinterlace_device(self._h, frames.data_ptr() or None, n, width, height, code, m, fr, o, out.data_ptr() or None,
+                                                     out.numel(), run_on.cuda_stream), "m2v_deinterlace_device")
+        finally:
+            if run_on is not s:
+                s.wait_stream(run_on)
+        return out.reshape(-1)[:nout * fb].reshape(nout, fb)
 
     def decode_streams_report(self, max_records=None):
         """Pops the waiting records of m2v_decode_streams_report, oldest first, at most max_records of them: a numpy structured array

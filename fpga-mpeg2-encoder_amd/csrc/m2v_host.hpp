@@ -48,6 +48,9 @@
 //   m2v_scale.hip     m2v_set_source_size: frames of another size resampled to the picture size in front of the conversions - the setting,
 //                     the tap tables (m2v_scale_taps), k_scale and its launch (m2v_scale_kernels.hpp holds the arithmetic, for the device
 //                     and the host alike; no device global, nothing of m2v_kernels.hpp)
+//   m2v_deint.hip     m2v_deinterlace_device: woven 4:2:0 frames in HBM to progressive frames, behind the decoder and in front of an encode -
+//                     the entry, k_deint and its launch (m2v_deint_kernels.hpp holds the arithmetic, for the device and the host alike; no
+//                     device global, nothing of m2v_kernels.hpp, no state on the handle)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -6,7 +6,7 @@
 //          [-fps N/D] [-aspect 1:1|4:3|16:9|2.21:1] [-bitrate B] [-vbv K] [-colour bt601|bt709|P,T,M] [-repeat-headers]
 //          [-scale SWxSH [-filter triangle|area]]
 //          in.yuv W H out.m2v  [in2.yuv W2 H2 out2.m2v ...]
-//   m2v_tb -decode in.m2v out.yuv [-reconfmt i420|yv12|nv12|nv21] [-mode iso|module] [-syntax module|main [-bpictures] [-interlaced] [-extended [-mbtools [-fieldpictures [-join head|tail|both]]]]] [-container ts|ps [-pid N]] [-d device]
+//   m2v_tb -decode in.m2v out.yuv [-reconfmt i420|yv12|nv12|nv21] [-mode iso|module] [-syntax module|main [-bpictures] [-interlaced] [-extended [-mbtools [-fieldpictures [-join head|tail|both]]]]] [-container ts|ps [-pid N]] [-deint line|adaptive|blend [-fieldrate] [-bff]] [-d device]
 //   m2v_tb -demux ts|ps in.ts out.m2v [-pid N] [-d device]
 //
 // -demux: the video elementary stream of a transport or program stream, demultiplexed on the device (m2v_demux_device), into out.m2v, with
@@ -23,6 +23,8 @@
 // -fieldpictures with -interlaced -extended -mbtools: option "decode_field_pictures" = 1, picture_structure 1 / 2 too, two field pictures a frame.
 // -join head|tail|both with -fieldpictures: option "decode_join" = 1 / 2 / 3, a stream cut from a broadcast; prints the join record.
 // -interlaced with it: option "decode_interlaced" = 1, frame pictures with field prediction and field DCT too, one frame per picture.
+// -deint line|adaptive|blend: the decoded frames are deinterlaced on the device (m2v_deinterlace_device) before they are written, a frame
+// per frame or with -fieldrate a frame per field (not with blend), top field first or with -bff bottom field first.
 // A stream the decoder refuses ends with its status and the offset of the unit in error, exit status 1.
 // -pad: W, H are any size from 49 up; the files hold frames of that size in the chosen format, which are padded to whole macroblocks on
 // the device (m2v_set_frame_size) - the stream is the module's for the padded frames.  -truesize: -pad, and the stream's headers say
@@ -152,7 +154,7 @@ static int demux_main(int argc, char **argv)
 static int decode_main(int argc, char **argv)
 {
     const char *in = argv[2], *out = argv[3];
-    int layout = M2V_420_I420, mode = M2V_DEC_ISO, dev = 0, container = 0, pid = -1, syntax = M2V_SYNTAX_MODULE, bpictures = 0, interlaced = 0, extended = 0, mbtools = 0, fieldpictures = 0, join = 0;
+    int layout = M2V_420_I420, mode = M2V_DEC_ISO, dev = 0, container = 0, pid = -1, syntax = M2V_SYNTAX_MODULE, bpictures = 0, interlaced = 0, extended = 0, mbtools = 0, fieldpictures = 0, join = 0, deint = -1, fieldrate = 0, bff = 0;
     bool bad = false;
     for (int i = 4; i < argc; ++i) {
         const char *v = i + 1 < argc ? argv[i + 1] : "";
@@ -181,6 +183,14 @@ static int decode_main(int argc, char **argv)
             join = !strcmp(v, "head") ? M2V_JOIN_HEAD : !strcmp(v, "tail") ? M2V_JOIN_TAIL : !strcmp(v, "both") ? (M2V_JOIN_HEAD | M2V_JOIN_TAIL) : -1;
             bad = bad || join < 0;
             ++i;
+        } else if (!strcmp(argv[i], "-deint")) {
+            deint = !strcmp(v, "line") ? M2V_DEINT_LINE : !strcmp(v, "adaptive") ? M2V_DEINT_ADAPTIVE : !strcmp(v, "blend") ? M2V_DEINT_BLEND : -1;
+            bad = bad || deint < 0;
+            ++i;
+        } else if (!strcmp(argv[i], "-fieldrate")) {
+            fieldrate = 1;
+        } else if (!strcmp(argv[i], "-bff")) {
+            bff = 1;
         } else if (!strcmp(argv[i], "-d")) {
             dev = atoi(v);
             ++i;
@@ -195,8 +205,8 @@ static int decode_main(int argc, char **argv)
             bad = true;
         }
     }
-    if (bad || (pid >= 0 && !container)) {
-        fprintf(stderr, "m2v_tb -decode in.m2v out.yuv [-reconfmt i420|yv12|nv12|nv21] [-mode iso|module] [-syntax module|main [-bpictures] [-interlaced] [-extended [-mbtools [-fieldpictures [-join head|tail|both]]]]] [-container ts|ps [-pid N]] [-d device]\n");
+    if (bad || (pid >= 0 && !container) || ((fieldrate || bff) && deint < 0) || (fieldrate && deint == M2V_DEINT_BLEND)) {
+        fprintf(stderr, "m2v_tb -decode in.m2v out.yuv [-reconfmt i420|yv12|nv12|nv21] [-mode iso|module] [-syntax module|main [-bpictures] [-interlaced] [-extended [-mbtools [-fieldpictures [-join head|tail|both]]]]] [-container ts|ps [-pid N]] [-deint line|adaptive|blend [-fieldrate] [-bff]] [-d device]\n");
         return 2;
     }
     std::vector<uint8_t> es;
@@ -204,7 +214,7 @@ static int decode_main(int argc, char **argv)
     int err = 0;
     m2v_enc *e = m2v_create(7, 7, 3, 2, dev, &err);
     if (!e) { fprintf(stderr, "m2v_create: %s\n", m2v_last_error(nullptr)); return 1; }
-    void *d_in = nullptr, *d_box = nullptr, *d_out = nullptr;
+    void *d_in = nullptr, *d_box = nullptr, *d_out = nullptr, *d_prog = nullptr;
     const void *d_es = nullptr;
     size_t es_bytes = es.size();
     m2v_decode_stat r;
@@ -234,13 +244,22 @@ static int decode_main(int argc, char **argv)
         fprintf(stderr, "m2v_decode_device: %s\n", m2v_last_error(e));
     } else if (r.status != M2V_DEC_OK) {
         fprintf(stderr, "%s: not decoded: status %d, the unit at byte %llu\n", in, (int)r.status, (unsigned long long)r.err_offset);
+    } else if (deint >= 0 && r.pictures && hipMalloc(&d_prog, (size_t)r.out_bytes * (fieldrate ? 2 : 1)) != hipSuccess) {
+        fprintf(stderr, "m2v_tb: no device memory for %llu bytes of deinterlaced frames\n", (unsigned long long)r.out_bytes * (fieldrate ? 2 : 1));
+    } else if (deint >= 0 && r.pictures && m2v_deinterlace_device(e, d_out, r.pictures, (int)r.width, (int)r.height, layout, deint, fieldrate, bff, d_prog,
+                                                                  (size_t)r.out_bytes * (fieldrate ? 2 : 1), nullptr) != M2V_OK) {
+        fprintf(stderr, "m2v_deinterlace_device: %s\n", m2v_last_error(e));
+    } else if (deint >= 0 && hipDeviceSynchronize() != hipSuccess) {      // (the entry does not wait, and the handle's stream does not block the copy below)
+        fprintf(stderr, "m2v_tb: the deinterlacer's launch failed\n");
     } else {
-        std::vector<uint8_t> frames((size_t)r.out_bytes);
+        const bool prog = deint >= 0 && r.pictures;
+        std::vector<uint8_t> frames((size_t)r.out_bytes * (prog && fieldrate ? 2 : 1));
         FILE *o = fopen(out, "wb");
-        if (hipMemcpy(frames.data(), d_out, frames.size(), hipMemcpyDeviceToHost) != hipSuccess || !o || fwrite(frames.data(), 1, frames.size(), o) != frames.size()) {
+        if (hipMemcpy(frames.data(), prog ? d_prog : d_out, frames.size(), hipMemcpyDeviceToHost) != hipSuccess || !o || fwrite(frames.data(), 1, frames.size(), o) != frames.size()) {
             fprintf(stderr, "m2v_tb: cannot write %s\n", out);
         } else {
-            printf("%s: %u pictures of %u x %u, %u GOPs -> %s (%llu bytes)\n", in, r.pictures, r.width, r.height, r.gops, out, (unsigned long long)r.out_bytes);
+            printf("%s: %u pictures of %u x %u, %u GOPs -> %s (%llu bytes)\n", in, r.pictures, r.width, r.height, r.gops, out, (unsigned long long)frames.size());
+            if (prog) printf("%s: deinterlaced on the device, mode %d, %s, %s field first\n", in, deint, fieldrate ? "a frame per field" : "a frame per frame", bff ? "bottom" : "top");
             m2v_decode_join j;
             if (join && m2v_decode_join_report(e, &j) == M2V_OK)
                 printf("%s: joined at byte %llu, read up to byte %llu of %llu; %u frames dropped in front, %u behind\n", in, (unsigned long long)j.join_offset,
@@ -252,6 +271,7 @@ static int decode_main(int argc, char **argv)
     if (d_in) (void)hipFree(d_in);
     if (d_box) (void)hipFree(d_box);
     if (d_out) (void)hipFree(d_out);
+    if (d_prog) (void)hipFree(d_prog);
     m2v_destroy(e);
     return rc;
 }

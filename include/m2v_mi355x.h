@@ -1340,6 +1340,59 @@ int m2v_demux_device(m2v_enc *e, int kind, const void *d_src, const uint64_t *sr
 int m2v_demux_report(m2v_enc *e, m2v_demux_stat *out, size_t max);
 int m2v_demux_scan_tile(void);
 
+/*
+ * Deinterlace on the device: woven 4:2:0 frames to progressive frames, the stage between m2v_decode_device and an encode (the encoder is
+ * progressive only, and a source size - m2v_set_source_size - filters vertically across both fields).  d_src holds nframes frames of
+ * width x height back to back, exactly as m2v_decode_device writes them (layout = M2V_420_I420 / YV12 / NV12 / NV21; frame_bytes =
+ * w * h + 2 * ((w + 1) / 2) * ((h + 1) / 2), rows without padding); the output frames have the same size and layout, nframes of them
+ * (rate M2V_DEINT_FRAME_RATE) or 2 * nframes (M2V_DEINT_FIELD_RATE), back to back at d_dst.  Both pointers may be any byte address.
+ * The call enqueues ONE launch for all frames, planes and outputs on hip_stream (NULL: the handle's stream) and returns without a host
+ * wait; nothing has to be read back.  All offsets are computed in 64 bits.  What reads the output is ordered behind the launch by the
+ * stream: an m2v_encode_resident420 on the same stream needs nothing else, a copy on another stream needs a wait of the caller's.  The
+ * handle keeps no state of the call and allocates nothing for it.
+ *
+ * Planes.  Every plane is processed alone and bytewise: Y is h rows of w bytes, each I420 / YV12 chroma plane (h + 1) / 2 rows of
+ * (w + 1) / 2 bytes, the NV12 / NV21 chroma plane (h + 1) / 2 rows of 2 * ((w + 1) / 2) bytes.  Row r of ANY plane belongs to the field
+ * of parity r & 1, 0 being the top field: interlaced 4:2:0 as 13818-2 lays it out.  A plane with a single row is copied to every output.
+ *
+ * Fields.  The fields of a call form one sequence in time: F[k], k = 0 .. 2 * nframes - 1, lies in frame k >> 1 and has parity
+ * order ^ (k & 1) (order: the parity of the field that is first in time, M2V_DEINT_TFF or M2V_DEINT_BFF, the same for the whole call).
+ * A field index outside the call means the nearest field of the same parity inside it: k - 2 becomes k at the front, k + 1 becomes
+ * k - 1 at the back, and so on.  Frame rate writes one frame for every even k, field rate one for every k, in order.
+ *
+ * The output for field k of parity p, in a plane of H >= 2 rows: a row y with (y & 1) == p is row y of frame k >> 1.  Any other row is
+ * interpolated.  yc = y - 1 if that is >= 0, else y + 1; ye = y + 1 if that is < H, else y - 1 (a row missing at the plane's edge is
+ * replaced by the one kept row beside it); c and e are the samples of frame k >> 1 in rows yc and ye, sp = (c + e + 1) >> 1.
+ *   M2V_DEINT_LINE      the sample is sp.
+ *   M2V_DEINT_ADAPTIVE  the sample is min(max(sp, d - m), d + m), with b and a the samples of row y in the frames that hold F[k - 1]
+ *                       and F[k + 1], d = (b + a) >> 1, t0 = |b - a| >> 1, t1 = (|c' - c| + |e' - e|) >> 1 with c' and e' rows yc and
+ *                       ye of the frame that holds F[k - 2], t2 the same against F[k + 2], m = max(t0, t1, t2).  The temporal core
+ *                       of the familiar motion-adaptive filters: where nothing moves the other field is woven in, where something
+ *                       moves the sample falls back to sp, and the width of the clamp is the motion found.  No threshold, no
+ *                       edge-directed search.
+ *   M2V_DEINT_BLEND     frame rate only, knows no parity: o[y] = (s[max(y - 1, 0)] + 2 * s[y] + s[min(y + 1, H - 1)] + 2) >> 2, frame
+ *                       by frame.
+ * A column of one plane, rows 0 2 4 6 8 10 12 14: LINE gives 0 2 4 6 8 10 12 12 (TFF) and 2 2 4 6 8 10 12 14 (BFF), BLEND
+ * 1 2 4 6 8 10 12 14.
+ *
+ * M2V_E_PARAM for an unknown layout, mode, rate or order, for BLEND with FIELD_RATE, for width < 1, height < 2 or either above 16384,
+ * and where the source range and the destination range overlap.  M2V_E_OVERFLOW where cap is below m2v_deinterlace_bound: not one byte
+ * is written.  M2V_E_STATE while a sequence is in progress or a resident call is in flight, as m2v_decode_device.  nframes == 0 is
+ * M2V_OK and launches nothing.  m2v_deinterlace_bound: the bytes a call writes, 0 for illegal arguments.  m2v_deinterlace_tile: the
+ * bytes of a row and the rows after which the kernel hands over to another group of lanes (a test aims sizes at them).
+ *
+ * Out of scope: a per-picture record of top_field_first / progressive_frame / repeat_first_field from the decoder (the caller states the
+ * order for the whole call), pulldown, edge-directed interpolation, 4:4:4 and RGB frames, deinterlacing as an automatic stage inside
+ * the resident entries, and the batch entries.
+ */
+enum { M2V_DEINT_LINE = 0, M2V_DEINT_ADAPTIVE = 1, M2V_DEINT_BLEND = 2 };   /* mode  */
+enum { M2V_DEINT_FRAME_RATE = 0, M2V_DEINT_FIELD_RATE = 1 };                 /* rate  */
+enum { M2V_DEINT_TFF = 0, M2V_DEINT_BFF = 1 };                               /* order: parity of the field that is first in time */
+int m2v_deinterlace_device(m2v_enc *e, const void *d_src, size_t nframes, int width, int height, int layout,
+                           int mode, int rate, int order, void *d_dst, size_t cap, void *hip_stream);
+unsigned long long m2v_deinterlace_bound(int width, int height, size_t nframes, int rate);   /* bytes written; 0 for illegal arguments */
+int m2v_deinterlace_tile(int *cols, int *rows);   /* the kernel's tile, for tests, like m2v_decode_scan_tile */
+
 /* Per-kernel statistics of the last m2v_encode_resident call with "profile" = 1.
  * kernel: 0 = macroblock kernel on P frames, 1 = macroblock kernel on I frames,
  * 2 = strip mode's final assembly (k_strip_layout + k_strip_assemble), 3 = slice assembly (k_assemble), 4 = scans,
