@@ -39,8 +39,8 @@
 // with "decode_b_pictures" either way: frame pictures with frame_pred_frame_dct 0; the same two places go to m2v_decode_i.hip
 // (dec_i_plan, dec_i_chunks).  Option "decode_extended" = 1, with the other two either way: several slices a row, slice header extras,
 // quant_matrix_extension, composite_display_flag 1; the same two places go to m2v_decode_x.hip (dec_x_plan, dec_x_chunks).  Option
-// "decode_mb_tools" = 1 on top of "decode_extended": Table B-15, concealment motion vectors, dual prime; from the same two places to
-// m2v_decode_t.hip (dec_t_plan, dec_t_chunks).
+// "decode_mb_tools" = 1 on top of "decode_extended": Table B-15, concealment motion vectors, dual prime; the plan is m2v_decode_t.hip's
+// (dec_t_plan), and dec_x_chunks takes the option as `tools`.
 // "decode_field_pictures" = 1 on top of "decode_interlaced", "decode_extended" and "decode_mb_tools": picture_structure 1 / 2, two field
 // pictures a frame; from the same two places to m2v_decode_f.hip (dec_f_plan, dec_f_chunks), whose chunks are whole frames.
 // "decode_join" = 1 .. 3 on top of all of them: a stream that begins in front of its first sequence header, whose first B pictures lack
@@ -395,8 +395,8 @@ static int decode_impl(m2v_enc *e, void *argp)
     const bool b_pictures = e->decode_b_pictures != 0;                 // m2v_decode_b.hip: its plan, and everything behind the plan's wait
     const bool interlaced = e->decode_interlaced != 0;                 // m2v_decode_i.hip: the same two places, with b_pictures either way
     const bool extended = e->decode_extended != 0;                     // m2v_decode_x.hip: the same two places, with the other two either way
-    const bool mb_tools = e->decode_mb_tools != 0;                     // m2v_decode_t.hip: in the places of dec_x_plan and dec_x_chunks
-    const bool field_pictures = e->decode_field_pictures != 0;         // m2v_decode_f.hip: in the places of dec_t_plan and dec_t_chunks
+    const bool mb_tools = e->decode_mb_tools != 0;                     // m2v_decode_t.hip: its plan in the place of dec_x_plan; dec_x_chunks takes it
+    const bool field_pictures = e->decode_field_pictures != 0;         // m2v_decode_f.hip: in the places of dec_t_plan and dec_x_chunks
     const int join = e->decode_join;                                   // m2v_decode_j.hip: its plan in the place of dec_f_plan, dec_f_chunks behind it
     e->d_dec_x.recorded = false;
     const size_t ntiles = (n + dec::kScanTile - 1) / dec::kScanTile;
@@ -488,7 +488,7 @@ static int decode_impl(m2v_enc *e, void *argp)
         const size_t rows = *(const uint32_t *)(e->h_dec + rec_off + 96);
         if (!e->decode_batch) B = std::min(np, std::max<size_t>(1, std::min(kDecBatchMax, kDecLevelBytes / (mbw * rows * 768))));
         auto *h_list = (uint32_t *)(e->h_dec + rec_off + 128 + ((pic_cap + 3) & ~(size_t)3));
-        (mb_tools ? dec_t_chunks : dec_x_chunks)(e, s, a->es, n, a->dst, a->layout, R, rows, B, types, h_list, h_list + pic_cap, (m2v_decode_stat *)(e->h_dec + rec_off));
+        dec_x_chunks(e, s, a->es, n, a->dst, a->layout, R, rows, B, types, mb_tools, h_list, h_list + pic_cap, (m2v_decode_stat *)(e->h_dec + rec_off));
         R = *h_rec;
         return M2V_OK;
     }

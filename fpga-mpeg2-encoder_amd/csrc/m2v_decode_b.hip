@@ -1,6 +1,5 @@
 // m2v_decode_b.hip — B pictures for m2v_decode_device (option "decode_b_pictures" = 1 on top of "decode_syntax" = M2V_SYNTAX_MAIN).
-// m2v_decode.hip tells the whole story and keeps the scan; this unit holds the plan and everything behind the plan's wait, in kernels
-// of its own so that those of m2v_decode.hip and m2v_decode_main.hip come out of the compiler exactly as they did.
+// m2v_decode.hip tells the whole story and keeps the scan; this unit holds the plan and everything behind the plan's wait.
 // decoder.decode_main(b_pictures=True) is the definition; every function that decides a bit or a sample is a bp_ (or main_) function of
 // m2v_decode_kernels.hpp.
 //
@@ -14,18 +13,17 @@
 //   k_db_recon   one wavefront per macroblock with k_dm_recon's lane mapping; one or two predictions from the slots the picture's
 //                table names, the mean of both where both are used.  grid = (macroblocks, pictures of the launch).
 //   k_db_out     every picture of the chunk at its display index: grid = (units, pictures); 16-byte stores where the destination is
-//                aligned, the first and last unit of a picture byte by byte.
+//                aligned, the first and last unit of a picture byte by byte (out_picture, m2v_decode_device.hpp).
 //
 // The chunk's buffer: slot 0 = the anchor before the last one in front of the chunk, slot 1 = the last one, slot 2 + k = picture k of
 // the chunk.  Within a chunk the anchors run step by step along their chains (a step counts anchors only), then all B pictures of the
-// chunk in one launch: nothing depends on a B picture.  The host waits where it did: behind the plan and at the end.
+// chunk in one launch: nothing depends on a B picture (dec_chunk_schedule, m2v_decode_chunks.hpp, which the units of the later options
+// run too; slot, m2v_decode_device.hpp).  The host waits where it did: behind the plan and at the end.
 #include "m2v_decode_state.hpp"
 
 static_assert(sizeof(dec::BMb) == sizeof(dec::MbRec), "the B-picture record lies where the module's does");
 
 namespace m2v {
-
-constexpr uint32_t kNoPic = 0xFFFFFFFFu;
 
 __global__ __launch_bounds__(kDecThreads) void k_db_plan(const uint8_t *__restrict__ es, unsigned long long n, const unsigned long long *__restrict__ ev, DecState *st,
                                                          DecPic *__restrict__ pics, uint32_t pic_cap, uint8_t *h_types, unsigned long long cap, int probe,
@@ -188,10 +186,6 @@ __global__ void k_db_judge(DecState *st)
     if (st->status == dec::kOk && st->err != dec::kNone) st->status = dec::kSyntax;
 }
 
-// the chunk's slot of the picture with coded index r: the chunk's own pictures from slot 2, the last anchor in front of the chunk
-// (coded index c1) in slot 1, the one before it in slot 0
-__device__ inline uint32_t db_slot(uint32_t r, uint32_t p0, uint32_t c1) { return r == kNoPic ? 0u : r >= p0 ? 2u + (r - p0) : r == c1 ? 1u : 0u; }
-
 // as k_dm_recon: grid = (macroblocks, pictures of the launch); list: their coded indices, all of chunk [p0, ...)
 __global__ __launch_bounds__(64) void k_db_recon(const DecState *__restrict__ st, const uint32_t *__restrict__ list, uint32_t p0, uint32_t c1,
                                                  const uint8_t *__restrict__ mats, const DecBPic *__restrict__ bp, const dec::BMb *__restrict__ mb,
@@ -207,7 +201,7 @@ __global__ __launch_bounds__(64) void k_db_recon(const DecState *__restrict__ st
     const dec::BMb m = mb[at];
     const uint32_t col = k % mbw, row = k / mbw;
     uint8_t *cur = buf + (size_t)(pic + 2u) * psz;
-    const uint8_t *fwd = buf + (size_t)db_slot(Q.fwd, p0, c1) * psz, *bwd = buf + (size_t)db_slot(Q.bwd, p0, c1) * psz;
+    const uint8_t *fwd = buf + (size_t)slot(Q.fwd, p0, c1) * psz, *bwd = buf + (size_t)slot(Q.bwd, p0, c1) * psz;
     const bool intra = m.intra != 0;
     const uint32_t dirs = m.dirs;
     const int32_t qscale = dec::main_scale(m.qcode, pp.qst), weight = mats[(intra ? 0u : 64u) + l];
@@ -271,8 +265,6 @@ __global__ __launch_bounds__(64) void k_db_recon(const DecState *__restrict__ st
     }
 }
 
-typedef uint32_t db_store_t __attribute__((ext_vector_type(4)));
-
 // picture blockIdx.y of chunk [p0, p0 + np) into dst at its display index: bytes [display * fb, (display + 1) * fb) of the output
 __global__ __launch_bounds__(kDecThreads) void k_db_out(const DecState *__restrict__ st, const DecBPic *__restrict__ bp, const uint8_t *__restrict__ buf, size_t psz,
                                                         uint32_t p0, uint8_t *__restrict__ dst, int layout)
@@ -281,30 +273,8 @@ __global__ __launch_bounds__(kDecThreads) void k_db_out(const DecState *__restri
     const uint32_t w = st->width, h = st->height, W = 16u * st->mbw, H = 16u * st->mbh;
     const uint32_t d = bp[p0 + blockIdx.y].display;
     if (d >= st->npics) return;                                        // (an accepted stream's display indices are a permutation)
-    const uint8_t *pic = buf + (size_t)(blockIdx.y + 2u) * psz;
-    const unsigned long long fb = st->frame_bytes, lo = (unsigned long long)d * fb, hi = lo + fb;
-    const unsigned long long lead = (unsigned long long)(uintptr_t)dst & 15ull;
-    const unsigned long long u0 = (lo + lead) >> 4, u1 = (hi + lead + 15ull) >> 4;
-    for (unsigned long long g = u0 + (unsigned long long)blockIdx.x * kDecThreads + threadIdx.x; g < u1; g += (unsigned long long)gridDim.x * kDecThreads) {
-        const long long o0 = (long long)(g << 4) - (long long)lead;
-        const int k0 = o0 < (long long)lo ? (int)((long long)lo - o0) : 0, k1 = (long long)hi - o0 < 16 ? (int)((long long)hi - o0) : 16;
-        if (k0 >= k1) continue;
-        uint32_t q = (uint32_t)((unsigned long long)(o0 + k0) - lo);
-        dec::OutAt at = dec::out_locate(q, w, h, layout);
-        uint32_t v[4] = {0, 0, 0, 0};
-        for (int k = k0; k < k1; ++k) {
-            v[k >> 2] |= (uint32_t)dec::pic_sample(pic, W, H, at) << (8 * (k & 3));
-            if (k + 1 == k1) break;
-            ++q;
-            if (at.run > 1) dec::out_step(at, layout);
-            else at = dec::out_locate(q, w, h, layout);
-        }
-        if (k0 == 0 && k1 == 16) {
-            *(__attribute__((address_space(1))) db_store_t *)(dst + o0) = db_store_t{v[0], v[1], v[2], v[3]};
-        } else {
-            for (int k = k0; k < k1; ++k) dst[o0 + k] = (uint8_t)(v[k >> 2] >> (8 * (k & 3)));
-        }
-    }
+    const unsigned long long fb = st->frame_bytes, lo = (unsigned long long)d * fb;
+    out_picture(buf + (size_t)(blockIdx.y + 2u) * psz, w, h, W, H, lo, lo + fb, dst, layout, kDecThreads);
 }
 
 __global__ void k_db_finish(const DecState *st, m2v_decode_stat *h_rec)
@@ -331,41 +301,7 @@ void dec_b_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_
     e->d_dec_lv.ensure(B * mbs * 384);
     e->d_dec_buf.ensure((B + 2) * psz);
     e->d_dec_list.ensure(np);
-    // every chunk's anchors ordered by their step inside the chunk - a chain starts at its I picture, or at the chunk's first anchor -,
-    // then its B pictures; and what the chunk leaves in slots 0 and 1 for the next
-    struct Launch { size_t off, count; };
-    struct Chunk { std::vector<Launch> steps; Launch b; long c1, carry0, carry1; };      // carry: the chunk's slot to copy into slot 0 / 1 (-1: nothing)
-    std::vector<Chunk> chunks;
-    long a1 = -1, a2 = -1;                                             // the last two anchors in front of the chunk, coded indices
-    for (size_t p0 = 0; p0 < np; p0 += B) {
-        const size_t nb = std::min(B, np - p0);
-        Chunk C;
-        C.c1 = a1;
-        std::vector<long> step(nb, -1);
-        long deepest = -1, prev = -1;
-        for (size_t k = 0; k < nb; ++k) {
-            if (types[p0 + k] == 3) continue;
-            step[k] = prev >= 0 && types[p0 + k] != 1 ? step[prev] + 1 : 0;
-            deepest = std::max(deepest, step[k]);
-            prev = (long)k;
-        }
-        size_t at = p0;
-        for (long j = 0; j <= deepest; ++j) {
-            const size_t first = at;
-            for (size_t k = 0; k < nb; ++k) if (step[k] == j) h_list[at++] = (uint32_t)(p0 + k);
-            C.steps.push_back(Launch{first, at - first});
-        }
-        C.b.off = at;
-        for (size_t k = 0; k < nb; ++k) if (types[p0 + k] == 3) h_list[at++] = (uint32_t)(p0 + k);
-        C.b.count = at - C.b.off;
-        auto slot = [&](long r) { return r >= (long)p0 ? 2 + (r - (long)p0) : r == C.c1 ? 1L : 0L; };
-        long n1 = a1, n2 = a2;
-        for (size_t k = 0; k < nb; ++k) if (types[p0 + k] != 3) { n2 = n1; n1 = (long)(p0 + k); }
-        C.carry0 = n2 >= 0 && slot(n2) != 0 ? slot(n2) : -1;
-        C.carry1 = n1 >= 0 && slot(n1) != 1 ? slot(n1) : -1;
-        a1 = n1; a2 = n2;
-        chunks.push_back(C);
-    }
+    const std::vector<DecChunk> chunks = dec_chunk_schedule(types, np, B, h_list);
     auto *d_st = (DecState *)e->d_dec_st.p;
     auto *d_mb = (dec::BMb *)e->d_dec_mb.p;
     const uint8_t *mats = e->d_dec_main.p;
@@ -373,20 +309,20 @@ void dec_b_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_
     HIPCHK(hipMemcpyAsync(e->d_dec_list.p, h_list, np * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     for (size_t p0 = 0, c = 0; p0 < np; p0 += B, ++c) {
         const size_t nb = std::min(B, np - p0);
-        const Chunk &C = chunks[c];
+        const DecChunk &C = chunks[c];
         HIPCHK(hipMemsetAsync(e->d_dec_lv.p, 0, nb * mbs * 768, s));
         k_db_slices<<<(unsigned)((nb * mbh + 63) / 64), 64, 0, s>>>(es, n, e->d_dec_ev.p, d_st, (const DecPic *)e->d_dec_pics.p, bp, (uint32_t)p0, (uint32_t)nb, d_mb,
                                                                     e->d_dec_dc.p, e->d_dec_lv.p);
         HIPCHK(hipGetLastError());
         k_db_judge<<<1, 1, 0, s>>>(d_st);
         HIPCHK(hipGetLastError());
-        auto recon = [&](const Launch &l) {
+        auto recon = [&](const DecLaunch &l) {
             if (!l.count) return;
             k_db_recon<<<dim3((unsigned)mbs, (unsigned)l.count), 64, 0, s>>>(d_st, e->d_dec_list.p + l.off, (uint32_t)p0, (uint32_t)C.c1, mats, bp, d_mb, e->d_dec_dc.p,
                                                                             e->d_dec_lv.p, e->d_dec_buf.p, psz);
             HIPCHK(hipGetLastError());
         };
-        for (const Launch &l : C.steps) recon(l);
+        for (const DecLaunch &l : C.steps) recon(l);
         recon(C.b);                                                    // every B picture of the chunk at once: its anchors are done
         const size_t units = (R.frame_bytes + 15) / 16 + 1;
         k_db_out<<<dim3((unsigned)std::min<size_t>((units + kDecThreads - 1) / kDecThreads, 1024), (unsigned)nb), kDecThreads, 0, s>>>(d_st, bp, e->d_dec_buf.p, psz,

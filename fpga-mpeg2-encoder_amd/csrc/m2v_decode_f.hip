@@ -1,14 +1,13 @@
 // m2v_decode_f.hip — field pictures for m2v_decode_device (option "decode_field_pictures" = 1 on top of "decode_interlaced",
-// "decode_extended" and "decode_mb_tools" = 1, with "decode_b_pictures" 0 or 1).  Modelled on m2v_decode_t.hip, whose tables and
-// launches these are: m2v_decode.hip keeps the scan; this unit holds the plan and everything behind the plan's wait, in kernels of its
-// own so that those of the other six units come out of the compiler exactly as they did.
+// "decode_extended" and "decode_mb_tools" = 1, with "decode_b_pictures" 0 or 1).  Modelled on m2v_decode_x.hip with TOOLS, whose tables
+// and launches these are: m2v_decode.hip keeps the scan; this unit holds the plan and everything behind the plan's wait.
 // decoder.decode_main(..., field_pictures=True) is the definition; every function that decides a bit, a column, a pair or a verdict is
 // an fp_ (or t_ / x_ / il_ / bp_ / main_) function of m2v_decode_kernels.hpp.
 //
 // Two indices: a CODED PICTURE (a frame picture or one field: slices, records, parameters, matrices) and a FRAME (a slot of the
 // chunk's buffer, a display index, a reference).  The table behind the matrices holds one DecFPic a coded picture.
 //
-//   k_df_plan    k_dt_plan's grammar by dec::fp_event, plus the pairs.  A lane sums the pictures of its range of events twice
+//   k_df_plan    k_dx_plan's grammar by dec::fp_event, plus the pairs.  A lane sums the pictures of its range of events twice
 //                (dec::fp_range: nothing waiting in front of it / a first field waiting), lane 0 joins the sums in order
 //                (dec::fp_join), and every lane places its pictures behind the sums in front of its range (dec::fp_place): the frame,
 //                "second field", the frames it refers to, and the refusals of a pair.  A pair parted by a range's edge is planned from
@@ -16,11 +15,11 @@
 //                frame's when the next anchor frame begins (written to the entry of its first picture, wherever that lies).
 //   k_df_slices  one lane per slice EVENT of the chunk: dec::t_slice for a frame picture, dec::fp_slice for a field (half the rows).
 //                A field's records lie in its frame's stretch: the first field's in the first half, the second field's behind them.
-//   k_df_recon   a frame picture as k_dt_recon; a field writes the lines of its parity of its frame's slot at twice the stride, and
-//                reads reference fields the same way (dec::fp_predict).  The second field of an anchor frame reads the other parity's
+//   k_df_recon   the residual as every dec::IMb unit's (imb_residual); a frame picture predicts as k_dx_recon, a field writes the
+//                lines of its parity of its frame's slot at twice the stride, and reads reference fields the same way (dec::fp_predict).  The second field of an anchor frame reads the other parity's
 //                lines of its OWN slot: it is launched a step behind its first field, and those lines are not the ones it writes.
-//   k_df_out     one frame per slot at its display index, as k_dt_out (the entry of the frame's first picture carries the index).
-//   k_df_mats, k_df_cont, k_df_judge, k_df_finish   k_dt_*'s text.
+//   k_df_out     one frame per slot at its display index, through out_picture (the entry of the frame's first picture carries the index).
+//   k_df_mats, k_df_cont, k_df_judge, k_df_finish   as k_dx_*, over DecFPic.
 //
 // A chunk is a run of whole FRAMES ("decode_batch" counts frames): its edge never parts a pair, and the two carried slots hold whole
 // anchor frames.
@@ -29,8 +28,6 @@
 static_assert(sizeof(dec::IMb) == 32, "the interlaced record is two of the module's");
 
 namespace m2v {
-
-constexpr uint32_t kNoPic = 0xFFFFFFFFu;
 
 __global__ __launch_bounds__(kDecThreads) void k_df_plan(const uint8_t *__restrict__ es, unsigned long long n, const unsigned long long *__restrict__ ev, DecState *st,
                                                          DecPic *__restrict__ pics, uint32_t pic_cap, uint8_t *h_types, unsigned long long cap, int probe,
@@ -169,19 +166,6 @@ __global__ __launch_bounds__(kDecThreads) void k_df_plan(const uint8_t *__restri
     *h_rec = r;
 }
 
-struct DecFSink {
-    dec::IMb *mb_;
-    int32_t *dc_;
-    int16_t *lv_;
-    M2V_HD void mb(int col, const dec::IMb &m, const int32_t (&dc)[6])
-    {
-        mb_[col] = m;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) dc_[col * 6 + k] = dc[k];
-    }
-    M2V_HD void level(int col, int blk, uint32_t i, int32_t l) { lv_[(col * 6 + blk) * 64 + (int)i] = (int16_t)l; }
-};
-
 // the first record of coded picture Q in a chunk that begins at frame f0: a frame's stretch is mbs records, a second field's half of it
 // lies behind its first field's
 __device__ inline size_t df_first(const DecFPic &Q, uint32_t f0, uint32_t mbs) { return (size_t)(Q.frame - f0) * mbs + (((Q.params >> 26) & 1u) ? mbs / 2u : 0u); }
@@ -210,7 +194,7 @@ __global__ __launch_bounds__(64) void k_df_slices(const uint8_t *__restrict__ es
     const uint32_t rows = field ? mbh / 2u : mbh;
     if (code < 1u || code > rows || Q.frame < f0) { atomicMin(&st->err, start); return; }      // (the plan's grammar: 1 <= code <= rows)
     const size_t first = df_first(Q, f0, mbw * mbh) + (size_t)(code - 1u) * mbw;
-    DecFSink sink{mb + first, dc + first * 6, lv + first * 384};
+    IMbSink sink{mb + first, dc + first * 6, lv + first * 384};
     int c0, c1;
     const bool ok = field ? dec::fp_slice(es, start, end, P.type, pp, (int)mbw, (int)rows, (int)code - 1, sink, c0, c1)
                           : dec::t_slice(es, start, end, P.type, pp.t, (int)mbw, (int)mbh, (int)code - 1, sink, c0, c1);
@@ -248,12 +232,8 @@ __global__ __launch_bounds__(128) void k_df_mats(const uint8_t *__restrict__ es,
     table[(size_t)p * 128u + l] = (uint8_t)dec::x_matrix_weight(es, n, (const uint64_t *)ev, st->nev, src, (int)m, t, mats + 64u * m);
 }
 
-// the chunk's slot of frame r: the chunk's own frames from slot 2 on, the last anchor frame in front of it (c1) in slot 1, the one
-// before that in slot 0
-__device__ inline uint32_t df_slot(uint32_t r, uint32_t f0, uint32_t c1) { return r == kNoPic ? 0u : r >= f0 ? 2u + (r - f0) : r == c1 ? 1u : 0u; }
-
 // grid = (macroblocks of a frame, coded pictures of the launch); list: their coded indices, all of the chunk that begins at frame f0.
-// A frame picture is k_dt_recon's; a field has half the macroblocks and works on the lines of its parity.  Every read of a reference
+// A frame picture is k_dx_recon's; a field has half the macroblocks and works on the lines of its parity.  Every read of a reference
 // lies inside its picture or its field, and the field is there: the slice walk refused the slice otherwise (dec::il_inside,
 // dec::fp_inside), and a refused slice stops the call before this kernel (k_df_judge)
 __global__ __launch_bounds__(64) void k_df_recon(const DecState *__restrict__ st, const uint32_t *__restrict__ list, uint32_t f0, uint32_t c1,
@@ -273,41 +253,12 @@ __global__ __launch_bounds__(64) void k_df_recon(const DecState *__restrict__ st
     const dec::IMb m = mb[at];
     const uint32_t col = k % mbw, row = k / mbw, par = field ? fp.ps - 1u : 0u;
     uint8_t *cur = buf + (size_t)(Q.frame - f0 + 2u) * psz;
-    const uint8_t *fwd = buf + (size_t)df_slot(Q.fwd, f0, c1) * psz, *bwd = buf + (size_t)df_slot(Q.bwd, f0, c1) * psz;
+    const uint8_t *fwd = buf + (size_t)slot(Q.fwd, f0, c1) * psz, *bwd = buf + (size_t)slot(Q.bwd, f0, c1) * psz;
     // the frame that holds the field of parity q of direction d: the second field of an anchor frame finds the other parity in its own slot
     const bool own = field && fp.second && pics[gp].type == 2u;
     const uint8_t *const ref[4] = {own && par != 0u ? cur : fwd, own && par != 1u ? cur : fwd, own && par != 0u ? cur : bwd, own && par != 1u ? cur : bwd};
     const bool intra = m.intra != 0;
-    const int32_t qscale = dec::main_scale(m.qcode, pp.qst), weight = mats[(size_t)gp * 128u + (intra ? 0u : 64u) + l];
-#pragma unroll
-    for (int blk = 0; blk < 6; ++blk) {
-        if (!((m.cbp >> (5 - blk)) & 1)) continue;                     // (uniform: the whole wavefront works on one macroblock)
-        int32_t f = intra && l == 0 ? dec::main_dequant_dc(dc[at * 6 + blk], pp.prec) : dec::main_dequant(lv[(at * 6 + blk) * 64 + l], weight, intra, qscale);
-        const int odd = __popcll(__ballot(f & 1)) & 1;
-        if (!odd && l == 63) f = dec::mismatch(f);
-        F[blk][l] = f;
-    }
-    __syncthreads();
-    const int blk8 = (int)(l >> 3), r8 = (int)(l & 7u);
-    const bool mine = l < 48 && ((m.cbp >> (5 - blk8)) & 1);
-    if (mine) {
-        int32_t a[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] = F[blk8][r8 * 8 + j];
-        dec::idct_1d(a, true, dec::kIso);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) F[blk8][r8 * 8 + j] = a[j];
-    }
-    __syncthreads();
-    if (mine) {
-        int32_t a[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] = F[blk8][j * 8 + r8];
-        dec::idct_1d(a, false, dec::kIso);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) F[blk8][j * 8 + r8] = a[j];
-    }
-    __syncthreads();
+    imb_residual(F, m, pp, mats + (size_t)gp * 128u, dc, lv, at, l);
     {   // luma: four samples of one row per lane.  A field's row y of macroblock row `row` is line 16 row + y of the field: frame line 2 (16 row + y) + par
         const uint32_t y = l >> 2, x0 = (l & 3u) * 4u, blk = dec::il_luma_block(x0, y, m.dct_type), brow = dec::il_luma_row(y, m.dct_type);
         const bool coded = (m.cbp >> (5 - blk)) & 1;
@@ -341,8 +292,6 @@ __global__ __launch_bounds__(64) void k_df_recon(const DecState *__restrict__ st
     }
 }
 
-typedef uint32_t df_store_t __attribute__((ext_vector_type(4)));
-
 // the frame of coded picture p0 + blockIdx.y (its first picture: a second field has nothing to put out) into dst at its display index:
 // bytes [display * fb, (display + 1) * fb) of the output
 __global__ __launch_bounds__(kDecThreads) void k_df_out(const DecState *__restrict__ st, const DecFPic *__restrict__ bp, const uint8_t *__restrict__ buf, size_t psz,
@@ -353,30 +302,8 @@ __global__ __launch_bounds__(kDecThreads) void k_df_out(const DecState *__restri
     const DecFPic Q = bp[p0 + blockIdx.y];
     const uint32_t d = Q.display;
     if (((Q.params >> 26) & 1u) || d >= st->npics || Q.frame < f0) return;      // (an accepted stream's display indices are a permutation of its frames)
-    const uint8_t *pic = buf + (size_t)(Q.frame - f0 + 2u) * psz;
-    const unsigned long long fb = st->frame_bytes, lo = (unsigned long long)d * fb, hi = lo + fb;
-    const unsigned long long lead = (unsigned long long)(uintptr_t)dst & 15ull;
-    const unsigned long long u0 = (lo + lead) >> 4, u1 = (hi + lead + 15ull) >> 4;
-    for (unsigned long long g = u0 + (unsigned long long)blockIdx.x * kDecThreads + threadIdx.x; g < u1; g += (unsigned long long)gridDim.x * kDecThreads) {
-        const long long o0 = (long long)(g << 4) - (long long)lead;
-        const int k0 = o0 < (long long)lo ? (int)((long long)lo - o0) : 0, k1 = (long long)hi - o0 < 16 ? (int)((long long)hi - o0) : 16;
-        if (k0 >= k1) continue;
-        uint32_t q = (uint32_t)((unsigned long long)(o0 + k0) - lo);
-        dec::OutAt at = dec::out_locate(q, w, h, layout);
-        uint32_t v[4] = {0, 0, 0, 0};
-        for (int k = k0; k < k1; ++k) {
-            v[k >> 2] |= (uint32_t)dec::pic_sample(pic, W, H, at) << (8 * (k & 3));
-            if (k + 1 == k1) break;
-            ++q;
-            if (at.run > 1) dec::out_step(at, layout);
-            else at = dec::out_locate(q, w, h, layout);
-        }
-        if (k0 == 0 && k1 == 16) {
-            *(__attribute__((address_space(1))) df_store_t *)(dst + o0) = df_store_t{v[0], v[1], v[2], v[3]};
-        } else {
-            for (int k = k0; k < k1; ++k) dst[o0 + k] = (uint8_t)(v[k >> 2] >> (8 * (k & 3)));
-        }
-    }
+    const unsigned long long fb = st->frame_bytes, lo = (unsigned long long)d * fb;
+    out_picture(buf + (size_t)(Q.frame - f0 + 2u) * psz, w, h, W, H, lo, lo + fb, dst, layout, kDecThreads);
 }
 
 __global__ void k_df_finish(const DecState *st, m2v_decode_stat *h_rec)
@@ -392,7 +319,7 @@ void dec_f_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long 
     HIPCHK(hipGetLastError());
 }
 
-// dec_t_chunks over frames: a chunk is B whole frames, its coded pictures the one or two of each.  types[p]: coded picture p's type,
+// dec_x_chunks over frames: a chunk is B whole frames, its coded pictures the one or two of each.  types[p]: coded picture p's type,
 // structure << 2, "second field" << 4 (the plan's); ncp: the coded pictures; h_sl[p]: the slices in front of coded picture p
 void dec_f_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_t *dst, int layout, const m2v_decode_stat &R, size_t mbh, size_t B,
                   const uint8_t *types, size_t ncp, uint32_t *h_list, const uint32_t *h_sl, m2v_decode_stat *h_rec)
@@ -422,13 +349,11 @@ void dec_f_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_
     // every chunk's anchor pictures ordered by their step inside the chunk - a picture is a step behind everything of the chunk it reads:
     // a P picture the anchor frame in front of its frame, the second field of a frame its first field too -, then its B pictures; and what
     // the chunk leaves in slots 0 and 1 for the next
-    struct Launch { size_t off, count; };
-    struct Chunk { std::vector<Launch> steps; Launch b; long c1, carry0, carry1; };      // carry: the chunk's slot to copy into slot 0 / 1 (-1: nothing)
-    std::vector<Chunk> chunks;
+    std::vector<DecChunk> chunks;
     long a1 = -1, a2 = -1;                                             // the last two anchor frames in front of the chunk
     for (size_t f0 = 0; f0 < nf; f0 += B) {
         const size_t nb = std::min(B, nf - f0), p0 = fcp[f0], p1 = fcp[f0 + nb];
-        Chunk C;
+        DecChunk C;
         C.c1 = a1;
         std::vector<long> step(p1 - p0, -1), fstep(nb, -1);
         long deepest = -1;
@@ -448,7 +373,7 @@ void dec_f_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_
         for (long j = 0; j <= deepest; ++j) {
             const size_t first = at;
             for (size_t p = p0; p < p1; ++p) if (step[p - p0] == j) h_list[at++] = (uint32_t)p;
-            C.steps.push_back(Launch{first, at - first});
+            C.steps.push_back(DecLaunch{first, at - first});
         }
         C.b.off = at;
         for (size_t p = p0; p < p1; ++p) if (type_of(p) == 3u) h_list[at++] = (uint32_t)p;
@@ -472,7 +397,7 @@ void dec_f_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_
     HIPCHK(hipGetLastError());
     for (size_t f0 = 0, c = 0; f0 < nf; f0 += B, ++c) {
         const size_t nb = std::min(B, nf - f0), p0 = fcp[f0], np = fcp[f0 + nb] - p0;
-        const Chunk &C = chunks[c];
+        const DecChunk &C = chunks[c];
         HIPCHK(hipMemsetAsync(e->d_dec_lv.p, 0, nb * mbs * 768, s));
         const size_t total = h_sl[p0 + np] - h_sl[p0];                 // (every picture the plan accepted has a slice)
         if (total) {
@@ -484,13 +409,13 @@ void dec_f_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_
         }
         k_df_judge<<<1, 1, 0, s>>>(d_st);
         HIPCHK(hipGetLastError());
-        auto recon = [&](const Launch &l) {
+        auto recon = [&](const DecLaunch &l) {
             if (!l.count) return;
             k_df_recon<<<dim3((unsigned)mbs, (unsigned)l.count), 64, 0, s>>>(d_st, e->d_dec_list.p + l.off, (uint32_t)f0, (uint32_t)C.c1, mats, pics, bp, d_mb, e->d_dec_dc.p,
                                                                             e->d_dec_lv.p, e->d_dec_buf.p, psz);
             HIPCHK(hipGetLastError());
         };
-        for (const Launch &l : C.steps) recon(l);
+        for (const DecLaunch &l : C.steps) recon(l);
         recon(C.b);                                                    // every B picture of the chunk at once: its anchor frames are done
         const size_t units = (R.frame_bytes + 15) / 16 + 1;
         k_df_out<<<dim3((unsigned)std::min<size_t>((units + kDecThreads - 1) / kDecThreads, 1024), (unsigned)np), kDecThreads, 0, s>>>(d_st, bp, e->d_dec_buf.p, psz,

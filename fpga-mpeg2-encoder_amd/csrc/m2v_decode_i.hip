@@ -1,8 +1,7 @@
 // m2v_decode_i.hip — interlaced frame pictures for m2v_decode_device (option "decode_interlaced" = 1 on top of "decode_syntax" =
 // M2V_SYNTAX_MAIN, with "decode_b_pictures" 0 or 1).  Modelled on m2v_decode_b.hip: m2v_decode.hip keeps the scan; this unit holds the
-// plan and everything behind the plan's wait, in kernels of its own so that those of the other three units come out of the compiler
-// exactly as they did.  decoder.decode_main(interlaced=True) is the definition; every function that decides a bit or a sample is an il_
-// (or bp_ / main_) function of m2v_decode_kernels.hpp.
+// plan and everything behind the plan's wait.  decoder.decode_main(interlaced=True) is the definition; every function that decides a bit
+// or a sample is an il_ (or bp_ / main_) function of m2v_decode_kernels.hpp.
 //
 //   k_di_plan    k_db_plan with dec::il_first (the macroblock rows of a sequence that is not progressive), dec::il_event (a coding
 //                extension may say frame_pred_frame_dct 0) and a flag for whether picture_coding_type 3 is accepted ("decode_b_pictures").
@@ -12,8 +11,9 @@
 //   k_di_recon   one wavefront per macroblock with k_db_recon's lane mapping.  A lane's luma row y of a field-based macroblock takes
 //                vector y & 1 and its field select and reads reference rows of one parity at twice the stride (dec::il_predict); the
 //                residual of a field-DCT macroblock comes from block (y & 1) * 2 + (x >> 3), row y >> 1.  Chroma the same with four
-//                lines per field; its blocks are frame blocks.
-//   k_di_out     k_db_out (a copy: a kernel is launched from the unit that holds it).
+//                lines per field; its blocks are frame blocks.  The body is imb_recon (m2v_decode_device.hpp), which the units of the
+//                later options and the main-syntax batch entries call too.
+//   k_di_out     as k_db_out: the shared output loop (out_picture) for the picture's frame at its display index.
 //
 // The chunk's buffer, the steps of the anchors and the single launch for a chunk's B pictures are m2v_decode_b.hip's; a stream without
 // B pictures has display order = coded order there already.
@@ -22,8 +22,6 @@
 static_assert(sizeof(dec::IMb) == 32, "the interlaced record is two of the module's");
 
 namespace m2v {
-
-constexpr uint32_t kNoPic = 0xFFFFFFFFu;
 
 __global__ __launch_bounds__(kDecThreads) void k_di_plan(const uint8_t *__restrict__ es, unsigned long long n, const unsigned long long *__restrict__ ev, DecState *st,
                                                          DecPic *__restrict__ pics, uint32_t pic_cap, uint8_t *h_types, unsigned long long cap, int probe,
@@ -151,19 +149,6 @@ __global__ __launch_bounds__(kDecThreads) void k_di_plan(const uint8_t *__restri
     *h_rec = r;
 }
 
-struct DecISink {
-    dec::IMb *mb_;
-    int32_t *dc_;
-    int16_t *lv_;
-    M2V_HD void mb(int col, const dec::IMb &m, const int32_t (&dc)[6])
-    {
-        mb_[col] = m;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) dc_[col * 6 + k] = dc[k];
-    }
-    M2V_HD void level(int col, int blk, uint32_t i, int32_t l) { lv_[(col * 6 + blk) * 64 + (int)i] = (int16_t)l; }
-};
-
 // as k_db_slices: pictures [p0, p0 + np) of any type, one slice per lane, the earliest refused slice lowers st->err
 __global__ __launch_bounds__(64) void k_di_slices(const uint8_t *__restrict__ es, unsigned long long n, const unsigned long long *__restrict__ ev, DecState *st,
                                                   const DecPic *__restrict__ pics, const DecBPic *__restrict__ bp, uint32_t p0, uint32_t np, dec::IMb *mb,
@@ -179,7 +164,7 @@ __global__ __launch_bounds__(64) void k_di_slices(const uint8_t *__restrict__ es
     if (i >= nev) return;                                              // (the plan accepted the picture: its slices are there)
     const unsigned long long start = dec::ev_pos(ev[i]), end = i + 1 < nev ? dec::ev_pos(ev[i + 1]) : n;
     const size_t first = ((size_t)pic * mbh + row) * mbw;
-    DecISink sink{mb + first, dc + first * 6, lv + first * 384};
+    IMbSink sink{mb + first, dc + first * 6, lv + first * 384};
     if (!dec::il_slice(es, start, end, P.type, dec::il_params_unpack(Q.params), (int)mbw, (int)mbh, (int)row, sink)) atomicMin(&st->err, start);
 }
 
@@ -187,9 +172,6 @@ __global__ void k_di_judge(DecState *st)
 {
     if (st->status == dec::kOk && st->err != dec::kNone) st->status = dec::kSyntax;
 }
-
-// the chunk's slot of the picture with coded index r, as m2v_decode_b.hip's
-__device__ inline uint32_t di_slot(uint32_t r, uint32_t p0, uint32_t c1) { return r == kNoPic ? 0u : r >= p0 ? 2u + (r - p0) : r == c1 ? 1u : 0u; }
 
 // as k_db_recon: grid = (macroblocks, pictures of the launch); list: their coded indices, all of chunk [p0, ...).  Every read of a
 // reference lies inside its picture: the slice walk refused the slice otherwise (dec::il_inside), and a refused slice stops the call
@@ -203,73 +185,10 @@ __global__ __launch_bounds__(64) void k_di_recon(const DecState *__restrict__ st
     const uint32_t mbw = st->mbw, mbh = st->mbh, mbs = mbw * mbh, W = 16u * mbw, H = 16u * mbh, CW = W / 2u;
     const uint32_t k = blockIdx.x, l = threadIdx.x, gp = list[blockIdx.y], pic = gp - p0;
     const DecBPic Q = bp[gp];
-    const dec::PicParams pp = dec::params_unpack(Q.params);
     const size_t at = (size_t)pic * mbs + k;
-    const dec::IMb m = mb[at];
-    const uint32_t col = k % mbw, row = k / mbw;
-    uint8_t *cur = buf + (size_t)(pic + 2u) * psz;
-    const uint8_t *fwd = buf + (size_t)di_slot(Q.fwd, p0, c1) * psz, *bwd = buf + (size_t)di_slot(Q.bwd, p0, c1) * psz;
-    const bool intra = m.intra != 0;
-    const int32_t qscale = dec::main_scale(m.qcode, pp.qst), weight = mats[(intra ? 0u : 64u) + l];
-#pragma unroll
-    for (int blk = 0; blk < 6; ++blk) {
-        if (!((m.cbp >> (5 - blk)) & 1)) continue;                     // (uniform: the whole wavefront works on one macroblock)
-        int32_t f = intra && l == 0 ? dec::main_dequant_dc(dc[at * 6 + blk], pp.prec) : dec::main_dequant(lv[(at * 6 + blk) * 64 + l], weight, intra, qscale);
-        const int odd = __popcll(__ballot(f & 1)) & 1;
-        if (!odd && l == 63) f = dec::mismatch(f);
-        F[blk][l] = f;
-    }
-    __syncthreads();
-    const int blk8 = (int)(l >> 3), r8 = (int)(l & 7u);
-    const bool mine = l < 48 && ((m.cbp >> (5 - blk8)) & 1);
-    if (mine) {
-        int32_t a[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] = F[blk8][r8 * 8 + j];
-        dec::idct_1d(a, true, dec::kIso);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) F[blk8][r8 * 8 + j] = a[j];
-    }
-    __syncthreads();
-    if (mine) {
-        int32_t a[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] = F[blk8][j * 8 + r8];
-        dec::idct_1d(a, false, dec::kIso);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) F[blk8][j * 8 + r8] = a[j];
-    }
-    __syncthreads();
-    {   // luma: four samples of one row per lane; the row's block and the row inside it through the field-DCT map
-        const uint32_t y = l >> 2, x0 = (l & 3u) * 4u, blk = dec::il_luma_block(x0, y, m.dct_type), brow = dec::il_luma_row(y, m.dct_type);
-        const bool coded = (m.cbp >> (5 - blk)) & 1;
-        const int px = (int)(16u * col + x0), py = (int)(16u * row + y);
-        uint32_t v = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int32_t pred = intra ? 128 : dec::il_predict(fwd, bwd, (int)W, px + j, py, m, false);
-            const int32_t res = coded ? F[blk][brow * 8u + ((x0 + j) & 7u)] : 0;
-            v |= (uint32_t)dec::clip255(pred + res) << (8 * j);
-        }
-        *(uint32_t *)(cur + (size_t)(16u * row + y) * W + 16u * col + x0) = v;
-    }
-    {   // chroma: two samples per lane, U in the first half of the wavefront; frame blocks always
-        const uint32_t pl = l >> 5, y = (l >> 2) & 7u, x0 = (l & 3u) * 2u;
-        const bool coded = (m.cbp >> (1 - pl)) & 1;
-        const size_t plane = (size_t)W * H + (size_t)pl * CW * (H / 2u);
-        const int px = (int)(8u * col + x0), py = (int)(8u * row + y);
-        uint32_t v = 0;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int32_t pred = intra ? 128 : dec::il_predict(fwd + plane, bwd + plane, (int)CW, px + j, py, m, true);
-            const int32_t res = coded ? F[4u + pl][y * 8u + x0 + j] : 0;
-            v |= (uint32_t)dec::clip255(pred + res) << (8 * j);
-        }
-        *(uint16_t *)(cur + plane + (size_t)(8u * row + y) * CW + 8u * col + x0) = (uint16_t)v;
-    }
+    imb_recon(F, mb[at], dec::params_unpack(Q.params), mats, dc, lv, at, buf + (size_t)(pic + 2u) * psz, buf + (size_t)slot(Q.fwd, p0, c1) * psz,
+              buf + (size_t)slot(Q.bwd, p0, c1) * psz, W, H, CW, k % mbw, k / mbw, l);
 }
-
-typedef uint32_t di_store_t __attribute__((ext_vector_type(4)));
 
 // picture blockIdx.y of chunk [p0, p0 + np) into dst at its display index: bytes [display * fb, (display + 1) * fb) of the output
 __global__ __launch_bounds__(kDecThreads) void k_di_out(const DecState *__restrict__ st, const DecBPic *__restrict__ bp, const uint8_t *__restrict__ buf, size_t psz,
@@ -279,30 +198,8 @@ __global__ __launch_bounds__(kDecThreads) void k_di_out(const DecState *__restri
     const uint32_t w = st->width, h = st->height, W = 16u * st->mbw, H = 16u * st->mbh;
     const uint32_t d = bp[p0 + blockIdx.y].display;
     if (d >= st->npics) return;                                        // (an accepted stream's display indices are a permutation)
-    const uint8_t *pic = buf + (size_t)(blockIdx.y + 2u) * psz;
-    const unsigned long long fb = st->frame_bytes, lo = (unsigned long long)d * fb, hi = lo + fb;
-    const unsigned long long lead = (unsigned long long)(uintptr_t)dst & 15ull;
-    const unsigned long long u0 = (lo + lead) >> 4, u1 = (hi + lead + 15ull) >> 4;
-    for (unsigned long long g = u0 + (unsigned long long)blockIdx.x * kDecThreads + threadIdx.x; g < u1; g += (unsigned long long)gridDim.x * kDecThreads) {
-        const long long o0 = (long long)(g << 4) - (long long)lead;
-        const int k0 = o0 < (long long)lo ? (int)((long long)lo - o0) : 0, k1 = (long long)hi - o0 < 16 ? (int)((long long)hi - o0) : 16;
-        if (k0 >= k1) continue;
-        uint32_t q = (uint32_t)((unsigned long long)(o0 + k0) - lo);
-        dec::OutAt at = dec::out_locate(q, w, h, layout);
-        uint32_t v[4] = {0, 0, 0, 0};
-        for (int k = k0; k < k1; ++k) {
-            v[k >> 2] |= (uint32_t)dec::pic_sample(pic, W, H, at) << (8 * (k & 3));
-            if (k + 1 == k1) break;
-            ++q;
-            if (at.run > 1) dec::out_step(at, layout);
-            else at = dec::out_locate(q, w, h, layout);
-        }
-        if (k0 == 0 && k1 == 16) {
-            *(__attribute__((address_space(1))) di_store_t *)(dst + o0) = di_store_t{v[0], v[1], v[2], v[3]};
-        } else {
-            for (int k = k0; k < k1; ++k) dst[o0 + k] = (uint8_t)(v[k >> 2] >> (8 * (k & 3)));
-        }
-    }
+    const unsigned long long fb = st->frame_bytes, lo = (unsigned long long)d * fb;
+    out_picture(buf + (size_t)(blockIdx.y + 2u) * psz, w, h, W, H, lo, lo + fb, dst, layout, kDecThreads);
 }
 
 __global__ void k_di_finish(const DecState *st, m2v_decode_stat *h_rec)
@@ -329,41 +226,7 @@ void dec_i_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_
     e->d_dec_lv.ensure(B * mbs * 384);
     e->d_dec_buf.ensure((B + 2) * psz);
     e->d_dec_list.ensure(np);
-    // every chunk's anchors ordered by their step inside the chunk - a chain starts at its I picture, or at the chunk's first anchor -,
-    // then its B pictures; and what the chunk leaves in slots 0 and 1 for the next
-    struct Launch { size_t off, count; };
-    struct Chunk { std::vector<Launch> steps; Launch b; long c1, carry0, carry1; };      // carry: the chunk's slot to copy into slot 0 / 1 (-1: nothing)
-    std::vector<Chunk> chunks;
-    long a1 = -1, a2 = -1;                                             // the last two anchors in front of the chunk, coded indices
-    for (size_t p0 = 0; p0 < np; p0 += B) {
-        const size_t nb = std::min(B, np - p0);
-        Chunk C;
-        C.c1 = a1;
-        std::vector<long> step(nb, -1);
-        long deepest = -1, prev = -1;
-        for (size_t k = 0; k < nb; ++k) {
-            if (types[p0 + k] == 3) continue;
-            step[k] = prev >= 0 && types[p0 + k] != 1 ? step[prev] + 1 : 0;
-            deepest = std::max(deepest, step[k]);
-            prev = (long)k;
-        }
-        size_t at = p0;
-        for (long j = 0; j <= deepest; ++j) {
-            const size_t first = at;
-            for (size_t k = 0; k < nb; ++k) if (step[k] == j) h_list[at++] = (uint32_t)(p0 + k);
-            C.steps.push_back(Launch{first, at - first});
-        }
-        C.b.off = at;
-        for (size_t k = 0; k < nb; ++k) if (types[p0 + k] == 3) h_list[at++] = (uint32_t)(p0 + k);
-        C.b.count = at - C.b.off;
-        auto slot = [&](long r) { return r >= (long)p0 ? 2 + (r - (long)p0) : r == C.c1 ? 1L : 0L; };
-        long n1 = a1, n2 = a2;
-        for (size_t k = 0; k < nb; ++k) if (types[p0 + k] != 3) { n2 = n1; n1 = (long)(p0 + k); }
-        C.carry0 = n2 >= 0 && slot(n2) != 0 ? slot(n2) : -1;
-        C.carry1 = n1 >= 0 && slot(n1) != 1 ? slot(n1) : -1;
-        a1 = n1; a2 = n2;
-        chunks.push_back(C);
-    }
+    const std::vector<DecChunk> chunks = dec_chunk_schedule(types, np, B, h_list);
     auto *d_st = (DecState *)e->d_dec_st.p;
     auto *d_mb = (dec::IMb *)e->d_dec_mb.p;
     const uint8_t *mats = e->d_dec_main.p;
@@ -371,20 +234,20 @@ void dec_i_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_
     HIPCHK(hipMemcpyAsync(e->d_dec_list.p, h_list, np * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     for (size_t p0 = 0, c = 0; p0 < np; p0 += B, ++c) {
         const size_t nb = std::min(B, np - p0);
-        const Chunk &C = chunks[c];
+        const DecChunk &C = chunks[c];
         HIPCHK(hipMemsetAsync(e->d_dec_lv.p, 0, nb * mbs * 768, s));
         k_di_slices<<<(unsigned)((nb * mbh + 63) / 64), 64, 0, s>>>(es, n, e->d_dec_ev.p, d_st, (const DecPic *)e->d_dec_pics.p, bp, (uint32_t)p0, (uint32_t)nb, d_mb,
                                                                     e->d_dec_dc.p, e->d_dec_lv.p);
         HIPCHK(hipGetLastError());
         k_di_judge<<<1, 1, 0, s>>>(d_st);
         HIPCHK(hipGetLastError());
-        auto recon = [&](const Launch &l) {
+        auto recon = [&](const DecLaunch &l) {
             if (!l.count) return;
             k_di_recon<<<dim3((unsigned)mbs, (unsigned)l.count), 64, 0, s>>>(d_st, e->d_dec_list.p + l.off, (uint32_t)p0, (uint32_t)C.c1, mats, bp, d_mb, e->d_dec_dc.p,
                                                                             e->d_dec_lv.p, e->d_dec_buf.p, psz);
             HIPCHK(hipGetLastError());
         };
-        for (const Launch &l : C.steps) recon(l);
+        for (const DecLaunch &l : C.steps) recon(l);
         recon(C.b);                                                    // every B picture of the chunk at once: its anchors are done
         const size_t units = (R.frame_bytes + 15) / 16 + 1;
         k_di_out<<<dim3((unsigned)std::min<size_t>((units + kDecThreads - 1) / kDecThreads, 1024), (unsigned)nb), kDecThreads, 0, s>>>(d_st, bp, e->d_dec_buf.p, psz,

@@ -1,9 +1,14 @@
-// m2v_decode_state.hpp — what the three translation units of m2v_decode_device share: the call's state and picture table on the device
-// (m2v_decode.hip: the module syntax and everything syntax-blind), the launchers of the main syntax's three kernels
-// (m2v_decode_main.hip) and those of the B-picture path (m2v_decode_b.hip).  The kernels of one unit are not touched by a change in another.
+// m2v_decode_state.hpp — what the translation units of the decoder share on the host side: the call's state and picture table on the
+// device (m2v_decode.hip: the module syntax and everything syntax-blind), every option's picture table and the plan / chunk functions
+// m2v_decode.hip dispatches to (m2v_decode_main.hip, _b, _i, _x, _f, _j), and - at the end - the batch entries' table of streams with
+// the launchers of their one scan and of the main-syntax batch entries' first pass, output kernel and report.  The device code the units
+// share is m2v_decode_device.hpp's, the chunk schedule m2v_decode_chunks.hpp's; a kernel lives in one unit and is launched from there.
 #pragma once
+#include <functional>
 #include "m2v_host.hpp"
 #include "m2v_decode_kernels.hpp"
+#include "m2v_decode_device.hpp"
+#include "m2v_decode_chunks.hpp"
 
 namespace m2v {
 
@@ -57,18 +62,15 @@ void dec_i_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_
 // holds the matrix table (128 bytes a picture) and the spans of the chunk's slices
 struct DecXPic { uint32_t slice0, params, display, fwd, bwd, nslices, sbase, mi, mn; };      // params: dec::il_params_pack
 
+// tools: Table B-15, concealment motion vectors, dual prime (option "decode_mb_tools" on top of "decode_extended").  The plan is then
+// dec_t_plan (m2v_decode_t.hip) with the same tables: DecXPic::params carries dec::t_params_pack's three flags above bit 20, and a P
+// picture's bwd is its fwd - a dual-prime macroblock's second prediction reads the same reference
 void dec_x_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long long *ev, DecState *st, DecPic *pics, uint32_t pic_cap, uint8_t *h_types,
                 unsigned long long cap, int probe, m2v_decode_stat *h_rec, uint8_t *d_main, int b_pictures, int interlaced, uint32_t *h_mbh, uint32_t *h_sl);
-void dec_x_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_t *dst, int layout, const m2v_decode_stat &R, size_t mbh, size_t B,
-                  const uint8_t *types, uint32_t *h_list, const uint32_t *h_sl, m2v_decode_stat *h_rec);
-
-// Table B-15, concealment motion vectors, dual prime (option "decode_mb_tools" on top of "decode_extended"; m2v_decode_t.hip): the tables
-// and buffers are those of dec_x_plan / dec_x_chunks.  DecXPic::params carries dec::t_params_pack's three flags above bit 20, and a P
-// picture's bwd is its fwd: a dual-prime macroblock's second prediction reads the same reference
 void dec_t_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long long *ev, DecState *st, DecPic *pics, uint32_t pic_cap, uint8_t *h_types,
                 unsigned long long cap, int probe, m2v_decode_stat *h_rec, uint8_t *d_main, int b_pictures, int interlaced, uint32_t *h_mbh, uint32_t *h_sl);
-void dec_t_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_t *dst, int layout, const m2v_decode_stat &R, size_t mbh, size_t B,
-                  const uint8_t *types, uint32_t *h_list, const uint32_t *h_sl, m2v_decode_stat *h_rec);
+void dec_x_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_t *dst, int layout, const m2v_decode_stat &R, size_t mbh, size_t B,
+                  const uint8_t *types, bool tools, uint32_t *h_list, const uint32_t *h_sl, m2v_decode_stat *h_rec);
 
 // Field pictures (option "decode_field_pictures" on top of "decode_interlaced", "decode_extended" and "decode_mb_tools";
 // m2v_decode_f.hip): the table behind the matrices holds one DecFPic a CODED PICTURE - a frame picture or one field -, DecXPic's fields
@@ -92,5 +94,33 @@ constexpr uint32_t kDecJoinWord = 2;               // h_mbh[kDecJoinWord .. kDec
 static_assert(kDecPlanWords + 4 * (kDecJoinWord + 6) <= 128, "the join record ends where the types begin");
 void dec_j_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long long *ev, DecState *st, DecPic *pics, uint32_t pic_cap, uint8_t *h_types,
                 unsigned long long cap, int probe, m2v_decode_stat *h_rec, uint8_t *d_main, int b_pictures, int join, uint32_t *h_mbh, uint32_t *h_sl);
+
+// The batch entries (m2v_decode_streams.hip, m2v_decode_streams_main.hip, m2v_decode_streams_ex.hip): the table of streams, a stream's
+// state on the device and its verdict in pinned memory are the same for all three, and so are the kernels that do not read the syntax.
+// They live in m2v_decode_streams.hip
+struct DsIn { unsigned long long off, n, ev_base, pic_base; uint32_t tile0, ntiles, ev_cap, pic_cap; };
+struct DsState { unsigned long long err, last_nz; uint32_t nev; int32_t status; uint32_t mbw, mbh; };
+struct DsVerdict { unsigned long long err; int32_t status; uint32_t pad; };
+
+inline size_t ds_up64(size_t v) { return (v + 63) & ~(size_t)63; }
+// the counts of every tile, the prefix sum per stream, the events (k_ds_scan<false>, k_ds_tiles, k_ds_scan<true>); tiles 0: nothing
+void ds_scan(hipStream_t s, const uint8_t *es, const DsIn *d_in, size_t n, size_t tiles, DsState *d_st, uint32_t *d_tiles, unsigned long long *d_ev);
+void ds_judge(hipStream_t s, DsState *d_st, size_t n);                                  // k_ds_judge, a lane per stream
+void ds_finish(hipStream_t s, const DsState *d_st, size_t n, DsVerdict *h_v);           // k_ds_finish
+// every stream's record into e->ds_q; v: the verdicts behind the last chunk, or nullptr where nothing was decoded
+void ds_report(m2v_enc *e, const uint64_t *off, size_t n, const std::vector<uint64_t> &out_offset, const std::vector<uint8_t> &overflow,
+               const std::vector<m2v_decode_stat> &rec, const DsVerdict *v);
+
+// The two main-syntax batch entries share their first pass and their output kernel (m2v_decode_streams_main.hip).  ds_main_first: the
+// layout of e->h_ds, the limits (`entry` names the caller in the messages), the uploads, the scan, the unit's plan kernel through `plan`,
+// the call's one wait, and the second run where a stream's event list was too small.  pic_bytes: a picture's entry in e->d_dec_pics;
+// slices: the plan leaves every picture's slice events at h_sl (else h_sl is nullptr and nsl stays empty).  M2V_OK or M2V_E_PARAM
+struct DsMainFirst { std::vector<m2v_decode_stat> rec; std::vector<uint8_t> types; std::vector<uint32_t> mbh, nsl; std::vector<size_t> pic_base; };
+typedef std::function<void(const DsIn *d_in, DsState *d_st, uint8_t *h_types, uint32_t *h_sl, m2v_decode_stat *h_rec, uint32_t *h_mbh)> DsPlanLaunch;
+int ds_main_first(m2v_enc *e, hipStream_t s, const char *entry, const uint8_t *es, const uint64_t *off, const uint64_t *bytes, size_t n, size_t pic_bytes,
+                  bool slices, const DsPlanLaunch &plan, DsMainFirst &out);
+namespace dec { struct MainChunkPic; }
+// k_dsm_out over the `count` pictures of the chunk's table, 65535 a launch; most_units: the 16-byte units of its largest frame
+void dsm_out(hipStream_t s, const DsState *d_st, const dec::MainChunkPic *tab, size_t count, uint32_t most_units, const uint8_t *buf, uint8_t *dst, int layout);
 
 }  // namespace m2v

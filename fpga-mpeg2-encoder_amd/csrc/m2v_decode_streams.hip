@@ -1,7 +1,8 @@
 // m2v_decode_streams.hip — a batch of MPEG-2 I / P streams back to 4:2:0 frames in one call (include/m2v_mi355x.h:
 // m2v_decode_streams_device): the pipeline of m2v_decode.hip over a table of streams, of any sizes, each judged alone.  Every function
-// that decides a bit or a sample is the one m2v_decode.hip uses (m2v_decode_kernels.hpp); the kernels here are new loops over them, and
-// m2v_decode_device keeps its own (m2v_decode.hip is untouched: its records, bytes and launches per chunk stay what they were).
+// that decides a bit or a sample is the one m2v_decode.hip uses (m2v_decode_kernels.hpp); the kernels here are loops of their own over
+// them.  The scan, the judge, the finish and the report do not read the syntax: the two main-syntax batch units launch them through
+// ds_scan, ds_judge, ds_finish and ds_report (m2v_decode_state.hpp).
 //
 //   k_ds_scan     the tiles of all streams in one grid; a tile belongs to one stream (found by its number in the streams' table, as
 //                 m2v_demux.hip finds a workgroup's container), and its loads are clamped to the segment: a start code in a gap, or one
@@ -21,8 +22,7 @@
 //   k_ds_out      one lane per 16 destination bytes of the chunk's range, one aligned store; a unit that holds a byte outside the range or
 //                 of a refused stream's room goes byte by byte for the part that may be written (dec::streams_out_locate).
 //   k_ds_finish   every stream's verdict to pinned memory, behind the last chunk.  Two host waits, whatever the number of streams.
-#include "m2v_host.hpp"
-#include "m2v_decode_kernels.hpp"
+#include "m2v_decode_state.hpp"
 #include "m2v_decode_streams.hpp"
 
 static_assert(sizeof(m2v_decode_stream_stat) == 88, "the record of include/m2v_mi355x.h is 88 bytes");
@@ -34,10 +34,7 @@ constexpr int kDsThreads = 256;
 static_assert(dec::kScanTile == (uint32_t)kDsThreads * 16u, "a tile is one pass of a block");
 typedef unsigned long long ull;
 
-struct DsIn { ull off, n, ev_base, pic_base; uint32_t tile0, ntiles, ev_cap, pic_cap; };
-struct DsState { ull err, last_nz; uint32_t nev; int32_t status; uint32_t mbw, mbh; };
 struct DsPic { uint32_t ev, type; };
-struct DsVerdict { ull err; int32_t status; uint32_t pad; };
 
 // the stream tile t belongs to: the last one whose first tile is not behind t (a stream without tiles shares its number with the next)
 __device__ inline uint32_t ds_stream_of(const DsIn *__restrict__ in, uint32_t n, uint32_t t)
@@ -388,6 +385,44 @@ __global__ void k_ds_finish(const DsState *sts, uint32_t n, DsVerdict *h_v)
     if (b < n) h_v[b] = DsVerdict{sts[b].err, sts[b].status, 0};
 }
 
+void ds_scan(hipStream_t s, const uint8_t *es, const DsIn *d_in, size_t n, size_t tiles, DsState *d_st, uint32_t *d_tiles, ull *d_ev)
+{
+    if (!tiles) return;
+    const unsigned gx = (unsigned)std::min<size_t>(tiles, 4096);
+    k_ds_scan<false><<<gx, kDsThreads, 0, s>>>(es, d_in, (uint32_t)n, (uint32_t)tiles, d_st, d_tiles, d_ev);
+    HIPCHK(hipGetLastError());
+    k_ds_tiles<<<(unsigned)n, kDsThreads, 0, s>>>(d_in, d_tiles, d_st);
+    HIPCHK(hipGetLastError());
+    k_ds_scan<true><<<gx, kDsThreads, 0, s>>>(es, d_in, (uint32_t)n, (uint32_t)tiles, d_st, d_tiles, d_ev);
+    HIPCHK(hipGetLastError());
+}
+
+void ds_judge(hipStream_t s, DsState *d_st, size_t n)
+{
+    k_ds_judge<<<(unsigned)((n + 63) / 64), 64, 0, s>>>(d_st, (uint32_t)n);
+    HIPCHK(hipGetLastError());
+}
+
+void ds_finish(hipStream_t s, const DsState *d_st, size_t n, DsVerdict *h_v)
+{
+    k_ds_finish<<<(unsigned)((n + 63) / 64), 64, 0, s>>>(d_st, (uint32_t)n, h_v);
+    HIPCHK(hipGetLastError());
+}
+
+void ds_report(m2v_enc *e, const uint64_t *off, size_t n, const std::vector<uint64_t> &out_offset, const std::vector<uint8_t> &overflow,
+               const std::vector<m2v_decode_stat> &rec, const DsVerdict *v)
+{
+    for (size_t b = 0; b < n; ++b) {
+        m2v_decode_stream_stat r{off[b], out_offset[b], rec[b]};
+        if (r.rec.status == M2V_DEC_OK) {
+            if (overflow[b]) r.rec.status = M2V_DEC_OVERFLOW;
+            else if (v && v[b].status != dec::kOk) { r.rec.status = v[b].status; r.rec.err_offset = v[b].err; }
+            else r.rec.out_bytes = r.rec.frame_bytes * r.rec.pictures;
+        }
+        e->ds_q.push(&r, &r + 1);
+    }
+}
+
 void ds_release(m2v_enc *e)
 {
     e->d_ds_in.release(); e->d_ds_tab.release();
@@ -399,8 +434,6 @@ void ds_release(m2v_enc *e)
 }  // namespace m2v
 
 struct DecodeStreamsArgs { const uint8_t *es; const uint64_t *off, *bytes; size_t n; uint8_t *dst; size_t cap; int layout, mode; hipStream_t s; };
-
-static size_t up64(size_t v) { return (v + 63) & ~(size_t)63; }
 
 static int decode_streams_impl(m2v_enc *e, void *argp)
 {
@@ -420,7 +453,7 @@ static int decode_streams_impl(m2v_enc *e, void *argp)
     timer_break(e);
     for (int run = 0; run < 2; ++run) {
         size_t tiles = 0, evs = 0, pics = 0;
-        const size_t in_bytes = up64(n * sizeof(DsIn)), st_bytes = up64(n * sizeof(DsState)), rec_bytes = up64(n * sizeof(m2v_decode_stat));
+        const size_t in_bytes = ds_up64(n * sizeof(DsIn)), st_bytes = ds_up64(n * sizeof(DsState)), rec_bytes = ds_up64(n * sizeof(m2v_decode_stat));
         for (size_t b = 0; b < n; ++b) pics += ev_cap[b] / 3 + 2;
         ensure_pinned(e->h_ds, e->h_ds_cap, in_bytes + st_bytes + rec_bytes + pics + 64);
         auto *h_in = (DsIn *)e->h_ds;
@@ -447,15 +480,7 @@ static int decode_streams_impl(m2v_enc *e, void *argp)
         auto *d_st = (DsState *)e->d_dec_st.p;
         HIPCHK(hipMemcpyAsync(e->d_ds_in.p, h_in, in_bytes, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(d_st, h_st, st_bytes, hipMemcpyHostToDevice, s));
-        if (tiles) {
-            const unsigned gx = (unsigned)std::min<size_t>(tiles, 4096);
-            k_ds_scan<false><<<gx, kDsThreads, 0, s>>>(a->es, d_in, (uint32_t)n, (uint32_t)tiles, d_st, e->d_dec_tiles.p, e->d_dec_ev.p);
-            HIPCHK(hipGetLastError());
-            k_ds_tiles<<<(unsigned)n, kDsThreads, 0, s>>>(d_in, e->d_dec_tiles.p, d_st);
-            HIPCHK(hipGetLastError());
-            k_ds_scan<true><<<gx, kDsThreads, 0, s>>>(a->es, d_in, (uint32_t)n, (uint32_t)tiles, d_st, e->d_dec_tiles.p, e->d_dec_ev.p);
-            HIPCHK(hipGetLastError());
-        }
+        ds_scan(s, a->es, d_in, n, tiles, d_st, e->d_dec_tiles.p, e->d_dec_ev.p);
         k_ds_plan<<<(unsigned)n, kDsThreads, 0, s>>>(a->es, d_in, e->d_dec_ev.p, d_st, (DsPic *)e->d_dec_pics.p, h_types, h_rec);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s));                              // the call's one wait for the plan: every stream's pictures, size, types
@@ -473,21 +498,10 @@ static int decode_streams_impl(m2v_enc *e, void *argp)
         info[b] = dec::StreamInfo{rec[b].status, rec[b].pictures, rec[b].width, rec[b].height, types.data() + pic_base[b]};
     }
     const dec::StreamsPlan P = dec::plan_streams(info.data(), n, a->cap, a->dst == nullptr, e->decode_batch);
-    auto report = [&](const DsVerdict *v) {
-        for (size_t b = 0; b < n; ++b) {
-            m2v_decode_stream_stat r{a->off[b], P.out_offset[b], rec[b]};
-            if (r.rec.status == M2V_DEC_OK) {
-                if (P.overflow[b]) r.rec.status = M2V_DEC_OVERFLOW;
-                else if (v && v[b].status != dec::kOk) { r.rec.status = v[b].status; r.rec.err_offset = v[b].err; }
-                else r.rec.out_bytes = r.rec.frame_bytes * r.rec.pictures;
-            }
-            e->ds_q.push(&r, &r + 1);
-        }
-    };
-    if (!a->dst || P.pics.empty()) { report(nullptr); return M2V_OK; }
+    if (!a->dst || P.pics.empty()) { ds_report(e, a->off, n, P.out_offset, P.overflow, rec, nullptr); return M2V_OK; }
     // the tables: every chunk's pictures, the cut streams' pictures, the step lists; the verdicts come back behind them
-    const size_t tab_bytes = up64(P.pics.size() * sizeof(dec::ChunkPic)), pre_bytes = up64(P.pre.size() * sizeof(dec::ChunkPic)),
-                 list_bytes = up64(P.list.size() * sizeof(uint32_t));
+    const size_t tab_bytes = ds_up64(P.pics.size() * sizeof(dec::ChunkPic)), pre_bytes = ds_up64(P.pre.size() * sizeof(dec::ChunkPic)),
+                 list_bytes = ds_up64(P.list.size() * sizeof(uint32_t));
     ensure_pinned(e->h_ds_tab, e->h_ds_tab_cap, tab_bytes + pre_bytes + list_bytes + n * sizeof(DsVerdict) + 64);
     memcpy(e->h_ds_tab, P.pics.data(), P.pics.size() * sizeof(dec::ChunkPic));
     if (!P.pre.empty()) memcpy(e->h_ds_tab + tab_bytes, P.pre.data(), P.pre.size() * sizeof(dec::ChunkPic));
@@ -508,13 +522,11 @@ static int decode_streams_impl(m2v_enc *e, void *argp)
     auto *d_tab = (const dec::ChunkPic *)e->d_ds_tab.p;
     auto *d_pre = (const dec::ChunkPic *)(e->d_ds_tab.p + tab_bytes);
     auto *d_list = (const uint32_t *)(e->d_ds_tab.p + tab_bytes + pre_bytes);
-    const unsigned gj = (unsigned)((n + 63) / 64);
     if (P.pre_slices) {
         k_ds_slices<false><<<(P.pre_slices + 63u) / 64u, 64, 0, s>>>(a->es, d_in, e->d_dec_ev.p, d_st, d_pics, d_pre, (uint32_t)P.pre.size(), P.pre_slices, a->mode,
                                                                    nullptr, nullptr, nullptr);
         HIPCHK(hipGetLastError());
-        k_ds_judge<<<gj, 64, 0, s>>>(d_st, (uint32_t)n);
-        HIPCHK(hipGetLastError());
+        ds_judge(s, d_st, n);
     }
     for (const dec::StreamsChunk &C : P.chunks) {
         const dec::ChunkPic *tab = d_tab + C.first;
@@ -522,8 +534,7 @@ static int decode_streams_impl(m2v_enc *e, void *argp)
         k_ds_slices<true><<<(C.slices + 63u) / 64u, 64, 0, s>>>(a->es, d_in, e->d_dec_ev.p, d_st, d_pics, tab, (uint32_t)C.count, C.slices, a->mode, d_mb,
                                                               e->d_dec_dc.p, e->d_dec_lv.p);
         HIPCHK(hipGetLastError());
-        k_ds_judge<<<gj, 64, 0, s>>>(d_st, (uint32_t)n);
-        HIPCHK(hipGetLastError());
+        ds_judge(s, d_st, n);
         for (const dec::StreamsChunk::Step &S : C.steps) {
             for (size_t y = 0; y < S.count; y += 65535) {             // (a grid's second dimension ends there)
                 k_ds_recon<<<dim3(S.most_mbs, (unsigned)std::min<size_t>(S.count - y, 65535)), 64, 0, s>>>(d_st, tab, d_list + S.off + y, a->mode, d_mb, e->d_dec_dc.p,
@@ -540,10 +551,9 @@ static int decode_streams_impl(m2v_enc *e, void *argp)
             HIPCHK(hipMemcpyAsync(e->d_dec_buf.p, e->d_dec_buf.p + L.buf_off, (size_t)L.mbw * L.mbh * 384, hipMemcpyDeviceToDevice, s));
         }
     }
-    k_ds_finish<<<gj, 64, 0, s>>>(d_st, (uint32_t)n, h_v);
-    HIPCHK(hipGetLastError());
+    ds_finish(s, d_st, n, h_v);
     HIPCHK(hipStreamSynchronize(s));
-    report(h_v);
+    ds_report(e, a->off, n, P.out_offset, P.overflow, rec, h_v);
     return M2V_OK;
 }
 

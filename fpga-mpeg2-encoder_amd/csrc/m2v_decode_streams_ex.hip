@@ -1,12 +1,11 @@
 // m2v_decode_streams_ex.hip — a batch of main-syntax streams with the extended options in one call (include/m2v_mi355x.h:
 // m2v_decode_streams_main_ex_device): the pipeline of m2v_decode_streams_main.hip over the x_ / t_ functions of m2v_decode_kernels.hpp,
 // each stream judged alone as m2v_decode_device judges it with "decode_syntax" = main and the four options set as the call's flags say.
-// With flags below M2V_DECS_EXTENDED the entry hands the call to m2v_decode_streams_main_device as it stands.  No other unit changes its
-// text, so every other kernel comes out of the compiler as it did.
+// With flags below M2V_DECS_EXTENDED the entry hands the call to m2v_decode_streams_main_device as it stands.  The first
+// pass up to the plan's wait and the output kernel are that unit's (ds_main_first, dsm_out); the scan, the judge, the finish and the
+// report are m2v_decode_streams.hip's.
 //
-//   k_dsx_scan    copies of k_dsm_scan / k_dsm_tiles (a kernel is launched from the unit that holds it; the syntax does not matter to
-//   k_dsx_tiles   them).
-//   k_dsx_plan    one block per stream: k_dt_plan's grammar with the stream's own segment, events, picture table and record.  flag 8:
+//   k_dsx_plan    one block per stream: k_dx_plan's grammar with the stream's own segment, events, picture table and record.  flag 8:
 //                 dec::t_event / t_picture_params, else dec::x_event / x_picture_params (a packing without the three flags above bit 20
 //                 leaves them 0).  256 ranges of ceil(events / 256); carried from range to range: the last significant event, the last I
 //                 picture, the anchors, the events that loaded each matrix with the sequence header's reset, the earliest refusal.  Per
@@ -23,9 +22,7 @@
 //                 stream's err.  Runs in the verdict pass too: a slice that breaks continuity is refused at its own start code.
 //   k_dsx_recon   k_dsm_recon with the weights from the picture's row of the matrix table; a P picture's second prediction reads
 //                 bwd = fwd (dual prime).  Anchors step by step, then every B picture of the chunk in one launch.
-//   k_dsx_out / k_dsx_judge / k_dsx_finish   as k_dsm_*.
-#include "m2v_host.hpp"
-#include "m2v_decode_kernels.hpp"
+#include "m2v_decode_state.hpp"
 #include "m2v_decode_streams.hpp"
 #include "m2v_decode_streams_ex.hpp"
 
@@ -35,96 +32,14 @@ static_assert(sizeof(dec::IMb) == 32, "the interlaced record is two of the modul
 namespace m2v {
 
 constexpr int kDsxThreads = 256;
-static_assert(dec::kScanTile == (uint32_t)kDsxThreads * 16u, "a tile is one pass of a block");
 typedef unsigned long long ull;
 
-struct DsxIn { ull off, n, ev_base, pic_base; uint32_t tile0, ntiles, ev_cap, pic_cap; };
-struct DsxState { ull err, last_nz; uint32_t nev; int32_t status; uint32_t mbw, mbh; };
 // a picture: the event of its first slice, dec::t_params_pack, its slice events, the events that loaded its matrices (kNoEvent: the sequence's)
 struct DsxPic { uint32_t slice0, params, nslices, mi, mn; };
-struct DsxVerdict { ull err; int32_t status; uint32_t pad; };
 constexpr uint32_t kDsxMatrices = 128;
 
-__device__ inline uint32_t dsx_stream_of(const DsxIn *__restrict__ in, uint32_t n, uint32_t t)
-{
-    uint32_t a = 0, b = n;
-    while (b - a > 1u) { const uint32_t m = (a + b) / 2u; if (in[m].tile0 <= t) a = m; else b = m; }
-    return a;
-}
-
-template <bool EMIT>
-__global__ __launch_bounds__(kDsxThreads) void k_dsx_scan(const uint8_t *__restrict__ base, const DsxIn *__restrict__ in, uint32_t nstreams, uint32_t ntiles,
-                                                          DsxState *st, uint32_t *__restrict__ tiles, ull *__restrict__ evs)
-{
-    __shared__ uint32_t s_w[kDsxThreads / 64];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const uint32_t b = dsx_stream_of(in, nstreams, t);
-        const DsxIn S = in[b];
-        const uint8_t *es = base + S.off;
-        const ull n = S.n, p0 = (ull)(t - S.tile0) * dec::kScanTile + (ull)tid * 16u;
-        uint64_t w0 = 0, w1 = 0, w2 = 0, nz = 0;
-        uint32_t cand = 0;
-        if (p0 < n) {
-            mux::load24(es, p0, n, w0, w1, w2);              // (clamped to the segment: what lies behind it reads as FF)
-            cand = dec::scan16(p0, n, w0, w1, w2, nz);
-        }
-        const uint32_t c = (uint32_t)__popc(cand);
-        uint32_t incl = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t v = __shfl_up(incl, d);
-            if (lane >= (uint32_t)d) incl += v;
-        }
-        if (lane == 63) s_w[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < (uint32_t)kDsxThreads / 64; ++k) { if (k < wave) before += s_w[k]; total += s_w[k]; }
-        if (!EMIT) {
-            if (tid == 0) tiles[t] = total;
-#pragma unroll
-            for (int d = 32; d; d >>= 1) nz = mux::max64(nz, __shfl_xor(nz, d));
-            if (lane == 0 && nz) atomicMax(&st[b].last_nz, (ull)nz);
-        } else {
-            ull *ev = evs + S.ev_base;
-            uint32_t at = tiles[t] + before + incl - c;
-            while (cand) {
-                const uint32_t j = (uint32_t)__builtin_ctz(cand);
-                cand &= cand - 1u;
-                if (at < S.ev_cap) ev[at] = (p0 + j) << 8 | mux::byte24(w0, w1, w2, j + 3);
-                ++at;
-            }
-        }
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(kDsxThreads) void k_dsx_tiles(const DsxIn *__restrict__ in, uint32_t *tiles_all, DsxState *sts)
-{
-    __shared__ uint32_t s_sum[kDsxThreads];
-    const DsxIn S = in[blockIdx.x];
-    DsxState *st = sts + blockIdx.x;
-    uint32_t *tiles = tiles_all + S.tile0;
-    const uint32_t ntiles = S.ntiles, tid = threadIdx.x, per = (ntiles + kDsxThreads - 1) / kDsxThreads;
-    const uint32_t a = min(ntiles, tid * per), b = min(ntiles, a + per);
-    uint32_t sum = 0;
-    for (uint32_t t = a; t < b; ++t) sum += tiles[t];
-    s_sum[tid] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t run = 0;
-        for (int k = 0; k < kDsxThreads; ++k) { const uint32_t v = s_sum[k]; s_sum[k] = run; run += v; }
-        st->nev = run;
-        if (run > S.ev_cap) st->status = dec::kEvents;
-    }
-    __syncthreads();
-    uint32_t run = s_sum[tid];
-    for (uint32_t t = a; t < b; ++t) { const uint32_t v = tiles[t]; tiles[t] = run; run += v; }
-}
-
 // one block per stream.  Whether the frames fit is the host's to say, behind the wait (the rooms depend on the streams in front)
-__global__ __launch_bounds__(kDsxThreads) void k_dsx_plan(const uint8_t *__restrict__ base, const DsxIn *__restrict__ in, const ull *__restrict__ evs, DsxState *sts,
+__global__ __launch_bounds__(kDsxThreads) void k_dsx_plan(const uint8_t *__restrict__ base, const DsIn *__restrict__ in, const ull *__restrict__ evs, DsState *sts,
                                                           DsxPic *__restrict__ pics_all, uint8_t *h_types_all, uint32_t *h_sl_all, m2v_decode_stat *h_recs, uint32_t *h_mbh,
                                                           uint8_t *__restrict__ mats_all, unsigned flags)
 {
@@ -133,8 +48,8 @@ __global__ __launch_bounds__(kDsxThreads) void k_dsx_plan(const uint8_t *__restr
     __shared__ uint32_t s_np[kDsxThreads], s_ng[kDsxThreads], s_nr[kDsxThreads], s_ni[kDsxThreads], s_na[kDsxThreads];
     __shared__ int s_last[kDsxThreads], s_sig[kDsxThreads];
     __shared__ uint32_t s_mi[kDsxThreads], s_mn[kDsxThreads], s_rs[kDsxThreads];      // the events that loaded the matrices; a reset
-    const DsxIn S = in[blockIdx.x];
-    DsxState *st = sts + blockIdx.x;
+    const DsIn S = in[blockIdx.x];
+    DsState *st = sts + blockIdx.x;
     m2v_decode_stat *h_rec = h_recs + blockIdx.x;
     const uint8_t *es = base + S.off;
     const ull *ev = evs + S.ev_base, n = S.n;
@@ -257,44 +172,27 @@ __global__ __launch_bounds__(kDsxThreads) void k_dsx_plan(const uint8_t *__restr
 
 // the matrix table: entry p of the call's table of chunk pictures gets its picture's 128 weights, raster order - its stream's
 // sequence matrices, or those of the extension in force.  One thread per weight, the blocks stride over the table
-__global__ __launch_bounds__(128) void k_dsx_mats(const uint8_t *__restrict__ base, const DsxIn *__restrict__ in, const ull *__restrict__ evs,
-                                                  const DsxState *__restrict__ sts, const dec::MainChunkPic *__restrict__ tab, uint32_t ntab,
+__global__ __launch_bounds__(128) void k_dsx_mats(const uint8_t *__restrict__ base, const DsIn *__restrict__ in, const ull *__restrict__ evs,
+                                                  const DsState *__restrict__ sts, const dec::MainChunkPic *__restrict__ tab, uint32_t ntab,
                                                   const DsxPic *__restrict__ pics, const uint8_t *__restrict__ mats_all, uint8_t *__restrict__ table)
 {
     const uint32_t l = threadIdx.x, m = l >> 6, t = l & 63u;
     for (uint32_t p = blockIdx.x; p < ntab; p += gridDim.x) {
         const dec::MainChunkPic C = tab[p];
-        const DsxState *st = sts + C.stream;
+        const DsState *st = sts + C.stream;
         if (st->status != dec::kOk) continue;
-        const DsxIn S = in[C.stream];
+        const DsIn S = in[C.stream];
         const DsxPic Q = pics[C.gpic];
         table[(size_t)p * 128u + l] = (uint8_t)dec::x_matrix_weight(base + S.off, S.n, (const uint64_t *)(evs + S.ev_base), st->nev, m ? Q.mn : Q.mi, (int)m, t,
                                                                      mats_all + (size_t)C.stream * kDsxMatrices + 64u * m);
     }
 }
 
-struct DsxSink {
-    dec::IMb *mb_;
-    int32_t *dc_;
-    int16_t *lv_;
-    M2V_HD void mb(int col, const dec::IMb &m, const int32_t (&dc)[6])
-    {
-        mb_[col] = m;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) dc_[col * 6 + k] = dc[k];
-    }
-    M2V_HD void level(int col, int blk, uint32_t i, int32_t l) { lv_[(col * 6 + blk) * 64 + (int)i] = (int16_t)l; }
-};
-struct DsxNoSink {
-    M2V_HD void mb(int, const dec::IMb &, const int32_t (&)[6]) {}
-    M2V_HD void level(int, int, uint32_t, int32_t) {}
-};
-
 // the nslices slice events of the table's pictures, one per lane, each into the row its code names.  The lane leaves its span (0: not
 // walked); a slice that cannot be read lowers its stream's err, which no lane of the launch reads.  Two slices that overlap write the
 // same records - the judge refuses the stream before anything reads them.  STORE false: for the verdict alone
 template <bool STORE, bool TOOLS>
-__global__ __launch_bounds__(64) void k_dsx_slices(const uint8_t *__restrict__ base, const DsxIn *__restrict__ in, const ull *__restrict__ evs, DsxState *sts,
+__global__ __launch_bounds__(64) void k_dsx_slices(const uint8_t *__restrict__ base, const DsIn *__restrict__ in, const ull *__restrict__ evs, DsState *sts,
                                                    const DsxPic *__restrict__ pics, const dec::MainChunkPic *__restrict__ tab, uint32_t ntab, uint32_t nslices,
                                                    dec::IMb *mb, int32_t *dc, int16_t *lv, uint32_t *__restrict__ spans)
 {
@@ -302,9 +200,9 @@ __global__ __launch_bounds__(64) void k_dsx_slices(const uint8_t *__restrict__ b
     if (g >= nslices) return;
     spans[g] = 0u;
     const dec::MainChunkPic C = tab[dec::main_chunk_slice_pic(tab, ntab, g)];
-    DsxState *st = sts + C.stream;
+    DsState *st = sts + C.stream;
     if (st->status != dec::kOk) return;
-    const DsxIn S = in[C.stream];
+    const DsIn S = in[C.stream];
     const DsxPic Q = pics[C.gpic];
     const uint32_t k = g - C.slice0, nev = st->nev;
     const uint32_t i = Q.slice0 + k;
@@ -318,11 +216,11 @@ __global__ __launch_bounds__(64) void k_dsx_slices(const uint8_t *__restrict__ b
     bool ok;
     if (STORE) {
         const size_t first = (size_t)C.mb_base + (size_t)(code - 1u) * C.mbw;
-        DsxSink sink{mb + first, dc + first * 6, lv + first * 384};
+        IMbSink sink{mb + first, dc + first * 6, lv + first * 384};
         ok = TOOLS ? dec::t_slice(es, start, end, C.type, dec::t_params_unpack(Q.params), (int)C.mbw, (int)C.mbh, (int)code - 1, sink, c0, c1)
                    : dec::x_slice(es, start, end, C.type, dec::il_params_unpack(Q.params), (int)C.mbw, (int)C.mbh, (int)code - 1, sink, c0, c1);
     } else {
-        DsxNoSink sink;
+        IMbNoSink sink;
         ok = TOOLS ? dec::t_slice(es, start, end, C.type, dec::t_params_unpack(Q.params), (int)C.mbw, (int)C.mbh, (int)code - 1, sink, c0, c1)
                    : dec::x_slice(es, start, end, C.type, dec::il_params_unpack(Q.params), (int)C.mbw, (int)C.mbh, (int)code - 1, sink, c0, c1);
     }
@@ -331,13 +229,13 @@ __global__ __launch_bounds__(64) void k_dsx_slices(const uint8_t *__restrict__ b
 }
 
 // continuity behind the walk: every readable slice against the span of the slice in front of it in its picture
-__global__ __launch_bounds__(64) void k_dsx_cont(const DsxIn *__restrict__ in, const ull *__restrict__ evs, DsxState *sts, const DsxPic *__restrict__ pics,
+__global__ __launch_bounds__(64) void k_dsx_cont(const DsIn *__restrict__ in, const ull *__restrict__ evs, DsState *sts, const DsxPic *__restrict__ pics,
                                                  const dec::MainChunkPic *__restrict__ tab, uint32_t ntab, uint32_t nslices, const uint32_t *__restrict__ spans)
 {
     const uint32_t g = blockIdx.x * 64u + threadIdx.x;
     if (g >= nslices) return;
     const dec::MainChunkPic C = tab[dec::main_chunk_slice_pic(tab, ntab, g)];
-    DsxState *st = sts + C.stream;
+    DsState *st = sts + C.stream;
     if (st->status != dec::kOk) return;
     const DsxPic Q = pics[C.gpic];
     const uint32_t k = g - C.slice0, cur = spans[g];
@@ -345,16 +243,10 @@ __global__ __launch_bounds__(64) void k_dsx_cont(const DsxIn *__restrict__ in, c
     if (!dec::x_continuous(cur, k ? spans[g - 1] : 0u, k, Q.nslices, C.mbw)) atomicMin(&st->err, dec::ev_pos(evs[in[C.stream].ev_base + Q.slice0 + k]));
 }
 
-__global__ void k_dsx_judge(DsxState *sts, uint32_t n)
-{
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < n && sts[b].status == dec::kOk && sts[b].err != dec::kNone) sts[b].status = dec::kSyntax;
-}
-
 // grid = (the most macroblocks of a picture of the launch, its pictures); list: their entries of the chunk's table; table: the chunk's
 // rows of the matrix table.  Every read of a reference lies inside its picture: the slice walk refused the slice otherwise
-// (dec::il_inside), and a refused slice makes its stream's status not OK before this kernel (k_dsx_judge)
-__global__ __launch_bounds__(64) void k_dsx_recon(const DsxState *__restrict__ sts, const dec::MainChunkPic *__restrict__ tab, const uint32_t *__restrict__ list,
+// (dec::il_inside), and a refused slice makes its stream's status not OK before this kernel (k_ds_judge)
+__global__ __launch_bounds__(64) void k_dsx_recon(const DsState *__restrict__ sts, const dec::MainChunkPic *__restrict__ tab, const uint32_t *__restrict__ list,
                                                   const DsxPic *__restrict__ pics, const uint8_t *__restrict__ table, const dec::IMb *__restrict__ mb,
                                                   const int32_t *__restrict__ dc, const int16_t *__restrict__ lv, uint8_t *buf)
 {
@@ -365,121 +257,14 @@ __global__ __launch_bounds__(64) void k_dsx_recon(const DsxState *__restrict__ s
     if (k >= mbw * mbh) return;                                        // (a smaller picture of the launch; the whole workgroup leaves)
     if (sts[C.stream].status != dec::kOk) return;
     const uint32_t W = 16u * mbw, H = 16u * mbh, CW = W / 2u;
-    const dec::PicParams pp = dec::params_unpack(pics[C.gpic].params);
-    const uint8_t *mats = table + (size_t)entry * 128u;
     const size_t at = (size_t)C.mb_base + k;
-    const dec::IMb m = mb[at];
-    const uint32_t col = k % mbw, row = k / mbw;
-    uint8_t *cur = buf + C.buf_off;
-    const uint8_t *fwd = buf + C.fwd_off, *bwd = buf + C.bwd_off;
-    const bool intra = m.intra != 0;
-    const int32_t qscale = dec::main_scale(m.qcode, pp.qst), weight = mats[(intra ? 0u : 64u) + l];
-#pragma unroll
-    for (int blk = 0; blk < 6; ++blk) {
-        if (!((m.cbp >> (5 - blk)) & 1)) continue;                     // (uniform: the whole wavefront works on one macroblock)
-        int32_t f = intra && l == 0 ? dec::main_dequant_dc(dc[at * 6 + blk], pp.prec) : dec::main_dequant(lv[(at * 6 + blk) * 64 + l], weight, intra, qscale);
-        const int odd = __popcll(__ballot(f & 1)) & 1;
-        if (!odd && l == 63) f = dec::mismatch(f);
-        F[blk][l] = f;
-    }
-    __syncthreads();
-    const int blk8 = (int)(l >> 3), r8 = (int)(l & 7u);
-    const bool mine = l < 48 && ((m.cbp >> (5 - blk8)) & 1);
-    if (mine) {
-        int32_t a[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] = F[blk8][r8 * 8 + j];
-        dec::idct_1d(a, true, dec::kIso);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) F[blk8][r8 * 8 + j] = a[j];
-    }
-    __syncthreads();
-    if (mine) {
-        int32_t a[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] = F[blk8][j * 8 + r8];
-        dec::idct_1d(a, false, dec::kIso);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) F[blk8][j * 8 + r8] = a[j];
-    }
-    __syncthreads();
-    {   // luma: four samples of one row per lane; the row's block and the row inside it through the field-DCT map
-        const uint32_t y = l >> 2, x0 = (l & 3u) * 4u, blk = dec::il_luma_block(x0, y, m.dct_type), brow = dec::il_luma_row(y, m.dct_type);
-        const bool coded = (m.cbp >> (5 - blk)) & 1;
-        const int px = (int)(16u * col + x0), py = (int)(16u * row + y);
-        uint32_t v = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int32_t pred = intra ? 128 : dec::il_predict(fwd, bwd, (int)W, px + j, py, m, false);
-            const int32_t res = coded ? F[blk][brow * 8u + ((x0 + j) & 7u)] : 0;
-            v |= (uint32_t)dec::clip255(pred + res) << (8 * j);
-        }
-        *(uint32_t *)(cur + (size_t)(16u * row + y) * W + 16u * col + x0) = v;
-    }
-    {   // chroma: two samples per lane, U in the first half of the wavefront; frame blocks always
-        const uint32_t pl = l >> 5, y = (l >> 2) & 7u, x0 = (l & 3u) * 2u;
-        const bool coded = (m.cbp >> (1 - pl)) & 1;
-        const size_t plane = (size_t)W * H + (size_t)pl * CW * (H / 2u);
-        const int px = (int)(8u * col + x0), py = (int)(8u * row + y);
-        uint32_t v = 0;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int32_t pred = intra ? 128 : dec::il_predict(fwd + plane, bwd + plane, (int)CW, px + j, py, m, true);
-            const int32_t res = coded ? F[4u + pl][y * 8u + x0 + j] : 0;
-            v |= (uint32_t)dec::clip255(pred + res) << (8 * j);
-        }
-        *(uint16_t *)(cur + plane + (size_t)(8u * row + y) * CW + 8u * col + x0) = (uint16_t)v;
-    }
-}
-
-typedef uint32_t dsx_store_t __attribute__((ext_vector_type(4)));
-
-// picture first + blockIdx.y of the chunk's table into dst: bytes [out_off, out_off + fb) of the output, iff its stream is OK.  A
-// 16-byte unit of the destination that lies inside the frame is one aligned store; the units at the frame's edges go byte by byte, so
-// two frames that share a unit never write each other's bytes
-__global__ __launch_bounds__(kDsxThreads) void k_dsx_out(const DsxState *__restrict__ sts, const dec::MainChunkPic *__restrict__ tab, uint32_t first,
-                                                         const uint8_t *__restrict__ buf, uint8_t *__restrict__ dst, int layout)
-{
-    const dec::MainChunkPic C = tab[first + blockIdx.y];
-    if (sts[C.stream].status != dec::kOk) return;
-    const uint32_t w = C.w, h = C.h, W = 16u * C.mbw, H = 16u * C.mbh;
-    const uint8_t *pic = buf + C.buf_off;
-    const ull lo = C.out_off, hi = lo + C.fb;
-    const ull lead = (ull)(uintptr_t)dst & 15ull;
-    const ull u0 = (lo + lead) >> 4, u1 = (hi + lead + 15ull) >> 4;
-    for (ull g = u0 + (ull)blockIdx.x * kDsxThreads + threadIdx.x; g < u1; g += (ull)gridDim.x * kDsxThreads) {
-        const long long o0 = (long long)(g << 4) - (long long)lead;
-        const int k0 = o0 < (long long)lo ? (int)((long long)lo - o0) : 0, k1 = (long long)hi - o0 < 16 ? (int)((long long)hi - o0) : 16;
-        if (k0 >= k1) continue;
-        uint32_t q = (uint32_t)((ull)(o0 + k0) - lo);
-        dec::OutAt at = dec::out_locate(q, w, h, layout);
-        uint32_t v[4] = {0, 0, 0, 0};
-        for (int k = k0; k < k1; ++k) {
-            v[k >> 2] |= (uint32_t)dec::pic_sample(pic, W, H, at) << (8 * (k & 3));
-            if (k + 1 == k1) break;
-            ++q;
-            if (at.run > 1) dec::out_step(at, layout);
-            else at = dec::out_locate(q, w, h, layout);
-        }
-        if (k0 == 0 && k1 == 16) {
-            *(__attribute__((address_space(1))) dsx_store_t *)(dst + o0) = dsx_store_t{v[0], v[1], v[2], v[3]};
-        } else {
-            for (int k = k0; k < k1; ++k) dst[o0 + k] = (uint8_t)(v[k >> 2] >> (8 * (k & 3)));
-        }
-    }
-}
-
-__global__ void k_dsx_finish(const DsxState *sts, uint32_t n, DsxVerdict *h_v)
-{
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < n) h_v[b] = DsxVerdict{sts[b].err, sts[b].status, 0};
+    imb_recon(F, mb[at], dec::params_unpack(pics[C.gpic].params), table + (size_t)entry * 128u, dc, lv, at, buf + C.buf_off, buf + C.fwd_off, buf + C.bwd_off, W, H, CW,
+              k % mbw, k / mbw, l);
 }
 
 }  // namespace m2v
 
 struct DecodeStreamsExArgs { const uint8_t *es; const uint64_t *off, *bytes; size_t n; uint8_t *dst; size_t cap; int layout; unsigned flags; hipStream_t s; };
-
-static size_t dsx_up64(size_t v) { return (v + 63) & ~(size_t)63; }
 
 static int decode_streams_ex_impl(m2v_enc *e, void *argp)
 {
@@ -492,113 +277,45 @@ static int decode_streams_ex_impl(m2v_enc *e, void *argp)
     e->d_dec_st.recorded = e->d_dec_ev.recorded = e->d_dec_pics.recorded = e->d_dec_mb.recorded = e->d_dec_dc.recorded = false;
     e->d_dec_lv.recorded = e->d_dec_buf.recorded = e->d_dec_tiles.recorded = e->d_dec_list.recorded = e->d_dec_main.recorded = false;
     e->d_ds_in.recorded = e->d_ds_tab.recorded = e->d_dec_x.recorded = false;
-    std::vector<size_t> ev_cap(n);
-    for (size_t b = 0; b < n; ++b) ev_cap[b] = std::max<size_t>(256, a->bytes[b] / 16 + 64);      // a guess per stream: a second run takes the counts of the first
-    std::vector<m2v_decode_stat> rec(n);
-    std::vector<uint8_t> types;
-    std::vector<uint32_t> mbh(n), nsl;
-    std::vector<size_t> pic_base(n);
-    timer_break(e);
-    for (int run = 0; run < 2; ++run) {
-        size_t tiles = 0, evs = 0, pics = 0;
-        const size_t in_bytes = dsx_up64(n * sizeof(DsxIn)), st_bytes = dsx_up64(n * sizeof(DsxState)), rec_bytes = dsx_up64(n * sizeof(m2v_decode_stat)),
-                     mbh_bytes = dsx_up64(n * sizeof(uint32_t));
-        for (size_t b = 0; b < n; ++b) pics += ev_cap[b] / 3 + 2;
-        const size_t sl_bytes = dsx_up64(pics * sizeof(uint32_t));
-        ensure_pinned(e->h_ds, e->h_ds_cap, in_bytes + st_bytes + rec_bytes + mbh_bytes + sl_bytes + pics + 64);
-        auto *h_in = (DsxIn *)e->h_ds;
-        auto *h_st = (DsxState *)(e->h_ds + in_bytes);
-        auto *h_rec = (m2v_decode_stat *)(e->h_ds + in_bytes + st_bytes);
-        auto *h_mbh = (uint32_t *)(e->h_ds + in_bytes + st_bytes + rec_bytes);
-        auto *h_sl = (uint32_t *)(e->h_ds + in_bytes + st_bytes + rec_bytes + mbh_bytes);
-        uint8_t *h_types = e->h_ds + in_bytes + st_bytes + rec_bytes + mbh_bytes + sl_bytes;
-        pics = 0;
-        for (size_t b = 0; b < n; ++b) {
-            const size_t nb = a->bytes[b], nt = nb < 4 ? 0 : (nb + dec::kScanTile - 1) / dec::kScanTile;
-            if (ev_cap[b] > 0x7FFFFFFFu) { e->set_err("m2v_decode_streams_main_ex_device: stream %zu holds more than 2^31 start codes", b); return M2V_E_PARAM; }
-            if (tiles + nt > 0x7FFFFFFFu) { e->set_err("m2v_decode_streams_main_ex_device: the streams are longer than 2^31 scan tiles"); return M2V_E_PARAM; }
-            const size_t pic_cap = ev_cap[b] / 3 + 2;
-            h_in[b] = DsxIn{a->off[b], nb, evs, pics, (uint32_t)tiles, (uint32_t)nt, (uint32_t)ev_cap[b], (uint32_t)pic_cap};
-            h_st[b] = DsxState{dec::kNone, 0, 0, dec::kOk, 0, 0};
-            pic_base[b] = pics;
-            tiles += nt; evs += ev_cap[b]; pics += pic_cap;
-        }
-        if (pics > 0xFFFFFFFFull) { e->set_err("m2v_decode_streams_main_ex_device: more than 2^32 pictures"); return M2V_E_PARAM; }
-        e->d_ds_in.ensure(in_bytes);
-        e->d_dec_st.ensure(st_bytes);
-        e->d_dec_tiles.ensure(std::max<size_t>(tiles, 1));
-        e->d_dec_ev.ensure(evs);
-        e->d_dec_pics.ensure(pics * sizeof(DsxPic));
-        e->d_dec_main.ensure(n * kDsxMatrices);
-        auto *d_in = (const DsxIn *)e->d_ds_in.p;
-        auto *d_st = (DsxState *)e->d_dec_st.p;
-        HIPCHK(hipMemcpyAsync(e->d_ds_in.p, h_in, in_bytes, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(d_st, h_st, st_bytes, hipMemcpyHostToDevice, s));
-        if (tiles) {
-            const unsigned gx = (unsigned)std::min<size_t>(tiles, 4096);
-            k_dsx_scan<false><<<gx, kDsxThreads, 0, s>>>(a->es, d_in, (uint32_t)n, (uint32_t)tiles, d_st, e->d_dec_tiles.p, e->d_dec_ev.p);
-            HIPCHK(hipGetLastError());
-            k_dsx_tiles<<<(unsigned)n, kDsxThreads, 0, s>>>(d_in, e->d_dec_tiles.p, d_st);
-            HIPCHK(hipGetLastError());
-            k_dsx_scan<true><<<gx, kDsxThreads, 0, s>>>(a->es, d_in, (uint32_t)n, (uint32_t)tiles, d_st, e->d_dec_tiles.p, e->d_dec_ev.p);
-            HIPCHK(hipGetLastError());
-        }
+    DsMainFirst F;
+    const int err = ds_main_first(e, s, "m2v_decode_streams_main_ex_device", a->es, a->off, a->bytes, n, sizeof(DsxPic), true,
+                                  [&](const DsIn *d_in, DsState *d_st, uint8_t *h_types, uint32_t *h_sl, m2v_decode_stat *h_rec, uint32_t *h_mbh) {
         k_dsx_plan<<<(unsigned)n, kDsxThreads, 0, s>>>(a->es, d_in, e->d_dec_ev.p, d_st, (DsxPic *)e->d_dec_pics.p, h_types, h_sl, h_rec, h_mbh, e->d_dec_main.p, a->flags);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(s));                              // the call's one wait for the plan: every stream's pictures, size, rows, types, slices
-        bool again = false;
-        for (size_t b = 0; b < n; ++b) {
-            rec[b] = h_rec[b];
-            mbh[b] = h_mbh[b];
-            if (rec[b].status == dec::kEvents) { again = true; ev_cap[b] = rec[b].pictures; }      // (the count of events travels there)
-        }
-        types.assign(h_types, h_types + pics);
-        nsl.assign(h_sl, h_sl + pics);
-        if (!again) break;
-    }
+    }, F);
+    if (err != M2V_OK) return err;
+    const std::vector<m2v_decode_stat> &rec = F.rec;
+    const std::vector<size_t> &pic_base = F.pic_base;
     std::vector<dec::ExStreamInfo> info(n);
     for (size_t b = 0; b < n; ++b) {
-        if (rec[b].status == dec::kEvents) { const uint64_t nb = rec[b].es_bytes; rec[b] = m2v_decode_stat{}; rec[b].es_bytes = nb; rec[b].status = M2V_DEC_SYNTAX; }
-        info[b] = dec::ExStreamInfo{dec::MainStreamInfo{rec[b].status, rec[b].pictures, rec[b].width, rec[b].height, mbh[b], types.data() + pic_base[b]},
-                                    nsl.data() + pic_base[b]};
+        info[b] = dec::ExStreamInfo{dec::MainStreamInfo{rec[b].status, rec[b].pictures, rec[b].width, rec[b].height, F.mbh[b], F.types.data() + pic_base[b]},
+                                    F.nsl.data() + pic_base[b]};
     }
     dec::MainStreamsPlan P = dec::plan_streams_main_ex(info.data(), n, a->cap, a->dst == nullptr, e->decode_batch, (a->flags & M2V_DECS_B_PICTURES) != 0, tools);
     for (dec::MainChunkPic &c : P.pics) c.gpic = (uint32_t)(pic_base[c.stream] + c.pic);
     for (dec::MainChunkPic &c : P.pre) c.gpic = (uint32_t)(pic_base[c.stream] + c.pic);
-    auto report = [&](const DsxVerdict *v) {
-        for (size_t b = 0; b < n; ++b) {
-            m2v_decode_stream_stat r{a->off[b], P.out_offset[b], rec[b]};
-            if (r.rec.status == M2V_DEC_OK) {
-                if (P.overflow[b]) r.rec.status = M2V_DEC_OVERFLOW;
-                else if (v && v[b].status != dec::kOk) { r.rec.status = v[b].status; r.rec.err_offset = v[b].err; }
-                else r.rec.out_bytes = r.rec.frame_bytes * r.rec.pictures;
-            }
-            e->ds_q.push(&r, &r + 1);
-        }
-    };
-    if (!a->dst || P.pics.empty()) { report(nullptr); return M2V_OK; }
+    if (!a->dst || P.pics.empty()) { ds_report(e, a->off, n, P.out_offset, P.overflow, rec, nullptr); return M2V_OK; }
     if (P.pics.size() > 0xFFFFFFFFull) { e->set_err("m2v_decode_streams_main_ex_device: more than 2^32 pictures"); return M2V_E_PARAM; }
-    const size_t tab_bytes = dsx_up64(P.pics.size() * sizeof(dec::MainChunkPic)), pre_bytes = dsx_up64(P.pre.size() * sizeof(dec::MainChunkPic)),
-                 list_bytes = dsx_up64(P.list.size() * sizeof(uint32_t));
-    ensure_pinned(e->h_ds_tab, e->h_ds_tab_cap, tab_bytes + pre_bytes + list_bytes + n * sizeof(DsxVerdict) + 64);
+    const size_t tab_bytes = ds_up64(P.pics.size() * sizeof(dec::MainChunkPic)), pre_bytes = ds_up64(P.pre.size() * sizeof(dec::MainChunkPic)),
+                 list_bytes = ds_up64(P.list.size() * sizeof(uint32_t));
+    ensure_pinned(e->h_ds_tab, e->h_ds_tab_cap, tab_bytes + pre_bytes + list_bytes + n * sizeof(DsVerdict) + 64);
     memcpy(e->h_ds_tab, P.pics.data(), P.pics.size() * sizeof(dec::MainChunkPic));
     if (!P.pre.empty()) memcpy(e->h_ds_tab + tab_bytes, P.pre.data(), P.pre.size() * sizeof(dec::MainChunkPic));
     memcpy(e->h_ds_tab + tab_bytes + pre_bytes, P.list.data(), P.list.size() * sizeof(uint32_t));
-    auto *h_v = (DsxVerdict *)(e->h_ds_tab + tab_bytes + pre_bytes + list_bytes);
+    auto *h_v = (DsVerdict *)(e->h_ds_tab + tab_bytes + pre_bytes + list_bytes);
     e->d_ds_tab.ensure(tab_bytes + pre_bytes + list_bytes);
     HIPCHK(hipMemcpyAsync(e->d_ds_tab.p, e->h_ds_tab, tab_bytes + pre_bytes + list_bytes, hipMemcpyHostToDevice, s));
     uint64_t most_mbs = 0, most_buf = 0, most_slices = P.pre_slices;
     for (const dec::MainStreamsChunk &C : P.chunks) {
         most_mbs = std::max(most_mbs, C.mbs); most_buf = std::max(most_buf, C.buf_bytes); most_slices = std::max<uint64_t>(most_slices, C.slices);
     }
-    const size_t span_off = dsx_up64(P.pics.size() * 128);             // the matrix table, then the spans of a launch's slices
+    const size_t span_off = ds_up64(P.pics.size() * 128);             // the matrix table, then the spans of a launch's slices
     e->d_dec_x.ensure(span_off + std::max<size_t>(most_slices, 1) * sizeof(uint32_t));
     e->d_dec_mb.ensure(most_mbs * sizeof(dec::IMb));
     e->d_dec_dc.ensure(most_mbs * 6);
     e->d_dec_lv.ensure(most_mbs * 384);
     e->d_dec_buf.ensure(most_buf);
-    auto *d_in = (const DsxIn *)e->d_ds_in.p;
-    auto *d_st = (DsxState *)e->d_dec_st.p;
+    auto *d_in = (const DsIn *)e->d_ds_in.p;
+    auto *d_st = (DsState *)e->d_dec_st.p;
     auto *d_mb = (dec::IMb *)e->d_dec_mb.p;
     auto *d_pics = (const DsxPic *)e->d_dec_pics.p;
     auto *d_tab = (const dec::MainChunkPic *)e->d_ds_tab.p;
@@ -606,7 +323,6 @@ static int decode_streams_ex_impl(m2v_enc *e, void *argp)
     auto *d_list = (const uint32_t *)(e->d_ds_tab.p + tab_bytes + pre_bytes);
     uint8_t *d_table = e->d_dec_x.p;
     auto *d_spans = (uint32_t *)(e->d_dec_x.p + span_off);
-    const unsigned gj = (unsigned)((n + 63) / 64);
     auto walk = [&](bool store, const dec::MainChunkPic *tab, uint32_t ntab, uint32_t nslices) {
         const unsigned g = (nslices + 63u) / 64u;
         if (store && tools) k_dsx_slices<true, true><<<g, 64, 0, s>>>(a->es, d_in, e->d_dec_ev.p, d_st, d_pics, tab, ntab, nslices, d_mb, e->d_dec_dc.p, e->d_dec_lv.p, d_spans);
@@ -616,8 +332,7 @@ static int decode_streams_ex_impl(m2v_enc *e, void *argp)
         HIPCHK(hipGetLastError());
         k_dsx_cont<<<g, 64, 0, s>>>(d_in, e->d_dec_ev.p, d_st, d_pics, tab, ntab, nslices, d_spans);
         HIPCHK(hipGetLastError());
-        k_dsx_judge<<<gj, 64, 0, s>>>(d_st, (uint32_t)n);
-        HIPCHK(hipGetLastError());
+        ds_judge(s, d_st, n);
     };
     if (P.pre_slices) walk(false, d_pre, (uint32_t)P.pre.size(), P.pre_slices);
     k_dsx_mats<<<(unsigned)std::min<size_t>(P.pics.size(), 1u << 20), 128, 0, s>>>(a->es, d_in, e->d_dec_ev.p, d_st, d_tab, (uint32_t)P.pics.size(), d_pics, e->d_dec_main.p,
@@ -636,19 +351,14 @@ static int decode_streams_ex_impl(m2v_enc *e, void *argp)
         };
         for (const dec::MainStreamsChunk::Step &S : C.steps) recon(S);
         recon(C.b);                                                   // every B picture of the chunk, of all streams, at once: their anchors are done
-        const unsigned gx = (unsigned)std::min<size_t>(((size_t)C.most_units + kDsxThreads - 1) / kDsxThreads, 1024);
-        for (size_t y = 0; y < C.count; y += 65535) {
-            k_dsx_out<<<dim3(gx, (unsigned)std::min<size_t>(C.count - y, 65535)), kDsxThreads, 0, s>>>(d_st, tab, (uint32_t)y, e->d_dec_buf.p, a->dst, a->layout);
-            HIPCHK(hipGetLastError());
-        }
+        dsm_out(s, d_st, tab, C.count, C.most_units, e->d_dec_buf.p, a->dst, a->layout);
         // the next chunk's carried anchors: slot 0 first (it may come from slot 1)
         if (C.carry0_from >= 0) HIPCHK(hipMemcpyAsync(e->d_dec_buf.p, e->d_dec_buf.p + C.carry0_from, C.carry_bytes, hipMemcpyDeviceToDevice, s));
         if (C.carry1_from >= 0) HIPCHK(hipMemcpyAsync(e->d_dec_buf.p + P.carry, e->d_dec_buf.p + C.carry1_from, C.carry_bytes, hipMemcpyDeviceToDevice, s));
     }
-    k_dsx_finish<<<gj, 64, 0, s>>>(d_st, (uint32_t)n, h_v);
-    HIPCHK(hipGetLastError());
+    ds_finish(s, d_st, n, h_v);
     HIPCHK(hipStreamSynchronize(s));
-    report(h_v);
+    ds_report(e, a->off, n, P.out_offset, P.overflow, rec, h_v);
     return M2V_OK;
 }
 

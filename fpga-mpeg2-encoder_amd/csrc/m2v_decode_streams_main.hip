@@ -1,10 +1,10 @@
 // m2v_decode_streams_main.hip — a batch of main-syntax streams back to 4:2:0 frames in one call (include/m2v_mi355x.h:
 // m2v_decode_streams_main_device): the pipeline of m2v_decode_streams.hip over the main_ / bp_ / il_ functions of
 // m2v_decode_kernels.hpp, each stream judged alone as m2v_decode_device judges it with "decode_syntax" = main and the two options set
-// as the call's flags say.  m2v_decode_streams.hip and the four single-stream units keep their text and their kernels.
+// as the call's flags say.  The scan, the judge, the finish and the report are m2v_decode_streams.hip's (ds_scan, ds_judge, ds_finish,
+// ds_report); the first pass up to the plan's wait (ds_main_first) and the output kernel (dsm_out) live here and serve
+// m2v_decode_streams_ex.hip too.
 //
-//   k_dsm_scan    copies of k_ds_scan / k_ds_tiles (a kernel is launched from the unit that holds it; the syntax does not matter to
-//   k_dsm_tiles   them).
 //   k_dsm_plan    one block per stream: k_di_plan's grammar with the stream's own segment, events, picture table and record.  flag 2:
 //                 dec::il_first / il_event / il_picture_params; flag 1 alone: main_first / bp_event / bp_picture_params; neither:
 //                 main_first / main_event / main_picture_params.  Per picture: its first slice's event and its packed parameters (all
@@ -16,13 +16,11 @@
 //                 field bit to bp_slice, and bp_slice hands one that is not a B picture to main_slice: with flag 2 off no accepted
 //                 stream has the field bit (its coding extension was refused), with flag 1 off none has a B picture (its header was
 //                 refused), so the walk and its refusals are bp_slice's, or main_slice's, exactly.
-//   k_dsm_recon   k_di_recon per picture of a step: the picture's own slot, the slots of its references (dec::MainChunkPic), the
-//                 matrices of its stream.  Anchors step by step, then every B picture of the chunk in one launch.
-//   k_dsm_out     k_di_out over (units, pictures): every picture to out_offset[stream] + display * frame_bytes - a chunk's frames are
-//                 no contiguous range.  16-byte stores where a unit lies inside one frame, bytes at a frame's edges.
-//   k_dsm_judge / k_dsm_finish   per stream, as k_ds_judge / k_ds_finish.
-#include "m2v_host.hpp"
-#include "m2v_decode_kernels.hpp"
+//   k_dsm_recon   imb_recon (m2v_decode_device.hpp) per picture of a step: the picture's own slot, the slots of its references
+//                 (dec::MainChunkPic), the matrices of its stream.  Anchors step by step, then every B picture of the chunk in one launch.
+//   k_dsm_out     out_picture over (units, pictures): every picture to out_offset[stream] + display * frame_bytes - a chunk's frames
+//                 are no contiguous range.  16-byte stores where a unit lies inside one frame, bytes at a frame's edges.
+#include "m2v_decode_state.hpp"
 #include "m2v_decode_streams.hpp"
 #include "m2v_decode_streams_main.hpp"
 
@@ -32,92 +30,10 @@ static_assert(sizeof(dec::IMb) == 32, "the interlaced record is two of the modul
 namespace m2v {
 
 constexpr int kDsmThreads = 256;
-static_assert(dec::kScanTile == (uint32_t)kDsmThreads * 16u, "a tile is one pass of a block");
 typedef unsigned long long ull;
 
-struct DsmIn { ull off, n, ev_base, pic_base; uint32_t tile0, ntiles, ev_cap, pic_cap; };
-struct DsmState { ull err, last_nz; uint32_t nev; int32_t status; uint32_t mbw, mbh; };
 struct DsmPic { uint32_t slice0, params; };
-struct DsmVerdict { ull err; int32_t status; uint32_t pad; };
 constexpr uint32_t kDsmMatrices = 128;
-
-__device__ inline uint32_t dsm_stream_of(const DsmIn *__restrict__ in, uint32_t n, uint32_t t)
-{
-    uint32_t a = 0, b = n;
-    while (b - a > 1u) { const uint32_t m = (a + b) / 2u; if (in[m].tile0 <= t) a = m; else b = m; }
-    return a;
-}
-
-template <bool EMIT>
-__global__ __launch_bounds__(kDsmThreads) void k_dsm_scan(const uint8_t *__restrict__ base, const DsmIn *__restrict__ in, uint32_t nstreams, uint32_t ntiles,
-                                                          DsmState *st, uint32_t *__restrict__ tiles, ull *__restrict__ evs)
-{
-    __shared__ uint32_t s_w[kDsmThreads / 64];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const uint32_t b = dsm_stream_of(in, nstreams, t);
-        const DsmIn S = in[b];
-        const uint8_t *es = base + S.off;
-        const ull n = S.n, p0 = (ull)(t - S.tile0) * dec::kScanTile + (ull)tid * 16u;
-        uint64_t w0 = 0, w1 = 0, w2 = 0, nz = 0;
-        uint32_t cand = 0;
-        if (p0 < n) {
-            mux::load24(es, p0, n, w0, w1, w2);              // (clamped to the segment: what lies behind it reads as FF)
-            cand = dec::scan16(p0, n, w0, w1, w2, nz);
-        }
-        const uint32_t c = (uint32_t)__popc(cand);
-        uint32_t incl = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t v = __shfl_up(incl, d);
-            if (lane >= (uint32_t)d) incl += v;
-        }
-        if (lane == 63) s_w[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < (uint32_t)kDsmThreads / 64; ++k) { if (k < wave) before += s_w[k]; total += s_w[k]; }
-        if (!EMIT) {
-            if (tid == 0) tiles[t] = total;
-#pragma unroll
-            for (int d = 32; d; d >>= 1) nz = mux::max64(nz, __shfl_xor(nz, d));
-            if (lane == 0 && nz) atomicMax(&st[b].last_nz, (ull)nz);
-        } else {
-            ull *ev = evs + S.ev_base;
-            uint32_t at = tiles[t] + before + incl - c;
-            while (cand) {
-                const uint32_t j = (uint32_t)__builtin_ctz(cand);
-                cand &= cand - 1u;
-                if (at < S.ev_cap) ev[at] = (p0 + j) << 8 | mux::byte24(w0, w1, w2, j + 3);
-                ++at;
-            }
-        }
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(kDsmThreads) void k_dsm_tiles(const DsmIn *__restrict__ in, uint32_t *tiles_all, DsmState *sts)
-{
-    __shared__ uint32_t s_sum[kDsmThreads];
-    const DsmIn S = in[blockIdx.x];
-    DsmState *st = sts + blockIdx.x;
-    uint32_t *tiles = tiles_all + S.tile0;
-    const uint32_t ntiles = S.ntiles, tid = threadIdx.x, per = (ntiles + kDsmThreads - 1) / kDsmThreads;
-    const uint32_t a = min(ntiles, tid * per), b = min(ntiles, a + per);
-    uint32_t sum = 0;
-    for (uint32_t t = a; t < b; ++t) sum += tiles[t];
-    s_sum[tid] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t run = 0;
-        for (int k = 0; k < kDsmThreads; ++k) { const uint32_t v = s_sum[k]; s_sum[k] = run; run += v; }
-        st->nev = run;
-        if (run > S.ev_cap) st->status = dec::kEvents;
-    }
-    __syncthreads();
-    uint32_t run = s_sum[tid];
-    for (uint32_t t = a; t < b; ++t) { const uint32_t v = tiles[t]; tiles[t] = run; run += v; }
-}
 
 // event i of a stream by the call's flags
 __device__ inline dec::EvInfo dsm_event(const uint8_t *es, ull n, const ull *ev, uint32_t nev, uint32_t i, const dec::MainPlan &P, ull last_nz, int prev, unsigned flags)
@@ -128,7 +44,7 @@ __device__ inline dec::EvInfo dsm_event(const uint8_t *es, ull n, const ull *ev,
 }
 
 // one block per stream.  Whether the frames fit is the host's to say, behind the wait (the rooms depend on the streams in front)
-__global__ __launch_bounds__(kDsmThreads) void k_dsm_plan(const uint8_t *__restrict__ base, const DsmIn *__restrict__ in, const ull *__restrict__ evs, DsmState *sts,
+__global__ __launch_bounds__(kDsmThreads) void k_dsm_plan(const uint8_t *__restrict__ base, const DsIn *__restrict__ in, const ull *__restrict__ evs, DsState *sts,
                                                           DsmPic *__restrict__ pics_all, uint8_t *h_types_all, m2v_decode_stat *h_recs, uint32_t *h_mbh,
                                                           uint8_t *__restrict__ mats_all, unsigned flags)
 {
@@ -136,8 +52,8 @@ __global__ __launch_bounds__(kDsmThreads) void k_dsm_plan(const uint8_t *__restr
     __shared__ ull s_bad;
     __shared__ uint32_t s_np[kDsmThreads], s_ng[kDsmThreads], s_nr[kDsmThreads], s_ni[kDsmThreads], s_na[kDsmThreads];
     __shared__ int s_last[kDsmThreads], s_sig[kDsmThreads];
-    const DsmIn S = in[blockIdx.x];
-    DsmState *st = sts + blockIdx.x;
+    const DsIn S = in[blockIdx.x];
+    DsState *st = sts + blockIdx.x;
     m2v_decode_stat *h_rec = h_recs + blockIdx.x;
     const uint8_t *es = base + S.off;
     const ull *ev = evs + S.ev_base, n = S.n;
@@ -242,36 +158,19 @@ __global__ __launch_bounds__(kDsmThreads) void k_dsm_plan(const uint8_t *__restr
     *h_rec = r;
 }
 
-struct DsmSink {
-    dec::IMb *mb_;
-    int32_t *dc_;
-    int16_t *lv_;
-    M2V_HD void mb(int col, const dec::IMb &m, const int32_t (&dc)[6])
-    {
-        mb_[col] = m;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) dc_[col * 6 + k] = dc[k];
-    }
-    M2V_HD void level(int col, int blk, uint32_t i, int32_t l) { lv_[(col * 6 + blk) * 64 + (int)i] = (int16_t)l; }
-};
-struct DsmNoSink {
-    M2V_HD void mb(int, const dec::IMb &, const int32_t (&)[6]) {}
-    M2V_HD void level(int, int, uint32_t, int32_t) {}
-};
-
 // the nslices slices of the table's pictures, one per lane.  Only lowers its stream's err, which no lane of the launch reads.
 // STORE false: for the verdict alone
 template <bool STORE>
-__global__ __launch_bounds__(64) void k_dsm_slices(const uint8_t *__restrict__ base, const DsmIn *__restrict__ in, const ull *__restrict__ evs, DsmState *sts,
+__global__ __launch_bounds__(64) void k_dsm_slices(const uint8_t *__restrict__ base, const DsIn *__restrict__ in, const ull *__restrict__ evs, DsState *sts,
                                                    const DsmPic *__restrict__ pics, const dec::MainChunkPic *__restrict__ tab, uint32_t ntab, uint32_t nslices,
                                                    dec::IMb *mb, int32_t *dc, int16_t *lv)
 {
     const uint32_t g = blockIdx.x * 64u + threadIdx.x;
     if (g >= nslices) return;
     const dec::MainChunkPic C = tab[dec::main_chunk_slice_pic(tab, ntab, g)];
-    DsmState *st = sts + C.stream;
+    DsState *st = sts + C.stream;
     if (st->status != dec::kOk) return;
-    const DsmIn S = in[C.stream];
+    const DsIn S = in[C.stream];
     const DsmPic Q = pics[C.gpic];
     const uint32_t row = g - C.slice0, nev = st->nev;
     const uint32_t i = Q.slice0 + row;
@@ -282,25 +181,19 @@ __global__ __launch_bounds__(64) void k_dsm_slices(const uint8_t *__restrict__ b
     bool ok;
     if (STORE) {
         const size_t first = (size_t)C.mb_base + (size_t)row * C.mbw;
-        DsmSink sink{mb + first, dc + first * 6, lv + first * 384};
+        IMbSink sink{mb + first, dc + first * 6, lv + first * 384};
         ok = dec::il_slice(base + S.off, start, end, C.type, pp, (int)C.mbw, (int)C.mbh, (int)row, sink);
     } else {
-        DsmNoSink sink;
+        IMbNoSink sink;
         ok = dec::il_slice(base + S.off, start, end, C.type, pp, (int)C.mbw, (int)C.mbh, (int)row, sink);
     }
     if (!ok) atomicMin(&st->err, start);
 }
 
-__global__ void k_dsm_judge(DsmState *sts, uint32_t n)
-{
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < n && sts[b].status == dec::kOk && sts[b].err != dec::kNone) sts[b].status = dec::kSyntax;
-}
-
 // grid = (the most macroblocks of a picture of the launch, its pictures); list: their entries of the chunk's table.  Every read of a
 // reference lies inside its picture: the slice walk refused the slice otherwise (dec::il_inside), and a refused slice makes its stream's
-// status not OK before this kernel (k_dsm_judge)
-__global__ __launch_bounds__(64) void k_dsm_recon(const DsmState *__restrict__ sts, const dec::MainChunkPic *__restrict__ tab, const uint32_t *__restrict__ list,
+// status not OK before this kernel (k_ds_judge)
+__global__ __launch_bounds__(64) void k_dsm_recon(const DsState *__restrict__ sts, const dec::MainChunkPic *__restrict__ tab, const uint32_t *__restrict__ list,
                                                   const DsmPic *__restrict__ pics, const uint8_t *__restrict__ mats_all, const dec::IMb *__restrict__ mb,
                                                   const int32_t *__restrict__ dc, const int16_t *__restrict__ lv, uint8_t *buf)
 {
@@ -310,121 +203,95 @@ __global__ __launch_bounds__(64) void k_dsm_recon(const DsmState *__restrict__ s
     if (k >= mbw * mbh) return;                                        // (a smaller picture of the launch; the whole workgroup leaves)
     if (sts[C.stream].status != dec::kOk) return;
     const uint32_t W = 16u * mbw, H = 16u * mbh, CW = W / 2u;
-    const dec::PicParams pp = dec::params_unpack(pics[C.gpic].params);
-    const uint8_t *mats = mats_all + (size_t)C.stream * kDsmMatrices;
     const size_t at = (size_t)C.mb_base + k;
-    const dec::IMb m = mb[at];
-    const uint32_t col = k % mbw, row = k / mbw;
-    uint8_t *cur = buf + C.buf_off;
-    const uint8_t *fwd = buf + C.fwd_off, *bwd = buf + C.bwd_off;
-    const bool intra = m.intra != 0;
-    const int32_t qscale = dec::main_scale(m.qcode, pp.qst), weight = mats[(intra ? 0u : 64u) + l];
-#pragma unroll
-    for (int blk = 0; blk < 6; ++blk) {
-        if (!((m.cbp >> (5 - blk)) & 1)) continue;                     // (uniform: the whole wavefront works on one macroblock)
-        int32_t f = intra && l == 0 ? dec::main_dequant_dc(dc[at * 6 + blk], pp.prec) : dec::main_dequant(lv[(at * 6 + blk) * 64 + l], weight, intra, qscale);
-        const int odd = __popcll(__ballot(f & 1)) & 1;
-        if (!odd && l == 63) f = dec::mismatch(f);
-        F[blk][l] = f;
-    }
-    __syncthreads();
-    const int blk8 = (int)(l >> 3), r8 = (int)(l & 7u);
-    const bool mine = l < 48 && ((m.cbp >> (5 - blk8)) & 1);
-    if (mine) {
-        int32_t a[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] = F[blk8][r8 * 8 + j];
-        dec::idct_1d(a, true, dec::kIso);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) F[blk8][r8 * 8 + j] = a[j];
-    }
-    __syncthreads();
-    if (mine) {
-        int32_t a[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] = F[blk8][j * 8 + r8];
-        dec::idct_1d(a, false, dec::kIso);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) F[blk8][j * 8 + r8] = a[j];
-    }
-    __syncthreads();
-    {   // luma: four samples of one row per lane; the row's block and the row inside it through the field-DCT map
-        const uint32_t y = l >> 2, x0 = (l & 3u) * 4u, blk = dec::il_luma_block(x0, y, m.dct_type), brow = dec::il_luma_row(y, m.dct_type);
-        const bool coded = (m.cbp >> (5 - blk)) & 1;
-        const int px = (int)(16u * col + x0), py = (int)(16u * row + y);
-        uint32_t v = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int32_t pred = intra ? 128 : dec::il_predict(fwd, bwd, (int)W, px + j, py, m, false);
-            const int32_t res = coded ? F[blk][brow * 8u + ((x0 + j) & 7u)] : 0;
-            v |= (uint32_t)dec::clip255(pred + res) << (8 * j);
-        }
-        *(uint32_t *)(cur + (size_t)(16u * row + y) * W + 16u * col + x0) = v;
-    }
-    {   // chroma: two samples per lane, U in the first half of the wavefront; frame blocks always
-        const uint32_t pl = l >> 5, y = (l >> 2) & 7u, x0 = (l & 3u) * 2u;
-        const bool coded = (m.cbp >> (1 - pl)) & 1;
-        const size_t plane = (size_t)W * H + (size_t)pl * CW * (H / 2u);
-        const int px = (int)(8u * col + x0), py = (int)(8u * row + y);
-        uint32_t v = 0;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int32_t pred = intra ? 128 : dec::il_predict(fwd + plane, bwd + plane, (int)CW, px + j, py, m, true);
-            const int32_t res = coded ? F[4u + pl][y * 8u + x0 + j] : 0;
-            v |= (uint32_t)dec::clip255(pred + res) << (8 * j);
-        }
-        *(uint16_t *)(cur + plane + (size_t)(8u * row + y) * CW + 8u * col + x0) = (uint16_t)v;
-    }
+    imb_recon(F, mb[at], dec::params_unpack(pics[C.gpic].params), mats_all + (size_t)C.stream * kDsmMatrices, dc, lv, at, buf + C.buf_off, buf + C.fwd_off,
+              buf + C.bwd_off, W, H, CW, k % mbw, k / mbw, l);
 }
-
-typedef uint32_t dsm_store_t __attribute__((ext_vector_type(4)));
 
 // picture first + blockIdx.y of the chunk's table into dst: bytes [out_off, out_off + fb) of the output, iff its stream is OK.  A
 // 16-byte unit of the destination that lies inside the frame is one aligned store; the units at the frame's edges go byte by byte, so
 // two frames that share a unit never write each other's bytes
-__global__ __launch_bounds__(kDsmThreads) void k_dsm_out(const DsmState *__restrict__ sts, const dec::MainChunkPic *__restrict__ tab, uint32_t first,
+__global__ __launch_bounds__(kDsmThreads) void k_dsm_out(const DsState *__restrict__ sts, const dec::MainChunkPic *__restrict__ tab, uint32_t first,
                                                          const uint8_t *__restrict__ buf, uint8_t *__restrict__ dst, int layout)
 {
     const dec::MainChunkPic C = tab[first + blockIdx.y];
     if (sts[C.stream].status != dec::kOk) return;
-    const uint32_t w = C.w, h = C.h, W = 16u * C.mbw, H = 16u * C.mbh;
-    const uint8_t *pic = buf + C.buf_off;
-    const ull lo = C.out_off, hi = lo + C.fb;
-    const ull lead = (ull)(uintptr_t)dst & 15ull;
-    const ull u0 = (lo + lead) >> 4, u1 = (hi + lead + 15ull) >> 4;
-    for (ull g = u0 + (ull)blockIdx.x * kDsmThreads + threadIdx.x; g < u1; g += (ull)gridDim.x * kDsmThreads) {
-        const long long o0 = (long long)(g << 4) - (long long)lead;
-        const int k0 = o0 < (long long)lo ? (int)((long long)lo - o0) : 0, k1 = (long long)hi - o0 < 16 ? (int)((long long)hi - o0) : 16;
-        if (k0 >= k1) continue;
-        uint32_t q = (uint32_t)((ull)(o0 + k0) - lo);
-        dec::OutAt at = dec::out_locate(q, w, h, layout);
-        uint32_t v[4] = {0, 0, 0, 0};
-        for (int k = k0; k < k1; ++k) {
-            v[k >> 2] |= (uint32_t)dec::pic_sample(pic, W, H, at) << (8 * (k & 3));
-            if (k + 1 == k1) break;
-            ++q;
-            if (at.run > 1) dec::out_step(at, layout);
-            else at = dec::out_locate(q, w, h, layout);
-        }
-        if (k0 == 0 && k1 == 16) {
-            *(__attribute__((address_space(1))) dsm_store_t *)(dst + o0) = dsm_store_t{v[0], v[1], v[2], v[3]};
-        } else {
-            for (int k = k0; k < k1; ++k) dst[o0 + k] = (uint8_t)(v[k >> 2] >> (8 * (k & 3)));
-        }
+    out_picture(buf + C.buf_off, C.w, C.h, 16u * C.mbw, 16u * C.mbh, C.out_off, C.out_off + C.fb, dst, layout, kDsmThreads);
+}
+
+void dsm_out(hipStream_t s, const DsState *d_st, const dec::MainChunkPic *tab, size_t count, uint32_t most_units, const uint8_t *buf, uint8_t *dst, int layout)
+{
+    const unsigned gx = (unsigned)std::min<size_t>(((size_t)most_units + kDsmThreads - 1) / kDsmThreads, 1024);
+    for (size_t y = 0; y < count; y += 65535) {                       // (a grid's second dimension ends there)
+        k_dsm_out<<<dim3(gx, (unsigned)std::min<size_t>(count - y, 65535)), kDsmThreads, 0, s>>>(d_st, tab, (uint32_t)y, buf, dst, layout);
+        HIPCHK(hipGetLastError());
     }
 }
 
-__global__ void k_dsm_finish(const DsmState *sts, uint32_t n, DsmVerdict *h_v)
+int ds_main_first(m2v_enc *e, hipStream_t s, const char *entry, const uint8_t *es, const uint64_t *off, const uint64_t *bytes, size_t n, size_t pic_bytes,
+                  bool slices, const DsPlanLaunch &plan, DsMainFirst &out)
 {
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < n) h_v[b] = DsmVerdict{sts[b].err, sts[b].status, 0};
+    std::vector<size_t> ev_cap(n);
+    for (size_t b = 0; b < n; ++b) ev_cap[b] = std::max<size_t>(256, bytes[b] / 16 + 64);      // a guess per stream: a second run takes the counts of the first
+    out.rec.resize(n); out.mbh.resize(n); out.pic_base.resize(n);
+    timer_break(e);
+    for (int run = 0; run < 2; ++run) {
+        size_t tiles = 0, evs = 0, pics = 0;
+        const size_t in_bytes = ds_up64(n * sizeof(DsIn)), st_bytes = ds_up64(n * sizeof(DsState)), rec_bytes = ds_up64(n * sizeof(m2v_decode_stat)),
+                     mbh_bytes = ds_up64(n * sizeof(uint32_t));
+        for (size_t b = 0; b < n; ++b) pics += ev_cap[b] / 3 + 2;
+        const size_t sl_bytes = slices ? ds_up64(pics * sizeof(uint32_t)) : 0;
+        ensure_pinned(e->h_ds, e->h_ds_cap, in_bytes + st_bytes + rec_bytes + mbh_bytes + sl_bytes + pics + 64);
+        auto *h_in = (DsIn *)e->h_ds;
+        auto *h_st = (DsState *)(e->h_ds + in_bytes);
+        auto *h_rec = (m2v_decode_stat *)(e->h_ds + in_bytes + st_bytes);
+        auto *h_mbh = (uint32_t *)(e->h_ds + in_bytes + st_bytes + rec_bytes);
+        auto *h_sl = slices ? (uint32_t *)(e->h_ds + in_bytes + st_bytes + rec_bytes + mbh_bytes) : nullptr;
+        uint8_t *h_types = e->h_ds + in_bytes + st_bytes + rec_bytes + mbh_bytes + sl_bytes;
+        pics = 0;
+        for (size_t b = 0; b < n; ++b) {
+            const size_t nb = bytes[b], nt = nb < 4 ? 0 : (nb + dec::kScanTile - 1) / dec::kScanTile;
+            if (ev_cap[b] > 0x7FFFFFFFu) { e->set_err("%s: stream %zu holds more than 2^31 start codes", entry, b); return M2V_E_PARAM; }
+            if (tiles + nt > 0x7FFFFFFFu) { e->set_err("%s: the streams are longer than 2^31 scan tiles", entry); return M2V_E_PARAM; }
+            const size_t pic_cap = ev_cap[b] / 3 + 2;
+            h_in[b] = DsIn{off[b], nb, evs, pics, (uint32_t)tiles, (uint32_t)nt, (uint32_t)ev_cap[b], (uint32_t)pic_cap};
+            h_st[b] = DsState{dec::kNone, 0, 0, dec::kOk, 0, 0};
+            out.pic_base[b] = pics;
+            tiles += nt; evs += ev_cap[b]; pics += pic_cap;
+        }
+        if (pics > 0xFFFFFFFFull) { e->set_err("%s: more than 2^32 pictures", entry); return M2V_E_PARAM; }
+        e->d_ds_in.ensure(in_bytes);
+        e->d_dec_st.ensure(st_bytes);
+        e->d_dec_tiles.ensure(std::max<size_t>(tiles, 1));
+        e->d_dec_ev.ensure(evs);
+        e->d_dec_pics.ensure(pics * pic_bytes);
+        e->d_dec_main.ensure(n * kDsmMatrices);
+        auto *d_in = (const DsIn *)e->d_ds_in.p;
+        auto *d_st = (DsState *)e->d_dec_st.p;
+        HIPCHK(hipMemcpyAsync(e->d_ds_in.p, h_in, in_bytes, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_st, h_st, st_bytes, hipMemcpyHostToDevice, s));
+        ds_scan(s, es, d_in, n, tiles, d_st, e->d_dec_tiles.p, e->d_dec_ev.p);
+        plan(d_in, d_st, h_types, h_sl, h_rec, h_mbh);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(s));                              // the call's one wait for the plan: every stream's pictures, size, rows, types, slices
+        bool again = false;
+        for (size_t b = 0; b < n; ++b) {
+            out.rec[b] = h_rec[b];
+            out.mbh[b] = h_mbh[b];
+            if (out.rec[b].status == dec::kEvents) { again = true; ev_cap[b] = out.rec[b].pictures; }      // (the count of events travels there)
+        }
+        out.types.assign(h_types, h_types + pics);
+        if (slices) out.nsl.assign(h_sl, h_sl + pics);
+        if (!again) break;
+    }
+    for (m2v_decode_stat &r : out.rec)                                // still too small behind the second run: refused
+        if (r.status == dec::kEvents) { const uint64_t nb = r.es_bytes; r = m2v_decode_stat{}; r.es_bytes = nb; r.status = M2V_DEC_SYNTAX; }
+    return M2V_OK;
 }
 
 }  // namespace m2v
 
 struct DecodeStreamsMainArgs { const uint8_t *es; const uint64_t *off, *bytes; size_t n; uint8_t *dst; size_t cap; int layout; unsigned flags; hipStream_t s; };
-
-static size_t dsm_up64(size_t v) { return (v + 63) & ~(size_t)63; }
 
 static int decode_streams_main_impl(m2v_enc *e, void *argp)
 {
@@ -436,94 +303,27 @@ static int decode_streams_main_impl(m2v_enc *e, void *argp)
     e->d_dec_st.recorded = e->d_dec_ev.recorded = e->d_dec_pics.recorded = e->d_dec_mb.recorded = e->d_dec_dc.recorded = false;
     e->d_dec_lv.recorded = e->d_dec_buf.recorded = e->d_dec_tiles.recorded = e->d_dec_list.recorded = e->d_dec_main.recorded = false;
     e->d_ds_in.recorded = e->d_ds_tab.recorded = false;
-    std::vector<size_t> ev_cap(n);
-    for (size_t b = 0; b < n; ++b) ev_cap[b] = std::max<size_t>(256, a->bytes[b] / 16 + 64);      // a guess per stream: a second run takes the counts of the first
-    std::vector<m2v_decode_stat> rec(n);
-    std::vector<uint8_t> types;
-    std::vector<uint32_t> mbh(n);
-    std::vector<size_t> pic_base(n);
-    timer_break(e);
-    for (int run = 0; run < 2; ++run) {
-        size_t tiles = 0, evs = 0, pics = 0;
-        const size_t in_bytes = dsm_up64(n * sizeof(DsmIn)), st_bytes = dsm_up64(n * sizeof(DsmState)), rec_bytes = dsm_up64(n * sizeof(m2v_decode_stat)),
-                     mbh_bytes = dsm_up64(n * sizeof(uint32_t));
-        for (size_t b = 0; b < n; ++b) pics += ev_cap[b] / 3 + 2;
-        ensure_pinned(e->h_ds, e->h_ds_cap, in_bytes + st_bytes + rec_bytes + mbh_bytes + pics + 64);
-        auto *h_in = (DsmIn *)e->h_ds;
-        auto *h_st = (DsmState *)(e->h_ds + in_bytes);
-        auto *h_rec = (m2v_decode_stat *)(e->h_ds + in_bytes + st_bytes);
-        auto *h_mbh = (uint32_t *)(e->h_ds + in_bytes + st_bytes + rec_bytes);
-        uint8_t *h_types = e->h_ds + in_bytes + st_bytes + rec_bytes + mbh_bytes;
-        pics = 0;
-        for (size_t b = 0; b < n; ++b) {
-            const size_t nb = a->bytes[b], nt = nb < 4 ? 0 : (nb + dec::kScanTile - 1) / dec::kScanTile;
-            if (ev_cap[b] > 0x7FFFFFFFu) { e->set_err("m2v_decode_streams_main_device: stream %zu holds more than 2^31 start codes", b); return M2V_E_PARAM; }
-            if (tiles + nt > 0x7FFFFFFFu) { e->set_err("m2v_decode_streams_main_device: the streams are longer than 2^31 scan tiles"); return M2V_E_PARAM; }
-            const size_t pic_cap = ev_cap[b] / 3 + 2;
-            h_in[b] = DsmIn{a->off[b], nb, evs, pics, (uint32_t)tiles, (uint32_t)nt, (uint32_t)ev_cap[b], (uint32_t)pic_cap};
-            h_st[b] = DsmState{dec::kNone, 0, 0, dec::kOk, 0, 0};
-            pic_base[b] = pics;
-            tiles += nt; evs += ev_cap[b]; pics += pic_cap;
-        }
-        if (pics > 0xFFFFFFFFull) { e->set_err("m2v_decode_streams_main_device: more than 2^32 pictures"); return M2V_E_PARAM; }
-        e->d_ds_in.ensure(in_bytes);
-        e->d_dec_st.ensure(st_bytes);
-        e->d_dec_tiles.ensure(std::max<size_t>(tiles, 1));
-        e->d_dec_ev.ensure(evs);
-        e->d_dec_pics.ensure(pics * sizeof(DsmPic));
-        e->d_dec_main.ensure(n * kDsmMatrices);
-        auto *d_in = (const DsmIn *)e->d_ds_in.p;
-        auto *d_st = (DsmState *)e->d_dec_st.p;
-        HIPCHK(hipMemcpyAsync(e->d_ds_in.p, h_in, in_bytes, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(d_st, h_st, st_bytes, hipMemcpyHostToDevice, s));
-        if (tiles) {
-            const unsigned gx = (unsigned)std::min<size_t>(tiles, 4096);
-            k_dsm_scan<false><<<gx, kDsmThreads, 0, s>>>(a->es, d_in, (uint32_t)n, (uint32_t)tiles, d_st, e->d_dec_tiles.p, e->d_dec_ev.p);
-            HIPCHK(hipGetLastError());
-            k_dsm_tiles<<<(unsigned)n, kDsmThreads, 0, s>>>(d_in, e->d_dec_tiles.p, d_st);
-            HIPCHK(hipGetLastError());
-            k_dsm_scan<true><<<gx, kDsmThreads, 0, s>>>(a->es, d_in, (uint32_t)n, (uint32_t)tiles, d_st, e->d_dec_tiles.p, e->d_dec_ev.p);
-            HIPCHK(hipGetLastError());
-        }
+    DsMainFirst F;
+    const int err = ds_main_first(e, s, "m2v_decode_streams_main_device", a->es, a->off, a->bytes, n, sizeof(DsmPic), false,
+                                  [&](const DsIn *d_in, DsState *d_st, uint8_t *h_types, uint32_t *, m2v_decode_stat *h_rec, uint32_t *h_mbh) {
         k_dsm_plan<<<(unsigned)n, kDsmThreads, 0, s>>>(a->es, d_in, e->d_dec_ev.p, d_st, (DsmPic *)e->d_dec_pics.p, h_types, h_rec, h_mbh, e->d_dec_main.p, a->flags);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(s));                              // the call's one wait for the plan: every stream's pictures, size, rows, types
-        bool again = false;
-        for (size_t b = 0; b < n; ++b) {
-            rec[b] = h_rec[b];
-            mbh[b] = h_mbh[b];
-            if (rec[b].status == dec::kEvents) { again = true; ev_cap[b] = rec[b].pictures; }      // (the count of events travels there)
-        }
-        types.assign(h_types, h_types + pics);
-        if (!again) break;
-    }
+    }, F);
+    if (err != M2V_OK) return err;
+    const std::vector<m2v_decode_stat> &rec = F.rec;
+    const std::vector<size_t> &pic_base = F.pic_base;
     std::vector<dec::MainStreamInfo> info(n);
-    for (size_t b = 0; b < n; ++b) {
-        if (rec[b].status == dec::kEvents) { const uint64_t nb = rec[b].es_bytes; rec[b] = m2v_decode_stat{}; rec[b].es_bytes = nb; rec[b].status = M2V_DEC_SYNTAX; }
-        info[b] = dec::MainStreamInfo{rec[b].status, rec[b].pictures, rec[b].width, rec[b].height, mbh[b], types.data() + pic_base[b]};
-    }
+    for (size_t b = 0; b < n; ++b) info[b] = dec::MainStreamInfo{rec[b].status, rec[b].pictures, rec[b].width, rec[b].height, F.mbh[b], F.types.data() + pic_base[b]};
     dec::MainStreamsPlan P = dec::plan_streams_main(info.data(), n, a->cap, a->dst == nullptr, e->decode_batch, (a->flags & M2V_DECS_B_PICTURES) != 0);
     for (dec::MainChunkPic &c : P.pics) c.gpic = (uint32_t)(pic_base[c.stream] + c.pic);
     for (dec::MainChunkPic &c : P.pre) c.gpic = (uint32_t)(pic_base[c.stream] + c.pic);
-    auto report = [&](const DsmVerdict *v) {
-        for (size_t b = 0; b < n; ++b) {
-            m2v_decode_stream_stat r{a->off[b], P.out_offset[b], rec[b]};
-            if (r.rec.status == M2V_DEC_OK) {
-                if (P.overflow[b]) r.rec.status = M2V_DEC_OVERFLOW;
-                else if (v && v[b].status != dec::kOk) { r.rec.status = v[b].status; r.rec.err_offset = v[b].err; }
-                else r.rec.out_bytes = r.rec.frame_bytes * r.rec.pictures;
-            }
-            e->ds_q.push(&r, &r + 1);
-        }
-    };
-    if (!a->dst || P.pics.empty()) { report(nullptr); return M2V_OK; }
-    const size_t tab_bytes = dsm_up64(P.pics.size() * sizeof(dec::MainChunkPic)), pre_bytes = dsm_up64(P.pre.size() * sizeof(dec::MainChunkPic)),
-                 list_bytes = dsm_up64(P.list.size() * sizeof(uint32_t));
-    ensure_pinned(e->h_ds_tab, e->h_ds_tab_cap, tab_bytes + pre_bytes + list_bytes + n * sizeof(DsmVerdict) + 64);
+    if (!a->dst || P.pics.empty()) { ds_report(e, a->off, n, P.out_offset, P.overflow, rec, nullptr); return M2V_OK; }
+    const size_t tab_bytes = ds_up64(P.pics.size() * sizeof(dec::MainChunkPic)), pre_bytes = ds_up64(P.pre.size() * sizeof(dec::MainChunkPic)),
+                 list_bytes = ds_up64(P.list.size() * sizeof(uint32_t));
+    ensure_pinned(e->h_ds_tab, e->h_ds_tab_cap, tab_bytes + pre_bytes + list_bytes + n * sizeof(DsVerdict) + 64);
     memcpy(e->h_ds_tab, P.pics.data(), P.pics.size() * sizeof(dec::MainChunkPic));
     if (!P.pre.empty()) memcpy(e->h_ds_tab + tab_bytes, P.pre.data(), P.pre.size() * sizeof(dec::MainChunkPic));
     memcpy(e->h_ds_tab + tab_bytes + pre_bytes, P.list.data(), P.list.size() * sizeof(uint32_t));
-    auto *h_v = (DsmVerdict *)(e->h_ds_tab + tab_bytes + pre_bytes + list_bytes);
+    auto *h_v = (DsVerdict *)(e->h_ds_tab + tab_bytes + pre_bytes + list_bytes);
     e->d_ds_tab.ensure(tab_bytes + pre_bytes + list_bytes);
     HIPCHK(hipMemcpyAsync(e->d_ds_tab.p, e->h_ds_tab, tab_bytes + pre_bytes + list_bytes, hipMemcpyHostToDevice, s));
     uint64_t most_mbs = 0, most_buf = 0;
@@ -532,21 +332,19 @@ static int decode_streams_main_impl(m2v_enc *e, void *argp)
     e->d_dec_dc.ensure(most_mbs * 6);
     e->d_dec_lv.ensure(most_mbs * 384);
     e->d_dec_buf.ensure(most_buf);
-    auto *d_in = (const DsmIn *)e->d_ds_in.p;
-    auto *d_st = (DsmState *)e->d_dec_st.p;
+    auto *d_in = (const DsIn *)e->d_ds_in.p;
+    auto *d_st = (DsState *)e->d_dec_st.p;
     auto *d_mb = (dec::IMb *)e->d_dec_mb.p;
     auto *d_pics = (const DsmPic *)e->d_dec_pics.p;
     auto *d_tab = (const dec::MainChunkPic *)e->d_ds_tab.p;
     auto *d_pre = (const dec::MainChunkPic *)(e->d_ds_tab.p + tab_bytes);
     auto *d_list = (const uint32_t *)(e->d_ds_tab.p + tab_bytes + pre_bytes);
     const uint8_t *d_mats = e->d_dec_main.p;
-    const unsigned gj = (unsigned)((n + 63) / 64);
     if (P.pre_slices) {
         k_dsm_slices<false><<<(P.pre_slices + 63u) / 64u, 64, 0, s>>>(a->es, d_in, e->d_dec_ev.p, d_st, d_pics, d_pre, (uint32_t)P.pre.size(), P.pre_slices, nullptr,
                                                                     nullptr, nullptr);
         HIPCHK(hipGetLastError());
-        k_dsm_judge<<<gj, 64, 0, s>>>(d_st, (uint32_t)n);
-        HIPCHK(hipGetLastError());
+        ds_judge(s, d_st, n);
     }
     for (const dec::MainStreamsChunk &C : P.chunks) {
         const dec::MainChunkPic *tab = d_tab + C.first;
@@ -554,8 +352,7 @@ static int decode_streams_main_impl(m2v_enc *e, void *argp)
         k_dsm_slices<true><<<(C.slices + 63u) / 64u, 64, 0, s>>>(a->es, d_in, e->d_dec_ev.p, d_st, d_pics, tab, (uint32_t)C.count, C.slices, d_mb, e->d_dec_dc.p,
                                                                e->d_dec_lv.p);
         HIPCHK(hipGetLastError());
-        k_dsm_judge<<<gj, 64, 0, s>>>(d_st, (uint32_t)n);
-        HIPCHK(hipGetLastError());
+        ds_judge(s, d_st, n);
         auto recon = [&](const dec::MainStreamsChunk::Step &S) {
             for (size_t y = 0; y < S.count; y += 65535) {             // (a grid's second dimension ends there)
                 k_dsm_recon<<<dim3(S.most_mbs, (unsigned)std::min<size_t>(S.count - y, 65535)), 64, 0, s>>>(d_st, tab, d_list + S.off + y, d_pics, d_mats, d_mb,
@@ -565,19 +362,14 @@ static int decode_streams_main_impl(m2v_enc *e, void *argp)
         };
         for (const dec::MainStreamsChunk::Step &S : C.steps) recon(S);
         recon(C.b);                                                   // every B picture of the chunk, of all streams, at once: their anchors are done
-        const unsigned gx = (unsigned)std::min<size_t>(((size_t)C.most_units + kDsmThreads - 1) / kDsmThreads, 1024);
-        for (size_t y = 0; y < C.count; y += 65535) {
-            k_dsm_out<<<dim3(gx, (unsigned)std::min<size_t>(C.count - y, 65535)), kDsmThreads, 0, s>>>(d_st, tab, (uint32_t)y, e->d_dec_buf.p, a->dst, a->layout);
-            HIPCHK(hipGetLastError());
-        }
+        dsm_out(s, d_st, tab, C.count, C.most_units, e->d_dec_buf.p, a->dst, a->layout);
         // the next chunk's carried anchors: slot 0 first (it may come from slot 1)
         if (C.carry0_from >= 0) HIPCHK(hipMemcpyAsync(e->d_dec_buf.p, e->d_dec_buf.p + C.carry0_from, C.carry_bytes, hipMemcpyDeviceToDevice, s));
         if (C.carry1_from >= 0) HIPCHK(hipMemcpyAsync(e->d_dec_buf.p + P.carry, e->d_dec_buf.p + C.carry1_from, C.carry_bytes, hipMemcpyDeviceToDevice, s));
     }
-    k_dsm_finish<<<gj, 64, 0, s>>>(d_st, (uint32_t)n, h_v);
-    HIPCHK(hipGetLastError());
+    ds_finish(s, d_st, n, h_v);
     HIPCHK(hipStreamSynchronize(s));
-    report(h_v);
+    ds_report(e, a->off, n, P.out_offset, P.overflow, rec, h_v);
     return M2V_OK;
 }
 

@@ -1,7 +1,6 @@
-// m2v_decode_t.hip — Table B-15, concealment motion vectors and dual prime for m2v_decode_device (option "decode_mb_tools" = 1 on top of
-// "decode_extended" = 1, with "decode_b_pictures" and "decode_interlaced" 0 or 1 each).  Modelled on m2v_decode_x.hip, whose plan, tables
-// and launches these are: m2v_decode.hip keeps the scan; this unit holds the plan and everything behind the plan's wait, in kernels of
-// its own so that those of the other five units come out of the compiler exactly as they did.
+// m2v_decode_t.hip — the plan of Table B-15, concealment motion vectors and dual prime for m2v_decode_device (option "decode_mb_tools"
+// = 1 on top of "decode_extended" = 1, with "decode_b_pictures" and "decode_interlaced" 0 or 1 each).  Everything behind the plan's
+// wait is m2v_decode_x.hip's, which takes the option as `tools`.
 // decoder.decode_main(extended=True, mb_tools=True) is the definition; every function that decides a bit, a column or a verdict is a t_
 // (or x_ / il_ / bp_ / main_) function of m2v_decode_kernels.hpp.
 //
@@ -9,19 +8,16 @@
 //                concealment_motion_vectors and top_field_first are kept in bits 21 .. 23 of the packed parameters, and a P picture's
 //                "backward" picture is its forward reference - a dual-prime macroblock's record is a field-based one with both
 //                directions, and the reconstruction reads it as such.
-//   k_dt_slices  one lane per slice EVENT of the chunk, as k_dx_slices, walking with dec::t_slice: one macroblock function for every
-//                picture kind, Table B-15 by dec::vlc_ac15 - two dependent table loads a code, as dec::vlc_ac.
-//   k_dt_mats, k_dt_cont, k_dt_judge, k_dt_recon, k_dt_out, k_dt_finish   k_dx_*'s text (a kernel is launched from the unit that holds it).
 //
-// The chunk's buffer, the steps of the anchors and the single launch for a chunk's B pictures are m2v_decode_b.hip's.  Records and
-// levels stay indexed by macroblock address: nothing behind the walk knows how a row was cut.
+// Why this kernel has a unit to itself: it differs from k_dx_plan in three lines, and as k_dx_plan<true> beside k_dx_plan<false> it
+// was tried.  dec::x_event then has two callers in one unit (the plan, and dec::t_event), the compiler no longer inlines it into
+// either, and both plans go from 24 to 40 bytes of scratch a lane and from 168 to 216 VGPRs (profiles/decode_shared.json).  In two
+// units each plan compiles to what it was.  Folding them needs dec::x_event forced inline in m2v_decode_kernels.hpp.
 #include "m2v_decode_state.hpp"
 
 static_assert(sizeof(dec::IMb) == 32, "the interlaced record is two of the module's");
 
 namespace m2v {
-
-constexpr uint32_t kNoPic = 0xFFFFFFFFu;
 
 __global__ __launch_bounds__(kDecThreads) void k_dt_plan(const uint8_t *__restrict__ es, unsigned long long n, const unsigned long long *__restrict__ ev, DecState *st,
                                                          DecPic *__restrict__ pics, uint32_t pic_cap, uint8_t *h_types, unsigned long long cap, int probe,
@@ -173,301 +169,12 @@ __global__ __launch_bounds__(kDecThreads) void k_dt_plan(const uint8_t *__restri
     *h_rec = r;
 }
 
-struct DecTSink {
-    dec::IMb *mb_;
-    int32_t *dc_;
-    int16_t *lv_;
-    M2V_HD void mb(int col, const dec::IMb &m, const int32_t (&dc)[6])
-    {
-        mb_[col] = m;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) dc_[col * 6 + k] = dc[k];
-    }
-    M2V_HD void level(int col, int blk, uint32_t i, int32_t l) { lv_[(col * 6 + blk) * 64 + (int)i] = (int16_t)l; }
-};
-
-// pictures [p0, p0 + np) of any type with `total` slices: one slice EVENT per lane, into the row its code names.  The lane leaves its
-// span; a slice that cannot be read lowers st->err.  Two slices that overlap write the same records - the judge refuses the stream
-// before anything reads them
-__global__ __launch_bounds__(64) void k_dt_slices(const uint8_t *__restrict__ es, unsigned long long n, const unsigned long long *__restrict__ ev, DecState *st,
-                                                  const DecPic *__restrict__ pics, const DecXPic *__restrict__ xp, uint32_t p0, uint32_t np, uint32_t total,
-                                                  dec::IMb *mb, int32_t *dc, int16_t *lv, uint32_t *__restrict__ spans)
-{
-    if (st->status != dec::kOk) return;
-    const uint32_t mbw = st->mbw, mbh = st->mbh, nev = st->nev;
-    const uint32_t g = blockIdx.x * 64u + threadIdx.x;
-    if (g >= total) return;
-    uint32_t k;
-    const uint32_t pic = dec::x_slice_pic(xp + p0, np, g, k);
-    const DecPic P = pics[p0 + pic];
-    const DecXPic Q = xp[p0 + pic];
-    const uint32_t i = Q.slice0 + k;
-    spans[g] = 0u;
-    if (k >= Q.nslices || i >= nev) return;                            // (the plan accepted the picture: its slices are there)
-    const unsigned long long start = dec::ev_pos(ev[i]), end = i + 1 < nev ? dec::ev_pos(ev[i + 1]) : n;
-    const uint32_t code = dec::ev_code(ev[i]);
-    if (code < 1u || code > mbh) { atomicMin(&st->err, start); return; }      // (the plan's grammar: 1 <= code <= mbh)
-    const size_t first = ((size_t)pic * mbh + (code - 1u)) * mbw;
-    DecTSink sink{mb + first, dc + first * 6, lv + first * 384};
-    int c0, c1;
-    const bool ok = dec::t_slice(es, start, end, P.type, dec::t_params_unpack(Q.params), (int)mbw, (int)mbh, (int)code - 1, sink, c0, c1);
-    spans[g] = dec::x_span_pack(ok, code, c0, c1);
-    if (!ok) atomicMin(&st->err, start);
-}
-
-// continuity behind the walk: every readable slice against the span of the slice in front of it in its picture
-__global__ __launch_bounds__(64) void k_dt_cont(const unsigned long long *__restrict__ ev, DecState *st, const DecXPic *__restrict__ xp, uint32_t p0, uint32_t np,
-                                                uint32_t total, const uint32_t *__restrict__ spans)
-{
-    if (st->status != dec::kOk) return;
-    const uint32_t g = blockIdx.x * 64u + threadIdx.x;
-    if (g >= total) return;
-    uint32_t k;
-    const uint32_t pic = dec::x_slice_pic(xp + p0, np, g, k);
-    const DecXPic Q = xp[p0 + pic];
-    const uint32_t cur = spans[g];
-    if (!(cur >> 31) || k >= Q.nslices || Q.slice0 + k >= st->nev) return;      // (not readable: reported by its walk)
-    if (!dec::x_continuous(cur, k ? spans[g - 1] : 0u, k, Q.nslices, st->mbw)) atomicMin(&st->err, dec::ev_pos(ev[Q.slice0 + k]));
-}
-
-__global__ void k_dt_judge(DecState *st)
-{
-    if (st->status == dec::kOk && st->err != dec::kNone) st->status = dec::kSyntax;
-}
-
-// the matrix table: block p writes picture p's 128 weights, raster order - the sequence's, or those of the extension in force
-__global__ __launch_bounds__(128) void k_dt_mats(const uint8_t *__restrict__ es, unsigned long long n, const unsigned long long *__restrict__ ev, const DecState *__restrict__ st,
-                                                 const uint8_t *__restrict__ mats, const DecXPic *__restrict__ xp, uint8_t *__restrict__ table)
-{
-    if (st->status != dec::kOk || blockIdx.x >= st->npics) return;
-    const uint32_t p = blockIdx.x, l = threadIdx.x, m = l >> 6, t = l & 63u;
-    const uint32_t src = m ? xp[p].mn : xp[p].mi;
-    table[(size_t)p * 128u + l] = (uint8_t)dec::x_matrix_weight(es, n, (const uint64_t *)ev, st->nev, src, (int)m, t, mats + 64u * m);
-}
-
-// the chunk's slot of the picture with coded index r, as m2v_decode_b.hip's
-__device__ inline uint32_t dt_slot(uint32_t r, uint32_t p0, uint32_t c1) { return r == kNoPic ? 0u : r >= p0 ? 2u + (r - p0) : r == c1 ? 1u : 0u; }
-
-// as k_di_recon, the weights from the picture's row of the matrix table: grid = (macroblocks, pictures of the launch); list: their coded indices, all of chunk [p0, ...).  Every read of a
-// reference lies inside its picture: the slice walk refused the slice otherwise (dec::il_inside), and a refused slice stops the call
-// before this kernel (k_dt_judge)
-__global__ __launch_bounds__(64) void k_dt_recon(const DecState *__restrict__ st, const uint32_t *__restrict__ list, uint32_t p0, uint32_t c1,
-                                                 const uint8_t *__restrict__ mats, const DecXPic *__restrict__ bp, const dec::IMb *__restrict__ mb,
-                                                 const int32_t *__restrict__ dc, const int16_t *__restrict__ lv, uint8_t *buf, size_t psz)
-{
-    __shared__ int32_t F[6][64];
-    if (st->status != dec::kOk) return;
-    const uint32_t mbw = st->mbw, mbh = st->mbh, mbs = mbw * mbh, W = 16u * mbw, H = 16u * mbh, CW = W / 2u;
-    const uint32_t k = blockIdx.x, l = threadIdx.x, gp = list[blockIdx.y], pic = gp - p0;
-    const DecXPic Q = bp[gp];
-    const dec::PicParams pp = dec::params_unpack(Q.params);
-    const size_t at = (size_t)pic * mbs + k;
-    const dec::IMb m = mb[at];
-    const uint32_t col = k % mbw, row = k / mbw;
-    uint8_t *cur = buf + (size_t)(pic + 2u) * psz;
-    const uint8_t *fwd = buf + (size_t)dt_slot(Q.fwd, p0, c1) * psz, *bwd = buf + (size_t)dt_slot(Q.bwd, p0, c1) * psz;
-    const bool intra = m.intra != 0;
-    const int32_t qscale = dec::main_scale(m.qcode, pp.qst), weight = mats[(size_t)gp * 128u + (intra ? 0u : 64u) + l];
-#pragma unroll
-    for (int blk = 0; blk < 6; ++blk) {
-        if (!((m.cbp >> (5 - blk)) & 1)) continue;                     // (uniform: the whole wavefront works on one macroblock)
-        int32_t f = intra && l == 0 ? dec::main_dequant_dc(dc[at * 6 + blk], pp.prec) : dec::main_dequant(lv[(at * 6 + blk) * 64 + l], weight, intra, qscale);
-        const int odd = __popcll(__ballot(f & 1)) & 1;
-        if (!odd && l == 63) f = dec::mismatch(f);
-        F[blk][l] = f;
-    }
-    __syncthreads();
-    const int blk8 = (int)(l >> 3), r8 = (int)(l & 7u);
-    const bool mine = l < 48 && ((m.cbp >> (5 - blk8)) & 1);
-    if (mine) {
-        int32_t a[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] = F[blk8][r8 * 8 + j];
-        dec::idct_1d(a, true, dec::kIso);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) F[blk8][r8 * 8 + j] = a[j];
-    }
-    __syncthreads();
-    if (mine) {
-        int32_t a[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] = F[blk8][j * 8 + r8];
-        dec::idct_1d(a, false, dec::kIso);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) F[blk8][j * 8 + r8] = a[j];
-    }
-    __syncthreads();
-    {   // luma: four samples of one row per lane; the row's block and the row inside it through the field-DCT map
-        const uint32_t y = l >> 2, x0 = (l & 3u) * 4u, blk = dec::il_luma_block(x0, y, m.dct_type), brow = dec::il_luma_row(y, m.dct_type);
-        const bool coded = (m.cbp >> (5 - blk)) & 1;
-        const int px = (int)(16u * col + x0), py = (int)(16u * row + y);
-        uint32_t v = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int32_t pred = intra ? 128 : dec::il_predict(fwd, bwd, (int)W, px + j, py, m, false);
-            const int32_t res = coded ? F[blk][brow * 8u + ((x0 + j) & 7u)] : 0;
-            v |= (uint32_t)dec::clip255(pred + res) << (8 * j);
-        }
-        *(uint32_t *)(cur + (size_t)(16u * row + y) * W + 16u * col + x0) = v;
-    }
-    {   // chroma: two samples per lane, U in the first half of the wavefront; frame blocks always
-        const uint32_t pl = l >> 5, y = (l >> 2) & 7u, x0 = (l & 3u) * 2u;
-        const bool coded = (m.cbp >> (1 - pl)) & 1;
-        const size_t plane = (size_t)W * H + (size_t)pl * CW * (H / 2u);
-        const int px = (int)(8u * col + x0), py = (int)(8u * row + y);
-        uint32_t v = 0;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int32_t pred = intra ? 128 : dec::il_predict(fwd + plane, bwd + plane, (int)CW, px + j, py, m, true);
-            const int32_t res = coded ? F[4u + pl][y * 8u + x0 + j] : 0;
-            v |= (uint32_t)dec::clip255(pred + res) << (8 * j);
-        }
-        *(uint16_t *)(cur + plane + (size_t)(8u * row + y) * CW + 8u * col + x0) = (uint16_t)v;
-    }
-}
-
-typedef uint32_t dt_store_t __attribute__((ext_vector_type(4)));
-
-// picture blockIdx.y of chunk [p0, p0 + np) into dst at its display index: bytes [display * fb, (display + 1) * fb) of the output
-__global__ __launch_bounds__(kDecThreads) void k_dt_out(const DecState *__restrict__ st, const DecXPic *__restrict__ bp, const uint8_t *__restrict__ buf, size_t psz,
-                                                        uint32_t p0, uint8_t *__restrict__ dst, int layout)
-{
-    if (st->status != dec::kOk) return;
-    const uint32_t w = st->width, h = st->height, W = 16u * st->mbw, H = 16u * st->mbh;
-    const uint32_t d = bp[p0 + blockIdx.y].display;
-    if (d >= st->npics) return;                                        // (an accepted stream's display indices are a permutation)
-    const uint8_t *pic = buf + (size_t)(blockIdx.y + 2u) * psz;
-    const unsigned long long fb = st->frame_bytes, lo = (unsigned long long)d * fb, hi = lo + fb;
-    const unsigned long long lead = (unsigned long long)(uintptr_t)dst & 15ull;
-    const unsigned long long u0 = (lo + lead) >> 4, u1 = (hi + lead + 15ull) >> 4;
-    for (unsigned long long g = u0 + (unsigned long long)blockIdx.x * kDecThreads + threadIdx.x; g < u1; g += (unsigned long long)gridDim.x * kDecThreads) {
-        const long long o0 = (long long)(g << 4) - (long long)lead;
-        const int k0 = o0 < (long long)lo ? (int)((long long)lo - o0) : 0, k1 = (long long)hi - o0 < 16 ? (int)((long long)hi - o0) : 16;
-        if (k0 >= k1) continue;
-        uint32_t q = (uint32_t)((unsigned long long)(o0 + k0) - lo);
-        dec::OutAt at = dec::out_locate(q, w, h, layout);
-        uint32_t v[4] = {0, 0, 0, 0};
-        for (int k = k0; k < k1; ++k) {
-            v[k >> 2] |= (uint32_t)dec::pic_sample(pic, W, H, at) << (8 * (k & 3));
-            if (k + 1 == k1) break;
-            ++q;
-            if (at.run > 1) dec::out_step(at, layout);
-            else at = dec::out_locate(q, w, h, layout);
-        }
-        if (k0 == 0 && k1 == 16) {
-            *(__attribute__((address_space(1))) dt_store_t *)(dst + o0) = dt_store_t{v[0], v[1], v[2], v[3]};
-        } else {
-            for (int k = k0; k < k1; ++k) dst[o0 + k] = (uint8_t)(v[k >> 2] >> (8 * (k & 3)));
-        }
-    }
-}
-
-__global__ void k_dt_finish(const DecState *st, m2v_decode_stat *h_rec)
-{
-    if (st->status == dec::kOk) { h_rec->out_bytes = st->frame_bytes * st->npics; return; }
-    h_rec->status = st->status; h_rec->err_offset = st->err; h_rec->out_bytes = 0;
-}
-
 void dec_t_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long long *ev, DecState *st, DecPic *pics, uint32_t pic_cap, uint8_t *h_types,
                 unsigned long long cap, int probe, m2v_decode_stat *h_rec, uint8_t *d_main, int b_pictures, int interlaced, uint32_t *h_mbh, uint32_t *h_sl)
 {
     k_dt_plan<<<1, kDecThreads, 0, s>>>(es, n, ev, st, pics, pic_cap, h_types, cap, probe, h_rec, d_main, (DecXPic *)(d_main + kDecMainMatrices), b_pictures, interlaced,
                                         h_mbh, h_sl);
     HIPCHK(hipGetLastError());
-}
-
-// dec_x_chunks with this unit's kernels: the matrix table once, then per chunk the walk and the continuity judge over the chunk's slices
-// (h_sl[p]: the slices in front of picture p; h_sl[pictures]: all of them) in front of the reconstruction
-void dec_t_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_t *dst, int layout, const m2v_decode_stat &R, size_t mbh, size_t B,
-                  const uint8_t *types, uint32_t *h_list, const uint32_t *h_sl, m2v_decode_stat *h_rec)
-{
-    const size_t np = R.pictures, mbw = (R.width + 15) / 16, mbs = mbw * mbh, psz = mbs * 384;
-    size_t most = 1;                                                   // the most slices of a chunk
-    for (size_t p0 = 0; p0 < np; p0 += B) most = std::max<size_t>(most, h_sl[std::min(p0 + B, np)] - h_sl[p0]);
-    const size_t span_off = (np * 128 + 3) & ~(size_t)3;
-    e->d_dec_x.ensure(span_off + most * sizeof(uint32_t));
-    e->d_dec_mb.ensure(B * mbs * sizeof(dec::IMb));
-    e->d_dec_dc.ensure(B * mbs * 6);
-    e->d_dec_lv.ensure(B * mbs * 384);
-    e->d_dec_buf.ensure((B + 2) * psz);
-    e->d_dec_list.ensure(np);
-    // every chunk's anchors ordered by their step inside the chunk - a chain starts at its I picture, or at the chunk's first anchor -,
-    // then its B pictures; and what the chunk leaves in slots 0 and 1 for the next
-    struct Launch { size_t off, count; };
-    struct Chunk { std::vector<Launch> steps; Launch b; long c1, carry0, carry1; };      // carry: the chunk's slot to copy into slot 0 / 1 (-1: nothing)
-    std::vector<Chunk> chunks;
-    long a1 = -1, a2 = -1;                                             // the last two anchors in front of the chunk, coded indices
-    for (size_t p0 = 0; p0 < np; p0 += B) {
-        const size_t nb = std::min(B, np - p0);
-        Chunk C;
-        C.c1 = a1;
-        std::vector<long> step(nb, -1);
-        long deepest = -1, prev = -1;
-        for (size_t k = 0; k < nb; ++k) {
-            if (types[p0 + k] == 3) continue;
-            step[k] = prev >= 0 && types[p0 + k] != 1 ? step[prev] + 1 : 0;
-            deepest = std::max(deepest, step[k]);
-            prev = (long)k;
-        }
-        size_t at = p0;
-        for (long j = 0; j <= deepest; ++j) {
-            const size_t first = at;
-            for (size_t k = 0; k < nb; ++k) if (step[k] == j) h_list[at++] = (uint32_t)(p0 + k);
-            C.steps.push_back(Launch{first, at - first});
-        }
-        C.b.off = at;
-        for (size_t k = 0; k < nb; ++k) if (types[p0 + k] == 3) h_list[at++] = (uint32_t)(p0 + k);
-        C.b.count = at - C.b.off;
-        auto slot = [&](long r) { return r >= (long)p0 ? 2 + (r - (long)p0) : r == C.c1 ? 1L : 0L; };
-        long n1 = a1, n2 = a2;
-        for (size_t k = 0; k < nb; ++k) if (types[p0 + k] != 3) { n2 = n1; n1 = (long)(p0 + k); }
-        C.carry0 = n2 >= 0 && slot(n2) != 0 ? slot(n2) : -1;
-        C.carry1 = n1 >= 0 && slot(n1) != 1 ? slot(n1) : -1;
-        a1 = n1; a2 = n2;
-        chunks.push_back(C);
-    }
-    auto *d_st = (DecState *)e->d_dec_st.p;
-    auto *d_mb = (dec::IMb *)e->d_dec_mb.p;
-    const uint8_t *mats = e->d_dec_x.p;                                // the matrix table: 128 bytes a picture
-    auto *spans = (uint32_t *)(e->d_dec_x.p + span_off);
-    const auto *bp = (const DecXPic *)(e->d_dec_main.p + kDecMainMatrices);
-    HIPCHK(hipMemcpyAsync(e->d_dec_list.p, h_list, np * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    k_dt_mats<<<(unsigned)np, 128, 0, s>>>(es, n, e->d_dec_ev.p, d_st, e->d_dec_main.p, bp, e->d_dec_x.p);
-    HIPCHK(hipGetLastError());
-    for (size_t p0 = 0, c = 0; p0 < np; p0 += B, ++c) {
-        const size_t nb = std::min(B, np - p0);
-        const Chunk &C = chunks[c];
-        HIPCHK(hipMemsetAsync(e->d_dec_lv.p, 0, nb * mbs * 768, s));
-        const size_t total = h_sl[p0 + nb] - h_sl[p0];                 // (every picture the plan accepted has a slice)
-        if (total) {
-            k_dt_slices<<<(unsigned)((total + 63) / 64), 64, 0, s>>>(es, n, e->d_dec_ev.p, d_st, (const DecPic *)e->d_dec_pics.p, bp, (uint32_t)p0, (uint32_t)nb,
-                                                                     (uint32_t)total, d_mb, e->d_dec_dc.p, e->d_dec_lv.p, spans);
-            HIPCHK(hipGetLastError());
-            k_dt_cont<<<(unsigned)((total + 63) / 64), 64, 0, s>>>(e->d_dec_ev.p, d_st, bp, (uint32_t)p0, (uint32_t)nb, (uint32_t)total, spans);
-            HIPCHK(hipGetLastError());
-        }
-        k_dt_judge<<<1, 1, 0, s>>>(d_st);
-        HIPCHK(hipGetLastError());
-        auto recon = [&](const Launch &l) {
-            if (!l.count) return;
-            k_dt_recon<<<dim3((unsigned)mbs, (unsigned)l.count), 64, 0, s>>>(d_st, e->d_dec_list.p + l.off, (uint32_t)p0, (uint32_t)C.c1, mats, bp, d_mb, e->d_dec_dc.p,
-                                                                            e->d_dec_lv.p, e->d_dec_buf.p, psz);
-            HIPCHK(hipGetLastError());
-        };
-        for (const Launch &l : C.steps) recon(l);
-        recon(C.b);                                                    // every B picture of the chunk at once: its anchors are done
-        const size_t units = (R.frame_bytes + 15) / 16 + 1;
-        k_dt_out<<<dim3((unsigned)std::min<size_t>((units + kDecThreads - 1) / kDecThreads, 1024), (unsigned)nb), kDecThreads, 0, s>>>(d_st, bp, e->d_dec_buf.p, psz,
-                                                                                                                                      (uint32_t)p0, dst, layout);
-        HIPCHK(hipGetLastError());
-        if (p0 + B < np) {                                             // the next chunk's carried anchors: slot 0 first (it may come from slot 1)
-            if (C.carry0 >= 0) HIPCHK(hipMemcpyAsync(e->d_dec_buf.p, e->d_dec_buf.p + (size_t)C.carry0 * psz, psz, hipMemcpyDeviceToDevice, s));
-            if (C.carry1 >= 0) HIPCHK(hipMemcpyAsync(e->d_dec_buf.p + psz, e->d_dec_buf.p + (size_t)C.carry1 * psz, psz, hipMemcpyDeviceToDevice, s));
-        }
-    }
-    k_dt_finish<<<1, 1, 0, s>>>(d_st, h_rec);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s));
 }
 
 }  // namespace m2v

@@ -33,16 +33,22 @@
 //   m2v_decode.hip    m2v_decode_device: an elementary stream in HBM back to 4:2:0 frames.  Its kernels touch no device global and nothing of
 //                     m2v_kernels.hpp, so they live in their own unit with their launches (m2v_decode_kernels.hpp holds the arithmetic, for
 //                     the device and the host alike)
-//   m2v_decode_main.hip, m2v_decode_b.hip, m2v_decode_i.hip, m2v_decode_x.hip, m2v_decode_t.hip, m2v_decode_f.hip, m2v_decode_j.hip   m2v_decode_device's other syntaxes,
-//                     each in kernels of its own: the main syntax (option "decode_syntax"), B pictures on top of it (option
-//                     "decode_b_pictures"), interlaced frame pictures (option "decode_interlaced"), several slices a row, slice header
-//                     extras and quant_matrix_extension (option "decode_extended"), and Table B-15, concealment motion vectors and dual
-//                     prime (option "decode_mb_tools"), field pictures, two a frame (option "decode_field_pictures"), and the plan for streams
-//                     cut from a broadcast (option "decode_join"); m2v_decode_state.hpp is what the eight share
+//   m2v_decode_main.hip, m2v_decode_b.hip, m2v_decode_i.hip, m2v_decode_x.hip, m2v_decode_t.hip, m2v_decode_f.hip, m2v_decode_j.hip   m2v_decode_device's other syntaxes:
+//                     the main syntax (option "decode_syntax"), B pictures on top of it (option "decode_b_pictures"), interlaced frame
+//                     pictures (option "decode_interlaced"), several slices a row, slice header extras and quant_matrix_extension (option
+//                     "decode_extended") with Table B-15, concealment motion vectors and dual prime (option "decode_mb_tools": a template
+//                     flag of m2v_decode_x.hip's slice walk; m2v_decode_t.hip holds its plan alone), field pictures, two a frame (option
+//                     "decode_field_pictures"), and the plan for streams cut from a broadcast (option "decode_join").  A unit holds what
+//                     its option changes - the plan, the slice walk, where a record, its weights and its slots come from.  What the
+//                     units have in common exists once: m2v_decode_state.hpp (the call's state, the tables, every launcher),
+//                     m2v_decode_device.hpp (the dec::IMb sink, the reconstruction of a macroblock, the output loop, slot) and
+//                     m2v_decode_chunks.hpp (the chunk schedule, plain C++)
 //   m2v_decode_streams.hip   m2v_decode_streams_device: a batch of elementary streams of any sizes in one call - the same arithmetic over a
-//                     table of streams, in kernels of its own (m2v_decode_streams.hpp lays the batch out, for the host build too)
+//                     table of streams (m2v_decode_streams.hpp lays the batch out, for the host build too).  Its scan, judge, finish and
+//                     report serve all three batch entries (m2v_decode_state.hpp declares their launchers)
 //   m2v_decode_streams_main.hip   m2v_decode_streams_main_device: the same for main-syntax streams, B pictures and interlaced frame pictures
-//                     by the call's flags, again in kernels of its own (m2v_decode_streams_main.hpp lays the batch out)
+//                     by the call's flags (m2v_decode_streams_main.hpp lays the batch out); its first pass and its output kernel serve
+//                     m2v_decode_streams_ex.hip (m2v_decode_streams_main_ex_device: the extended options by the call's flags) too
 //   m2v_demux.hip     m2v_demux_device: transport / program streams in HBM back to the elementary stream, the inverse of m2v_mux.hip and like it
 //                     a unit of its own (m2v_demux_kernels.hpp holds the arithmetic, for the device and the host alike)
 //   m2v_scale.hip     m2v_set_source_size: frames of another size resampled to the picture size in front of the conversions - the setting,
@@ -426,7 +432,7 @@ struct m2v_enc {
     int decode_interlaced = 0;            // option "decode_interlaced": frame pictures with frame_pred_frame_dct 0 on top of the main syntax (m2v_decode_i.hip)
     int decode_extended = 0;              // option "decode_extended": several slices a row, slice extras, quant_matrix_extension on top of the main syntax (m2v_decode_x.hip)
     DevBuf<uint8_t> d_dec_x;              // its matrix table (128 bytes a picture) and the spans of a chunk's slices
-    int decode_mb_tools = 0;              // option "decode_mb_tools": Table B-15, concealment vectors, dual prime on top of "decode_extended" (m2v_decode_t.hip)
+    int decode_mb_tools = 0;              // option "decode_mb_tools": Table B-15, concealment vectors, dual prime on top of "decode_extended" (m2v_decode_t.hip: the plan; m2v_decode_x.hip: the rest)
     int decode_field_pictures = 0;        // option "decode_field_pictures": picture_structure 1 / 2, two fields a frame, on top of the three above it (m2v_decode_f.hip)
     int decode_join = 0;                  // option "decode_join": M2V_JOIN_HEAD | M2V_JOIN_TAIL on top of the four above it (m2v_decode_j.hip)
     m2v_decode_join dec_join{};           // the last call's join record (m2v_decode_join_report)
