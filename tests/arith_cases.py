@@ -109,16 +109,19 @@ def build(w, h, pictures, seq=None):
                         m["mv"] = tuple(fwd)
                 sl["mbs"].append(m)
                 lmbs.append(dict(row=row, col=col, first=col == 0, intra=intra, fwd=fwd if (fwd is not None or intra or ptype == 3) else (0, 0), bwd=bwd,
-                                 motion=mb.get("motion", "frame") if (fwd is not None or bwd is not None) else "frame",
+                                 motion=mb.get("motion", "frame") if (fwd is not None or bwd is not None) else "frame", nomc=ptype == 2 and not intra and fwd is None,
                                  dct=mb.get("dct", 0) if (intra or cbp) else 0, cbp=cbp, qcode=code, blocks=lblocks))
             slices.append(sl)
         wp = dict(type=ptype, prec=prec, qst=qst, alt=alt, slices=slices, extras=extras)
         if pic.get("field"):
             wp["field"] = True
         if ptype == 3 or pic.get("field"):
-            wp["f_code"] = (1, 1, 1, 1)
+            wp["f_code"] = tuple(pic.get("f_code", (1, 1, 1, 1)))
+        elif "f_code" in pic:
+            wp["f_code"] = tuple(pic["f_code"][:2])
         wpics.append(wp)
-        lpics.append(dict(type=ptype, prec=prec, qst=qst, scan=list(scan_of(alt)), matrices=(mats[0], mats[1]), mbs=lmbs))
+        lpics.append(dict(type=ptype, prec=prec, qst=qst, scan=list(scan_of(alt)), matrices=(mats[0], mats[1]), mbs=lmbs, f_code=tuple(pic.get("f_code", (1, 1, 1, 1))),
+                          field=bool(pic.get("field"))))
     s, L = IW.stream(w, h, wpics, seq=seq)
     return s, dict(w=w, h=h, mbw=mbw, rows=rows, pictures=lpics, writer=L)
 

@@ -312,8 +312,9 @@ def build(w, h, pictures, seq=None):
                 incr = 1
             assert incr == 1
             slices.append(sl)
-        wpics.append(dict(type=ptype, ps=pic["ps"], prec=prec, alt=alt, slices=slices, f_code=(1, 1, 1, 1)))
-        lpics.append(dict(type=ptype, ps=pic["ps"], prec=prec, qst=0, scan=list(AC.scan_of(alt)), matrices=mats, mbs=lmbs))
+        f_code = tuple(pic.get("f_code", (1, 1, 1, 1)))
+        wpics.append(dict(type=ptype, ps=pic["ps"], prec=prec, alt=alt, slices=slices, f_code=f_code))
+        lpics.append(dict(type=ptype, ps=pic["ps"], prec=prec, qst=0, scan=list(AC.scan_of(alt)), matrices=mats, mbs=lmbs, f_code=f_code))
     s, L = FW.stream(w, h, wpics, seq=seq)
     return s, dict(w=w, h=h, mbw=mbw, rows=rows, pictures=lpics, writer=L)
 

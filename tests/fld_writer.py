@@ -138,7 +138,7 @@ def field_units(tref, pic, mbw, rows, L, second, frame):
                 else:                                              # component, dmvector, component, dmvector
                     (vx, vy), dmv = v
                     for t, target in enumerate((vx, vy)):
-                        TW._component(w, target, pmv[0][0][t], fc[t])
+                        TW._component(w, target, pmv[0][0][t], fc[t], L)
                         MW.put_bits(w, {0: "0", 1: "10", -1: "11"}[dmv[t]])
                     pmv[0][0] = [vx, vy]
                     pmv[1][0] = [vx, vy]

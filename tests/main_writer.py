@@ -78,6 +78,7 @@ def put_vector(w, mv, pmv, f_code, L):
         if residual is not None:
             w.put(residual, r_size)
         L["vectors"].append((f_code[c], wrap, mv[c], delta))
+        L.setdefault("codes", []).append((f_code[c], -code if delta < 0 else code, residual or 0, pmv[c]))      # what a decoder reads, and the predictor it was written against
         pmv[c] = mv[c]
 
 

@@ -247,8 +247,10 @@ def build(w, h, pictures, seq=None):
                 lmbs.append(dict(row=row, col=col, first=col == 0, intra=intra, fwd=fwd if (fwd is not None or intra) else (0, 0), bwd=None, nomc=not intra and fwd is None,
                                  motion=motion if fwd is not None else "frame", dct=mb.get("dct", 0) if (intra or cbp) else 0, cbp=cbp, qcode=pic.get("q", 2), blocks=lblocks))
             slices.append(sl)
-        wpics.append(dict(type=ptype, prec=prec, alt=alt, field=True, slices=slices, f_code=(1, 1, 1, 1), tff=pic.get("tff", 1), ivf=pic.get("ivf", 0), cmv=pic.get("cmv", 0)))
-        lpics.append(dict(type=ptype, prec=prec, qst=0, scan=list(AC.scan_of(alt)), matrices=mats, mbs=lmbs, tff=pic.get("tff", 1)))
+        f_code = tuple(pic.get("f_code", (1, 1, 1, 1)))
+        wpics.append(dict(type=ptype, prec=prec, alt=alt, field=True, slices=slices, f_code=f_code, tff=pic.get("tff", 1), ivf=pic.get("ivf", 0), cmv=pic.get("cmv", 0)))
+        lpics.append(dict(type=ptype, prec=prec, qst=0, scan=list(AC.scan_of(alt)), matrices=mats, mbs=lmbs, tff=pic.get("tff", 1), f_code=f_code, field=True,
+                          cmv=pic.get("cmv", 0)))
     s, L = TW.stream(w, h, wpics, seq=seq)
     return s, dict(w=w, h=h, mbw=mbw, rows=rows, pictures=lpics, writer=L)
 

@@ -67,9 +67,9 @@ def toward_zero(a):
     return -((-a) // 2) if a < 0 else a // 2
 
 
-def dual(ref, col, row, v, dmv, tff, wrong=()):
-    """the prediction of a dual-prime macroblock -> [16 x 16, 8 x 8, 8 x 8]"""
-    t, b = derived(v, dmv, tff, wrong)
+def dual(ref, col, row, v, dmv, tff, wrong=(), given=None):
+    """the prediction of a dual-prime macroblock -> [16 x 16, 8 x 8, 8 x 8]; given: (T, B) from tests/vec_ref.py in the place of derived()"""
+    t, b = given if given is not None else derived(v, dmv, tff, wrong)
     out = []
     for p, n in ((0, 16), (1, 8), (2, 8)):
         same, opp = [v, v], [t, b]
@@ -125,7 +125,7 @@ def frames(log, wrong=()):
         mbs = _pmv1_kept(pic["mbs"]) if "pmv1_kept" in wrong and pic["type"] == 2 else pic["mbs"]
         for mb, res in zip(mbs, R.residuals(pic)):
             if not mb["intra"] and mb.get("motion") == "dual":
-                pred = dual(anchors[-1], mb["col"], mb["row"], mb["fwd"][0], mb["fwd"][1], pic.get("tff", 1), wrong)
+                pred = dual(anchors[-1], mb["col"], mb["row"], mb["fwd"][0], mb["fwd"][1], pic.get("tff", 1), wrong, mb.get("derived"))
             else:
                 pred = R.predict(mb, pic["type"], anchors)
             col, row = mb["col"], mb["row"]

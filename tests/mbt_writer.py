@@ -98,11 +98,15 @@ def _normal(mb):
     return mb
 
 
-def _component(w, v, p, f_code):
-    """one vector component v behind its predictor p (7.6.3.1 backwards): motion_code, sign, motion_residual"""
+def _component(w, v, p, f_code, L=None):
+    """one vector component v behind its predictor p (7.6.3.1 backwards): motion_code, sign, motion_residual; L: the log that gets it"""
     tmp = D._Writer()
     pmv = [p, 0]
-    MW.put_vector(tmp, (v, 0), pmv, (f_code, 1), dict(vectors=[]))
+    own = dict(vectors=[])
+    MW.put_vector(tmp, (v, 0), pmv, (f_code, 1), own)
+    if L is not None:
+        L.setdefault("dual_vectors", []).append(own["vectors"][0])
+        L.setdefault("codes", []).append(own["codes"][0])
     w.s += tmp.s[:-1]                                              # (the second component, 0 behind 0, is motion_code '1')
     assert tmp.s[-1] == "1"
 
@@ -184,7 +188,7 @@ def picture_units(n, pic, mbw, mbh, L):
                 elif motion == "dual":                             # component, dmvector, component, dmvector; the vertical one a field vector
                     (vx, vy), dmv = v
                     for t, (target, p) in enumerate(((vx, pmv[0][0][0]), (vy, pmv[0][0][1] >> 1))):
-                        _component(w, target, p, fc[t])
+                        _component(w, target, p, fc[t], L)
                         MW.put_bits(w, {0: "0", 1: "10", -1: "11"}[dmv[t]])
                     pmv[0][0] = [vx, 2 * vy]
                     pmv[1][0] = [vx, 2 * vy]
