@@ -132,6 +132,9 @@ DECODE_STAT_DTYPE = np.dtype([("es_bytes", "<u8"), ("out_bytes", "<u8"), ("frame
 DECODE_STREAM_STAT_DTYPE = np.dtype([("es_offset", "<u8"), ("out_offset", "<u8"), ("rec", DECODE_STAT_DTYPE)])
 # m2v_decode_join: the join record of the last decode_device, 32 bytes (Mpeg2Encoder.decode_join_report)
 DECODE_JOIN_DTYPE = np.dtype([("join_offset", "<u8"), ("tail_offset", "<u8"), ("dropped_leading", "<u4"), ("dropped_trailing", "<u4"), ("reserved", "<u4", (2,))])
+# m2v_decode_conceal: the concealment report of the last decode_device, 32 bytes (Mpeg2Encoder.decode_conceal_report)
+DECODE_CONCEAL_DTYPE = np.dtype([("first_offset", "<u8"), ("bad_slices", "<u4"), ("concealed_rows", "<u4"), ("grey_rows", "<u4"), ("damaged_pictures", "<u4"),
+                                 ("reserved", "<u4", (2,))])
 DEC_JOINS = {"head": 1, "tail": 2, "both": 3}                    # M2V_JOIN_*: option "decode_join"
 DEC_MODES = {"iso": 0, "module": 1}                              # M2V_DEC_*
 DEC_SYNTAXES = {"module": 0, "main": 1}                          # M2V_SYNTAX_*: option "decode_syntax"
@@ -450,6 +453,7 @@ def lib(debug=False):
             L.m2v_decode_device.argtypes = [vp, vp, sz, vp, sz, ci, ci, vp]
             L.m2v_decode_report.argtypes = [vp, vp]
             L.m2v_decode_join_report.argtypes = [vp, vp]
+            L.m2v_decode_conceal_report.argtypes = [vp, vp]
             L.m2v_decode_scan_tile.argtypes = []
             L.m2v_decode_streams_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, ci, ci, vp]
             L.m2v_decode_streams_report.argtypes = [vp, vp, sz]
@@ -828,7 +832,7 @@ class Mpeg2Encoder:
         self._chk(self._L.m2v_set_option(self._h, name.encode(), int(value)), "m2v_set_option(%s)" % name)
         if name == "stats":
             self._set[name] = bool(value)
-        if name in ("gop_bytes_max", "scene_cut", "decode_syntax", "decode_b_pictures", "decode_interlaced", "decode_extended", "decode_mb_tools", "decode_field_pictures", "decode_join"):
+        if name in ("gop_bytes_max", "scene_cut", "decode_syntax", "decode_b_pictures", "decode_interlaced", "decode_extended", "decode_mb_tools", "decode_field_pictures", "decode_join", "decode_conceal"):
             self._set[name] = int(value)
 
     def _set_list(self, key, values, ctype, what):
@@ -1017,7 +1021,16 @@ class Mpeg2Encoder:
         self._chk(self._L.m2v_decode_join_report(self._h, out.ctypes.data), "m2v_decode_join_report")
         return out[0]
 
-    def decode_device(self, es, layout="i420", mode="iso", out=None, container=None, stream=None, syntax="module", b_pictures=False, interlaced=False, extended=False, mb_tools=False, field_pictures=False, join=0):
+    def decode_conceal_report(self):
+        """m2v_decode_conceal_report: the concealment report of the last decode_device on this handle, a numpy record of
+        DECODE_CONCEAL_DTYPE - the picture start code of the first damaged picture, the slices dropped, the rows concealed, those of
+        them without a frame in front, the pictures with such a row; es_bytes, 0, 0, 0, 0 with option "decode_conceal" off and for a
+        call that did not answer M2V_DEC_OK"""
+        out = np.zeros(1, DECODE_CONCEAL_DTYPE)
+        self._chk(self._L.m2v_decode_conceal_report(self._h, out.ctypes.data), "m2v_decode_conceal_report")
+        return out[0]
+
+    def decode_device(self, es, layout="i420", mode="iso", out=None, container=None, stream=None, syntax="module", b_pictures=False, interlaced=False, extended=False, mb_tools=False, field_pictures=False, join=0, conceal=False):
         """m2v_decode_device: the MPEG-2 elementary stream in the one-dimensional uint8 device tensor `es` (at any byte alignment) decoded
         on the device to 4:2:0 frames in `layout`; mode "iso" is decoder.decode(quirks=False), "module" the module's own loop
         (quirks=True).  Returns (frames [pictures, frame_bytes] uint8 on es's device, record).  out: a contiguous uint8 tensor to write into
@@ -1070,8 +1083,16 @@ class Mpeg2Encoder:
         out the frame the stream breaks off in (decoder.decode(..., field_pictures=True, join=...) is the definition;
         decode_join_report answers what was left out).  With container= the stream is what the demultiplexer extracts, and the join
         record's offsets count in it.  0, the default, decodes without the option whatever set_option("decode_join") left on the
-        handle."""
+        handle.
+
+        conceal = True (with field_pictures=True and what it needs, join 0 .. 3; ValueError otherwise): option "decode_conceal" for this
+        call, put back afterwards as join= is - a damaged slice is dropped and its macroblock row patched from the frame in front
+        instead of refusing the stream (decoder.decode(..., field_pictures=True, join=..., conceal=True) is the definition;
+        decode_conceal_report answers what was patched).  False, the default, decodes without the option whatever
+        set_option("decode_conceal") left on the handle."""
         import torch
+        if conceal and not field_pictures:
+            raise ValueError("decode_device: conceal goes with field_pictures=True")
         if isinstance(join, str):
             if join not in DEC_JOINS:
                 raise ValueError("decode_device: join is 0 .. 3 or one of %s" % ", ".join(DEC_JOINS))
@@ -1092,12 +1113,20 @@ class Mpeg2Encoder:
             raise ValueError("decode_device: mb_tools goes with extended=True")
         if field_pictures and not (interlaced and extended and mb_tools):
             raise ValueError("decode_device: field_pictures goes with interlaced=True, extended=True and mb_tools=True")
+        held_c = self._set.get("decode_conceal", 0)                        # what set_option("decode_conceal") left on the handle
+        if int(bool(conceal)) != held_c:
+            self.set_option("decode_conceal", int(bool(conceal)))
+            try:
+                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced,
+                                          extended=extended, mb_tools=mb_tools, field_pictures=field_pictures, join=join, conceal=conceal)
+            finally:
+                self.set_option("decode_conceal", held_c)
         held_j = self._set.get("decode_join", 0)                           # what set_option("decode_join") left on the handle
         if int(join) != held_j:
             self.set_option("decode_join", int(join))
             try:
                 return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced,
-                                          extended=extended, mb_tools=mb_tools, field_pictures=field_pictures, join=join)
+                                          extended=extended, mb_tools=mb_tools, field_pictures=field_pictures, join=join, conceal=conceal)
             finally:
                 self.set_option("decode_join", held_j)
         held_f = self._set.get("decode_field_pictures", 0)                 # what set_option("decode_field_pictures") left on the handle
@@ -1105,7 +1134,7 @@ class Mpeg2Encoder:
             self.set_option("decode_field_pictures", int(bool(field_pictures)))
             try:
                 return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced,
-                                          extended=extended, mb_tools=mb_tools, field_pictures=field_pictures, join=join)
+                                          extended=extended, mb_tools=mb_tools, field_pictures=field_pictures, join=join, conceal=conceal)
             finally:
                 self.set_option("decode_field_pictures", held_f)
         held_t = self._set.get("decode_mb_tools", 0)                       # what set_option("decode_mb_tools") left on the handle
@@ -1113,7 +1142,7 @@ class Mpeg2Encoder:
             self.set_option("decode_mb_tools", int(bool(mb_tools)))
             try:
                 return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced,
-                                          extended=extended, mb_tools=mb_tools, field_pictures=field_pictures, join=join)
+                                          extended=extended, mb_tools=mb_tools, field_pictures=field_pictures, join=join, conceal=conceal)
             finally:
                 self.set_option("decode_mb_tools", held_t)
         held_x = self._set.get("decode_extended", 0)                       # what set_option("decode_extended") left on the handle
@@ -1121,28 +1150,28 @@ class Mpeg2Encoder:
             self.set_option("decode_extended", int(bool(extended)))
             try:
                 return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced,
-                                          extended=extended, mb_tools=mb_tools, field_pictures=field_pictures, join=join)
+                                          extended=extended, mb_tools=mb_tools, field_pictures=field_pictures, join=join, conceal=conceal)
             finally:
                 self.set_option("decode_extended", held_x)
         held_i = self._set.get("decode_interlaced", 0)                     # what set_option("decode_interlaced") left on the handle
         if int(bool(interlaced)) != held_i:
             self.set_option("decode_interlaced", int(bool(interlaced)))
             try:
-                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended, mb_tools=mb_tools, field_pictures=field_pictures, join=join)
+                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended, mb_tools=mb_tools, field_pictures=field_pictures, join=join, conceal=conceal)
             finally:
                 self.set_option("decode_interlaced", held_i)
         held_b = self._set.get("decode_b_pictures", 0)                     # what set_option("decode_b_pictures") left on the handle
         if int(bool(b_pictures)) != held_b:
             self.set_option("decode_b_pictures", int(bool(b_pictures)))
             try:
-                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended, mb_tools=mb_tools, field_pictures=field_pictures, join=join)
+                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended, mb_tools=mb_tools, field_pictures=field_pictures, join=join, conceal=conceal)
             finally:
                 self.set_option("decode_b_pictures", held_b)
         held = self._set.get("decode_syntax", DEC_SYNTAXES["module"])      # what set_option("decode_syntax") left on the handle
         if DEC_SYNTAXES[syntax] != held:
             self.set_option("decode_syntax", DEC_SYNTAXES[syntax])
             try:
-                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended, mb_tools=mb_tools, field_pictures=field_pictures, join=join)
+                return self.decode_device(es, layout=layout, mode=mode, out=out, container=container, stream=stream, syntax=syntax, b_pictures=b_pictures, interlaced=interlaced, extended=extended, mb_tools=mb_tools, field_pictures=field_pictures, join=join, conceal=conceal)
             finally:
                 self.set_option("decode_syntax", held)
         if container is not None:

@@ -10,7 +10,7 @@ LIB_DBG = os.path.join(HERE, "libm2v_mi355x_dbg.so")       # -DM2V_DEBUG: level 
 TB = os.path.join(HERE, "m2v_tb")
 CONTAINER_LIB = os.path.join(HERE, "libm2v_container.so")      # CPU-only conveniences (include/m2v_container.h)
 # translation units of the library (csrc/m2v_host.hpp says what lives where); m2v_launch.hip contains the encoder's device code, m2v_mux.hip the muxer's
-UNITS = ["m2v_launch.hip", "m2v_core.hip", "m2v_begin.hip", "m2v_port.hip", "m2v_resident.hip", "m2v_strips.hip", "m2v_stats.hip", "m2v_gop.hip", "m2v_scene.hip", "m2v_recon.hip", "m2v_desc.hip", "m2v_sequences.hip", "m2v_mux.hip", "m2v_scale.hip", "m2v_decode.hip", "m2v_decode_main.hip", "m2v_decode_b.hip", "m2v_decode_i.hip", "m2v_decode_x.hip", "m2v_decode_t.hip", "m2v_decode_f.hip", "m2v_decode_j.hip", "m2v_decode_streams.hip", "m2v_decode_streams_main.hip", "m2v_decode_streams_ex.hip", "m2v_demux.hip", "m2v_deint.hip"]
+UNITS = ["m2v_launch.hip", "m2v_core.hip", "m2v_begin.hip", "m2v_port.hip", "m2v_resident.hip", "m2v_strips.hip", "m2v_stats.hip", "m2v_gop.hip", "m2v_scene.hip", "m2v_recon.hip", "m2v_desc.hip", "m2v_sequences.hip", "m2v_mux.hip", "m2v_scale.hip", "m2v_decode.hip", "m2v_decode_main.hip", "m2v_decode_b.hip", "m2v_decode_i.hip", "m2v_decode_x.hip", "m2v_decode_t.hip", "m2v_decode_f.hip", "m2v_decode_j.hip", "m2v_decode_c.hip", "m2v_decode_streams.hip", "m2v_decode_streams_main.hip", "m2v_decode_streams_ex.hip", "m2v_demux.hip", "m2v_deint.hip"]
 HEADERS = ["m2v_kernels.hpp", "m2v_tables.hpp", "m2v_types.hpp", "m2v_host.hpp", "m2v_comm.hpp", "m2v_stats_kernels.hpp", "m2v_gop_kernels.hpp", "m2v_scene_kernels.hpp", "m2v_recon_kernels.hpp", "m2v_seq_kernels.hpp", "m2v_mux_kernels.hpp", "m2v_scale_kernels.hpp", "m2v_decode_kernels.hpp", "m2v_decode_state.hpp", "m2v_decode_device.hpp", "m2v_decode_chunks.hpp", "m2v_decode_streams.hpp", "m2v_decode_streams_main.hpp", "m2v_decode_streams_ex.hpp", "m2v_demux_kernels.hpp", "m2v_deint_kernels.hpp"]
 SOURCES = UNITS + HEADERS
 OBJDIR = os.path.join(HERE, "build")

@@ -745,6 +745,11 @@ int m2v_set_option(m2v_enc *e, const char *name, long long value)
         e->decode_field_pictures = (int)value;
         return M2V_OK;
     }
+    if (!strcmp(name, "decode_conceal")) {
+        if (value != 0 && value != 1) { e->set_err("m2v_set_option: decode_conceal is 0 (the default) or 1"); return M2V_E_PARAM; }
+        e->decode_conceal = (int)value;
+        return M2V_OK;
+    }
     if (!strcmp(name, "decode_join")) {
         if (value < 0 || value > 3) { e->set_err("m2v_set_option: decode_join is 0 (the default) or a mask of M2V_JOIN_HEAD (1) and M2V_JOIN_TAIL (2)"); return M2V_E_PARAM; }
         e->decode_join = (int)value;

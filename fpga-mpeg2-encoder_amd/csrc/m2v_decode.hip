@@ -45,10 +45,13 @@
 // pictures a frame; from the same two places to m2v_decode_f.hip (dec_f_plan, dec_f_chunks), whose chunks are whole frames.
 // "decode_join" = 1 .. 3 on top of all of them: a stream that begins in front of its first sequence header, whose first B pictures lack
 // their anchors, or that breaks off inside a picture; the plan is m2v_decode_j.hip's (dec_j_plan), the chunks stay dec_f_chunks.
+// "decode_conceal" = 1 on top of "decode_field_pictures" and what it needs, "decode_join" 0 .. 3: damaged slices are dropped, their rows
+// patched from the frame in front; the plan is dec_c_plan, dec_f_chunks hands the walk to m2v_decode_c.hip (dec_c_walk, dec_c_finish).
 #include "m2v_decode_state.hpp"
 
 static_assert(sizeof(m2v_decode_stat) == 72, "the record of include/m2v_mi355x.h is 72 bytes");
 static_assert(sizeof(m2v_decode_join) == 32, "the join record of include/m2v_mi355x.h is 32 bytes");
+static_assert(sizeof(m2v_decode_conceal) == 32, "the concealment report of include/m2v_mi355x.h is 32 bytes");
 static_assert(sizeof(dec::MbRec) == 16, "a macroblock's record is 16 bytes");
 static_assert(M2V_DEC_ISO == dec::kIso && M2V_DEC_MODULE == dec::kModule && M2V_DEC_SYNTAX == dec::kSyntax && M2V_DEC_OVERFLOW == dec::kOverflow,
               "m2v_decode_kernels.hpp repeats the values of include/m2v_mi355x.h");
@@ -388,6 +391,7 @@ static int decode_impl(m2v_enc *e, void *argp)
     R = m2v_decode_stat{};
     R.es_bytes = n;
     e->dec_join = m2v_decode_join{0, n, 0, 0, {0, 0}};
+    e->dec_conceal = m2v_decode_conceal{n, 0, 0, 0, 0, {0, 0}};
     if (n < 4) { R.status = M2V_DEC_SYNTAX; return M2V_OK; }          // not one start code
     e->d_dec_st.recorded = e->d_dec_ev.recorded = e->d_dec_pics.recorded = e->d_dec_mb.recorded = e->d_dec_dc.recorded = false;     // (no recorded graph references them)
     e->d_dec_lv.recorded = e->d_dec_buf.recorded = e->d_dec_tiles.recorded = e->d_dec_list.recorded = e->d_dec_main.recorded = false;
@@ -398,6 +402,7 @@ static int decode_impl(m2v_enc *e, void *argp)
     const bool mb_tools = e->decode_mb_tools != 0;                     // m2v_decode_t.hip: its plan in the place of dec_x_plan; dec_x_chunks takes it
     const bool field_pictures = e->decode_field_pictures != 0;         // m2v_decode_f.hip: in the places of dec_t_plan and dec_x_chunks
     const int join = e->decode_join;                                   // m2v_decode_j.hip: its plan in the place of dec_f_plan, dec_f_chunks behind it
+    const bool conceal = e->decode_conceal != 0;                       // m2v_decode_c.hip: dec_c_plan in the place of either, dec_f_chunks with its walk
     e->d_dec_x.recorded = false;
     const size_t ntiles = (n + dec::kScanTile - 1) / dec::kScanTile;
     if (ntiles > 0x7FFFFFFFu) { e->set_err("m2v_decode_device: the stream is longer than 2^31 scan tiles"); return M2V_E_PARAM; }
@@ -407,16 +412,17 @@ static int decode_impl(m2v_enc *e, void *argp)
     timer_break(e);
     for (int run = 0; run < 2; ++run) {
         if (ev_cap > 0x7FFFFFFFu) { e->set_err("m2v_decode_device: the stream holds more than 2^31 start codes"); return M2V_E_PARAM; }
-        pic_cap = ev_cap / 3 + 2;
+        pic_cap = conceal ? ev_cap / 2 + 2 : ev_cap / 3 + 2;          // (a picture is three events at least - two where its slices may be gone)
         e->d_dec_st.ensure(sizeof(DecState));
         e->d_dec_tiles.ensure(ntiles);
         e->d_dec_ev.ensure(ev_cap);
         e->d_dec_pics.ensure(pic_cap * sizeof(DecPic));
         rec_off = (sizeof(DecState) + 63) & ~(size_t)63;
-        ensure_pinned(e->h_dec, e->h_dec_cap, rec_off + 128 + pic_cap + 4 * pic_cap + 16 + (extended ? 4 * (pic_cap + 1) : 0));      // extended: the slices in front of every picture
+        ensure_pinned(e->h_dec, e->h_dec_cap, rec_off + 128 + pic_cap + 4 * pic_cap + 16 + (extended ? 4 * (pic_cap + 1) : 0) +
+                      (conceal ? 8 + 4 * kDecConcealWords : 0));      // extended: the slices in front of every picture; conceal: the report behind them
         auto *init = (DecState *)e->h_dec;
         *init = DecState{};
-        init->err = dec::kNone; init->ev_cap = (uint32_t)ev_cap;
+        init->err = dec::kNone; init->ev_cap = (uint32_t)ev_cap; init->c_first = dec::kNone;
         auto *d_st = (DecState *)e->d_dec_st.p;
         HIPCHK(hipMemcpyAsync(d_st, init, sizeof(DecState), hipMemcpyHostToDevice, s));
         const unsigned gx = (unsigned)std::min<size_t>(ntiles, 512);
@@ -426,7 +432,12 @@ static int decode_impl(m2v_enc *e, void *argp)
         HIPCHK(hipGetLastError());
         k_dec_scan<true><<<gx, kDecThreads, 0, s>>>(a->es, n, d_st, e->d_dec_tiles.p, e->d_dec_ev.p);
         HIPCHK(hipGetLastError());
-        if (join) {
+        if (conceal) {
+            e->d_dec_main.ensure(kDecMainMatrices + pic_cap * sizeof(DecFPic));
+            dec_c_plan(s, a->es, n, e->d_dec_ev.p, d_st, (DecPic *)e->d_dec_pics.p, (uint32_t)pic_cap, e->h_dec + rec_off + 128, (unsigned long long)a->cap, a->dst ? 0 : 1,
+                       (m2v_decode_stat *)(e->h_dec + rec_off), e->d_dec_main.p, b_pictures ? 1 : 0, join, (uint32_t *)(e->h_dec + rec_off + kDecPlanWords),
+                       (uint32_t *)(e->h_dec + rec_off + 128 + ((pic_cap + 3) & ~(size_t)3) + 4 * pic_cap));
+        } else if (join) {
             e->d_dec_main.ensure(kDecMainMatrices + pic_cap * sizeof(DecFPic));
             dec_j_plan(s, a->es, n, e->d_dec_ev.p, d_st, (DecPic *)e->d_dec_pics.p, (uint32_t)pic_cap, e->h_dec + rec_off + 128, (unsigned long long)a->cap, a->dst ? 0 : 1,
                        (m2v_decode_stat *)(e->h_dec + rec_off), e->d_dec_main.p, b_pictures ? 1 : 0, join, (uint32_t *)(e->h_dec + rec_off + kDecPlanWords),
@@ -479,8 +490,12 @@ static int decode_impl(m2v_enc *e, void *argp)
         const size_t rows = *(const uint32_t *)(e->h_dec + rec_off + 96), ncp = *(const uint32_t *)(e->h_dec + rec_off + 100);
         if (!e->decode_batch) B = std::min(np, std::max<size_t>(1, std::min(kDecBatchMax, kDecLevelBytes / (mbw * rows * 768))));
         auto *h_list = (uint32_t *)(e->h_dec + rec_off + 128 + ((pic_cap + 3) & ~(size_t)3));
-        dec_f_chunks(e, s, a->es, n, a->dst, a->layout, R, rows, B, types, ncp, h_list, h_list + pic_cap, (m2v_decode_stat *)(e->h_dec + rec_off));
+        // the report's words: behind the slices in front of every picture, on an 8-byte boundary
+        uint32_t *h_conceal = conceal ? (uint32_t *)(e->h_dec + ((rec_off + 128 + ((pic_cap + 3) & ~(size_t)3) + 4 * pic_cap + 4 * (pic_cap + 1) + 7) & ~(size_t)7)) : nullptr;
+        dec_f_chunks(e, s, a->es, n, a->dst, a->layout, R, rows, B, types, ncp, h_list, h_list + pic_cap, (m2v_decode_stat *)(e->h_dec + rec_off), h_conceal);
         R = *h_rec;
+        if (conceal && R.status == M2V_DEC_OK)                         // (it came with the record: one wait)
+            e->dec_conceal = m2v_decode_conceal{(uint64_t)h_conceal[1] << 32 | h_conceal[0], h_conceal[2], h_conceal[3], h_conceal[4], h_conceal[5], {0, 0}};
         if (R.status == M2V_DEC_SYNTAX) e->dec_join = m2v_decode_join{0, n, 0, 0, {0, 0}};      // a slice refused the stream
         return M2V_OK;
     }
@@ -576,6 +591,12 @@ int m2v_decode_device(m2v_enc *e, const void *d_es, size_t es_bytes, void *d_dst
     if (!layout420_ok(layout)) { e->set_err("m2v_decode_device: unknown layout %d", layout); return M2V_E_PARAM; }
     if (mode != M2V_DEC_ISO && mode != M2V_DEC_MODULE) { e->set_err("m2v_decode_device: unknown mode %d", mode); return M2V_E_PARAM; }
     if (!d_es && es_bytes) { e->set_err("m2v_decode_device: d_es is NULL"); return M2V_E_PARAM; }
+    if (e->decode_conceal && (e->decode_syntax != M2V_SYNTAX_MAIN || mode != M2V_DEC_ISO || !e->decode_interlaced || !e->decode_extended || !e->decode_mb_tools ||
+                              !e->decode_field_pictures)) {
+        e->set_err("m2v_decode_device: \"decode_conceal\" = 1 needs \"decode_syntax\" = main, the mode M2V_DEC_ISO and \"decode_interlaced\", "
+                   "\"decode_extended\", \"decode_mb_tools\" and \"decode_field_pictures\" = 1");
+        return M2V_E_PARAM;
+    }
     if (e->decode_join && (e->decode_syntax != M2V_SYNTAX_MAIN || mode != M2V_DEC_ISO || !e->decode_interlaced || !e->decode_extended || !e->decode_mb_tools ||
                            !e->decode_field_pictures)) {
         e->set_err("m2v_decode_device: \"decode_join\" = 1 .. 3 needs \"decode_syntax\" = main, the mode M2V_DEC_ISO and \"decode_interlaced\", "
@@ -623,6 +644,13 @@ int m2v_decode_join_report(m2v_enc *e, m2v_decode_join *out)
 {
     if (!e || !out) return M2V_E_PARAM;
     *out = e->dec_join;
+    return M2V_OK;
+}
+
+int m2v_decode_conceal_report(m2v_enc *e, m2v_decode_conceal *out)
+{
+    if (!e || !out) return M2V_E_PARAM;
+    *out = e->dec_conceal;
     return M2V_OK;
 }
 

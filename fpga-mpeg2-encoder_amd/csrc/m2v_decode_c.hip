@@ -1,29 +1,35 @@
-// m2v_decode_j.hip — streams cut from a broadcast for m2v_decode_device (option "decode_join" = 1 .. 3 on top of "decode_interlaced",
-// "decode_extended", "decode_mb_tools" and "decode_field_pictures" = 1, with "decode_b_pictures" 0 or 1).  m2v_decode.hip keeps the
-// scan - whatever lies in front of the join point is just events -, and everything behind the plan's wait is dec_f_chunks of
-// m2v_decode_f.hip with its kernels: this unit holds the plan alone, in k_df_plan's place.  decoder.decode(..., join=) is the definition;
-// every function that decides an index or a verdict is a j_ (or fp_ ...) function of m2v_decode_kernels.hpp.
+// m2v_decode_c.hip — damaged slices concealed for m2v_decode_device (option "decode_conceal" = 1 on top of "decode_interlaced",
+// "decode_extended", "decode_mb_tools" and "decode_field_pictures" = 1, with "decode_b_pictures" 0 or 1 and "decode_join" 0 .. 3).
+// m2v_decode.hip keeps the scan, and the chunks are dec_f_chunks of m2v_decode_f.hip with its reconstruction and output: a concealed
+// macroblock is a record, and k_df_recon draws it as any other.  This unit holds the plan and what stands between the plan and the
+// reconstruction of a chunk.
+// decoder.decode(..., conceal=True) is the definition; every function that decides a bit, a verdict or a record is a c_ (or fp_ / t_ ..)
+// function of m2v_decode_kernels.hpp.
 //
-//   k_dj_plan    J: the first sequence_header_code, a minimum over the lanes.  The events from J on are cut into 256 ranges.  Every lane
-//                sums the pairing of its range for both states in front of it (dec::j_pair_range), lane 0 joins the sums
-//                (dec::j_pair_join): the state in front of every range, F - the last picture start code that begins a frame -, and E2,
-//                the picture that begins the second anchor frame.  T follows from the last slice in front of F.  Then k_df_plan's
-//                text runs over the window's events with T as the stream's length, but for the frames that are dropped - a frame whose
-//                first picture is a B picture in front of E2 -: their events are judged, their pictures are in no sum and no table,
-//                their slices are not counted (dec::j_keep_range, dec::j_place).  Event indices that leave the kernel are those of the
-//                whole list, so the slice walk, the matrices and the spans of dec_f_chunks find the kept pictures' events where they are.
+//   k_dc_plan    k_dj_plan's text with dec::c_event and dec::c_place: a slice behind a coding extension or a slice whatever the codes, a
+//                picture that ends behind any slice or none, an I picture with a P picture's forward frame; nslices may be 0
+//   k_dc_slices  k_df_slices' text: one lane per slice EVENT of the chunk into the records of the row its code names.  It refuses
+//                nothing: a slice whose code is above its picture's rows is not walked, and its span, like that of a slice that does not
+//                read, says so.  A walk writes inside the row its code names alone (the column is below mbw before every store), so
+//                whatever a damaged slice leaves lies in a row that k_dc_rows conceals whole
+//   k_dc_rows    in k_df_cont's place: a block per coded picture of the chunk, a lane per macroblock row.  The lane walks the picture's
+//                spans (dec::c_row_kept); for a concealed row it writes the mbw records (dec::c_record).  The counts are summed over
+//                the wavefront by shuffles and added to DecState by lane 0, one atomic a count and block; the first damaged picture's
+//                start code is a minimum
+//   k_dc_finish  k_df_finish, and the report beside the record
 #include "m2v_decode_state.hpp"
 
 namespace m2v {
 
-constexpr uint32_t kNoPicJ = 0xFFFFFFFFu;
-
-// (k_dc_plan of m2v_decode_c.hip is this text with dec::c_event and dec::c_place: a fix made here is to be made there too)
-__global__ __launch_bounds__(kDecThreads) void k_dj_plan(const uint8_t *__restrict__ es, unsigned long long n, const unsigned long long *__restrict__ ev0, DecState *st,
+// k_dj_plan's text (m2v_decode_j.hip; join 0: the window is the stream, and the plan is k_df_plan's) with the relaxed rules: an event is
+// judged by dec::c_event - no rule reads the rows, so there is no second plan with a field's -, a picture placed by dec::c_place.
+// The text stands twice because as a template the instantiation the other paths run did not keep its registers and scratch: a fix
+// made in k_dj_plan is to be made here too, and the other way round
+__global__ __launch_bounds__(kDecThreads) void k_dc_plan(const uint8_t *__restrict__ es, unsigned long long n, const unsigned long long *__restrict__ ev0, DecState *st,
                                                          DecPic *__restrict__ pics, uint32_t pic_cap, uint8_t *h_types, unsigned long long cap, int probe,
                                                          m2v_decode_stat *h_rec, uint8_t *__restrict__ mats, DecFPic *bp, int b_pictures, int join, uint32_t *h_mbh, uint32_t *h_sl)
 {
-    __shared__ dec::MainPlan s_P, s_Pf;                    // s_Pf: with a field's macroblock rows
+    __shared__ dec::MainPlan s_P;
     __shared__ unsigned long long s_bad, s_T, s_lnz;
     __shared__ dec::JSum s_A[kDecThreads], s_B[kDecThreads];
     __shared__ dec::JPair s_pin[kDecThreads];
@@ -36,7 +42,7 @@ __global__ __launch_bounds__(kDecThreads) void k_dj_plan(const uint8_t *__restri
     const bool head = (join & (int)dec::kJoinHead) != 0, tail = (join & (int)dec::kJoinTail) != 0, drop = head && b_pictures != 0;
     m2v_decode_stat r{};
     r.es_bytes = n;
-    if (tid == 0) {                                // the join record of a call that drops nothing: 0, es_bytes, 0, 0
+    if (tid == 0) {                                // the join record of a call that drops nothing: 0, es_bytes, 0, 0 (read with "decode_join" alone)
         uint32_t *j = h_mbh + kDecJoinWord;
         j[0] = j[1] = 0; j[2] = (uint32_t)n; j[3] = (uint32_t)(n >> 32); j[4] = j[5] = 0;
     }
@@ -103,8 +109,6 @@ __global__ __launch_bounds__(kDecThreads) void k_dj_plan(const uint8_t *__restri
         s_T = tw < nw ? dec::ev_pos(ev[tw]) : n;
         s_lnz = tw < nw ? dec::j_last_nz(es, s_T, (const uint64_t *)ev, tw) : st->last_nz;
         s_bad = head ? dec::j_first(es, s_T, (const uint64_t *)ev, tw, s_P) : dec::il_first(es, s_T, (const uint64_t *)ev, tw, s_P);
-        s_Pf = s_P;
-        s_Pf.mbh = s_P.mbh / 2u;
     }
     __syncthreads();
     const unsigned long long T = s_T;
@@ -131,7 +135,7 @@ __global__ __launch_bounds__(kDecThreads) void k_dj_plan(const uint8_t *__restri
         uint32_t ng = 0, nr = 0, reset = 0;
         dec::XMats xm{dec::kNoEvent, dec::kNoEvent};           // what the range's events loaded behind its last sequence header
         for (uint32_t i = aw; i < bw; ++i) {
-            const dec::EvInfo f = dec::fp_event(es, T, (const uint64_t *)ev, nev, i, P, s_Pf, last_nz, prev, b_pictures != 0);
+            const dec::EvInfo f = dec::c_event(es, T, (const uint64_t *)ev, nev, i, P, last_nz, prev, b_pictures != 0);
             const int role = dec::main_role(es, T, ev[i]);
             if (dec::main_significant(role)) prev = (int)i;
             reset |= role == dec::rSeq;
@@ -188,12 +192,12 @@ __global__ __launch_bounds__(kDecThreads) void k_dj_plan(const uint8_t *__restri
             if (w.open) atomicMax(&s_lastopen, i + 1u);
             if (gone) { if (wrong) atomicMin(&s_bad, pos); continue; }
             const int32_t anchor_cp = s.a1cp;
-            const dec::FpPlace q = dec::fp_place(s, cp, ps, type, tref);
+            const dec::FpPlace q = dec::c_place(s, cp, ps, type, tref);
             if (q.bad) atomicMin(&s_bad, pos);
             if (cp < pic_cap) {
                 uint32_t slice0, nslices, quant;
                 dec::FPicParams pp = dec::fp_picture_params(es, T, (const uint64_t *)ev, nev, i, b_pictures != 0, progressive, slice0, nslices, quant);
-                pp.second = q.second; pp.noref = q.second && type == 2u && q.fwd == kNoPicJ;
+                pp.second = q.second; pp.noref = q.second && type == 2u && q.fwd == kNoPic;
                 const dec::XMats own = dec::x_mats_picture(es, T, (const uint64_t *)ev, nev, xm, quant);
                 DecFPic *d = bp + cp;                          // (field by field: an anchor frame's display index is another lane's to write)
                 d->slice0 = slice0 + jev; d->params = dec::fp_params_pack(pp); d->fwd = q.fwd; d->bwd = q.bwd; d->nslices = nslices; d->sbase = sl;
@@ -217,7 +221,7 @@ __global__ __launch_bounds__(kDecThreads) void k_dj_plan(const uint8_t *__restri
     r.width = h.width; r.height = h.height;
     r.frame_bytes = dec::frame_bytes(h.width, h.height);
     if (s_bad != dec::kNone) { r.status = dec::kSyntax; r.err_offset = s_bad; }
-    else if (s_ncp > pic_cap) { r.status = dec::kSyntax; r.err_offset = 0; }           // (cannot happen: a picture is three events at least)
+    else if (s_ncp > pic_cap) { r.status = dec::kSyntax; r.err_offset = 0; }           // (cannot happen: a picture is two events at least, and the table is sized so)
     else if (!probe && r.frame_bytes * r.pictures > cap) r.status = dec::kOverflow;
     else if (probe) r.out_bytes = r.frame_bytes * r.pictures;
     st->status = r.status; st->err = s_bad; st->npics = r.pictures; st->gops = r.gops; st->reps = r.repeated_headers; st->chains = r.chains;
@@ -233,11 +237,99 @@ __global__ __launch_bounds__(kDecThreads) void k_dj_plan(const uint8_t *__restri
     *h_rec = r;
 }
 
-void dec_j_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long long *ev, DecState *st, DecPic *pics, uint32_t pic_cap, uint8_t *h_types,
+__global__ __launch_bounds__(64) void k_dc_slices(const uint8_t *__restrict__ es, unsigned long long n, const unsigned long long *__restrict__ ev, const DecState *__restrict__ st,
+                                                  const DecPic *__restrict__ pics, const DecFPic *__restrict__ xp, uint32_t p0, uint32_t np, uint32_t f0, uint32_t total,
+                                                  dec::IMb *mb, int32_t *dc, int16_t *lv, uint32_t *__restrict__ spans)
+{
+    if (st->status != dec::kOk) return;
+    const uint32_t mbw = st->mbw, mbh = st->mbh, nev = st->nev;
+    const uint32_t g = blockIdx.x * 64u + threadIdx.x;
+    if (g >= total) return;
+    uint32_t k;
+    const uint32_t pic = dec::x_slice_pic(xp + p0, np, g, k);          // (pictures without a slice share their sbase with the next one: the search passes them)
+    const DecPic P = pics[p0 + pic];
+    const DecFPic Q = xp[p0 + pic];
+    const uint32_t i = Q.slice0 + k;
+    spans[g] = 0u;
+    if (k >= Q.nslices || i >= nev || Q.frame < f0) return;            // (the plan counted the picture's slices: they are there)
+    const unsigned long long start = dec::ev_pos(ev[i]), end = i + 1 < nev ? dec::ev_pos(ev[i + 1]) : n;
+    const uint32_t code = dec::ev_code(ev[i]);
+    const dec::FPicParams pp = dec::fp_params_unpack(Q.params);
+    const bool field = dec::fp_is_field(pp.ps);
+    const uint32_t rows = field ? mbh / 2u : mbh;
+    spans[g] = dec::x_span_pack(false, code, -1, -1);
+    if (dec::c_bad_code(code, rows)) return;                           // a bad slice: counted behind the walk, not walked
+    const size_t first = df_first(Q, f0, mbw * mbh) + (size_t)(code - 1u) * mbw;
+    IMbSink sink{mb + first, dc + first * 6, lv + first * 384};
+    int c0, c1;
+    const bool ok = field ? dec::fp_slice(es, start, end, P.type, pp, (int)mbw, (int)rows, (int)code - 1, sink, c0, c1)
+                          : dec::t_slice(es, start, end, P.type, pp.t, (int)mbw, (int)mbh, (int)code - 1, sink, c0, c1);
+    spans[g] = dec::x_span_pack(ok, code, c0, c1);
+}
+
+// grid: the coded pictures [p0, p0 + gridDim.x) of the chunk that begins at frame f0; spans: the chunk's, picture p's from sbase on
+__global__ __launch_bounds__(64) void k_dc_rows(const unsigned long long *__restrict__ ev, DecState *st, const DecPic *__restrict__ pics, const DecFPic *__restrict__ xp,
+                                                uint32_t p0, uint32_t f0, dec::IMb *mb, const uint32_t *__restrict__ spans)
+{
+    if (st->status != dec::kOk) return;
+    const uint32_t mbw = st->mbw, mbh = st->mbh, l = threadIdx.x;
+    const DecFPic Q = xp[p0 + blockIdx.x];
+    if (Q.frame < f0) return;
+    const dec::FPicParams pp = dec::fp_params_unpack(Q.params);
+    const bool field = dec::fp_is_field(pp.ps);
+    const uint32_t rows = field ? mbh / 2u : mbh, par = field ? pp.ps - 1u : 0u;
+    const uint32_t *sp = spans + (Q.sbase - xp[p0].sbase);
+    const bool grey = Q.fwd == kNoPic;                                 // no frame in front: the first anchor frame, both of its fields
+    uint32_t bad = 0, hidden = 0;
+    for (uint32_t k = l; k < Q.nslices; k += 64u) bad += !(sp[k] >> 31);
+    const dec::IMb rec = dec::c_record(field, par, grey);
+    dec::IMb *at = mb + df_first(Q, f0, mbw * mbh);
+    for (uint32_t r = l; r < rows; r += 64u) {
+        if (dec::c_row_kept(sp, Q.nslices, r + 1u, mbw)) continue;
+        for (uint32_t c = 0; c < mbw; ++c) at[(size_t)r * mbw + c] = rec;
+        ++hidden;
+    }
+    for (int o = 32; o; o >>= 1) { bad += __shfl_down(bad, o); hidden += __shfl_down(hidden, o); }
+    if (l) return;
+    if (bad) atomicAdd(&st->c_bad, bad);
+    if (!hidden) return;
+    atomicAdd(&st->c_rows, hidden);
+    if (grey) atomicAdd(&st->c_grey, hidden);
+    atomicAdd(&st->c_pics, 1u);
+    atomicMin(&st->c_first, dec::ev_pos(ev[pics[p0 + blockIdx.x].ev]));
+}
+
+__global__ void k_dc_finish(const DecState *st, m2v_decode_stat *h_rec, uint32_t *h_conceal)
+{
+    if (st->status != dec::kOk) { h_rec->status = st->status; h_rec->err_offset = st->err; h_rec->out_bytes = 0; return; }
+    h_rec->out_bytes = st->frame_bytes * st->npics;
+    const unsigned long long first = st->c_first == dec::kNone ? h_rec->es_bytes : st->c_first;
+    h_conceal[0] = (uint32_t)first; h_conceal[1] = (uint32_t)(first >> 32);
+    h_conceal[2] = st->c_bad; h_conceal[3] = st->c_rows; h_conceal[4] = st->c_grey; h_conceal[5] = st->c_pics;
+}
+
+void dec_c_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long long *ev, DecState *st, DecPic *pics, uint32_t pic_cap, uint8_t *h_types,
                 unsigned long long cap, int probe, m2v_decode_stat *h_rec, uint8_t *d_main, int b_pictures, int join, uint32_t *h_mbh, uint32_t *h_sl)
 {
-    k_dj_plan<<<1, kDecThreads, 0, s>>>(es, n, ev, st, pics, pic_cap, h_types, cap, probe, h_rec, d_main, (DecFPic *)(d_main + kDecMainMatrices), b_pictures, join, h_mbh,
+    k_dc_plan<<<1, kDecThreads, 0, s>>>(es, n, ev, st, pics, pic_cap, h_types, cap, probe, h_rec, d_main, (DecFPic *)(d_main + kDecMainMatrices), b_pictures, join, h_mbh,
                                         h_sl);
+    HIPCHK(hipGetLastError());
+}
+
+void dec_c_walk(hipStream_t s, const uint8_t *es, size_t n, const unsigned long long *ev, DecState *st, const DecPic *pics, const DecFPic *xp, uint32_t p0, uint32_t np,
+                uint32_t f0, uint32_t total, dec::IMb *mb, int32_t *dc, int16_t *lv, uint32_t *spans)
+{
+    if (total) {
+        k_dc_slices<<<(total + 63u) / 64u, 64, 0, s>>>(es, n, ev, st, pics, xp, p0, np, f0, total, mb, dc, lv, spans);
+        HIPCHK(hipGetLastError());
+    }
+    k_dc_rows<<<np, 64, 0, s>>>(ev, st, pics, xp, p0, f0, mb, spans);  // (a chunk without a slice has rows all the same)
+    HIPCHK(hipGetLastError());
+}
+
+void dec_c_finish(hipStream_t s, const DecState *st, m2v_decode_stat *h_rec, uint32_t *h_conceal)
+{
+    k_dc_finish<<<1, 1, 0, s>>>(st, h_rec, h_conceal);
     HIPCHK(hipGetLastError());
 }
 

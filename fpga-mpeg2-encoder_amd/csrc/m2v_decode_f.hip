@@ -166,10 +166,6 @@ __global__ __launch_bounds__(kDecThreads) void k_df_plan(const uint8_t *__restri
     *h_rec = r;
 }
 
-// the first record of coded picture Q in a chunk that begins at frame f0: a frame's stretch is mbs records, a second field's half of it
-// lies behind its first field's
-__device__ inline size_t df_first(const DecFPic &Q, uint32_t f0, uint32_t mbs) { return (size_t)(Q.frame - f0) * mbs + (((Q.params >> 26) & 1u) ? mbs / 2u : 0u); }
-
 // coded pictures [p0, p0 + np) - the frames from f0 on - with `total` slices: one slice EVENT per lane, into the row its code names.
 // The lane leaves its span; a slice that cannot be read lowers st->err
 __global__ __launch_bounds__(64) void k_df_slices(const uint8_t *__restrict__ es, unsigned long long n, const unsigned long long *__restrict__ ev, DecState *st,
@@ -235,7 +231,9 @@ __global__ __launch_bounds__(128) void k_df_mats(const uint8_t *__restrict__ es,
 // grid = (macroblocks of a frame, coded pictures of the launch); list: their coded indices, all of the chunk that begins at frame f0.
 // A frame picture is k_dx_recon's; a field has half the macroblocks and works on the lines of its parity.  Every read of a reference
 // lies inside its picture or its field, and the field is there: the slice walk refused the slice otherwise (dec::il_inside,
-// dec::fp_inside), and a refused slice stops the call before this kernel (k_df_judge)
+// dec::fp_inside), and a refused slice stops the call before this kernel (k_df_judge) - or, with "decode_conceal", its whole row is
+// concealed before it (k_dc_rows): a record that reaches this kernel is a readable slice's or dec::c_record's, which reads its own
+// macroblock of the forward frame
 __global__ __launch_bounds__(64) void k_df_recon(const DecState *__restrict__ st, const uint32_t *__restrict__ list, uint32_t f0, uint32_t c1,
                                                  const uint8_t *__restrict__ mats, const DecPic *__restrict__ pics, const DecFPic *__restrict__ bp,
                                                  const dec::IMb *__restrict__ mb, const int32_t *__restrict__ dc, const int16_t *__restrict__ lv, uint8_t *buf, size_t psz)
@@ -322,8 +320,9 @@ void dec_f_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long 
 // dec_x_chunks over frames: a chunk is B whole frames, its coded pictures the one or two of each.  types[p]: coded picture p's type,
 // structure << 2, "second field" << 4 (the plan's); ncp: the coded pictures; h_sl[p]: the slices in front of coded picture p
 void dec_f_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_t *dst, int layout, const m2v_decode_stat &R, size_t mbh, size_t B,
-                  const uint8_t *types, size_t ncp, uint32_t *h_list, const uint32_t *h_sl, m2v_decode_stat *h_rec)
+                  const uint8_t *types, size_t ncp, uint32_t *h_list, const uint32_t *h_sl, m2v_decode_stat *h_rec, uint32_t *h_conceal)
 {
+    const bool conceal = h_conceal != nullptr;
     const size_t nf = R.pictures, mbw = (R.width + 15) / 16, mbs = mbw * mbh, psz = mbs * 384;
     auto type_of = [&](size_t p) { return (unsigned)(types[p] & 3u); };
     auto second = [&](size_t p) { return ((types[p] >> 4) & 1u) != 0; };
@@ -347,7 +346,8 @@ void dec_f_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_
     e->d_dec_buf.ensure((B + 2) * psz);
     e->d_dec_list.ensure(ncp);
     // every chunk's anchor pictures ordered by their step inside the chunk - a picture is a step behind everything of the chunk it reads:
-    // a P picture the anchor frame in front of its frame, the second field of a frame its first field too -, then its B pictures; and what
+    // a P picture the anchor frame in front of its frame, the second field of a frame its first field too; with "decode_conceal" an I
+    // picture as a P picture, for a concealed row of it reads that frame -, then its B pictures; and what
     // the chunk leaves in slots 0 and 1 for the next
     std::vector<DecChunk> chunks;
     long a1 = -1, a2 = -1;                                             // the last two anchor frames in front of the chunk
@@ -361,7 +361,7 @@ void dec_f_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_
             if (type_of(p) == 3u) continue;
             const size_t f = (size_t)(std::upper_bound(fcp.begin(), fcp.end(), p) - fcp.begin()) - 1;
             long dep = -1;
-            if (type_of(p) == 2u) {
+            if (type_of(p) == 2u || conceal) {
                 if (before[f] >= (long)f0) dep = std::max(dep, fstep[(size_t)before[f] - f0]);
                 if (second(p)) dep = std::max(dep, step[p - 1 - p0]);
             }
@@ -399,16 +399,20 @@ void dec_f_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_
         const size_t nb = std::min(B, nf - f0), p0 = fcp[f0], np = fcp[f0 + nb] - p0;
         const DecChunk &C = chunks[c];
         HIPCHK(hipMemsetAsync(e->d_dec_lv.p, 0, nb * mbs * 768, s));
-        const size_t total = h_sl[p0 + np] - h_sl[p0];                 // (every picture the plan accepted has a slice)
-        if (total) {
+        const size_t total = h_sl[p0 + np] - h_sl[p0];                 // (every picture the plan accepted has a slice; with "decode_conceal" it may have none, and a chunk too)
+        if (conceal) {                                                 // nothing is refused behind the plan: a verdict per row, the rows concealed
+            dec_c_walk(s, es, n, e->d_dec_ev.p, d_st, pics, bp, (uint32_t)p0, (uint32_t)np, (uint32_t)f0, (uint32_t)total, d_mb, e->d_dec_dc.p, e->d_dec_lv.p, spans);
+        } else if (total) {
             k_df_slices<<<(unsigned)((total + 63) / 64), 64, 0, s>>>(es, n, e->d_dec_ev.p, d_st, pics, bp, (uint32_t)p0, (uint32_t)np, (uint32_t)f0, (uint32_t)total, d_mb,
                                                                      e->d_dec_dc.p, e->d_dec_lv.p, spans);
             HIPCHK(hipGetLastError());
             k_df_cont<<<(unsigned)((total + 63) / 64), 64, 0, s>>>(e->d_dec_ev.p, d_st, bp, (uint32_t)p0, (uint32_t)np, (uint32_t)total, spans);
             HIPCHK(hipGetLastError());
         }
-        k_df_judge<<<1, 1, 0, s>>>(d_st);
-        HIPCHK(hipGetLastError());
+        if (!conceal) {
+            k_df_judge<<<1, 1, 0, s>>>(d_st);
+            HIPCHK(hipGetLastError());
+        }
         auto recon = [&](const DecLaunch &l) {
             if (!l.count) return;
             k_df_recon<<<dim3((unsigned)mbs, (unsigned)l.count), 64, 0, s>>>(d_st, e->d_dec_list.p + l.off, (uint32_t)f0, (uint32_t)C.c1, mats, pics, bp, d_mb, e->d_dec_dc.p,
@@ -426,8 +430,12 @@ void dec_f_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_
             if (C.carry1 >= 0) HIPCHK(hipMemcpyAsync(e->d_dec_buf.p + psz, e->d_dec_buf.p + (size_t)C.carry1 * psz, psz, hipMemcpyDeviceToDevice, s));
         }
     }
-    k_df_finish<<<1, 1, 0, s>>>(d_st, h_rec);
-    HIPCHK(hipGetLastError());
+    if (conceal) {
+        dec_c_finish(s, d_st, h_rec, h_conceal);
+    } else {
+        k_df_finish<<<1, 1, 0, s>>>(d_st, h_rec);
+        HIPCHK(hipGetLastError());
+    }
     HIPCHK(hipStreamSynchronize(s));
 }
 

@@ -1848,7 +1848,9 @@ M2V_HD inline uint32_t x_picture_params(const uint8_t *es, uint64_t n, const uin
 }
 
 // the picture of slice g of a chunk whose pictures' entries are t[0 .. n) and the slice's number k inside it: the last entry whose
-// sbase (the slices in front of the picture) is not behind g - every picture has a slice, so sbase grows -, as chunk_slice_pic above
+// sbase (the slices in front of the picture) is not behind g, as chunk_slice_pic above.  sbase never falls; where every picture has a
+// slice it grows, and with "decode_conceal" pictures without a slice share theirs with the picture behind them: the LAST such entry
+// is the one that owns slice g, so the search passes them (g is below the chunk's slices, so it never ends on a trailing one)
 template <class Pic>
 M2V_HD inline uint32_t x_slice_pic(const Pic *t, uint32_t n, uint32_t g, uint32_t &k)
 {
@@ -2881,6 +2883,125 @@ M2V_HD inline void j_keep_range(const uint8_t *es, uint64_t n, const uint64_t *e
         front = false;
     }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Damaged slices (option "decode_conceal" on top of all of "decode_interlaced", "decode_extended", "decode_mb_tools" and
+// "decode_field_pictures", "decode_b_pictures" either way, "decode_join" 0 .. 3; decoder.decode(..., conceal=True) is the
+// definition).  The functions above keep their text; these stand beside them:
+//   grammar     c_event: fp_event's rules, but a slice is legal behind a coding extension or a slice whatever the two codes are, and a
+//               picture may end behind a slice of any code or behind its coding extension (c_top).  No rule reads the rows
+//   bad slice   a slice whose code is above its picture's rows (c_bad_code) is not walked; its span says "not readable" with its code,
+//               which is no row's
+//   rows        c_row_kept: the spans of a picture that carry a row's code, in stream order - all readable, the first from column 0,
+//               each further one from the last column of the one in front + 1, the last to column mbw - 1.  Any other row is concealed
+//   record      c_record: every macroblock of a concealed row - a P picture's skipped macroblock (a field: field-based from its own
+//               parity), or intra without a block where no frame stands in front
+//   reference   c_place: fp_place, but an I picture is placed with a P picture's forward frame
+// ---------------------------------------------------------------------------------------------------------------------------
+M2V_HD inline bool c_top(const uint8_t *es, uint64_t n, const uint64_t *ev, int prev)
+{
+    if (prev < 0) return false;
+    const int role = main_role(es, n, ev[prev]);
+    return role == rSeqExt || role == rDisp || role == rSlice || role == rPicExt;
+}
+
+// event i by its own rule; prev: the significant event in front of it, -1: none
+M2V_HD inline EvInfo c_event(const uint8_t *es, uint64_t n, const uint64_t *ev, uint32_t nev, uint32_t i, const MainPlan &P, uint64_t last_nz, int prev, bool b_pictures)
+{
+    const int role = x_role(es, n, ev[i]);
+    if (role == rQuant) return x_event(es, n, ev, nev, i, P, last_nz, prev, b_pictures, true);      // (behind a coding extension, once, never the last unit)
+    EvInfo r{kNone, 0, 0, 0, 0};
+    const uint64_t pos = ev_pos(ev[i]), end = i + 1 < nev ? ev_pos(ev[i + 1]) : n;
+    const int prole = prev >= 0 ? main_role(es, n, ev[prev]) : rBad;
+    const int before = i ? main_role(es, n, ev[i - 1]) : rBad;      // the event right in front, transparent or not
+    const bool top = c_top(es, n, ev, prev);
+    bool ok = true;
+    switch (role) {
+    case rBad: ok = false; break;
+    case rSeq:
+        if (i) {
+            SeqHdr h;
+            uint32_t display;
+            bool same = true;
+            const uint64_t bad = main_group(es, n, ev, nev, i, h, display,
+                                            [&](int m, uint32_t k, uint32_t v) { same = same && (m ? P.seq.wn : P.seq.wi)[k & 63u] == v; });
+            if (bad != kNone) r.bad = bad;
+            else { ok = top && same && seq_equal(h, P.seq.h) && display == P.seq.display; r.rep = 1; }
+        }
+        break;
+    case rSeqExt: ok = before == rSeq; break;
+    case rDisp: { SeqHdr h; ok = prole == rSeqExt && parse_display_extension(es, pos, end, h); break; }
+    case rUser: ok = prole == rSeqExt || prole == rDisp || prole == rGop || prole == rPicExt; break;
+    case rSkipExt: ok = prole == rPicExt; break;
+    case rGop: { const bool good = parse_gop_header(es, pos, end); ok = top && good; r.gop = good; break; }
+    case rPic: {
+        const bool good = b_pictures ? bp_picture_header(es, pos, end, r.type) : parse_picture_header(es, pos, end, r.type);
+        ok = (top || prole == rGop) && good;
+        r.pic = good;
+        break;
+    }
+    case rPicExt: {
+        FPicParams q;
+        const uint64_t pp = i ? ev_pos(ev[i - 1]) : 0;
+        const uint32_t ptype = before == rPic && pp + 5 < n ? (es[pp + 5] >> 3) & 7u : 0u;
+        ok = before == rPic && fp_picture_extension(es, pos, end, ptype, b_pictures, P.seq.h.progressive, q);
+        break;
+    }
+    case rSlice: ok = prole == rPicExt || prole == rSlice; break;
+    default:                                                       // rEnd: the last code, zeros behind it
+        ok = top && i + 1 == nev && last_nz <= pos + 4;
+        break;
+    }
+    if (i + 1 == nev && role != rEnd && ok)                        // no sequence_end_code: the stream ends where a picture may end
+        ok = c_top(es, n, ev, main_significant(role) ? (int)i : prev);
+    if (!ok) r.bad = min64(r.bad, pos);
+    return r;
+}
+
+// fp_place, but an I picture gets the forward frame a P picture would get in its place
+M2V_HD inline FpPlace c_place(FpRange &s, uint32_t cp, uint32_t ps, uint32_t type, uint32_t tref)
+{
+    const int32_t a1 = s.a1;
+    const uint32_t openf = s.openf;
+    FpPlace q = fp_place(s, cp, ps, type, tref);
+    if (type == 1u) {
+        // a second I field: s.a1 is its own frame (its first field was an I field too), the frame in front s.a2
+        const int32_t f = q.second ? (s.a1 == (int32_t)openf ? s.a2 : s.a1) : a1;
+        q.fwd = q.bwd = (uint32_t)f;
+    }
+    return q;
+}
+
+M2V_HD inline bool c_bad_code(uint32_t code, uint32_t rows) { return code < 1u || code > rows; }
+
+// whether the row with slice code `code` is kept: spans[0 .. nslices) are the picture's, in stream order
+M2V_HD inline bool c_row_kept(const uint32_t *spans, uint32_t nslices, uint32_t code, uint32_t mbw)
+{
+    uint32_t next = 0;
+    bool seen = false, ok = true;
+    for (uint32_t k = 0; k < nslices; ++k) {
+        const uint32_t s = spans[k];
+        if (((s >> 16) & 255u) != code) continue;
+        seen = true;
+        ok = ok && (s >> 31) && ((s >> 8) & 255u) == next;
+        next = (s & 255u) + 1u;
+    }
+    return seen && ok && next == mbw;
+}
+
+// the record of every macroblock of a concealed row; grey: no frame stands in front
+M2V_HD inline IMb c_record(bool field, uint32_t par, bool grey)
+{
+    IMb m{};
+    if (grey) { m.intra = 1; m.motion_type = (uint8_t)kFrameBased; return m; }
+    m.skipped = 1; m.dirs = (uint8_t)kFwd;
+    m.motion_type = (uint8_t)(field ? kFieldBased : kFrameBased);
+    for (int k = 0; k < 4; ++k) m.sel[k] = (uint8_t)(field ? par : 0u);
+    return m;
+}
+
+// what a call concealed, as m2v_decode_conceal of include/m2v_mi355x.h carries it
+struct CReport { uint64_t first_offset; uint32_t bad_slices, concealed_rows, grey_rows, damaged_pictures; };
 
 }  // namespace dec
 }  // namespace m2v

@@ -20,6 +20,10 @@ struct DecState {
     int32_t status;
     uint32_t npics, gops, reps, chains, width, height, mbw, mbh, pad;
     unsigned long long frame_bytes;
+    // option "decode_conceal" (m2v_decode_c.hip), summed over the chunks: the first damaged picture's start code (dec::kNone: none), the
+    // slices that did not read, the rows concealed, those of them without a frame in front, the pictures with such a row
+    unsigned long long c_first;
+    uint32_t c_bad, c_rows, c_grey, c_pics;
 };
 struct DecPic { uint32_t ev, type, chain, step; };
 
@@ -82,8 +86,13 @@ struct DecFPic { uint32_t slice0, params, display, fwd, bwd, nslices, sbase, mi,
 
 void dec_f_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long long *ev, DecState *st, DecPic *pics, uint32_t pic_cap, uint8_t *h_types,
                 unsigned long long cap, int probe, m2v_decode_stat *h_rec, uint8_t *d_main, int b_pictures, uint32_t *h_mbh, uint32_t *h_sl);
+// h_conceal: nullptr, or (option "decode_conceal") where the report goes with the record - the walk and the verdict per row are then
+// dec_c_walk's, an I picture is a step behind the anchor frame in front of it, and the last kernel is dec_c_finish's
 void dec_f_chunks(m2v_enc *e, hipStream_t s, const uint8_t *es, size_t n, uint8_t *dst, int layout, const m2v_decode_stat &R, size_t mbh, size_t B,
-                  const uint8_t *types, size_t ncp, uint32_t *h_list, const uint32_t *h_sl, m2v_decode_stat *h_rec);
+                  const uint8_t *types, size_t ncp, uint32_t *h_list, const uint32_t *h_sl, m2v_decode_stat *h_rec, uint32_t *h_conceal = nullptr);
+// the first record of coded picture Q in a chunk that begins at frame f0: a frame's stretch is mbs records, a second field's half of it
+// lies behind its first field's
+__device__ inline size_t df_first(const DecFPic &Q, uint32_t f0, uint32_t mbs) { return (size_t)(Q.frame - f0) * mbs + (((Q.params >> 26) & 1u) ? mbs / 2u : 0u); }
 
 // Streams cut from a broadcast (option "decode_join" on top of "decode_field_pictures" and what it stands on; m2v_decode_j.hip): the
 // plan alone, in dec_f_plan's place, with its tables and for dec_f_chunks.  The pictures it drops are in no table, the kept pictures'
@@ -94,6 +103,19 @@ constexpr uint32_t kDecJoinWord = 2;               // h_mbh[kDecJoinWord .. kDec
 static_assert(kDecPlanWords + 4 * (kDecJoinWord + 6) <= 128, "the join record ends where the types begin");
 void dec_j_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long long *ev, DecState *st, DecPic *pics, uint32_t pic_cap, uint8_t *h_types,
                 unsigned long long cap, int probe, m2v_decode_stat *h_rec, uint8_t *d_main, int b_pictures, int join, uint32_t *h_mbh, uint32_t *h_sl);
+
+// Damaged slices (option "decode_conceal" on top of "decode_field_pictures" and what it stands on, "decode_join" 0 .. 3;
+// m2v_decode_c.hip).  The plan is k_dj_plan's text with the relaxed rules (dec_c_plan, k_dc_plan: a picture may have no slice,
+// so the picture tables hold a picture per two events); the chunks stay dec_f_chunks, which hands the walk of a chunk's slices and
+// the verdict per macroblock row to dec_c_walk - k_dc_slices refuses nothing, k_dc_rows writes the records of the concealed rows and
+// sums the report in DecState - and the end to dec_c_finish, which leaves the report (kDecConcealWords words: first_offset low, high,
+// bad_slices, concealed_rows, grey_rows, damaged_pictures) in pinned memory beside the record
+constexpr size_t kDecConcealWords = 6;
+void dec_c_plan(hipStream_t s, const uint8_t *es, size_t n, const unsigned long long *ev, DecState *st, DecPic *pics, uint32_t pic_cap, uint8_t *h_types,
+                unsigned long long cap, int probe, m2v_decode_stat *h_rec, uint8_t *d_main, int b_pictures, int join, uint32_t *h_mbh, uint32_t *h_sl);
+void dec_c_walk(hipStream_t s, const uint8_t *es, size_t n, const unsigned long long *ev, DecState *st, const DecPic *pics, const DecFPic *xp, uint32_t p0, uint32_t np,
+                uint32_t f0, uint32_t total, dec::IMb *mb, int32_t *dc, int16_t *lv, uint32_t *spans);
+void dec_c_finish(hipStream_t s, const DecState *st, m2v_decode_stat *h_rec, uint32_t *h_conceal);
 
 // The batch entries (m2v_decode_streams.hip, m2v_decode_streams_main.hip, m2v_decode_streams_ex.hip): the table of streams, a stream's
 // state on the device and its verdict in pinned memory are the same for all three, and so are the kernels that do not read the syntax.

@@ -33,12 +33,12 @@
 //   m2v_decode.hip    m2v_decode_device: an elementary stream in HBM back to 4:2:0 frames.  Its kernels touch no device global and nothing of
 //                     m2v_kernels.hpp, so they live in their own unit with their launches (m2v_decode_kernels.hpp holds the arithmetic, for
 //                     the device and the host alike)
-//   m2v_decode_main.hip, m2v_decode_b.hip, m2v_decode_i.hip, m2v_decode_x.hip, m2v_decode_t.hip, m2v_decode_f.hip, m2v_decode_j.hip   m2v_decode_device's other syntaxes:
+//   m2v_decode_main.hip, m2v_decode_b.hip, m2v_decode_i.hip, m2v_decode_x.hip, m2v_decode_t.hip, m2v_decode_f.hip, m2v_decode_j.hip, m2v_decode_c.hip   m2v_decode_device's other syntaxes:
 //                     the main syntax (option "decode_syntax"), B pictures on top of it (option "decode_b_pictures"), interlaced frame
 //                     pictures (option "decode_interlaced"), several slices a row, slice header extras and quant_matrix_extension (option
 //                     "decode_extended") with Table B-15, concealment motion vectors and dual prime (option "decode_mb_tools": a template
 //                     flag of m2v_decode_x.hip's slice walk; m2v_decode_t.hip holds its plan alone), field pictures, two a frame (option
-//                     "decode_field_pictures"), and the plan for streams cut from a broadcast (option "decode_join").  A unit holds what
+//                     "decode_field_pictures"), the plan for streams cut from a broadcast (option "decode_join"), and damaged slices concealed (option "decode_conceal").  A unit holds what
 //                     its option changes - the plan, the slice walk, where a record, its weights and its slots come from.  What the
 //                     units have in common exists once: m2v_decode_state.hpp (the call's state, the tables, every launcher),
 //                     m2v_decode_device.hpp (the dec::IMb sink, the reconstruction of a macroblock, the output loop, slot) and
@@ -436,6 +436,8 @@ struct m2v_enc {
     int decode_field_pictures = 0;        // option "decode_field_pictures": picture_structure 1 / 2, two fields a frame, on top of the three above it (m2v_decode_f.hip)
     int decode_join = 0;                  // option "decode_join": M2V_JOIN_HEAD | M2V_JOIN_TAIL on top of the four above it (m2v_decode_j.hip)
     m2v_decode_join dec_join{};           // the last call's join record (m2v_decode_join_report)
+    int decode_conceal = 0;               // option "decode_conceal": damaged slices dropped, their rows concealed, on top of the four above "decode_join" (m2v_decode_c.hip)
+    m2v_decode_conceal dec_conceal{};     // the last call's concealment report (m2v_decode_conceal_report)
     size_t decode_batch = 0;              // option "decode_batch": pictures per chunk (0: as many as keep the levels within 256 MiB, 256 at most)
     m2v_decode_stat dec_rec{};            // the last call's record (m2v_decode_report)
     // several streams per call (m2v_decode_streams.hip): the work buffers above serve it too; its own are the streams' table, the

@@ -6,7 +6,7 @@
 //          [-fps N/D] [-aspect 1:1|4:3|16:9|2.21:1] [-bitrate B] [-vbv K] [-colour bt601|bt709|P,T,M] [-repeat-headers]
 //          [-scale SWxSH [-filter triangle|area]]
 //          in.yuv W H out.m2v  [in2.yuv W2 H2 out2.m2v ...]
-//   m2v_tb -decode in.m2v out.yuv [-reconfmt i420|yv12|nv12|nv21] [-mode iso|module] [-syntax module|main [-bpictures] [-interlaced] [-extended [-mbtools [-fieldpictures [-join head|tail|both]]]]] [-container ts|ps [-pid N]] [-deint line|adaptive|blend [-fieldrate] [-bff]] [-d device]
+//   m2v_tb -decode in.m2v out.yuv [-reconfmt i420|yv12|nv12|nv21] [-mode iso|module] [-syntax module|main [-bpictures] [-interlaced] [-extended [-mbtools [-fieldpictures [-join head|tail|both] [-conceal]]]]] [-container ts|ps [-pid N]] [-deint line|adaptive|blend [-fieldrate] [-bff]] [-d device]
 //   m2v_tb -demux ts|ps in.ts out.m2v [-pid N] [-d device]
 //
 // -demux: the video elementary stream of a transport or program stream, demultiplexed on the device (m2v_demux_device), into out.m2v, with
@@ -22,6 +22,7 @@
 // -mbtools with -extended: option "decode_mb_tools" = 1, Table B-15, concealment motion vectors and dual prime.
 // -fieldpictures with -interlaced -extended -mbtools: option "decode_field_pictures" = 1, picture_structure 1 / 2 too, two field pictures a frame.
 // -join head|tail|both with -fieldpictures: option "decode_join" = 1 / 2 / 3, a stream cut from a broadcast; prints the join record.
+// -conceal with -fieldpictures: option "decode_conceal" = 1, damaged slices dropped and their rows patched; prints the report.
 // -interlaced with it: option "decode_interlaced" = 1, frame pictures with field prediction and field DCT too, one frame per picture.
 // -deint line|adaptive|blend: the decoded frames are deinterlaced on the device (m2v_deinterlace_device) before they are written, a frame
 // per frame or with -fieldrate a frame per field (not with blend), top field first or with -bff bottom field first.
@@ -154,7 +155,7 @@ static int demux_main(int argc, char **argv)
 static int decode_main(int argc, char **argv)
 {
     const char *in = argv[2], *out = argv[3];
-    int layout = M2V_420_I420, mode = M2V_DEC_ISO, dev = 0, container = 0, pid = -1, syntax = M2V_SYNTAX_MODULE, bpictures = 0, interlaced = 0, extended = 0, mbtools = 0, fieldpictures = 0, join = 0, deint = -1, fieldrate = 0, bff = 0;
+    int layout = M2V_420_I420, mode = M2V_DEC_ISO, dev = 0, container = 0, pid = -1, syntax = M2V_SYNTAX_MODULE, bpictures = 0, interlaced = 0, extended = 0, mbtools = 0, fieldpictures = 0, join = 0, conceal = 0, deint = -1, fieldrate = 0, bff = 0;
     bool bad = false;
     for (int i = 4; i < argc; ++i) {
         const char *v = i + 1 < argc ? argv[i + 1] : "";
@@ -179,6 +180,8 @@ static int decode_main(int argc, char **argv)
             mbtools = 1;
         } else if (!strcmp(argv[i], "-fieldpictures")) {
             fieldpictures = 1;
+        } else if (!strcmp(argv[i], "-conceal")) {
+            conceal = 1;
         } else if (!strcmp(argv[i], "-join")) {
             join = !strcmp(v, "head") ? M2V_JOIN_HEAD : !strcmp(v, "tail") ? M2V_JOIN_TAIL : !strcmp(v, "both") ? (M2V_JOIN_HEAD | M2V_JOIN_TAIL) : -1;
             bad = bad || join < 0;
@@ -206,7 +209,7 @@ static int decode_main(int argc, char **argv)
         }
     }
     if (bad || (pid >= 0 && !container) || ((fieldrate || bff) && deint < 0) || (fieldrate && deint == M2V_DEINT_BLEND)) {
-        fprintf(stderr, "m2v_tb -decode in.m2v out.yuv [-reconfmt i420|yv12|nv12|nv21] [-mode iso|module] [-syntax module|main [-bpictures] [-interlaced] [-extended [-mbtools [-fieldpictures [-join head|tail|both]]]]] [-container ts|ps [-pid N]] [-deint line|adaptive|blend [-fieldrate] [-bff]] [-d device]\n");
+        fprintf(stderr, "m2v_tb -decode in.m2v out.yuv [-reconfmt i420|yv12|nv12|nv21] [-mode iso|module] [-syntax module|main [-bpictures] [-interlaced] [-extended [-mbtools [-fieldpictures [-join head|tail|both] [-conceal]]]]] [-container ts|ps [-pid N]] [-deint line|adaptive|blend [-fieldrate] [-bff]] [-d device]\n");
         return 2;
     }
     std::vector<uint8_t> es;
@@ -233,7 +236,7 @@ static int decode_main(int argc, char **argv)
     } else if (m2v_set_option(e, "decode_syntax", syntax) != M2V_OK || m2v_set_option(e, "decode_b_pictures", bpictures) != M2V_OK ||
                m2v_set_option(e, "decode_interlaced", interlaced) != M2V_OK || m2v_set_option(e, "decode_extended", extended) != M2V_OK ||
                m2v_set_option(e, "decode_mb_tools", mbtools) != M2V_OK || m2v_set_option(e, "decode_field_pictures", fieldpictures) != M2V_OK ||
-               m2v_set_option(e, "decode_join", join) != M2V_OK) {
+               m2v_set_option(e, "decode_join", join) != M2V_OK || m2v_set_option(e, "decode_conceal", conceal) != M2V_OK) {
         fprintf(stderr, "m2v_set_option: %s\n", m2v_last_error(e));
     } else if (m2v_decode_device(e, d_es, es_bytes, nullptr, 0, layout, mode, nullptr) != M2V_OK || m2v_decode_report(e, &r) != M2V_OK) {
         fprintf(stderr, "m2v_decode_device: %s\n", m2v_last_error(e));
@@ -264,6 +267,10 @@ static int decode_main(int argc, char **argv)
             if (join && m2v_decode_join_report(e, &j) == M2V_OK)
                 printf("%s: joined at byte %llu, read up to byte %llu of %llu; %u frames dropped in front, %u behind\n", in, (unsigned long long)j.join_offset,
                        (unsigned long long)j.tail_offset, (unsigned long long)r.es_bytes, j.dropped_leading, j.dropped_trailing);
+            m2v_decode_conceal c;
+            if (conceal && m2v_decode_conceal_report(e, &c) == M2V_OK)
+                printf("%s: %u slices dropped, %u rows concealed (%u grey) in %u pictures, the first at byte %llu\n", in, c.bad_slices, c.concealed_rows, c.grey_rows,
+                       c.damaged_pictures, (unsigned long long)c.first_offset);
             rc = 0;
         }
         if (o) fclose(o);

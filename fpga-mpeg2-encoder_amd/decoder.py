@@ -301,7 +301,7 @@ def sequence_headers(data):
     return _sequence_headers(BitReader(data))
 
 
-def decode(data, quirks=True, syntax="module", b_pictures=False, interlaced=False, extended=False, mb_tools=False, field_pictures=False, join=0):
+def decode(data, quirks=True, syntax="module", b_pictures=False, interlaced=False, extended=False, mb_tools=False, field_pictures=False, join=0, conceal=False):
     """syntax="module" (the default): the subset this encoder emits, as the head of this file says.  syntax="main": Main-Profile
     streams of progressive frame pictures, I and P, 4:2:0, from any encoder (decode_main below); it needs quirks=False, and a
     refusal is a Refused exception that names the unit.  b_pictures=True (syntax="main" only): B pictures too, and the frames in
@@ -316,7 +316,11 @@ def decode(data, quirks=True, syntax="module", b_pictures=False, interlaced=Fals
     and mb_tools all True, b_pictures either way): pictures with picture_structure 1 / 2 too, two of them woven into one frame (the
     section "Field pictures" below); with False the function is what it was for every input.  join=1 .. 3 (JOIN_HEAD | JOIN_TAIL, with
     the four keywords in front of it all True, b_pictures either way): a stream cut from a running broadcast (the section "Streams
-    cut from a broadcast" below); with 0 the function is what it was for every input."""
+    cut from a broadcast" below); with 0 the function is what it was for every input.  conceal=True (with the same four keywords all
+    True, b_pictures either way, join 0 .. 3): damaged slices are dropped and their macroblock rows patched from the picture in front
+    (the section "Damaged slices" below); with False the function is what it was for every input."""
+    if conceal and not (syntax == "main" and interlaced and extended and mb_tools and field_pictures):
+        raise ValueError("conceal goes with syntax=\"main\", interlaced=True, extended=True, mb_tools=True and field_pictures=True")
     if join not in (0, 1, 2, 3):
         raise ValueError("join is 0 or a mask of JOIN_HEAD (1) and JOIN_TAIL (2)")
     if join and not (syntax == "main" and interlaced and extended and mb_tools and field_pictures):
@@ -334,8 +338,8 @@ def decode(data, quirks=True, syntax="module", b_pictures=False, interlaced=Fals
     if syntax == "main":
         assert not quirks, "the module's quirks have no meaning outside its own syntax"
         if join:
-            return decode_join(data, b_pictures, join)
-        return decode_main(data, b_pictures, interlaced, extended, mb_tools, field_pictures)
+            return decode_join(data, b_pictures, join, bool(conceal))
+        return decode_main(data, b_pictures, interlaced, extended, mb_tools, field_pictures, conceal=bool(conceal))
     assert syntax == "module", syntax
     T = tables()
     br = BitReader(data)
@@ -753,6 +757,34 @@ def psnr(a, b):
 # Decoded.join_offset = J (0 without bit 1), .tail_offset = T (len(data) where nothing was dropped behind), .dropped_leading and
 # .dropped_trailing count frames.  A stream in which no frame is left is a stream without pictures.  Every stream accepted with join=0
 # decodes to the same frames with join=1, and with join=2 or 3 where it ends with sequence_end_code.
+#
+# Damaged slices (decode(..., syntax="main", interlaced=True, extended=True, mb_tools=True, field_pictures=True, conceal=True), b_pictures
+# either way, join 0 .. 3; option "decode_conceal" of the device decoder).  A slice that cannot be read no longer refuses the stream: it
+# is dropped, the hole is patched from the frame in front, and the record is that of the undamaged stream.  These rules replace the ones
+# above; they stay local - a unit and the unit in front of it that is not skipped:
+#   grammar     a slice is legal behind a picture_coding_extension or behind a slice, whatever the two codes are.  A slice whose code is
+#               above the picture's rows (a field's rows for a field) is a bad slice: counted, not walked, not refused.  A sequence
+#               header, GOP header, picture header or sequence_end_code, and the end of the stream, are legal behind a slice of any code
+#               or behind a picture_coding_extension (a picture with no slice left).  Everything else is judged as with conceal=False -
+#               headers, extensions, the pairs, "P without an I frame", "B without two anchor frames", a second
+#               quant_matrix_extension, the join window - and refused at the same unit: damage to a header stays a refusal
+#   rows        the unit of concealment is the macroblock row of a coded picture (a field's row for a field).  A row is kept if and only
+#               if the slices of the picture that carry its code, in stream order, all read, the first starts at column 0, each further
+#               one starts one column behind the last column of the one in front, and the last ends at column mbw - 1.  Any other row is
+#               concealed whole: no slice, a slice that does not read (a bad slice too), a gap, an overlap, a duplicate.  The rule is
+#               blunt on purpose: where inside a slice an error is noticed is not pinned, only the verdict per slice is; and whatever a
+#               damaged slice wrote lies in its own row, which is overwritten
+#   patch       every macroblock of a concealed row of a frame picture is a P picture's skipped macroblock - forward, frame-based, the
+#               zero vector, no residual -, of a field picture forward, field-based from the field of its own parity, the zero vector.
+#               The reference is the frame the picture's forward reference names: for P the anchor frame in front, for B the earlier
+#               of its two, for I the anchor frame in front as if it were P; a second field takes its own parity from that frame too,
+#               never from its own.  No such frame (the first anchor frame of the stream or of the join window, both of its fields):
+#               Y = U = V = 128, a grey row.  A concealed picture is a reference like any other
+# Decoded.concealed lists (coded picture, row) of every concealed row (coded pictures as Decoded.fields counts them); Decoded.conceal is the
+# report: first_offset - the offset, from the first byte of the input, of the picture start code of the first coded picture with a
+# concealed row, len(data) where there is none -, bad_slices, concealed_rows, grey_rows, damaged_pictures (coded pictures).  Decoded.mbs
+# and .slice_qcodes hold what the walks left and say nothing of a concealed row.  Every stream accepted with conceal=False decodes to the
+# same frames with True, and a report of zeros.
 # ---------------------------------------------------------------------------------------------------------------
 JOIN_HEAD, JOIN_TAIL = 1, 2
 
@@ -957,9 +989,10 @@ def _main_mbh(hdr, interlaced=False):
     return (hdr["height"] + 15) // 16
 
 
-def _main_plan(data, b_pictures=False, interlaced=False, extended=False, mb_tools=False, field_pictures=False, dropped=None):
+def _main_plan(data, b_pictures=False, interlaced=False, extended=False, mb_tools=False, field_pictures=False, dropped=None, conceal=False):
     """the grammar over the start codes -> (sequence fields, pictures, gops, repeated headers, number of start codes).  dropped (a
-    list, with field_pictures): the leading B frames are dropped, not refused; their first pictures are appended to it"""
+    list, with field_pictures): the leading B frames are dropped, not refused; their first pictures are appended to it.  conceal: the
+    relaxed rules of the section "Damaged slices" - no order among the slice codes, a picture may end behind any slice or none"""
     n = len(data)
     ev = start_codes(data)
     if not ev or any(data[:ev[0][0]]):
@@ -1018,6 +1051,8 @@ def _main_plan(data, b_pictures=False, interlaced=False, extended=False, mb_tool
             top = prole in (_SEQEXT, _DISP) or (prole == _SLICE and ev[prev][1] == rows)
             if waiting is not None and role in (_SEQ, _GOP, _END):
                 bad.append(pos)                                 # between the two fields of a frame
+        if conceal:                                             # a picture ends behind a slice of any code, or with no slice left
+            top = prole in (_SEQEXT, _DISP, _SLICE, _PICEXT)
         ok = True
         try:
             if role == _BAD:
@@ -1116,6 +1151,8 @@ def _main_plan(data, b_pictures=False, interlaced=False, extended=False, mb_tool
                     ok = code <= mbh and ((code == 1 and prole == _PICEXT) or (prole == _SLICE and ev[prev][1] in (code, code - 1)))
                 if field_pictures:
                     ok = ok and code <= rows
+                if conceal:                                     # behind the coding extension or a slice, whatever the two codes are
+                    ok = prole in (_PICEXT, _SLICE)
                 if ok and pictures:
                     pictures[-1]["slices"].append(i)
             else:                                               # sequence_end_code: the last one, only zeros behind it
@@ -1129,6 +1166,8 @@ def _main_plan(data, b_pictures=False, interlaced=False, extended=False, mb_tool
             ok = prole in (_SEQEXT, _DISP) or (prole == _SLICE and ev[prev][1] == mbh)
             if field_pictures:
                 ok = prole in (_SEQEXT, _DISP) or (prole == _SLICE and ev[prev][1] == rows)
+            if conceal:
+                ok = prole in (_SEQEXT, _DISP, _SLICE, _PICEXT) and role != _QUANT
         if not ok:
             bad.append(pos)
     if waiting is not None:
@@ -1227,25 +1266,30 @@ def join_window(data, join, b_pictures=False):
     return J, ev[t][0], 1
 
 
-def decode_join(data, b_pictures=False, join=JOIN_HEAD | JOIN_TAIL):
+def decode_join(data, b_pictures=False, join=JOIN_HEAD | JOIN_TAIL, conceal=False):
     """decode(..., join=): the bytes [J, T) as a stream of their own, its leading B frames dropped with JOIN_HEAD; offsets count from
     the first byte of data"""
     data = bytes(data)
     J, T, trailing = join_window(data, join, b_pictures)
     dropped = [] if join & JOIN_HEAD else None
     try:
-        out = decode_main(data[J:T], b_pictures, True, True, True, True, dropped)
+        out = decode_main(data[J:T], b_pictures, True, True, True, True, dropped, conceal)
     except Refused as r:
         raise Refused(r.offset + J, "in the window [%d, %d): %s" % (J, T, r))
+    if conceal:                                                 # offsets count from the first byte of the input
+        out.conceal["first_offset"] = out.conceal["first_offset"] + J if out.concealed else len(data)
     out.join_offset, out.tail_offset, out.dropped_leading, out.dropped_trailing = J, T, len(dropped or ()), trailing
     return out
 
 
-def decode_main(data, b_pictures=False, interlaced=False, extended=False, mb_tools=False, field_pictures=False, dropped=None):
+def decode_main(data, b_pictures=False, interlaced=False, extended=False, mb_tools=False, field_pictures=False, dropped=None, conceal=False):
     data = bytes(data)
     T, TM = tables(), _main_tables()
-    hdr, pictures, gops, repeats, ev, ends = _main_plan(data, b_pictures, interlaced, extended, mb_tools, field_pictures, dropped)
+    hdr, pictures, gops, repeats, ev, ends = _main_plan(data, b_pictures, interlaced, extended, mb_tools, field_pictures, dropped, conceal)
     out = Decoded()
+    if conceal:                                                 # (coded picture, row) of every concealed row; the report
+        out.concealed = []
+        out.conceal = dict(first_offset=len(data), bad_slices=0, concealed_rows=0, grey_rows=0, damaged_pictures=0)
     out.width, out.height, out.sequence, out.gops, out.repeated_headers, out.units = hdr["width"], hdr["height"], hdr, gops, repeats, len(ev)
     mbw, mbh = (out.width + 15) // 16, _main_mbh(hdr, interlaced)
     W, H = 16 * mbw, 16 * mbh
@@ -1688,6 +1732,11 @@ def decode_main(data, b_pictures=False, interlaced=False, extended=False, mb_too
             full, a further one where the slice in front ended; the picture's last slice ends the row"""
             code = ev[unit][1]
             assert span, "a slice without a macroblock"
+            if conceal:                                         # per row: the first slice at column 0, a further one where the one in front ended
+                st = rowstate.setdefault(code, [True, 0])
+                st[0] = st[0] and span[0] == st[1]
+                st[1] = span[1] + 1
+                return
             if front and front[0] == code:
                 assert span[0] == front[1] + 1, "a gap or an overlap between two slices of a row"
             else:
@@ -1695,8 +1744,12 @@ def decode_main(data, b_pictures=False, interlaced=False, extended=False, mb_too
             assert unit != pic["slices"][-1] or span[1] == mbw - 1, "the picture's last slice ends short"
             front[:] = [code, span[1]]
 
+        rowstate = {}                                           # conceal: slice code -> [every slice so far read and joined, the next column]
         for row, unit in enumerate(pic["slices"]):
             pos = ev[unit][0]
+            if conceal and ev[unit][1] > (mbh // 2 if fld else mbh):
+                out.conceal["bad_slices"] += 1                  # a code above the picture's rows: counted, not walked
+                continue
             if extended:                                        # the slice's code names its row
                 row = ev[unit][1] - 1
                 del span[:]
@@ -1839,7 +1892,29 @@ def decode_main(data, b_pictures=False, interlaced=False, extended=False, mb_too
             except Refused:
                 raise
             except Exception as e:
+                if conceal:                                     # a slice that does not read: its whole row goes
+                    out.conceal["bad_slices"] += 1
+                    rowstate.setdefault(ev[unit][1], [True, 0])[0] = False
+                    continue
                 raise Refused(pos, "slice: %s" % e)
+        if conceal:
+            rows_, par_ = (mbh // 2, pic["picture_structure"] - 1) if fld else (mbh, 0)
+            src = before if pic["type"] == 3 else ref           # the frame the forward reference names; an I picture's as if it were P
+            hidden = [r for r in range(rows_) if not (rowstate.get(r + 1, [False, 0])[0] and rowstate[r + 1][1] == mbw)]
+            for r in hidden:
+                for k, (plane, n) in enumerate(((Y, 16), (U, 8), (V, 8))):
+                    dst = plane[par_::2] if fld else plane
+                    if src is None:
+                        dst[n * r:n * r + n] = 128              # a grey row: no frame in front
+                    else:
+                        dst[n * r:n * r + n] = (src[k][par_::2] if fld else src[k])[n * r:n * r + n]
+                out.concealed.append((len(out.fields) - 1, r))
+            if hidden:
+                c = out.conceal
+                c["first_offset"] = min(c["first_offset"], ev[pic["unit"]][0])
+                c["concealed_rows"] += len(hidden)
+                c["grey_rows"] += len(hidden) if src is None else 0
+                c["damaged_pictures"] += 1
         if field_pictures:                                      # a frame is done behind a frame picture or a second field; its type is its first picture's
             out.mbs.append(mbs)
             out.slice_qcodes.append(qcodes)

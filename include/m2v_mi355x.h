@@ -1177,6 +1177,42 @@ int m2v_mux_scan_tile(void);
  * the next segment.  m2v_decode_stat is what it was, `reserved` 0.
  * Out of scope: the batch entries; resynchronising behind damage in the middle of a stream; a sequence header that changes
  * mid-stream; D pictures; repeat_first_field and display timing; the module syntax.
+ *
+ * Option "decode_conceal" (m2v_set_option), per handle: 0 (the default) or 1; any other value is M2V_E_PARAM.  0 - everything above,
+ * bit for bit, launch for launch and refusal for refusal.  1 - a damaged slice no longer refuses the stream: the slice is dropped, the
+ * hole is patched from the frame in front, and the call answers M2V_DEC_OK with the record of the undamaged stream.  It has the
+ * requirements of "decode_join": "decode_syntax" M2V_SYNTAX_MAIN, `mode` M2V_DEC_ISO and "decode_interlaced", "decode_extended",
+ * "decode_mb_tools" and "decode_field_pictures" all 1; otherwise m2v_decode_device returns M2V_E_PARAM, writes nothing and
+ * m2v_last_error names the option.  "decode_b_pictures" may be 0 or 1, "decode_join" 0 .. 3.  The batch entries neither read nor
+ * change the option.  The definition is decoder.decode(stream, ..., field_pictures=True, join=..., conceal=True).  Every stream accepted
+ * with the option off decodes with it on to the same bytes and the same record, and a report of zeros.
+ *   grammar    a slice is legal behind a picture coding extension or behind a slice, whatever the two codes are.  A slice whose code
+ *             is above the picture's macroblock rows (a field's rows for a field) is a BAD SLICE: counted, not walked, not refused.  A
+ *             sequence header, GOP header, picture header or sequence_end_code, and the end of the stream, are legal behind a slice of
+ *             any code or behind a picture coding extension (a picture with no slice left).  Everything else is judged as with the
+ *             option off - headers, extensions, the pairing of fields, "P without an I frame", "B without two anchor frames", a second
+ *             quant_matrix_extension, the join window -, and a stream refused there is M2V_DEC_SYNTAX at the same offset: damage to
+ *             a header stays a refusal
+ *   rows       the unit of concealment is the macroblock row of a coded picture (a field's row for a field).  A row is KEPT if and
+ *             only if the slices of its picture that carry its code, in stream order, all read, the first starts at column 0, each
+ *             further one starts one column behind the last column of the one in front, and the last ends at column mbw - 1.  Any
+ *             other row is CONCEALED whole: one with no slice, with a slice that does not read (a bad slice too), with a gap, an
+ *             overlap or a duplicate.  The rule is blunt on purpose: where inside a slice an error is noticed is not pinned, only the
+ *             verdict per slice is; and whatever a damaged slice's walk left in its row - it writes nowhere else - is overwritten
+ *   patch      every macroblock of a concealed row of a frame picture is a P picture's skipped macroblock: forward, frame-based,
+ *             vector (0, 0), no residual; of a field picture: forward, field-based from the field of its own parity, vector (0, 0).  The
+ *             reference is the frame the picture's forward reference names: for P the anchor frame in front, for B the earlier of its
+ *             two, for an I picture the anchor frame in front as if it were P; a second field takes its own parity from that frame
+ *             too, never from its own.  Where there is no such frame (the first anchor frame of the stream or of the join window,
+ *             both of its fields) the macroblock is intra without a block: Y = U = V = 128, a GREY ROW.  A concealed picture is a
+ *             reference like any other
+ * m2v_decode_conceal_report describes the same call as m2v_decode_report: first_offset is the offset, from the first byte of the
+ * input, of the picture start code of the first coded picture in coded order with a concealed row (es_bytes where there is none);
+ * bad_slices, concealed_rows, grey_rows count what their names say, damaged_pictures coded pictures with a concealed row.  The counts
+ * are summed on the device and come with the record: no further wait.  They do not depend on "decode_batch".  All zero (first_offset
+ * es_bytes) for a call with the option off and for a call that did not answer M2V_DEC_OK.
+ * Out of scope: damage to any header; keeping the macroblocks in front of an error; motion-compensated or spatial concealment;
+ * transport_error_indicator and continuity faults from the demultiplexer; the batch entries; D pictures; repeat_first_field.
  */
 enum { M2V_DEC_ISO = 0, M2V_DEC_MODULE = 1 };
 enum { M2V_SYNTAX_MODULE = 0, M2V_SYNTAX_MAIN = 1 };                            /* option "decode_syntax" */
@@ -1189,6 +1225,8 @@ int m2v_decode_report(m2v_enc *e, m2v_decode_stat *out);
 enum { M2V_JOIN_HEAD = 1, M2V_JOIN_TAIL = 2 };                                  /* option "decode_join" */
 typedef struct { uint64_t join_offset, tail_offset; uint32_t dropped_leading, dropped_trailing, reserved[2]; } m2v_decode_join;   /* 32 bytes */
 int m2v_decode_join_report(m2v_enc *e, m2v_decode_join *out);
+typedef struct { uint64_t first_offset; uint32_t bad_slices, concealed_rows, grey_rows, damaged_pictures, reserved[2]; } m2v_decode_conceal;   /* 32 bytes */
+int m2v_decode_conceal_report(m2v_enc *e, m2v_decode_conceal *out);
 int m2v_decode_scan_tile(void);
 
 /*
